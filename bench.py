@@ -29,6 +29,12 @@ Launch:  python bench.py --gpus N [--steps K --warmup W]     N > 1 without a lau
                                                                before this process touches a GPU
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the configuration).  `--full`
+adds what takes runs of its own: per-kernel times and rooflines, the sustained leg, the CPU oracle's baseline and parity sample,
+the replayed-vs-launched comparison, C5's haploid job, and the default workload's c4_whole / general_blocks_c5 (N = 1) or
+strong_c4 (N > 1) legs.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (seeded inputs: two
+builds run with the same arguments can be compared output for output).
 """
 import argparse
 import json
@@ -102,7 +108,17 @@ def parse_args(argv=None):
     ap.add_argument("--launch-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)   # tests of the self-launch: this rank exits 3 at once, the others would wait a minute
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N ranks share GPU 0 and reduce over gloo: exercises the multi-rank code path on a 1-GPU box (numbers meaningless)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-kernel times and rooflines, the sustained leg, the CPU oracle's baseline and parity "
+                         "sample, the replayed-vs-launched comparison, C5's haploid job, and the default workload's c4_whole and general_blocks_c5 "
+                         "legs (N = 1) or strong_c4 leg (N > 1).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (block cuts, coverages, GT, GQ, status and overflow flags of "
+                         "every record) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: larger outputs are cut to a fixed, seeded "
+                         "sample of their elements; N > 1: one set per rank, <name>_rank<r>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "c4":
         args.strong = True
     d = {"c3": (1e8, 1e6, 4, 43), "c4": (3e9, 8e7, 16, 43), "c5": (1e8, None, 8, 63)}[args.workload]
@@ -459,7 +475,7 @@ class Job:
         self.barrier()
         elapsed = time.perf_counter() - t_start
         self.stream_ms = None
-        if run != self.step:        # the same K steps launched one by one: for the record, and as the check that a replayed step leaves what a launched one does
+        if run != self.step and self.args.full:     # the same K steps launched one by one: for the record, and as the check that a replayed step leaves what a launched one does
             def state():
                 r = self.rp.results()
                 return [r[k].copy() for k in ("cov", "g1", "g2", "gq", "overflow")]
@@ -773,10 +789,52 @@ def traffic_of(job):
 
 
 def record(job, elapsed, steps, warmup, kt, sustained):
-    """the JSON fields of one measured job (rank 0)"""
+    """the JSON fields of one measured job (rank 0); kt = None (no kernel timing run): the line without rooflines and kernel times"""
     args, ctx, K, R, world = job.args, job.ctx, job.K, job.R, job.world
     total_kmers = job.total_rows * steps
     total_vars = job.n_vars_total * steps
+    wl = {"c3": "C3", "c4": "C4 (whole genome, clustered panel as SURVEY 8(d) draws it)", "c5": "C5 (indel / MNP clusters, %s)" % ("haploid" if job.haploid else "diploid")}[job.workload]
+    if job.workload == "c3" and (job.n_vars_total, job.b, K, R) != (1000000, 4, 35, 43):
+        wl = "custom (C3 shape)"
+    out = {
+        "metric": "KMC k-mers scanned/sec (whole call step: scan + counter all-reduce + record loop: cut, signatures, coverage, likelihoods), k=%d r=%d" % (K, R),
+        "value": total_kmers / elapsed,
+        "unit": "kmers/s",
+        "variants_per_s": total_vars / elapsed,
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": warmup,
+        "ms_per_step": 1e3 * elapsed / steps,
+        "launch": getattr(job, "launch", "stream"),                      # how the timed steps were issued: kernel by kernel, or one captured step replayed
+        "ms_per_step_stream": getattr(job, "stream_ms", None),           # (graph replay, --full) the same steps launched kernel by kernel
+        "replay_equals_launched": getattr(job, "replay_equals_launched", None),   # ... and whether both left the same coverages, GT, GQ
+        "higher_is_better": True,
+        "scaling": "strong" if job.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {"workload": "%s: %.3g KMC k-mers per GPU (table of %.3g rows %s) against a panel of %.3g records, k=%d r=%d b=%d, table and panel resident in HBM" % (
+                       wl, job.n_rows, job.total_rows, "cut over the ranks" if job.strong else "= rows per GPU x N", job.n_vars_total, K, R, job.b),
+                   "kmers_per_gpu": job.n_rows, "kmers_total": job.total_rows, "panel_variants": job.n_vars_total, "variants_genotyped_per_gpu": job.n_vars,
+                   "k": K, "ref_k": R, "bf_bits": job.bf_bits, "haploid": job.haploid,
+                   "table_layout": "12-byte rows (count << 2r | r-mer), packed outside the step" if job.compact else "SoA hi[] lo[] cnt[] (20 B/row)",
+                   "parallelism": "table rows x%d (%s), record loop split x%d at block boundaries, index replicated" % (world, "strong" if job.strong else "weak", world),
+                   "summary_bitmaps": not args.no_summary,
+                   "exchange": ("none" if world == 1 else "%s over %d counters%s" % (
+                       job.exchange, job.n_bf + job.n_map, ", 16-bit packed when exact (%d of %d steps)" % (sum(job.packed_steps), len(job.packed_steps)) if job.packed_steps else "")),
+                   "comm_ranks": (ctx.comm_info()[1] if job.native else (world if world > 1 else 0))},
+    }
+    tail = {
+        "pack_rows_ms": job.pack_ms,
+        # the same step with the SoA -> 12-byte-row conversion counted in (no pipeline stage produces compact rows today: see DESIGN.md)
+        "ms_per_step_incl_pack": (1e3 * elapsed / steps + job.pack_ms) if job.pack_ms is not None else None,
+        "value_incl_pack": (job.total_rows / (elapsed / steps + job.pack_ms * 1e-3)) if job.pack_ms is not None else None,
+        "index_build_s": job.index_s,
+        "sustained": sustained,
+    }
+    if kt is None:
+        out.update(tail)
+        return out
     rows_per_launch = min(job.n_rows, 1 << 27)      # the scan walks the table in launch groups of 2^27 rows; mg_scan_stats times every one of them and
                                                     # gives the durations per group of this many rows, averaged over all groups (= rocprofv3's per-kernel averages)
     n_groups = (job.n_rows + (1 << 27) - 1) >> 27
@@ -819,46 +877,8 @@ def record(job, elapsed, steps, warmup, kt, sustained):
     roof_filter = {"kernel": fname, "bound": "hbm", "achieved": ach_filter, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_filter / HBM_PEAK_GBS,
                    "traffic": traffic, "traffic_source": tsrc, "algorithmic_bytes_per_launch": SCAN_BYTES_PER_KMER * rows_per_launch,
                    "bytes_per_unit": SCAN_BYTES_PER_KMER, "units_per_launch": rows_per_launch, "avg_launch_ms": filt}
-    wl = {"c3": "C3", "c4": "C4 (whole genome, clustered panel as SURVEY 8(d) draws it)", "c5": "C5 (indel / MNP clusters, %s)" % ("haploid" if job.haploid else "diploid")}[job.workload]
-    if job.workload == "c3" and (job.n_vars_total, job.b, K, R) != (1000000, 4, 35, 43):
-        wl = "custom (C3 shape)"
-    out = {
-        "metric": "KMC k-mers scanned/sec (whole call step: scan + counter all-reduce + record loop: cut, signatures, coverage, likelihoods), k=%d r=%d" % (K, R),
-        "value": total_kmers / elapsed,
-        "unit": "kmers/s",
-        "variants_per_s": total_vars / elapsed,
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": warmup,
-        "ms_per_step": 1e3 * elapsed / steps,
-        "launch": getattr(job, "launch", "stream"),                      # how the timed steps were issued: kernel by kernel, or one captured step replayed
-        "ms_per_step_stream": getattr(job, "stream_ms", None),           # (graph replay only) the same steps launched kernel by kernel
-        "replay_equals_launched": getattr(job, "replay_equals_launched", None),   # ... and whether both left the same coverages, GT, GQ
-        "higher_is_better": True,
-        "scaling": "strong" if job.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic",
-        "config": {"workload": "%s: %.3g KMC k-mers per GPU (table of %.3g rows %s) against a panel of %.3g records, k=%d r=%d b=%d, table and panel resident in HBM" % (
-                       wl, job.n_rows, job.total_rows, "cut over the ranks" if job.strong else "= rows per GPU x N", job.n_vars_total, K, R, job.b),
-                   "kmers_per_gpu": job.n_rows, "kmers_total": job.total_rows, "panel_variants": job.n_vars_total, "variants_genotyped_per_gpu": job.n_vars,
-                   "k": K, "ref_k": R, "bf_bits": job.bf_bits, "haploid": job.haploid,
-                   "table_layout": "12-byte rows (count << 2r | r-mer), packed outside the step" if job.compact else "SoA hi[] lo[] cnt[] (20 B/row)",
-                   "parallelism": "table rows x%d (%s), record loop split x%d at block boundaries, index replicated" % (world, "strong" if job.strong else "weak", world),
-                   "summary_bitmaps": not args.no_summary,
-                   "exchange": ("none" if world == 1 else "%s over %d counters%s" % (
-                       job.exchange, job.n_bf + job.n_map, ", 16-bit packed when exact (%d of %d steps)" % (sum(job.packed_steps), len(job.packed_steps)) if job.packed_steps else "")),
-                   "comm_ranks": (ctx.comm_info()[1] if job.native else (world if world > 1 else 0))},
-        "roofline": roof_scan,
-        "roofline_filter": roof_filter,
-        "kernels_ms": kt,
-        "pack_rows_ms": job.pack_ms,
-        # the same step with the SoA -> 12-byte-row conversion counted in (no pipeline stage produces compact rows today: see DESIGN.md)
-        "ms_per_step_incl_pack": (1e3 * elapsed / steps + job.pack_ms) if job.pack_ms is not None else None,
-        "value_incl_pack": (job.total_rows / (elapsed / steps + job.pack_ms * 1e-3)) if job.pack_ms is not None else None,
-        "index_build_s": job.index_s,
-        "sustained": sustained,
-    }
+    out.update(roofline=roof_scan, roofline_filter=roof_filter, kernels_ms=kt)
+    out.update(tail)
     if job.flat:
         n_sig = kt["lone_signature_kmers"] + kt["general_signature_kmers"]
         alg = blocks_bytes(job.n_vars, n_sig, job.n_genotypes)
@@ -884,6 +904,39 @@ def record(job, elapsed, steps, warmup, kt, sustained):
         out["genotype_roofline"] = {"achieved": GENO_BYTES_PER_SNP * job.n_vars / (kt["record_loop"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                     "frac": GENO_BYTES_PER_SNP * job.n_vars / (kt["record_loop"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "bytes_per_unit": GENO_BYTES_PER_SNP}
     return out
+
+
+OUTPUT_BUDGET = 64 << 20     # bytes of --dump-outputs in all (over every rank's files)
+OUTPUT_SEED = 20261016
+
+
+def write_outputs(out_dir, arrays, budget=OUTPUT_BUDGET, suffix=""):
+    """arrays: name -> (1-D array, np.float32 or np.float64).  Each is written as out_dir/<name><suffix>.npy in that type.  When the
+    whole would exceed `budget` bytes, every array is cut to the same fraction of its elements: a sample drawn with a fixed seed
+    (per name), kept in index order -- so two runs with the same arguments write the same elements."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    room = budget - 256 * len(arrays)                  # (the .npy headers)
+    total = sum(a.size * np.dtype(t).itemsize for a, t in arrays.values())
+    frac = min(1.0, room / total) if total else 1.0
+    for name, (a, t) in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if frac < 1.0:
+            m = int(a.size * frac)
+            idx = np.random.default_rng(OUTPUT_SEED + zlib.crc32(name.encode())).choice(a.size, m, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.astype(t))
+
+
+def dump_outputs(job, out_dir):
+    """what the timed path's last step left for its caller, on this rank: the records' block cuts, coverage of every allele slot, GT,
+    GQ, genotype status and overflow flags (the normalised likelihoods are not computed by the step: `malva-geno call` without -v)"""
+    r = job.rp.results()
+    f32, f64 = np.float32, np.float64        # (32-bit counts and offsets in float64: exact beyond 2^24)
+    arrays = {"block_var_off": (r["blk_var_off"], f64), "coverage": (r["cov"], f64), "gt1": (r["g1"], f32), "gt2": (r["g2"], f32),
+              "gq": (r["gq"], f32), "status": (r["status"], f32), "overflow": (r["overflow"], f32)}
+    write_outputs(out_dir, arrays, OUTPUT_BUDGET // job.world, "_rank%d" % job.rank if job.world > 1 else "")
+    log(job.rank, "outputs of the last timed step written to %s" % out_dir)
 
 
 def main():
@@ -933,10 +986,14 @@ def main():
     work_stream = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(work_stream)
 
-    def measure(job, cpu):
+    def measure(job, cpu, dump=False):
         elapsed = job.timed(args.steps, args.warmup)
-        kt = job.kernel_times(max(3, min(args.steps, 10)))
-        sus = job.sustained(args.sustained_s)
+        if dump:
+            dump_outputs(job, args.dump_outputs)
+        kt = sus = None
+        if args.full:
+            kt = job.kernel_times(max(3, min(args.steps, 10)))
+            sus = job.sustained(args.sustained_s)
         g1, g2, gq, n_ovf = job.results()
         out = None
         if rank == 0:
@@ -949,21 +1006,21 @@ def main():
             if n_ovf:
                 raise SystemExit("bench: %d records exceeded a device capacity at call time: not a measurement of the device path" % n_ovf)
             out["cpu_baseline"], out["parity_sample"] = (None, None)
-            if cpu and world == 1 and args.cpu_sample > 0:
+            if cpu and args.full and world == 1 and args.cpu_sample > 0:
                 out["cpu_baseline"], out["parity_sample"] = cpu_leg(job, rank)
         return out
 
     job = Job(args.workload, args, rank, world, local, torch, dist, haploid=False)
-    out = measure(job, cpu=True)
+    out = measure(job, cpu=True, dump=args.dump_outputs is not None)
     job.close()
-    if args.workload == "c5":      # config C5 names both modes: the haploid index and step, same panel arrays
+    if args.full and args.workload == "c5":      # config C5 names both modes: the haploid index and step, same panel arrays
         hj = Job("c5", args, rank, world, local, torch, dist, haploid=True)
         hout = measure(hj, cpu=True)
         hj.close()
         if rank == 0:
             out["haploid"] = {k_: hout[k_] for k_ in ("value", "variants_per_s", "ms_per_step", "kernels_ms", "roofline", "roofline_blocks", "sustained",
                                                       "calls", "cpu_baseline", "parity_sample", "index_build_s")}
-    if world == 1 and args.workload == "c3" and not args.no_c5_leg and not args.scan_ablate:
+    if args.full and world == 1 and args.workload == "c3" and not args.no_c5_leg and not args.scan_ablate:
         # BASELINE config C5's shape at a fifth of its bench size, so that the default line carries the general-block path too
         # (`--workload c5` is the full measurement): diploid and haploid, parity of everything against the oracle
         leg = {}
@@ -980,7 +1037,7 @@ def main():
                 "overflow_records": n_ovf, "parity_sample": par, "cpu_variants_per_s": cpu and cpu["variants_per_s"], "config": rec["config"]["workload"]}
             lj.close()
         out["general_blocks_c5"] = leg
-    if world == 1 and args.workload == "c3" and not args.no_c4_leg and not args.scan_ablate:
+    if args.full and world == 1 and args.workload == "c3" and not args.no_c4_leg and not args.scan_ablate:
         # BASELINE config C4 (whole genome: 3e9 k-mers against the 8e7-record index, b=16) on this one GPU -- the per-GPU rate of
         # the 8-GPU configuration too, whose index is replicated: step, kernel times, roofline of the scan and of the record
         # loop, and parity of three slices of the panel at the full index
@@ -997,7 +1054,7 @@ def main():
         out["c4_whole"]["parity_slices"] = c4_slice_parity(cj, rank) if args.cpu_sample > 0 else None
         cj.close()
     # (under --rehearse-on-one-gpu the leg runs only at explicitly reduced sizes: N whole-genome indexes do not share one GPU)
-    if world > 1 and args.workload == "c3" and not args.no_strong_c4 and (not args.rehearse_on_one_gpu or args.strong_c4_kmers < 1e9):
+    if args.full and world > 1 and args.workload == "c3" and not args.no_strong_c4 and (not args.rehearse_on_one_gpu or args.strong_c4_kmers < 1e9):
         # north_star's whole-genome claim on the same ranks: the 3e9-row table cut N ways against the 8e7-SNP index
         def all_ok(ok):
             """every rank abandons the leg together: a failure on one rank only (an out-of-memory, say) must not leave its peers inside a collective"""

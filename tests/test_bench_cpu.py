@@ -51,3 +51,38 @@ def test_self_launch_ends_all_ranks_when_one_fails():
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--launch-fail-rank", "1"], capture_output=True, text=True, timeout=50, env=env)
     assert r.returncode == 3 and time.time() - t0 < 30
+
+
+def test_full_and_dump_options():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_write_outputs_types_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs' writer: each array in the float type it is given; beyond the budget the same fraction of every array, a
+    sample fixed by its seed and kept in index order, so two runs write the same elements"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.arange(1_000_000, dtype=np.uint32) * np.uint32(4001)
+    small = (np.arange(300_000) % 7).astype(np.int32)
+    arrays = {"cov": (big, np.float64), "gt": (small, np.float32)}
+    bench.write_outputs(str(tmp_path / "whole"), arrays)
+    assert np.array_equal(np.load(tmp_path / "whole" / "cov.npy"), big.astype(np.float64))
+    assert np.load(tmp_path / "whole" / "gt.npy").dtype == np.float32
+    budget = 2 << 20
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), arrays, budget=budget)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= budget
+    a, b = np.load(tmp_path / "a" / "cov.npy"), np.load(tmp_path / "b" / "cov.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, b) and 100_000 < a.size < big.size
+    idx = (a / 4001).astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(big[idx].astype(np.float64), a)
+    g = np.load(tmp_path / "a" / "gt.npy")
+    assert g.dtype == np.float32 and abs(g.size / small.size - a.size / big.size) < 1e-4

@@ -276,7 +276,7 @@ def test_bench_one_gpu_line_replays_a_captured_step():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     common = [sys.executable, os.path.join(root, "bench.py"), "--kmers", "4e6", "--variants", "5e4", "--steps", "3", "--warmup", "2", "--no-c4-leg", "--no-c5-leg",
-              "--sustained-s", "0", "--cpu-sample", "2e5", "--cpu-variants", "2e4"]
+              "--sustained-s", "0", "--cpu-sample", "2e5", "--cpu-variants", "2e4", "--full"]
     for extra, launch in (([], "hipGraph"), (["--no-graph"], "stream")):
         r = subprocess.run(common + extra, capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -288,3 +288,37 @@ def test_bench_one_gpu_line_replays_a_captured_step():
         assert all(v is True for k, v in d["parity_sample"].items() if k.endswith("_equal")), d["parity_sample"]
         if launch == "hipGraph":
             assert d["replay_equals_launched"] is True and d["ms_per_step_stream"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py` without --full at a reduced C3: ONE JSON line with the headline and none of the --full figures, and
+    --dump-outputs writes the last timed step's per-record results as float .npy files -- the same ones on a second run with the
+    same arguments, and the same calls as the line counts"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--kmers", "4e6", "--variants", "5e4", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.split("\n") if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["value"] > 0 and d["ms_per_step"] > 0 and d["overflow_records"] == 0
+        assert abs(d["value"] - d["config"]["kmers_total"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert all(k_ in d for k_ in ("metric", "unit", "higher_is_better", "dtype"))
+        assert not any(k_ in d for k_ in ("kernels_ms", "roofline", "general_blocks_c5", "c4_whole")) and d["cpu_baseline"] is None and d["sustained"] is None
+        files = sorted(os.listdir(out))
+        assert files == sorted(n + ".npy" for n in ("block_var_off", "coverage", "gt1", "gt2", "gq", "status", "overflow")), files
+        arrs = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        assert arrs["gt1"].size == 50000 and arrs["coverage"].size == 100000 and not arrs["overflow"].any()
+        g1, g2 = arrs["gt1"], arrs["gt2"]
+        assert d["calls"] == {"0/0": int(np.sum((g1 == 0) & (g2 == 0))), "het": int(np.sum(g1 != g2)), "hom-alt": int(np.sum((g1 == g2) & (g1 > 0)))}
+        got.append(arrs)
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in got[0])

@@ -309,7 +309,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu(workload, extra):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--workload", workload, "--steps", "2",
-                        "--warmup", "1", "--cpu-sample", "0", "--sustained-s", "0.2"] + extra, capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "1", "--cpu-sample", "0", "--sustained-s", "0.2", "--full"] + extra, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.split("\n") if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -1,8 +1,8 @@
 """Pins for the CPU oracle: it must agree with everything the reference holds
 for this path before any GPU parity claim leans on it.
 
-  * XXH3_64bits vs the reference's own vendored xxhash.c (oracle/_ref, built by
-    `make ref` from /root/reference/xxhash.c; skipped where it is absent)
+  * XXH3_64bits vs the reference's own vendored xxhash.c: hashes it gave, stored under
+    tests/golden/, and the build itself (oracle/_ref, `make ref`) where that is present
   * the known-answer vectors recorded from the compiled reference in
     SURVEY.md Appendix B (hashes, canonical forms, counter wrap, raw likelihoods)
   * the reference's example: example/haploid.tar.gz -> example/haploid.malva.vcf,
@@ -33,10 +33,37 @@ def test_xxh3_known_answers():
     assert capi.xxh3_64(kat[0][0]) % (1 << 33) == 638663402
 
 
+def _xxh3_inputs():
+    """the inputs of tests/golden/xxh3_ref_hashes.npy: 25 strings of random bytes of every length 0..240, then 2000 ACGTN strings
+    of each of the lengths 35, 43, 63, drawn from a splitmix64 stream (spelled out here: no library's generator to drift)"""
+    m = (1 << 64) - 1
+    x = 20261016
+
+    def word():
+        nonlocal x
+        x = (x + 0x9E3779B97F4A7C15) & m
+        z = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return z ^ (z >> 31)
+    for length in range(0, 241):
+        for _ in range(25):
+            yield b"".join(word().to_bytes(8, "little") for _ in range((length + 7) // 8))[:length]
+    for length in (35, 43, 63):
+        for _ in range(2000):
+            yield bytes(b"ACGTN"[word() % 5] for _ in range(length))
+
+
 def test_xxh3_matches_reference_build():
+    """against hashes the reference's own xxhash.c gave for the same inputs (stored), and against that build itself where
+    oracle/_ref holds it"""
+    want = np.load(os.path.join(ROOT, "tests", "golden", "xxh3_ref_hashes.npy"))
+    inputs = list(_xxh3_inputs())
+    assert want.dtype == np.uint64 and want.size == len(inputs) == 241 * 25 + 3 * 2000
+    for b, h in zip(inputs, want):
+        assert capi.xxh3_64(b) == int(h), len(b)
     path = os.path.join(ROOT, "oracle", "_ref", "libxxhash_ref.so")
     if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference checkout absent)")
+        return
     ref = ctypes.CDLL(path)
     ref.XXH3_64bits.restype = ctypes.c_uint64
     ref.XXH3_64bits.argtypes = [ctypes.c_char_p, ctypes.c_size_t]

@@ -7,7 +7,7 @@ TAG=${1:-x}; shift
 OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="$PWD/bench.py --cpu-sample 0 --sustained-s 0 $*"
+BENCH="$PWD/bench.py --full --cpu-sample 0 --sustained-s 0 $*"
 # PMC_SCRIPT=tools/c5_blocks_bench.py: another python command of this repository instead of bench.py (its arguments follow the tag)
 if [ -n "$PMC_SCRIPT" ]; then BENCH="$PWD/$PMC_SCRIPT $*"; fi
 GROUPS_=(

@@ -6,7 +6,7 @@ TAG=${1:-x}; shift
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="$PWD/bench.py --cpu-sample 0 --sustained-s 0 $*"
+BENCH="$PWD/bench.py --full --cpu-sample 0 --sustained-s 0 $*"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 $BENCH > "$OUT/bench.json" 2> "$OUT/bench.log" || { echo "stats pass failed"; tail -5 "$OUT/bench.log"; exit 1; }
 cd - > /dev/null

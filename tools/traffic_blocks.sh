@@ -8,7 +8,7 @@ WL=${1:-c5}; shift
 OUT=$PWD/gpurun_out/traffic_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="$PWD/bench.py --workload $WL --steps 1 --warmup 0 --cpu-sample 0 --sustained-s 0 $*"
+BENCH="$PWD/bench.py --full --workload $WL --steps 1 --warmup 0 --cpu-sample 0 --sustained-s 0 $*"
 cd /tmp
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 $BENCH > "$OUT/bench_fetch.json" 2> "$OUT/fetch.log" || { echo "FETCH_SIZE pass failed"; tail -3 "$OUT/fetch.log"; exit 1; }
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- python3 $BENCH > /dev/null 2> "$OUT/write.log" || { echo "WRITE_SIZE pass failed"; tail -3 "$OUT/write.log"; exit 1; }
