@@ -148,6 +148,33 @@ int mg_kmc_scan_records(mg_ctx *ctx, const void *records, size_t n, uint64_t fir
 int mg_kmc_decode_records(mg_ctx *ctx, const void *records, size_t n, uint64_t first_record, uint64_t *hi_out,
                           uint64_t *lo_out, uint32_t *cnt_out);
 
+/* ---- counting from reads: the KMC step of MALVA:104-110 fused into the call-time scan (main.cpp:482-500) ----------------
+ * `kmc -k<ref_k> -ci<min> -cs<max> -fm` (MALVA:107) on the device: canonical ref_k-mers of the reads, a window with a byte outside
+ * ACGT skipped (lower-case acgt count as upper case), a k-mer kept when seen >= min_count times (0 counts as 1), its count
+ * capped at max_count.  Only the windows that pass the scan's own gate are counted: the others cannot change a counter
+ * (BF::increment / KMAP::increment are no-ops for them, bloom_filter.hpp:100-113, kmap.hpp:114-122), so after mg_reads_finish
+ * the counters are exactly what mg_kmc_scan_device leaves given KMC's table of the same reads -- record counters, lazy vectors
+ * and groups alike.  Both filters must be finalised; ref_k <= MG_MAX_PACKED_K.
+ *   mg_reads_begin       starts a count.  Keeps only the keys whose hash % n_parts == part: with N devices, every device sees
+ *                        every chunk with part = its rank, n_parts = N, and the exchange (mg_counters_allreduce*) sums the
+ *                        counters -- a k-mer's count is then global before min_count applies.
+ *   mg_reads_add         a chunk of WHOLE records, one byte outside ACGT (e.g. '\n') between two of them: no window crosses it.
+ *                        Returns once the bytes are up (pinned buffers from mg_host_alloc make that a DMA); the device packs
+ *                        the chunk (2 bits + 1 mask bit per base) and keeps it until mg_reads_finish.
+ *   mg_reads_add_device  the same from a device buffer (asynchronous).
+ *   mg_reads_finish      count (passes whose pairs fit option reads_budget_mb, at least reads_passes of them), apply
+ *                        min / max, scan the kept rows; *n_kept_out = rows kept.
+ *   mg_reads_export      the kept rows (any order; only the gate's survivors, a subset of KMC's table): up to cap of them,
+ *                        *n_out = all of them.
+ *   mg_reads_stats       ms_out[5]: device milliseconds (HIP events) of pack, window + filter, file, reduce, scan;
+ *                        counts_out[5]: bases, windows inside ACGT, gate survivors, passes, rows kept. */
+int mg_reads_begin(mg_ctx *ctx, uint32_t min_count, uint32_t max_count, uint32_t part, uint32_t n_parts);
+int mg_reads_add(mg_ctx *ctx, const char *seq, size_t bytes);
+int mg_reads_add_device(mg_ctx *ctx, const void *d_seq, size_t bytes);
+int mg_reads_finish(mg_ctx *ctx, uint64_t *n_kept_out);
+int mg_reads_export(mg_ctx *ctx, uint64_t *hi, uint64_t *lo, uint32_t *cnt, size_t cap, uint64_t *n_out);
+int mg_reads_stats(mg_ctx *ctx, float *ms_out, uint64_t *counts_out);
+
 /* ---- multi-GPU exchange step --------------------------------------------- */
 
 /* The scan's only state is two commutative wrapping-u32 sums:

@@ -88,6 +88,12 @@ def lib():
         "mg_host_alloc": [C.POINTER(vp), sz],
         "mg_host_free": [vp],
         "mg_kmc_set_lut": [vp, vp, sz, u32, u32, u32, u32, u64, u64],
+        "mg_reads_begin": [vp, u32, u32, u32, u32],
+        "mg_reads_add": [vp, vp, sz],
+        "mg_reads_add_device": [vp, vp, sz],
+        "mg_reads_finish": [vp, vp],
+        "mg_reads_export": [vp, vp, vp, vp, sz, vp],
+        "mg_reads_stats": [vp, vp, vp],
         "mg_kmc_scan_records": [vp, vp, sz, u64],
         "mg_kmc_decode_records": [vp, vp, sz, u64, vp, vp, vp],
         "mg_counters_size": [vp, vp, vp],
@@ -151,6 +157,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_bf_finalize", "mg_bf_increment", "mg_bf_get_count", "mg_bf_info", "mg_map_insert", "mg_map_test",
             "mg_map_increment", "mg_map_get_count", "mg_map_size", "mg_ref_scan", "mg_ref_scan_resident", "mg_reference_upload_device", "mg_kmc_scan", "mg_kmc_scan_device", "mg_kmc_rows_bytes", "mg_kmc_pack_rows_device", "mg_kmc_scan_rows_device",
             "mg_host_alloc", "mg_host_free", "mg_kmc_set_lut", "mg_kmc_scan_records", "mg_kmc_decode_records",
+            "mg_reads_begin", "mg_reads_add", "mg_reads_add_device", "mg_reads_finish", "mg_reads_export", "mg_reads_stats",
             "mg_counters_size", "mg_counters_export_device", "mg_counters_import_device", "mg_counters_reset", "mg_counters_view",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -445,6 +452,38 @@ class Context:
         hi, lo, cnt = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
         self._ck(self._L.mg_kmc_decode_records(self.h, _p(records), n, first_record, _p(hi), _p(lo), _p(cnt)))
         return hi, lo, cnt
+
+    # counting from reads (the KMC step, MALVA:104-110)
+    def reads_begin(self, min_count=2, max_count=255, part=0, n_parts=1):
+        self._ck(self._L.mg_reads_begin(self.h, min_count, max_count, part, n_parts))
+
+    def reads_add(self, seq):
+        """seq: bytes of whole records, a byte outside ACGT (newline) between two of them"""
+        buf = np.frombuffer(bytes(seq), dtype=np.uint8)
+        self._ck(self._L.mg_reads_add(self.h, _p(buf), buf.size))
+
+    def reads_add_device(self, d_ptr, nbytes):
+        self._ck(self._L.mg_reads_add_device(self.h, C.c_void_p(d_ptr), int(nbytes)))
+
+    def reads_finish(self):
+        """-> rows kept (count >= min) and scanned"""
+        n = C.c_uint64(0)
+        self._ck(self._L.mg_reads_finish(self.h, C.byref(n)))
+        return n.value
+
+    def reads_export(self):
+        """-> (hi, lo, cnt) of the kept rows, any order"""
+        n = C.c_uint64(0)
+        self._ck(self._L.mg_reads_export(self.h, None, None, None, 0, C.byref(n)))
+        hi, lo, cnt = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+        self._ck(self._L.mg_reads_export(self.h, _p(hi), _p(lo), _p(cnt), n.value, C.byref(n)))
+        return hi, lo, cnt
+
+    def reads_stats(self):
+        """-> (ms: pack, window + filter, file, reduce, scan; counts: bases, windows, survivors, passes, kept)"""
+        ms, cn = (C.c_float * 5)(), (C.c_uint64 * 5)()
+        self._ck(self._L.mg_reads_stats(self.h, ms, cn))
+        return list(ms), list(cn)
 
     def kmc_rows_bytes(self, n):
         return self._L.mg_kmc_rows_bytes(n)

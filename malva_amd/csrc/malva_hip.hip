@@ -38,6 +38,7 @@ constexpr int TPB = 256;
 #include "variant_kernels.h"
 #include "block_pipeline.h"
 #include "gt_text_kernels.h"
+#include "reads_kernels.h"
 
 } // namespace
 
@@ -199,6 +200,11 @@ struct mg_ctx {
     u64 kmc_n_lut = 0;
     u32 kmc_prefix_len = 0, kmc_suffix_bytes = 0, kmc_counter_bytes = 0, kmc_min_count = 0;
     u64 kmc_max_count = 0;
+    // counting from reads (mg_reads_*): the state of the current begin .. finish, and two tunables
+    struct ReadsState *reads = nullptr;
+    int reads_budget_mb = 4096; // pairs (20 B each) one pass may file
+    int reads_passes = 0;       // at least this many passes (tests)
+    int reads_parts_log2 = RD_PART_LOG2; // key partitions (tests: fewer, so that one bin outgrows LDS with distinct keys)
     std::string err;
 };
 
@@ -230,6 +236,7 @@ int fail(mg_ctx *c, int code, const char *fmt, ...)
 
 inline unsigned nblocks(u64 n) { return (unsigned)((n + TPB - 1) / TPB); }
 int comm_drop(mg_ctx *c); // multi-GPU section
+void reads_drop(mg_ctx *c); // reads section
 
 int scratch(mg_ctx *c, Scratch &s, size_t bytes, void **out)
 {
@@ -631,6 +638,7 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     comm_drop(c);
+    reads_drop(c);
     if (c->ev_x) hipEventDestroy(c->ev_x);
     for (auto &e : c->ev_xs)
         if (e) hipEventDestroy(e);
@@ -771,6 +779,9 @@ MG_EXPORT int mg_set_option(mg_ctx *c, const char *name, int64_t value)
         c->pregate_log2 = (int)value;
         return alloc_gate(c);
     }
+    else if (!strcmp(name, "reads_budget_mb")) c->reads_budget_mb = (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, value));
+    else if (!strcmp(name, "reads_passes")) c->reads_passes = (int)std::max<int64_t>(0, std::min<int64_t>(RD_PARTS, value));
+    else if (!strcmp(name, "reads_parts_log2")) c->reads_parts_log2 = (int)std::max<int64_t>(0, std::min<int64_t>(RD_PART_LOG2, value));
     else if (!strcmp(name, "scan_variant")) c->scan_variant = (int)value & 2;
     else if (!strcmp(name, "scan_grid")) c->scan_grid = value > 0 ? (int)value : 8192;
     else if (!strcmp(name, "gate_log2") || !strcmp(name, "gate_k")) {
@@ -834,6 +845,9 @@ MG_EXPORT int mg_get_option(mg_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "vectors_stale")) *value = c->vec_stale;
     else if (!strcmp(name, "ticket_gate_grid")) *value = c->tkg_grid;
     else if (!strcmp(name, "use_tickets")) *value = c->use_tickets;
+    else if (!strcmp(name, "reads_budget_mb")) *value = c->reads_budget_mb;
+    else if (!strcmp(name, "reads_passes")) *value = c->reads_passes;
+    else if (!strcmp(name, "reads_parts_log2")) *value = c->reads_parts_log2;
     else if (!strcmp(name, "scan_spilled")) { // rows of the last chunk that took the spill list
         unsigned long long t = 0;
         if (c->last_bins || c->last_tickets || c->last_subs) {
@@ -3509,6 +3523,351 @@ MG_EXPORT int mg_map_import(mg_ctx *c, const char *rows, size_t stride, size_t n
                 auto it = c->map.irregular.find(host_irregular_key(rows + i * stride, stride));
                 if (it != c->map.irregular.end()) it->second = vals[i];
             }
+    }
+    return MG_OK;
+}
+
+// ---- counting from reads: the KMC step of MALVA:104-110 fused into the call-time scan (main.cpp:482-500) ----------------------
+
+namespace {
+struct ReadsSeg { // one chunk, packed (pack_word): it stays on the device until the passes of mg_reads_finish have read it
+    u64 n = 0;
+    u64 *codes = nullptr;
+    u32 *bad = nullptr;
+};
+struct ReadsTable { // the kept rows of one pass (what the scan took; mg_reads_export)
+    u64 *hi = nullptr, *lo = nullptr;
+    u32 *cnt = nullptr;
+    u64 n = 0;
+};
+struct ReadsTiming {
+    int phase; // 0 pack, 1 window + filter (counting pre-pass), 2 file, 3 reduce, 4 scan
+    hipEvent_t a, b;
+};
+} // namespace
+struct ReadsState {
+    u32 min_count = 2, max_count = 255, part = 0, n_parts = 1, n_bins = RD_PARTS;
+    bool finished = false;
+    std::vector<ReadsSeg> segs;
+    u32 *d_parts = nullptr;               // [RD_PARTS] gate survivors per partition (reads_window_kernel<0>)
+    unsigned long long *d_meta = nullptr; // [0] windows inside ACGT, [1] survivors, [2] kept rows of the current pass
+    std::vector<ReadsTable> kept;
+    std::vector<ReadsTiming> tm;
+    u64 bases = 0, windows = 0, survivors = 0, n_kept = 0, passes = 0;
+    float ms[5] = {0, 0, 0, 0, 0};
+    int slot = 0;
+    bool slot_used[2] = {false, false};
+    Scratch ascii[2], pairs[3], bin_base, bin_fill, out[3];
+};
+
+namespace {
+void reads_drop(mg_ctx *c)
+{
+    ReadsState *R = c->reads;
+    if (!R) return;
+    hipStreamSynchronize(c->stream);
+    for (auto &s : R->segs) {
+        hipFree(s.codes);
+        hipFree(s.bad);
+    }
+    for (auto &t : R->kept) {
+        hipFree(t.hi);
+        hipFree(t.lo);
+        hipFree(t.cnt);
+    }
+    for (auto &t : R->tm) {
+        if (t.a) hipEventDestroy(t.a);
+        if (t.b) hipEventDestroy(t.b);
+    }
+    hipFree(R->d_parts);
+    hipFree(R->d_meta);
+    for (Scratch *s : {&R->ascii[0], &R->ascii[1], &R->pairs[0], &R->pairs[1], &R->pairs[2], &R->bin_base, &R->bin_fill, &R->out[0], &R->out[1], &R->out[2]})
+        hipFree(s->p);
+    delete R;
+    c->reads = nullptr;
+}
+int reads_open(mg_ctx *c)
+{
+    if (!c) return MG_ERR_ARG;
+    if (!c->reads) return fail(c, MG_ERR_STATE, "mg_reads_begin first");
+    if (c->reads->finished) return fail(c, MG_ERR_STATE, "mg_reads_finish has run: mg_reads_begin starts a new count");
+    return MG_OK;
+}
+int reads_event(mg_ctx *c, hipEvent_t *e)
+{
+    HIP_TRY(c, hipEventCreate(e));
+    HIP_TRY(c, hipEventRecord(*e, c->stream));
+    return MG_OK;
+}
+template <int MODE>
+void launch_reads_windows(mg_ctx *c, const ReadsSeg &s, const ReadsPass &rp)
+{
+    if (s.n < c->ref_k) return;
+    const u64 nw = s.n - c->ref_k + 1;
+    const unsigned grid = (unsigned)std::min<u64>(nblocks((nw + RD_W - 1) / RD_W), 1u << 16);
+    const BFView bf = view(c, MG_BF_ALT);
+    if (c->k == 35 && c->ref_k == 43)
+        hipLaunchKernelGGL((reads_window_kernel<35, 43, MODE>), dim3(grid), dim3(TPB), 0, c->stream, s.codes, s.bad, nw, (int)c->k, (int)c->ref_k, bf, rp);
+    else if (c->k == 35 && c->ref_k == 63)
+        hipLaunchKernelGGL((reads_window_kernel<35, 63, MODE>), dim3(grid), dim3(TPB), 0, c->stream, s.codes, s.bad, nw, (int)c->k, (int)c->ref_k, bf, rp);
+    else
+        hipLaunchKernelGGL((reads_window_kernel<0, 0, MODE>), dim3(grid), dim3(TPB), 0, c->stream, s.codes, s.bad, nw, (int)c->k, (int)c->ref_k, bf, rp);
+}
+// a chunk already on the device (4-byte aligned): packed into a segment of its own, its survivors counted per partition
+int reads_add_dev(mg_ctx *c, const u8 *d_ascii, size_t bytes)
+{
+    ReadsState &R = *c->reads;
+    const u64 n_words = (bytes + 31) / 32 + 4; // (+ the words the window loads may touch past the last base)
+    R.segs.push_back(ReadsSeg{});
+    ReadsSeg &s = R.segs.back();
+    s.n = bytes;
+    HIP_TRY(c, hipMalloc(&s.codes, n_words * 8));
+    HIP_TRY(c, hipMalloc(&s.bad, n_words * 4));
+    ReadsTiming t0{0, nullptr, nullptr}, t1{1, nullptr, nullptr};
+    TRY(reads_event(c, &t0.a));
+    hipLaunchKernelGGL(reads_pack_kernel, dim3(nblocks(n_words)), dim3(TPB), 0, c->stream, d_ascii, (u64)bytes, s.codes, s.bad, n_words);
+    TRY(reads_event(c, &t0.b));
+    ReadsPass rp{};
+    rp.part = R.part;
+    rp.n_parts = R.n_parts;
+    rp.bin_mask = R.n_bins - 1;
+    rp.part_count = R.d_parts;
+    rp.meta = R.d_meta;
+    launch_reads_windows<0>(c, s, rp);
+    HIP_TRY(c, hipGetLastError());
+    TRY(reads_event(c, &t1.b));
+    R.tm.push_back(t0);
+    R.tm.push_back(t1); // (no `a`: it starts where the pack ended)
+    R.bases += bytes;
+    return MG_OK;
+}
+int reads_timings(mg_ctx *c)
+{
+    ReadsState &R = *c->reads;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipEvent_t prev = nullptr;
+    for (auto &t : R.tm) {
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, t.a ? t.a : prev, t.b));
+        R.ms[t.phase] += ms;
+        prev = t.b;
+    }
+    return MG_OK;
+}
+} // namespace
+
+MG_EXPORT int mg_reads_begin(mg_ctx *c, uint32_t min_count, uint32_t max_count, uint32_t part, uint32_t n_parts)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (c->ref_k > MG_MAX_PACKED_K) return fail(c, MG_ERR_LIMIT, "counting reads supports ref_k <= %d (ref_k = %u), as the KMC database path does", MG_MAX_PACKED_K, c->ref_k);
+    if (n_parts == 0 || part >= n_parts) return fail(c, MG_ERR_ARG, "key partition %u of %u", part, n_parts);
+    if (!c->bf[0].mode || !c->bf[1].mode) return fail(c, MG_ERR_STATE, "mg_reads_begin needs both filters finalised (the scan's gate decides what is counted)");
+    reads_drop(c);
+    c->reads = new ReadsState();
+    ReadsState &R = *c->reads;
+    R.min_count = min_count ? min_count : 1; // (KMC: -ci0 keeps what -ci1 keeps)
+    R.max_count = max_count ? max_count : 1;
+    R.part = part;
+    R.n_parts = n_parts;
+    R.n_bins = 1u << c->reads_parts_log2;
+    HIP_TRY(c, hipMalloc(&R.d_parts, (size_t)RD_PARTS * 4));
+    HIP_TRY(c, hipMalloc(&R.d_meta, 32));
+    HIP_TRY(c, hipMemsetAsync(R.d_parts, 0, (size_t)RD_PARTS * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(R.d_meta, 0, 32, c->stream));
+    TRY(pipeline_ready(c));
+    return MG_OK;
+}
+
+// Whole records, any byte outside ACGT (a newline) between two of them.  The bytes go up on the copy stream into one of two
+// slots (a pinned source -- mg_host_alloc -- makes that a DMA beside the device's work); the call returns once they are
+// up, while the pack and the pre-pass of this chunk run behind on the context's stream.
+MG_EXPORT int mg_reads_add(mg_ctx *c, const char *seq, size_t bytes)
+{
+    const DeviceGuard on_device(c, LAZY);
+    TRY(reads_open(c));
+    if (bytes == 0) return MG_OK;
+    if (!seq) return fail(c, MG_ERR_ARG, "NULL reads");
+    ReadsState &R = *c->reads;
+    const int sl = R.slot;
+    R.slot ^= 1;
+    const size_t want = (bytes + 63) / 64 * 64 + 256;
+    if (want > R.ascii[sl].cap) HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the slot is about to be freed and reallocated)
+    void *d;
+    TRY(scratch(c, R.ascii[sl], want, &d));
+    if (R.slot_used[sl]) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_free[sl], 0)); // the pack that read this slot is done
+    HIP_TRY(c, hipMemcpyAsync(d, seq, bytes, hipMemcpyHostToDevice, c->copy_stream));
+    HIP_TRY(c, hipEventRecord(c->ev_up[sl], c->copy_stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_up[sl], 0));
+    TRY(reads_add_dev(c, (const u8 *)d, bytes));
+    HIP_TRY(c, hipEventRecord(c->ev_free[sl], c->stream));
+    R.slot_used[sl] = true;
+    HIP_TRY(c, hipEventSynchronize(c->ev_up[sl])); // the caller may reuse its buffer
+    return MG_OK;
+}
+
+MG_EXPORT int mg_reads_add_device(mg_ctx *c, const void *d_seq, size_t bytes)
+{
+    const DeviceGuard on_device(c, LAZY);
+    TRY(reads_open(c));
+    if (bytes == 0) return MG_OK;
+    if (!d_seq) return fail(c, MG_ERR_ARG, "NULL reads");
+    if (((uintptr_t)d_seq & 3) == 0) return reads_add_dev(c, (const u8 *)d_seq, bytes);
+    ReadsState &R = *c->reads; // (the pack reads whole dwords: an unaligned source is copied first)
+    const int sl = R.slot;
+    R.slot ^= 1;
+    const size_t want = (bytes + 63) / 64 * 64 + 256;
+    if (want > R.ascii[sl].cap) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    void *d;
+    TRY(scratch(c, R.ascii[sl], want, &d));
+    HIP_TRY(c, hipMemcpyAsync(d, d_seq, bytes, hipMemcpyDeviceToDevice, c->stream));
+    TRY(reads_add_dev(c, (const u8 *)d, bytes));
+    HIP_TRY(c, hipEventRecord(c->ev_free[sl], c->stream));
+    R.slot_used[sl] = true;
+    return MG_OK;
+}
+
+// The passes: partitions grouped so that the pairs of one pass fit reads_budget_mb (at least reads_passes of them); per pass
+// every chunk's survivors of those partitions are filed into their bins, each bin is reduced to its distinct keys, [min, max]
+// applied, and the kept rows scanned by mg_kmc_scan_device -- the scan itself, not a second one.
+MG_EXPORT int mg_reads_finish(mg_ctx *c, uint64_t *n_kept_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    TRY(reads_open(c));
+    ReadsState &R = *c->reads;
+    R.finished = true;
+    std::vector<u32> parts(RD_PARTS);
+    unsigned long long meta[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(parts.data(), R.d_parts, (size_t)RD_PARTS * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(meta, R.d_meta, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    R.windows = meta[0];
+    R.survivors = meta[1];
+    // passes: runs of partitions whose pairs fit the budget (a partition is never split: a bin larger than the budget takes a pass
+    // of its own); reads_passes cuts the partitions into that many equal ranges first
+    const u64 per_pass = std::max<u64>(1, ((u64)c->reads_budget_mb << 20) / 20);
+    const u32 range = c->reads_passes > 0 ? (R.n_bins + (u32)c->reads_passes - 1) / (u32)c->reads_passes : R.n_bins;
+    struct Pass {
+        u32 lo, hi;
+        u64 pairs;
+    };
+    std::vector<Pass> plan;
+    u64 biggest = 0;
+    for (u32 p = 0; p < R.n_bins;) {
+        const u32 end = std::min<u32>(R.n_bins, (p / range + 1) * range);
+        u64 sum = 0;
+        u32 q = p;
+        while (q < end && (q == p || sum + parts[q] <= per_pass)) sum += parts[q++];
+        if (sum) plan.push_back(Pass{p, q, sum});
+        biggest = std::max(biggest, sum);
+        p = q;
+    }
+    void *ph, *pl, *pc, *pbase, *pfill, *oh, *ol, *oc;
+    if (biggest) {
+        TRY(scratch(c, R.pairs[0], biggest * 8, &ph));
+        TRY(scratch(c, R.pairs[1], biggest * 8, &pl));
+        TRY(scratch(c, R.pairs[2], biggest * 4, &pc));
+        TRY(scratch(c, R.out[0], biggest * 8, &oh));
+        TRY(scratch(c, R.out[1], biggest * 8, &ol));
+        TRY(scratch(c, R.out[2], biggest * 4, &oc));
+        TRY(scratch(c, R.bin_base, (size_t)RD_PARTS * 8, &pbase));
+        TRY(scratch(c, R.bin_fill, (size_t)RD_PARTS * 4, &pfill));
+    }
+    std::vector<u64> base(RD_PARTS);
+    for (const Pass &ps : plan) {
+        const u32 nb = ps.hi - ps.lo;
+        u64 at = 0;
+        for (u32 b = 0; b < nb; ++b) {
+            base[b] = at;
+            at += parts[ps.lo + b];
+        }
+        HIP_TRY(c, hipMemcpyAsync(pbase, base.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(pfill, 0, (size_t)nb * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(R.d_meta + 2, 0, 8, c->stream));
+        ReadsTiming tf{2, nullptr, nullptr}, tr{3, nullptr, nullptr}, ts{4, nullptr, nullptr}; // (each event destroyed once: entries without `a` start at the previous entry's end)
+        TRY(reads_event(c, &tf.a));
+        ReadsPass rp{};
+        rp.part = R.part;
+        rp.n_parts = R.n_parts;
+        rp.bin_mask = R.n_bins - 1;
+        rp.p_lo = ps.lo;
+        rp.p_hi = ps.hi;
+        rp.bin_base = (const u64 *)pbase;
+        rp.bin_fill = (u32 *)pfill;
+        rp.key_hi = (u64 *)ph;
+        rp.key_lo = (u64 *)pl;
+        for (const ReadsSeg &s : R.segs) launch_reads_windows<1>(c, s, rp);
+        HIP_TRY(c, hipGetLastError());
+        TRY(reads_event(c, &tf.b));
+        ReadsReduce rr{(const u64 *)pbase, (const u32 *)pfill, (u64 *)ph, (u64 *)pl, (u32 *)pc, R.min_count, R.max_count, (u64 *)oh, (u64 *)ol, (u32 *)oc, R.d_meta + 2};
+        hipLaunchKernelGGL(reads_reduce_kernel, dim3(nb), dim3(RD_TPB), 0, c->stream, rr);
+        HIP_TRY(c, hipGetLastError());
+        TRY(reads_event(c, &tr.b));
+        unsigned long long kept = 0;
+        HIP_TRY(c, hipMemcpyAsync(&kept, R.d_meta + 2, 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // (also: `base` may be rewritten for the next pass)
+        ReadsTable t;
+        t.n = kept;
+        R.kept.push_back(t);
+        ReadsTable &kt = R.kept.back();
+        if (kept) {
+            HIP_TRY(c, hipMalloc(&kt.hi, kept * 8));
+            HIP_TRY(c, hipMalloc(&kt.lo, kept * 8));
+            HIP_TRY(c, hipMalloc(&kt.cnt, kept * 4));
+            HIP_TRY(c, hipMemcpyAsync(kt.hi, oh, kept * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(kt.lo, ol, kept * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(kt.cnt, oc, kept * 4, hipMemcpyDeviceToDevice, c->stream));
+            TRY(reads_event(c, &ts.a));
+            TRY(mg_kmc_scan_device(c, kt.hi, kt.lo, kt.cnt, kept));
+            TRY(reads_event(c, &ts.b));
+        }
+        R.tm.push_back(tf);
+        R.tm.push_back(ReadsTiming{3, nullptr, tr.b}); // (from where the filing ended)
+        if (kept) R.tm.push_back(ts);
+        R.n_kept += kept;
+        ++R.passes;
+    }
+    TRY(reads_timings(c));
+    if (n_kept_out) *n_kept_out = R.n_kept;
+    return MG_OK;
+}
+
+MG_EXPORT int mg_reads_export(mg_ctx *c, uint64_t *hi, uint64_t *lo, uint32_t *cnt, size_t cap, uint64_t *n_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (!c->reads || !c->reads->finished) return fail(c, MG_ERR_STATE, "mg_reads_finish first");
+    const ReadsState &R = *c->reads;
+    if (n_out) *n_out = R.n_kept;
+    size_t at = 0;
+    for (const ReadsTable &t : R.kept) {
+        if (at >= cap) break;
+        const size_t m = std::min<size_t>(t.n, cap - at);
+        if (!m) continue;
+        if (!hi || !lo || !cnt) return fail(c, MG_ERR_ARG, "NULL output");
+        HIP_TRY(c, hipMemcpyAsync(hi + at, t.hi, m * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(lo + at, t.lo, m * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cnt + at, t.cnt, m * 4, hipMemcpyDeviceToHost, c->stream));
+        at += m;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_reads_stats(mg_ctx *c, float *ms_out, uint64_t *counts_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (!c->reads || !c->reads->finished) return fail(c, MG_ERR_STATE, "mg_reads_finish first");
+    const ReadsState &R = *c->reads;
+    if (ms_out)
+        for (int i = 0; i < 5; ++i) ms_out[i] = R.ms[i];
+    if (counts_out) {
+        counts_out[0] = R.bases;
+        counts_out[1] = R.windows;
+        counts_out[2] = R.survivors;
+        counts_out[3] = R.passes;
+        counts_out[4] = R.n_kept;
     }
     return MG_OK;
 }

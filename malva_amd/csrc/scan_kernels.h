@@ -72,10 +72,11 @@ __global__ void __launch_bounds__(TPB) ref_scan_kernel(const u8 *contig, u64 w0,
 // bits 2 (i % 32) of word i / 32 -- the L-form's order, so a span comes out as the L-form of its bases with two loads and a
 // shift -- and refbad one bit per base, set where the byte is not one of ACGT (N, IUPAC, a lower-case letter that escaped
 // the caller's toupper).  Both arrays are padded with two zero words.  One thread packs 32 bases from eight aligned dwords.
-__global__ void __launch_bounds__(TPB) ref_pack_kernel(const u8 *__restrict__ ascii, u64 n, u64 *__restrict__ ref2, u32 *__restrict__ refbad, u64 n_words)
+// FOLD: lower-case acgt count as upper case (sequencing reads, reads_kernels.h): a byte with bit 6 set loses bit 5 first, which
+// turns exactly a c g t into A C G T and leaves every other byte outside ACGT
+template <bool FOLD>
+__device__ __forceinline__ void pack_word(const u8 *__restrict__ ascii, u64 n, u64 w, u64 *__restrict__ ref2, u32 *__restrict__ refbad)
 {
-    const u64 w = (u64)blockIdx.x * TPB + threadIdx.x;
-    if (w >= n_words) return;
     u64 codes = 0;
     u32 bad = 0;
     const u32 *q = (const u32 *)(ascii + 32 * w); // (the buffer is padded to a multiple of 64 bytes)
@@ -86,6 +87,7 @@ __global__ void __launch_bounds__(TPB) ref_pack_kernel(const u8 *__restrict__ as
         if (at + 4 <= n) d = q[j];
         else // the last, partial dword byte by byte: the buffer may end with its last base (the record loop's allele pool)
             for (u64 i = at; i < n; ++i) d |= (u32)ascii[i] << (8 * (i - at));
+        if (FOLD) d &= ~((d & 0x40404040u) >> 1);
         u32 t = (d >> 1) & 0x03030303u; // per byte: A0 C1 G3 T2
         t ^= (t >> 1) & 0x01010101u;    //           A0 C1 G2 T3
         const u32 c8 = (t * 0x01041040u) >> 24;
@@ -99,6 +101,12 @@ __global__ void __launch_bounds__(TPB) ref_pack_kernel(const u8 *__restrict__ as
     }
     ref2[w] = codes;
     refbad[w] = bad;
+}
+__global__ void __launch_bounds__(TPB) ref_pack_kernel(const u8 *__restrict__ ascii, u64 n, u64 *__restrict__ ref2, u32 *__restrict__ refbad, u64 n_words)
+{
+    const u64 w = (u64)blockIdx.x * TPB + threadIdx.x;
+    if (w >= n_words) return;
+    pack_word<false>(ascii, n, w, ref2, refbad);
 }
 // n <= 32 bases from position `start` as an L-form (base i of the span at bits 2i)
 __device__ __forceinline__ u64 ref_codes(const u64 *__restrict__ ref2, u64 start, int n)
@@ -378,6 +386,15 @@ __global__ void __launch_bounds__(TPB) scan_filter_kernel(const u64 *__restrict_
         finish(t);
     }
     st.flush_if_above(0, open, &counters[0]);
+}
+
+// The filter's gate test of ONE table row -- phases B-D of scan_filter_kernel for a row that is not read from a table: m is the
+// canonical ref_k-mer (M-form), l the same string as an L-form.  Callers that make rows themselves (reads_kernels.h) drop a row
+// exactly where the scan would.
+template <int KC>
+__device__ __forceinline__ bool row_gate_open(U128 m, U128 l, int r, int off, int k, const u32 *lut, const BFView &bf)
+{
+    return gate_open(bf, mod_size(xxh3_packed_k<KC>(canon_sub(m, l, r, off, k), k, lut), bf.mod));
 }
 
 // ---- compact table rows ------------------------------------------------------------------------------------------

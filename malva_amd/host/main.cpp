@@ -26,6 +26,7 @@
 #include "block.hpp"
 #include "index_file.hpp"
 #include "kmc_db.hpp"
+#include "reads.hpp"
 extern "C" {
 #include "malva_hip.h"
 }
@@ -36,7 +37,7 @@ namespace {
 
 const char *USAGE =
     "Usage: malva-geno <index|call> [-k KMER-SIZE] [-r REF-KMER-SIZE] [-c MAX-COV] "
-    "<reference.fa> <variants.vcf> <kmc_output_prefix>\n"
+    "<reference.fa> <variants.vcf> <kmc_output_prefix | READS>\n"
     "\n"
     "      -h, --help                        display this help and exit\n"
     "      -k, --kmer-size                   size of the kmers to index (default:35)\n"
@@ -55,9 +56,15 @@ const char *USAGE =
     "                                        only with all contexts on ONE device: untested on multi-GPU hardware]\n"
     "                                        call: the k-mer table is sharded over them, the per-allele counters\n"
     "                                        are all-reduced over RCCL, the variants are split between them\n"
+    "          --min-count                   READS only: drop k-mers seen fewer times (default:2, KMC -ci; 0 = 1)  [this build]\n"
+    "          --max-count                   READS only: cap counts at this value (default:255, KMC -cs)             [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
+    "  READS (call): the sample's reads, counted on the GPU as `kmc -k<r> -ci<min> -cs<max> -fm` would (MALVA:107) -- a FASTQ\n"
+    "  file, a FASTA or multi-line FASTA file, either of them gzip- or BGZF-compressed; a comma-separated list of such files\n"
+    "  (paired ends: a.fq,b.fq, counted together); or @list.txt, one path per line.  Taken in this order: a KMC database at\n"
+    "  the prefix, <prefix>.txt, @list / a comma list, a file whose first non-blank byte is '>' or '@', else a text dump.\n"
     "  index file: <variants.vcf>.c<r>.k<k>.malvax.zst, the reference's container (sdsl + zstd); `call` also reads this\n"
     "  build's compact <...>.malvax.hipz (written when MALVA_GENO_INDEX_FORMAT=hipz).\n"
     "  extra sub-commands (no GPU needed): dump-kmers (signature k-mers of every block); index-convert <fa> <vcf> zst|hipz\n"
@@ -76,6 +83,7 @@ struct Options { // argument_parser.hpp:51-66
     uint64_t bf_size = 1ULL << 35;
     bool strip_chr = false, uniform = false, verbose = false, haploid = false;
     int device = 0, gpus = 1;
+    uint32_t min_count = 2, max_count = 255; // READS: KMC's -ci / -cs defaults (MALVA:107)
     std::string fasta_path, vcf_path, kmc_path;
 };
 
@@ -91,6 +99,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"haplod", no_argument, nullptr, '1'},            {"haploid", no_argument, nullptr, '1'},
                                       {"device", required_argument, nullptr, 'd'},      {"help", no_argument, nullptr, 'h'},
                                       {"gpus", required_argument, nullptr, 'g'},
+                                      {"min-count", required_argument, nullptr, 1001}, {"max-count", required_argument, nullptr, 1002},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -111,6 +120,16 @@ bool parse_arguments(int argc, char **argv, Options &o)
             break;
         case 'd': arg >> o.device; break;
         case 'g': arg >> o.gpus; break;
+        case 1001:
+        case 1002: {
+            long long v = -1;
+            if (!(arg >> v) || v < 0 || v > 0xFFFFFFFFLL) {
+                std::cerr << "malva : --" << (c == 1001 ? "min" : "max") << "-count takes a count 0.." << 0xFFFFFFFFu << "\n";
+                die = true;
+            } else if (c == 1001) o.min_count = (uint32_t)v;
+            else o.max_count = (uint32_t)v;
+            break;
+        }
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -1184,6 +1203,55 @@ void scan_kmc_db(std::vector<Device> &devs, const Options &o, const std::string 
     std::cerr << "[malva-geno] scanned " << db.total << " k-mers" << (devs.size() > 1 ? " on " + std::to_string(devs.size()) + " devices" : std::string()) << std::endl;
 }
 
+// The sample's reads, counted on the devices (the KMC step of MALVA:104-110, mg_reads_*): one reader thread per file fills pinned
+// chunks of whole records; every chunk goes to EVERY device, each counting only its own partition of the keys (part = its
+// rank), so a k-mer's count is whole on one device before --min-count applies; the exchange then sums the counters.
+void count_reads(std::vector<Device> &devs, const Options &o, const std::vector<std::string> &files)
+{
+    const uint32_t n = (uint32_t)devs.size();
+    for (uint32_t d = 0; d < n; ++d) devs[d].check(mg_reads_begin(devs[d].ctx, o.min_count, o.max_count, d, n), "mg_reads_begin");
+    ReadsChunker ch;
+    ch.ref_k = o.ref_k;
+    if (const char *cb = getenv("MALVA_GENO_READS_CHUNK")) // bytes per chunk (tests shrink it to split records across chunks)
+        if (atol(cb) > 0) ch.chunk_bytes = std::max<size_t>((size_t)atol(cb), 2 * o.ref_k + 4096);
+    ch.alloc = [](size_t bytes) -> void * {
+        void *p = nullptr;
+        return mg_host_alloc(&p, bytes) == MG_OK ? p : nullptr;
+    };
+    ch.release = [](void *p) { mg_host_free(p); };
+    uint64_t bytes = 0;
+    {
+        Timed t("reads: read + upload");
+        ch.run(files, [&](const char *buf, size_t len) {
+            for (auto &d : devs) d.check(mg_reads_add(d.ctx, buf, len), "mg_reads_add");
+            bytes += len;
+        });
+    }
+    uint64_t kept = 0;
+    {
+        Timed t("reads: count + scan");
+        std::vector<uint64_t> k(n, 0);
+        on_all_devices(devs, [&](Device &d, size_t i) { d.check(mg_reads_finish(d.ctx, &k[i]), "mg_reads_finish"); });
+        for (auto v : k) kept += v;
+    }
+    float ms[5] = {0, 0, 0, 0, 0};
+    uint64_t cn[5] = {0, 0, 0, 0, 0};
+    devs[0].check(mg_reads_stats(devs[0].ctx, ms, cn), "mg_reads_stats");
+    if (g_timers.on) { // device time of device 0's phases (HIP events)
+        const char *names[5] = {"reads device: pack", "reads device: window+filter", "reads device: file", "reads device: reduce", "reads device: scan"};
+        for (int i = 0; i < 5; ++i) g_timers.add(names[i], ms[i] / 1000.0);
+    }
+    if (devs.size() > 1) {
+        std::vector<mg_ctx *> ctxs;
+        for (auto &d : devs) ctxs.push_back(d.ctx);
+        devs[0].check(mg_counters_allreduce_all(ctxs.data(), (int)ctxs.size()), "mg_counters_allreduce_all");
+        for (auto &d : devs) d.check(mg_synchronize(d.ctx), "mg_synchronize");
+    }
+    std::cerr << "[malva-geno] counted " << cn[1] << " " << o.ref_k << "-mer windows of " << files.size() << " read file(s) (" << bytes
+              << " bytes), " << cn[2] << " through the gate, " << kept << " k-mers kept (count " << std::max<uint32_t>(o.min_count, 1) << ".."
+              << o.max_count << ", " << cn[3] << " pass(es))" << (devs.size() > 1 ? " on " + std::to_string(devs.size()) + " devices" : std::string()) << std::endl;
+}
+
 // one output record waiting for its device results
 struct Rec {
     std::string prefix; // CHROM .. QUAL columns
@@ -1247,11 +1315,27 @@ int call_main(const Options &o)
         return 1;
     };
     // the sample's k-mers: the KMC database the reference opens (main.cpp:444-449), or -- when there is none -- a text dump
+    // or the reads themselves, counted on the devices (MALVA:104-110)
     std::string table = o.kmc_path;
     const bool use_db = KmcDb::present(o.kmc_path);
+    std::vector<std::string> read_files;
+    bool use_reads = false;
     if (!use_db) {
         if (file_exists(o.kmc_path + ".txt")) table = o.kmc_path + ".txt";
-        if (!file_exists(table)) return fail_early("ERROR: cannot open " + o.kmc_path);
+        else {
+            try {
+                use_reads = reads_input(o.kmc_path, &read_files);
+                if (use_reads) {
+                    if (o.ref_k > MG_MAX_PACKED_K)
+                        return fail_early("ERROR: counting reads needs -r <= " + std::to_string(MG_MAX_PACKED_K) + " (the packed k-mer paths; -r " + std::to_string(o.ref_k) +
+                                          "): give a k-mer table instead");
+                    reads_check_heads(read_files); // (before any device: a file that is not reads fails at once)
+                }
+            } catch (const std::exception &e) {
+                return fail_early(e.what());
+            }
+        }
+        if (!use_reads && !file_exists(table)) return fail_early("ERROR: cannot open " + o.kmc_path);
     }
     // --gpus N: one context per device -d .. -d+N-1.  MALVA_GENO_SHARE_DEVICE=1 puts all N contexts on device -d: the
     // N-way layout (sharded scan, exchange, split genotyping) rehearsed on a one-GPU box, the exchange then being a
@@ -1283,7 +1367,8 @@ int call_main(const Options &o)
     pelapsed("Reference processed"); // (the phase names are the reference's, main.cpp:452-470; the FASTA itself may still be on its way)
     {
         Timed t("startup: table scan");
-        if (use_db) scan_kmc_db(devs, o, o.kmc_path); // main.cpp:482-500
+        if (use_reads) count_reads(devs, o, read_files); // MALVA:104-110 + main.cpp:482-500
+        else if (use_db) scan_kmc_db(devs, o, o.kmc_path); // main.cpp:482-500
         else scan_table(devs, o, table);
     }
     pelapsed("BF weights created");
