@@ -161,7 +161,10 @@ int mg_kmc_decode_records(mg_ctx *ctx, const void *records, size_t n, uint64_t f
  *   mg_reads_add         a chunk of WHOLE records, one byte outside ACGT (e.g. '\n') between two of them: no window crosses it.
  *                        Returns once the bytes are up (pinned buffers from mg_host_alloc make that a DMA); the device packs
  *                        the chunk (2 bits + 1 mask bit per base) and keeps it until mg_reads_finish.
- *   mg_reads_add_device  the same from a device buffer (asynchronous).
+ *   mg_reads_add_device  the same from a device buffer, asynchronously: the context's stream reads the buffer (packed in place
+ *                        when 4-byte aligned, else copied into a staging slot first), so the caller orders its writes to it
+ *                        before the call (e.g. a device synchronize, or work on the context's stream) and leaves it unchanged
+ *                        until mg_reads_finish (or mg_synchronize) returns.
  *   mg_reads_finish      count (passes whose pairs fit option reads_budget_mb, at least reads_passes of them), apply
  *                        min / max, scan the kept rows; *n_kept_out = rows kept.
  *   mg_reads_export      the kept rows (any order; only the gate's survivors, a subset of KMC's table): up to cap of them,

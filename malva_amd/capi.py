@@ -471,13 +471,18 @@ class Context:
         self._ck(self._L.mg_reads_finish(self.h, C.byref(n)))
         return n.value
 
-    def reads_export(self):
-        """-> (hi, lo, cnt) of the kept rows, any order"""
+    def reads_export(self, cap=None, with_total=False):
+        """-> (hi, lo, cnt) of the kept rows, any order: all of them, or the first `cap`; with_total adds the library's
+        count of all the kept rows"""
         n = C.c_uint64(0)
-        self._ck(self._L.mg_reads_export(self.h, None, None, None, 0, C.byref(n)))
-        hi, lo, cnt = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
-        self._ck(self._L.mg_reads_export(self.h, _p(hi), _p(lo), _p(cnt), n.value, C.byref(n)))
-        return hi, lo, cnt
+        if cap is None:
+            self._ck(self._L.mg_reads_export(self.h, None, None, None, 0, C.byref(n)))
+            cap = n.value
+        hi, lo, cnt = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+        self._ck(self._L.mg_reads_export(self.h, _p(hi), _p(lo), _p(cnt), cap, C.byref(n)))
+        m = min(cap, n.value)
+        out = (hi[:m], lo[:m], cnt[:m])
+        return out + (n.value,) if with_total else out
 
     def reads_stats(self):
         """-> (ms: pack, window + filter, file, reduce, scan; counts: bases, windows, survivors, passes, kept)"""

@@ -3,6 +3,7 @@ a FASTQ file that runs before any device is created."""
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 from malva_amd import capi
@@ -52,3 +53,55 @@ def test_reads_refused_beyond_packed_ref_k(tmp_path):
                         str(tmp_path / "none.vcf"), str(fq)], capture_output=True, text=True, timeout=60)
     assert r.returncode != 0
     assert "-r <= 64" in r.stderr, r.stderr
+
+
+def _random_records(rng, ref_k, n=300):
+    """reads with N runs, IUPAC codes, lower case, reverse-complement palindromes, repeats and records shorter than ref_k"""
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    recs = []
+    for _ in range(n):
+        s = bytearray(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=int(rng.integers(0, 3 * ref_k + 40))).tobytes())
+        for p in rng.integers(0, max(1, len(s)), size=int(rng.integers(0, 3))):
+            if len(s):
+                s[int(p)] = int(rng.choice(np.frombuffer(b"NRYKMSWBDHV", dtype=np.uint8)))
+        if len(s) and rng.random() < 0.3:
+            a = int(rng.integers(0, len(s)))
+            s[a:] = s[a:].lower()
+        recs.append(bytes(s))
+    for _ in range(20):                                             # palindromes: a window that is its own reverse complement
+        h = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=ref_k // 2 + 3).tobytes()
+        recs += [h + h.translate(comp)[::-1]] * int(rng.integers(1, 4))
+    recs += [recs[5]] * 7 + [recs[7].lower()] * 3
+    return [recs[i] for i in rng.permutation(len(recs))]
+
+
+@pytest.mark.parametrize("ref_k", [9, 17, 22, 32, 33, 43, 63, 64])
+def test_count_chunks_equals_standin(tmp_path, ref_k):
+    """count_chunks, the exact count the device counter is tested against, agrees with the plain stand-in (count_fastq) and
+    with the FASTA reader's count, over reads with N, IUPAC codes, lower case and palindromes"""
+    from oracle import kmc_standin
+    rng = np.random.default_rng(ref_k)
+    recs = _random_records(rng, ref_k)
+    fq, fa = tmp_path / "r.fq", tmp_path / "r.fa"
+    fq.write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)) for i, s in enumerate(recs)))
+    with open(fa, "wb") as fh:                                     # multi-line records, \r\n line ends, blank lines
+        for i, s in enumerate(recs):
+            fh.write(b">r%d some text\r\n" % i + b"".join(s[j:j + 50] + b"\r\n" for j in range(0, len(s), 50)) + b"\n" * (i % 2))
+    assert kmc_standin.read_fasta(str(fa)) == recs
+    n_windows = sum(1 for s in recs for p in range(len(s) - ref_k + 1) if all(c in b"ACGTacgt" for c in s[p:p + ref_k]))
+    chunks = [b"\n".join(recs[i:i + 37]) for i in range(0, len(recs), 37)]
+    for ci, cs in ((1, 2 ** 32 - 1), (2, 255), (3, 4), (1, 1)):
+        hi, lo, cnt, nw = kmc_standin.count_chunks(chunks, ref_k, ci, cs)
+        assert nw == n_windows
+        got = list(zip((bytes(r) for r in kmc_standin.decode_m(hi, lo, ref_k)), (int(c) for c in cnt)))
+        assert got == kmc_standin.count_fastq(str(fq), ref_k, ci, cs), (ci, cs)
+        assert got == kmc_standin.count_fasta(str(fa), ref_k, ci, cs), (ci, cs)
+    # a chunk boundary ends a run as a separator byte does
+    s = b"".join(recs).upper().replace(b"\n", b"")
+    for cut in (1, ref_k - 1, ref_k, len(s) // 2):
+        a = kmc_standin.count_chunks([s[:cut], s[cut:]], ref_k)
+        b = kmc_standin.count_chunks([s[:cut] + b"\n" + s[cut:]], ref_k)
+        assert all(np.array_equal(x, y) for x, y in zip(a[:3], b[:3])) and a[3] == b[3]
+    hi, lo, cnt, nw = kmc_standin.count_chunks([], ref_k)
+    assert hi.size == lo.size == cnt.size == nw == 0
+    assert kmc_standin.count_chunks([b"", b"\n", b"A" * (ref_k - 1)], ref_k)[3] == 0
