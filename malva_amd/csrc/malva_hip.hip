@@ -1254,16 +1254,6 @@ u64 ticket_slices(mg_ctx *c) // slices of half the L2-resident size (2 MiB) the 
     const u32 word_shift = (u32)(c->pregate_log2 - 1 - 6);
     return (((c->bf[MG_BF_ALT].n_gate_bits + 63) / 64) + (1ULL << word_shift) - 1) >> word_shift;
 }
-// does this index take the ticket form?  *row_bits = bits of a ticket left for the row number (rows per launch group = 2^row_bits)
-bool ticket_form(mg_ctx *c, u32 *row_bits)
-{
-    const BFState &alt = c->bf[MG_BF_ALT];
-    const u64 TP = ticket_slices(c);
-    u32 idx_bits = 1;
-    while (idx_bits < 64 && (alt.size - 1) >> idx_bits) ++idx_bits;
-    *row_bits = std::min<u32>(27, 64 - idx_bits);
-    return c->use_summary && c->use_tickets && alt.gate && c->gate_log2 >= c->ticket_min_log2 && TP >= 2 && TP <= (u64)TK_MAXP && idx_bits <= 44;
-}
 // segments, staging and meta block for launch groups of up to `cap` rows
 int ticket_layout(mg_ctx *c, u64 cap, u32 row_bits, TicketSet *out)
 {
@@ -1287,6 +1277,30 @@ int ticket_layout(mg_ctx *c, u64 cap, u32 row_bits, TicketSet *out)
     *out = tks;
     return MG_OK;
 }
+// the partition form: the coarse gate's survivors binned by fine-gate slice, in segments for launch groups of up to `cap` rows
+int bin_layout(mg_ctx *c, u64 cap, BinSet *out)
+{
+    BinSet bins{};
+    const u64 P = ticket_slices(c);
+    bins.nbins = (u32)P;
+    bins.word_shift = (u32)(c->pregate_log2 - 1 - 6);
+    bins.nseg = (u32)std::min<u64>((cap + 2 * TPB - 1) / (2 * TPB), BIN_SEGS);
+    // 1.5x an even share of the worst case (every row passes the coarse gate)
+    bins.segcap = c->bin_cap ? c->bin_cap : ((cap / P / bins.nseg) * 3 / 2 + 256 + 63) / 64 * 64; // line-aligned segments
+    bins.ring = 64;
+    while (bins.ring < 256 && bins.ring * 2 * P <= BIN_LDS_ROWS) bins.ring *= 2;
+    if (c->bin_ring && (u64)c->bin_ring * P <= BIN_LDS_ROWS) bins.ring = (u32)c->bin_ring;
+    void *q[6];
+    for (int i = 0; i < 3; ++i) TRY(scratch(c, c->s_bin[i], P * bins.nseg * bins.segcap * (i == 2 ? 4 : 8), &q[i]));
+    for (int i = 0; i < 3; ++i) TRY(scratch(c, c->s_spill[i], cap * (i == 2 ? 4 : 8), &q[3 + i]));
+    bins.rows = RowList{(u64 *)q[0], (u64 *)q[1], (u32 *)q[2]};
+    bins.spill = RowList{(u64 *)q[3], (u64 *)q[4], (u32 *)q[5]};
+    if (!c->d_bin_meta) HIP_TRY(c, hipMalloc(&c->d_bin_meta, 8 + (size_t)BIN_MAXP * BIN_SEGS * 4));
+    bins.spill_count = c->d_bin_meta;
+    bins.counts = (u32 *)(c->d_bin_meta + 1);
+    *out = bins;
+    return MG_OK;
+}
 // ---- the sub-slice form's host side ---------------------------------------------------------------------------------------
 constexpr int SCAN_EV_CHUNKS = 64; // launch groups of one scan whose kernels are timed (mg_scan_stats)
 int device_cus(mg_ctx *c)
@@ -1303,26 +1317,9 @@ u64 sub_bins(const mg_ctx *c) // LDS-sized pieces (2^sub_words_log2 words) the f
     const u64 nwords = (c->bf[MG_BF_ALT].n_gate_bits + 63) / 64;
     return (nwords + (1ULL << c->sub_words_log2) - 1) >> c->sub_words_log2;
 }
-// does this index take the sub-slice form?  *row_bits as in ticket_form
-bool sub_form(mg_ctx *c, u32 *row_bits)
-{
-    const BFState &alt = c->bf[MG_BF_ALT];
-    u32 idx_bits = 1;
-    while (idx_bits < 64 && (alt.size - 1) >> idx_bits) ++idx_bits;
-    *row_bits = std::min<u32>(27, 64 - idx_bits);
-    const u64 NB = sub_bins(c);
-    return c->use_summary && c->use_sub && alt.gate && c->gate_log2 >= c->sub_min_log2 && NB >= 2 && NB <= (u64)SB_MAXB && idx_bits <= 44 &&
-           c->sub_words_log2 >= 0 && c->sub_words_log2 <= SB_WORDS_LOG2;
-}
-// what one launch group of the sub-slice form works in: pass one / two's segments and regions, the probe kernel's hit regions
-struct SubPlan {
-    SubSet ss{};
-    u32 split = 1;
-};
 // segments, regions and meta block for launch groups of up to `cap` rows
-int sub_layout(mg_ctx *c, u64 cap, u32 row_bits, SubPlan *plan)
+int sub_layout(mg_ctx *c, u64 cap, u32 row_bits, SubSet *out)
 {
-    SubSet *out = &plan->ss;
     const BFState &alt = c->bf[MG_BF_ALT];
     SubSet ss{};
     const u64 NB = sub_bins(c);
@@ -1339,7 +1336,6 @@ int sub_layout(mg_ctx *c, u64 cap, u32 row_bits, SubPlan *plan)
     ss.parts = (u32)std::max<u64>(1, std::min<u64>(std::min<u64>(8, ss.nseg), (u64)cus / NB)); // bins fewer than CUs: several workgroups share one
     const u64 spp = (ss.nseg + ss.parts - 1) / ss.parts, units = NB * ss.parts;
     ss.ucap = spp * ss.segcap;
-    plan->split = (u32)std::max(1, c->sub_split);
     void *q[4];
     TRY(scratch(c, c->s_sb[0], NB * ss.nseg * ss.segcap * 8, &q[0]));
     TRY(scratch(c, c->s_sb[1], cap * 8, &q[1]));
@@ -1358,55 +1354,91 @@ int sub_layout(mg_ctx *c, u64 cap, u32 row_bits, SubPlan *plan)
 }
 // bytes of the meta block's head that every launch group starts from zero: the spill count and the regions' counts
 size_t sub_meta_head(const SubSet &ss) { return 8 + ((size_t)ss.nbins * ss.parts + 1) * 4; }
-// the four events of launch group `chunk` of the running scan (created on first use); nullptr beyond SCAN_EV_CHUNKS
+// ---- one scan's plan ------------------------------------------------------------------------------------------------------
+// the table a scan walks: the SoA arrays (hi, lo, cnt) or, when `rows12` is set, the compact 12-byte rows
+struct ScanTable {
+    const u64 *hi = nullptr, *lo = nullptr;
+    const u32 *cnt = nullptr, *rows12 = nullptr;
+    ScanTable from(u64 r0) const // the table from row r0 on (compact rows: r0 is a multiple of 4, a quad of rows is three 16-byte words)
+    {
+        return rows12 ? ScanTable{nullptr, nullptr, nullptr, rows12 + r0 / 4 * 12} : ScanTable{hi + r0, lo + r0, cnt + r0, nullptr};
+    }
+};
+enum class ScanForm { direct, bins, tickets, subs };
+// the form a scan takes, its rows per launch group, its two row lists and the form's layout
+struct ScanPlan {
+    ScanForm form = ScanForm::direct;
+    u64 chunk = 0;
+    RowList open{}, hits{};
+    BinSet bins{};
+    TicketSet tks{};
+    SubSet subs{};
+};
+// The first form that fits the index: sub-slices of the gate answered out of LDS (whole-genome index), 2 MiB slices walked out
+// of L2 (tickets), the coarse gate's survivors binned by slice (partition: SoA tables only), else the filter kernel alone.
+int scan_plan(mg_ctx *c, u64 n, bool rows12, ScanPlan *out)
+{
+    ScanPlan p{};
+    const BFState &alt = c->bf[MG_BF_ALT];
+    u32 idx_bits = 1; // a ticket holds a filter index and the row number: rows per launch group = 2^row_bits
+    while (idx_bits < 64 && (alt.size - 1) >> idx_bits) ++idx_bits;
+    const u32 row_bits = std::min<u32>(27, 64 - idx_bits);
+    const bool two_pass = c->use_summary && alt.gate && idx_bits <= 44;
+    const u64 NB = sub_bins(c), TP = ticket_slices(c);
+    if (two_pass && c->use_sub && c->gate_log2 >= c->sub_min_log2 && NB >= 2 && NB <= (u64)SB_MAXB && c->sub_words_log2 >= 0 &&
+        c->sub_words_log2 <= SB_WORDS_LOG2)
+        p.form = ScanForm::subs;
+    else if (two_pass && c->use_tickets && c->gate_log2 >= c->ticket_min_log2 && TP >= 2 && TP <= (u64)TK_MAXP)
+        p.form = ScanForm::tickets;
+    else if (!rows12 && alt.pregate && pregate_on(c) && c->use_summary && c->use_pregate && c->use_partition && TP >= 2 && TP <= BIN_MAXP)
+        p.form = ScanForm::bins;
+    const bool ticketed = p.form == ScanForm::tickets || p.form == ScanForm::subs;
+    p.chunk = 1ULL << std::min<u32>(ticketed ? row_bits : 27, (u32)c->chunk_log2); // (bounds the two lists' worst-case size)
+    if (rows12) p.chunk = std::max<u64>(4, p.chunk); // (a multiple of 4 rows: chunks start on whole quads)
+    const u64 cap = n < p.chunk ? n : p.chunk; // worst case (gate disabled): every row is listed
+    void *q[6];
+    Scratch *sc[6] = {&c->s_open[0], &c->s_open[1], &c->s_open[2], &c->s_hit[0], &c->s_hit[1], &c->s_hit[2]};
+    for (int i = 0; i < 6; ++i) TRY(scratch(c, *sc[i], cap * (i % 3 == 2 ? 4 : 8), &q[i]));
+    p.open = RowList{(u64 *)q[0], (u64 *)q[1], (u32 *)q[2]};
+    p.hits = RowList{(u64 *)q[3], (u64 *)q[4], (u32 *)q[5]};
+    if (c->use_hit_entries && c->map.cap_log2 <= 30) { // (record * 2 + entry in 32 bits)
+        void *pa;
+        TRY(scratch(c, c->s_hit[3], cap * 8, &pa));
+        p.hits.aux = (u64 *)pa;
+    }
+    if (p.form == ScanForm::tickets) TRY(ticket_layout(c, cap, row_bits, &p.tks));
+    if (p.form == ScanForm::subs) TRY(sub_layout(c, cap, row_bits, &p.subs));
+    if (p.form == ScanForm::bins) TRY(bin_layout(c, cap, &p.bins));
+    *out = p;
+    return MG_OK;
+}
+// the four events of launch group `chunk` of the running scan (created on first use); nullptr beyond SCAN_EV_CHUNKS, and from the
+// first group whose events could not be made on (ev_rows only ever lists groups with all four events)
 hipEvent_t *scan_events(mg_ctx *c, u64 chunk, u64 rows)
 {
-    if (chunk >= (u64)SCAN_EV_CHUNKS) return nullptr;
+    if (chunk >= (u64)SCAN_EV_CHUNKS || chunk != c->ev_rows.size()) return nullptr;
     while (c->ev.size() < 4 * (chunk + 1)) {
         hipEvent_t e = nullptr;
         if (hipEventCreate(&e) != hipSuccess) return nullptr;
         c->ev.push_back(e);
     }
-    if (c->ev_rows.size() <= chunk) c->ev_rows.resize(chunk + 1);
-    c->ev_rows[chunk] = rows;
+    c->ev_rows.push_back(rows);
     return c->ev.data() + 4 * chunk;
 }
+// ---- one launch group ------------------------------------------------------------------------------------------------------
 template <int KC, int RC>
 void launch_sub_passes(mg_ctx *c, const u64 *d_hi, const u64 *d_lo, const u32 *rows12, u64 n, const SubSet &layout)
 {
     SubSet ss = layout;
     ss.nseg = (u32)std::min<u64>((n + SB_TILE - 1) / SB_TILE, layout.nseg); // (regions and segments stay as laid out: a smaller grid fills fewer of them)
     const BFView alt = view(c, MG_BF_ALT);
-if (rows12) hipLaunchKernelGGL((scan_sub_sort_kernel<KC, RC, true>), dim3(ss.nseg), dim3(SB_TPB), 0, c->stream, d_hi, d_lo, rows12, n, (int)c->k, (int)c->ref_k, alt, ss);
+    if (rows12) hipLaunchKernelGGL((scan_sub_sort_kernel<KC, RC, true>), dim3(ss.nseg), dim3(SB_TPB), 0, c->stream, d_hi, d_lo, rows12, n, (int)c->k, (int)c->ref_k, alt, ss);
     else hipLaunchKernelGGL((scan_sub_sort_kernel<KC, RC, false>), dim3(ss.nseg), dim3(SB_TPB), 0, c->stream, d_hi, d_lo, rows12, n, (int)c->k, (int)c->ref_k, alt, ss);
     const unsigned units = ss.nbins * ss.parts;
     const unsigned grid = std::min<unsigned>(units, (unsigned)device_cus(c));
     if (c->gate_k == 4) hipLaunchKernelGGL(scan_sub_gate_kernel<4>, dim3(grid), dim3(SB_TPB), 0, c->stream, alt, ss);
     else hipLaunchKernelGGL(scan_sub_gate_kernel<0>, dim3(grid), dim3(SB_TPB), 0, c->stream, alt, ss);
     hipLaunchKernelGGL(sub_total_kernel, dim3(1), dim3(SB_TPB), 0, c->stream, (const u32 *)ss.out_counts, units + 1, c->d_hit_count);
-}
-SubOpen sub_open(const SubPlan *plan)
-{
-    SubOpen r{};
-    const SubSet *ss = &plan->ss;
-    r.counts = ss->out_counts;
-    r.tickets = ss->out_tk;
-    r.ucap = ss->ucap;
-    r.n_units = ss->nbins * ss->parts + 1;
-    r.split = plan->split;
-    r.row_bits = ss->row_bits;
-    return r;
-}
-// the probe kernel of the sub-slice form (which is its hit pass too) over one launch group (ev: its four events, or NULL)
-template <int KC, int RC>
-void launch_sub_tail(mg_ctx *c, const SubPlan *plan, hipEvent_t *ev, const u32 *d_cnt, const u64 *d_hi, const u64 *d_lo, const u32 *rows12)
-{
-    const SubOpen so = sub_open(plan);
-    const unsigned pgrid = std::min<unsigned>(so.n_units * so.split, 2 * (unsigned)c->probe_grid);
-    hipLaunchKernelGGL((scan_sub_probe_kernel<KC, RC>), dim3(pgrid), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), view(c, MG_BF_CTX), view(c), so,
-                       c->d_hit_count, d_cnt, d_hi, d_lo, rows12);
-    if (ev) hipEventRecord(ev[2], c->stream);
-    if (ev) hipEventRecord(ev[3], c->stream);
 }
 template <int KC, int RC, int ROWS, int VAR>
 void launch_filter_var(mg_ctx *c, const u64 *d_hi, const u64 *d_lo, const u32 *d_cnt, u64 n, RowList open)
@@ -1434,56 +1466,114 @@ void launch_ticket_passes(mg_ctx *c, const u64 *d_hi, const u64 *d_lo, const u32
     ts.nseg = (u32)std::min<u64>((n + 4 * TPB - 1) / (4 * TPB), layout.nseg);
     hipLaunchKernelGGL((scan_ticket_sort_kernel<KC, RC>), dim3(ts.nseg), dim3(TPB), 0, c->stream, d_hi, d_lo, rows12, n, (int)c->k, (int)c->ref_k,
                        view(c, MG_BF_ALT), ts);
-    if (!c->tkg_grid) { // pass two walks the slices in step: one workgroup per CU, all resident together
-        int cus = 0, dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        c->tkg_grid = std::max(8, cus / 8 * 8);
-    }
+    if (!c->tkg_grid) c->tkg_grid = std::max(8, device_cus(c) / 8 * 8); // pass two walks the slices in step: one workgroup per CU, all resident together
     if (c->gate_k == 4)
         hipLaunchKernelGGL(scan_ticket_gate_kernel<4>, dim3(c->tkg_grid), dim3(TKG_TPB), 0, c->stream, view(c, MG_BF_ALT), ts, open.cnt, c->d_hit_count);
     else
         hipLaunchKernelGGL(scan_ticket_gate_kernel<0>, dim3(c->tkg_grid), dim3(TKG_TPB), 0, c->stream, view(c, MG_BF_ALT), ts, open.cnt, c->d_hit_count);
 }
+constexpr u32 ROWS12_MAX_R = 44; // compact rows hold a ref_k-mer of 33..44 bases and a count of 96 - 2 ref_k bits
+int rows12_ok(mg_ctx *c)
+{
+    if (c->ref_k < 33 || c->ref_k > ROWS12_MAX_R)
+        return fail(c, MG_ERR_LIMIT, "packed 12-byte rows hold a ref_k-mer of 33..44 bases and a count of 96 - 2 ref_k bits (ref_k = %u): use the SoA table", c->ref_k);
+    return MG_OK;
+}
+// One launch group of a scan: its form's passes, then (but for the sub-slice form, whose probe kernel is its hit pass too) the
+// probe and hit kernels over the two row lists.  ev: the group's four events, or NULL.
 template <int KC, int RC>
-void launch_scan_chunk(mg_ctx *c, const u64 *d_hi, const u64 *d_lo, const u32 *d_cnt, u64 n, RowList open, RowList hits, hipEvent_t *ev,
-                       const BinSet *bins, const TicketSet *tickets, const SubPlan *subs)
+void launch_scan_chunk(mg_ctx *c, const ScanTable &t, u64 n, const ScanPlan &p, hipEvent_t *ev)
 {
     if (ev) hipEventRecord(ev[0], c->stream);
-    if (subs) { // whole-genome index: tickets filed by LDS-sized sub-slice of the gate, then each sub-slice answered out of LDS
-        launch_sub_passes<KC, RC>(c, d_hi, d_lo, nullptr, n, subs->ss);
+    switch (p.form) {
+    case ScanForm::subs: { // whole-genome index: tickets filed by LDS-sized sub-slice of the gate, then each sub-slice answered out of LDS
+        launch_sub_passes<KC, RC>(c, t.hi, t.lo, t.rows12, n, p.subs);
         if (ev) hipEventRecord(ev[1], c->stream);
-        launch_sub_tail<KC, RC>(c, subs, ev, d_cnt, d_hi, d_lo, nullptr); // regions of surviving tickets: the record first, the table row where the record asks for it
+        // regions of surviving tickets: the record first, the table row where the record asks for it
+        const SubSet &ss = p.subs;
+        const SubOpen so{ss.out_counts, ss.out_tk, ss.ucap, ss.nbins * ss.parts + 1, (u32)std::max(1, c->sub_split), ss.row_bits};
+        const unsigned pgrid = std::min<unsigned>(so.n_units * so.split, 2 * (unsigned)c->probe_grid);
+        hipLaunchKernelGGL((scan_sub_probe_kernel<KC, RC>), dim3(pgrid), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), view(c, MG_BF_CTX), view(c), so,
+                           c->d_hit_count, t.cnt, t.hi, t.lo, t.rows12);
+        if (ev) hipEventRecord(ev[2], c->stream);
+        if (ev) hipEventRecord(ev[3], c->stream);
         return;
-    } else if (tickets) { // the same with 2 MiB slices walked out of L2
-        launch_ticket_passes<KC, RC>(c, d_hi, d_lo, nullptr, n, *tickets, open);
-    } else if (bins) { // large index: coarse gate + binning, then the fine gate slice by slice
-        BinSet bs = *bins; // the last chunk may need fewer workgroups than segments were laid out for
-        bs.nseg = (u32)std::min<u64>((n + 2 * TPB - 1) / (2 * TPB), bins->nseg);
-        bins = &bs;
+    }
+    case ScanForm::tickets: // the same with 2 MiB slices walked out of L2; the open list holds row numbers
+        launch_ticket_passes<KC, RC>(c, t.hi, t.lo, t.rows12, n, p.tks, p.open);
+        break;
+    case ScanForm::bins: { // large index: coarse gate + binning, then the fine gate slice by slice
+        BinSet bs = p.bins; // the last chunk may need fewer workgroups than segments were laid out for
+        bs.nseg = (u32)std::min<u64>((n + 2 * TPB - 1) / (2 * TPB), p.bins.nseg);
         if (c->bin_rows == 4)
-            hipLaunchKernelGGL((scan_bin_kernel<KC, RC, 4>), dim3(bs.nseg), dim3(TPB), (size_t)bs.nbins * bs.ring * 20, c->stream, d_hi, d_lo, d_cnt, n,
-                               (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), *bins, c->scan_ablate);
+            hipLaunchKernelGGL((scan_bin_kernel<KC, RC, 4>), dim3(bs.nseg), dim3(TPB), (size_t)bs.nbins * bs.ring * 20, c->stream, t.hi, t.lo, t.cnt, n,
+                               (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), bs, c->scan_ablate);
         else
-            hipLaunchKernelGGL((scan_bin_kernel<KC, RC, 2>), dim3(bs.nseg), dim3(TPB), (size_t)bs.nbins * bs.ring * 20, c->stream, d_hi, d_lo, d_cnt, n,
-                               (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), *bins, c->scan_ablate);
+            hipLaunchKernelGGL((scan_bin_kernel<KC, RC, 2>), dim3(bs.nseg), dim3(TPB), (size_t)bs.nbins * bs.ring * 20, c->stream, t.hi, t.lo, t.cnt, n,
+                               (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), bs, c->scan_ablate);
         hipLaunchKernelGGL((scan_bin_gate_kernel<KC, RC>), dim3(2048), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT),
-                           *bins, open, c->d_hit_count);
-    } else
-        switch (c->scan_rows) {
-        case 1: launch_filter_rows<KC, RC, 1>(c, d_hi, d_lo, d_cnt, n, open); break;
-        case 4: launch_filter_rows<KC, RC, 4>(c, d_hi, d_lo, d_cnt, n, open); break;
-        default: launch_filter_rows<KC, RC, 2>(c, d_hi, d_lo, d_cnt, n, open); break;
-        }
+                           bs, p.open, c->d_hit_count);
+        break;
+    }
+    case ScanForm::direct:
+        if (t.rows12) {
+            if constexpr (RC <= (int)ROWS12_MAX_R) { // (no compact-row instance for a longer fixed ref_k: rows12_ok keeps those tables out)
+                const unsigned fgrid = (unsigned)std::min<u64>(((n + 1) / 2 + TPB - 1) / TPB, (u64)c->scan_grid);
+                hipLaunchKernelGGL((scan_filter12_kernel<KC, RC>), dim3(fgrid), dim3(TPB), 0, c->stream, t.rows12, n, (int)c->k, (int)c->ref_k,
+                                   view(c, MG_BF_ALT), p.open, c->d_hit_count, c->scan_ablate);
+            }
+        } else
+            switch (c->scan_rows) {
+            case 1: launch_filter_rows<KC, RC, 1>(c, t.hi, t.lo, t.cnt, n, p.open); break;
+            case 4: launch_filter_rows<KC, RC, 4>(c, t.hi, t.lo, t.cnt, n, p.open); break;
+            default: launch_filter_rows<KC, RC, 2>(c, t.hi, t.lo, t.cnt, n, p.open); break;
+            }
+        break;
+    }
     if (ev) hipEventRecord(ev[1], c->stream);
-    // the list lengths live on the device; fixed grids walk them with a stride, so no host round trip
+    // the list lengths live on the device; fixed grids walk them with a stride, so no host round trip.  The lists hold the rows, but for
+    // the direct form over SoA arrays (the row's index: the probe fetches its count) and the ticket form (row numbers: it fetches the row)
+    const bool tk = p.form == ScanForm::tickets;
     const unsigned grid = (unsigned)std::min<u64>(nblocks(n), (u64)c->probe_grid);
-    hipLaunchKernelGGL((scan_probe_kernel<KC, RC>), dim3(grid), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), view(c), open, hits, c->d_hit_count,
-                       bins && !tickets ? (const u32 *)nullptr : d_cnt, tickets ? d_hi : (const u64 *)nullptr, tickets ? d_lo : (const u64 *)nullptr, (const u32 *)nullptr);
+    hipLaunchKernelGGL((scan_probe_kernel<KC, RC>), dim3(grid), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), view(c), p.open, p.hits,
+                       c->d_hit_count, p.form == ScanForm::bins ? nullptr : t.cnt, tk ? t.hi : nullptr, tk ? t.lo : nullptr, tk ? t.rows12 : nullptr);
     if (ev) hipEventRecord(ev[2], c->stream);
     hipLaunchKernelGGL((scan_hits_kernel<KC, RC>), dim3(std::min(grid, (unsigned)c->hits_grid)), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k,
-                       view(c, MG_BF_ALT), view(c, MG_BF_CTX), view(c), hits, c->d_hit_count);
+                       view(c, MG_BF_ALT), view(c, MG_BF_CTX), view(c), p.hits, c->d_hit_count);
     if (ev) hipEventRecord(ev[3], c->stream);
+}
+// A scan of a device-resident table (after the entry point's argument checks), in launch groups of plan.chunk rows
+int scan_table(mg_ctx *c, const ScanTable &t, u64 n)
+{
+    if (!c->map.slots) TRY(map_reserve(c, 0));
+    TRY(ctx_set_ready(c));
+    TRY(records_current(c));
+    c->stats_valid = false;
+    c->ev_rows.clear();
+    ScanPlan p;
+    TRY(scan_plan(c, n, t.rows12 != nullptr, &p));
+    HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 32, c->stream));
+    for (u64 r0 = 0; r0 < n; r0 += p.chunk) {
+        const u64 nr = n - r0 < p.chunk ? n - r0 : p.chunk;
+        if (r0) HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 16, c->stream));
+        if (p.form == ScanForm::bins) HIP_TRY(c, hipMemsetAsync(c->d_bin_meta, 0, 8, c->stream));
+        if (p.form == ScanForm::tickets) HIP_TRY(c, hipMemsetAsync(c->d_tk_meta, 0, TK_META_HEAD, c->stream));
+        if (p.form == ScanForm::subs) HIP_TRY(c, hipMemsetAsync(p.subs.spill_count, 0, sub_meta_head(p.subs), c->stream));
+        hipEvent_t *ev = scan_events(c, r0 / p.chunk, nr);
+        const ScanTable tc = t.from(r0);
+        // the reference's defaults (k35 r43, argument_parser.hpp:57-58) and config C5 (k35 r63: SoA tables only) get fixed-length hashing
+        if (c->k == 35 && c->ref_k == 43) launch_scan_chunk<35, 43>(c, tc, nr, p, ev);
+        else if (c->k == 35 && c->ref_k == 63) launch_scan_chunk<35, 63>(c, tc, nr, p, ev);
+        else launch_scan_chunk<0, 0>(c, tc, nr, p, ev);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->last_bins = p.form == ScanForm::bins ? (int)p.bins.nbins : 0;
+    c->last_tickets = p.form == ScanForm::tickets ? (int)p.tks.nbins : 0;
+    c->last_subs = p.form == ScanForm::subs ? (int)p.subs.nbins : 0;
+    if (p.form == ScanForm::subs && view(c).lazy) c->vec_stale = true; // (the records' copies are ahead of the vectors now)
+    else c->vec_zero = false;
+    c->stats_valid = true;
+    return MG_OK;
 }
 } // namespace
 
@@ -1496,114 +1586,10 @@ MG_EXPORT int mg_kmc_scan_device(mg_ctx *c, const void *d_hi, const void *d_lo, 
         return fail(c, MG_ERR_LIMIT, "packed scan supports k <= ref_k <= 64 (k=%u ref_k=%u)", c->k, c->ref_k);
     if (n == 0) return MG_OK;
     if (!d_hi || !d_lo || !d_cnt) return fail(c, MG_ERR_ARG, "NULL table pointer");
-    if (!c->map.slots) TRY(map_reserve(c, 0));
-    TRY(ctx_set_ready(c));
-    TRY(records_current(c));
-    // large index: tickets by gate slice (takes precedence over the row-moving partition below)
-    const BFState &alt = c->bf[MG_BF_ALT];
-    const u32 word_shift = (u32)(c->pregate_log2 - 1 - 6); // slices of half the L2-resident size: 2 MiB
-    u32 row_bits = 27;
-    const bool subs = sub_form(c, &row_bits);
-    const bool tickets = !subs && ticket_form(c, &row_bits);
-    const u64 TP = ticket_slices(c);
-    const u64 chunk = 1ULL << std::min<u32>(tickets || subs ? row_bits : 27, (u32)c->chunk_log2); // rows per launch group (bounds the two lists' worst-case size; a ticket holds the row number)
-    const u64 cap = n < chunk ? n : chunk; // worst case (gate disabled): every row is listed
-    void *p[6];
-    Scratch *sc[6] = {&c->s_open[0], &c->s_open[1], &c->s_open[2], &c->s_hit[0], &c->s_hit[1], &c->s_hit[2]};
-    for (int i = 0; i < 6; ++i) TRY(scratch(c, *sc[i], cap * (i % 3 == 2 ? 4 : 8), &p[i]));
-    RowList open{(u64 *)p[0], (u64 *)p[1], (u32 *)p[2]}, hits{(u64 *)p[3], (u64 *)p[4], (u32 *)p[5]};
-    if (c->use_hit_entries && c->map.cap_log2 <= 30) { // (record * 2 + entry in 32 bits)
-        void *pa;
-        TRY(scratch(c, c->s_hit[3], cap * 8, &pa));
-        hits.aux = (u64 *)pa;
-    }
-    c->stats_valid = false;
-    // partitioned second level: two-level gate in use and the fine gate splits into 2..BIN_MAXP slices of half the coarse gate's size
-    BinSet bins{};
-    TicketSet tks{};
-    SubPlan sbs{};
-    if (tickets) TRY(ticket_layout(c, cap, row_bits, &tks));
-    if (subs) TRY(sub_layout(c, cap, row_bits, &sbs));
-    const u64 P = !tickets && !subs && alt.pregate && pregate_on(c) ? (((alt.n_gate_bits + 63) / 64 + (1ULL << word_shift) - 1) >> word_shift) : 0;
-    const bool partition = c->use_summary && c->use_pregate && c->use_partition && P >= 2 && P <= BIN_MAXP;
-    if (partition) {
-        bins.nbins = (u32)P;
-        bins.word_shift = word_shift;
-        bins.nseg = (u32)std::min<u64>((cap + 2 * TPB - 1) / (2 * TPB), BIN_SEGS);
-        // 1.5x an even share of the worst case (every row passes the coarse gate)
-        bins.segcap = c->bin_cap ? c->bin_cap : ((cap / P / bins.nseg) * 3 / 2 + 256 + 63) / 64 * 64; // line-aligned segments
-        bins.ring = 64;
-        while (bins.ring < 256 && bins.ring * 2 * P <= BIN_LDS_ROWS) bins.ring *= 2;
-        if (c->bin_ring && (u64)c->bin_ring * P <= BIN_LDS_ROWS) bins.ring = (u32)c->bin_ring;
-        void *q[6];
-        for (int i = 0; i < 3; ++i) TRY(scratch(c, c->s_bin[i], P * bins.nseg * bins.segcap * (i == 2 ? 4 : 8), &q[i]));
-        for (int i = 0; i < 3; ++i) TRY(scratch(c, c->s_spill[i], cap * (i == 2 ? 4 : 8), &q[3 + i]));
-        bins.rows = RowList{(u64 *)q[0], (u64 *)q[1], (u32 *)q[2]};
-        bins.spill = RowList{(u64 *)q[3], (u64 *)q[4], (u32 *)q[5]};
-        if (!c->d_bin_meta) HIP_TRY(c, hipMalloc(&c->d_bin_meta, 8 + (size_t)BIN_MAXP * BIN_SEGS * 4));
-        bins.spill_count = c->d_bin_meta;
-        bins.counts = (u32 *)(c->d_bin_meta + 1);
-    }
-    HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 32, c->stream));
-    for (u64 r0 = 0; r0 < n; r0 += chunk) {
-        const u64 nr = n - r0 < chunk ? n - r0 : chunk;
-        const u64 *ph = (const u64 *)d_hi + r0, *pl = (const u64 *)d_lo + r0;
-        const u32 *pc = (const u32 *)d_cnt + r0;
-        if (r0) HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 16, c->stream));
-        if (partition) HIP_TRY(c, hipMemsetAsync(c->d_bin_meta, 0, 8, c->stream));
-        if (tickets) HIP_TRY(c, hipMemsetAsync(c->d_tk_meta, 0, TK_META_HEAD, c->stream));
-        if (subs) HIP_TRY(c, hipMemsetAsync(sbs.ss.spill_count, 0, sub_meta_head(sbs.ss), c->stream));
-        hipEvent_t *ev = scan_events(c, r0 / chunk, nr);
-        // the reference's defaults (k35 r43, argument_parser.hpp:57-58) and config C5 (k35 r63) get fixed-length hashing
-        if (c->k == 35 && c->ref_k == 43) launch_scan_chunk<35, 43>(c, ph, pl, pc, nr, open, hits, ev, partition ? &bins : nullptr, tickets ? &tks : nullptr, subs ? &sbs : nullptr);
-        else if (c->k == 35 && c->ref_k == 63) launch_scan_chunk<35, 63>(c, ph, pl, pc, nr, open, hits, ev, partition ? &bins : nullptr, tickets ? &tks : nullptr, subs ? &sbs : nullptr);
-        else launch_scan_chunk<0, 0>(c, ph, pl, pc, nr, open, hits, ev, partition ? &bins : nullptr, tickets ? &tks : nullptr, subs ? &sbs : nullptr);
-        HIP_TRY(c, hipGetLastError());
-    }
-    c->ev_rows.resize(std::min<u64>((n + chunk - 1) / chunk, (u64)SCAN_EV_CHUNKS));
-    c->last_bins = partition ? (int)P : 0;
-    c->last_tickets = tickets ? (int)TP : 0;
-    c->last_subs = subs ? (int)sbs.ss.nbins : 0;
-    if (subs && view(c).lazy) c->vec_stale = true; // (the records' copies are ahead of the vectors now)
-    else c->vec_zero = false;
-    c->stats_valid = true;
-    return MG_OK;
+    return scan_table(c, ScanTable{(const u64 *)d_hi, (const u64 *)d_lo, (const u32 *)d_cnt, nullptr}, n);
 }
 
 // ---- compact (12-byte) table rows --------------------------------------------------------------------------------
-namespace {
-template <int KC, int RC>
-void launch_rows12_chunk(mg_ctx *c, const uint4 *rows, u64 n, RowList open, RowList hits, hipEvent_t *ev, const TicketSet *tickets, const SubPlan *subs)
-{
-    if (ev) hipEventRecord(ev[0], c->stream);
-    if (subs) { // whole-genome index: tickets filed by LDS-sized sub-slice of the gate, each sub-slice then answered out of LDS; regions of tickets
-        launch_sub_passes<KC, RC>(c, nullptr, nullptr, (const u32 *)rows, n, subs->ss);
-        if (ev) hipEventRecord(ev[1], c->stream);
-        launch_sub_tail<KC, RC>(c, subs, ev, nullptr, nullptr, nullptr, (const u32 *)rows);
-        return;
-    } else if (tickets) // the same with 2 MiB slices walked out of L2; the open list holds row numbers
-        launch_ticket_passes<KC, RC>(c, nullptr, nullptr, (const u32 *)rows, n, *tickets, open);
-    else {
-        const unsigned fgrid = (unsigned)std::min<u64>(((n + 1) / 2 + TPB - 1) / TPB, (u64)c->scan_grid);
-        hipLaunchKernelGGL((scan_filter12_kernel<KC, RC>), dim3(fgrid), dim3(TPB), 0, c->stream, (const u32 *)rows, n, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT),
-                           open, c->d_hit_count, c->scan_ablate);
-    }
-    if (ev) hipEventRecord(ev[1], c->stream);
-    const unsigned grid = (unsigned)std::min<u64>(nblocks(n), (u64)c->probe_grid);
-    hipLaunchKernelGGL((scan_probe_kernel<KC, RC>), dim3(grid), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k, view(c, MG_BF_ALT), view(c), open, hits, c->d_hit_count,
-                       (const u32 *)nullptr, (const u64 *)nullptr, (const u64 *)nullptr, tickets ? (const u32 *)rows : (const u32 *)nullptr);
-    if (ev) hipEventRecord(ev[2], c->stream);
-    hipLaunchKernelGGL((scan_hits_kernel<KC, RC>), dim3(std::min(grid, (unsigned)c->hits_grid)), dim3(TPB), 0, c->stream, (int)c->k, (int)c->ref_k,
-                       view(c, MG_BF_ALT), view(c, MG_BF_CTX), view(c), hits, c->d_hit_count);
-    if (ev) hipEventRecord(ev[3], c->stream);
-}
-int rows12_ok(mg_ctx *c)
-{
-    if (c->ref_k < 33 || c->ref_k > 44)
-        return fail(c, MG_ERR_LIMIT, "packed 12-byte rows hold a ref_k-mer of 33..44 bases and a count of 96 - 2 ref_k bits (ref_k = %u): use the SoA table", c->ref_k);
-    return MG_OK;
-}
-} // namespace
 
 MG_EXPORT size_t mg_kmc_rows_bytes(size_t n) { return (n + 3) / 4 * 4 * 12; }
 
@@ -1634,48 +1620,7 @@ MG_EXPORT int mg_kmc_scan_rows_device(mg_ctx *c, const void *d_rows, size_t n)
     TRY(rows12_ok(c));
     if (n == 0) return MG_OK;
     if (!d_rows || ((uintptr_t)d_rows & 15)) return fail(c, MG_ERR_ARG, "packed rows must be 16-byte aligned");
-    if (!c->map.slots) TRY(map_reserve(c, 0));
-    TRY(ctx_set_ready(c));
-    TRY(records_current(c));
-    u32 row_bits = 27;
-    const bool subs = sub_form(c, &row_bits);
-    const bool tickets = !subs && ticket_form(c, &row_bits);
-    const u64 chunk = std::max<u64>(4, 1ULL << std::min<u32>(tickets || subs ? row_bits : 27, (u32)c->chunk_log2)); // (a multiple of 4 rows: chunks start on whole quads)
-    const u64 cap = n < chunk ? n : chunk;
-    void *p[6];
-    Scratch *sc[6] = {&c->s_open[0], &c->s_open[1], &c->s_open[2], &c->s_hit[0], &c->s_hit[1], &c->s_hit[2]};
-    for (int i = 0; i < 6; ++i) TRY(scratch(c, *sc[i], cap * (i % 3 == 2 ? 4 : 8), &p[i]));
-    RowList open{(u64 *)p[0], (u64 *)p[1], (u32 *)p[2]}, hits{(u64 *)p[3], (u64 *)p[4], (u32 *)p[5]};
-    if (c->use_hit_entries && c->map.cap_log2 <= 30) { // (record * 2 + entry in 32 bits)
-        void *pa;
-        TRY(scratch(c, c->s_hit[3], cap * 8, &pa));
-        hits.aux = (u64 *)pa;
-    }
-    TicketSet tks{};
-    SubPlan sbs{};
-    if (tickets) TRY(ticket_layout(c, cap, row_bits, &tks));
-    if (subs) TRY(sub_layout(c, cap, row_bits, &sbs));
-    c->stats_valid = false;
-    HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 32, c->stream));
-    for (u64 r0 = 0; r0 < n; r0 += chunk) {
-        const u64 nr = n - r0 < chunk ? n - r0 : chunk;
-        const uint4 *pr = (const uint4 *)d_rows + r0 / 4 * 3;
-        if (r0) HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 16, c->stream));
-        if (tickets) HIP_TRY(c, hipMemsetAsync(c->d_tk_meta, 0, TK_META_HEAD, c->stream));
-        if (subs) HIP_TRY(c, hipMemsetAsync(sbs.ss.spill_count, 0, sub_meta_head(sbs.ss), c->stream));
-        hipEvent_t *ev = scan_events(c, r0 / chunk, nr);
-        if (c->k == 35 && c->ref_k == 43) launch_rows12_chunk<35, 43>(c, pr, nr, open, hits, ev, tickets ? &tks : nullptr, subs ? &sbs : nullptr);
-        else launch_rows12_chunk<0, 0>(c, pr, nr, open, hits, ev, tickets ? &tks : nullptr, subs ? &sbs : nullptr);
-        HIP_TRY(c, hipGetLastError());
-    }
-    c->ev_rows.resize(std::min<u64>((n + chunk - 1) / chunk, (u64)SCAN_EV_CHUNKS));
-    c->last_bins = 0;
-    c->last_subs = subs ? (int)sbs.ss.nbins : 0;
-    if (subs && view(c).lazy) c->vec_stale = true; // (the records' copies are ahead of the vectors now)
-    else c->vec_zero = false;
-    c->last_tickets = tickets ? (int)ticket_slices(c) : 0;
-    c->stats_valid = true;
-    return MG_OK;
+    return scan_table(c, ScanTable{nullptr, nullptr, nullptr, (const u32 *)d_rows}, n);
 }
 
 namespace {
@@ -1694,9 +1639,6 @@ int pipeline_ready(mg_ctx *c)
     return MG_OK;
 }
 constexpr size_t HOST_PIECE = 1u << 24; // rows per staged piece: 320 MB of SoA rows per slot
-} // namespace
-
-namespace {
 // Host-fed scans leave DMA from the caller's buffers in flight on copy_stream: whatever way the call ends, both streams are
 // drained before the caller (who may free or unmap the source on an error) sees the result.
 struct StreamsDrained {
@@ -1707,15 +1649,11 @@ struct StreamsDrained {
         hipStreamSynchronize(c->stream);
     }
 };
-} // namespace
-
-MG_EXPORT int mg_kmc_scan(mg_ctx *c, const uint64_t *hi, const uint64_t *lo, const uint32_t *cnt, size_t n)
+// The two-slot loop of a host-fed scan, HOST_PIECE rows at a time: `upload(slot, r0, nr, d)` queues the piece's copies on
+// copy_stream, `decode(slot, r0, nr, d)` what turns them into the SoA rows d[0..2] on the scan stream, and the rows are scanned.
+template <class Upload, class Decode>
+int scan_host_pieces(mg_ctx *c, size_t n, Upload upload, Decode decode)
 {
-    const DeviceGuard on_device(c, KEEP);
-    if (!c) return MG_ERR_ARG;
-    if (n == 0) return MG_OK;
-    if (!hi || !lo || !cnt) return fail(c, MG_ERR_ARG, "NULL table pointer");
-    if (!c->bf[0].mode || !c->bf[1].mode) return fail(c, MG_ERR_STATE, "mg_kmc_scan needs both filters finalised");
     TRY(pipeline_ready(c));
     const StreamsDrained drained{c};
     const size_t cap = n < HOST_PIECE ? n : HOST_PIECE;
@@ -1727,16 +1665,32 @@ MG_EXPORT int mg_kmc_scan(mg_ctx *c, const uint64_t *hi, const uint64_t *lo, con
         const size_t nr = n - r0 < HOST_PIECE ? n - r0 : HOST_PIECE;
         const int sl = (int)(piece_no & 1);
         if (piece_no >= 2) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_free[sl], 0)); // the scan that used this slot is done
-        HIP_TRY(c, hipMemcpyAsync(d[sl][0], hi + r0, nr * 8, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(c, hipMemcpyAsync(d[sl][1], lo + r0, nr * 8, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(c, hipMemcpyAsync(d[sl][2], cnt + r0, nr * 4, hipMemcpyHostToDevice, c->copy_stream));
+        TRY(upload(sl, r0, nr, d[sl]));
         HIP_TRY(c, hipEventRecord(c->ev_up[sl], c->copy_stream));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_up[sl], 0));
+        TRY(decode(sl, r0, nr, d[sl]));
         TRY(mg_kmc_scan_device(c, d[sl][0], d[sl][1], d[sl][2], nr));
         HIP_TRY(c, hipEventRecord(c->ev_free[sl], c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the caller may reuse its buffers
     return MG_OK;
+}
+} // namespace
+
+MG_EXPORT int mg_kmc_scan(mg_ctx *c, const uint64_t *hi, const uint64_t *lo, const uint32_t *cnt, size_t n)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n == 0) return MG_OK;
+    if (!hi || !lo || !cnt) return fail(c, MG_ERR_ARG, "NULL table pointer");
+    if (!c->bf[0].mode || !c->bf[1].mode) return fail(c, MG_ERR_STATE, "mg_kmc_scan needs both filters finalised");
+    const auto upload = [&](int, size_t r0, size_t nr, void *const *d) -> int {
+        HIP_TRY(c, hipMemcpyAsync(d[0], hi + r0, nr * 8, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(d[1], lo + r0, nr * 8, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(d[2], cnt + r0, nr * 4, hipMemcpyHostToDevice, c->copy_stream));
+        return MG_OK;
+    };
+    return scan_host_pieces(c, n, upload, [](int, size_t, size_t, void *const *) -> int { return MG_OK; });
 }
 
 // ---- KMC database feed -------------------------------------------------------------------------
@@ -1792,32 +1746,21 @@ MG_EXPORT int mg_kmc_scan_records(mg_ctx *c, const void *records, size_t n, uint
     if (!records) return fail(c, MG_ERR_ARG, "NULL records");
     if (!c->d_kmc_lut) return fail(c, MG_ERR_STATE, "mg_kmc_set_lut first");
     if (!c->bf[0].mode || !c->bf[1].mode) return fail(c, MG_ERR_STATE, "mg_kmc_scan needs both filters finalised");
-    TRY(pipeline_ready(c));
-    const StreamsDrained drained{c};
     const size_t rs = c->kmc_suffix_bytes + c->kmc_counter_bytes;
-    const size_t cap = n < HOST_PIECE ? n : HOST_PIECE;
-    void *d[2][3], *raw[2];
-    for (int sl = 0; sl < 2; ++sl) {
-        for (int i = 0; i < 3; ++i) TRY(scratch(c, c->s_stage[sl][i], cap * (i == 2 ? 4 : 8), &d[sl][i]));
-        TRY(scratch(c, c->s_raw[sl], cap * rs + 64, &raw[sl]));
-    }
-    size_t piece_no = 0;
-    for (size_t r0 = 0; r0 < n; r0 += HOST_PIECE, ++piece_no) {
-        const size_t nr = n - r0 < HOST_PIECE ? n - r0 : HOST_PIECE;
-        const int sl = (int)(piece_no & 1);
-        if (piece_no >= 2) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_free[sl], 0));
+    void *raw[2];
+    for (int sl = 0; sl < 2; ++sl) TRY(scratch(c, c->s_raw[sl], (n < HOST_PIECE ? n : HOST_PIECE) * rs + 64, &raw[sl]));
+    const auto upload = [&](int sl, size_t r0, size_t nr, void *const *) -> int {
         HIP_TRY(c, hipMemcpyAsync(raw[sl], (const char *)records + r0 * rs, nr * rs, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(c, hipEventRecord(c->ev_up[sl], c->copy_stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_up[sl], 0));
+        return MG_OK;
+    };
+    const auto decode = [&](int sl, size_t r0, size_t nr, void *const *d) -> int {
         hipLaunchKernelGGL(kmc_decode_kernel, dim3((unsigned)((nr + KMC_TILE - 1) / KMC_TILE)), dim3(TPB), 0, c->stream, (const u8 *)raw[sl], (u64)nr,
                            (u64)(first_record + r0), c->kmc_suffix_bytes, c->kmc_counter_bytes, c->kmc_prefix_len, (const u64 *)c->d_kmc_lut, c->kmc_n_lut,
-                           c->kmc_min_count, c->kmc_max_count, (u64 *)d[sl][0], (u64 *)d[sl][1], (u32 *)d[sl][2]);
+                           c->kmc_min_count, c->kmc_max_count, (u64 *)d[0], (u64 *)d[1], (u32 *)d[2]);
         HIP_TRY(c, hipGetLastError());
-        TRY(mg_kmc_scan_device(c, d[sl][0], d[sl][1], d[sl][2], nr));
-        HIP_TRY(c, hipEventRecord(c->ev_free[sl], c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return MG_OK;
+        return MG_OK;
+    };
+    return scan_host_pieces(c, n, upload, decode);
 }
 
 // the decoded rows of a run of records (tests, and callers that want the table itself)
@@ -2636,9 +2579,7 @@ int blocks_setup(mg_ctx *c, const mg_panel_dev *p, const u32 *d_blk_var_off, con
     R.slides = (PickItem *)q[7];
     R.retry = (u32 *)q_retry;
     R.order = (u32 *)q_order;
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&R.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) R.cus = 256;
+    R.cus = device_cus(c);
     *out = R;
     return MG_OK;
 }
@@ -2706,11 +2647,9 @@ template <int MODE> unsigned blocks_grid(mg_ctx *c)
 {
     int &g = c->blocks_grid[MODE];
     if (!g) {
-        int per_cu = 0, cus = 0, dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+        int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cover_blocks_kernel<MODE>, TPB, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-        g = cus * per_cu;
+        g = device_cus(c) * per_cu;
     }
     return (unsigned)g;
 }
