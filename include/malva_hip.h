@@ -178,6 +178,30 @@ int mg_reads_finish(mg_ctx *ctx, uint64_t *n_kept_out);
 int mg_reads_export(mg_ctx *ctx, uint64_t *hi, uint64_t *lo, uint32_t *cnt, size_t cap, uint64_t *n_out);
 int mg_reads_stats(mg_ctx *ctx, float *ms_out, uint64_t *counts_out);
 
+/* ---- cohort mode: several samples against one resident index ----------------
+ * The reference genotypes one individual per run: every sample is a whole call_main (main.cpp:421-594) that loads the
+ * index, parses the panel and cuts the blocks again before the one thing that differs happens -- the KMC scan
+ * (main.cpp:482-500) and the counter lookups of set_coverages (main.cpp:151-184).  It has no counterpart for what follows.
+ * In cohort mode a context holds the counters of n_planes samples (1..64) at once, sample-minor: the cell of filter
+ * counter r, plane s at counts[r * G' + s], of exact-map key id at vals[id * G' + s], G' = n_planes rounded up to a power
+ * of two (so the stride is a shift, and a counter's cells never straddle a 64-byte line they need not: 16 planes share one).
+ *   mg_cohort_begin    both filters finalised, no multi-GPU group, no reads count open; allocates the planes, zeroed, and
+ *                      selects plane 0.  The single-sample vectors are kept aside.  While the mode lasts the counters live in
+ *                      the vectors alone (as on a context in a group: the records' own copies are not used), and the calls that
+ *                      change the index (inserts, finalize, imports of filters / map, mg_index_*, mg_ref_scan*),
+ *                      mg_counters_view and every mg_comm_* / mg_counters_allreduce* return MG_ERR_STATE.
+ *   mg_cohort_select   the plane that scans (mg_kmc_scan*, mg_reads_*), per-k-mer increments and reads (mg_bf_increment,
+ *                      mg_bf_get_count, mg_map_*, mg_lookup_cover, mg_call_isolated*, mg_cover_blocks*), mg_counters_reset /
+ *                      _export_device / _import_device and the counter halves of mg_bf_export / mg_map_export act on.
+ *                      Not between mg_reads_begin and mg_reads_finish.
+ *   mg_cohort_end      frees the planes; the single-sample vectors are back, zeroed, and the next scan republishes the
+ *                      records' copies.
+ *   mg_cohort_info     n_planes (0 outside cohort mode) and the selected plane. */
+int mg_cohort_begin(mg_ctx *ctx, uint32_t n_planes);
+int mg_cohort_select(mg_ctx *ctx, uint32_t plane);
+int mg_cohort_end(mg_ctx *ctx);
+int mg_cohort_info(mg_ctx *ctx, uint32_t *n_planes, uint32_t *selected);
+
 /* ---- multi-GPU exchange step --------------------------------------------- */
 
 /* The scan's only state is two commutative wrapping-u32 sums:
@@ -330,6 +354,26 @@ int mg_cut_blocks_device(mg_ctx *ctx, const mg_panel_dev *panel, void *d_blk_var
  * that pipeline's capacities the workgroup-per-record kernel; what exceeds ITS capacities is flagged in d_overflow_out. */
 int mg_cover_blocks_device(mg_ctx *ctx, const mg_panel_dev *panel, const void *d_blk_var_off, const void *d_var_block /* or NULL */,
                            const void *d_n_blocks, int haploid, void *d_cov_out, void *d_overflow_out);
+/* mg_cover_blocks_device for every plane of a context in cohort mode (the record loop of main.cpp:522-579, which the
+ * reference repeats per sample inside call_main, main.cpp:421-594): d_cov_out is [n_planes][slots] u32, plane-major
+ * (slots = var_allele_off[n_vars]); plane s holds exactly what mg_cover_blocks_device writes with plane s selected.
+ * d_overflow_out ([n_vars] u8) does not depend on the sample.  Tier 1 runs ONCE for all planes: classification, signature
+ * k-mer, hash and the walk to the record once per allele, then the record's n_planes cells -- one contiguous run -- become
+ * the n_planes coverages.  Tiers 2 and 3 run plane by plane over the general list tier 1 wrote once.  The selected plane
+ * is left as it was.  Reads var_allele_off[n_vars] back (waits for the stream once, on four bytes), asynchronous otherwise.
+ * mg_cohort_stats (waits for it): ms_out[0] tier 1 over all planes, ms_out[1] tiers 2 and 3 of all planes (mg_blocks_stats describes
+ * the single-sample call only and returns MG_ERR_STATE after this one). */
+int mg_cover_blocks_cohort_device(mg_ctx *ctx, const mg_panel_dev *panel, const void *d_blk_var_off, const void *d_var_block /* or NULL */,
+                                  const void *d_n_blocks, int haploid, void *d_cov_out, void *d_overflow_out);
+int mg_cohort_stats(mg_ctx *ctx, float *ms_out);
+/* The host form (as mg_cover_blocks / mg_cover_blocks_sparse are of mg_cover_blocks_device): the batch is uploaded ONCE and covered
+ * for every plane; `gt` dense, or NULL with the sparse triple; cov_out is [n_planes][slots], overflow_out [n_vars].  Knows the slot
+ * count from var_allele_off, so it does not wait for the device before the copy back.  Synchronous. */
+int mg_cover_blocks_cohort(mg_ctx *ctx, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off,
+                           size_t n_vars, const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present,
+                           const uint32_t *var_allele_off, const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
+                           const uint16_t *gt, const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default,
+                           uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out);
 /* extract_kmers + add_kmers_to_bf (main.cpp:349-350) for every block (the panel holds only what `index` keeps,
  * main.cpp:332); d_overflow_out as mg_index_blocks.  The arrays stay where they are, but the call waits for the device
  * twice on eight bytes: the exact map is sized from a counting pass before the insert pass runs. */

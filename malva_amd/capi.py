@@ -101,6 +101,13 @@ def lib():
         "mg_counters_import_device": [vp, vp],
         "mg_counters_reset": [vp],
         "mg_counters_view": [vp, vp, vp, vp],
+        "mg_cohort_begin": [vp, u32],
+        "mg_cohort_select": [vp, u32],
+        "mg_cohort_end": [vp],
+        "mg_cohort_info": [vp, vp, vp],
+        "mg_cover_blocks_cohort_device": [vp, vp, vp, vp, vp, it, vp, vp],
+        "mg_cohort_stats": [vp, vp],
+        "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
         "mg_comm_unique_id": [vp],
         "mg_comm_init": [vp, it, it, vp],
         "mg_comm_init_all": [C.POINTER(vp), it],
@@ -159,6 +166,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_host_alloc", "mg_host_free", "mg_kmc_set_lut", "mg_kmc_scan_records", "mg_kmc_decode_records",
             "mg_reads_begin", "mg_reads_add", "mg_reads_add_device", "mg_reads_finish", "mg_reads_export", "mg_reads_stats",
             "mg_counters_size", "mg_counters_export_device", "mg_counters_import_device", "mg_counters_reset", "mg_counters_view",
+            "mg_cohort_begin", "mg_cohort_select", "mg_cohort_end", "mg_cohort_info", "mg_cover_blocks_cohort_device", "mg_cohort_stats", "mg_cover_blocks_cohort",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
@@ -551,6 +559,33 @@ class Context:
 
     def counters_reset(self):
         self._ck(self._L.mg_counters_reset(self.h))
+
+    # cohort mode: the counters of several samples side by side (planes)
+    def cohort_begin(self, n_planes):
+        self._ck(self._L.mg_cohort_begin(self.h, int(n_planes)))
+
+    def cohort_select(self, plane):
+        self._ck(self._L.mg_cohort_select(self.h, int(plane)))
+
+    def cohort_end(self):
+        self._ck(self._L.mg_cohort_end(self.h))
+
+    def cohort_info(self):
+        """-> (planes, selected plane); (0, 0) outside cohort mode"""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.mg_cohort_info(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def cover_blocks_cohort_device(self, panel: "PanelDev", d_blk_var_off, d_var_block, d_n_blocks, haploid, d_cov, d_overflow):
+        """d_cov: [planes][slots] u32, plane-major"""
+        v = C.c_void_p
+        self._ck(self._L.mg_cover_blocks_cohort_device(self.h, C.byref(panel), v(d_blk_var_off), v(d_var_block), v(d_n_blocks), int(haploid), v(d_cov), v(d_overflow)))
+
+    def cohort_stats(self):
+        """-> device ms of the most recent cover_blocks_cohort_device: (tier 1 over all planes, tiers 2-3 of all planes)"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.mg_cohort_stats(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     # multi-GPU exchange inside the library (RCCL)
     def comm_init(self, rank, world, comm_id: bytes):

@@ -243,6 +243,51 @@ __global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) panel_lone_kernel(PanelView
     __syncthreads();
     for (u32 i = threadIdx.x; i < sh_n; i += TPB) gen_list[sh_base + i] = sh_gen[i];
 }
+// Tier 1 of a cohort (mg_cover_blocks_cohort_device): panel_lone_kernel with the sample taken out of everything that does not
+// depend on it.  Classification, the general list and the class words exactly as there; per lone allele the signature k-mer is
+// assembled, made canonical and hashed ONCE and its record found once; then the record's n_planes cells (one contiguous run,
+// BFView::cshift) become the n_planes coverages, plane s at cov_out + s * plane_stride.  A thread loops over the planes: the
+// cells of one record are consecutive addresses of ONE lane (a 16-byte load per four planes, 64 planes = one 256-byte run),
+// and each plane's store is coalesced across the lanes like panel_lone_kernel's single one.
+template <bool SLOW>
+__global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) cohort_lone_kernel(PanelView P, u64 n_vars, const u32 *__restrict__ blk_var_off, const u32 *__restrict__ var_block,
+                                                          const u8 *reference, const u64 *__restrict__ ref2, const u32 *__restrict__ refbad, const u8 *pool, int k,
+                                                          int haploid, BFView bf, MapView map, u32 *cov_out, u32 n_planes, u64 plane_stride, u32 *need_slow, u32 call_no,
+                                                          u32 *gen_list, unsigned long long *counters, unsigned short *rec_class)
+{
+    __shared__ u32 sh_gen[LONE_TILES * TPB / 2];
+    __shared__ u32 sh_n, sh_sigs;
+    __shared__ unsigned long long sh_base;
+    if (SLOW && *need_slow != call_no) return;
+    if (threadIdx.x == 0) sh_n = sh_sigs = 0;
+    __syncthreads();
+    u32 sigs = 0;
+    for (int tile = 0; tile < LONE_TILES; ++tile) {
+        const u64 t = ((u64)blockIdx.x * LONE_TILES + tile) * TPB + threadIdx.x;
+        const u64 v = t >> 1;
+        if (v >= n_vars) break;
+        const LoneClass c = classify_lone(P, blk_var_off, var_block, v, k, haploid, pool);
+        if (!SLOW && !(t & 1)) {
+            if (!c.lone) {
+                sh_gen[atomicAdd(&sh_n, 1u)] = (u32)v;
+                rec_class[v] = c.cls;
+            } else sigs += (u32)__popcll(c.mask);
+        }
+        if (c.lone)
+            iso_cover_body<SLOW, true>(reference, ref2, refbad, c.site, c.a0, c.A, c.eligible, c.mask, (u32)(t & 1), P.allele_off, pool, k, bf, map, cov_out, need_slow, call_no,
+                                       n_planes, plane_stride);
+    }
+    if (SLOW) return;
+    for (int d = 32; d; d >>= 1) sigs += __shfl_xor(sigs, d, 64);
+    if ((threadIdx.x & 63) == 0 && sigs) atomicAdd(&sh_sigs, sigs);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sh_base = sh_n ? atomicAdd(counters, (unsigned long long)sh_n) : 0ULL;
+        if (sh_sigs) atomicAdd(counters + 2, (unsigned long long)sh_sigs);
+    }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < sh_n; i += TPB) gen_list[sh_base + i] = sh_gen[i];
+}
 // index time: lone records are inserted here (REF key of record v takes insertion row row0 + v), the others listed
 __global__ void __launch_bounds__(TPB, 8) panel_lone_index_kernel(PanelView P, u64 n_vars, const u32 *__restrict__ blk_var_off, const u32 *__restrict__ var_block,
                                                                const u8 *reference, const u8 *pool, int k, int haploid, BFView bf, MapView map, u32 row0,
@@ -801,7 +846,7 @@ __global__ void __launch_bounds__(TPB, 8) fw_snp_kernel(BlockBatch B, FlatWork W
         if (MODE == 0) {
             i32 w;
             if (is_ref) w = k == (int)map.klen ? map_value(map, key, h, idx) : 0;
-            else w = (i32)bucket_count(map, bf.counts, idx);
+            else w = (i32)bucket_count(map, bf, idx);
             if (w > 0) atomicMax(&cov_out[a0 + mid_canon], (u32)w);
         } else if (is_ref) {
             if (MODE == 1) ++ref_rows;
@@ -981,7 +1026,7 @@ __global__ void __launch_bounds__(TPB) fw_eval_kernel(BlockBatch B, FlatWork W, 
         if (MODE == 0) {
             i32 w;
             if (is_ref) w = k == (int)map.klen ? map_value(map, key, h, idx) : 0;
-            else w = (i32)bucket_count(map, bf.counts, idx);
+            else w = (i32)bucket_count(map, bf, idx);
             if (w > 0) atomicMax(&cov_out[a0 + mid_canon], (u32)w);
         } else if (is_ref) {
             if (MODE == 1) ++ref_rows;
@@ -1124,7 +1169,7 @@ __device__ __forceinline__ void fc_eval(const BlockBatch &B, const unsigned char
     if (MODE == 0) {
         i32 w;
         if (is_ref) w = k == (int)map.klen ? map_value(map, key, h, idx) : 0;
-        else w = (i32)bucket_count(map, bf.counts, idx);
+        else w = (i32)bucket_count(map, bf, idx);
         if (w > 0) atomicMax(&cov_out[hd.a0 + mid_canon], (u32)w);
     } else if (is_ref) {
         if (MODE == 1) ++ref_rows;
@@ -1452,7 +1497,7 @@ __global__ void __launch_bounds__(TPB) fw_slide_kernel(BlockBatch B, FlatWork W,
                 const u64 idx = mod_size(h, bf.mod);
                 if (MODE == 0) {
                     if (is_ref) w = k == (int)map.klen ? map_value(map, key, h, idx) : 0;
-                    else w = (i32)bucket_count(map, bf.counts, idx);
+                    else w = (i32)bucket_count(map, bf, idx);
                 } else if (MODE == 2) {
                     if (is_ref) map_insert_key(map, bf, key, h, row0 + wave_take(cursor), row0);
                     else {

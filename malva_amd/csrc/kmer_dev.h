@@ -185,6 +185,11 @@ struct BFView {
     u64 *words;        // size bits
     const u32 *blk;    // ones before each 512-bit block (valid once finalised)
     u32 *counts;       // one wrapping u32 per set bit; the u16 cell of the reference is its low half
+    // Cohort mode (mg_cohort_begin): the counters of G samples lie side by side, sample-minor -- the cell of counter r, plane s
+    // at counts[(r << cshift) + s], 2^cshift = G rounded up to a power of two, so that a counter's cells never straddle a 64-byte
+    // line they need not (16 planes of u32 cells share one) and the stride costs a shift, not a multiply.  coff = the plane this
+    // view reads and writes.  Outside cohort mode both are 0 and every address is what it was without them.
+    u32 cshift, coff;
     // The gate: one cache-resident blocked Bloom filter in front of BOTH stores of the
     // call-time scan, keyed by the filter slot idx = XXH3 % size (the exact map is
     // addressed by the same XXH3, so one hash and one probe serve both).  Every set
@@ -213,6 +218,8 @@ struct BFView {
     u32 pre_k;
     u32 use_gate;
 };
+// the cell of filter counter (rank) r in the view's plane
+__device__ __forceinline__ u32 *bf_cell(const BFView &b, u32 r) { return b.counts + (((u64)r << b.cshift) + b.coff); }
 __device__ __forceinline__ bool bf_bit(const BFView &b, u64 idx) { return (b.words[idx >> 6] >> (idx & 63)) & 1; }
 // the same answer from the set of set positions, where the view carries one
 __device__ __forceinline__ bool bf_bit_via_set(const BFView &b, u64 idx)
@@ -301,7 +308,7 @@ __device__ __forceinline__ u32 bf_rank(const BFView &b, u64 idx)
 __device__ __forceinline__ u32 bf_count_at(const BFView &b, u64 idx)
 {
     u32 r;
-    return bf_bit_rank(b, idx, &r) ? b.counts[r] : 0;
+    return bf_bit_rank(b, idx, &r) ? *bf_cell(b, r) : 0;
 }
 
 // ---- exact map view --------------------------------------------------------------
@@ -335,12 +342,15 @@ static_assert(sizeof(MapSlot) == 64, "one record per 64 bytes");
 struct MapView {
     MapSlot *slots;
     u32 *vals;
+    u32 cshift, coff; // cohort mode: the cell of key `id`, plane s at vals[(id << cshift) + s]; coff = this view's plane (BFView::cshift)
     u32 cap_log2;
     u32 klen;  // every key held here is exactly this long (other lengths live in the host overflow list)
     u32 epoch; // != 0: the records' counter copies of this epoch are current (single GPU, every increment since the reset made by the scan)
     u32 lazy;  // (epoch != 0 only) the scan adds to the records' copies ALONE: vals[] / counts[] catch up when somebody asks for them (rec_collect_kernel)
     u64 home_mul; // see map_home
 };
+// the cell of exact-map counter `id` in the view's plane
+__device__ __forceinline__ u32 *map_cell(const MapView &m, u32 id) { return m.vals + (((u64)id << m.cshift) + m.coff); }
 // the scan's side of the copies: add `c` to the record's counter of the current epoch (a word of an older epoch restarts at zero)
 __device__ __forceinline__ void rec_add_val(MapSlot *rec, u32 epoch, u32 c)
 {
@@ -436,7 +446,7 @@ __device__ __forceinline__ i32 map_value(const MapView &m, U128 key, u64 h, u64 
 {
     if (!m.epoch) {
         const long long id = map_find_id(m, key, h, idx);
-        return id >= 0 ? (i32)m.vals[id] : 0;
+        return id >= 0 ? (i32)*map_cell(m, (u32)id) : 0;
     }
     const u64 mask = (1ULL << m.cap_log2) - 1;
     u64 s = map_home(m, idx);
@@ -451,11 +461,11 @@ __device__ __forceinline__ i32 map_value(const MapView &m, U128 key, u64 h, u64 
     }
 }
 // BF::get_count of filter slot idx as the genotyping reads it (bloom_filter.hpp:115-125: the u16 cell, 0 when the bit is clear)
-__device__ __forceinline__ u32 bucket_count(const MapView &m, const u32 *counts, u64 idx)
+__device__ __forceinline__ u32 bucket_count(const MapView &m, const BFView &bf, u64 idx)
 {
     if (!m.epoch) {
         const long long rank = bucket_rank(m, idx);
-        return rank >= 0 ? (u32)(uint16_t)counts[rank] : 0u;
+        return rank >= 0 ? (u32)(uint16_t)*bf_cell(bf, (u32)rank) : 0u;
     }
     const u64 mask = (1ULL << m.cap_log2) - 1, want = idx + 1;
     u64 s = map_home(m, idx);

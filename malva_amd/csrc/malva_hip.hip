@@ -130,6 +130,14 @@ struct mg_ctx {
     std::vector<hipEvent_t> ev;
     std::vector<u64> ev_rows; // rows of each timed chunk
     bool stats_valid = false;
+    // cohort mode (mg_cohort_begin): bf[ALT].counts / map.vals hold coh_planes samples' counters side by side, sample-minor, a counter's
+    // cells 2^coh_shift apart (the planes rounded up to a power of two); every view reads and writes plane coh_sel.  Counters live
+    // in the vectors alone while it lasts (records_wanted), like a context in a group.  The single-sample vectors wait in coh_sv_*;
+    // coh_irr: the host-side values of the keys the table cannot hold, per plane, and ([coh_planes]) the single-sample ones.
+    u32 coh_planes = 0, coh_shift = 0, coh_sel = 0;
+    u32 *coh_sv_counts = nullptr, *coh_sv_vals = nullptr;
+    std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
+    hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -237,6 +245,7 @@ int fail(mg_ctx *c, int code, const char *fmt, ...)
 inline unsigned nblocks(u64 n) { return (unsigned)((n + TPB - 1) / TPB); }
 int comm_drop(mg_ctx *c); // multi-GPU section
 void reads_drop(mg_ctx *c); // reads section
+bool reads_unfinished(const mg_ctx *c); // reads section: between mg_reads_begin and mg_reads_finish
 
 int scratch(mg_ctx *c, Scratch &s, size_t bytes, void **out)
 {
@@ -309,6 +318,7 @@ BFView view(const mg_ctx *c, int which)
     v.use_gate = (c->use_summary && b.gate) ? 1 : 0;
     v.pos_set = b.pos_set_valid ? b.pos_set : nullptr;
     v.pos_set_log2 = b.pos_set_log2;
+    if (which == MG_BF_ALT) v.cshift = c->coh_shift, v.coff = c->coh_sel; // (0 and 0 outside cohort mode)
     return v;
 }
 // Are the records' counter copies worth keeping?  They cost the scan a compare-and-swap per hit beside its add to the vector
@@ -316,7 +326,7 @@ BFView view(const mg_ctx *c, int which)
 // the copies lose (measured: 1.043 against 1.000 ms per C3 step); beyond that they win (use_record_counters: 0 never, 2 always).
 bool records_wanted(const mg_ctx *c)
 {
-    if (!c->use_record_counters || c->rec_off || c->comm_world > 1 || !c->local_group.empty()) return false;
+    if (!c->use_record_counters || c->rec_off || c->comm_world > 1 || !c->local_group.empty() || c->coh_planes) return false;
     return c->use_record_counters >= 2 || (u64)(c->bf[MG_BF_ALT].nset + c->map.rows_total) * 4 > (256ull << 20);
 }
 MapView view(const mg_ctx *c)
@@ -325,6 +335,8 @@ MapView view(const mg_ctx *c)
     MapView v{};
     v.slots = m.slots;
     v.vals = m.vals;
+    v.cshift = c->coh_shift;
+    v.coff = c->coh_sel;
     v.cap_log2 = m.cap_log2;
     v.klen = c->k;
     v.home_mul = c->map_ordered ? ~0ULL / c->bf[MG_BF_ALT].mod.size : 0x9E3779B97F4A7C15ULL;
@@ -411,6 +423,7 @@ int map_reserve(mg_ctx *c, u64 extra)
 {
     MapState &m = c->map;
     const u64 need_rows = m.rows_total + extra;
+    if (c->coh_planes && extra) return fail(c, MG_ERR_STATE, "the index is fixed while the context is in cohort mode (mg_cohort_end first)");
     if (need_rows >= 0xFFFFFFFFULL) return fail(c, MG_ERR_LIMIT, "exact map: more than 2^32-1 insertion rows");
     if (need_rows > m.vals_cap) {
         TRY(unjoin(c));
@@ -656,6 +669,10 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     if (c->copy_stream) hipStreamDestroy(c->copy_stream);
     if (c->h_gt_stage) hipHostFree(c->h_gt_stage);
     hipFree(c->d_kmc_lut);
+    hipFree(c->coh_sv_counts);
+    hipFree(c->coh_sv_vals);
+    for (auto &e : c->ev_c)
+        if (e) hipEventDestroy(e);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -864,6 +881,7 @@ MG_EXPORT int mg_get_option(mg_ctx *c, const char *name, int64_t *value)
 
 MG_EXPORT int mg_bf_insert(mg_ctx *c, int which, const char *rows, size_t stride, size_t n)
 {
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (c && (which == MG_BF_ALT || which == MG_BF_CTX)) c->bf[which].pos_set_valid = false; // (the bits are about to change)
     const DeviceGuard on_device(c);
     TRY(check_which(c, which));
@@ -892,6 +910,7 @@ MG_EXPORT int mg_debug_bf_index(mg_ctx *c, int which, const char *rows, size_t s
 
 MG_EXPORT int mg_bf_finalize(mg_ctx *c, int which)
 {
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (c && (which == MG_BF_ALT || which == MG_BF_CTX)) c->bf[which].pos_set_valid = false;
     const DeviceGuard on_device(c);
     TRY(check_which(c, which));
@@ -997,6 +1016,7 @@ MG_EXPORT int mg_bf_info(mg_ctx *c, int which, uint64_t *size_bits, uint64_t *n_
 MG_EXPORT int mg_map_insert(mg_ctx *c, const char *rows, size_t stride, size_t n)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     TRY(check_rows(c, rows, stride, n));
     if (n == 0) return MG_OK;
     TRY(map_reserve(c, n));
@@ -1165,6 +1185,7 @@ int ref_scan_short(mg_ctx *c, const char *contig, size_t len)
 MG_EXPORT int mg_ref_scan(mg_ctx *c, const char *contig, size_t len)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     if (len && !contig) return fail(c, MG_ERR_ARG, "contig is NULL");
     TRY(ref_scan_checks(c, len));
@@ -1192,6 +1213,7 @@ MG_EXPORT int mg_ref_scan(mg_ctx *c, const char *contig, size_t len)
 MG_EXPORT int mg_ref_scan_resident(mg_ctx *c, uint64_t offset, size_t len)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     if (!c->d_ref) return fail(c, MG_ERR_STATE, "mg_reference_upload first");
     if (offset + len > c->ref_len) return fail(c, MG_ERR_ARG, "contig lies outside the uploaded reference");
@@ -1881,6 +1903,7 @@ int ensure_joined(mg_ctx *c)
 MG_EXPORT int mg_counters_view(mg_ctx *c, void **d_ptr, uint64_t *n_bf, uint64_t *n_map)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c || !d_ptr) return MG_ERR_ARG;
     TRY(ensure_joined(c));
     c->rec_off = true; // the caller may write the vector (an all-reduce by other means): from here on it alone holds the counters
@@ -1889,12 +1912,40 @@ MG_EXPORT int mg_counters_view(mg_ctx *c, void **d_ptr, uint64_t *n_bf, uint64_t
     if (n_map) *n_map = c->map.rows_total;
     return MG_OK;
 }
+namespace {
+// one plane of a sample-minor counter vector (cohort mode): cell i of the plane at cells[i << shift]
+__global__ void __launch_bounds__(TPB) plane_gather_kernel(const u32 *__restrict__ cells, u32 shift, u64 n, u32 *__restrict__ out)
+{
+    const u64 i = (u64)blockIdx.x * TPB + threadIdx.x;
+    if (i < n) out[i] = cells[i << shift];
+}
+__global__ void __launch_bounds__(TPB) plane_scatter_kernel(u32 *__restrict__ cells, u32 shift, u64 n, const u32 *__restrict__ in)
+{
+    const u64 i = (u64)blockIdx.x * TPB + threadIdx.x;
+    if (i < n) cells[i << shift] = in[i];
+}
+__global__ void __launch_bounds__(TPB) plane_zero_kernel(u32 *__restrict__ cells, u32 shift, u64 n)
+{
+    const u64 i = (u64)blockIdx.x * TPB + threadIdx.x;
+    if (i < n) cells[i << shift] = 0u;
+}
+// the selected plane of the two vectors, gathered to d_bf / d_map (either may be NULL)
+int plane_gather(mg_ctx *c, u32 *d_bf, u32 *d_map)
+{
+    const u64 nb = c->bf[0].mode ? c->bf[0].nset : 0, nm = c->map.rows_total;
+    if (d_bf && nb) hipLaunchKernelGGL(plane_gather_kernel, dim3(nblocks(nb)), dim3(TPB), 0, c->stream, (const u32 *)c->bf[0].counts + c->coh_sel, c->coh_shift, nb, d_bf);
+    if (d_map && nm) hipLaunchKernelGGL(plane_gather_kernel, dim3(nblocks(nm)), dim3(TPB), 0, c->stream, (const u32 *)c->map.vals + c->coh_sel, c->coh_shift, nm, d_map);
+    HIP_TRY(c, hipGetLastError());
+    return MG_OK;
+}
+} // namespace
 MG_EXPORT int mg_counters_export_device(mg_ctx *c, void *d_out)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c || !d_out) return MG_ERR_ARG;
     if (!c->bf[0].mode) return fail(c, MG_ERR_STATE, "`bf` not finalised");
     const u64 nb = c->bf[0].nset, nm = c->map.rows_total;
+    if (c->coh_planes) return plane_gather(c, (u32 *)d_out, (u32 *)d_out + nb);
     if (nb) HIP_TRY(c, hipMemcpyAsync(d_out, c->bf[0].counts, nb * 4, hipMemcpyDeviceToDevice, c->stream));
     if (nm) HIP_TRY(c, hipMemcpyAsync((u32 *)d_out + nb, c->map.vals, nm * 4, hipMemcpyDeviceToDevice, c->stream));
     return MG_OK;
@@ -1905,6 +1956,12 @@ MG_EXPORT int mg_counters_import_device(mg_ctx *c, const void *d_in)
     if (!c || !d_in) return MG_ERR_ARG;
     if (!c->bf[0].mode) return fail(c, MG_ERR_STATE, "`bf` not finalised");
     const u64 nb = c->bf[0].nset, nm = c->map.rows_total;
+    if (c->coh_planes) {
+        if (nb) hipLaunchKernelGGL(plane_scatter_kernel, dim3(nblocks(nb)), dim3(TPB), 0, c->stream, c->bf[0].counts + c->coh_sel, c->coh_shift, nb, (const u32 *)d_in);
+        if (nm) hipLaunchKernelGGL(plane_scatter_kernel, dim3(nblocks(nm)), dim3(TPB), 0, c->stream, c->map.vals + c->coh_sel, c->coh_shift, nm, (const u32 *)d_in + nb);
+        HIP_TRY(c, hipGetLastError());
+        return MG_OK;
+    }
     if (nb) HIP_TRY(c, hipMemcpyAsync(c->bf[0].counts, d_in, nb * 4, hipMemcpyDeviceToDevice, c->stream));
     if (nm) HIP_TRY(c, hipMemcpyAsync(c->map.vals, (const u32 *)d_in + nb, nm * 4, hipMemcpyDeviceToDevice, c->stream));
     return MG_OK;
@@ -1913,6 +1970,14 @@ MG_EXPORT int mg_counters_reset(mg_ctx *c)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
+    if (c->coh_planes) { // the selected plane alone; the records hold no copies in cohort mode
+        const u64 nb = c->bf[0].mode ? c->bf[0].nset : 0, nm = c->map.rows_total;
+        if (nb) hipLaunchKernelGGL(plane_zero_kernel, dim3(nblocks(nb)), dim3(TPB), 0, c->stream, c->bf[0].counts + c->coh_sel, c->coh_shift, nb);
+        if (nm) hipLaunchKernelGGL(plane_zero_kernel, dim3(nblocks(nm)), dim3(TPB), 0, c->stream, c->map.vals + c->coh_sel, c->coh_shift, nm);
+        HIP_TRY(c, hipGetLastError());
+        for (auto &kv : c->map.irregular) kv.second = 0;
+        return MG_OK;
+    }
     if (!c->vec_zero) { // (vectors that nothing has written since the last reset -- lazy scans only -- are still all zero)
         if (c->bf[0].mode && c->bf[0].nset) HIP_TRY(c, hipMemsetAsync(c->bf[0].counts, 0, c->bf[0].nset * 4, c->stream));
         if (c->map.rows_total) HIP_TRY(c, hipMemsetAsync(c->map.vals, 0, c->map.rows_total * 4, c->stream));
@@ -1928,6 +1993,105 @@ MG_EXPORT int mg_counters_reset(mg_ctx *c)
         c->rec_ok = false;
     } else
         c->rec_ok = records_wanted(c) && c->map.slots != nullptr;
+    return MG_OK;
+}
+
+// ---- cohort mode: the counters of several samples side by side ---------------------------------
+// No counterpart in the reference, which runs the whole `call` (main.cpp:421-594) once per sample.
+MG_EXPORT int mg_cohort_begin(mg_ctx *c, uint32_t n_planes)
+{
+    const DeviceGuard on_device(c); // (vectors brought up to date; the records' copies are invalid from here on)
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_cohort_begin: 1 <= n_planes <= 64 (got %u)", n_planes);
+    if (c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cohort_begin: already in cohort mode (%u planes)", c->coh_planes);
+    if (!c->bf[MG_BF_ALT].mode || !c->bf[MG_BF_CTX].mode) return fail(c, MG_ERR_STATE, "mg_cohort_begin: both filters must be finalised");
+    if (c->comm || c->comm_world > 1 || !c->local_group.empty())
+        return fail(c, MG_ERR_STATE, "mg_cohort_begin: the context is part of a multi-GPU group (cohort mode and mg_comm_* do not combine)");
+    if (reads_unfinished(c)) return fail(c, MG_ERR_STATE, "mg_cohort_begin: a reads count is open (mg_reads_finish first)");
+    TRY(unjoin(c));
+    BFState &b = c->bf[MG_BF_ALT];
+    MapState &m = c->map;
+    u32 shift = 0;
+    while ((1u << shift) < n_planes) ++shift;
+    const u64 nb = (b.nset ? b.nset : 1) << shift, nm = (m.vals_cap ? m.vals_cap : 1) << shift;
+    u32 *pc = nullptr, *pv = nullptr;
+    if (hipMalloc(&pc, nb * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MG_ERR_NOMEM, "mg_cohort_begin: %u planes of %llu counters do not fit", n_planes, (unsigned long long)(b.nset + m.vals_cap));
+    }
+    if (hipMalloc(&pv, nm * 4) != hipSuccess) {
+        hipFree(pc);
+        (void)hipGetLastError(); // (the caller may go on with fewer planes: the runtime's sticky last-error must not surface in its next launch check)
+        return fail(c, MG_ERR_NOMEM, "mg_cohort_begin: %u planes of %llu counters do not fit", n_planes, (unsigned long long)(b.nset + m.vals_cap));
+    }
+    hipError_t e = hipMemsetAsync(pc, 0, nb * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(pv, 0, nm * 4, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        hipFree(pc);
+        hipFree(pv);
+        return fail(c, MG_ERR_HIP, "mg_cohort_begin: clearing the planes: %s", hipGetErrorString(e));
+    }
+    c->coh_sv_counts = b.counts;
+    c->coh_sv_vals = m.vals;
+    b.counts = pc;
+    m.vals = pv;
+    c->coh_irr.assign(n_planes + 1, m.irregular);
+    for (u32 s = 0; s < n_planes; ++s)
+        for (auto &kv : c->coh_irr[s]) kv.second = 0;
+    m.irregular = c->coh_irr[0];
+    c->coh_planes = n_planes;
+    c->coh_shift = shift;
+    c->coh_sel = 0;
+    c->rec_ok = false;
+    c->vec_stale = c->vec_zero = false;
+    return MG_OK;
+}
+MG_EXPORT int mg_cohort_select(mg_ctx *c, uint32_t plane)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (!c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cohort_select: not in cohort mode");
+    if (plane >= c->coh_planes) return fail(c, MG_ERR_ARG, "mg_cohort_select: plane %u of %u", plane, c->coh_planes);
+    if (reads_unfinished(c)) return fail(c, MG_ERR_STATE, "mg_cohort_select: a reads count is open (mg_reads_finish first)");
+    if (plane != c->coh_sel) {
+        c->coh_irr[c->coh_sel].swap(c->map.irregular);
+        c->map.irregular.swap(c->coh_irr[plane]);
+        c->coh_sel = plane;
+    }
+    return MG_OK;
+}
+MG_EXPORT int mg_cohort_end(mg_ctx *c)
+{
+    const DeviceGuard on_device(c);
+    if (!c) return MG_ERR_ARG;
+    if (!c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cohort_end: not in cohort mode");
+    if (reads_unfinished(c)) return fail(c, MG_ERR_STATE, "mg_cohort_end: a reads count is open (mg_reads_finish first)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BFState &b = c->bf[MG_BF_ALT];
+    MapState &m = c->map;
+    hipFree(b.counts);
+    hipFree(m.vals);
+    b.counts = c->coh_sv_counts;
+    m.vals = c->coh_sv_vals;
+    c->coh_sv_counts = c->coh_sv_vals = nullptr;
+    m.irregular.swap(c->coh_irr[c->coh_planes]);
+    for (auto &kv : m.irregular) kv.second = 0;
+    c->coh_irr.clear();
+    c->coh_planes = c->coh_shift = c->coh_sel = 0;
+    if (b.nset) HIP_TRY(c, hipMemsetAsync(b.counts, 0, b.nset * 4, c->stream));
+    if (m.rows_total) HIP_TRY(c, hipMemsetAsync(m.vals, 0, m.rows_total * 4, c->stream));
+    c->rec_ok = false; // the next single-sample scan republishes the records' copies from the (zero) vectors
+    c->vec_stale = false;
+    c->vec_zero = !c->rec_off;
+    return MG_OK;
+}
+MG_EXPORT int mg_cohort_info(mg_ctx *c, uint32_t *n_planes, uint32_t *selected)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes) *n_planes = c->coh_planes;
+    if (selected) *selected = c->coh_sel;
     return MG_OK;
 }
 
@@ -2086,6 +2250,7 @@ MG_EXPORT int mg_comm_unique_id(void *id_out)
 MG_EXPORT int mg_comm_init(mg_ctx *c, int rank, int world, const void *id)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     if (world < 1 || rank < 0 || rank >= world || !id) return fail(c, MG_ERR_ARG, "mg_comm_init: rank %d of %d", rank, world);
     Rccl *R = rccl();
@@ -2104,6 +2269,8 @@ MG_EXPORT int mg_comm_init_all(mg_ctx **ctxs, int n)
     if (!ctxs || n < 1 || n > 64) return MG_ERR_ARG;
     for (int i = 0; i < n; ++i)
         if (!ctxs[i]) return MG_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (ctxs[i]->coh_planes) return fail(ctxs[i], MG_ERR_STATE, "mg_comm_init_all: context %d is in cohort mode (mg_cohort_end first)", i);
     bool distinct = true, same = true;
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < i; ++j) {
@@ -2216,6 +2383,7 @@ int exchange_ready(mg_ctx *c)
 MG_EXPORT int mg_counters_allreduce(mg_ctx *c)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     TRY(exchange_ready(c));
     return exchange_rccl(c, c->stream);
@@ -2226,6 +2394,7 @@ MG_EXPORT int mg_counters_allreduce(mg_ctx *c)
 MG_EXPORT int mg_counters_allreduce_begin(mg_ctx *c)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     if (c->x_pending) return fail(c, MG_ERR_STATE, "mg_counters_allreduce_begin twice without mg_counters_allreduce_end");
     TRY(exchange_ready(c));
@@ -2240,6 +2409,7 @@ MG_EXPORT int mg_counters_allreduce_begin(mg_ctx *c)
 MG_EXPORT int mg_counters_allreduce_end(mg_ctx *c)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     if (!c->x_pending) return fail(c, MG_ERR_STATE, "mg_counters_allreduce_end without mg_counters_allreduce_begin");
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_xs[1], 0));
@@ -2265,6 +2435,8 @@ MG_EXPORT int mg_counters_allreduce_all(mg_ctx **ctxs, int n)
         if (!ctxs[i]) return MG_ERR_ARG;
     mg_ctx *c0 = ctxs[0];
     u64 nn = 0;
+    for (int i = 0; i < n; ++i)
+        if (ctxs[i]->coh_planes) return fail(ctxs[i], MG_ERR_STATE, "mg_counters_allreduce_all: context %d is in cohort mode (mg_cohort_end first)", i);
     for (int i = 0; i < n; ++i) {
         const DeviceGuard g(ctxs[i]);
         TRY(ensure_joined(ctxs[i]));
@@ -2763,6 +2935,86 @@ MG_EXPORT int mg_cover_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
     return MG_OK;
 }
 
+// The record loop for every plane of a cohort: tier 1 once over all planes (cohort_lone_kernel), tiers 2 and 3 plane by plane over the
+// general list tier 1 wrote once.  (The chain walks are repeated per plane: fw_walk_kernel also clears the plane's coverages and
+// reserves in the round's counter block what the kernels behind it consume, so a round's buffers serve one pass.)
+namespace {
+// slots = var_allele_off[n_vars], the distance between the planes of d_cov_out; 0: not known to the caller, read back from the device
+int cover_cohort(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, const void *d_var_block, const void *d_n_blocks, int haploid, void *d_cov_out,
+                 void *d_overflow_out, u64 slots_known)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (!c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cover_blocks_cohort_device: not in cohort mode (mg_cohort_begin first)");
+    TRY(check_panel(c, p, true));
+    if (p->n_vars == 0) return MG_OK;
+    if (!d_blk_var_off || !d_n_blocks || !d_cov_out || !d_overflow_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (!c->map.slots) TRY(map_reserve(c, 0));
+    for (auto &e : c->ev_c)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->blocks_stats_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev_c[0], c->stream));
+    BlocksRun R{};
+    TRY(blocks_setup(c, p, (const u32 *)d_blk_var_off, (const u32 *)d_var_block, (const unsigned long long *)d_n_blocks, haploid, &R));
+    const u64 n = p->n_vars;
+    u64 slots = slots_known; // the planes of d_cov_out are `slots` apart
+    if (!slots) {
+        u32 h_slots = 0;
+        HIP_TRY(c, hipMemcpyAsync(&h_slots, p->var_allele_off + n, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        slots = h_slots;
+    }
+    HIP_TRY(c, hipMemsetAsync(d_overflow_out, 0, n, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_gen_count, 0, 64, c->stream));
+    u32 *need_slow = (u32 *)(c->d_hit_count + 3);
+    if (++c->iso_call_no == 0) c->iso_call_no = 1;
+    const u32 sel = c->coh_sel;
+    c->coh_sel = 0; // tier 1's views address plane 0: the kernel walks the cells from there
+    const unsigned grid = (unsigned)((2 * n + (u64)LONE_TILES * TPB - 1) / ((u64)LONE_TILES * TPB));
+    hipLaunchKernelGGL(cohort_lone_kernel<false>, dim3(grid), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u64 *)c->d_ref2,
+                       (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, c->coh_planes, slots, need_slow,
+                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
+    hipLaunchKernelGGL(cohort_lone_kernel<true>, dim3(grid), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u64 *)c->d_ref2,
+                       (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, c->coh_planes, slots, need_slow,
+                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
+    int rc = hipGetLastError() == hipSuccess ? MG_OK : fail(c, MG_ERR_HIP, "cohort_lone_kernel launch failed");
+    if (rc == MG_OK && hipEventRecord(c->ev_c[1], c->stream) != hipSuccess) rc = fail(c, MG_ERR_HIP, "hipEventRecord failed");
+    for (u32 s = 0; s < c->coh_planes && rc == MG_OK; ++s) { // the other records, plane by plane, through the single-sample tiers
+        c->coh_sel = s;
+        u32 *cov = (u32 *)d_cov_out + (u64)s * slots;
+        if (hipMemsetAsync(R.fb_flag, 0, n, c->stream) != hipSuccess || hipMemsetAsync(c->d_gen_count + 3, 0, 16, c->stream) != hipSuccess) {
+            rc = fail(c, MG_ERR_HIP, "hipMemsetAsync failed");
+            break;
+        }
+        rc = blocks_tier2<0>(R, cov, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3);
+        if (rc == MG_OK) rc = blocks_tier3<0>(R, true, cov, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3);
+        if (rc != MG_OK) break;
+        hipLaunchKernelGGL(fw_finish_kernel, dim3(R.cus * 8), dim3(TPB), 0, c->stream, R.B, (const u32 *)R.gen_list, (const unsigned long long *)c->d_gen_count,
+                           (const u8 *)d_overflow_out, cov);
+        if (hipGetLastError() != hipSuccess) rc = fail(c, MG_ERR_HIP, "fw_finish_kernel launch failed");
+    }
+    c->coh_sel = sel;
+    TRY(rc);
+    HIP_TRY(c, hipEventRecord(c->ev_c[2], c->stream));
+    return MG_OK;
+}
+} // namespace
+MG_EXPORT int mg_cover_blocks_cohort_device(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, const void *d_var_block, const void *d_n_blocks, int haploid,
+                                            void *d_cov_out, void *d_overflow_out)
+{
+    return cover_cohort(c, p, d_blk_var_off, d_var_block, d_n_blocks, haploid, d_cov_out, d_overflow_out, 0);
+}
+// device milliseconds of the most recent mg_cover_blocks_cohort_device (waits for it): ms_out[0] tier 1 over all planes, [1] tiers 2-3 of all planes
+MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    if (!c->ev_c[2]) return fail(c, MG_ERR_STATE, "no mg_cover_blocks_cohort_device yet");
+    HIP_TRY(c, hipEventSynchronize(c->ev_c[2]));
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_c[i], c->ev_c[i + 1]));
+    return MG_OK;
+}
+
 // timing and counts of the most recent mg_cover_blocks_device (waits for it)
 MG_EXPORT int mg_blocks_stats(mg_ctx *c, float *ms_out, uint64_t *counts_out)
 {
@@ -2853,7 +3105,8 @@ namespace {
 int cover_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
                       const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
                       const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out);
+                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out,
+                      bool all_planes = false);
 int index_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
                       const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
                       const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
@@ -2879,12 +3132,25 @@ MG_EXPORT int mg_cover_blocks_sparse(mg_ctx *c, size_t n_blocks, const uint64_t 
     return cover_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
                              canon, nullptr, sp_off, sp_sample, sp_gt, sp_default, n_samples, haploid, cov_out, overflow_out);
 }
+// the batch goes up once and is covered for every plane of a context in cohort mode: cov_out is [n_planes][slots]
+MG_EXPORT int mg_cover_blocks_cohort(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
+                                     const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
+                                     const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
+                                     const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out,
+                                     uint8_t *overflow_out)
+{
+    if (c && !c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cover_blocks_cohort: not in cohort mode (mg_cohort_begin first)");
+    if (c && !gt && !sp_off) return fail(c, MG_ERR_ARG, "NULL argument");
+    return cover_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
+                             canon, sp_off ? nullptr : gt, sp_off, sp_sample, sp_gt, sp_default, n_samples, haploid, cov_out, overflow_out, true);
+}
 MG_EXPORT int mg_index_blocks_sparse(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off,
                                      size_t n_vars, const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present,
                                      const uint32_t *var_allele_off, const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
                                      const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid,
                                      uint8_t *overflow_out)
 {
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (c && !sp_off) return fail(c, MG_ERR_ARG, "NULL argument");
     return index_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
                              canon, nullptr, sp_off, sp_sample, sp_gt, sp_default, n_samples, haploid, overflow_out);
@@ -2894,7 +3160,8 @@ namespace {
 int cover_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
                       const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
                       const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out)
+                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out,
+                      bool all_planes)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
@@ -2906,11 +3173,13 @@ int cover_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, 
     TRY(upload_blocks(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
                       canon, gt, n_samples, &p, &d_bo, &d_vb, &d_nb, sp_off, sp_sample, sp_gt));
     p.sp_default = sp_default;
-    const size_t na = var_allele_off[n_vars];
+    const size_t planes = all_planes ? c->coh_planes : 1;
+    const size_t na = (size_t)var_allele_off[n_vars] * planes;
     void *d_cov, *d_ovf;
     TRY(scratch(c, c->s_out, 4 * na, &d_cov));
     TRY(scratch(c, c->s_irr, n_vars, &d_ovf));
-    TRY(mg_cover_blocks_device(c, &p, d_bo, d_vb, d_nb, haploid, d_cov, d_ovf));
+    if (all_planes) TRY(cover_cohort(c, &p, d_bo, d_vb, d_nb, haploid, d_cov, d_ovf, var_allele_off[n_vars]));
+    else TRY(mg_cover_blocks_device(c, &p, d_bo, d_vb, d_nb, haploid, d_cov, d_ovf));
     HIP_TRY(c, hipMemcpyAsync(cov_out, d_cov, 4 * na, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(overflow_out, d_ovf, n_vars, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2924,6 +3193,7 @@ MG_EXPORT int mg_index_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
                                      void *d_overflow_out)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     TRY(check_panel(c, p, true));
     if (p->n_vars == 0) return MG_OK;
@@ -2968,6 +3238,7 @@ MG_EXPORT int mg_index_blocks(mg_ctx *c, size_t n_blocks, const uint64_t *blk_re
                               const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt,
                               uint32_t n_samples, int haploid, uint8_t *overflow_out)
 {
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     return index_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
                              canon, gt, nullptr, nullptr, nullptr, 0, n_samples, haploid, overflow_out);
 }
@@ -3001,6 +3272,7 @@ MG_EXPORT int mg_index_isolated(mg_ctx *c, size_t n_vars, const uint64_t *pos, c
                                 const char *allele_pool, size_t pool_len, const uint64_t *present_mask, const uint8_t *flags, uint8_t *overflow_out)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (!c) return MG_ERR_ARG;
     if (n_vars == 0) return MG_OK;
     if (!pos || !var_allele_off || !allele_off || !allele_pool || !present_mask || !flags || !overflow_out) return fail(c, MG_ERR_ARG, "NULL argument");
@@ -3293,7 +3565,14 @@ MG_EXPORT int mg_bf_export(mg_ctx *c, int which, uint64_t *words_out, uint16_t *
     if (counts_out && b.mode && b.nset) {
         void *d16;
         TRY(scratch(c, c->s_out, b.nset * 2, &d16));
-        hipLaunchKernelGGL(mask_u16_kernel, dim3(nblocks(b.nset)), dim3(TPB), 0, c->stream, (const u32 *)b.counts, (uint16_t *)d16,
+        const u32 *src = b.counts;
+        if (which == MG_BF_ALT && c->coh_planes) { // the selected plane
+            void *d32;
+            TRY(scratch(c, c->s_aux, b.nset * 4, &d32));
+            TRY(plane_gather(c, (u32 *)d32, nullptr));
+            src = (const u32 *)d32;
+        }
+        hipLaunchKernelGGL(mask_u16_kernel, dim3(nblocks(b.nset)), dim3(TPB), 0, c->stream, src, (uint16_t *)d16,
                            b.nset);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(counts_out, d16, b.nset * 2, hipMemcpyDeviceToHost, c->stream));
@@ -3304,6 +3583,7 @@ MG_EXPORT int mg_bf_export(mg_ctx *c, int which, uint64_t *words_out, uint16_t *
 MG_EXPORT int mg_bf_import(mg_ctx *c, int which, int mode, uint64_t size_bits, const uint64_t *words, const uint16_t *counts,
                            uint64_t n_counts)
 {
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (c && (which == MG_BF_ALT || which == MG_BF_CTX)) c->bf[which].pos_set_valid = false;
     const DeviceGuard on_device(c);
     TRY(check_which(c, which));
@@ -3360,6 +3640,7 @@ MG_EXPORT int mg_bf_export_sparse(mg_ctx *c, int which, uint64_t *positions_out,
 MG_EXPORT int mg_bf_import_sparse(mg_ctx *c, int which, int mode, uint64_t size_bits, const uint64_t *positions,
                                   const uint16_t *counts, uint64_t n)
 {
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     if (c && (which == MG_BF_ALT || which == MG_BF_CTX)) c->bf[which].pos_set_valid = false;
     const DeviceGuard on_device(c);
     TRY(check_which(c, which));
@@ -3426,7 +3707,13 @@ MG_EXPORT int mg_map_export(mg_ctx *c, char *rows_out, size_t stride, int32_t *v
     if (!rows_out && !vals_out) return MG_OK;
     if (stride < c->k + 1) return fail(c, MG_ERR_ARG, "stride %zu < k+1", stride);
     std::vector<u32> vals(c->map.rows_total);
-    if (c->map.rows_total) HIP_TRY(c, hipMemcpy(vals.data(), c->map.vals, c->map.rows_total * 4, hipMemcpyDeviceToHost));
+    if (c->map.rows_total && c->coh_planes) { // the selected plane
+        void *d32;
+        TRY(scratch(c, c->s_aux, c->map.rows_total * 4, &d32));
+        TRY(plane_gather(c, nullptr, (u32 *)d32));
+        HIP_TRY(c, hipMemcpyAsync(vals.data(), d32, c->map.rows_total * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (c->map.rows_total) HIP_TRY(c, hipMemcpy(vals.data(), c->map.vals, c->map.rows_total * 4, hipMemcpyDeviceToHost));
     size_t j = 0;
     for (; j < lo.size(); ++j) {
         if (rows_out) {
@@ -3448,6 +3735,7 @@ MG_EXPORT int mg_map_export(mg_ctx *c, char *rows_out, size_t stride, int32_t *v
 MG_EXPORT int mg_map_import(mg_ctx *c, const char *rows, size_t stride, size_t n, const int32_t *vals)
 {
     const DeviceGuard on_device(c);
+    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
     TRY(check_rows(c, rows, stride, n));
     if (n == 0) return MG_OK;
     TRY(mg_map_insert(c, rows, stride, n));
@@ -3500,6 +3788,7 @@ struct ReadsState {
 };
 
 namespace {
+bool reads_unfinished(const mg_ctx *c) { return c->reads && !c->reads->finished; }
 void reads_drop(mg_ctx *c)
 {
     ReadsState *R = c->reads;

@@ -1338,7 +1338,7 @@ __global__ void __launch_bounds__(TPB) scan_probe_kernel(int k_rt, int r_rt, BFV
             u64 slot = 0, ent = 0;
             bucket_probe_coop(map, c, h, idx, live, &id, &rank, &slot, &ent); // (whole waves: the records are fetched four lanes to a record)
             if (id >= 0) {
-                atomicAdd(&map.vals[id], count); // ref_bf.increment (main.cpp:495)
+                atomicAdd(map_cell(map, (u32)id), count); // ref_bf.increment (main.cpp:495)
                 if (map.epoch) rec_add_val(&map.slots[slot], map.epoch, count); // ... and the record's copy, on the line just read
             }
             hit = rank >= 0;
@@ -1427,7 +1427,7 @@ __global__ void __launch_bounds__(TPB) scan_sub_probe_kernel(int k_rt, int r_rt,
                         const U128 cc = canon_sub(m, mform_to_lform(m, r), r, 0, r);
                         const u64 cidx = mod_size(xxh3_packed_k<RC>(cc, r), ctx.mod);
                         if (!bf_bit_via_set(ctx, cidx)) {                     // context_bf.test_key (main.cpp:496)
-                            if (!map.lazy) atomicAdd(&bf.counts[e ? b.w : b.z], count); // bf.increment (main.cpp:498)
+                            if (!map.lazy) atomicAdd(bf_cell(bf, e ? b.w : b.z), count); // bf.increment (main.cpp:498)
                             if (map.epoch) rec_add_bf_from(&map.slots[s], e, map.epoch, count, d.z | (unsigned long long)d.w << 32); // ... and its copy in the record
                         }
                     } else if (b0 == 0 || b1 == 0)
@@ -1438,7 +1438,7 @@ __global__ void __launch_bounds__(TPB) scan_sub_probe_kernel(int k_rt, int r_rt,
                     if (a.x == 0) map_open = false;
                     else if (a.z == (u32)key.lo && a.w == (u32)(key.lo >> 32) && b.x == (u32)key.hi && b.y == (u32)(key.hi >> 32)) {
                         map_open = false;
-                        if (!map.lazy) atomicAdd(&map.vals[a.y], count); // ref_bf.increment (main.cpp:495)
+                        if (!map.lazy) atomicAdd(map_cell(map, a.y), count); // ref_bf.increment (main.cpp:495)
                         if (map.epoch) rec_add_val_from(&map.slots[s], map.epoch, count, d.x | (unsigned long long)d.y << 32); // ... and the record's copy, on the line just read
                     }
                 }
@@ -1483,7 +1483,7 @@ __global__ void __launch_bounds__(TPB) scan_hits_kernel(int k_rt, int r_rt, BFVi
             const bool in_ctx = live && bf_bit_via_set(ctx, cidx);        // context_bf.test_key (main.cpp:496)
             if (live && !in_ctx) {
                 const u64 x = hits.aux[j];
-                atomicAdd(&bf.counts[(u32)x], hits.cnt[j]);               // bf.increment (main.cpp:498)
+                atomicAdd(bf_cell(bf, (u32)x), hits.cnt[j]);               // bf.increment (main.cpp:498)
                 if (map.epoch) rec_add_bf(&map.slots[(x >> 32) >> 1], (int)((x >> 32) & 1), map.epoch, hits.cnt[j]);
             }
             continue;
@@ -1493,7 +1493,7 @@ __global__ void __launch_bounds__(TPB) scan_hits_kernel(int k_rt, int r_rt, BFVi
         u64 ent = 0;
         const long long rank = bucket_rank_coop(map, idx, live, &ent);    // set for every row of this list
         if (!in_ctx && rank >= 0) {
-            atomicAdd(&bf.counts[rank], hits.cnt[j]); // bf.increment (main.cpp:498)
+            atomicAdd(bf_cell(bf, (u32)rank), hits.cnt[j]); // bf.increment (main.cpp:498)
             if (map.epoch) rec_add_bf(&map.slots[ent >> 1], (int)(ent & 1), map.epoch, hits.cnt[j]);
         }
     }

@@ -60,9 +60,9 @@ __global__ void __launch_bounds__(TPB) rows_kernel(const u8 *rows, size_t stride
         }
         if (irregular) irregular[i] = regular ? 0 : 1;
         if (OP == OP_MAP_TEST) ((u8 *)out)[i] = s >= 0;
-        if (OP == OP_MAP_INC && s >= 0) atomicAdd(&map.vals[s], counters[i]);
-        if (OP == OP_MAP_SET && s >= 0) map.vals[s] = counters[i]; // index load: the stored value of an imported key
-        if (OP == OP_MAP_GET || OP == OP_WEIGHT) ((i32 *)out)[i] = s >= 0 ? (i32)map.vals[s] : 0;
+        if (OP == OP_MAP_INC && s >= 0) atomicAdd(map_cell(map, (u32)s), counters[i]);
+        if (OP == OP_MAP_SET && s >= 0) *map_cell(map, (u32)s) = counters[i]; // index load: the stored value of an imported key
+        if (OP == OP_MAP_GET || OP == OP_WEIGHT) ((i32 *)out)[i] = s >= 0 ? (i32)*map_cell(map, (u32)s) : 0;
         return;
     }
     const u64 idx = mod_size(xxh3_bytes(can, k), bf.mod);
@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(TPB) rows_kernel(const u8 *rows, size_t stride
     if (OP == OP_BF_TEST) ((u8 *)out)[i] = bf_bit(bf, idx);
     if (OP == OP_BF_INC) {
         u32 r;
-        if (bf_bit_rank(bf, idx, &r)) atomicAdd(&bf.counts[r], counters[i]);
+        if (bf_bit_rank(bf, idx, &r)) atomicAdd(bf_cell(bf, r), counters[i]);
     }
     if (OP == OP_BF_GET) ((uint16_t *)out)[i] = bf.counts ? (uint16_t)bf_count_at(bf, idx) : 0;
     if (OP == OP_WEIGHT) ((i32 *)out)[i] = bf.counts ? (i32)(uint16_t)bf_count_at(bf, idx) : 0;
@@ -112,7 +112,7 @@ __device__ __forceinline__ void map_insert_key(const MapView &map, const BFView 
             const u64 b = __hip_atomic_load(&map.slots[s].khi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (a == key.lo && b == key.hi) {
                 const u32 old = atomicMin(&map.slots[s].id, my_id);
-                if (old < row0) map.vals[old] = 0; // kmers[ckmer] = 0 on a key from an earlier call
+                if (old < row0) *map_cell(map, old) = 0; // kmers[ckmer] = 0 on a key from an earlier call
                 done = true;
                 continue;
             }
@@ -386,6 +386,8 @@ __global__ void __launch_bounds__(TPB) widen_u16_kernel(const uint16_t *in, u32 
 // the record of its key, counts[rank] to the record entry of its set bit -- so one pass over the table writes them all; a copy
 // of an older epoch is zero.  The filter's counters come back as the reference's u16 cells (the vector's upper halves, which
 // only ever matter modulo 2^16, restart at zero).
+// (rec_collect_kernel and rec_publish_kernel index vals[] / counts[] without the planes' stride: a context in cohort mode keeps no
+// copies in the records -- records_wanted() -- so neither kernel ever runs there)
 __global__ void __launch_bounds__(TPB) rec_collect_kernel(MapView m, u32 *__restrict__ counts, u32 epoch)
 {
     const u64 n = 1ULL << m.cap_log2;

@@ -133,10 +133,13 @@ constexpr u32 ISO_SLOW = 0xFFFFFFFFu; // never a coverage: those are float-round
 // pm = mask of the alleles some panel haplotype carries, live = eligible (var_block.hpp:104)
 // ref2 / refbad: the packed reference (scan_kernels.h); the flanks come out of it in two loads and a shift each, and a
 // 128-byte line of it holds 512 bases (five SNPs of a whole-genome panel share one, against one line of text each)
-template <bool SLOW>
+// COH (cohort mode, cohort_lone_kernel): everything up to the record is done once -- it does not depend on the sample -- and the
+// record's n_planes cells, which lie side by side (BFView::cshift), are read as one run and written to the planes of cov_out
+// (plane s at cov_out + s * plane_stride); the rule that turns a counter into a coverage is the same expression per plane.
+template <bool SLOW, bool COH = false>
 __device__ __forceinline__ void iso_cover_body(const u8 *reference, const u64 *__restrict__ ref2, const u32 *__restrict__ refbad, u64 site_off, u32 a0, u32 A, bool live,
                                                u64 pm_in, u32 par, const u32 *allele_off, const u8 *pool, int k, const BFView &bf, const MapView &map, u32 *cov_out,
-                                               u32 *need_slow, u32 call_no)
+                                               u32 *need_slow, u32 call_no, u32 n_planes = 1, u64 plane_stride = 0)
 {
     const u32 ref_size = allele_off[a0 + 1] - allele_off[a0];
     u32 *cov = cov_out + a0;
@@ -163,6 +166,16 @@ __device__ __forceinline__ void iso_cover_body(const u8 *reference, const u64 *_
             if (cov[a] != ISO_SLOW) continue;
             const int alen = (int)(allele_off[a0 + a + 1] - allele_off[a0 + a]);
             const int mp = k / 2 - alen / 2;
+            if (COH) { // (rare: a base outside ACGT in reach.  The bytes are hashed again for every plane)
+                BFView bs = bf;
+                MapView ms = map;
+                for (u32 s = 0; s < n_planes; ++s) {
+                    bs.coff = ms.coff = s;
+                    const i32 w = weight_bytes(SigIn{site - mp, pool + allele_off[a0 + a], site + ref_size, mp, alen}, k, a == 0, bs, ms);
+                    cov[s * plane_stride + a] = w > 0 ? (u32)(float)(u32)w : 0;
+                }
+                continue;
+            }
             const i32 w = weight_bytes(SigIn{site - mp, pool + allele_off[a0 + a], site + ref_size, mp, alen}, k, a == 0, bf, map);
             cov[a] = w > 0 ? (u32)(float)(u32)w : 0;
             continue;
@@ -202,10 +215,48 @@ __device__ __forceinline__ void iso_cover_body(const u8 *reference, const u64 *_
                 const U128 key = lt128(L, rc) ? L : rc;
                 const u64 h = k == 35 ? xxh3_packed_fixed<35>(key.lo, key.hi) : xxh3_packed(key, k);
                 const u64 idx = mod_size(h, bf.mod);
+                if (COH) { // the record once, then its cells: 16 planes to a 64-byte line, four to a load
+                    const u32 *cells = nullptr;
+                    if (a == 0) {
+                        const long long id = map_find_id(map, key, h, idx);
+                        if (id >= 0) cells = map.vals + ((u64)(u32)id << map.cshift);
+                    } else {
+                        const long long rank = bucket_rank(map, idx);
+                        if (rank >= 0) cells = bf.counts + ((u64)(u32)rank << bf.cshift);
+                    }
+                    const u32 lowmask = a == 0 ? 0xFFFFFFFFu : 0xFFFFu; // KMAP::get_count is an int, BF::get_count the u16 cell
+                    if (bf.cshift >= 2) { // (a cell group of four or more is 16-byte aligned and padded to whole groups)
+                        for (u32 s = 0; s < n_planes; s += 16) { // a 64-byte line of cells: its four loads requested together, then the stores
+                            uint4 q[4];
+#pragma unroll
+                            for (u32 g = 0; g < 4; ++g) q[g] = cells && s + 4 * g < n_planes ? *reinterpret_cast<const uint4 *>(cells + s + 4 * g) : uint4{0, 0, 0, 0};
+#pragma unroll
+                            for (u32 g = 0; g < 4; ++g) {
+                                const u32 c4[4] = {q[g].x, q[g].y, q[g].z, q[g].w};
+#pragma unroll
+                                for (u32 j = 0; j < 4; ++j)
+                                    if (s + 4 * g + j < n_planes) {
+                                        const i32 wj = (i32)(c4[j] & lowmask);
+                                        cov[(s + 4 * g + j) * plane_stride + a] = wj > 0 ? (u32)(float)(u32)wj : 0;
+                                    }
+                            }
+                        }
+                    } else {
+                        for (u32 s = 0; s < n_planes; ++s) {
+                            const i32 ws = cells ? (i32)(cells[s] & lowmask) : 0;
+                            cov[s * plane_stride + a] = ws > 0 ? (u32)(float)(u32)ws : 0;
+                        }
+                    }
+                    continue;
+                }
                 if (a == 0) w = map_value(map, key, h, idx);
-                else w = (i32)bucket_count(map, bf.counts, idx); // the filter's directory entry sits in the exact map's record of the same slot
+                else w = (i32)bucket_count(map, bf, idx); // the filter's directory entry sits in the exact map's record of the same slot
                 if (w > 0) out = (u32)(float)(u32)w;
             }
+        }
+        if (COH) {
+            for (u32 s = 0; s < n_planes; ++s) cov[s * plane_stride + a] = out; // (0 or the mark: neither depends on the sample)
+            continue;
         }
         cov[a] = out;
     }

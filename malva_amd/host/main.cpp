@@ -27,6 +27,7 @@
 #include "index_file.hpp"
 #include "kmc_db.hpp"
 #include "reads.hpp"
+#include "cohort.hpp"
 extern "C" {
 #include "malva_hip.h"
 }
@@ -58,6 +59,15 @@ const char *USAGE =
     "                                        are all-reduced over RCCL, the variants are split between them\n"
     "          --min-count                   READS only: drop k-mers seen fewer times (default:2, KMC -ci; 0 = 1)  [this build]\n"
     "          --max-count                   READS only: cap counts at this value (default:255, KMC -cs)             [this build]\n"
+    "          --cohort                      call: the third argument is a manifest, one sample per line NAME<tab>INPUT ('#' lines\n"
+    "                                        and blank lines skipped; INPUT as the third argument of call, relative paths relative\n"
+    "                                        to the manifest); needs -o; not with --gpus > 1                        [this build]\n"
+    "      -o, --out-dir                     --cohort: directory that receives NAME.vcf per sample, each byte for byte what\n"
+    "                                        `call` with that INPUT prints to stdout                                 [this build]\n"
+    "          --cohort-group                --cohort: samples held on the GPU at once, 1..64 (default: all of them, at most 64,\n"
+    "                                        halved while their counters do not fit in HBM beside the index).  A cohort of any\n"
+    "                                        size runs as groups of that many; the index is loaded once, the panel VCF is read\n"
+    "                                        again for every group (it does not stay resident across groups)          [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -85,6 +95,9 @@ struct Options { // argument_parser.hpp:51-66
     int device = 0, gpus = 1;
     uint32_t min_count = 2, max_count = 255; // READS: KMC's -ci / -cs defaults (MALVA:107)
     std::string fasta_path, vcf_path, kmc_path;
+    bool cohort = false;    // kmc_path is a manifest (host/cohort.hpp)
+    std::string out_dir;    // -o
+    int cohort_group = 0;   // 0: as many as fit, at most 64
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -100,10 +113,12 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"device", required_argument, nullptr, 'd'},      {"help", no_argument, nullptr, 'h'},
                                       {"gpus", required_argument, nullptr, 'g'},
                                       {"min-count", required_argument, nullptr, 1001}, {"max-count", required_argument, nullptr, 1002},
+                                      {"cohort", no_argument, nullptr, 1003},          {"cohort-group", required_argument, nullptr, 1004},
+                                      {"out-dir", required_argument, nullptr, 'o'},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
-    for (int c; (c = getopt_long(argc, argv, "k:r:e:s:f:c:b:d:g:hpuv1", longopts, nullptr)) != -1;) {
+    for (int c; (c = getopt_long(argc, argv, "k:r:e:s:f:c:b:d:g:o:hpuv1", longopts, nullptr)) != -1;) {
         std::istringstream arg(optarg ? optarg : "");
         switch (c) {
         case 'p': o.strip_chr = true; break;
@@ -130,6 +145,14 @@ bool parse_arguments(int argc, char **argv, Options &o)
             else o.max_count = (uint32_t)v;
             break;
         }
+        case 1003: o.cohort = true; break;
+        case 1004:
+            if (!(arg >> o.cohort_group) || o.cohort_group < 1 || o.cohort_group > 64) {
+                std::cerr << "malva : --cohort-group takes 1..64\n";
+                die = true;
+            }
+            break;
+        case 'o': o.out_dir = optarg; break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -145,6 +168,18 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.gpus < 1 || o.gpus > 64) {
         std::cerr << "malva : --gpus must be 1..64\n";
+        die = true;
+    }
+    if (o.cohort && o.out_dir.empty()) {
+        std::cerr << "malva : --cohort needs -o OUTDIR\n";
+        die = true;
+    }
+    if (o.cohort && o.gpus > 1) {
+        std::cerr << "malva : --cohort does not combine with --gpus > 1\n";
+        die = true;
+    }
+    if (!o.cohort && (!o.out_dir.empty() || o.cohort_group)) {
+        std::cerr << "malva : -o and --cohort-group go with --cohort\n";
         die = true;
     }
     if (die) {
@@ -234,11 +269,6 @@ struct Rows {
     }
 };
 
-bool file_exists(const std::string &p)
-{
-    struct stat st;
-    return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-}
 // main.cpp:407 / :456: <vcf>.c<ref_k>.k<k>.malvax + ".zst" (the reference's container) or ".hipz" (this build's compact one)
 std::string index_path(const Options &o, const char *suffix)
 {
@@ -1302,12 +1332,15 @@ int call_main(const Options &o)
     });
     IndexPayload payload;
     auto index_read = std::async(std::launch::async, [&]() { read_index(o, payload); });
-    VcfReader vcf(o.vcf_path, o.samples); // (a panel of any size is decoded by a pool of threads: started here, it works through start-up)
-    if (vcf.ok()) {
-        vcf.want_prefix = true;
-        vcf.defer_genotypes = device_gt_wanted(vcf) && !getenv("MALVA_GENO_HOST_CUT"); // (the decode rides on the device cutter's batches)
-        vcf.decode_ahead(o.freq_key, o.uniform);
-    }
+    auto start_vcf = [&](VcfReader &r) {
+        if (r.ok()) {
+            r.want_prefix = true;
+            r.defer_genotypes = device_gt_wanted(r) && !getenv("MALVA_GENO_HOST_CUT"); // (the decode rides on the device cutter's batches)
+            r.decode_ahead(o.freq_key, o.uniform);
+        }
+    };
+    std::unique_ptr<VcfReader> vcf_first(new VcfReader(o.vcf_path, o.samples)); // (a panel of any size is decoded by a pool of threads: started here, it works through start-up)
+    start_vcf(*vcf_first);
     auto fail_early = [&](const std::string &msg) { // (the readers hold references to this frame: let them finish first)
         fasta_read.wait();
         index_read.wait();
@@ -1315,27 +1348,14 @@ int call_main(const Options &o)
         return 1;
     };
     // the sample's k-mers: the KMC database the reference opens (main.cpp:444-449), or -- when there is none -- a text dump
-    // or the reads themselves, counted on the devices (MALVA:104-110)
-    std::string table = o.kmc_path;
-    const bool use_db = KmcDb::present(o.kmc_path);
-    std::vector<std::string> read_files;
-    bool use_reads = false;
-    if (!use_db) {
-        if (file_exists(o.kmc_path + ".txt")) table = o.kmc_path + ".txt";
-        else {
-            try {
-                use_reads = reads_input(o.kmc_path, &read_files);
-                if (use_reads) {
-                    if (o.ref_k > MG_MAX_PACKED_K)
-                        return fail_early("ERROR: counting reads needs -r <= " + std::to_string(MG_MAX_PACKED_K) + " (the packed k-mer paths; -r " + std::to_string(o.ref_k) +
-                                          "): give a k-mer table instead");
-                    reads_check_heads(read_files); // (before any device: a file that is not reads fails at once)
-                }
-            } catch (const std::exception &e) {
-                return fail_early(e.what());
-            }
-        }
-        if (!use_reads && !file_exists(table)) return fail_early("ERROR: cannot open " + o.kmc_path);
+    // or the reads themselves, counted on the devices (MALVA:104-110).  --cohort: a manifest of such inputs, all of them
+    // resolved and checked here, before any device exists and before anything is written.
+    std::vector<CohortSample> samples;
+    try {
+        if (o.cohort) samples = read_cohort_manifest(o.kmc_path, o.ref_k, MG_MAX_PACKED_K);
+        else samples.push_back({std::string(), resolve_sample_input(o.kmc_path, o.ref_k, MG_MAX_PACKED_K)});
+    } catch (const std::exception &e) {
+        return fail_early(e.what());
     }
     // --gpus N: one context per device -d .. -d+N-1.  MALVA_GENO_SHARE_DEVICE=1 puts all N contexts on device -d: the
     // N-way layout (sharded scan, exchange, split genotyping) rehearsed on a one-GPU box, the exchange then being a
@@ -1365,11 +1385,14 @@ int call_main(const Options &o)
     import_index(devs, o, payload);
     payload = IndexPayload();
     pelapsed("Reference processed"); // (the phase names are the reference's, main.cpp:452-470; the FASTA itself may still be on its way)
-    {
+    auto scan_sample = [&](const SampleInput &in) {
+        if (in.kind == SampleInput::READS) count_reads(devs, o, in.reads); // MALVA:104-110 + main.cpp:482-500
+        else if (in.kind == SampleInput::KMC_DB) scan_kmc_db(devs, o, in.path); // main.cpp:482-500
+        else scan_table(devs, o, in.path);
+    };
+    if (!o.cohort) {
         Timed t("startup: table scan");
-        if (use_reads) count_reads(devs, o, read_files); // MALVA:104-110 + main.cpp:482-500
-        else if (use_db) scan_kmc_db(devs, o, o.kmc_path); // main.cpp:482-500
-        else scan_table(devs, o, table);
+        scan_sample(samples[0].input);
     }
     pelapsed("BF weights created");
     if (!fasta_read.get()) {
@@ -1388,20 +1411,31 @@ int call_main(const Options &o)
         Timed t("startup: reference upload");
         on_all_devices(devs, [&](Device &d, size_t) { d.check(mg_reference_upload(d.ctx, all.data(), all.size()), "mg_reference_upload"); });
     }
+    std::atomic<size_t> gt_bytes_uploaded{0}; // panel genotypes handed to mg_cover_blocks[_sparse], all batches
+    std::string header_text;
     {
         VcfReader hdr(o.vcf_path, "-");
         if (!hdr.ok()) {
             std::cerr << hdr.error << std::endl;
             return 1;
         }
-        std::cout << cleaned_header(hdr.header_lines, o.verbose); // main.cpp:505-510
-        std::cout.flush();
+        header_text = cleaned_header(hdr.header_lines, o.verbose); // main.cpp:505-510
     }
-    if (!vcf.ok()) {
-        std::cerr << vcf.error << std::endl;
+    if (!vcf_first->ok()) {
+        std::cerr << vcf_first->error << std::endl;
         return 1;
     }
+    if (!o.cohort) {
+        std::cout << header_text;
+        std::cout.flush();
+    }
     pelapsed("VCF parsing and genotyping");
+
+    // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to outs[0] (stdout).  planes > 0: the
+    // context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
+    // only the INFO and GT:GQ fields per sample; sample p's text goes to outs[p].
+    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs) -> size_t {
+    const size_t P = planes ? planes : 1;
 
     // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
     const size_t batch_records = getenv("MALVA_GENO_BATCH") ? (size_t)std::max(1L, atol(getenv("MALVA_GENO_BATCH"))) : 200000;
@@ -1411,7 +1445,6 @@ int call_main(const Options &o)
     const size_t n_samples_kept = vcf.keep.size();
     const bool dense_gt = n_samples_kept <= SPARSE_GT_SAMPLES && !vcf.defer_genotypes;
     gen.dense_gt = dense_gt;
-    std::atomic<size_t> gt_bytes_uploaded{0}; // panel genotypes handed to mg_cover_blocks[_sparse], all batches
     const std::string best_default = o.haploid ? "0" : "0/0";
     auto n_gt = [&](uint64_t A) { return o.haploid ? A : A * (A + 1) / 2; };
 
@@ -1422,26 +1455,29 @@ int call_main(const Options &o)
         Batch iso, gen;
         size_t device = 0; // batches go round the devices: after the exchange every one of them holds the whole table's counters
     };
-    auto process = [&](Job &job) -> std::string {
+    auto process = [&](Job &job) -> std::vector<std::string> {
         std::vector<Rec> &recs = job.recs;
         Batch &iso = job.iso, &gen = job.gen;
         Device &dev = devs[job.device];
         Timed *t_dev = new Timed("worker: device calls");
         std::unique_lock<std::mutex> device_lock(dev.mu); // (the parsing thread cuts blocks on device 0 meanwhile)
         if (iso.n()) {
-            const size_t n = iso.n(), na = iso.var_allele_off.back();
-            iso.cov.resize(na); iso.g1.resize(n); iso.g2.resize(n); iso.gq.resize(n); iso.status.resize(n);
-            iso.probs.resize(o.verbose ? iso.var_gt_off.back() : 0);
-            dev.check(mg_call_isolated(dev.ctx, n, iso.pos.data(), iso.var_allele_off.data(), iso.allele_off.data(), iso.pool.data(), iso.pool.size(),
-                                       iso.freq.data(), iso.present.data(), iso.flags.data(), o.error_rate, (int)o.max_coverage, o.haploid, iso.cov.data(),
-                                       iso.g1.data(), iso.g2.data(), iso.gq.data(), iso.status.data(), o.verbose ? iso.probs.data() : nullptr,
-                                       o.verbose ? iso.var_gt_off.data() : nullptr),
-                      "mg_call_isolated");
+            const size_t n = iso.n(), na = iso.var_allele_off.back(), ng = o.verbose ? iso.var_gt_off.back() : 0;
+            iso.cov.resize(P * na); iso.g1.resize(P * n); iso.g2.resize(P * n); iso.gq.resize(P * n); iso.status.resize(P * n);
+            iso.probs.resize(P * ng);
+            for (size_t pl = 0; pl < P; ++pl) { // (the fused lone-variant call reads the selected plane)
+                if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
+                dev.check(mg_call_isolated(dev.ctx, n, iso.pos.data(), iso.var_allele_off.data(), iso.allele_off.data(), iso.pool.data(), iso.pool.size(),
+                                           iso.freq.data(), iso.present.data(), iso.flags.data(), o.error_rate, (int)o.max_coverage, o.haploid, iso.cov.data() + pl * na,
+                                           iso.g1.data() + pl * n, iso.g2.data() + pl * n, iso.gq.data() + pl * n, iso.status.data() + pl * n,
+                                           o.verbose ? iso.probs.data() + pl * ng : nullptr, o.verbose ? iso.var_gt_off.data() : nullptr),
+                          "mg_call_isolated");
+            }
         }
         if (gen.n()) {
-            const size_t n = gen.n(), na = gen.var_allele_off.back();
-            gen.cov.resize(na); gen.g1.resize(n); gen.g2.resize(n); gen.gq.resize(n); gen.status.resize(n);
-            gen.probs.resize(o.verbose ? gen.var_gt_off.back() : 0);
+            const size_t n = gen.n(), na = gen.var_allele_off.back(), ng = o.verbose ? gen.var_gt_off.back() : 0;
+            gen.cov.resize(P * na); gen.g1.resize(P * n); gen.g2.resize(P * n); gen.gq.resize(P * n); gen.status.resize(P * n);
+            gen.probs.resize(P * ng);
             // panel genotypes of the batch as one [variant][sample] matrix of a1 | a2 << 7 | phased << 14
             const uint32_t n_samples = (uint32_t)vcf.keep.size();
             std::vector<uint8_t> overflow(n, 0);
@@ -1452,7 +1488,15 @@ int call_main(const Options &o)
             if (gen.dense_gt) pg.gt = std::move(gen.gt_dense);
             else pg = pack_genotypes(gen.vars, n, n_samples, o.haploid); // (every record of such a batch is kept)
             gt_bytes_uploaded += pg.bytes();
-            if (device_ok && pg.sparse)
+            if (device_ok && planes) // the batch goes up once and is covered for every plane (cov: [planes][na])
+                dev.check(mg_cover_blocks_cohort(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
+                                                 gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
+                                                 gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sparse ? nullptr : pg.gt.data(),
+                                                 pg.sparse ? pg.sp_off.data() : nullptr, pg.sparse ? pg.sp_sample.data() : nullptr,
+                                                 pg.sparse ? pg.sp_gt.data() : nullptr, pg.sparse ? pg.sp_default : (uint16_t)0, n_samples, o.haploid, gen.cov.data(),
+                                                 overflow.data()),
+                          "mg_cover_blocks_cohort");
+            else if (device_ok && pg.sparse)
                 dev.check(mg_cover_blocks_sparse(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
                                                  gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
                                                  gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sp_off.data(), pg.sp_sample.data(),
@@ -1498,27 +1542,34 @@ int call_main(const Options &o)
                         al_off.push_back(sig_off.size() - 1);
                     }
                 const size_t slot0 = gen.var_allele_off[gen.blk_var_off[b]];
-                dev.check(mg_lookup_cover(dev.ctx, rows.data.data(), STRIDE, rows.n, is_ref.data(), sig_off.data(), sig_off.size() - 1, al_off.data(),
-                                          al_off.size() - 1, gen.cov.data() + slot0),
-                          "mg_lookup_cover");
+                for (size_t pl = 0; pl < P; ++pl) { // (enumerated once; the lookups read the selected plane)
+                    if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
+                    dev.check(mg_lookup_cover(dev.ctx, rows.data.data(), STRIDE, rows.n, is_ref.data(), sig_off.data(), sig_off.size() - 1, al_off.data(),
+                                              al_off.size() - 1, gen.cov.data() + pl * na + slot0),
+                              "mg_lookup_cover");
+                }
             }
             if (n_fallback) std::cerr << "[malva-geno] " << n_fallback << " block(s) enumerated on the host" << std::endl;
-            dev.check(mg_genotype(dev.ctx, gen.cov.data(), gen.freq.data(), gen.var_allele_off.data(), n, o.error_rate, (int)o.max_coverage, o.haploid,
-                                  gen.g1.data(), gen.g2.data(), gen.gq.data(), gen.status.data(), o.verbose ? gen.probs.data() : nullptr,
-                                  o.verbose ? gen.var_gt_off.data() : nullptr),
-                      "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
+            for (size_t pl = 0; pl < P; ++pl)
+                dev.check(mg_genotype(dev.ctx, gen.cov.data() + pl * na, gen.freq.data(), gen.var_allele_off.data(), n, o.error_rate, (int)o.max_coverage, o.haploid,
+                                      gen.g1.data() + pl * n, gen.g2.data() + pl * n, gen.gq.data() + pl * n, gen.status.data() + pl * n,
+                                      o.verbose ? gen.probs.data() + pl * ng : nullptr, o.verbose ? gen.var_gt_off.data() : nullptr),
+                          "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
         }
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
-        std::string out;
+        std::vector<std::string> outv(P);
         char num[64];
-        for (const Rec &r : recs) { // output_variants, var_block.hpp:337-396
+        for (const Rec &r : recs) // output_variants, var_block.hpp:337-396
+          for (size_t pl = 0; pl < P; ++pl) {
             const Batch &b = r.isolated ? iso : gen;
+            std::string &out = outv[pl];
+            const size_t bn = b.n(), bna = b.var_allele_off.back(), bng = b.probs.size() / P;
             out += r.prefix;
             out += "\tPASS\t";
-            const uint32_t *cov = &b.cov[r.allele0];
-            const uint8_t st = b.status[r.slot];
+            const uint32_t *cov = &b.cov[pl * bna + r.allele0];
+            const uint8_t st = b.status[pl * bn + r.slot];
             auto gname = [&](int a, int c) { return o.haploid ? std::to_string(a) : std::to_string(a) + "/" + std::to_string(c); };
             if (o.verbose) {
                 out += "COVS=";
@@ -1528,7 +1579,7 @@ int call_main(const Options &o)
                 }
                 out += ";GTS=";
                 if (st == MG_GT_NORMAL) {
-                    size_t q = r.gt0;
+                    size_t q = pl * bng + r.gt0;
                     bool first = true;
                     for (uint32_t a = 0; a < r.n_alleles; ++a)
                         for (uint32_t c = a; c < (o.haploid ? a + 1 : r.n_alleles); ++c, ++q) {
@@ -1549,20 +1600,21 @@ int call_main(const Options &o)
             } else
                 out += ".";
             out += "\tGT:GQ\t";
-            out += gname(b.g1[r.slot], b.g2[r.slot]); // early-outs and "nothing beats 0.0" come back as 0 / 0/0
-            out += ":" + std::to_string(b.gq[r.slot]) + "\n";
-        }
-        return out;
+            out += gname(b.g1[pl * bn + r.slot], b.g2[pl * bn + r.slot]); // early-outs and "nothing beats 0.0" come back as 0 / 0/0
+            out += ":" + std::to_string(b.gq[pl * bn + r.slot]) + "\n";
+          }
+        return outv;
     };
     // as many batches in flight as there are devices; their text leaves in submission order
-    std::deque<std::future<std::string>> in_flight;
+    std::deque<std::future<std::vector<std::string>>> in_flight;
     size_t jobs_started = 0;
     auto drain = [&](size_t keep) {
         Timed t_drain("main: wait for worker + write");
         while (in_flight.size() > keep) {
-            const std::string text = in_flight.front().get(); // (or the batch's exception comes back here)
+            const std::vector<std::string> text = in_flight.front().get(); // (or the batch's exception comes back here)
             in_flight.pop_front();
-            if (fwrite(text.data(), 1, text.size(), stdout) != text.size()) throw std::runtime_error("cannot write the output");
+            for (size_t pl = 0; pl < P; ++pl)
+                if (fwrite(text[pl].data(), 1, text[pl].size(), outs[pl]) != text[pl].size()) throw std::runtime_error("cannot write the output");
         }
     };
     auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
@@ -1677,7 +1729,79 @@ int call_main(const Options &o)
     }, &devs[0]);
     run_and_print();
     drain(0);
-    fflush(stdout);
+    for (FILE *f : outs) fflush(f);
+    return n;
+    }; // vcf_pass
+
+    size_t n = 0;
+    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout});
+    else {
+        if (mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
+        Device &dev = devs[0];
+        size_t G = o.cohort_group ? (size_t)o.cohort_group : std::min<size_t>(samples.size(), 64);
+        for (size_t s0 = 0; s0 < samples.size();) {
+            size_t g = std::min(G, samples.size() - s0);
+            {
+                Timed t("cohort: planes");
+                int rc = mg_cohort_begin(dev.ctx, (uint32_t)g);
+                while (rc == MG_ERR_NOMEM && !o.cohort_group && g > 1) { // (as many as fit beside the index)
+                    G = g = (g + 1) / 2;
+                    rc = mg_cohort_begin(dev.ctx, (uint32_t)g);
+                }
+                dev.check(rc, "mg_cohort_begin");
+            }
+            {
+                Timed t("cohort: table scans");
+                for (size_t i = 0; i < g; ++i) {
+                    dev.check(mg_cohort_select(dev.ctx, (uint32_t)i), "mg_cohort_select");
+                    scan_sample(samples[s0 + i].input);
+                }
+            }
+            // a group's files are written as NAME.vcf.part and take their names when the group is complete: a failure on the way
+            // leaves no truncated NAME.vcf behind
+            struct Parts {
+                std::vector<std::string> paths;
+                std::vector<FILE *> files;
+                bool done = false;
+                ~Parts()
+                {
+                    if (done) return;
+                    for (FILE *f : files)
+                        if (f) fclose(f);
+                    for (const auto &p : paths) unlink((p + ".part").c_str());
+                }
+            } parts;
+            std::vector<FILE *> &outs = parts.files;
+            for (size_t i = 0; i < g; ++i) {
+                const std::string path = o.out_dir + "/" + samples[s0 + i].name + ".vcf";
+                FILE *f = fopen((path + ".part").c_str(), "wb");
+                if (!f) throw std::runtime_error("cannot write " + path);
+                parts.paths.push_back(path);
+                outs.push_back(f);
+                if (fwrite(header_text.data(), 1, header_text.size(), f) != header_text.size()) throw std::runtime_error("cannot write " + path);
+            }
+            {
+                Timed t("cohort: panel pass");
+                std::unique_ptr<VcfReader> again;
+                if (s0) { // (the panel does not stay resident across groups: it is read again)
+                    again.reset(new VcfReader(o.vcf_path, o.samples));
+                    start_vcf(*again);
+                    if (!again->ok()) throw std::runtime_error(again->error);
+                }
+                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs);
+            }
+            for (FILE *&f : outs) {
+                FILE *closing = f;
+                f = nullptr;
+                if (fclose(closing) != 0) throw std::runtime_error("cannot write the output");
+            }
+            for (const auto &p : parts.paths)
+                if (rename((p + ".part").c_str(), p.c_str()) != 0) throw std::runtime_error("cannot write " + p);
+            parts.done = true;
+            dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
+            s0 += g;
+        }
+    }
     if (gt_bytes_uploaded) std::cerr << "[malva-geno] panel genotypes of the general blocks: " << gt_bytes_uploaded.load() << " bytes uploaded" << std::endl;
     pelapsed("Processed " + std::to_string(n) + " variants");
     pelapsed("Execution completed");

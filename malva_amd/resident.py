@@ -93,3 +93,56 @@ class ResidentPanel:
         return {"blk_var_off": self.blk_var_off[:nb + 1].cpu().numpy().view(np.uint32), "cov": self.cov[:na].cpu().numpy().view(np.uint32),
                 "overflow": self.overflow[:n].cpu().numpy(), "g1": self.g1[:n].cpu().numpy(), "g2": self.g2[:n].cpu().numpy(),
                 "gq": self.gq[:n].cpu().numpy(), "status": self.status[:n].cpu().numpy(), "probs": self.probs[:self.n_gt].cpu().numpy()}
+
+
+class ResidentCohort:
+    """The samples of a cohort against one ResidentPanel: a context in cohort mode holds their counters side by side (planes),
+    the record loop reads every plane in one pass (mg_cover_blocks_cohort_device) and the likelihoods run per plane on that
+    plane's slice of the coverages.
+
+        co = ResidentCohort(rp, ctx, n_planes)
+        for s in range(n_planes): co.select(s); ctx.kmc_scan_device(...)        # or mg_reads_*
+        co.call_step(); r = co.results(s)
+        co.close()
+    """
+
+    def __init__(self, rp: ResidentPanel, ctx, n_planes):
+        torch = rp.torch
+        self.rp, self.ctx, self.n_planes = rp, ctx, int(n_planes)
+        ctx.cohort_begin(self.n_planes)
+        z = lambda n, dt: torch.zeros(max(int(n), 1), dtype=dt, device=rp.dev_t)
+        self.cov = z(self.n_planes * rp.n_slots, torch.int32)  # [planes][slots]
+        G, n = self.n_planes, rp.n
+        self.g1, self.g2, self.gq, self.status = z(G * n, torch.int32), z(G * n, torch.int32), z(G * n, torch.int32), z(G * n, torch.uint8)
+        self.probs = z(G * rp.n_gt, torch.float64)
+
+    def select(self, plane):
+        self.ctx.cohort_select(plane)
+
+    def cover(self):
+        rp = self.rp
+        self.ctx.cover_blocks_cohort_device(rp.dev, rp.blk_var_off.data_ptr(), rp.var_block.data_ptr(), rp.n_blocks.data_ptr(), rp.haploid,
+                                            self.cov.data_ptr(), rp.overflow.data_ptr())
+
+    def genotype(self, error_rate=0.001, max_cov=200, probs=True):
+        rp, n = self.rp, self.rp.n
+        for s in range(self.n_planes):
+            self.ctx.genotype_device(self.cov.data_ptr() + 4 * s * rp.n_slots, rp.t["freq"].data_ptr(), rp.t["var_allele_off"].data_ptr(), n, error_rate, max_cov,
+                                     rp.haploid, self.g1.data_ptr() + 4 * s * n, self.g2.data_ptr() + 4 * s * n, self.gq.data_ptr() + 4 * s * n,
+                                     self.status.data_ptr() + s * n, self.probs.data_ptr() + 8 * s * rp.n_gt if probs else None,
+                                     rp.t["gt_off"].data_ptr() if probs else None)
+
+    def call_step(self, error_rate=0.001, max_cov=200, probs=True):
+        self.rp.cut(self.ctx)
+        self.cover()
+        self.genotype(error_rate, max_cov, probs)
+
+    def results(self, plane):
+        rp, n, na, s = self.rp, self.rp.n, self.rp.n_slots, int(plane)
+        rp.torch.cuda.synchronize()
+        cut = lambda t, m: t[s * m:s * m + m].cpu().numpy()
+        return {"cov": cut(self.cov, na).view(np.uint32), "overflow": rp.overflow[:n].cpu().numpy(), "g1": cut(self.g1, n), "g2": cut(self.g2, n),
+                "gq": cut(self.gq, n), "status": cut(self.status, n), "probs": cut(self.probs, rp.n_gt)}
+
+    def close(self):
+        self.ctx.cohort_end()
