@@ -474,6 +474,28 @@ int mg_call_isolated_device(mg_ctx *ctx, size_t n_vars, const void *d_pos, const
                             int haploid, void *d_cov_out, void *d_gt1, void *d_gt2, void *d_gq, void *d_status,
                             void *d_probs, const void *d_var_gt_off);
 
+/* ---- the sample columns of a multi-sample VCF ------------------------------------
+ * The GT/GQ print of VB::output_variants (var_block.hpp:337-396), which the reference does for its one individual, repeated
+ * per sample: the reference has no multi-sample output.  gt1 / gt2 / gq are [n_planes][n_vars] int32, plane-major, as n_planes
+ * calls of mg_genotype / mg_call_isolated fill them (n_planes 1..64; the context need not be in cohort mode: the call formats
+ * arrays and reads no counters; gt2 is not read in haploid mode and may then be NULL).  Row v is
+ * text_out[row_off_out[v] .. row_off_out[v + 1]): for every plane in order a tab and the cell, then '\n'.  The cell is
+ * `<gt1>:<gq>` in haploid mode, else `<gt1>/<gt2>:<gq>`; with cov ([n_planes][slots], slots = var_allele_off[n_vars]) and
+ * var_allele_off ([n_vars + 1]) -- both or neither -- a third field follows: ':' and the record's coverages of that plane,
+ * comma-separated.  Every number prints as std::to_string(int) prints it, a coverage as std::to_string((int)cov).
+ * n_vars == 0 is legal: row_off_out[0] = 0.  *text_bytes_out always receives the bytes the text needs; when that is more
+ * than text_cap the call returns MG_ERR_LIMIT, nothing is written at or behind text_cap, row_off_out is valid all the
+ * same, and the caller may come again with a larger buffer.  The host form synchronises; the device form is asynchronous on
+ * the context's stream until it reads the 8-byte total back (text_bytes_out is a HOST pointer in both).
+ * mg_format_stats (waits for it): ms_out[3], device milliseconds of the most recent call's length pass, scan and write pass. */
+int mg_format_calls(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
+                    const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
+                    uint64_t *text_bytes_out);
+int mg_format_calls_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
+                           const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
+                           uint64_t *text_bytes_out);
+int mg_format_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- index payloads  (bloom_filter.hpp:127-146, kmap.hpp:52-82) ----------- */
 
 /* BF: _mode, _size, bit words (ceil(size/64) u64), counters (n_set u16).

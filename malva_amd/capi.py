@@ -107,6 +107,9 @@ def lib():
         "mg_cohort_info": [vp, vp, vp],
         "mg_cover_blocks_cohort_device": [vp, vp, vp, vp, vp, it, vp, vp],
         "mg_cohort_stats": [vp, vp],
+        "mg_format_calls": [vp, sz, u32, it, vp, vp, vp, vp, vp, vp, sz, vp, vp],
+        "mg_format_calls_device": [vp, sz, u32, it, vp, vp, vp, vp, vp, vp, sz, vp, vp],
+        "mg_format_stats": [vp, vp],
         "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
         "mg_comm_unique_id": [vp],
         "mg_comm_init": [vp, it, it, vp],
@@ -167,6 +170,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_reads_begin", "mg_reads_add", "mg_reads_add_device", "mg_reads_finish", "mg_reads_export", "mg_reads_stats",
             "mg_counters_size", "mg_counters_export_device", "mg_counters_import_device", "mg_counters_reset", "mg_counters_view",
             "mg_cohort_begin", "mg_cohort_select", "mg_cohort_end", "mg_cohort_info", "mg_cover_blocks_cohort_device", "mg_cohort_stats", "mg_cover_blocks_cohort",
+            "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
@@ -586,6 +590,49 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_cohort_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
+
+    # the sample columns of a multi-sample VCF
+    def format_calls(self, gt1, gt2, gq, haploid, cov=None, var_allele_off=None, text_cap=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 -> (bytes, row_off): row v = bytes[row_off[v]:row_off[v + 1]], a tab and a
+        `GT:GQ[:COVS]` cell per plane, then a newline.  cov: [planes, slots] with var_allele_off [n_vars + 1].  text_cap: the
+        buffer to try first (default: sized by a first call); a buffer that is too small raises MalvaError(MG_ERR_LIMIT) with
+        .needed and .row_off set."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
+        planes, n = g1.shape
+        cv, vo = a(cov, np.uint32), a(var_allele_off, np.uint32)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+
+        def call(cap):
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self._L.mg_format_calls(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), _p(cv), _p(vo), _p(text) if cap else None, cap, _p(row_off),
+                                         C.byref(need))
+            return rc, text
+        rc, text = call(0 if text_cap is None else int(text_cap))
+        if rc == -5 and text_cap is None and need.value:
+            rc, text = call(need.value)
+        if rc != 0:
+            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
+            e.needed, e.row_off, e.text = need.value, row_off, text
+            raise e
+        return text[:need.value].tobytes(), row_off
+
+    def format_calls_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_text, text_cap, d_row_off):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_format_calls_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), v(d_cov), v(d_var_allele_off), v(d_text),
+                                            int(text_cap), v(d_row_off), C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
+    def format_stats(self):
+        """-> device ms of the most recent format_calls: (length pass, scan, write pass)"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.mg_format_stats(self.h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # multi-GPU exchange inside the library (RCCL)
     def comm_init(self, rank, world, comm_id: bytes):

@@ -38,6 +38,7 @@ constexpr int TPB = 256;
 #include "variant_kernels.h"
 #include "block_pipeline.h"
 #include "gt_text_kernels.h"
+#include "call_text_kernels.h"
 #include "reads_kernels.h"
 
 } // namespace
@@ -138,6 +139,10 @@ struct mg_ctx {
     u32 *coh_sv_counts = nullptr, *coh_sv_vals = nullptr;
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
     hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
+    // mg_format_calls*: row lengths, the meta block (total, "a row beyond 32 bits"), and the host form's staging (gt1, gt2, gq, cov, var_allele_off, text, row_off)
+    Scratch s_fmt[9];
+    hipEvent_t ev_f[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
+    bool fmt_stats_valid = false;
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -673,6 +678,9 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     hipFree(c->coh_sv_vals);
     for (auto &e : c->ev_c)
         if (e) hipEventDestroy(e);
+    for (auto &e : c->ev_f)
+        if (e) hipEventDestroy(e);
+    for (auto &q : c->s_fmt) hipFree(q.p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3012,6 +3020,99 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
     if (!c->ev_c[2]) return fail(c, MG_ERR_STATE, "no mg_cover_blocks_cohort_device yet");
     HIP_TRY(c, hipEventSynchronize(c->ev_c[2]));
     for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_c[i], c->ev_c[i + 1]));
+    return MG_OK;
+}
+
+// ---- the sample columns of a batch as text (call_text_kernels.h) --------------------------------------------------------------
+MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
+                                     const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
+                                     uint64_t *text_bytes_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_format_calls: n_planes is 1..64");
+    if (!d_row_off_out || !text_bytes_out || (!d_text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if ((d_cov != nullptr) != (d_var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_format_calls: cov and var_allele_off go together");
+    if (n_vars && (!d_gt1 || !d_gq || (!haploid && !d_gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_format_calls: more than 2^32 - 1 records in one call");
+    for (auto &e : c->ev_f)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->fmt_stats_valid = false;
+    *text_bytes_out = 0;
+    HIP_TRY(c, hipEventRecord(c->ev_f[0], c->stream));
+    if (n_vars == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
+        for (int i = 1; i < 4; ++i) HIP_TRY(c, hipEventRecord(c->ev_f[i], c->stream));
+        c->fmt_stats_valid = true;
+        return MG_OK;
+    }
+    void *d_len, *d_meta, *part;
+    TRY(scratch(c, c->s_fmt[0], 4 * n_vars, &d_len));
+    TRY(scratch(c, c->s_fmt[1], 16, &d_meta));
+    const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    const FmtArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off};
+    unsigned long long *meta = (unsigned long long *)d_meta;
+    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
+    hipLaunchKernelGGL(fmt_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len, meta);
+    HIP_TRY(c, hipEventRecord(c->ev_f[1], c->stream));
+    hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, (u64)n_vars, (unsigned long long *)part);
+    hipLaunchKernelGGL(part_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, c->stream, (unsigned long long *)part, n_part, meta);
+    hipLaunchKernelGGL(fmt_rescan_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, (u64)n_vars, (const unsigned long long *)part,
+                       (unsigned long long *)d_row_off_out, meta);
+    HIP_TRY(c, hipEventRecord(c->ev_f[2], c->stream));
+    hipLaunchKernelGGL(fmt_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a,
+                       (const unsigned long long *)d_row_off_out, (char *)d_text_out, (u64)text_cap);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_f[3], c->stream));
+    c->fmt_stats_valid = true;
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "mg_format_calls: a row of 4 GB or more");
+    *text_bytes_out = total;
+    if (total > text_cap) return fail(c, MG_ERR_LIMIT, "mg_format_calls: the text needs %llu bytes, text_cap is %llu", total, (unsigned long long)text_cap);
+    return MG_OK;
+}
+
+MG_EXPORT int mg_format_calls(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
+                              const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
+                              uint64_t *text_bytes_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_format_calls: n_planes is 1..64");
+    if (!row_off_out || !text_bytes_out || (!text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if ((cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_format_calls: cov and var_allele_off go together");
+    if (n_vars && (!gt1 || !gq || (!haploid && !gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t cells = 4 * (size_t)n_planes * n_vars;
+    void *d_g1, *d_g2 = nullptr, *d_gq, *d_cov = nullptr, *d_vao = nullptr, *d_text, *d_off;
+    TRY(upload(c, c->s_fmt[2], gt1, cells, &d_g1));
+    if (!haploid) TRY(upload(c, c->s_fmt[3], gt2, cells, &d_g2));
+    TRY(upload(c, c->s_fmt[4], gq, cells, &d_gq));
+    if (cov) {
+        TRY(upload(c, c->s_fmt[5], cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d_cov));
+        TRY(upload(c, c->s_fmt[6], var_allele_off, 4 * (n_vars + 1), &d_vao));
+    }
+    TRY(scratch(c, c->s_fmt[7], text_cap ? text_cap : 1, &d_text));
+    TRY(scratch(c, c->s_fmt[8], 8 * (n_vars + 1), &d_off));
+    const int rc = mg_format_calls_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, d_cov, d_vao, d_text, text_cap, d_off, text_bytes_out);
+    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *text_bytes_out)) return rc; // (a text that does not fit: row_off and the first text_cap bytes are still the caller's)
+    const size_t have = std::min<uint64_t>(*text_bytes_out, text_cap);
+    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
+    if (have) HIP_TRY(c, hipMemcpyAsync(text_out, d_text, have, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+// device milliseconds of the most recent mg_format_calls* (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
+MG_EXPORT int mg_format_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    if (!c->fmt_stats_valid) return fail(c, MG_ERR_STATE, "no mg_format_calls yet");
+    HIP_TRY(c, hipEventSynchronize(c->ev_f[3]));
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_f[i], c->ev_f[i + 1]));
     return MG_OK;
 }
 

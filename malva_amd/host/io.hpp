@@ -1314,4 +1314,20 @@ inline std::string cleaned_header(const std::vector<std::string> &lines_in, bool
     return out;
 }
 
+// header of the multi-sample VCF (call --cohort --merged): the single call's plain header with one column per sample in place of
+// DONOR; verbose: the cells carry a COVS field, declared as FORMAT (INFO stays '.', so neither INFO line of the verbose header)
+inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names)
+{
+    std::vector<std::string> lines = lines_in;
+    const std::string covs = "##FORMAT=<ID=COVS";
+    bool declared = false;
+    for (const auto &l : lines) declared = declared || (l.compare(0, covs.size(), covs) == 0 && (l[covs.size()] == ',' || l[covs.size()] == '>'));
+    std::string out = cleaned_header(lines, false);
+    out.resize(out.size() - std::string("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tDONOR\n").size());
+    if (verbose && !declared) out += covs + ",Number=R,Type=Integer,Description=\"Allele coverages\">\n";
+    out += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
+    for (const auto &n : names) out += "\t" + n;
+    return out + "\n";
+}
+
 } // namespace malva

@@ -61,13 +61,18 @@ const char *USAGE =
     "          --max-count                   READS only: cap counts at this value (default:255, KMC -cs)             [this build]\n"
     "          --cohort                      call: the third argument is a manifest, one sample per line NAME<tab>INPUT ('#' lines\n"
     "                                        and blank lines skipped; INPUT as the third argument of call, relative paths relative\n"
-    "                                        to the manifest); needs -o; not with --gpus > 1                        [this build]\n"
+    "                                        to the manifest); needs -o or --merged; not with --gpus > 1            [this build]\n"
     "      -o, --out-dir                     --cohort: directory that receives NAME.vcf per sample, each byte for byte what\n"
     "                                        `call` with that INPUT prints to stdout                                 [this build]\n"
     "          --cohort-group                --cohort: samples held on the GPU at once, 1..64 (default: all of them, at most 64,\n"
     "                                        halved while their counters do not fit in HBM beside the index).  A cohort of any\n"
     "                                        size runs as groups of that many; the index is loaded once, the panel VCF is read\n"
     "                                        again for every group (it does not stay resident across groups)          [this build]\n"
+    "          --merged                      --cohort: PATH ('-': stdout) receives ONE multi-sample VCF, a GT:GQ column per sample in\n"
+    "                                        manifest order -- the column paste of the per-sample outputs, whatever the grouping;\n"
+    "                                        the sample columns are formatted on the GPU.  -o is then optional (both: both are\n"
+    "                                        written in one pass).  With -v: INFO stays '.', FORMAT is GT:GQ:COVS and every cell\n"
+    "                                        carries its sample's allele coverages; GTS (the likelihoods) is not carried   [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -98,6 +103,7 @@ struct Options { // argument_parser.hpp:51-66
     bool cohort = false;    // kmc_path is a manifest (host/cohort.hpp)
     std::string out_dir;    // -o
     int cohort_group = 0;   // 0: as many as fit, at most 64
+    std::string merged;     // --merged: the multi-sample VCF ("-": stdout)
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -114,7 +120,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"gpus", required_argument, nullptr, 'g'},
                                       {"min-count", required_argument, nullptr, 1001}, {"max-count", required_argument, nullptr, 1002},
                                       {"cohort", no_argument, nullptr, 1003},          {"cohort-group", required_argument, nullptr, 1004},
-                                      {"out-dir", required_argument, nullptr, 'o'},
+                                      {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -153,6 +159,13 @@ bool parse_arguments(int argc, char **argv, Options &o)
             }
             break;
         case 'o': o.out_dir = optarg; break;
+        case 1005:
+            o.merged = optarg;
+            if (o.merged.empty()) {
+                std::cerr << "malva : --merged takes a path, or - for stdout\n";
+                die = true;
+            }
+            break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -170,8 +183,12 @@ bool parse_arguments(int argc, char **argv, Options &o)
         std::cerr << "malva : --gpus must be 1..64\n";
         die = true;
     }
-    if (o.cohort && o.out_dir.empty()) {
-        std::cerr << "malva : --cohort needs -o OUTDIR\n";
+    if (o.cohort && o.out_dir.empty() && o.merged.empty()) {
+        std::cerr << "malva : --cohort needs -o OUTDIR or --merged PATH\n";
+        die = true;
+    }
+    if (!o.cohort && !o.merged.empty()) {
+        std::cerr << "malva : --merged goes with --cohort\n";
         die = true;
     }
     if (o.cohort && o.gpus > 1) {
@@ -1412,6 +1429,8 @@ int call_main(const Options &o)
         on_all_devices(devs, [&](Device &d, size_t) { d.check(mg_reference_upload(d.ctx, all.data(), all.size()), "mg_reference_upload"); });
     }
     std::atomic<size_t> gt_bytes_uploaded{0}; // panel genotypes handed to mg_cover_blocks[_sparse], all batches
+    double format_ms[3] = {0, 0, 0};          // --merged: device milliseconds of the mg_format_calls (length pass, scan, write pass; one worker at a time)
+    size_t format_calls = 0;
     std::string header_text;
     {
         VcfReader hdr(o.vcf_path, "-");
@@ -1433,8 +1452,10 @@ int call_main(const Options &o)
 
     // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to outs[0] (stdout).  planes > 0: the
     // context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
-    // only the INFO and GT:GQ fields per sample; sample p's text goes to outs[p].
-    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs) -> size_t {
+    // only the INFO and GT:GQ fields per sample; sample p's text goes to outs[p] (outs empty: no per-sample text).  merged_out (--merged):
+    // the group's block of the multi-sample VCF -- a record's sample columns come as text from the device (mg_format_calls), behind the
+    // record's fixed columns when merged_fixed, else on their own (a later group's columns, pasted behind the first group's lines at the end).
+    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed) -> size_t {
     const size_t P = planes ? planes : 1;
 
     // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
@@ -1556,11 +1577,52 @@ int call_main(const Options &o)
                                       o.verbose ? gen.probs.data() + pl * ng : nullptr, o.verbose ? gen.var_gt_off.data() : nullptr),
                           "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
         }
+        // --merged: the sample columns of both batches as text, made where the genotypes were
+        std::vector<char> row_text[2];
+        std::vector<uint64_t> row_off[2];
+        if (merged_out) {
+            Timed t_fmt("worker: merged rows (mg_format_calls)");
+            for (int w = 0; w < 2; ++w) {
+                Batch &b = w ? gen : iso;
+                const size_t bn = b.n();
+                if (!bn) continue;
+                row_off[w].resize(bn + 1);
+                row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0)); // (a guess: the call says what it needs)
+                for (;;) {
+                    uint64_t need = 0;
+                    const int rc = mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.verbose ? b.cov.data() : nullptr,
+                                                   o.verbose ? b.var_allele_off.data() : nullptr, row_text[w].data(), row_text[w].size(), row_off[w].data(), &need);
+                    if (rc == MG_ERR_LIMIT && need > row_text[w].size()) {
+                        row_text[w].resize(need);
+                        continue;
+                    }
+                    dev.check(rc, "mg_format_calls");
+                    break;
+                }
+                float ms[3] = {0, 0, 0};
+                dev.check(mg_format_stats(dev.ctx, ms), "mg_format_stats");
+                for (int i = 0; i < 3; ++i) format_ms[i] += ms[i];
+                ++format_calls;
+            }
+        }
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
-        std::vector<std::string> outv(P);
+        std::vector<std::string> outv(outs.size() + 1); // (the last one: the merged block)
+        if (merged_out) {
+            std::string &out = outv.back();
+            const char *fixed = o.verbose ? "\tPASS\t.\tGT:GQ:COVS" : "\tPASS\t.\tGT:GQ";
+            for (const Rec &r : recs) {
+                const int w = r.isolated ? 0 : 1;
+                if (merged_fixed) {
+                    out += r.prefix;
+                    out += fixed;
+                }
+                out.append(row_text[w].data() + row_off[w][r.slot], row_text[w].data() + row_off[w][r.slot + 1]);
+            }
+        }
         char num[64];
+        if (!outs.empty())
         for (const Rec &r : recs) // output_variants, var_block.hpp:337-396
           for (size_t pl = 0; pl < P; ++pl) {
             const Batch &b = r.isolated ? iso : gen;
@@ -1613,8 +1675,9 @@ int call_main(const Options &o)
         while (in_flight.size() > keep) {
             const std::vector<std::string> text = in_flight.front().get(); // (or the batch's exception comes back here)
             in_flight.pop_front();
-            for (size_t pl = 0; pl < P; ++pl)
+            for (size_t pl = 0; pl < outs.size(); ++pl)
                 if (fwrite(text[pl].data(), 1, text[pl].size(), outs[pl]) != text[pl].size()) throw std::runtime_error("cannot write the output");
+            if (merged_out && fwrite(text.back().data(), 1, text.back().size(), merged_out) != text.back().size()) throw std::runtime_error("cannot write the merged output");
         }
     };
     auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
@@ -1730,14 +1793,41 @@ int call_main(const Options &o)
     run_and_print();
     drain(0);
     for (FILE *f : outs) fflush(f);
+    if (merged_out) fflush(merged_out);
     return n;
     }; // vcf_pass
 
     size_t n = 0;
-    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout});
+    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false);
     else {
-        if (mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
+        if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
         Device &dev = devs[0];
+        // --merged: a cohort that runs as ONE group writes its lines straight to the output (PATH.part, renamed at the end; stdout as it
+        // is).  Otherwise every group writes its block to a temporary file -- the first the header and whole lines, the others their
+        // sample columns alone -- beside the output, or under $TMPDIR when that is stdout, and a last pass pastes them line by line.
+        // Whatever is left of them is removed when this frame is left, on success and on error.
+        struct MergedFiles {
+            std::vector<std::string> paths; // temporary files, the first group's first
+            std::string part;               // PATH.part
+            FILE *open = nullptr;
+            ~MergedFiles()
+            {
+                if (open && open != stdout) fclose(open);
+                for (const auto &p : paths) unlink(p.c_str());
+                if (!part.empty()) unlink(part.c_str());
+            }
+        } merged;
+        const bool merged_stdout = o.merged == "-";
+        const std::string merged_tmp_base = !merged_stdout ? o.merged : std::string(getenv("TMPDIR") && *getenv("TMPDIR") ? getenv("TMPDIR") : "/tmp") + "/malva-geno." + std::to_string((long)getpid()) + ".merged";
+        std::string merged_head;
+        if (!o.merged.empty()) {
+            VcfReader hdr(o.vcf_path, "-");
+            if (!hdr.ok()) throw std::runtime_error(hdr.error);
+            std::vector<std::string> names;
+            for (const auto &sm : samples) names.push_back(sm.name);
+            merged_head = merged_header(hdr.header_lines, o.verbose, names);
+        }
+        bool merged_direct = false; // one group: no temporary blocks
         size_t G = o.cohort_group ? (size_t)o.cohort_group : std::min<size_t>(samples.size(), 64);
         for (size_t s0 = 0; s0 < samples.size();) {
             size_t g = std::min(G, samples.size() - s0);
@@ -1772,13 +1862,25 @@ int call_main(const Options &o)
                 }
             } parts;
             std::vector<FILE *> &outs = parts.files;
-            for (size_t i = 0; i < g; ++i) {
+            for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
                 const std::string path = o.out_dir + "/" + samples[s0 + i].name + ".vcf";
                 FILE *f = fopen((path + ".part").c_str(), "wb");
                 if (!f) throw std::runtime_error("cannot write " + path);
                 parts.paths.push_back(path);
                 outs.push_back(f);
                 if (fwrite(header_text.data(), 1, header_text.size(), f) != header_text.size()) throw std::runtime_error("cannot write " + path);
+            }
+            if (!o.merged.empty()) {
+                if (s0 == 0) merged_direct = g == samples.size();
+                if (merged_direct && merged_stdout) merged.open = stdout;
+                else {
+                    const std::string path = merged_direct ? o.merged + ".part" : merged_tmp_base + ".g" + std::to_string(merged.paths.size()) + ".part";
+                    if (merged_direct) merged.part = path;
+                    else merged.paths.push_back(path);
+                    merged.open = fopen(path.c_str(), "wb");
+                    if (!merged.open) throw std::runtime_error("cannot write " + path);
+                }
+                if (s0 == 0 && fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size()) throw std::runtime_error("cannot write the merged output");
             }
             {
                 Timed t("cohort: panel pass");
@@ -1788,7 +1890,12 @@ int call_main(const Options &o)
                     start_vcf(*again);
                     if (!again->ok()) throw std::runtime_error(again->error);
                 }
-                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs);
+                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0);
+            }
+            if (merged.open) {
+                FILE *closing = merged.open;
+                merged.open = nullptr;
+                if ((closing == stdout ? fflush(closing) : fclose(closing)) != 0) throw std::runtime_error("cannot write the merged output");
             }
             for (FILE *&f : outs) {
                 FILE *closing = f;
@@ -1800,6 +1907,68 @@ int call_main(const Options &o)
             parts.done = true;
             dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
             s0 += g;
+        }
+        if (!o.merged.empty() && !merged_direct) { // line i of the output = line i of every group's block, one behind the other
+            Timed t("cohort: merged paste");
+            std::vector<FILE *> in;
+            struct CloseAll {
+                std::vector<FILE *> &v;
+                ~CloseAll()
+                {
+                    for (FILE *f : v) fclose(f);
+                }
+            } close_all{in};
+            for (const auto &p : merged.paths) {
+                in.push_back(fopen(p.c_str(), "rb"));
+                if (!in.back()) {
+                    in.pop_back();
+                    throw std::runtime_error("cannot read " + p);
+                }
+            }
+            if (!merged_stdout) {
+                merged.part = o.merged + ".part";
+                merged.open = fopen(merged.part.c_str(), "wb");
+                if (!merged.open) throw std::runtime_error("cannot write " + merged.part);
+            } else
+                merged.open = stdout;
+            char *line = nullptr;
+            size_t line_cap = 0;
+            struct FreeLine {
+                char *&p;
+                ~FreeLine() { free(p); }
+            } free_line{line};
+            std::string out;
+            for (;;) { // (the header lines of the first block have no counterpart in the others)
+                ssize_t len = getline(&line, &line_cap, in[0]);
+                if (len < 0) break;
+                const bool record = line[0] != '#';
+                if (record && len && line[len - 1] == '\n') --len;
+                out.append(line, (size_t)len);
+                for (size_t gi = 1; record && gi < in.size(); ++gi) {
+                    ssize_t more = getline(&line, &line_cap, in[gi]);
+                    if (more <= 0) throw std::runtime_error("internal: a group's block of the merged output is short");
+                    if (gi + 1 < in.size() && line[more - 1] == '\n') --more;
+                    out.append(line, (size_t)more);
+                }
+                if (out.size() >= (1u << 20)) {
+                    if (fwrite(out.data(), 1, out.size(), merged.open) != out.size()) throw std::runtime_error("cannot write the merged output");
+                    out.clear();
+                }
+            }
+            if (fwrite(out.data(), 1, out.size(), merged.open) != out.size()) throw std::runtime_error("cannot write the merged output");
+            FILE *closing = merged.open;
+            merged.open = nullptr;
+            if ((closing == stdout ? fflush(closing) : fclose(closing)) != 0) throw std::runtime_error("cannot write the merged output");
+        }
+        if (!o.merged.empty() && !merged_stdout) {
+            if (rename(merged.part.c_str(), o.merged.c_str()) != 0) throw std::runtime_error("cannot write " + o.merged);
+            merged.part.clear();
+        }
+        if (format_calls) {
+            if (g_timers.on) g_timers.add("merged: format kernels (device)", (format_ms[0] + format_ms[1] + format_ms[2]) / 1000.0);
+            if (g_timers.on)
+                fprintf(stderr, "[malva-geno] merged: %zu mg_format_calls, device ms per call: length %.3f scan %.3f write %.3f\n", format_calls,
+                        format_ms[0] / format_calls, format_ms[1] / format_calls, format_ms[2] / format_calls);
         }
     }
     if (gt_bytes_uploaded) std::cerr << "[malva-geno] panel genotypes of the general blocks: " << gt_bytes_uploaded.load() << " bytes uploaded" << std::endl;

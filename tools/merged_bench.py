@@ -1,0 +1,138 @@
+"""`call --cohort --merged` against `call --cohort -o` on one MI355X, on the input of tools/cohort_bench.py --cli: a panel of 1e6
+isolated SNPs, 16 samples that all name one text dump of 2e6 k-mers.
+
+Timed, each the median of --repeats runs with their spread:
+    per_sample   `--cohort -o OUTDIR`         wall time and the `cohort: panel pass` timer (MALVA_GENO_TIMERS=1)
+    merged       `--cohort --merged PATH`     the same two, and the device milliseconds per mg_format_calls (mg_format_stats)
+    parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick
+The runs alternate (parent, per_sample, merged, parent, ...), so that whatever else the host is doing falls on all three alike.
+merged_equals_paste: the merged file is the column paste of the per-sample files.
+
+    python tools/merged_bench.py [--samples 16] [--snps 1000000] [--rows 2000000] [--repeats 3] [--parent-bin PATH] [--out profiles/cohort_merged_bench.json]
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from malva_amd import synth  # noqa: E402
+
+K, REF_K = 35, 43
+BIN = os.path.join(ROOT, "bin", "malva-geno")
+
+
+def stat(xs):
+    xs = sorted(xs)
+    return {"median": round(float(np.median(xs)), 3), "min": round(xs[0], 3), "max": round(xs[-1], 3)}
+
+
+def timer(stderr, label):
+    m = re.search(r"timer\] %s\s+([0-9.]+)s" % re.escape(label), stderr)
+    return float(m.group(1)) if m else None
+
+
+def is_paste(merged_path, sample_paths):
+    """line by line: columns 1-9 of the first per-sample file, then column 10 of each"""
+    files = [open(p, "rb") for p in sample_paths]
+    try:
+        with open(merged_path, "rb") as mf:
+            for line in mf:
+                rows = [f.readline() for f in files]
+                if line.startswith(b"##"):
+                    if any(r != line for r in rows):
+                        return False
+                    continue
+                cols = [r.rstrip(b"\n").split(b"\t") for r in rows]
+                if line.startswith(b"#CHROM"):
+                    continue
+                if line != b"\t".join(cols[0][:9] + [c[9] for c in cols]) + b"\n":
+                    return False
+        return all(f.readline() == b"" for f in files)
+    finally:
+        for f in files:
+            f.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=16)
+    ap.add_argument("--snps", type=int, default=1_000_000)
+    ap.add_argument("--rows", type=int, default=2_000_000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--parent-bin", default=None, help="malva-geno of the parent commit: its `--cohort -o` panel pass is the yardstick")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cohort_merged_bench.json"))
+    a = ap.parse_args()
+    S = a.samples
+    out = {"workload": "cohort-merged", "k": K, "ref_k": REF_K, "snps": a.snps, "table_rows": a.rows, "samples": S, "repeats": a.repeats}
+    panel = synth.flat_from_snp_panel(synth.snp_panel(a.snps, seed=20261016))
+    with tempfile.TemporaryDirectory() as td:
+        prefix = os.path.join(td, "c3")
+        synth.write_vcf_fasta(panel, prefix)
+        hi, lo, _ = synth.flat_kmer_table(panel, a.rows, K, REF_K, seed=7, max_records=min(a.snps, 200_000))
+        text = synth.unpack_ascii(hi, lo, REF_K, stride=REF_K + 4)          # KMER<tab>NN<newline>, two-digit counts
+        cnt = 10 + (np.arange(len(hi)) * 7) % 50
+        text[:, REF_K] = 9
+        text[:, REF_K + 1] = 48 + cnt // 10
+        text[:, REF_K + 2] = 48 + cnt % 10
+        text[:, REF_K + 3] = 10
+        with open(os.path.join(td, "sample.txt"), "wb") as fh:
+            fh.write(text.tobytes())
+        with open(os.path.join(td, "cohort.tsv"), "w") as fh:
+            fh.write("".join("s%02d\tsample\n" % i for i in range(S)))
+        common = ["-k", str(K), "-r", str(REF_K), "-b", "4", prefix + ".fa", prefix + ".vcf"]
+        subprocess.run([BIN, "index"] + common + [os.path.join(td, "sample")], check=True, capture_output=True, timeout=600)
+        env = dict(os.environ, MALVA_GENO_TIMERS="1")
+        legs = {"per_sample": (BIN, ["-o", os.path.join(td, "out")]), "merged": (BIN, ["--merged", os.path.join(td, "merged.vcf")])}
+        if a.parent_bin:
+            legs = dict({"parent": (a.parent_bin, ["-o", os.path.join(td, "out_parent")])}, **legs)
+        res = {leg: {"wall_s": [], "panel_pass_s": []} for leg in legs}
+        fmt_ms, fmt_calls = [], 0
+
+        def run(leg):
+            b, dest = legs[leg]
+            t0 = time.perf_counter()
+            r = subprocess.run([b, "call", "--cohort"] + dest + common + [os.path.join(td, "cohort.tsv")], capture_output=True, text=True, timeout=1800, env=env)
+            wall = time.perf_counter() - t0
+            assert r.returncode == 0, r.stderr[-800:]
+            return wall, r.stderr
+        for leg in legs:                                                    # (one run each warms the page cache and the output files' blocks)
+            run(leg)
+        for _ in range(a.repeats):
+            for leg in legs:
+                wall, err = run(leg)
+                res[leg]["wall_s"].append(wall)
+                res[leg]["panel_pass_s"].append(timer(err, "cohort: panel pass"))
+                if leg == "merged":
+                    m = re.search(r"merged: (\d+) mg_format_calls, device ms per call: length ([0-9.]+) scan ([0-9.]+) write ([0-9.]+)", err)
+                    fmt_calls = int(m.group(1))
+                    fmt_ms.append([float(m.group(i)) for i in (2, 3, 4)])
+                    out["merged_timers"] = [l.split("]", 1)[1].strip() for l in err.split("\n") if "timer]" in l and ("cohort" in l or "merged" in l or "worker" in l or "main" in l)]
+                if leg == "per_sample":
+                    out["per_sample_timers"] = [l.split("]", 1)[1].strip() for l in err.split("\n") if "timer]" in l and ("cohort" in l or "worker" in l or "main" in l)]
+        for leg in legs:
+            out[leg] = {key: stat(v) for key, v in res[leg].items()}
+        out["format_calls_per_run"] = fmt_calls
+        out["format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms]) for i, name in enumerate(("length", "scan", "write"))}
+        out["merged_bytes"] = os.path.getsize(os.path.join(td, "merged.vcf"))
+        out["per_sample_bytes"] = sum(os.path.getsize(os.path.join(td, "out", "s%02d.vcf" % i)) for i in range(S))
+        out["merged_equals_paste"] = int(is_paste(os.path.join(td, "merged.vcf"), [os.path.join(td, "out", "s%02d.vcf" % i) for i in range(S)]))
+        if a.parent_bin:
+            out["parent_same_bytes"] = int(all(open(os.path.join(td, "out", "s%02d.vcf" % i), "rb").read() == open(os.path.join(td, "out_parent", "s%02d.vcf" % i), "rb").read()
+                                               for i in range(S)))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
