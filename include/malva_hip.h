@@ -495,6 +495,42 @@ int mg_format_calls_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int ha
                            const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
                            uint64_t *text_bytes_out);
 int mg_format_stats(mg_ctx *ctx, float *ms_out);
+/* mg_format_calls with a GQ mask: a cell whose gq < min_gq prints its genotype as missing -- `.` in haploid mode, else `./.` --
+ * and keeps its `:<gq>` and coverage fields.  Everything else, the buffer contract and mg_format_stats included, is
+ * mg_format_calls'; with a min_gq no cell is below, the text is mg_format_calls' byte for byte. */
+int mg_format_calls_masked(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
+                           int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
+                           uint64_t *row_off_out, uint64_t *text_bytes_out);
+int mg_format_calls_masked_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
+                                  int32_t min_gq, const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
+                                  void *d_row_off_out, uint64_t *text_bytes_out);
+
+/* ---- the site tags of a multi-sample VCF (AC / AN / AF / NS) -----------------------
+ * mg_site_counts: the allele counts of every record over the planes.  gt1 / gt2 / gq as for mg_format_calls (n_planes 1..64;
+ * gt2 is not read in haploid mode, gq not unless use_mask).  A cell is CALLED unless use_mask != 0 and its gq < min_gq.  Record v
+ * owns the slots ac[var_allele_off[v] .. var_allele_off[v + 1]), one per allele, REF first: a called cell adds 1 to slot gt1 and,
+ * in diploid mode, 1 to slot gt2; an allele index outside the record's slots (a negative one included) is not counted and
+ * nothing is written outside the record's slots.  ns[v] receives the number of planes whose cell is called.  accumulate != 0
+ * adds to what ac / ns hold (groups of a cohort larger than 64 are summed this way), accumulate == 0 overwrites.  The host
+ * form synchronises; the device form is asynchronous on the context's stream.
+ * mg_format_site_info: row v = text_out[row_off_out[v] .. row_off_out[v + 1]) is the INFO string of record v, no tab and no
+ * newline: `AC=a1,a2,..;AN=n;AF=f1,f2,..;NS=s`.  AC_i is the record's slot i (i >= 1), AN the sum of all its slots, NS ns[v].
+ * AF_i = AC_i / AN in integers: q = (2 * AC_i * 10^6 + AN) / (2 * AN) (64-bit; half rounds up at the sixth decimal); q == 0
+ * prints `0`, q == 10^6 prints `1`, anything else `0.` and q as six zero-padded digits with trailing zeros removed; AN == 0
+ * prints `.` for every AF.  A record with fewer than two slots prints `AN=n;NS=s`.  Buffer contract as mg_format_calls:
+ * *text_bytes_out (a HOST pointer in both forms) always receives the bytes needed, MG_ERR_LIMIT when that exceeds text_cap,
+ * nothing written at or behind text_cap, row_off_out valid all the same.
+ * mg_site_stats (waits): ms_out[2], device milliseconds of the most recent mg_site_counts* and of the most recent
+ * mg_format_site_info* (its three passes together); 0 for a kind not called yet, MG_ERR_STATE when neither was. */
+int mg_site_counts(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                   int32_t min_gq, const uint32_t *var_allele_off, int accumulate, uint32_t *ac, uint32_t *ns);
+int mg_site_counts_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                          int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_ac, void *d_ns);
+int mg_format_site_info(mg_ctx *ctx, size_t n_vars, const uint32_t *ac, const uint32_t *ns, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
+                        uint64_t *row_off_out, uint64_t *text_bytes_out);
+int mg_format_site_info_device(mg_ctx *ctx, size_t n_vars, const void *d_ac, const void *d_ns, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
+                               void *d_row_off_out, uint64_t *text_bytes_out);
+int mg_site_stats(mg_ctx *ctx, float *ms_out);
 
 /* ---- index payloads  (bloom_filter.hpp:127-146, kmap.hpp:52-82) ----------- */
 

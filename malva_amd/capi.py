@@ -110,6 +110,13 @@ def lib():
         "mg_format_calls": [vp, sz, u32, it, vp, vp, vp, vp, vp, vp, sz, vp, vp],
         "mg_format_calls_device": [vp, sz, u32, it, vp, vp, vp, vp, vp, vp, sz, vp, vp],
         "mg_format_stats": [vp, vp],
+        "mg_format_calls_masked": [vp, sz, u32, it, vp, vp, vp, i32, vp, vp, vp, sz, vp, vp],
+        "mg_format_calls_masked_device": [vp, sz, u32, it, vp, vp, vp, i32, vp, vp, vp, sz, vp, vp],
+        "mg_site_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp],
+        "mg_site_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp],
+        "mg_format_site_info": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
+        "mg_format_site_info_device": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
+        "mg_site_stats": [vp, vp],
         "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
         "mg_comm_unique_id": [vp],
         "mg_comm_init": [vp, it, it, vp],
@@ -171,6 +178,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_counters_size", "mg_counters_export_device", "mg_counters_import_device", "mg_counters_reset", "mg_counters_view",
             "mg_cohort_begin", "mg_cohort_select", "mg_cohort_end", "mg_cohort_info", "mg_cover_blocks_cohort_device", "mg_cohort_stats", "mg_cover_blocks_cohort",
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
+            "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
+            "mg_format_site_info_device", "mg_site_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
@@ -592,11 +601,11 @@ class Context:
         return float(ms[0]), float(ms[1])
 
     # the sample columns of a multi-sample VCF
-    def format_calls(self, gt1, gt2, gq, haploid, cov=None, var_allele_off=None, text_cap=None):
+    def format_calls(self, gt1, gt2, gq, haploid, cov=None, var_allele_off=None, text_cap=None, min_gq=None):
         """gt1 / gt2 / gq: [planes, n_vars] int32 -> (bytes, row_off): row v = bytes[row_off[v]:row_off[v + 1]], a tab and a
         `GT:GQ[:COVS]` cell per plane, then a newline.  cov: [planes, slots] with var_allele_off [n_vars + 1].  text_cap: the
         buffer to try first (default: sized by a first call); a buffer that is too small raises MalvaError(MG_ERR_LIMIT) with
-        .needed and .row_off set."""
+        .needed and .row_off set.  min_gq (mg_format_calls_masked): cells whose gq is below it print a missing genotype."""
         a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
         g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
         planes, n = g1.shape
@@ -606,8 +615,12 @@ class Context:
 
         def call(cap):
             text = np.zeros(max(cap, 1), dtype=np.uint8)
-            rc = self._L.mg_format_calls(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), _p(cv), _p(vo), _p(text) if cap else None, cap, _p(row_off),
-                                         C.byref(need))
+            if min_gq is None:
+                rc = self._L.mg_format_calls(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), _p(cv), _p(vo), _p(text) if cap else None, cap, _p(row_off),
+                                             C.byref(need))
+            else:
+                rc = self._L.mg_format_calls_masked(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq), _p(cv), _p(vo),
+                                                    _p(text) if cap else None, cap, _p(row_off), C.byref(need))
             return rc, text
         rc, text = call(0 if text_cap is None else int(text_cap))
         if rc == -5 and text_cap is None and need.value:
@@ -633,6 +646,51 @@ class Context:
         ms = (C.c_float * 3)()
         self._ck(self._L.mg_format_stats(self.h, ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # the site tags of a multi-sample VCF
+    def site_counts(self, gt1, gt2, gq, haploid, var_allele_off, min_gq=None, ac=None, ns=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 -> (ac [var_allele_off[n_vars]], ns [n_vars]) uint32: per allele slot the called
+        copies over the planes, per record the called planes.  min_gq: cells whose gq is below it are not called.  ac / ns given:
+        the counts are added to them (in place)."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q, vo = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32), a(var_allele_off, np.uint32)
+        planes, n = g1.shape
+        acc = ac is not None
+        assert acc == (ns is not None)
+        if acc:
+            assert ac.dtype == np.uint32 and ns.dtype == np.uint32 and ac.flags.c_contiguous and ns.flags.c_contiguous
+            assert ac.size == int(vo[n]) and ns.size == n
+        else:
+            ac, ns = np.zeros(int(vo[n]), dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._ck(self._L.mg_site_counts(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(vo), int(acc),
+                                        _p(ac), _p(ns)))
+        return ac, ns
+
+    def format_site_info(self, ac, ns, var_allele_off, text_cap=None):
+        """-> (bytes, row_off): row v = bytes[row_off[v]:row_off[v + 1]] is record v's `AC=..;AN=..;AF=..;NS=..`.  text_cap as for
+        format_calls."""
+        ac, ns, vo = (np.ascontiguousarray(x, dtype=np.uint32) for x in (ac, ns, var_allele_off))
+        n = ns.size
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+
+        def call(cap):
+            text = np.zeros(max(cap, 1), dtype=np.uint8)
+            return self._L.mg_format_site_info(self.h, n, _p(ac), _p(ns), _p(vo), _p(text) if cap else None, cap, _p(row_off), C.byref(need)), text
+        rc, text = call(0 if text_cap is None else int(text_cap))
+        if rc == -5 and text_cap is None and need.value:
+            rc, text = call(need.value)
+        if rc != 0:
+            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
+            e.needed, e.row_off, e.text = need.value, row_off, text
+            raise e
+        return text[:need.value].tobytes(), row_off
+
+    def site_stats(self):
+        """-> device ms of the most recent site_counts and of the most recent format_site_info"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.mg_site_stats(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     # multi-GPU exchange inside the library (RCCL)
     def comm_init(self, rank, world, comm_id: bytes):

@@ -67,14 +67,21 @@ struct FmtArgs {
     const i32 *gt1, *gt2, *gq;   // [n_planes][n_vars]
     const u32 *cov;              // [n_planes][var_allele_off[n_vars]] or NULL
     const u32 *var_allele_off;   // [n_vars + 1] (with cov)
+    int masked;                  // mg_format_calls_masked: a cell whose gq < min_gq prints its genotype as missing ('.' or './.')
+    i32 min_gq;
 };
 
 // plane p's cell of record v, the tab in front of it included
 __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
 {
     const u64 i = (u64)p * a.n_vars + v;
-    u32 len = 1 + fmt_int_len(a.gt1[i]) + 1 + fmt_int_len(a.gq[i]);
-    if (!a.haploid) len += 1 + fmt_int_len(a.gt2[i]);
+    const i32 gq = a.gq[i];
+    u32 len = 1 + 1 + fmt_int_len(gq);
+    if (a.masked && gq < a.min_gq) len += a.haploid ? 1 : 3;
+    else {
+        len += fmt_int_len(a.gt1[i]);
+        if (!a.haploid) len += 1 + fmt_int_len(a.gt2[i]);
+    }
     if (a.cov) {
         const u32 a0 = a.var_allele_off[v], a1 = a.var_allele_off[v + 1];
         const u32 *cv = a.cov + (u64)p * a.var_allele_off[a.n_vars];
@@ -86,14 +93,23 @@ __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
 __device__ __forceinline__ u64 fmt_cell_put(const FmtArgs &a, const FmtWindow &w, u64 v, u32 p, u64 pos)
 {
     const u64 i = (u64)p * a.n_vars + v;
+    const i32 gq = a.gq[i];
     w.put(pos++, '\t');
-    pos = w.put_int(pos, a.gt1[i]);
-    if (!a.haploid) {
-        w.put(pos++, '/');
-        pos = w.put_int(pos, a.gt2[i]);
+    if (a.masked && gq < a.min_gq) {
+        w.put(pos++, '.');
+        if (!a.haploid) {
+            w.put(pos++, '/');
+            w.put(pos++, '.');
+        }
+    } else {
+        pos = w.put_int(pos, a.gt1[i]);
+        if (!a.haploid) {
+            w.put(pos++, '/');
+            pos = w.put_int(pos, a.gt2[i]);
+        }
     }
     w.put(pos++, ':');
-    pos = w.put_int(pos, a.gq[i]);
+    pos = w.put_int(pos, gq);
     if (a.cov) {
         const u32 a0 = a.var_allele_off[v], a1 = a.var_allele_off[v + 1];
         const u32 *cv = a.cov + (u64)p * a.var_allele_off[a.n_vars];
@@ -154,12 +170,28 @@ __global__ void __launch_bounds__(SCAN_TPB) fmt_rescan_kernel(const u32 *__restr
     }
 }
 
-__global__ void __launch_bounds__(FMT_TPB) fmt_write_kernel(FmtArgs a, const unsigned long long *__restrict__ row_off, char *text, u64 text_cap)
+// the window's bytes [w0, stop) leave: LDS bytes [mis, mis + stop - w0), whole 16-byte pieces at once and the ragged ends byte by byte
+__device__ __forceinline__ void fmt_window_flush(const char *sh, u32 mis, char *text, u64 w0, u64 stop)
 {
-    __shared__ __attribute__((aligned(16))) char sh[FMT_WINDOW];
+    const u32 lo = mis, hi = mis + (u32)(stop - w0);
+    char *dst = text + w0 - mis; // 16-byte aligned
+    for (u32 j = threadIdx.x; j * 16 < hi; j += FMT_TPB) {
+        const u32 p0 = j * 16;
+        if (p0 >= lo && p0 + 16 <= hi) *reinterpret_cast<uint4 *>(dst + p0) = *reinterpret_cast<const uint4 *>(sh + p0);
+        else
+            for (u32 q = p0 < lo ? lo : p0; q < p0 + 16 && q < hi; ++q) dst[q] = sh[q];
+    }
+}
+
+// The write pass of one workgroup: rows [t0, t1) are one contiguous byte range of the output, staged in `sh` (FMT_WINDOW bytes, 16-byte
+// aligned) a window at a time.  rows.put(w, v, lane, r0, r1) has one wave lay row v = bytes [r0, r1) into the window (FmtWindow::put drops
+// what lies outside it).
+template <class Rows>
+__device__ __forceinline__ void fmt_write_tile(const Rows &rows, char *sh, u64 n_rows, const unsigned long long *__restrict__ row_off, char *text, u64 text_cap)
+{
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 t0 = (u64)blockIdx.x * FMT_ROWS;
-    const u64 t1 = t0 + FMT_ROWS < a.n_vars ? t0 + FMT_ROWS : a.n_vars;
+    const u64 t1 = t0 + FMT_ROWS < n_rows ? t0 + FMT_ROWS : n_rows;
     const u64 b0 = row_off[t0], b1 = row_off[t1];
     const u64 end = b1 < text_cap ? b1 : text_cap; // nothing is written at or behind text_cap
     for (u64 w0 = b0; w0 < end;) {
@@ -170,29 +202,36 @@ __global__ void __launch_bounds__(FMT_TPB) fmt_write_kernel(FmtArgs a, const uns
         for (u64 v = t0 + wave; v < t1; v += FMT_TPB / 64) {
             const u64 r0 = row_off[v], r1 = row_off[v + 1];
             if (r1 <= w0 || r0 >= w1) continue; // (wave-uniform)
-            const u32 mine = lane < a.n_planes ? fmt_cell_len(a, v, lane) : 0;
-            u32 incl = mine;
-            for (int d = 1; d < 64; d <<= 1) {
-                const u32 up = (u32)__shfl_up((int)incl, d, 64);
-                if (lane >= (u32)d) incl += up;
-            }
-            const u64 at = r0 + (incl - mine);
-            if (lane < a.n_planes && at < w1 && at + mine > w0) fmt_cell_put(a, w, v, lane, at);
-            if (lane == 0) w.put(r1 - 1, '\n');
+            rows.put(w, v, lane, r0, r1);
         }
         __syncthreads();
-        const u64 stop = w1 < end ? w1 : end;          // bytes [w0, stop) leave
-        const u32 lo = mis, hi = mis + (u32)(stop - w0); // ... = LDS bytes [lo, hi)
-        char *dst = text + w0 - mis;                   // 16-byte aligned
-        for (u32 j = threadIdx.x; j * 16 < hi; j += FMT_TPB) {
-            const u32 p0 = j * 16;
-            if (p0 >= lo && p0 + 16 <= hi) *reinterpret_cast<uint4 *>(dst + p0) = *reinterpret_cast<const uint4 *>(sh + p0);
-            else
-                for (u32 q = p0 < lo ? lo : p0; q < p0 + 16 && q < hi; ++q) dst[q] = sh[q];
-        }
+        fmt_window_flush(sh, mis, text, w0, w1 < end ? w1 : end);
         __syncthreads(); // (the next window overwrites sh)
         w0 = w1;
     }
+}
+
+// a record's sample columns: every lane its plane's cell at the offset a wave prefix sum gives it
+struct FmtCellRows {
+    FmtArgs a;
+    __device__ __forceinline__ void put(const FmtWindow &w, u64 v, u32 lane, u64 r0, u64 r1) const
+    {
+        const u32 mine = lane < a.n_planes ? fmt_cell_len(a, v, lane) : 0;
+        u32 incl = mine;
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 up = (u32)__shfl_up((int)incl, d, 64);
+            if (lane >= (u32)d) incl += up;
+        }
+        const u64 at = r0 + (incl - mine);
+        if (lane < a.n_planes && at < w.w0 + w.wlen && at + mine > w.w0) fmt_cell_put(a, w, v, lane, at);
+        if (lane == 0) w.put(r1 - 1, '\n');
+    }
+};
+
+__global__ void __launch_bounds__(FMT_TPB) fmt_write_kernel(FmtArgs a, const unsigned long long *__restrict__ row_off, char *text, u64 text_cap)
+{
+    __shared__ __attribute__((aligned(16))) char sh[FMT_WINDOW];
+    fmt_write_tile(FmtCellRows{a}, sh, a.n_vars, row_off, text, text_cap);
 }
 
 } // namespace

@@ -39,6 +39,7 @@ constexpr int TPB = 256;
 #include "block_pipeline.h"
 #include "gt_text_kernels.h"
 #include "call_text_kernels.h"
+#include "site_tags_kernels.h"
 #include "reads_kernels.h"
 
 } // namespace
@@ -143,6 +144,11 @@ struct mg_ctx {
     Scratch s_fmt[9];
     hipEvent_t ev_f[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
     bool fmt_stats_valid = false;
+    // mg_site_counts* / mg_format_site_info*: the host forms' staging (gt1, gt2, gq, var_allele_off, ac, ns, text, row_off), the row lengths
+    // and the meta block; events: start and end of the latest count call, then of the latest info-format call
+    Scratch s_site[10];
+    hipEvent_t ev_s[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool site_stats_valid[2] = {false, false};
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -681,6 +687,9 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     for (auto &e : c->ev_f)
         if (e) hipEventDestroy(e);
     for (auto &q : c->s_fmt) hipFree(q.p);
+    for (auto &e : c->ev_s)
+        if (e) hipEventDestroy(e);
+    for (auto &q : c->s_site) hipFree(q.p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3024,9 +3033,18 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
 }
 
 // ---- the sample columns of a batch as text (call_text_kernels.h) --------------------------------------------------------------
-MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
-                                     const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
-                                     uint64_t *text_bytes_out)
+namespace {
+// row lengths -> row_off[n + 1] (u64) and, in meta[0], the total (~0 when meta[1] is set): what the text passes share
+void fmt_scan(mg_ctx *c, const void *d_len, u64 n, u64 n_part, void *part, void *d_row_off, unsigned long long *meta)
+{
+    hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, n, (unsigned long long *)part);
+    hipLaunchKernelGGL(part_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, c->stream, (unsigned long long *)part, n_part, meta);
+    hipLaunchKernelGGL(fmt_rescan_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, n, (const unsigned long long *)part,
+                       (unsigned long long *)d_row_off, meta);
+}
+
+int format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int masked, int32_t min_gq,
+                        const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
@@ -3051,15 +3069,13 @@ MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes
     TRY(scratch(c, c->s_fmt[1], 16, &d_meta));
     const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
     TRY(scratch(c, c->s_scan, 8 * n_part, &part));
-    const FmtArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off};
+    const FmtArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
+                    masked, min_gq};
     unsigned long long *meta = (unsigned long long *)d_meta;
     HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
     hipLaunchKernelGGL(fmt_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len, meta);
     HIP_TRY(c, hipEventRecord(c->ev_f[1], c->stream));
-    hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, (u64)n_vars, (unsigned long long *)part);
-    hipLaunchKernelGGL(part_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, c->stream, (unsigned long long *)part, n_part, meta);
-    hipLaunchKernelGGL(fmt_rescan_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, (u64)n_vars, (const unsigned long long *)part,
-                       (unsigned long long *)d_row_off_out, meta);
+    fmt_scan(c, d_len, (u64)n_vars, n_part, part, d_row_off_out, meta);
     HIP_TRY(c, hipEventRecord(c->ev_f[2], c->stream));
     hipLaunchKernelGGL(fmt_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a,
                        (const unsigned long long *)d_row_off_out, (char *)d_text_out, (u64)text_cap);
@@ -3075,9 +3091,8 @@ MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes
     return MG_OK;
 }
 
-MG_EXPORT int mg_format_calls(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
-                              const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
-                              uint64_t *text_bytes_out)
+int format_calls_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int masked, int32_t min_gq,
+                      const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
@@ -3096,13 +3111,39 @@ MG_EXPORT int mg_format_calls(mg_ctx *c, size_t n_vars, uint32_t n_planes, int h
     }
     TRY(scratch(c, c->s_fmt[7], text_cap ? text_cap : 1, &d_text));
     TRY(scratch(c, c->s_fmt[8], 8 * (n_vars + 1), &d_off));
-    const int rc = mg_format_calls_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, d_cov, d_vao, d_text, text_cap, d_off, text_bytes_out);
+    const int rc = format_calls_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, masked, min_gq, d_cov, d_vao, d_text, text_cap, d_off, text_bytes_out);
     if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *text_bytes_out)) return rc; // (a text that does not fit: row_off and the first text_cap bytes are still the caller's)
     const size_t have = std::min<uint64_t>(*text_bytes_out, text_cap);
     HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
     if (have) HIP_TRY(c, hipMemcpyAsync(text_out, d_text, have, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return rc;
+}
+} // namespace
+MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
+                                     const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
+                                     uint64_t *text_bytes_out)
+{
+    return format_calls_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 0, 0, d_cov, d_var_allele_off, d_text_out, text_cap, d_row_off_out, text_bytes_out);
+}
+MG_EXPORT int mg_format_calls(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
+                              const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
+                              uint64_t *text_bytes_out)
+{
+    return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, 0, 0, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out);
+}
+// the same with the genotype of every cell whose gq < min_gq printed as missing
+MG_EXPORT int mg_format_calls_masked_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
+                                            int32_t min_gq, const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
+                                            void *d_row_off_out, uint64_t *text_bytes_out)
+{
+    return format_calls_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 1, min_gq, d_cov, d_var_allele_off, d_text_out, text_cap, d_row_off_out, text_bytes_out);
+}
+MG_EXPORT int mg_format_calls_masked(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
+                                     int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
+                                     uint64_t *row_off_out, uint64_t *text_bytes_out)
+{
+    return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, 1, min_gq, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out);
 }
 
 // device milliseconds of the most recent mg_format_calls* (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
@@ -3113,6 +3154,135 @@ MG_EXPORT int mg_format_stats(mg_ctx *c, float *ms_out)
     if (!c->fmt_stats_valid) return fail(c, MG_ERR_STATE, "no mg_format_calls yet");
     HIP_TRY(c, hipEventSynchronize(c->ev_f[3]));
     for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_f[i], c->ev_f[i + 1]));
+    return MG_OK;
+}
+
+// ---- the site tags of a merged batch (site_tags_kernels.h) ---------------------------------------------------------------------
+MG_EXPORT int mg_site_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                    int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_ac, void *d_ns)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_site_counts: n_planes is 1..64");
+    if (n_vars && (!d_var_allele_off || !d_gt1 || (!haploid && !d_gt2) || (use_mask && !d_gq) || !d_ns)) return fail(c, MG_ERR_ARG, "NULL argument"); // (d_ac may be: records without slots)
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_site_counts: more than 2^32 - 1 records in one call");
+    for (int i = 0; i < 2; ++i)
+        if (!c->ev_s[i]) HIP_TRY(c, hipEventCreate(&c->ev_s[i]));
+    c->site_stats_valid[0] = false;
+    HIP_TRY(c, hipEventRecord(c->ev_s[0], c->stream));
+    if (n_vars) {
+        const SiteArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u32 *)d_var_allele_off, accumulate};
+        hipLaunchKernelGGL(site_count_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_ac, (u32 *)d_ns);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_s[1], c->stream));
+    c->site_stats_valid[0] = true;
+    return MG_OK;
+}
+
+MG_EXPORT int mg_site_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                             int32_t min_gq, const uint32_t *var_allele_off, int accumulate, uint32_t *ac, uint32_t *ns)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_site_counts: n_planes is 1..64");
+    if (n_vars && !var_allele_off) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t slots = n_vars ? var_allele_off[n_vars] : 0;
+    if (n_vars && (!gt1 || (!haploid && !gt2) || (use_mask && !gq) || !ns || (slots && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t cells = 4 * (size_t)n_planes * n_vars;
+    void *d_g1, *d_g2 = nullptr, *d_gq = nullptr, *d_vao, *d_ac, *d_ns;
+    TRY(upload(c, c->s_site[0], gt1, cells, &d_g1));
+    if (!haploid) TRY(upload(c, c->s_site[1], gt2, cells, &d_g2));
+    if (use_mask) TRY(upload(c, c->s_site[2], gq, cells, &d_gq));
+    TRY(upload(c, c->s_site[3], var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
+    TRY(scratch(c, c->s_site[4], slots ? 4 * slots : 1, &d_ac));
+    TRY(scratch(c, c->s_site[5], n_vars ? 4 * n_vars : 1, &d_ns));
+    if (accumulate && slots) HIP_TRY(c, hipMemcpyAsync(d_ac, ac, 4 * slots, hipMemcpyHostToDevice, c->stream));
+    if (accumulate && n_vars) HIP_TRY(c, hipMemcpyAsync(d_ns, ns, 4 * n_vars, hipMemcpyHostToDevice, c->stream));
+    TRY(mg_site_counts_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, use_mask, min_gq, d_vao, accumulate, d_ac, d_ns));
+    if (slots) HIP_TRY(c, hipMemcpyAsync(ac, d_ac, 4 * slots, hipMemcpyDeviceToHost, c->stream));
+    if (n_vars) HIP_TRY(c, hipMemcpyAsync(ns, d_ns, 4 * n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_format_site_info_device(mg_ctx *c, size_t n_vars, const void *d_ac, const void *d_ns, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
+                                         void *d_row_off_out, uint64_t *text_bytes_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (!d_row_off_out || !text_bytes_out || (!d_text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars && (!d_ns || !d_var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_format_site_info: more than 2^32 - 1 records in one call");
+    for (int i = 2; i < 4; ++i)
+        if (!c->ev_s[i]) HIP_TRY(c, hipEventCreate(&c->ev_s[i]));
+    c->site_stats_valid[1] = false;
+    *text_bytes_out = 0;
+    HIP_TRY(c, hipEventRecord(c->ev_s[2], c->stream));
+    if (n_vars == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
+        HIP_TRY(c, hipEventRecord(c->ev_s[3], c->stream));
+        c->site_stats_valid[1] = true;
+        return MG_OK;
+    }
+    void *d_len, *d_meta, *part;
+    TRY(scratch(c, c->s_site[8], 4 * n_vars, &d_len));
+    TRY(scratch(c, c->s_site[9], 16, &d_meta));
+    const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    const InfoArgs a{(u64)n_vars, (const u32 *)d_ac, (const u32 *)d_ns, (const u32 *)d_var_allele_off};
+    unsigned long long *meta = (unsigned long long *)d_meta;
+    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
+    hipLaunchKernelGGL(info_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len, meta);
+    fmt_scan(c, d_len, (u64)n_vars, n_part, part, d_row_off_out, meta);
+    hipLaunchKernelGGL(info_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a,
+                       (const unsigned long long *)d_row_off_out, (char *)d_text_out, (u64)text_cap);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_s[3], c->stream));
+    c->site_stats_valid[1] = true;
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "mg_format_site_info: a row of 4 GB or more");
+    *text_bytes_out = total;
+    if (total > text_cap) return fail(c, MG_ERR_LIMIT, "mg_format_site_info: the text needs %llu bytes, text_cap is %llu", total, (unsigned long long)text_cap);
+    return MG_OK;
+}
+
+MG_EXPORT int mg_format_site_info(mg_ctx *c, size_t n_vars, const uint32_t *ac, const uint32_t *ns, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
+                                  uint64_t *row_off_out, uint64_t *text_bytes_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (!row_off_out || !text_bytes_out || (!text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars && (!ns || !var_allele_off || (var_allele_off[n_vars] && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
+    void *d_ac, *d_ns, *d_vao, *d_text, *d_off;
+    TRY(upload(c, c->s_site[4], ac, n_vars ? 4 * (size_t)var_allele_off[n_vars] : 0, &d_ac));
+    TRY(upload(c, c->s_site[5], ns, 4 * n_vars, &d_ns));
+    TRY(upload(c, c->s_site[3], var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
+    TRY(scratch(c, c->s_site[6], text_cap ? text_cap : 1, &d_text));
+    TRY(scratch(c, c->s_site[7], 8 * (n_vars + 1), &d_off));
+    const int rc = mg_format_site_info_device(c, n_vars, d_ac, d_ns, d_vao, d_text, text_cap, d_off, text_bytes_out);
+    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *text_bytes_out)) return rc; // (as mg_format_calls: row_off and the first text_cap bytes are still the caller's)
+    const size_t have = std::min<uint64_t>(*text_bytes_out, text_cap);
+    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
+    if (have) HIP_TRY(c, hipMemcpyAsync(text_out, d_text, have, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+// device milliseconds (waits for them): ms_out[0] the most recent mg_site_counts*, [1] the most recent mg_format_site_info* (its three passes together); 0 where there was none
+MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    if (!c->site_stats_valid[0] && !c->site_stats_valid[1]) return fail(c, MG_ERR_STATE, "no mg_site_counts or mg_format_site_info yet");
+    for (int i = 0; i < 2; ++i) {
+        ms_out[i] = 0.f; // (none of that kind yet)
+        if (!c->site_stats_valid[i]) continue;
+        HIP_TRY(c, hipEventSynchronize(c->ev_s[2 * i + 1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_s[2 * i], c->ev_s[2 * i + 1]));
+    }
     return MG_OK;
 }
 

@@ -1315,8 +1315,9 @@ inline std::string cleaned_header(const std::vector<std::string> &lines_in, bool
 }
 
 // header of the multi-sample VCF (call --cohort --merged): the single call's plain header with one column per sample in place of
-// DONOR; verbose: the cells carry a COVS field, declared as FORMAT (INFO stays '.', so neither INFO line of the verbose header)
-inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names)
+// DONOR; verbose: the cells carry a COVS field, declared as FORMAT (INFO stays '.', so neither INFO line of the verbose header);
+// site_tags: INFO carries AC / AN / AF / NS, each declared directly in front of #CHROM unless the panel's header declares that ID
+inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names, bool site_tags = false)
 {
     std::vector<std::string> lines = lines_in;
     const std::string covs = "##FORMAT=<ID=COVS";
@@ -1325,6 +1326,18 @@ inline std::string merged_header(const std::vector<std::string> &lines_in, bool 
     std::string out = cleaned_header(lines, false);
     out.resize(out.size() - std::string("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tDONOR\n").size());
     if (verbose && !declared) out += covs + ",Number=R,Type=Integer,Description=\"Allele coverages\">\n";
+    if (site_tags) {
+        static const char *const tags[4][2] = {{"AC", "A,Type=Integer,Description=\"Allele count in called genotypes, for each ALT allele\""},
+                                               {"AN", "1,Type=Integer,Description=\"Total number of alleles in called genotypes\""},
+                                               {"AF", "A,Type=Float,Description=\"Allele frequency in called genotypes, for each ALT allele\""},
+                                               {"NS", "1,Type=Integer,Description=\"Number of samples with a called genotype\""}};
+        for (const auto &t : tags) {
+            const std::string id = std::string("##INFO=<ID=") + t[0];
+            bool have = false;
+            for (const auto &l : lines) have = have || (l.compare(0, id.size(), id) == 0 && (l[id.size()] == ',' || l[id.size()] == '>'));
+            if (!have) out += id + ",Number=" + t[1] + ">\n";
+        }
+    }
     out += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
     for (const auto &n : names) out += "\t" + n;
     return out + "\n";

@@ -73,6 +73,12 @@ const char *USAGE =
     "                                        the sample columns are formatted on the GPU.  -o is then optional (both: both are\n"
     "                                        written in one pass).  With -v: INFO stays '.', FORMAT is GT:GQ:COVS and every cell\n"
     "                                        carries its sample's allele coverages; GTS (the likelihoods) is not carried   [this build]\n"
+    "          --min-gq                      --merged: a cell whose GQ is below this integer prints its genotype as missing ('./.',\n"
+    "                                        haploid '.'); its :GQ (and :COVS) stay.  The files of -o are not touched        [this build]\n"
+    "          --site-tags                   --merged: INFO becomes AC=..;AN=..;AF=..;NS=.. over the called (not masked) cells of the\n"
+    "                                        WHOLE cohort, whatever the grouping: AC per ALT allele, AN the called allele copies, AF =\n"
+    "                                        AC/AN rounded half up to six decimals (trailing zeros dropped; '.' when AN is 0), NS the\n"
+    "                                        samples with a called cell; counted and formatted on the GPU                    [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -104,6 +110,9 @@ struct Options { // argument_parser.hpp:51-66
     std::string out_dir;    // -o
     int cohort_group = 0;   // 0: as many as fit, at most 64
     std::string merged;     // --merged: the multi-sample VCF ("-": stdout)
+    bool use_min_gq = false; // --min-gq: cells of the merged output below it print a missing genotype
+    int32_t min_gq = 0;
+    bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -121,6 +130,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"min-count", required_argument, nullptr, 1001}, {"max-count", required_argument, nullptr, 1002},
                                       {"cohort", no_argument, nullptr, 1003},          {"cohort-group", required_argument, nullptr, 1004},
                                       {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
+                                      {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -166,6 +176,18 @@ bool parse_arguments(int argc, char **argv, Options &o)
                 die = true;
             }
             break;
+        case 1006: {
+            long long v = 0;
+            if (!(arg >> v) || !(arg >> std::ws).eof() || v < INT32_MIN || v > INT32_MAX) {
+                std::cerr << "malva : --min-gq takes an integer (int32)\n";
+                die = true;
+            } else {
+                o.use_min_gq = true;
+                o.min_gq = (int32_t)v;
+            }
+            break;
+        }
+        case 1007: o.site_tags = true; break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -189,6 +211,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (!o.cohort && !o.merged.empty()) {
         std::cerr << "malva : --merged goes with --cohort\n";
+        die = true;
+    }
+    if (o.merged.empty() && (o.use_min_gq || o.site_tags)) {
+        std::cerr << "malva : --min-gq and --site-tags go with --merged\n";
         die = true;
     }
     if (o.cohort && o.gpus > 1) {
@@ -1431,6 +1457,8 @@ int call_main(const Options &o)
     std::atomic<size_t> gt_bytes_uploaded{0}; // panel genotypes handed to mg_cover_blocks[_sparse], all batches
     double format_ms[3] = {0, 0, 0};          // --merged: device milliseconds of the mg_format_calls (length pass, scan, write pass; one worker at a time)
     size_t format_calls = 0;
+    double site_ms[2] = {0, 0};               // --site-tags: device milliseconds of the mg_site_counts and of the mg_format_site_info
+    size_t site_calls[2] = {0, 0};
     std::string header_text;
     {
         VcfReader hdr(o.vcf_path, "-");
@@ -1450,12 +1478,36 @@ int call_main(const Options &o)
     }
     pelapsed("VCF parsing and genotyping");
 
+    // --site-tags: the INFO strings of n records from their counts (mg_format_site_info), whoever holds the device
+    auto site_info = [&](Device &dev, size_t n, const uint32_t *ac, const uint32_t *ns, const uint32_t *var_allele_off, std::vector<char> &text,
+                         std::vector<uint64_t> &off) {
+        off.resize(n + 1);
+        text.resize(n * 40); // (a guess: the call says what it needs)
+        for (;;) {
+            uint64_t need = 0;
+            const int rc = mg_format_site_info(dev.ctx, n, ac, ns, var_allele_off, text.data(), text.size(), off.data(), &need);
+            if (rc == MG_ERR_LIMIT && need > text.size()) {
+                text.resize(need);
+                continue;
+            }
+            dev.check(rc, "mg_format_site_info");
+            break;
+        }
+        float ms[2] = {0, 0};
+        dev.check(mg_site_stats(dev.ctx, ms), "mg_site_stats");
+        site_ms[1] += ms[1];
+        ++site_calls[1];
+    };
+
     // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to outs[0] (stdout).  planes > 0: the
     // context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
     // only the INFO and GT:GQ fields per sample; sample p's text goes to outs[p] (outs empty: no per-sample text).  merged_out (--merged):
     // the group's block of the multi-sample VCF -- a record's sample columns come as text from the device (mg_format_calls), behind the
     // record's fixed columns when merged_fixed, else on their own (a later group's columns, pasted behind the first group's lines at the end).
-    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed) -> size_t {
+    // --site-tags: the records' allele counts over the group's planes are made beside the columns (mg_site_counts); cnt_out == nullptr: the
+    // group is the cohort and INFO is made from them at once (mg_format_site_info), else they go to cnt_out, per record in output order the
+    // u32s n_alleles, ns, ac[n_alleles], for the paste pass to sum over the groups.
+    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed, FILE *cnt_out) -> size_t {
     const size_t P = planes ? planes : 1;
 
     // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
@@ -1578,8 +1630,10 @@ int call_main(const Options &o)
                           "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
         }
         // --merged: the sample columns of both batches as text, made where the genotypes were
-        std::vector<char> row_text[2];
-        std::vector<uint64_t> row_off[2];
+        std::vector<char> row_text[2], info_text[2];
+        std::vector<uint64_t> row_off[2], info_off[2];
+        std::vector<uint32_t> site_ac[2], site_ns[2];
+        const bool tags = merged_out && o.site_tags;
         if (merged_out) {
             Timed t_fmt("worker: merged rows (mg_format_calls)");
             for (int w = 0; w < 2; ++w) {
@@ -1590,8 +1644,11 @@ int call_main(const Options &o)
                 row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0)); // (a guess: the call says what it needs)
                 for (;;) {
                     uint64_t need = 0;
-                    const int rc = mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.verbose ? b.cov.data() : nullptr,
-                                                   o.verbose ? b.var_allele_off.data() : nullptr, row_text[w].data(), row_text[w].size(), row_off[w].data(), &need);
+                    const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose ? b.var_allele_off.data() : nullptr;
+                    const int rc = o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao,
+                                                                         row_text[w].data(), row_text[w].size(), row_off[w].data(), &need)
+                                                : mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), cov, vao,
+                                                                  row_text[w].data(), row_text[w].size(), row_off[w].data(), &need);
                     if (rc == MG_ERR_LIMIT && need > row_text[w].size()) {
                         row_text[w].resize(need);
                         continue;
@@ -1603,22 +1660,43 @@ int call_main(const Options &o)
                 dev.check(mg_format_stats(dev.ctx, ms), "mg_format_stats");
                 for (int i = 0; i < 3; ++i) format_ms[i] += ms[i];
                 ++format_calls;
+                if (!tags) continue;
+                site_ac[w].resize(b.var_allele_off.back());
+                site_ns[w].resize(bn);
+                dev.check(mg_site_counts(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.var_allele_off.data(), 0,
+                                         site_ac[w].data(), site_ns[w].data()),
+                          "mg_site_counts");
+                dev.check(mg_site_stats(dev.ctx, ms), "mg_site_stats");
+                site_ms[0] += ms[0];
+                ++site_calls[0];
+                if (!cnt_out) site_info(dev, bn, site_ac[w].data(), site_ns[w].data(), b.var_allele_off.data(), info_text[w], info_off[w]);
             }
         }
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
-        std::vector<std::string> outv(outs.size() + 1); // (the last one: the merged block)
+        std::vector<std::string> outv(outs.size() + 2); // (the last two: the merged block, the records' counts for cnt_out)
         if (merged_out) {
-            std::string &out = outv.back();
+            std::string &out = outv[outs.size()], &cnt = outv.back();
             const char *fixed = o.verbose ? "\tPASS\t.\tGT:GQ:COVS" : "\tPASS\t.\tGT:GQ";
+            const bool info_here = tags && !cnt_out; // (else INFO stays '.' in the block: the paste pass puts it in)
             for (const Rec &r : recs) {
                 const int w = r.isolated ? 0 : 1;
-                if (merged_fixed) {
+                if (merged_fixed && info_here) {
+                    out += r.prefix;
+                    out += "\tPASS\t";
+                    out.append(info_text[w].data() + info_off[w][r.slot], info_text[w].data() + info_off[w][r.slot + 1]);
+                    out += fixed + 7; // (behind "\tPASS\t.")
+                } else if (merged_fixed) {
                     out += r.prefix;
                     out += fixed;
                 }
                 out.append(row_text[w].data() + row_off[w][r.slot], row_text[w].data() + row_off[w][r.slot + 1]);
+                if (tags && cnt_out) {
+                    const uint32_t head[2] = {r.n_alleles, site_ns[w][r.slot]};
+                    cnt.append((const char *)head, 8);
+                    cnt.append((const char *)(site_ac[w].data() + r.allele0), 4 * (size_t)r.n_alleles);
+                }
             }
         }
         char num[64];
@@ -1677,7 +1755,9 @@ int call_main(const Options &o)
             in_flight.pop_front();
             for (size_t pl = 0; pl < outs.size(); ++pl)
                 if (fwrite(text[pl].data(), 1, text[pl].size(), outs[pl]) != text[pl].size()) throw std::runtime_error("cannot write the output");
-            if (merged_out && fwrite(text.back().data(), 1, text.back().size(), merged_out) != text.back().size()) throw std::runtime_error("cannot write the merged output");
+            const std::string &block = text[outs.size()];
+            if (merged_out && fwrite(block.data(), 1, block.size(), merged_out) != block.size()) throw std::runtime_error("cannot write the merged output");
+            if (cnt_out && fwrite(text.back().data(), 1, text.back().size(), cnt_out) != text.back().size()) throw std::runtime_error("cannot write the merged output's counts");
         }
     };
     auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
@@ -1794,11 +1874,12 @@ int call_main(const Options &o)
     drain(0);
     for (FILE *f : outs) fflush(f);
     if (merged_out) fflush(merged_out);
+    if (cnt_out) fflush(cnt_out);
     return n;
     }; // vcf_pass
 
     size_t n = 0;
-    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false);
+    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr);
     else {
         if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
         Device &dev = devs[0];
@@ -1808,12 +1889,15 @@ int call_main(const Options &o)
         // Whatever is left of them is removed when this frame is left, on success and on error.
         struct MergedFiles {
             std::vector<std::string> paths; // temporary files, the first group's first
+            std::vector<std::string> cnt_paths; // --site-tags: the groups' counts (PATH.gN.cnt.part)
             std::string part;               // PATH.part
-            FILE *open = nullptr;
+            FILE *open = nullptr, *cnt_open = nullptr;
             ~MergedFiles()
             {
                 if (open && open != stdout) fclose(open);
+                if (cnt_open) fclose(cnt_open);
                 for (const auto &p : paths) unlink(p.c_str());
+                for (const auto &p : cnt_paths) unlink(p.c_str());
                 if (!part.empty()) unlink(part.c_str());
             }
         } merged;
@@ -1825,7 +1909,7 @@ int call_main(const Options &o)
             if (!hdr.ok()) throw std::runtime_error(hdr.error);
             std::vector<std::string> names;
             for (const auto &sm : samples) names.push_back(sm.name);
-            merged_head = merged_header(hdr.header_lines, o.verbose, names);
+            merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags);
         }
         bool merged_direct = false; // one group: no temporary blocks
         size_t G = o.cohort_group ? (size_t)o.cohort_group : std::min<size_t>(samples.size(), 64);
@@ -1880,6 +1964,12 @@ int call_main(const Options &o)
                     merged.open = fopen(path.c_str(), "wb");
                     if (!merged.open) throw std::runtime_error("cannot write " + path);
                 }
+                if (o.site_tags && !merged_direct) {
+                    const std::string path = merged_tmp_base + ".g" + std::to_string(merged.cnt_paths.size()) + ".cnt.part";
+                    merged.cnt_paths.push_back(path);
+                    merged.cnt_open = fopen(path.c_str(), "wb");
+                    if (!merged.cnt_open) throw std::runtime_error("cannot write " + path);
+                }
                 if (s0 == 0 && fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size()) throw std::runtime_error("cannot write the merged output");
             }
             {
@@ -1890,7 +1980,12 @@ int call_main(const Options &o)
                     start_vcf(*again);
                     if (!again->ok()) throw std::runtime_error(again->error);
                 }
-                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0);
+                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0, merged.cnt_open);
+            }
+            if (merged.cnt_open) {
+                FILE *closing = merged.cnt_open;
+                merged.cnt_open = nullptr;
+                if (fclose(closing) != 0) throw std::runtime_error("cannot write the merged output's counts");
             }
             if (merged.open) {
                 FILE *closing = merged.open;
@@ -1910,14 +2005,50 @@ int call_main(const Options &o)
         }
         if (!o.merged.empty() && !merged_direct) { // line i of the output = line i of every group's block, one behind the other
             Timed t("cohort: merged paste");
-            std::vector<FILE *> in;
+            std::vector<FILE *> in, cnt_in;
             struct CloseAll {
                 std::vector<FILE *> &v;
                 ~CloseAll()
                 {
                     for (FILE *f : v) fclose(f);
                 }
-            } close_all{in};
+            } close_all{in}, close_cnt{cnt_in};
+            for (const auto &p : merged.cnt_paths) {
+                cnt_in.push_back(fopen(p.c_str(), "rb"));
+                if (!cnt_in.back()) {
+                    cnt_in.pop_back();
+                    throw std::runtime_error("cannot read " + p);
+                }
+            }
+            // --site-tags: the groups' counts summed, 65,536 records at a time (MALVA_GENO_BATCH, when set: tests), and their INFO strings made on the device
+            const size_t paste_batch = getenv("MALVA_GENO_BATCH") ? (size_t)std::max(1L, atol(getenv("MALVA_GENO_BATCH"))) : 65536;
+            std::vector<uint32_t> p_ac, p_ns, p_vao, p_more;
+            std::vector<char> p_text;
+            std::vector<uint64_t> p_off;
+            size_t p_at = 0;
+            auto next_infos = [&]() {
+                const char *short_file = "internal: a group's counts for the merged output are short";
+                p_ac.clear();
+                p_ns.clear();
+                p_vao.assign(1, 0u);
+                uint32_t head[2], more[2];
+                while (p_ns.size() < paste_batch && fread(head, 4, 2, cnt_in[0]) == 2) {
+                    const size_t A = head[0], at = p_ac.size();
+                    p_ac.resize(at + A);
+                    if (A && fread(&p_ac[at], 4, A, cnt_in[0]) != A) throw std::runtime_error(short_file);
+                    p_more.resize(A);
+                    for (size_t gi = 1; gi < cnt_in.size(); ++gi) {
+                        if (fread(more, 4, 2, cnt_in[gi]) != 2 || more[0] != A || (A && fread(p_more.data(), 4, A, cnt_in[gi]) != A)) throw std::runtime_error(short_file);
+                        head[1] += more[1];
+                        for (size_t a = 0; a < A; ++a) p_ac[at + a] += p_more[a];
+                    }
+                    p_ns.push_back(head[1]);
+                    p_vao.push_back((uint32_t)p_ac.size());
+                }
+                if (p_ns.empty()) throw std::runtime_error(short_file);
+                site_info(dev, p_ns.size(), p_ac.data(), p_ns.data(), p_vao.data(), p_text, p_off);
+                p_at = 0;
+            };
             for (const auto &p : merged.paths) {
                 in.push_back(fopen(p.c_str(), "rb"));
                 if (!in.back()) {
@@ -1943,7 +2074,20 @@ int call_main(const Options &o)
                 if (len < 0) break;
                 const bool record = line[0] != '#';
                 if (record && len && line[len - 1] == '\n') --len;
-                out.append(line, (size_t)len);
+                if (record && o.site_tags) { // INFO, the eighth column, is the block's '.'
+                    if (p_at == p_ns.size()) next_infos();
+                    const char *at = line;
+                    for (int t = 0; t < 7 && at; ++t) {
+                        at = (const char *)memchr(at, '\t', (size_t)(line + len - at));
+                        if (at) ++at;
+                    }
+                    if (!at || line + len - at < 2 || at[0] != '.' || at[1] != '\t') throw std::runtime_error("internal: a line of the merged output's first block has no INFO column");
+                    out.append(line, (size_t)(at - line));
+                    out.append(p_text.data() + p_off[p_at], p_text.data() + p_off[p_at + 1]);
+                    out.append(at + 1, (size_t)(line + len - at - 1));
+                    ++p_at;
+                } else
+                    out.append(line, (size_t)len);
                 for (size_t gi = 1; record && gi < in.size(); ++gi) {
                     ssize_t more = getline(&line, &line_cap, in[gi]);
                     if (more <= 0) throw std::runtime_error("internal: a group's block of the merged output is short");
@@ -1969,6 +2113,9 @@ int call_main(const Options &o)
             if (g_timers.on)
                 fprintf(stderr, "[malva-geno] merged: %zu mg_format_calls, device ms per call: length %.3f scan %.3f write %.3f\n", format_calls,
                         format_ms[0] / format_calls, format_ms[1] / format_calls, format_ms[2] / format_calls);
+            if (g_timers.on && site_calls[0] && site_calls[1])
+                fprintf(stderr, "[malva-geno] merged: %zu mg_site_counts, %zu mg_format_site_info, device ms per call: count %.3f info %.3f\n", site_calls[0], site_calls[1],
+                        site_ms[0] / site_calls[0], site_ms[1] / site_calls[1]);
         }
     }
     if (gt_bytes_uploaded) std::cerr << "[malva-geno] panel genotypes of the general blocks: " << gt_bytes_uploaded.load() << " bytes uploaded" << std::endl;

@@ -4,6 +4,8 @@ isolated SNPs, 16 samples that all name one text dump of 2e6 k-mers.
 Timed, each the median of --repeats runs with their spread:
     per_sample   `--cohort -o OUTDIR`         wall time and the `cohort: panel pass` timer (MALVA_GENO_TIMERS=1)
     merged       `--cohort --merged PATH`     the same two, and the device milliseconds per mg_format_calls (mg_format_stats)
+    merged_tags  the same with `--min-gq Q --site-tags` (Q: --min-gq, default 20): the same, and the device milliseconds per
+                 mg_site_counts and per mg_format_site_info (mg_site_stats) beside them
     parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick
 The runs alternate (parent, per_sample, merged, parent, ...), so that whatever else the host is doing falls on all three alike.
 merged_equals_paste: the merged file is the column paste of the per-sample files.
@@ -67,6 +69,7 @@ def main():
     ap.add_argument("--snps", type=int, default=1_000_000)
     ap.add_argument("--rows", type=int, default=2_000_000)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--min-gq", type=int, default=20, help="Q of the merged_tags leg")
     ap.add_argument("--parent-bin", default=None, help="malva-geno of the parent commit: its `--cohort -o` panel pass is the yardstick")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cohort_merged_bench.json"))
     a = ap.parse_args()
@@ -90,11 +93,13 @@ def main():
         common = ["-k", str(K), "-r", str(REF_K), "-b", "4", prefix + ".fa", prefix + ".vcf"]
         subprocess.run([BIN, "index"] + common + [os.path.join(td, "sample")], check=True, capture_output=True, timeout=600)
         env = dict(os.environ, MALVA_GENO_TIMERS="1")
-        legs = {"per_sample": (BIN, ["-o", os.path.join(td, "out")]), "merged": (BIN, ["--merged", os.path.join(td, "merged.vcf")])}
+        legs = {"per_sample": (BIN, ["-o", os.path.join(td, "out")]), "merged": (BIN, ["--merged", os.path.join(td, "merged.vcf")]),
+                "merged_tags": (BIN, ["--merged", os.path.join(td, "merged_tags.vcf"), "--min-gq", str(a.min_gq), "--site-tags"])}
         if a.parent_bin:
             legs = dict({"parent": (a.parent_bin, ["-o", os.path.join(td, "out_parent")])}, **legs)
         res = {leg: {"wall_s": [], "panel_pass_s": []} for leg in legs}
-        fmt_ms, fmt_calls = [], 0
+        fmt_ms, fmt_calls = {"merged": [], "merged_tags": []}, 0
+        site_ms, site_calls = [], [0, 0]
 
         def run(leg):
             b, dest = legs[leg]
@@ -110,17 +115,27 @@ def main():
                 wall, err = run(leg)
                 res[leg]["wall_s"].append(wall)
                 res[leg]["panel_pass_s"].append(timer(err, "cohort: panel pass"))
-                if leg == "merged":
+                if leg in fmt_ms:
                     m = re.search(r"merged: (\d+) mg_format_calls, device ms per call: length ([0-9.]+) scan ([0-9.]+) write ([0-9.]+)", err)
                     fmt_calls = int(m.group(1))
-                    fmt_ms.append([float(m.group(i)) for i in (2, 3, 4)])
+                    fmt_ms[leg].append([float(m.group(i)) for i in (2, 3, 4)])
+                if leg == "merged_tags":
+                    m = re.search(r"merged: (\d+) mg_site_counts, (\d+) mg_format_site_info, device ms per call: count ([0-9.]+) info ([0-9.]+)", err)
+                    site_calls = [int(m.group(1)), int(m.group(2))]
+                    site_ms.append([float(m.group(3)), float(m.group(4))])
+                if leg == "merged":
                     out["merged_timers"] = [l.split("]", 1)[1].strip() for l in err.split("\n") if "timer]" in l and ("cohort" in l or "merged" in l or "worker" in l or "main" in l)]
                 if leg == "per_sample":
                     out["per_sample_timers"] = [l.split("]", 1)[1].strip() for l in err.split("\n") if "timer]" in l and ("cohort" in l or "worker" in l or "main" in l)]
         for leg in legs:
             out[leg] = {key: stat(v) for key, v in res[leg].items()}
         out["format_calls_per_run"] = fmt_calls
-        out["format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms]) for i, name in enumerate(("length", "scan", "write"))}
+        out["format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms["merged"]]) for i, name in enumerate(("length", "scan", "write"))}
+        out["tags_min_gq"] = a.min_gq
+        out["tags_format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms["merged_tags"]]) for i, name in enumerate(("length", "scan", "write"))}
+        out["site_calls_per_run"] = {"count": site_calls[0], "info": site_calls[1]}
+        out["site_ms_per_call"] = {name: stat([x[i] for x in site_ms]) for i, name in enumerate(("count", "info"))}
+        out["merged_tags_bytes"] = os.path.getsize(os.path.join(td, "merged_tags.vcf"))
         out["merged_bytes"] = os.path.getsize(os.path.join(td, "merged.vcf"))
         out["per_sample_bytes"] = sum(os.path.getsize(os.path.join(td, "out", "s%02d.vcf" % i)) for i in range(S))
         out["merged_equals_paste"] = int(is_paste(os.path.join(td, "merged.vcf"), [os.path.join(td, "out", "s%02d.vcf" % i) for i in range(S)]))
