@@ -532,6 +532,35 @@ int mg_format_site_info_device(mg_ctx *ctx, size_t n_vars, const void *d_ac, con
                                void *d_row_off_out, uint64_t *text_bytes_out);
 int mg_site_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- the sample columns of a multi-sample BCF --------------------------------------
+ * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
+ * parity with htslib unpinned).  Arrays, n_planes (1..64), the host and _device forms, the stream behaviour and the buffer
+ * contract are mg_format_calls_masked's: *bytes_out (a HOST pointer in both forms) always receives the bytes needed,
+ * MG_ERR_LIMIT when that exceeds out_cap, nothing written at or behind out_cap, row_off_out valid all the same, n_vars == 0
+ * legal.  Row v = out[row_off_out[v] .. row_off_out[v + 1]) is exactly the record's per-sample ("indiv") block, its length the
+ * record's l_indiv: two fields, three with cov (cov and var_allele_off: both or neither), in this order --
+ *   GT    typed_int(key_gt),  desc(ploidy, T), for every plane `ploidy` values (1 in haploid mode, else 2): allele index a
+ *         as (a + 1) << 1, unphased; a cell with use_mask != 0 and gq < min_gq writes 0 (missing) for each of its values
+ *   GQ    typed_int(key_gq),  desc(1, T), one value per plane, as it is, mask or no mask
+ *   COVS  typed_int(key_cov), desc(A, T), for every plane the record's A = var_allele_off[v + 1] - var_allele_off[v] values
+ *         (int32_t)cov[..]
+ * desc(n, t): the byte n << 4 | t for n < 15, else 0xF0 | t and typed_int(n).  typed_int(x): desc(1, t) and x in the smallest of
+ * int8 (t = 1), int16 (2), int32 (3) that holds it.  Little endian.  T of a field of a record is the smallest type holding every
+ * value of the field over all planes with BCF's reserved codes kept free: int8 for [-120, 127], int16 for [-32760, 32767], else
+ * int32 (a field without values: int8).  An int32 value inside int32's reserved range [INT32_MIN, INT32_MIN + 7] is written as
+ * it is: what a reader makes of it is the caller's business.
+ * Where this departs from the text: an allele index outside [0, 2^30 - 2] has no code and writes 0 (missing), where
+ * mg_format_calls prints the index as it is.  The keys are the header's dictionary indexes, >= 0 (key_cov is not read without cov).
+ * mg_bcf_stats (waits): ms_out[3], device milliseconds of the most recent call's length pass, scan and write pass;
+ * MG_ERR_STATE before the first call. */
+int mg_encode_calls_bcf(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                        int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
+                        size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out);
+int mg_encode_calls_bcf_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                               int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
+                               size_t out_cap, void *d_row_off_out, uint64_t *bytes_out);
+int mg_bcf_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- index payloads  (bloom_filter.hpp:127-146, kmap.hpp:52-82) ----------- */
 
 /* BF: _mode, _size, bit words (ceil(size/64) u64), counters (n_set u16).

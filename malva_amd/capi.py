@@ -117,6 +117,9 @@ def lib():
         "mg_format_site_info": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
         "mg_format_site_info_device": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
         "mg_site_stats": [vp, vp],
+        "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
+        "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
+        "mg_bcf_stats": [vp, vp],
         "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
         "mg_comm_unique_id": [vp],
         "mg_comm_init": [vp, it, it, vp],
@@ -179,7 +182,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_cohort_begin", "mg_cohort_select", "mg_cohort_end", "mg_cohort_info", "mg_cover_blocks_cohort_device", "mg_cohort_stats", "mg_cover_blocks_cohort",
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
-            "mg_format_site_info_device", "mg_site_stats",
+            "mg_format_site_info_device", "mg_site_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
@@ -691,6 +694,50 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_site_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
+
+    # the sample columns of a multi-sample BCF
+    def encode_calls_bcf(self, gt1, gt2, gq, haploid, keys, cov=None, var_allele_off=None, out_cap=None, min_gq=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 -> (bytes, row_off): row v = bytes[row_off[v]:row_off[v + 1]] is record v's BCF
+        per-sample block, fields GT, GQ and (with cov [planes, slots] and var_allele_off [n_vars + 1]) COVS.  keys: the header's
+        dictionary indexes (gt, gq, cov).  out_cap and min_gq as format_calls' text_cap and min_gq; a buffer that is too small
+        raises MalvaError(MG_ERR_LIMIT) with .needed, .row_off and .text set."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
+        planes, n = g1.shape
+        cv, vo = a(cov, np.uint32), a(var_allele_off, np.uint32)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+
+        def call(cap):
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self._L.mg_encode_calls_bcf(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(cv), _p(vo),
+                                             int(keys[0]), int(keys[1]), int(keys[2]), _p(out) if cap else None, cap, _p(row_off), C.byref(need))
+            return rc, out
+        rc, out = call(0 if out_cap is None else int(out_cap))
+        if rc == -5 and out_cap is None and need.value:
+            rc, out = call(need.value)
+        if rc != 0:
+            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
+            e.needed, e.row_off, e.text = need.value, row_off, out
+            raise e
+        return out[:need.value].tobytes(), row_off
+
+    def encode_calls_bcf_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, keys, d_out, out_cap, d_row_off, min_gq=None):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_encode_calls_bcf_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
+                                                v(d_cov), v(d_var_allele_off), int(keys[0]), int(keys[1]), int(keys[2]), v(d_out), int(out_cap), v(d_row_off),
+                                                C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
+    def bcf_stats(self):
+        """-> device ms of the most recent encode_calls_bcf: (length pass, scan, write pass)"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.mg_bcf_stats(self.h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # multi-GPU exchange inside the library (RCCL)
     def comm_init(self, rank, world, comm_id: bytes):

@@ -40,6 +40,7 @@ constexpr int TPB = 256;
 #include "gt_text_kernels.h"
 #include "call_text_kernels.h"
 #include "site_tags_kernels.h"
+#include "bcf_kernels.h"
 #include "reads_kernels.h"
 
 } // namespace
@@ -149,6 +150,10 @@ struct mg_ctx {
     Scratch s_site[10];
     hipEvent_t ev_s[4] = {nullptr, nullptr, nullptr, nullptr};
     bool site_stats_valid[2] = {false, false};
+    // mg_encode_calls_bcf*: row lengths, the meta block, the records' type codes, and the host form's staging (gt1, gt2, gq, cov, var_allele_off, out, row_off)
+    Scratch s_bcf[10];
+    hipEvent_t ev_bcf[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
+    bool bcf_stats_valid = false;
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -690,6 +695,9 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     for (auto &e : c->ev_s)
         if (e) hipEventDestroy(e);
     for (auto &q : c->s_site) hipFree(q.p);
+    for (auto &e : c->ev_bcf)
+        if (e) hipEventDestroy(e);
+    for (auto &q : c->s_bcf) hipFree(q.p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3283,6 +3291,101 @@ MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
         HIP_TRY(c, hipEventSynchronize(c->ev_s[2 * i + 1]));
         HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_s[2 * i], c->ev_s[2 * i + 1]));
     }
+    return MG_OK;
+}
+
+// ---- the sample columns of a batch as BCF (bcf_kernels.h) -----------------------------------------------------------------------
+MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                         int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
+                                         size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: n_planes is 1..64");
+    if (!d_row_off_out || !bytes_out || (!d_out && out_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if ((d_cov != nullptr) != (d_var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: cov and var_allele_off go together");
+    if (key_gt < 0 || key_gq < 0 || (d_cov && key_cov < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
+    if (n_vars && (!d_gt1 || !d_gq || (!haploid && !d_gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_encode_calls_bcf: more than 2^32 - 1 records in one call");
+    for (auto &e : c->ev_bcf)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->bcf_stats_valid = false;
+    *bytes_out = 0;
+    HIP_TRY(c, hipEventRecord(c->ev_bcf[0], c->stream));
+    if (n_vars == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
+        for (int i = 1; i < 4; ++i) HIP_TRY(c, hipEventRecord(c->ev_bcf[i], c->stream));
+        c->bcf_stats_valid = true;
+        return MG_OK;
+    }
+    void *d_len, *d_meta, *d_types, *part;
+    TRY(scratch(c, c->s_bcf[0], 4 * n_vars, &d_len));
+    TRY(scratch(c, c->s_bcf[1], 16, &d_meta));
+    TRY(scratch(c, c->s_bcf[2], 3 * n_vars, &d_types));
+    const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    const BcfArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
+                    use_mask, min_gq, key_gt, key_gq, key_cov};
+    unsigned long long *meta = (unsigned long long *)d_meta;
+    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
+    hipLaunchKernelGGL(bcf_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len,
+                       (unsigned char *)d_types, meta);
+    HIP_TRY(c, hipEventRecord(c->ev_bcf[1], c->stream));
+    fmt_scan(c, d_len, (u64)n_vars, n_part, part, d_row_off_out, meta);
+    HIP_TRY(c, hipEventRecord(c->ev_bcf[2], c->stream));
+    hipLaunchKernelGGL(bcf_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types,
+                       (const unsigned long long *)d_row_off_out, (char *)d_out, (u64)out_cap);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_bcf[3], c->stream));
+    c->bcf_stats_valid = true;
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "mg_encode_calls_bcf: a row of 4 GB or more");
+    *bytes_out = total;
+    if (total > out_cap) return fail(c, MG_ERR_LIMIT, "mg_encode_calls_bcf: the rows need %llu bytes, out_cap is %llu", total, (unsigned long long)out_cap);
+    return MG_OK;
+}
+
+MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                  int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
+                                  size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: n_planes is 1..64");
+    if (!row_off_out || !bytes_out || (!out && out_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if ((cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: cov and var_allele_off go together");
+    if (n_vars && (!gt1 || !gq || (!haploid && !gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t cells = 4 * (size_t)n_planes * n_vars;
+    void *d_g1, *d_g2 = nullptr, *d_gq, *d_cov = nullptr, *d_vao = nullptr, *d_out, *d_off;
+    TRY(upload(c, c->s_bcf[3], gt1, cells, &d_g1));
+    if (!haploid) TRY(upload(c, c->s_bcf[4], gt2, cells, &d_g2));
+    TRY(upload(c, c->s_bcf[5], gq, cells, &d_gq));
+    if (cov) {
+        TRY(upload(c, c->s_bcf[6], cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d_cov));
+        TRY(upload(c, c->s_bcf[7], var_allele_off, 4 * (n_vars + 1), &d_vao));
+    }
+    TRY(scratch(c, c->s_bcf[8], out_cap ? out_cap : 1, &d_out));
+    TRY(scratch(c, c->s_bcf[9], 8 * (n_vars + 1), &d_off));
+    const int rc = mg_encode_calls_bcf_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, use_mask, min_gq, d_cov, d_vao, key_gt, key_gq, key_cov, d_out, out_cap,
+                                              d_off, bytes_out);
+    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *bytes_out)) return rc; // (as mg_format_calls: row_off and the first out_cap bytes are still the caller's)
+    const size_t have = std::min<uint64_t>(*bytes_out, out_cap);
+    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
+    if (have) HIP_TRY(c, hipMemcpyAsync(out, d_out, have, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+// device milliseconds of the most recent mg_encode_calls_bcf* (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
+MG_EXPORT int mg_bcf_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    if (!c->bcf_stats_valid) return fail(c, MG_ERR_STATE, "no mg_encode_calls_bcf yet");
+    HIP_TRY(c, hipEventSynchronize(c->ev_bcf[3]));
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_bcf[i], c->ev_bcf[i + 1]));
     return MG_OK;
 }
 

@@ -1316,8 +1316,10 @@ inline std::string cleaned_header(const std::vector<std::string> &lines_in, bool
 
 // header of the multi-sample VCF (call --cohort --merged): the single call's plain header with one column per sample in place of
 // DONOR; verbose: the cells carry a COVS field, declared as FORMAT (INFO stays '.', so neither INFO line of the verbose header);
-// site_tags: INFO carries AC / AN / AF / NS, each declared directly in front of #CHROM unless the panel's header declares that ID
-inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names, bool site_tags = false)
+// site_tags: INFO carries AC / AN / AF / NS, each declared directly in front of #CHROM unless the panel's header declares that ID;
+// contig_lines (the BCF form of the file, host/bcf_out.hpp): lines that go directly in front of those
+inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names, bool site_tags = false,
+                                 const std::vector<std::string> &contig_lines = {})
 {
     std::vector<std::string> lines = lines_in;
     const std::string covs = "##FORMAT=<ID=COVS";
@@ -1326,6 +1328,7 @@ inline std::string merged_header(const std::vector<std::string> &lines_in, bool 
     std::string out = cleaned_header(lines, false);
     out.resize(out.size() - std::string("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tDONOR\n").size());
     if (verbose && !declared) out += covs + ",Number=R,Type=Integer,Description=\"Allele coverages\">\n";
+    for (const auto &l : contig_lines) out += l + "\n";
     if (site_tags) {
         static const char *const tags[4][2] = {{"AC", "A,Type=Integer,Description=\"Allele count in called genotypes, for each ALT allele\""},
                                                {"AN", "1,Type=Integer,Description=\"Total number of alleles in called genotypes\""},

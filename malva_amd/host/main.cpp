@@ -28,6 +28,7 @@
 #include "kmc_db.hpp"
 #include "reads.hpp"
 #include "cohort.hpp"
+#include "bcf_out.hpp"
 extern "C" {
 #include "malva_hip.h"
 }
@@ -79,6 +80,13 @@ const char *USAGE =
     "                                        WHOLE cohort, whatever the grouping: AC per ALT allele, AN the called allele copies, AF =\n"
     "                                        AC/AN rounded half up to six decimals (trailing zeros dropped; '.' when AN is 0), NS the\n"
     "                                        samples with a called cell; counted and formatted on the GPU                    [this build]\n"
+    "          --merged-format               --merged: vcf (default: the text above), bcf (BCF2, BGZF-compressed) or ubcf (the same\n"
+    "                                        bytes uncompressed).  The same records and fields as the text; a cell costs 3 bytes\n"
+    "                                        (diploid GT:GQ) instead of 8 to 10, and the per-sample part of every record is encoded\n"
+    "                                        on the GPU.  A panel header without ##contig lines gets one per reference sequence;\n"
+    "                                        one with some must name every CHROM.  Combines with -1, -v (FORMAT COVS), --min-gq,\n"
+    "                                        --site-tags and -o.  Written from the published layout, like the BCF reader: no file\n"
+    "                                        written by bcftools was available to compare with (format UNPINNED)          [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -91,7 +99,7 @@ const char *USAGE =
     "  extra sub-commands (no GPU needed): dump-kmers (signature k-mers of every block); index-convert <fa> <vcf> zst|hipz\n"
     "\n"
     "  Verified inputs: the text k-mer dump and text / gzip / bgzip VCF (checked against the reference's own example).  The three\n"
-    "  BINARY formats -- a KMC database, a BCF panel, the reference's sdsl + zstd index container -- are read and written from their\n"
+    "  BINARY formats -- a KMC database, a BCF panel (and the BCF of --merged-format), the reference's sdsl + zstd index container -- are read and written from their\n"
     "  published layouts and checked against an independent second implementation only: no file written by KMC, bcftools or the\n"
     "  reference binary was available to this build (formats UNPINNED).  When in doubt convert: `kmc_tools transform <db> dump`,\n"
     "  `bcftools view -Ov`, and let this build write its own index.\n";
@@ -113,6 +121,7 @@ struct Options { // argument_parser.hpp:51-66
     bool use_min_gq = false; // --min-gq: cells of the merged output below it print a missing genotype
     int32_t min_gq = 0;
     bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
+    std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -131,6 +140,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"cohort", no_argument, nullptr, 1003},          {"cohort-group", required_argument, nullptr, 1004},
                                       {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
                                       {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
+                                      {"merged-format", required_argument, nullptr, 1008},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -188,6 +198,13 @@ bool parse_arguments(int argc, char **argv, Options &o)
             break;
         }
         case 1007: o.site_tags = true; break;
+        case 1008:
+            o.merged_format = optarg;
+            if (o.merged_format != "vcf" && o.merged_format != "bcf" && o.merged_format != "ubcf") {
+                std::cerr << "malva : --merged-format takes vcf, bcf or ubcf\n";
+                die = true;
+            }
+            break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -215,6 +232,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.merged.empty() && (o.use_min_gq || o.site_tags)) {
         std::cerr << "malva : --min-gq and --site-tags go with --merged\n";
+        die = true;
+    }
+    if (o.merged.empty() && !o.merged_format.empty()) {
+        std::cerr << "malva : --merged-format goes with --merged\n";
         die = true;
     }
     if (o.cohort && o.gpus > 1) {
@@ -1459,6 +1480,13 @@ int call_main(const Options &o)
     size_t format_calls = 0;
     double site_ms[2] = {0, 0};               // --site-tags: device milliseconds of the mg_site_counts and of the mg_format_site_info
     size_t site_calls[2] = {0, 0};
+    // --merged-format bcf | ubcf: the merged file as BCF2 (host/bcf_out.hpp), a record's per-sample block encoded by mg_encode_calls_bcf
+    const bool bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", bcf_bgzf = o.merged_format == "bcf";
+    BcfHeader bcf_hdr;
+    bool bcf_direct = false;                  // the cohort runs as one group: whole records leave the workers
+    size_t bcf_samples = 0;                   // the cohort's samples
+    double bcf_ms[3] = {0, 0, 0};             // device milliseconds of the mg_encode_calls_bcf (length pass, scan, write pass)
+    size_t bcf_calls = 0;
     std::string header_text;
     {
         VcfReader hdr(o.vcf_path, "-");
@@ -1635,7 +1663,7 @@ int call_main(const Options &o)
         std::vector<uint32_t> site_ac[2], site_ns[2];
         const bool tags = merged_out && o.site_tags;
         if (merged_out) {
-            Timed t_fmt("worker: merged rows (mg_format_calls)");
+            Timed t_fmt(bcf_out ? "worker: merged rows (mg_encode_calls_bcf)" : "worker: merged rows (mg_format_calls)");
             for (int w = 0; w < 2; ++w) {
                 Batch &b = w ? gen : iso;
                 const size_t bn = b.n();
@@ -1645,7 +1673,10 @@ int call_main(const Options &o)
                 for (;;) {
                     uint64_t need = 0;
                     const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose ? b.var_allele_off.data() : nullptr;
-                    const int rc = o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao,
+                    const int rc = bcf_out ? mg_encode_calls_bcf(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
+                                                                 bcf_hdr.key("GT"), bcf_hdr.key("GQ"), o.verbose ? bcf_hdr.key("COVS") : 0,
+                                                                 (uint8_t *)row_text[w].data(), row_text[w].size(), row_off[w].data(), &need)
+                                   : o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao,
                                                                          row_text[w].data(), row_text[w].size(), row_off[w].data(), &need)
                                                 : mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), cov, vao,
                                                                   row_text[w].data(), row_text[w].size(), row_off[w].data(), &need);
@@ -1653,13 +1684,19 @@ int call_main(const Options &o)
                         row_text[w].resize(need);
                         continue;
                     }
-                    dev.check(rc, "mg_format_calls");
+                    dev.check(rc, bcf_out ? "mg_encode_calls_bcf" : "mg_format_calls");
                     break;
                 }
                 float ms[3] = {0, 0, 0};
-                dev.check(mg_format_stats(dev.ctx, ms), "mg_format_stats");
-                for (int i = 0; i < 3; ++i) format_ms[i] += ms[i];
-                ++format_calls;
+                if (bcf_out) {
+                    dev.check(mg_bcf_stats(dev.ctx, ms), "mg_bcf_stats");
+                    for (int i = 0; i < 3; ++i) bcf_ms[i] += ms[i];
+                    ++bcf_calls;
+                } else {
+                    dev.check(mg_format_stats(dev.ctx, ms), "mg_format_stats");
+                    for (int i = 0; i < 3; ++i) format_ms[i] += ms[i];
+                    ++format_calls;
+                }
                 if (!tags) continue;
                 site_ac[w].resize(b.var_allele_off.back());
                 site_ns[w].resize(bn);
@@ -1669,14 +1706,44 @@ int call_main(const Options &o)
                 dev.check(mg_site_stats(dev.ctx, ms), "mg_site_stats");
                 site_ms[0] += ms[0];
                 ++site_calls[0];
-                if (!cnt_out) site_info(dev, bn, site_ac[w].data(), site_ns[w].data(), b.var_allele_off.data(), info_text[w], info_off[w]);
+                if (!cnt_out && !bcf_out) site_info(dev, bn, site_ac[w].data(), site_ns[w].data(), b.var_allele_off.data(), info_text[w], info_off[w]);
             }
         }
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
         std::vector<std::string> outv(outs.size() + 2); // (the last two: the merged block, the records' counts for cnt_out)
-        if (merged_out) {
+        if (merged_out && bcf_out) {
+            // BCF: one group -- whole records (l_shared, l_indiv, the shared block with INFO from the counts, the device's row), compressed
+            // here when BGZF; several -- per record the first group's shared block without INFO and every group's row, each behind its
+            // u32 length, for the paste pass to widen and join (the counts go to cnt_out as for text)
+            std::string &out = outv[outs.size()], &cnt = outv.back();
+            std::string plain;
+            std::string &rec_out = bcf_direct && bcf_bgzf ? plain : out;
+            const uint32_t n_fmt = o.verbose ? 3 : 2;
+            for (const Rec &r : recs) {
+                const int w = r.isolated ? 0 : 1;
+                const char *row = row_text[w].data() + row_off[w][r.slot];
+                const uint32_t l_indiv = (uint32_t)(row_off[w][r.slot + 1] - row_off[w][r.slot]);
+                if (merged_fixed) {
+                    const size_t at = rec_out.size();
+                    rec_out.append(bcf_direct ? 8 : 4, '\0');
+                    bcf_put_shared(rec_out, bcf_hdr, r.prefix, n_fmt, (uint32_t)(bcf_direct ? P : 0));
+                    if (bcf_direct && tags) bcf_put_info(rec_out, at + 8, bcf_hdr, site_ac[w].data() + r.allele0, r.n_alleles, site_ns[w][r.slot]);
+                    const uint32_t l_shared = (uint32_t)(rec_out.size() - at - (bcf_direct ? 8 : 4));
+                    memcpy(&rec_out[at], &l_shared, 4);
+                    if (bcf_direct) memcpy(&rec_out[at + 4], &l_indiv, 4);
+                }
+                if (!bcf_direct) bcf_put_u32(rec_out, l_indiv);
+                rec_out.append(row, l_indiv);
+                if (tags && cnt_out) {
+                    const uint32_t head[2] = {r.n_alleles, site_ns[w][r.slot]};
+                    cnt.append((const char *)head, 8);
+                    cnt.append((const char *)(site_ac[w].data() + r.allele0), 4 * (size_t)r.n_alleles);
+                }
+            }
+            if (bcf_direct && bcf_bgzf) bgzf_append(plain.data(), plain.size(), out);
+        } else if (merged_out) {
             std::string &out = outv[outs.size()], &cnt = outv.back();
             const char *fixed = o.verbose ? "\tPASS\t.\tGT:GQ:COVS" : "\tPASS\t.\tGT:GQ";
             const bool info_here = tags && !cnt_out; // (else INFO stays '.' in the block: the paste pass puts it in)
@@ -1909,9 +1976,20 @@ int call_main(const Options &o)
             if (!hdr.ok()) throw std::runtime_error(hdr.error);
             std::vector<std::string> names;
             for (const auto &sm : samples) names.push_back(sm.name);
-            merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags);
+            if (bcf_out) { // the text header with a ##contig line per reference sequence where the panel's header has none
+                const bool declared = bcf_has_contig_lines(hdr.header_lines);
+                bcf_hdr = bcf_parse_header(merged_header(hdr.header_lines, o.verbose, names, o.site_tags,
+                                                         declared ? std::vector<std::string>() : bcf_contig_lines(refs.names, refs.seqs)),
+                                           declared);
+                bcf_samples = samples.size();
+                const std::string head = bcf_hdr.file_head();
+                if (bcf_bgzf) bgzf_append(head.data(), head.size(), merged_head);
+                else merged_head = head;
+            } else
+                merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags);
         }
         bool merged_direct = false; // one group: no temporary blocks
+        std::vector<uint32_t> group_planes; // the samples of every group, in the order they ran
         size_t G = o.cohort_group ? (size_t)o.cohort_group : std::min<size_t>(samples.size(), 64);
         for (size_t s0 = 0; s0 < samples.size();) {
             size_t g = std::min(G, samples.size() - s0);
@@ -1924,6 +2002,7 @@ int call_main(const Options &o)
                 }
                 dev.check(rc, "mg_cohort_begin");
             }
+            group_planes.push_back((uint32_t)g);
             {
                 Timed t("cohort: table scans");
                 for (size_t i = 0; i < g; ++i) {
@@ -1955,10 +2034,10 @@ int call_main(const Options &o)
                 if (fwrite(header_text.data(), 1, header_text.size(), f) != header_text.size()) throw std::runtime_error("cannot write " + path);
             }
             if (!o.merged.empty()) {
-                if (s0 == 0) merged_direct = g == samples.size();
+                if (s0 == 0) bcf_direct = merged_direct = g == samples.size();
                 if (merged_direct && merged_stdout) merged.open = stdout;
                 else {
-                    const std::string path = merged_direct ? o.merged + ".part" : merged_tmp_base + ".g" + std::to_string(merged.paths.size()) + ".part";
+                    const std::string path = merged_direct ? o.merged + ".part" : merged_tmp_base + ".g" + std::to_string(merged.paths.size()) + (bcf_out ? ".bcf.part" : ".part");
                     if (merged_direct) merged.part = path;
                     else merged.paths.push_back(path);
                     merged.open = fopen(path.c_str(), "wb");
@@ -1970,7 +2049,9 @@ int call_main(const Options &o)
                     merged.cnt_open = fopen(path.c_str(), "wb");
                     if (!merged.cnt_open) throw std::runtime_error("cannot write " + path);
                 }
-                if (s0 == 0 && fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size()) throw std::runtime_error("cannot write the merged output");
+                // (BCF in several groups: the header goes in front of the pasted records, the groups' files hold records alone)
+                if (s0 == 0 && (!bcf_out || merged_direct) && fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size())
+                    throw std::runtime_error("cannot write the merged output");
             }
             {
                 Timed t("cohort: panel pass");
@@ -1988,9 +2069,11 @@ int call_main(const Options &o)
                 if (fclose(closing) != 0) throw std::runtime_error("cannot write the merged output's counts");
             }
             if (merged.open) {
+                const std::string tail = bcf_out && bcf_bgzf && merged_direct ? bgzf_eof() : std::string();
+                const bool short_write = fwrite(tail.data(), 1, tail.size(), merged.open) != tail.size();
                 FILE *closing = merged.open;
                 merged.open = nullptr;
-                if ((closing == stdout ? fflush(closing) : fclose(closing)) != 0) throw std::runtime_error("cannot write the merged output");
+                if (((closing == stdout ? fflush(closing) : fclose(closing)) != 0) || short_write) throw std::runtime_error("cannot write the merged output");
             }
             for (FILE *&f : outs) {
                 FILE *closing = f;
@@ -2003,7 +2086,93 @@ int call_main(const Options &o)
             dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
             s0 += g;
         }
-        if (!o.merged.empty() && !merged_direct) { // line i of the output = line i of every group's block, one behind the other
+        if (!o.merged.empty() && !merged_direct && bcf_out) {
+            // record i of the output = the first group's shared block (n_sample put right, INFO from the summed counts) and the groups'
+            // per-sample blocks joined field by field at the widest type a group chose (bcf_paste_rows)
+            Timed t("cohort: merged paste");
+            std::vector<FILE *> in, cnt_in;
+            struct CloseAll {
+                std::vector<FILE *> &v;
+                ~CloseAll()
+                {
+                    for (FILE *f : v) fclose(f);
+                }
+            } close_all{in}, close_cnt{cnt_in};
+            auto open_all = [](const std::vector<std::string> &paths, std::vector<FILE *> &files) {
+                for (const auto &p : paths) {
+                    FILE *f = fopen(p.c_str(), "rb");
+                    if (!f) throw std::runtime_error("cannot read " + p);
+                    files.push_back(f);
+                }
+            };
+            open_all(merged.cnt_paths, cnt_in);
+            open_all(merged.paths, in);
+            if (!merged_stdout) {
+                merged.part = o.merged + ".part";
+                merged.open = fopen(merged.part.c_str(), "wb");
+                if (!merged.open) throw std::runtime_error("cannot write " + merged.part);
+            } else
+                merged.open = stdout;
+            const std::vector<uint32_t> &planes = group_planes;
+            if (planes.size() != in.size()) throw std::runtime_error("internal: the groups of the merged output and their files disagree");
+            const char *short_file = "internal: a group's block of the merged output is short";
+            const uint32_t n_fmt = o.verbose ? 3 : 2;
+            std::vector<std::vector<unsigned char>> rows(in.size());
+            std::vector<std::pair<const unsigned char *, size_t>> row_of(in.size());
+            std::vector<uint32_t> ac, more;
+            std::string out, shared, indiv;
+            auto flush = [&]() {
+                std::string packed;
+                if (bcf_bgzf) bgzf_append(out.data(), out.size(), packed);
+                const std::string &bytes = bcf_bgzf ? packed : out;
+                if (fwrite(bytes.data(), 1, bytes.size(), merged.open) != bytes.size()) throw std::runtime_error("cannot write the merged output");
+                out.clear();
+            };
+            if (fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size()) throw std::runtime_error("cannot write the merged output");
+            for (;;) {
+                uint32_t l_shared;
+                if (fread(&l_shared, 4, 1, in[0]) != 1) break;
+                if (l_shared < 24) throw std::runtime_error(short_file);
+                shared.resize(l_shared);
+                if (fread(&shared[0], 1, l_shared, in[0]) != l_shared) throw std::runtime_error(short_file);
+                for (size_t gi = 0; gi < in.size(); ++gi) {
+                    uint32_t l_row;
+                    if (fread(&l_row, 4, 1, in[gi]) != 1) throw std::runtime_error(short_file);
+                    rows[gi].resize(l_row);
+                    if (l_row && fread(rows[gi].data(), 1, l_row, in[gi]) != l_row) throw std::runtime_error(short_file);
+                    row_of[gi] = {rows[gi].data(), l_row};
+                }
+                const uint32_t nfs = n_fmt << 24 | (uint32_t)bcf_samples;
+                memcpy(&shared[20], &nfs, 4);
+                if (o.site_tags) {
+                    uint32_t head[2] = {0, 0}, next[2];
+                    for (size_t gi = 0; gi < cnt_in.size(); ++gi) {
+                        if (fread(next, 4, 2, cnt_in[gi]) != 2 || (gi && next[0] != head[0])) throw std::runtime_error("internal: a group's counts for the merged output are short");
+                        const size_t A = next[0];
+                        more.resize(A);
+                        if (A && fread(more.data(), 4, A, cnt_in[gi]) != A) throw std::runtime_error("internal: a group's counts for the merged output are short");
+                        if (!gi) ac.assign(A, 0u);
+                        for (size_t a = 0; a < A; ++a) ac[a] += more[a];
+                        head[0] = next[0];
+                        head[1] += next[1];
+                    }
+                    bcf_put_info(shared, 0, bcf_hdr, ac.data(), head[0], head[1]);
+                }
+                indiv.clear();
+                bcf_paste_rows(row_of, planes, n_fmt, indiv);
+                bcf_put_u32(out, (uint32_t)shared.size());
+                bcf_put_u32(out, (uint32_t)indiv.size());
+                out += shared;
+                out += indiv;
+                if (out.size() >= (1u << 20)) flush();
+            }
+            flush();
+            const std::string tail = bcf_bgzf ? bgzf_eof() : std::string();
+            const bool short_write = fwrite(tail.data(), 1, tail.size(), merged.open) != tail.size();
+            FILE *closing = merged.open;
+            merged.open = nullptr;
+            if (((closing == stdout ? fflush(closing) : fclose(closing)) != 0) || short_write) throw std::runtime_error("cannot write the merged output");
+        } else if (!o.merged.empty() && !merged_direct) { // line i of the output = line i of every group's block, one behind the other
             Timed t("cohort: merged paste");
             std::vector<FILE *> in, cnt_in;
             struct CloseAll {
@@ -2107,6 +2276,12 @@ int call_main(const Options &o)
         if (!o.merged.empty() && !merged_stdout) {
             if (rename(merged.part.c_str(), o.merged.c_str()) != 0) throw std::runtime_error("cannot write " + o.merged);
             merged.part.clear();
+        }
+        if (bcf_calls && g_timers.on) {
+            g_timers.add("merged: encode kernels (device)", (bcf_ms[0] + bcf_ms[1] + bcf_ms[2]) / 1000.0);
+            fprintf(stderr, "[malva-geno] merged: %zu mg_encode_calls_bcf, device ms per call: length %.3f scan %.3f write %.3f\n", bcf_calls, bcf_ms[0] / bcf_calls,
+                    bcf_ms[1] / bcf_calls, bcf_ms[2] / bcf_calls);
+            if (site_calls[0]) fprintf(stderr, "[malva-geno] merged: %zu mg_site_counts, device ms per call: count %.3f\n", site_calls[0], site_ms[0] / site_calls[0]);
         }
         if (format_calls) {
             if (g_timers.on) g_timers.add("merged: format kernels (device)", (format_ms[0] + format_ms[1] + format_ms[2]) / 1000.0);

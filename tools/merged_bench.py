@@ -6,6 +6,8 @@ Timed, each the median of --repeats runs with their spread:
     merged       `--cohort --merged PATH`     the same two, and the device milliseconds per mg_format_calls (mg_format_stats)
     merged_tags  the same with `--min-gq Q --site-tags` (Q: --min-gq, default 20): the same, and the device milliseconds per
                  mg_site_counts and per mg_format_site_info (mg_site_stats) beside them
+    merged_bcf   `--cohort --merged PATH --merged-format bcf`, merged_ubcf the same with ubcf: the same two, the bytes written, and
+                 the device milliseconds per mg_encode_calls_bcf (mg_bcf_stats) -- on the batches the merged leg formats as text
     parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick
 The runs alternate (parent, per_sample, merged, parent, ...), so that whatever else the host is doing falls on all three alike.
 merged_equals_paste: the merged file is the column paste of the per-sample files.
@@ -94,12 +96,15 @@ def main():
         subprocess.run([BIN, "index"] + common + [os.path.join(td, "sample")], check=True, capture_output=True, timeout=600)
         env = dict(os.environ, MALVA_GENO_TIMERS="1")
         legs = {"per_sample": (BIN, ["-o", os.path.join(td, "out")]), "merged": (BIN, ["--merged", os.path.join(td, "merged.vcf")]),
-                "merged_tags": (BIN, ["--merged", os.path.join(td, "merged_tags.vcf"), "--min-gq", str(a.min_gq), "--site-tags"])}
+                "merged_tags": (BIN, ["--merged", os.path.join(td, "merged_tags.vcf"), "--min-gq", str(a.min_gq), "--site-tags"]),
+                "merged_bcf": (BIN, ["--merged", os.path.join(td, "merged.bcf"), "--merged-format", "bcf"]),
+                "merged_ubcf": (BIN, ["--merged", os.path.join(td, "merged.ubcf"), "--merged-format", "ubcf"])}
         if a.parent_bin:
             legs = dict({"parent": (a.parent_bin, ["-o", os.path.join(td, "out_parent")])}, **legs)
         res = {leg: {"wall_s": [], "panel_pass_s": []} for leg in legs}
         fmt_ms, fmt_calls = {"merged": [], "merged_tags": []}, 0
         site_ms, site_calls = [], [0, 0]
+        bcf_ms, bcf_calls = {"merged_bcf": [], "merged_ubcf": []}, 0
 
         def run(leg):
             b, dest = legs[leg]
@@ -119,6 +124,10 @@ def main():
                     m = re.search(r"merged: (\d+) mg_format_calls, device ms per call: length ([0-9.]+) scan ([0-9.]+) write ([0-9.]+)", err)
                     fmt_calls = int(m.group(1))
                     fmt_ms[leg].append([float(m.group(i)) for i in (2, 3, 4)])
+                if leg in bcf_ms:
+                    m = re.search(r"merged: (\d+) mg_encode_calls_bcf, device ms per call: length ([0-9.]+) scan ([0-9.]+) write ([0-9.]+)", err)
+                    bcf_calls = int(m.group(1))
+                    bcf_ms[leg].append([float(m.group(i)) for i in (2, 3, 4)])
                 if leg == "merged_tags":
                     m = re.search(r"merged: (\d+) mg_site_counts, (\d+) mg_format_site_info, device ms per call: count ([0-9.]+) info ([0-9.]+)", err)
                     site_calls = [int(m.group(1)), int(m.group(2))]
@@ -135,6 +144,11 @@ def main():
         out["tags_format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms["merged_tags"]]) for i, name in enumerate(("length", "scan", "write"))}
         out["site_calls_per_run"] = {"count": site_calls[0], "info": site_calls[1]}
         out["site_ms_per_call"] = {name: stat([x[i] for x in site_ms]) for i, name in enumerate(("count", "info"))}
+        out["encode_calls_per_run"] = bcf_calls
+        for leg in bcf_ms:
+            out[leg + "_encode_ms_per_call"] = {name: stat([x[i] for x in bcf_ms[leg]]) for i, name in enumerate(("length", "scan", "write"))}
+        out["merged_bcf_bytes"] = os.path.getsize(os.path.join(td, "merged.bcf"))
+        out["merged_ubcf_bytes"] = os.path.getsize(os.path.join(td, "merged.ubcf"))
         out["merged_tags_bytes"] = os.path.getsize(os.path.join(td, "merged_tags.vcf"))
         out["merged_bytes"] = os.path.getsize(os.path.join(td, "merged.vcf"))
         out["per_sample_bytes"] = sum(os.path.getsize(os.path.join(td, "out", "s%02d.vcf" % i)) for i in range(S))
