@@ -77,6 +77,18 @@ struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
 };
+// What one encoder of a merged batch's rows keeps between its passes and for its stats call (encode_rows)
+struct RowPass {
+    Scratch len, meta;                                       // the rows' lengths (u32); the meta block: the total, "a row beyond 32 bits"
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
+    bool valid = false;                                      // ev[] are those of a call that ran
+};
+// Device copies of the host forms' arguments and results (mg_format_calls*, mg_site_counts, mg_format_site_info, mg_encode_calls_bcf).  One
+// set serves them all: every host form runs on the context's stream and synchronises before it returns, so none outlives its call, and
+// no device form touches it (those own a RowPass, s_bcf_types and s_scan, and read and write the caller's buffers).
+struct RowStage {
+    Scratch gt1, gt2, gq, cov, var_allele_off, ac, ns, out, row_off;
+};
 
 struct mg_ctx {
     int device = 0;
@@ -141,19 +153,12 @@ struct mg_ctx {
     u32 *coh_sv_counts = nullptr, *coh_sv_vals = nullptr;
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
     hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
-    // mg_format_calls*: row lengths, the meta block (total, "a row beyond 32 bits"), and the host form's staging (gt1, gt2, gq, cov, var_allele_off, text, row_off)
-    Scratch s_fmt[9];
-    hipEvent_t ev_f[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
-    bool fmt_stats_valid = false;
-    // mg_site_counts* / mg_format_site_info*: the host forms' staging (gt1, gt2, gq, var_allele_off, ac, ns, text, row_off), the row lengths
-    // and the meta block; events: start and end of the latest count call, then of the latest info-format call
-    Scratch s_site[10];
-    hipEvent_t ev_s[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool site_stats_valid[2] = {false, false};
-    // mg_encode_calls_bcf*: row lengths, the meta block, the records' type codes, and the host form's staging (gt1, gt2, gq, cov, var_allele_off, out, row_off)
-    Scratch s_bcf[10];
-    hipEvent_t ev_bcf[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
-    bool bcf_stats_valid = false;
+    // the rows of a merged batch (encode_rows): one pass state per encoder, since each stats call reports its own encoder's latest call
+    RowPass rp_fmt, rp_info, rp_bcf;                  // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*
+    Scratch s_bcf_types;                              // mg_encode_calls_bcf*: the records' type codes, from its length pass to its write pass
+    hipEvent_t ev_cnt[2] = {nullptr, nullptr};        // mg_site_counts*: start and end of the latest call
+    bool cnt_stats_valid = false;
+    RowStage stage;
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -689,15 +694,14 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     hipFree(c->coh_sv_vals);
     for (auto &e : c->ev_c)
         if (e) hipEventDestroy(e);
-    for (auto &e : c->ev_f)
+    for (RowPass *rp : {&c->rp_fmt, &c->rp_info, &c->rp_bcf})
+        for (hipEvent_t e : rp->ev)
+            if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_cnt)
         if (e) hipEventDestroy(e);
-    for (auto &q : c->s_fmt) hipFree(q.p);
-    for (auto &e : c->ev_s)
-        if (e) hipEventDestroy(e);
-    for (auto &q : c->s_site) hipFree(q.p);
-    for (auto &e : c->ev_bcf)
-        if (e) hipEventDestroy(e);
-    for (auto &q : c->s_bcf) hipFree(q.p);
+    for (Scratch *q : {&c->rp_fmt.len, &c->rp_fmt.meta, &c->rp_info.len, &c->rp_info.meta, &c->rp_bcf.len, &c->rp_bcf.meta, &c->s_bcf_types, &c->stage.gt1, &c->stage.gt2,
+                       &c->stage.gq, &c->stage.cov, &c->stage.var_allele_off, &c->stage.ac, &c->stage.ns, &c->stage.out, &c->stage.row_off})
+        hipFree(q->p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3040,9 +3044,26 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
     return MG_OK;
 }
 
-// ---- the sample columns of a batch as text (call_text_kernels.h) --------------------------------------------------------------
+// ---- the rows of a merged batch: the sample columns as text (call_text_kernels.h), the site tags (site_tags_kernels.h), the sample columns
+// ---- as BCF (bcf_kernels.h) ---------------------------------------------------------------------------------------------------------
 namespace {
-// row lengths -> row_off[n + 1] (u64) and, in meta[0], the total (~0 when meta[1] is set): what the text passes share
+// The argument checks that a host form and its device form share (host pointers there, device pointers here): of whoever reads a batch's
+// cells (gq where reads_gq, cov with var_allele_off or neither), and of where an encoder's rows go
+int check_cells(mg_ctx *c, const char *who, size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, bool reads_gq,
+                const void *cov, const void *var_allele_off)
+{
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "%s: n_planes is 1..64", who);
+    if ((cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
+    if (n_vars && (!gt1 || (!haploid && !gt2) || (reads_gq && !gq))) return fail(c, MG_ERR_ARG, "NULL argument");
+    return MG_OK;
+}
+int check_rows_out(mg_ctx *c, const void *out, size_t cap, const void *row_off, const uint64_t *bytes_out)
+{
+    if (!row_off || !bytes_out || (!out && cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    return MG_OK;
+}
+
+// row lengths -> row_off[n + 1] (u64) and, in meta[0], the total (~0 when meta[1] is set)
 void fmt_scan(mg_ctx *c, const void *d_len, u64 n, u64 n_part, void *part, void *d_row_off, unsigned long long *meta)
 {
     hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, n, (unsigned long long *)part);
@@ -3050,53 +3071,113 @@ void fmt_scan(mg_ctx *c, const void *d_len, u64 n, u64 n_part, void *part, void 
     hipLaunchKernelGGL(fmt_rescan_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_len, n, (const unsigned long long *)part,
                        (unsigned long long *)d_row_off, meta);
 }
+inline dim3 fmt_len_grid(u64 n) { return dim3((unsigned)((n + FMT_TPB / 64 - 1) / (FMT_TPB / 64))); } // a wave per record
+inline dim3 fmt_write_grid(u64 n) { return dim3((unsigned)((n + FMT_ROWS - 1) / FMT_ROWS)); }         // FMT_ROWS records per workgroup
+
+// The device forms of the three encoders (mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*) differ in their two kernels alone:
+// a length pass, the scan of the lengths into d_row_off[n_rows + 1], a write pass into d_out[cap], the four events of the stats call between
+// them.  launch_len(len, meta) and launch_write(row_off) launch the encoder's kernel of that pass (launch_len may take scratch first, hence
+// its return code).  More than cap bytes: MG_ERR_LIMIT with *bytes_out set, row_off whole, nothing written at or behind cap.
+template <class LaunchLen, class LaunchWrite>
+int encode_rows(mg_ctx *c, RowPass &rp, const char *who, size_t n_rows, void *d_out, size_t cap, void *d_row_off, uint64_t *bytes_out, LaunchLen launch_len,
+                LaunchWrite launch_write)
+{
+    TRY(check_rows_out(c, d_out, cap, d_row_off, bytes_out));
+    if (n_rows >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "%s: more than 2^32 - 1 records in one call", who);
+    for (auto &e : rp.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    rp.valid = false;
+    *bytes_out = 0;
+    HIP_TRY(c, hipEventRecord(rp.ev[0], c->stream));
+    if (n_rows == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_row_off, 0, 8, c->stream));
+        for (int i = 1; i < 4; ++i) HIP_TRY(c, hipEventRecord(rp.ev[i], c->stream));
+        rp.valid = true;
+        return MG_OK;
+    }
+    void *d_len, *d_meta, *part;
+    TRY(scratch(c, rp.len, 4 * n_rows, &d_len));
+    TRY(scratch(c, rp.meta, 16, &d_meta));
+    const u64 n_part = (n_rows + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    unsigned long long *meta = (unsigned long long *)d_meta;
+    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
+    TRY(launch_len((u32 *)d_len, meta));
+    HIP_TRY(c, hipEventRecord(rp.ev[1], c->stream));
+    fmt_scan(c, d_len, (u64)n_rows, n_part, part, d_row_off, meta);
+    HIP_TRY(c, hipEventRecord(rp.ev[2], c->stream));
+    launch_write((const unsigned long long *)d_row_off);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(rp.ev[3], c->stream));
+    rp.valid = true;
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "%s: a row of 4 GB or more", who);
+    *bytes_out = total;
+    if (total > cap) return fail(c, MG_ERR_LIMIT, "%s: the rows need %llu bytes, the buffer holds %llu", who, total, (unsigned long long)cap);
+    return MG_OK;
+}
+
+// device milliseconds of an encoder's most recent call (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
+int rows_stats(mg_ctx *c, RowPass &rp, const char *who, float *ms_out)
+{
+    if (!rp.valid) return fail(c, MG_ERR_STATE, "no %s yet", who);
+    HIP_TRY(c, hipEventSynchronize(rp.ev[3]));
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], rp.ev[i], rp.ev[i + 1]));
+    return MG_OK;
+}
+
+// the host forms' way in: a batch's cells go up (gt1, gt2 unless haploid, gq, cov and var_allele_off where given), the rows get a place
+struct DevCells {
+    void *gt1 = nullptr, *gt2 = nullptr, *gq = nullptr, *cov = nullptr, *var_allele_off = nullptr;
+};
+int stage_cells(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, const uint32_t *cov,
+                const uint32_t *var_allele_off, DevCells *d)
+{
+    RowStage &s = c->stage;
+    const size_t cells = 4 * (size_t)n_planes * n_vars;
+    TRY(upload(c, s.gt1, gt1, cells, &d->gt1));
+    if (!haploid) TRY(upload(c, s.gt2, gt2, cells, &d->gt2));
+    if (gq) TRY(upload(c, s.gq, gq, cells, &d->gq));
+    if (cov) TRY(upload(c, s.cov, cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d->cov));
+    if (var_allele_off) TRY(upload(c, s.var_allele_off, var_allele_off, 4 * (n_vars + 1), &d->var_allele_off));
+    return MG_OK;
+}
+int stage_rows(mg_ctx *c, size_t n_rows, size_t cap, void **d_out, void **d_row_off)
+{
+    TRY(scratch(c, c->stage.out, cap ? cap : 1, d_out));
+    return scratch(c, c->stage.row_off, 8 * (n_rows + 1), d_row_off);
+}
+// the host forms' way out, behind the device form that returned rc: row_off and the rows come down (rows that do not fit, MG_ERR_LIMIT with
+// *bytes_out set: row_off and the first cap bytes are still the caller's)
+int fetch_rows(mg_ctx *c, int rc, size_t n_rows, const void *d_out, const void *d_row_off, void *out, size_t cap, uint64_t *row_off_out, const uint64_t *bytes_out)
+{
+    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *bytes_out)) return rc;
+    const size_t have = std::min<uint64_t>(*bytes_out, cap);
+    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_row_off, 8 * (n_rows + 1), hipMemcpyDeviceToHost, c->stream));
+    if (have) HIP_TRY(c, hipMemcpyAsync(out, d_out, have, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
 
 int format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int masked, int32_t min_gq,
                         const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_format_calls: n_planes is 1..64");
-    if (!d_row_off_out || !text_bytes_out || (!d_text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if ((d_cov != nullptr) != (d_var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_format_calls: cov and var_allele_off go together");
-    if (n_vars && (!d_gt1 || !d_gq || (!haploid && !d_gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_format_calls: more than 2^32 - 1 records in one call");
-    for (auto &e : c->ev_f)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->fmt_stats_valid = false;
-    *text_bytes_out = 0;
-    HIP_TRY(c, hipEventRecord(c->ev_f[0], c->stream));
-    if (n_vars == 0) {
-        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
-        for (int i = 1; i < 4; ++i) HIP_TRY(c, hipEventRecord(c->ev_f[i], c->stream));
-        c->fmt_stats_valid = true;
-        return MG_OK;
-    }
-    void *d_len, *d_meta, *part;
-    TRY(scratch(c, c->s_fmt[0], 4 * n_vars, &d_len));
-    TRY(scratch(c, c->s_fmt[1], 16, &d_meta));
-    const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off));
     const FmtArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
                     masked, min_gq};
-    unsigned long long *meta = (unsigned long long *)d_meta;
-    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
-    hipLaunchKernelGGL(fmt_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len, meta);
-    HIP_TRY(c, hipEventRecord(c->ev_f[1], c->stream));
-    fmt_scan(c, d_len, (u64)n_vars, n_part, part, d_row_off_out, meta);
-    HIP_TRY(c, hipEventRecord(c->ev_f[2], c->stream));
-    hipLaunchKernelGGL(fmt_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a,
-                       (const unsigned long long *)d_row_off_out, (char *)d_text_out, (u64)text_cap);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_f[3], c->stream));
-    c->fmt_stats_valid = true;
-    unsigned long long total = 0;
-    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "mg_format_calls: a row of 4 GB or more");
-    *text_bytes_out = total;
-    if (total > text_cap) return fail(c, MG_ERR_LIMIT, "mg_format_calls: the text needs %llu bytes, text_cap is %llu", total, (unsigned long long)text_cap);
-    return MG_OK;
+    return encode_rows(
+        c, c->rp_fmt, "mg_format_calls", n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
+        [&](u32 *len, unsigned long long *meta) -> int {
+            hipLaunchKernelGGL(fmt_len_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
+            return MG_OK;
+        },
+        [&](const unsigned long long *row_off) {
+            hipLaunchKernelGGL(fmt_write_kernel, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off, (char *)d_text_out, (u64)text_cap);
+        });
 }
 
 int format_calls_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int masked, int32_t min_gq,
@@ -3104,28 +3185,14 @@ int format_calls_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, 
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_format_calls: n_planes is 1..64");
-    if (!row_off_out || !text_bytes_out || (!text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if ((cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_format_calls: cov and var_allele_off go together");
-    if (n_vars && (!gt1 || !gq || (!haploid && !gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
-    const size_t cells = 4 * (size_t)n_planes * n_vars;
-    void *d_g1, *d_g2 = nullptr, *d_gq, *d_cov = nullptr, *d_vao = nullptr, *d_text, *d_off;
-    TRY(upload(c, c->s_fmt[2], gt1, cells, &d_g1));
-    if (!haploid) TRY(upload(c, c->s_fmt[3], gt2, cells, &d_g2));
-    TRY(upload(c, c->s_fmt[4], gq, cells, &d_gq));
-    if (cov) {
-        TRY(upload(c, c->s_fmt[5], cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d_cov));
-        TRY(upload(c, c->s_fmt[6], var_allele_off, 4 * (n_vars + 1), &d_vao));
-    }
-    TRY(scratch(c, c->s_fmt[7], text_cap ? text_cap : 1, &d_text));
-    TRY(scratch(c, c->s_fmt[8], 8 * (n_vars + 1), &d_off));
-    const int rc = format_calls_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, masked, min_gq, d_cov, d_vao, d_text, text_cap, d_off, text_bytes_out);
-    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *text_bytes_out)) return rc; // (a text that does not fit: row_off and the first text_cap bytes are still the caller's)
-    const size_t have = std::min<uint64_t>(*text_bytes_out, text_cap);
-    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
-    if (have) HIP_TRY(c, hipMemcpyAsync(text_out, d_text, have, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return rc;
+    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off));
+    TRY(check_rows_out(c, text_out, text_cap, row_off_out, text_bytes_out));
+    DevCells d;
+    void *d_text, *d_off;
+    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d));
+    TRY(stage_rows(c, n_vars, text_cap, &d_text, &d_off));
+    const int rc = format_calls_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, masked, min_gq, d.cov, d.var_allele_off, d_text, text_cap, d_off, text_bytes_out);
+    return fetch_rows(c, rc, n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
 }
 } // namespace
 MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
@@ -3154,37 +3221,33 @@ MG_EXPORT int mg_format_calls_masked(mg_ctx *c, size_t n_vars, uint32_t n_planes
     return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, 1, min_gq, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out);
 }
 
-// device milliseconds of the most recent mg_format_calls* (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
+// device milliseconds of the most recent mg_format_calls* (rows_stats)
 MG_EXPORT int mg_format_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    if (!c->fmt_stats_valid) return fail(c, MG_ERR_STATE, "no mg_format_calls yet");
-    HIP_TRY(c, hipEventSynchronize(c->ev_f[3]));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_f[i], c->ev_f[i + 1]));
-    return MG_OK;
+    return rows_stats(c, c->rp_fmt, "mg_format_calls", ms_out);
 }
 
-// ---- the site tags of a merged batch (site_tags_kernels.h) ---------------------------------------------------------------------
 MG_EXPORT int mg_site_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                     int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_ac, void *d_ns)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_site_counts: n_planes is 1..64");
-    if (n_vars && (!d_var_allele_off || !d_gt1 || (!haploid && !d_gt2) || (use_mask && !d_gq) || !d_ns)) return fail(c, MG_ERR_ARG, "NULL argument"); // (d_ac may be: records without slots)
+    TRY(check_cells(c, "mg_site_counts", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, nullptr, nullptr));
+    if (n_vars && (!d_var_allele_off || !d_ns)) return fail(c, MG_ERR_ARG, "NULL argument"); // (d_ac may be: records without slots)
     if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_site_counts: more than 2^32 - 1 records in one call");
-    for (int i = 0; i < 2; ++i)
-        if (!c->ev_s[i]) HIP_TRY(c, hipEventCreate(&c->ev_s[i]));
-    c->site_stats_valid[0] = false;
-    HIP_TRY(c, hipEventRecord(c->ev_s[0], c->stream));
+    for (auto &e : c->ev_cnt)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->cnt_stats_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev_cnt[0], c->stream));
     if (n_vars) {
         const SiteArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u32 *)d_var_allele_off, accumulate};
-        hipLaunchKernelGGL(site_count_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_ac, (u32 *)d_ns);
+        hipLaunchKernelGGL(site_count_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_ac, (u32 *)d_ns);
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipEventRecord(c->ev_s[1], c->stream));
-    c->site_stats_valid[0] = true;
+    HIP_TRY(c, hipEventRecord(c->ev_cnt[1], c->stream));
+    c->cnt_stats_valid = true;
     return MG_OK;
 }
 
@@ -3193,21 +3256,18 @@ MG_EXPORT int mg_site_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int ha
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_site_counts: n_planes is 1..64");
+    TRY(check_cells(c, "mg_site_counts", n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, nullptr, nullptr));
     if (n_vars && !var_allele_off) return fail(c, MG_ERR_ARG, "NULL argument");
     const size_t slots = n_vars ? var_allele_off[n_vars] : 0;
-    if (n_vars && (!gt1 || (!haploid && !gt2) || (use_mask && !gq) || !ns || (slots && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
-    const size_t cells = 4 * (size_t)n_planes * n_vars;
-    void *d_g1, *d_g2 = nullptr, *d_gq = nullptr, *d_vao, *d_ac, *d_ns;
-    TRY(upload(c, c->s_site[0], gt1, cells, &d_g1));
-    if (!haploid) TRY(upload(c, c->s_site[1], gt2, cells, &d_g2));
-    if (use_mask) TRY(upload(c, c->s_site[2], gq, cells, &d_gq));
-    TRY(upload(c, c->s_site[3], var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
-    TRY(scratch(c, c->s_site[4], slots ? 4 * slots : 1, &d_ac));
-    TRY(scratch(c, c->s_site[5], n_vars ? 4 * n_vars : 1, &d_ns));
+    if (n_vars && (!ns || (slots && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
+    DevCells d;
+    void *d_ac, *d_ns;
+    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, use_mask ? gq : nullptr, nullptr, n_vars ? var_allele_off : nullptr, &d));
+    TRY(scratch(c, c->stage.ac, slots ? 4 * slots : 1, &d_ac));
+    TRY(scratch(c, c->stage.ns, n_vars ? 4 * n_vars : 1, &d_ns));
     if (accumulate && slots) HIP_TRY(c, hipMemcpyAsync(d_ac, ac, 4 * slots, hipMemcpyHostToDevice, c->stream));
     if (accumulate && n_vars) HIP_TRY(c, hipMemcpyAsync(d_ns, ns, 4 * n_vars, hipMemcpyHostToDevice, c->stream));
-    TRY(mg_site_counts_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, use_mask, min_gq, d_vao, accumulate, d_ac, d_ns));
+    TRY(mg_site_counts_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, use_mask, min_gq, d.var_allele_off, accumulate, d_ac, d_ns));
     if (slots) HIP_TRY(c, hipMemcpyAsync(ac, d_ac, 4 * slots, hipMemcpyDeviceToHost, c->stream));
     if (n_vars) HIP_TRY(c, hipMemcpyAsync(ns, d_ns, 4 * n_vars, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3219,42 +3279,17 @@ MG_EXPORT int mg_format_site_info_device(mg_ctx *c, size_t n_vars, const void *d
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    if (!d_row_off_out || !text_bytes_out || (!d_text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
     if (n_vars && (!d_ns || !d_var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_format_site_info: more than 2^32 - 1 records in one call");
-    for (int i = 2; i < 4; ++i)
-        if (!c->ev_s[i]) HIP_TRY(c, hipEventCreate(&c->ev_s[i]));
-    c->site_stats_valid[1] = false;
-    *text_bytes_out = 0;
-    HIP_TRY(c, hipEventRecord(c->ev_s[2], c->stream));
-    if (n_vars == 0) {
-        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_s[3], c->stream));
-        c->site_stats_valid[1] = true;
-        return MG_OK;
-    }
-    void *d_len, *d_meta, *part;
-    TRY(scratch(c, c->s_site[8], 4 * n_vars, &d_len));
-    TRY(scratch(c, c->s_site[9], 16, &d_meta));
-    const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
     const InfoArgs a{(u64)n_vars, (const u32 *)d_ac, (const u32 *)d_ns, (const u32 *)d_var_allele_off};
-    unsigned long long *meta = (unsigned long long *)d_meta;
-    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
-    hipLaunchKernelGGL(info_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len, meta);
-    fmt_scan(c, d_len, (u64)n_vars, n_part, part, d_row_off_out, meta);
-    hipLaunchKernelGGL(info_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a,
-                       (const unsigned long long *)d_row_off_out, (char *)d_text_out, (u64)text_cap);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_s[3], c->stream));
-    c->site_stats_valid[1] = true;
-    unsigned long long total = 0;
-    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "mg_format_site_info: a row of 4 GB or more");
-    *text_bytes_out = total;
-    if (total > text_cap) return fail(c, MG_ERR_LIMIT, "mg_format_site_info: the text needs %llu bytes, text_cap is %llu", total, (unsigned long long)text_cap);
-    return MG_OK;
+    return encode_rows(
+        c, c->rp_info, "mg_format_site_info", n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
+        [&](u32 *len, unsigned long long *meta) -> int {
+            hipLaunchKernelGGL(info_len_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
+            return MG_OK;
+        },
+        [&](const unsigned long long *row_off) {
+            hipLaunchKernelGGL(info_write_kernel, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off, (char *)d_text_out, (u64)text_cap);
+        });
 }
 
 MG_EXPORT int mg_format_site_info(mg_ctx *c, size_t n_vars, const uint32_t *ac, const uint32_t *ns, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
@@ -3262,21 +3297,15 @@ MG_EXPORT int mg_format_site_info(mg_ctx *c, size_t n_vars, const uint32_t *ac, 
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    if (!row_off_out || !text_bytes_out || (!text_out && text_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    TRY(check_rows_out(c, text_out, text_cap, row_off_out, text_bytes_out));
     if (n_vars && (!ns || !var_allele_off || (var_allele_off[n_vars] && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
     void *d_ac, *d_ns, *d_vao, *d_text, *d_off;
-    TRY(upload(c, c->s_site[4], ac, n_vars ? 4 * (size_t)var_allele_off[n_vars] : 0, &d_ac));
-    TRY(upload(c, c->s_site[5], ns, 4 * n_vars, &d_ns));
-    TRY(upload(c, c->s_site[3], var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
-    TRY(scratch(c, c->s_site[6], text_cap ? text_cap : 1, &d_text));
-    TRY(scratch(c, c->s_site[7], 8 * (n_vars + 1), &d_off));
+    TRY(upload(c, c->stage.ac, ac, n_vars ? 4 * (size_t)var_allele_off[n_vars] : 0, &d_ac));
+    TRY(upload(c, c->stage.ns, ns, 4 * n_vars, &d_ns));
+    TRY(upload(c, c->stage.var_allele_off, var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
+    TRY(stage_rows(c, n_vars, text_cap, &d_text, &d_off));
     const int rc = mg_format_site_info_device(c, n_vars, d_ac, d_ns, d_vao, d_text, text_cap, d_off, text_bytes_out);
-    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *text_bytes_out)) return rc; // (as mg_format_calls: row_off and the first text_cap bytes are still the caller's)
-    const size_t have = std::min<uint64_t>(*text_bytes_out, text_cap);
-    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
-    if (have) HIP_TRY(c, hipMemcpyAsync(text_out, d_text, have, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return rc;
+    return fetch_rows(c, rc, n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
 }
 
 // device milliseconds (waits for them): ms_out[0] the most recent mg_site_counts*, [1] the most recent mg_format_site_info* (its three passes together); 0 where there was none
@@ -3284,67 +3313,39 @@ MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    if (!c->site_stats_valid[0] && !c->site_stats_valid[1]) return fail(c, MG_ERR_STATE, "no mg_site_counts or mg_format_site_info yet");
-    for (int i = 0; i < 2; ++i) {
-        ms_out[i] = 0.f; // (none of that kind yet)
-        if (!c->site_stats_valid[i]) continue;
-        HIP_TRY(c, hipEventSynchronize(c->ev_s[2 * i + 1]));
-        HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_s[2 * i], c->ev_s[2 * i + 1]));
+    if (!c->cnt_stats_valid && !c->rp_info.valid) return fail(c, MG_ERR_STATE, "no mg_site_counts or mg_format_site_info yet");
+    float info[3] = {0.f, 0.f, 0.f}; // (0: none of that kind yet)
+    ms_out[0] = 0.f;
+    if (c->cnt_stats_valid) {
+        HIP_TRY(c, hipEventSynchronize(c->ev_cnt[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms_out[0], c->ev_cnt[0], c->ev_cnt[1]));
     }
+    if (c->rp_info.valid) TRY(rows_stats(c, c->rp_info, "mg_format_site_info", info));
+    ms_out[1] = info[0] + info[1] + info[2];
     return MG_OK;
 }
 
-// ---- the sample columns of a batch as BCF (bcf_kernels.h) -----------------------------------------------------------------------
 MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                          int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
                                          size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: n_planes is 1..64");
-    if (!d_row_off_out || !bytes_out || (!d_out && out_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if ((d_cov != nullptr) != (d_var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: cov and var_allele_off go together");
+    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off));
     if (key_gt < 0 || key_gq < 0 || (d_cov && key_cov < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
-    if (n_vars && (!d_gt1 || !d_gq || (!haploid && !d_gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_encode_calls_bcf: more than 2^32 - 1 records in one call");
-    for (auto &e : c->ev_bcf)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->bcf_stats_valid = false;
-    *bytes_out = 0;
-    HIP_TRY(c, hipEventRecord(c->ev_bcf[0], c->stream));
-    if (n_vars == 0) {
-        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
-        for (int i = 1; i < 4; ++i) HIP_TRY(c, hipEventRecord(c->ev_bcf[i], c->stream));
-        c->bcf_stats_valid = true;
-        return MG_OK;
-    }
-    void *d_len, *d_meta, *d_types, *part;
-    TRY(scratch(c, c->s_bcf[0], 4 * n_vars, &d_len));
-    TRY(scratch(c, c->s_bcf[1], 16, &d_meta));
-    TRY(scratch(c, c->s_bcf[2], 3 * n_vars, &d_types));
-    const u64 n_part = (n_vars + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
     const BcfArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
                     use_mask, min_gq, key_gt, key_gq, key_cov};
-    unsigned long long *meta = (unsigned long long *)d_meta;
-    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
-    hipLaunchKernelGGL(bcf_len_kernel, dim3((unsigned)((n_vars + FMT_TPB / 64 - 1) / (FMT_TPB / 64))), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_len,
-                       (unsigned char *)d_types, meta);
-    HIP_TRY(c, hipEventRecord(c->ev_bcf[1], c->stream));
-    fmt_scan(c, d_len, (u64)n_vars, n_part, part, d_row_off_out, meta);
-    HIP_TRY(c, hipEventRecord(c->ev_bcf[2], c->stream));
-    hipLaunchKernelGGL(bcf_write_kernel, dim3((unsigned)((n_vars + FMT_ROWS - 1) / FMT_ROWS)), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types,
-                       (const unsigned long long *)d_row_off_out, (char *)d_out, (u64)out_cap);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_bcf[3], c->stream));
-    c->bcf_stats_valid = true;
-    unsigned long long total = 0;
-    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (total == ~0ull) return fail(c, MG_ERR_LIMIT, "mg_encode_calls_bcf: a row of 4 GB or more");
-    *bytes_out = total;
-    if (total > out_cap) return fail(c, MG_ERR_LIMIT, "mg_encode_calls_bcf: the rows need %llu bytes, out_cap is %llu", total, (unsigned long long)out_cap);
-    return MG_OK;
+    void *d_types = nullptr; // the records' type codes: what the length pass found, for the write pass
+    return encode_rows(
+        c, c->rp_bcf, "mg_encode_calls_bcf", n_vars, d_out, out_cap, d_row_off_out, bytes_out,
+        [&](u32 *len, unsigned long long *meta) -> int {
+            TRY(scratch(c, c->s_bcf_types, 3 * n_vars, &d_types));
+            hipLaunchKernelGGL(bcf_len_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types, meta);
+            return MG_OK;
+        },
+        [&](const unsigned long long *row_off) {
+            hipLaunchKernelGGL(bcf_write_kernel, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types, row_off, (char *)d_out, (u64)out_cap);
+        });
 }
 
 MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -3353,40 +3354,23 @@ MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, i
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: n_planes is 1..64");
-    if (!row_off_out || !bytes_out || (!out && out_cap)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if ((cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: cov and var_allele_off go together");
-    if (n_vars && (!gt1 || !gq || (!haploid && !gt2))) return fail(c, MG_ERR_ARG, "NULL argument");
-    const size_t cells = 4 * (size_t)n_planes * n_vars;
-    void *d_g1, *d_g2 = nullptr, *d_gq, *d_cov = nullptr, *d_vao = nullptr, *d_out, *d_off;
-    TRY(upload(c, c->s_bcf[3], gt1, cells, &d_g1));
-    if (!haploid) TRY(upload(c, c->s_bcf[4], gt2, cells, &d_g2));
-    TRY(upload(c, c->s_bcf[5], gq, cells, &d_gq));
-    if (cov) {
-        TRY(upload(c, c->s_bcf[6], cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d_cov));
-        TRY(upload(c, c->s_bcf[7], var_allele_off, 4 * (n_vars + 1), &d_vao));
-    }
-    TRY(scratch(c, c->s_bcf[8], out_cap ? out_cap : 1, &d_out));
-    TRY(scratch(c, c->s_bcf[9], 8 * (n_vars + 1), &d_off));
-    const int rc = mg_encode_calls_bcf_device(c, n_vars, n_planes, haploid, d_g1, d_g2, d_gq, use_mask, min_gq, d_cov, d_vao, key_gt, key_gq, key_cov, d_out, out_cap,
-                                              d_off, bytes_out);
-    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *bytes_out)) return rc; // (as mg_format_calls: row_off and the first out_cap bytes are still the caller's)
-    const size_t have = std::min<uint64_t>(*bytes_out, out_cap);
-    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_vars + 1), hipMemcpyDeviceToHost, c->stream));
-    if (have) HIP_TRY(c, hipMemcpyAsync(out, d_out, have, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return rc;
+    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off));
+    TRY(check_rows_out(c, out, out_cap, row_off_out, bytes_out));
+    DevCells d;
+    void *d_out, *d_off;
+    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d));
+    TRY(stage_rows(c, n_vars, out_cap, &d_out, &d_off));
+    const int rc = mg_encode_calls_bcf_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, use_mask, min_gq, d.cov, d.var_allele_off, key_gt, key_gq, key_cov, d_out,
+                                              out_cap, d_off, bytes_out);
+    return fetch_rows(c, rc, n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
 }
 
-// device milliseconds of the most recent mg_encode_calls_bcf* (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
+// device milliseconds of the most recent mg_encode_calls_bcf* (rows_stats)
 MG_EXPORT int mg_bcf_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    if (!c->bcf_stats_valid) return fail(c, MG_ERR_STATE, "no mg_encode_calls_bcf yet");
-    HIP_TRY(c, hipEventSynchronize(c->ev_bcf[3]));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_bcf[i], c->ev_bcf[i + 1]));
-    return MG_OK;
+    return rows_stats(c, c->rp_bcf, "mg_encode_calls_bcf", ms_out);
 }
 
 // timing and counts of the most recent mg_cover_blocks_device (waits for it)

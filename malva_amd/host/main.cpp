@@ -312,6 +312,18 @@ struct Device {
     }
 };
 
+// A call that fills `buf` and says in *need what it takes (mg_format_calls, mg_format_site_info, mg_encode_calls_bcf): made again with
+// the buffer grown while it answers MG_ERR_LIMIT with a larger need -> its last return code
+template <class Call> int call_grown(std::vector<char> &buf, Call call)
+{
+    for (;;) {
+        uint64_t need = 0;
+        const int rc = call(&need);
+        if (rc != MG_ERR_LIMIT || need <= buf.size()) return rc;
+        buf.resize(need);
+    }
+}
+
 constexpr size_t STRIDE = 136; // MG_MAX_KMER + NUL, rounded to 8
 
 // fixed-stride ASCII rows for the batch calls
@@ -1511,16 +1523,8 @@ int call_main(const Options &o)
                          std::vector<uint64_t> &off) {
         off.resize(n + 1);
         text.resize(n * 40); // (a guess: the call says what it needs)
-        for (;;) {
-            uint64_t need = 0;
-            const int rc = mg_format_site_info(dev.ctx, n, ac, ns, var_allele_off, text.data(), text.size(), off.data(), &need);
-            if (rc == MG_ERR_LIMIT && need > text.size()) {
-                text.resize(need);
-                continue;
-            }
-            dev.check(rc, "mg_format_site_info");
-            break;
-        }
+        dev.check(call_grown(text, [&](uint64_t *need) { return mg_format_site_info(dev.ctx, n, ac, ns, var_allele_off, text.data(), text.size(), off.data(), need); }),
+                  "mg_format_site_info");
         float ms[2] = {0, 0};
         dev.check(mg_site_stats(dev.ctx, ms), "mg_site_stats");
         site_ms[1] += ms[1];
@@ -1670,23 +1674,16 @@ int call_main(const Options &o)
                 if (!bn) continue;
                 row_off[w].resize(bn + 1);
                 row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0)); // (a guess: the call says what it needs)
-                for (;;) {
-                    uint64_t need = 0;
-                    const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose ? b.var_allele_off.data() : nullptr;
-                    const int rc = bcf_out ? mg_encode_calls_bcf(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
-                                                                 bcf_hdr.key("GT"), bcf_hdr.key("GQ"), o.verbose ? bcf_hdr.key("COVS") : 0,
-                                                                 (uint8_t *)row_text[w].data(), row_text[w].size(), row_off[w].data(), &need)
-                                   : o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao,
-                                                                         row_text[w].data(), row_text[w].size(), row_off[w].data(), &need)
-                                                : mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), cov, vao,
-                                                                  row_text[w].data(), row_text[w].size(), row_off[w].data(), &need);
-                    if (rc == MG_ERR_LIMIT && need > row_text[w].size()) {
-                        row_text[w].resize(need);
-                        continue;
-                    }
-                    dev.check(rc, bcf_out ? "mg_encode_calls_bcf" : "mg_format_calls");
-                    break;
-                }
+                const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose ? b.var_allele_off.data() : nullptr;
+                dev.check(call_grown(row_text[w], [&](uint64_t *need) {
+                    return bcf_out ? mg_encode_calls_bcf(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
+                                                         bcf_hdr.key("GT"), bcf_hdr.key("GQ"), o.verbose ? bcf_hdr.key("COVS") : 0,
+                                                         (uint8_t *)row_text[w].data(), row_text[w].size(), row_off[w].data(), need)
+                           : o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao,
+                                                                 row_text[w].data(), row_text[w].size(), row_off[w].data(), need)
+                                        : mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), cov, vao,
+                                                          row_text[w].data(), row_text[w].size(), row_off[w].data(), need);
+                }), bcf_out ? "mg_encode_calls_bcf" : "mg_format_calls");
                 float ms[3] = {0, 0, 0};
                 if (bcf_out) {
                     dev.check(mg_bcf_stats(dev.ctx, ms), "mg_bcf_stats");

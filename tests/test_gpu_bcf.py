@@ -193,6 +193,15 @@ def test_bcf_stats_before_the_first_call():
         assert len(ms) == 3 and all(np.isfinite(m) and m >= 0 for m in ms)
 
 
+def test_bcf_stats_after_an_empty_call():
+    with Context(35, 43, 1 << 20) as c:
+        g = np.zeros((2, 0), dtype=np.int32)
+        out, off = c.encode_calls_bcf(g, g, g, False, (1, 2, 3))                  # no record: the call still counts as one
+        assert out == b"" and list(off) == [0]
+        ms = c.bcf_stats()
+        assert len(ms) == 3 and all(np.isfinite(m) and m >= 0 for m in ms)
+
+
 def _device_form(ctx, g1, g2, gq, haploid, keys, cov, vao, min_gq, cap, guard=64, shift=0):
     """-> (rc, need, bytes [cap], guard bytes, row_off); the buffer starts `shift` bytes into its allocation"""
     dev = torch.device("cuda", 0)

@@ -17,7 +17,7 @@ from malva_amd import Context, MalvaError, synth
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bin", "malva-geno")
-MG_ERR_LIMIT = -5
+MG_ERR_LIMIT, MG_ERR_STATE = -5, -3
 INT_MIN, INT_MAX = -(1 << 31), (1 << 31) - 1
 EDGES = np.array([0, 9, 10, 99, 100, 127, 128, INT_MAX, -1, INT_MIN, 1, 999, 1000, 99999, 100000, 999999999, 1000000000, -9, -10, -2147483647], dtype=np.int64)
 COV_EDGES = np.array([0, 1, 9, 10, 200, 201, 65535, INT_MAX, 1 << 31, (1 << 31) + 1, (1 << 32) - 1, 3000000000], dtype=np.int64)
@@ -219,6 +219,18 @@ def test_buffer_too_small(ctx, planes, n, with_cov):
     with pytest.raises(MalvaError) as e:                                          # the binding hands the size and the offsets on
         ctx.format_calls(g1, g2, gq, haploid, cov, vao, text_cap=len(want) - 1)
     assert e.value.code == MG_ERR_LIMIT and e.value.needed == len(want) and np.array_equal(e.value.row_off, want_off)
+
+
+def test_format_stats_before_the_first_call_and_after_an_empty_one():
+    with Context(35, 43, 1 << 20) as c:
+        with pytest.raises(MalvaError) as e:
+            c.format_stats()
+        assert e.value.code == MG_ERR_STATE
+        g = np.zeros((2, 0), dtype=np.int32)
+        text, off = c.format_calls(g, g, g, False)                                # no record: the call still counts as one
+        assert text == b"" and list(off) == [0]
+        ms = c.format_stats()
+        assert len(ms) == 3 and all(np.isfinite(m) and m >= 0 for m in ms)
 
 
 def test_format_calls_arguments(ctx):

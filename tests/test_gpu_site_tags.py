@@ -12,10 +12,11 @@ import torch
 
 from malva_amd import Context, MalvaError, synth
 from test_gpu_merged import COMMON, _case, _cli, _no_leftovers, _singles, _split, format_plain, haploid_cohort  # noqa: F401 (the fixture)
+from test_gpu_bcf import _case as _bcf_case, encode_plain
 from test_site_tags_cpu import info_text
 
 pytestmark = pytest.mark.gpu
-MG_ERR_LIMIT = -5
+MG_ERR_LIMIT, MG_ERR_STATE = -5, -3
 INT_MIN, INT_MAX = -(1 << 31), (1 << 31) - 1
 ALLELES = np.array([1, 2, 3, 9, 100, 2, 2, 127, 0, 3], dtype=np.int64)             # records of these sizes, mixed
 STRAY = np.array([-1, INT_MIN, INT_MAX, 127, 128, 1 << 20, 100, 9, 3, 2], dtype=np.int64)  # indices most records do not have
@@ -231,6 +232,98 @@ def test_site_info_buffer_too_small(ctx, planes, n):
     with pytest.raises(MalvaError) as e:
         ctx.format_site_info(ac, ns, vao, text_cap=len(want) - 1)
     assert e.value.code == MG_ERR_LIMIT and e.value.needed == len(want) and np.array_equal(e.value.row_off, want_off)
+
+
+def _stats_ok(ms, k):
+    return len(ms) == k and all(np.isfinite(m) and m >= 0 for m in ms)
+
+
+def test_site_stats_before_the_first_call_and_after_empty_ones():
+    g, none, vao = np.zeros((2, 0), dtype=np.int32), np.zeros(0, dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+    with Context(35, 43, 1 << 20) as c:
+        with pytest.raises(MalvaError) as e:
+            c.site_stats()
+        assert e.value.code == MG_ERR_STATE
+        ac, ns = c.site_counts(g, g, g, False, vao)                               # no record: the call still counts as one
+        assert ac.size == 0 and ns.size == 0
+        assert _stats_ok(c.site_stats(), 2)
+    with Context(35, 43, 1 << 20) as c:
+        text, off = c.format_site_info(none, none, vao)
+        assert text == b"" and list(off) == [0]
+        assert _stats_ok(c.site_stats(), 2)
+
+
+def test_site_stats_with_one_kind_run():
+    """0 for the kind that has not run"""
+    g1, g2, gq, vao = _counts_case(3, 33, seed=8)
+    ac, ns = counts_numpy(g1, g2, gq, False, vao, None)
+    with Context(35, 43, 1 << 20) as c:
+        c.site_counts(g1, g2, gq, False, vao)
+        ms = c.site_stats()
+        assert _stats_ok(ms, 2) and ms[1] == 0
+    with Context(35, 43, 1 << 20) as c:
+        c.format_site_info(ac, ns, vao)
+        ms = c.site_stats()
+        assert _stats_ok(ms, 2) and ms[0] == 0
+
+
+# ---- the ABI: the encoders beside each other ----------------------------------------------------------------------------------
+
+def test_the_encoders_do_not_disturb_each_other():
+    """one context, 3 planes x 33 records (a full write tile and a ragged one): text, BCF, counts, INFO and the text again, through the
+    host forms; then through the device forms, every output held on the device until the last call has run and compared only then"""
+    planes, n, keys, min_gq = 3, 33, (1, 128, 32768), 50
+    g1, g2, gq, cov, vao = _bcf_case(planes, n, False, True, seed=33)
+    want_text = format_plain(g1, g2, gq, False, cov, vao)
+    want_bcf = encode_plain(g1, g2, gq, False, keys, cov, vao, min_gq)
+    want_ac, want_ns = counts_numpy(g1, g2, gq, False, vao, min_gq)
+    want_info = info_rows(want_ac, want_ns, vao)
+    assert want_ac.any() and (want_ns < planes).any()
+
+    def same(got, want):
+        assert np.array_equal(got[1], want[1]) and got[0] == want[0]
+    with Context(35, 43, 1 << 20) as c:
+        same(c.format_calls(g1, g2, gq, False, cov, vao), want_text)
+        same(c.encode_calls_bcf(g1, g2, gq, False, keys, cov, vao, min_gq=min_gq), want_bcf)
+        ac, ns = c.site_counts(g1, g2, gq, False, vao, min_gq=min_gq)
+        assert np.array_equal(ac, want_ac) and np.array_equal(ns, want_ns)
+        same(c.format_site_info(ac, ns, vao), want_info)
+        same(c.format_calls(g1, g2, gq, False, cov, vao), want_text)
+        assert _stats_ok(c.format_stats(), 3) and _stats_ok(c.bcf_stats(), 3) and _stats_ok(c.site_stats(), 2)
+
+        dev = torch.device("cuda", 0)
+        d1, d2, dq, dc, dv = (torch.from_numpy(a.view(np.int32)).to(dev) for a in (g1, g2, gq, cov, vao))
+        dac = torch.full((want_ac.size,), -1, dtype=torch.int32, device=dev)
+        dns = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        held = []                                                                 # (what, bytes on the device, offsets on the device, wanted)
+
+        def rows(what, want, call):
+            out = torch.full((len(want[0]) + 64,), 0xAA, dtype=torch.uint8, device=dev)
+            off = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            assert call(out.data_ptr(), len(want[0]), off.data_ptr()) == (0, len(want[0])), what
+            held.append((what, out, off, want))
+        v = C.c_void_p
+
+        def info(d_text, cap, d_off):
+            need = C.c_uint64(0)
+            return c._L.mg_format_site_info_device(c.h, n, v(dac.data_ptr()), v(dns.data_ptr()), v(dv.data_ptr()), v(d_text), cap, v(d_off), C.byref(need)), need.value
+        text = lambda d_text, cap, d_off: c.format_calls_device(n, planes, False, d1.data_ptr(), d2.data_ptr(), dq.data_ptr(), dc.data_ptr(), dv.data_ptr(), d_text, cap, d_off)
+        rows("text", want_text, text)
+        rows("bcf", want_bcf, lambda d_out, cap, d_off: c.encode_calls_bcf_device(n, planes, False, d1.data_ptr(), d2.data_ptr(), dq.data_ptr(), dc.data_ptr(), dv.data_ptr(),
+                                                                                 keys, d_out, cap, d_off, min_gq=min_gq))
+        c._ck(c._L.mg_site_counts_device(c.h, n, planes, 0, v(d1.data_ptr()), v(d2.data_ptr()), v(dq.data_ptr()), 1, min_gq, v(dv.data_ptr()), 0, v(dac.data_ptr()),
+                                         v(dns.data_ptr())))
+        rows("info", want_info, info)
+        rows("text again", want_text, text)
+        c.synchronize()
+        assert np.array_equal(dac.cpu().numpy().view(np.uint32), want_ac) and np.array_equal(dns.cpu().numpy().view(np.uint32), want_ns)
+        for what, out, off, want in held:
+            h = out.cpu().numpy()
+            assert np.array_equal(off.cpu().numpy().view(np.uint64), want[1]), what
+            assert h[:len(want[0])].tobytes() == want[0], what
+            assert (h[len(want[0]):] == 0xAA).all(), what
+        assert _stats_ok(c.format_stats(), 3) and _stats_ok(c.bcf_stats(), 3) and _stats_ok(c.site_stats(), 2)
 
 
 # ---- the ABI: masked cells --------------------------------------------------------------------------------------------------
