@@ -504,6 +504,27 @@ int mg_format_calls_masked(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int ha
 int mg_format_calls_masked_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
                                   int32_t min_gq, const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
                                   void *d_row_off_out, uint64_t *text_bytes_out);
+/* mg_format_calls_masked (the mask applies when use_mask != 0) with the genotype posteriors of every cell, the FORMAT field GP
+ * (Number=G, Type=Float), behind the cell's last field: `:` and the list, so a cell is `GT:GQ:GP` or, with cov, `GT:GQ:COVS:GP`.
+ * The values are the doubles mg_genotype / mg_call_isolated leave in probs (gt.second / total_qual, var_block.hpp:381: the
+ * numbers behind GTS= of the single-sample output): probs is [n_planes][var_gt_off[n_vars]], record v's values of plane p start
+ * at probs[p * var_gt_off[n_vars] + var_gt_off[v]] (var_gt_off: [n_vars + 1]); status is [n_planes][n_vars].  var_allele_off is
+ * required with or without cov (cov stays optional): the record has A = var_allele_off[v + 1] - var_allele_off[v] alleles and
+ * G = A (haploid) or A (A + 1) / 2 genotypes.  probs holds them in the reference's order -- a outer, c >= a inner: 0/0, 0/1,
+ * 0/2, 1/1, .. -- and GP is in VCF order, genotype j/k (j <= k) at index k (k + 1) / 2 + j: 0/0, 0/1, 1/1, 0/2, ..; haploid:
+ * the index is the allele.  A cell whose status is not MG_GT_NORMAL prints the whole field as one `.` and its probs are not
+ * read; otherwise G comma-separated values (none for a record without alleles).  A value is PRINTABLE when its sign bit is
+ * clear and 0 <= p <= 1 -- NaN, -0.0, negatives, anything above 1 and the infinities are not -- and prints exactly as
+ * printf("%f") prints it, always 8 bytes, `0.dddddd` or `1.000000`: rounded to nearest on the exact binary value, ties to even,
+ * as glibc does, in integers (N = m 10^6 with m the 53-bit significand, q = N >> s, s = 1075 - the biased exponent, and the
+ * remainder against 2^(s-1)).  An unprintable value prints `.`.  A masked cell keeps its GP as it keeps `:GQ` and `:COVS`.
+ * Everything else -- rows, buffer contract, n_vars == 0, the two forms, mg_format_stats -- is mg_format_calls'. */
+int mg_format_calls_gp(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                       int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                       const uint8_t *status, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out);
+int mg_format_calls_gp_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                              int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                              const void *d_status, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out);
 
 /* ---- the site tags of a multi-sample VCF (AC / AN / AF / NS) -----------------------
  * mg_site_counts: the allele counts of every record over the planes.  gt1 / gt2 / gq as for mg_format_calls (n_planes 1..64;
@@ -559,6 +580,20 @@ int mg_encode_calls_bcf(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haplo
 int mg_encode_calls_bcf_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
                                size_t out_cap, void *d_row_off_out, uint64_t *bytes_out);
+/* mg_encode_calls_bcf with a further field behind GT, GQ and COVS (cov stays optional; var_allele_off is required) --
+ *   GP    typed_int(key_gp),  desc(G, 5), for every plane the record's G float32
+ * probs, var_gt_off, status, G, the order and PRINTABLE as for mg_format_calls_gp.  A printable value is stored as (float)p,
+ * IEEE round to nearest even, float denormals kept (1e-40 does not become 0; the conversion is done in integers); an
+ * unprintable one as the missing float 0x7F800001; a cell that is not MG_GT_NORMAL as 0x7F800001 followed by G - 1
+ * end-of-vector floats 0x7F800002, which is what `.` for a vector is in BCF.  desc takes its long form from G = 15. */
+int mg_encode_calls_bcf_gp(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                           int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                           const uint8_t *status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap,
+                           uint64_t *row_off_out, uint64_t *bytes_out);
+int mg_encode_calls_bcf_gp_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                  int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                                  const void *d_status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap,
+                                  void *d_row_off_out, uint64_t *bytes_out);
 int mg_bcf_stats(mg_ctx *ctx, float *ms_out);
 
 /* ---- index payloads  (bloom_filter.hpp:127-146, kmap.hpp:52-82) ----------- */

@@ -112,6 +112,8 @@ def lib():
         "mg_format_stats": [vp, vp],
         "mg_format_calls_masked": [vp, sz, u32, it, vp, vp, vp, i32, vp, vp, vp, sz, vp, vp],
         "mg_format_calls_masked_device": [vp, sz, u32, it, vp, vp, vp, i32, vp, vp, vp, sz, vp, vp],
+        "mg_format_calls_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp],
+        "mg_format_calls_gp_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp],
         "mg_site_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp],
         "mg_site_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp],
         "mg_format_site_info": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
@@ -119,6 +121,8 @@ def lib():
         "mg_site_stats": [vp, vp],
         "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
+        "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
+        "mg_encode_calls_bcf_gp_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
         "mg_bcf_stats": [vp, vp],
         "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
         "mg_comm_unique_id": [vp],
@@ -183,6 +187,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
@@ -644,6 +649,47 @@ class Context:
             self._ck(rc)
         return rc, need.value
 
+    def _gp_rows(self, call_abi, gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, cap):
+        """the host form of a *_gp entry: call_abi(n, planes, arrays.., out, cap, row_off, need) -> rc; the buffer rule of format_calls"""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
+        planes, n = g1.shape
+        cv, vo = a(cov, np.uint32), a(var_allele_off, np.uint32)
+        pr, go, st = a(probs, np.float64), a(var_gt_off, np.uint64), a(status, np.uint8)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+
+        def call(c):
+            out = np.zeros(max(c, 1), dtype=np.uint8)
+            return call_abi(n, planes, _p(g1), _p(g2), _p(q), _p(cv), _p(vo), _p(pr), _p(go), _p(st), _p(out) if c else None, c, _p(row_off), C.byref(need)), out
+        rc, out = call(0 if cap is None else int(cap))
+        if rc == -5 and cap is None and need.value:
+            rc, out = call(need.value)
+        if rc != 0:
+            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
+            e.needed, e.row_off, e.text = need.value, row_off, out
+            raise e
+        return out[:need.value].tobytes(), row_off
+
+    def format_calls_gp(self, gt1, gt2, gq, haploid, var_allele_off, probs, var_gt_off, status, cov=None, text_cap=None, min_gq=None):
+        """format_calls with the field GP behind every cell's last (mg_format_calls_gp).  probs: [planes, var_gt_off[n_vars]] float64,
+        a record's likelihoods in the reference's order; var_gt_off: [n_vars + 1] uint64; status: [planes, n_vars] uint8;
+        var_allele_off is required, cov optional."""
+        return self._gp_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, out, cap, row_off, need: self._L.mg_format_calls_gp(
+            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, out, cap, row_off, need),
+            gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, text_cap)
+
+    def format_calls_gp_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_text, text_cap,
+                               d_row_off, min_gq=None):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_format_calls_gp_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0), v(d_cov),
+                                               v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), v(d_text), int(text_cap), v(d_row_off), C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
     def format_stats(self):
         """-> device ms of the most recent format_calls: (length pass, scan, write pass)"""
         ms = (C.c_float * 3)()
@@ -729,6 +775,25 @@ class Context:
         rc = self._L.mg_encode_calls_bcf_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
                                                 v(d_cov), v(d_var_allele_off), int(keys[0]), int(keys[1]), int(keys[2]), v(d_out), int(out_cap), v(d_row_off),
                                                 C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
+    def encode_calls_bcf_gp(self, gt1, gt2, gq, haploid, keys, var_allele_off, probs, var_gt_off, status, cov=None, out_cap=None, min_gq=None):
+        """encode_calls_bcf with the float field GP behind the record's last (mg_encode_calls_bcf_gp).  keys: (gt, gq, cov, gp);
+        the arrays as format_calls_gp's."""
+        return self._gp_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, out, cap, row_off, need: self._L.mg_encode_calls_bcf_gp(
+            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, int(keys[0]), int(keys[1]), int(keys[2]),
+            int(keys[3]), out, cap, row_off, need), gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, out_cap)
+
+    def encode_calls_bcf_gp_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, keys, d_out, out_cap,
+                                   d_row_off, min_gq=None):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_encode_calls_bcf_gp_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
+                                                   v(d_cov), v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), int(keys[0]), int(keys[1]), int(keys[2]),
+                                                   int(keys[3]), v(d_out), int(out_cap), v(d_row_off), C.byref(need))
         if rc not in (0, -5) or (rc == -5 and not need.value):
             self._ck(rc)
         return rc, need.value

@@ -2,10 +2,15 @@
 // specification v4.3, section 6.3.3) -- what call_text_kernels.h makes as text, here in the binary form, 3 bytes per diploid GT:GQ cell
 // instead of 8 to 10.  Restated from the published layout; no file written by htslib exists here: parity unpinned, as for the reader.
 //
-// Row v = for each of its two fields (three with cov), in this order:
+// Row v = for each of its two fields (three with cov, one more with probs: mg_encode_calls_bcf_gp), in this order:
 //   GT    typed_int(key_gt)  desc(ploidy, T)  [plane][ploidy] values   ploidy 1 (haploid) or 2; allele index a -> (a + 1) << 1 (unphased)
 //   GQ    typed_int(key_gq)  desc(1, T)       [plane] values           as they are, mask or no mask
 //   COVS  typed_int(key_cov) desc(A, T)       [plane][A] values        (int32_t)cov[..], A = the record's alleles
+//   GP    typed_int(key_gp)  desc(G, 5)       [plane][G] float32       the record's likelihoods in VCF genotype order, G = A (haploid) or
+//                                                                      A (A + 1) / 2; (float)p to nearest even, made in integers (gp_float_bits)
+//                                                                      so that float denormals stay; an unprintable value (gp_printable)
+//                                                                      is the missing float, a cell that is not MG_GT_NORMAL the missing
+//                                                                      float and G - 1 end-of-vector floats
 // desc(n, t) is the byte n << 4 | t for n < 15, else 0xF0 | t and typed_int(n); typed_int(x) is desc(1, t) and x in the smallest of int8
 // (t = 1), int16 (2), int32 (3) that holds it; little endian throughout.  T of a field of a record is the smallest type that holds
 // every value of that field over all planes with BCF's reserved codes (missing, end of vector) kept free: int8 for [-120, 127], int16
@@ -18,6 +23,7 @@
 // Three steps (mg_encode_calls_bcf_device), those of mg_format_calls:
 //   bcf_len_kernel     one wave per record, lane = plane: wave min / max of the GT codes, of GQ and (the lanes looping over the
 //                      record's alleles) of the coverages -> the three type codes types[3 v ..] and the row length len[v]
+//                      (GP is float32 whatever its values: its share of the length is arithmetic, probs are not read)
 //   the scan           fmt_scan: len[] -> row_off[] (u64) and the total
 //   bcf_write_kernel   fmt_write_tile with BcfRows: the field headers by lane 0, every lane its plane's values at an offset that is
 //                      pure arithmetic (no prefix sum: the cells of a field are of one width), through the same LDS window and
@@ -34,11 +40,33 @@ struct BcfArgs {
     int haploid;
     const i32 *gt1, *gt2, *gq;   // [n_planes][n_vars]
     const u32 *cov;              // [n_planes][var_allele_off[n_vars]] or NULL
-    const u32 *var_allele_off;   // [n_vars + 1] (with cov)
+    const u32 *var_allele_off;   // [n_vars + 1] (with cov or probs)
     int masked;
     i32 min_gq;
     i32 key_gt, key_gq, key_cov; // dictionary indexes, >= 0
+    // mg_encode_calls_bcf_gp (all three or none, as FmtArgs')
+    const double *probs;         // [n_planes][var_gt_off[n_vars]]
+    const u64 *var_gt_off;       // [n_vars + 1]
+    const u8 *status;            // [n_planes][n_vars]
+    i32 key_gp;
 };
+
+constexpr u32 BCF_FLOAT_MISSING = 0x7F800001u, BCF_FLOAT_EOV = 0x7F800002u;
+
+// (float)p of a printable p as bits, round to nearest even, without the conversion instruction (whose treatment of a denormal result
+// hangs on the kernel's mode): p = M 2^(e - 1075); a float's unit is 2^(e - 1046) where it is normal (e >= 897), else 2^-149
+__device__ __forceinline__ u32 gp_float_bits(double p)
+{
+    const u64 bits = (u64)__double_as_longlong(p);
+    const u32 e = (u32)(bits >> 52);
+    if (e <= 862) return 0; // below 2^-160 (zero and the double denormals included): less than half the smallest float
+    const u64 M = (bits & 0xFFFFFFFFFFFFFull) | 1ull << 52;
+    const u32 sh = e >= 897 ? 29u : 926u - e; // 29 .. 63
+    u32 f = (e >= 897 ? (e - 897) << 23 : 0u) + (u32)(M >> sh); // (a normal's hidden bit adds the exponent's last 1)
+    const u64 r = M & ((1ull << sh) - 1), half = 1ull << (sh - 1);
+    if (r > half || (r == half && (f & 1))) ++f; // (a carry out of the mantissa is the next exponent)
+    return f;
+}
 
 __device__ __forceinline__ u32 bcf_type_of(i32 lo, i32 hi)
 {
@@ -95,7 +123,9 @@ __device__ __forceinline__ i32 bcf_wave_max(i32 x)
     return x;
 }
 
-// the bytes of row v whose three fields have the types t[0..2] (t[2] unused without cov)
+// the bytes of row v whose three fields have the types t[0..2] (t[2] unused without cov).  GP: the kernels of mg_encode_calls_bcf_gp, a
+// build of their own as in call_text_kernels.h
+template <bool GP>
 __device__ __forceinline__ u64 bcf_row_len(const BcfArgs &a, u64 v, const u32 *t)
 {
     const u64 P = a.n_planes;
@@ -105,10 +135,15 @@ __device__ __forceinline__ u64 bcf_row_len(const BcfArgs &a, u64 v, const u32 *t
         const u32 A = a.var_allele_off[v + 1] - a.var_allele_off[v];
         len += bcf_typed_int_len(a.key_cov) + bcf_desc_len(A) + P * A * bcf_width(t[2]);
     }
+    if (GP) {
+        const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+        len += bcf_typed_int_len(a.key_gp) + bcf_desc_len((u32)G) + P * G * 4;
+    }
     return len;
 }
 
 // meta[1] is raised when a row does not fit 32 bits, as by fmt_len_kernel
+template <bool GP>
 __global__ void __launch_bounds__(FMT_TPB) bcf_len_kernel(BcfArgs a, u32 *__restrict__ len, unsigned char *__restrict__ types, unsigned long long *meta)
 {
     const u32 lane = threadIdx.x & 63;
@@ -145,13 +180,14 @@ __global__ void __launch_bounds__(FMT_TPB) bcf_len_kernel(BcfArgs a, u32 *__rest
     }
     if (lane < 3) types[3 * v + lane] = (unsigned char)(lane == 0 ? t[0] : lane == 1 ? t[1] : t[2]);
     if (lane == 0) {
-        const u64 bytes = bcf_row_len(a, v, t);
+        const u64 bytes = bcf_row_len<GP>(a, v, t);
         if (bytes > 0xFFFFFFFFull) atomicOr(meta + 1, 1ull);
         len[v] = (u32)bytes;
     }
 }
 
-// a record's row: the three field headers by lane 0, the values of plane `lane` by that lane
+// a record's row: the field headers by lane 0, the values of plane `lane` by that lane
+template <bool GP>
 struct BcfRows {
     BcfArgs a;
     const unsigned char *types;
@@ -178,24 +214,59 @@ struct BcfRows {
         pos += bcf_typed_int_len(a.key_gq) + 1;
         if (mine) bcf_put_val(w, pos + (u64)lane * bcf_width(t_gq), gq, t_gq);
         pos += (u64)a.n_planes * bcf_width(t_gq);
-        if (!a.cov) return;
-        // COVS
-        const u32 a0 = a.var_allele_off[v], A = a.var_allele_off[v + 1] - a0;
-        if (lane == 0) bcf_put_desc(w, bcf_put_typed_int(w, pos, a.key_cov), A, t_cov);
-        pos += bcf_typed_int_len(a.key_cov) + bcf_desc_len(A);
-        const u64 span = (u64)A * bcf_width(t_cov);
-        u64 at = pos + (u64)lane * span;
-        if (!mine || at >= w.w0 + w.wlen || at + span <= w.w0) return; // (nothing of this plane's in the window)
-        const u32 *cv = a.cov + (u64)lane * a.var_allele_off[a.n_vars] + a0;
-        for (u32 s = 0; s < A; ++s) at = bcf_put_val(w, at, (i32)cv[s], t_cov);
+        const u64 w1 = w.w0 + w.wlen;
+        if (a.cov) { // COVS
+            const u32 a0 = a.var_allele_off[v], A = a.var_allele_off[v + 1] - a0;
+            if (lane == 0) bcf_put_desc(w, bcf_put_typed_int(w, pos, a.key_cov), A, t_cov);
+            pos += bcf_typed_int_len(a.key_cov) + bcf_desc_len(A);
+            const u64 span = (u64)A * bcf_width(t_cov);
+            u64 at = pos + (u64)lane * span;
+            if (mine && at < w1 && at + span > w.w0) { // (else: nothing of this plane's in the window)
+                const u32 *cv = a.cov + (u64)lane * a.var_allele_off[a.n_vars] + a0;
+                for (u32 s = 0; s < A; ++s) at = bcf_put_val(w, at, (i32)cv[s], t_cov);
+            }
+            pos += (u64)a.n_planes * span;
+        }
+        if (!GP) return;
+        // GP: value g of this plane at pos + (lane G + g) 4 -- only those of the window are loaded
+        const u32 A = a.var_allele_off[v + 1] - a.var_allele_off[v];
+        const u64 G = a.haploid ? (u64)A : (u64)A * (A + 1) / 2;
+        if (lane == 0) bcf_put_desc(w, bcf_put_typed_int(w, pos, a.key_gp), (u32)G, 5);
+        pos += bcf_typed_int_len(a.key_gp) + bcf_desc_len((u32)G);
+        const u64 at = pos + (u64)lane * G * 4;
+        if (!mine || at >= w1 || at + G * 4 <= w.w0) return;
+        const u64 g_lo = w.w0 > at ? (w.w0 - at) / 4 : 0, g_hi = w1 - at < G * 4 ? (w1 - at + 3) / 4 : G; // (a value the window cuts is made on both sides)
+        const bool normal = a.status[i] == MG_GT_NORMAL;
+        const double *pr = a.probs + (u64)lane * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+        // VCF index g = k (k + 1) / 2 + j: (j, k) of g_lo from a square root, put right in integers, then stepped
+        u32 k = 0, j = 0;
+        if (!a.haploid && normal) {
+            k = (u32)((sqrt(8.0 * (double)g_lo + 1.0) - 1.0) / 2.0);
+            while ((u64)k * (k + 1) / 2 > g_lo) --k;
+            while ((u64)(k + 1) * (k + 2) / 2 <= g_lo) ++k;
+            j = (u32)(g_lo - (u64)k * (k + 1) / 2);
+        }
+        for (u64 g = g_lo; g < g_hi; ++g) {
+            u32 f = g ? BCF_FLOAT_EOV : BCF_FLOAT_MISSING;
+            if (normal) {
+                const double x = pr[a.haploid ? g : gp_src(A, j, k)];
+                f = gp_printable(x) ? gp_float_bits(x) : BCF_FLOAT_MISSING;
+                if (j++ == k) {
+                    ++k;
+                    j = 0;
+                }
+            }
+            bcf_put_val(w, at + g * 4, (i32)f, 3);
+        }
     }
 };
 
+template <bool GP>
 __global__ void __launch_bounds__(FMT_TPB) bcf_write_kernel(BcfArgs a, const unsigned char *__restrict__ types, const unsigned long long *__restrict__ row_off,
                                                            char *out, u64 out_cap)
 {
     __shared__ __attribute__((aligned(16))) char sh[FMT_WINDOW];
-    fmt_write_tile(BcfRows{a, types}, sh, a.n_vars, row_off, out, out_cap);
+    fmt_write_tile(BcfRows<GP>{a, types}, sh, a.n_vars, row_off, out, out_cap);
 }
 
 } // namespace

@@ -16,6 +16,11 @@
 //                      aligned 16-byte stores.  Only the pieces a tile shares with its neighbours (its first and last, and the one
 //                      text_cap cuts) are stored byte by byte.
 // Numbers print as std::to_string(int) prints them over the whole int32 range; a coverage as std::to_string((int)cov).
+//
+// mg_format_calls_gp adds the field GP behind the cell's last: the record's normalised likelihoods (`probs`, the doubles behind GTS= of the
+// single-sample output) in VCF genotype order, each printed as printf("%f") prints it.  A value is 8 bytes (`0.dddddd`, `1.000000`) when it
+// is printable -- sign bit clear and <= 1 -- and the one byte `.` when it is not, so the length pass formats nothing; the digits are made
+// in integers from the double's bits (gp_micro), to nearest on the exact value with ties to even, as glibc rounds.
 #pragma once
 #include "kmer_dev.h"
 
@@ -66,12 +71,106 @@ struct FmtArgs {
     int haploid;
     const i32 *gt1, *gt2, *gq;   // [n_planes][n_vars]
     const u32 *cov;              // [n_planes][var_allele_off[n_vars]] or NULL
-    const u32 *var_allele_off;   // [n_vars + 1] (with cov)
+    const u32 *var_allele_off;   // [n_vars + 1] (with cov or probs)
     int masked;                  // mg_format_calls_masked: a cell whose gq < min_gq prints its genotype as missing ('.' or './.')
     i32 min_gq;
+    // mg_format_calls_gp (all three or none; var_allele_off is then required with or without cov)
+    const double *probs;         // [n_planes][var_gt_off[n_vars]], a record's values in the reference's order: a outer, c >= a inner
+    const u64 *var_gt_off;       // [n_vars + 1]
+    const u8 *status;            // [n_planes][n_vars]: a cell that is not MG_GT_NORMAL has no list, its probs are not read
 };
 
-// plane p's cell of record v, the tab in front of it included
+// ---- GP: the genotype posteriors of a cell -----------------------------------------------------------------------------------------
+// printable: sign bit clear and 0 <= p <= 1 (as bit patterns the non-negative doubles are ordered like integers: NaN, +inf and
+// everything above 1 lie behind 1.0, whatever has its sign bit set -- -0.0 included -- behind those)
+__device__ __forceinline__ bool gp_printable(double p) { return (u64)__double_as_longlong(p) <= 0x3FF0000000000000ull; }
+
+// a printable p in millionths, rounded to nearest on the exact binary value, ties to even: what printf("%f") prints without its point.
+// p = m 2^-s with m the 53-bit significand (a denormal's without the hidden bit), s = 1075 - the biased exponent (1074 for denormals):
+// N = m 10^6 (< 2^73, two words), q = N >> s, r = N mod 2^s against half = 2^(s-1).  s >= 128: q = 0 and r = N < half.
+__device__ __forceinline__ u32 gp_micro(double p)
+{
+    const u64 bits = (u64)__double_as_longlong(p);
+    const u32 e = (u32)(bits >> 52);
+    const u64 m = e ? (bits & 0xFFFFFFFFFFFFFull) | 1ull << 52 : bits;
+    const u32 s = 1075u - (e ? e : 1u); // 52 .. 1074
+    if (s >= 128) return 0;
+    const u64 lo = m * 1000000ull, hi = __umul64hi(m, 1000000ull);
+    u64 q, r_hi, r_lo, h_hi, h_lo;
+    if (s < 64) {
+        q = hi << (64 - s) | lo >> s;
+        r_hi = 0;
+        r_lo = lo & ((1ull << s) - 1);
+        h_hi = 0;
+        h_lo = 1ull << (s - 1);
+    } else {
+        const u32 t = s - 64;
+        q = hi >> t;
+        r_hi = hi & ((1ull << t) - 1);
+        r_lo = lo;
+        h_hi = t ? 1ull << (t - 1) : 0;
+        h_lo = t ? 0 : 1ull << 63;
+    }
+    if (r_hi > h_hi || (r_hi == h_hi && r_lo > h_lo)) q += 1;
+    else if (r_hi == h_hi && r_lo == h_lo) q += q & 1;
+    return (u32)q;
+}
+
+// where genotype j/k (j <= k) of a diploid record of A alleles lies in probs' order
+__device__ __forceinline__ u64 gp_src(u32 A, u32 j, u32 k) { return (u64)j * (2ull * A - j + 1) / 2 + (k - j); }
+
+// the bytes of a cell's GP field, its ':' included
+__device__ __forceinline__ u32 gp_len(const FmtArgs &a, u64 v, u32 p)
+{
+    if (a.status[(u64)p * a.n_vars + v] != MG_GT_NORMAL) return 2;
+    const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+    const double *pr = a.probs + (u64)p * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+    u32 len = G ? 0 : 1;
+    for (u64 g = 0; g < G; ++g) len += gp_printable(pr[g]) ? 9 : 2; // (':' in front of the first, ',' of the others; the order does not matter here)
+    return len;
+}
+// A value whose bytes lie wholly outside the window is stepped over by its width alone; behind the window's end nothing is left to do.
+__device__ __forceinline__ u64 gp_put(const FmtArgs &a, const FmtWindow &w, u64 v, u32 p, u64 pos)
+{
+    w.put(pos++, ':');
+    if (a.status[(u64)p * a.n_vars + v] != MG_GT_NORMAL) {
+        w.put(pos++, '.');
+        return pos;
+    }
+    const u32 A = a.var_allele_off[v + 1] - a.var_allele_off[v];
+    const double *pr = a.probs + (u64)p * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+    const u64 w1 = w.w0 + w.wlen;
+    bool first = true;
+    for (u32 k = 0; k < A; ++k)
+        for (u32 j = a.haploid ? k : 0; j <= k; ++j) { // VCF order: index k (k + 1) / 2 + j; haploid: the allele
+            if (pos >= w1) return pos;
+            if (!first) w.put(pos++, ',');
+            first = false;
+            const double x = pr[a.haploid ? (u64)k : gp_src(A, j, k)];
+            if (!gp_printable(x)) {
+                w.put(pos++, '.');
+                continue;
+            }
+            if (pos + 8 <= w.w0 || pos >= w1) {
+                pos += 8;
+                continue;
+            }
+            u32 q = gp_micro(x);
+            w.put(pos, q == 1000000u ? '1' : '0');
+            w.put(pos + 1, '.');
+            if (q == 1000000u) q = 0;
+            for (u32 d = 8; d-- > 2;) {
+                w.put(pos + d, (char)('0' + q % 10u));
+                q /= 10u;
+            }
+            pos += 8;
+        }
+    return pos;
+}
+
+// plane p's cell of record v, the tab in front of it included.  GP: the kernels of mg_format_calls_gp -- a build of their own, so that
+// those of the entries without it keep the registers they had
+template <bool GP>
 __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
 {
     const u64 i = (u64)p * a.n_vars + v;
@@ -88,8 +187,10 @@ __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
         for (u32 s = a0; s < a1; ++s) len += 1 + fmt_int_len((i32)cv[s]); // (':' in front of the first, ',' of the others)
         if (a0 == a1) len += 1;                                          // a record without alleles: the empty list behind its ':'
     }
+    if (GP) len += gp_len(a, v, p);
     return len;
 }
+template <bool GP>
 __device__ __forceinline__ u64 fmt_cell_put(const FmtArgs &a, const FmtWindow &w, u64 v, u32 p, u64 pos)
 {
     const u64 i = (u64)p * a.n_vars + v;
@@ -119,16 +220,18 @@ __device__ __forceinline__ u64 fmt_cell_put(const FmtArgs &a, const FmtWindow &w
             pos = w.put_int(pos, (i32)cv[s]);
         }
     }
+    if (GP) pos = gp_put(a, w, v, p, pos);
     return pos;
 }
 
 // meta[1] is raised when a row does not fit 32 bits (the scan then reports ~0 as the total)
+template <bool GP>
 __global__ void __launch_bounds__(FMT_TPB) fmt_len_kernel(FmtArgs a, u32 *__restrict__ len, unsigned long long *meta)
 {
     const u32 lane = threadIdx.x & 63;
     const u64 v = (u64)blockIdx.x * (FMT_TPB / 64) + (threadIdx.x >> 6);
     if (v >= a.n_vars) return;
-    unsigned long long mine = lane < a.n_planes ? fmt_cell_len(a, v, lane) : 0;
+    unsigned long long mine = lane < a.n_planes ? fmt_cell_len<GP>(a, v, lane) : 0;
     for (int d = 32; d; d >>= 1) mine += (unsigned long long)__shfl_xor((long long)mine, d, 64);
     if (lane == 0) {
         mine += 1; // '\n'
@@ -212,26 +315,28 @@ __device__ __forceinline__ void fmt_write_tile(const Rows &rows, char *sh, u64 n
 }
 
 // a record's sample columns: every lane its plane's cell at the offset a wave prefix sum gives it
+template <bool GP>
 struct FmtCellRows {
     FmtArgs a;
     __device__ __forceinline__ void put(const FmtWindow &w, u64 v, u32 lane, u64 r0, u64 r1) const
     {
-        const u32 mine = lane < a.n_planes ? fmt_cell_len(a, v, lane) : 0;
+        const u32 mine = lane < a.n_planes ? fmt_cell_len<GP>(a, v, lane) : 0;
         u32 incl = mine;
         for (int d = 1; d < 64; d <<= 1) {
             const u32 up = (u32)__shfl_up((int)incl, d, 64);
             if (lane >= (u32)d) incl += up;
         }
         const u64 at = r0 + (incl - mine);
-        if (lane < a.n_planes && at < w.w0 + w.wlen && at + mine > w.w0) fmt_cell_put(a, w, v, lane, at);
+        if (lane < a.n_planes && at < w.w0 + w.wlen && at + mine > w.w0) fmt_cell_put<GP>(a, w, v, lane, at);
         if (lane == 0) w.put(r1 - 1, '\n');
     }
 };
 
+template <bool GP>
 __global__ void __launch_bounds__(FMT_TPB) fmt_write_kernel(FmtArgs a, const unsigned long long *__restrict__ row_off, char *text, u64 text_cap)
 {
     __shared__ __attribute__((aligned(16))) char sh[FMT_WINDOW];
-    fmt_write_tile(FmtCellRows{a}, sh, a.n_vars, row_off, text, text_cap);
+    fmt_write_tile(FmtCellRows<GP>{a}, sh, a.n_vars, row_off, text, text_cap);
 }
 
 } // namespace

@@ -88,6 +88,7 @@ struct RowPass {
 // no device form touches it (those own a RowPass, s_bcf_types and s_scan, and read and write the caller's buffers).
 struct RowStage {
     Scratch gt1, gt2, gq, cov, var_allele_off, ac, ns, out, row_off;
+    Scratch probs, var_gt_off, status; // mg_format_calls_gp, mg_encode_calls_bcf_gp
 };
 
 struct mg_ctx {
@@ -700,7 +701,8 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     for (hipEvent_t e : c->ev_cnt)
         if (e) hipEventDestroy(e);
     for (Scratch *q : {&c->rp_fmt.len, &c->rp_fmt.meta, &c->rp_info.len, &c->rp_info.meta, &c->rp_bcf.len, &c->rp_bcf.meta, &c->s_bcf_types, &c->stage.gt1, &c->stage.gt2,
-                       &c->stage.gq, &c->stage.cov, &c->stage.var_allele_off, &c->stage.ac, &c->stage.ns, &c->stage.out, &c->stage.row_off})
+                       &c->stage.gq, &c->stage.cov, &c->stage.var_allele_off, &c->stage.ac, &c->stage.ns, &c->stage.out, &c->stage.row_off, &c->stage.probs,
+                       &c->stage.var_gt_off, &c->stage.status})
         hipFree(q->p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
@@ -3048,13 +3050,19 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
 // ---- as BCF (bcf_kernels.h) ---------------------------------------------------------------------------------------------------------
 namespace {
 // The argument checks that a host form and its device form share (host pointers there, device pointers here): of whoever reads a batch's
-// cells (gq where reads_gq, cov with var_allele_off or neither), and of where an encoder's rows go
+// cells (gq where reads_gq, cov with var_allele_off or neither; gp, the *_gp entries: var_allele_off with or without cov, and the three
+// arrays of the likelihoods), and of where an encoder's rows go
+struct GpCells {
+    const void *probs, *var_gt_off, *status;
+};
 int check_cells(mg_ctx *c, const char *who, size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, bool reads_gq,
-                const void *cov, const void *var_allele_off)
+                const void *cov, const void *var_allele_off, const GpCells *gp = nullptr)
 {
     if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "%s: n_planes is 1..64", who);
-    if ((cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
+    if (!gp && (cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
+    if (gp && (!var_allele_off || !gp->var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
     if (n_vars && (!gt1 || (!haploid && !gt2) || (reads_gq && !gq))) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars && gp && (!gp->probs || !gp->status)) return fail(c, MG_ERR_ARG, "NULL argument");
     return MG_OK;
 }
 int check_rows_out(mg_ctx *c, const void *out, size_t cap, const void *row_off, const uint64_t *bytes_out)
@@ -3131,9 +3139,10 @@ int rows_stats(mg_ctx *c, RowPass &rp, const char *who, float *ms_out)
 // the host forms' way in: a batch's cells go up (gt1, gt2 unless haploid, gq, cov and var_allele_off where given), the rows get a place
 struct DevCells {
     void *gt1 = nullptr, *gt2 = nullptr, *gq = nullptr, *cov = nullptr, *var_allele_off = nullptr;
+    GpCells gp{nullptr, nullptr, nullptr};
 };
 int stage_cells(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, const uint32_t *cov,
-                const uint32_t *var_allele_off, DevCells *d)
+                const uint32_t *var_allele_off, DevCells *d, const GpCells *gp = nullptr)
 {
     RowStage &s = c->stage;
     const size_t cells = 4 * (size_t)n_planes * n_vars;
@@ -3142,6 +3151,13 @@ int stage_cells(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const 
     if (gq) TRY(upload(c, s.gq, gq, cells, &d->gq));
     if (cov) TRY(upload(c, s.cov, cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d->cov));
     if (var_allele_off) TRY(upload(c, s.var_allele_off, var_allele_off, 4 * (n_vars + 1), &d->var_allele_off));
+    if (gp) {
+        void *probs, *var_gt_off, *status;
+        TRY(upload(c, s.probs, gp->probs, 8 * (size_t)n_planes * ((const uint64_t *)gp->var_gt_off)[n_vars], &probs));
+        TRY(upload(c, s.var_gt_off, gp->var_gt_off, 8 * (n_vars + 1), &var_gt_off));
+        TRY(upload(c, s.status, gp->status, (size_t)n_planes * n_vars, &status));
+        d->gp = GpCells{probs, var_gt_off, status};
+    }
     return MG_OK;
 }
 int stage_rows(mg_ctx *c, size_t n_rows, size_t cap, void **d_out, void **d_row_off)
@@ -3162,36 +3178,40 @@ int fetch_rows(mg_ctx *c, int rc, size_t n_rows, const void *d_out, const void *
 }
 
 int format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int masked, int32_t min_gq,
-                        const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
+                        const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out,
+                        const GpCells *gp = nullptr)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off));
+    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off, gp));
     const FmtArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
-                    masked, min_gq};
+                    masked, min_gq, gp ? (const double *)gp->probs : nullptr, gp ? (const u64 *)gp->var_gt_off : nullptr, gp ? (const u8 *)gp->status : nullptr};
     return encode_rows(
         c, c->rp_fmt, "mg_format_calls", n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
-            hipLaunchKernelGGL(fmt_len_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
+            hipLaunchKernelGGL(gp ? fmt_len_kernel<true> : fmt_len_kernel<false>, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
             return MG_OK;
         },
         [&](const unsigned long long *row_off) {
-            hipLaunchKernelGGL(fmt_write_kernel, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off, (char *)d_text_out, (u64)text_cap);
+            hipLaunchKernelGGL(gp ? fmt_write_kernel<true> : fmt_write_kernel<false>, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off, (char *)d_text_out,
+                               (u64)text_cap);
         });
 }
 
 int format_calls_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int masked, int32_t min_gq,
-                      const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
+                      const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out,
+                      const GpCells *gp = nullptr)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off));
+    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off, gp));
     TRY(check_rows_out(c, text_out, text_cap, row_off_out, text_bytes_out));
     DevCells d;
     void *d_text, *d_off;
-    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d));
+    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d, gp));
     TRY(stage_rows(c, n_vars, text_cap, &d_text, &d_off));
-    const int rc = format_calls_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, masked, min_gq, d.cov, d.var_allele_off, d_text, text_cap, d_off, text_bytes_out);
+    const int rc = format_calls_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, masked, min_gq, d.cov, d.var_allele_off, d_text, text_cap, d_off, text_bytes_out,
+                                       gp ? &d.gp : nullptr);
     return fetch_rows(c, rc, n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
 }
 } // namespace
@@ -3219,6 +3239,22 @@ MG_EXPORT int mg_format_calls_masked(mg_ctx *c, size_t n_vars, uint32_t n_planes
                                      uint64_t *row_off_out, uint64_t *text_bytes_out)
 {
     return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, 1, min_gq, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out);
+}
+// the same with the field GP behind every cell's last: the record's likelihoods in VCF genotype order (call_text_kernels.h)
+MG_EXPORT int mg_format_calls_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                        int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                                        const void *d_status, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
+{
+    const GpCells gp{d_probs, d_var_gt_off, d_status};
+    return format_calls_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask != 0, min_gq, d_cov, d_var_allele_off, d_text_out, text_cap, d_row_off_out,
+                               text_bytes_out, &gp);
+}
+MG_EXPORT int mg_format_calls_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                 int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                                 const uint8_t *status, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
+{
+    const GpCells gp{probs, var_gt_off, status};
+    return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out, &gp);
 }
 
 // device milliseconds of the most recent mg_format_calls* (rows_stats)
@@ -3325,44 +3361,81 @@ MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
     return MG_OK;
 }
 
-MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                         int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
-                                         size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
+namespace {
+int encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask, int32_t min_gq,
+                            const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out, size_t out_cap,
+                            void *d_row_off_out, uint64_t *bytes_out, const GpCells *gp = nullptr, int32_t key_gp = 0)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off));
-    if (key_gt < 0 || key_gq < 0 || (d_cov && key_cov < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
+    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off, gp));
+    if (key_gt < 0 || key_gq < 0 || (d_cov && key_cov < 0) || (gp && key_gp < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
     const BcfArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
-                    use_mask, min_gq, key_gt, key_gq, key_cov};
+                    use_mask, min_gq, key_gt, key_gq, key_cov, gp ? (const double *)gp->probs : nullptr, gp ? (const u64 *)gp->var_gt_off : nullptr,
+                    gp ? (const u8 *)gp->status : nullptr, key_gp};
     void *d_types = nullptr; // the records' type codes: what the length pass found, for the write pass
     return encode_rows(
         c, c->rp_bcf, "mg_encode_calls_bcf", n_vars, d_out, out_cap, d_row_off_out, bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
             TRY(scratch(c, c->s_bcf_types, 3 * n_vars, &d_types));
-            hipLaunchKernelGGL(bcf_len_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types, meta);
+            hipLaunchKernelGGL(gp ? bcf_len_kernel<true> : bcf_len_kernel<false>, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types, meta);
             return MG_OK;
         },
         [&](const unsigned long long *row_off) {
-            hipLaunchKernelGGL(bcf_write_kernel, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types, row_off, (char *)d_out, (u64)out_cap);
+            hipLaunchKernelGGL(gp ? bcf_write_kernel<true> : bcf_write_kernel<false>, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types,
+                               row_off, (char *)d_out, (u64)out_cap);
         });
 }
 
+int encode_calls_bcf_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask, int32_t min_gq,
+                          const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out, size_t out_cap,
+                          uint64_t *row_off_out, uint64_t *bytes_out, const GpCells *gp = nullptr, int32_t key_gp = 0)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off, gp));
+    TRY(check_rows_out(c, out, out_cap, row_off_out, bytes_out));
+    DevCells d;
+    void *d_out, *d_off;
+    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d, gp));
+    TRY(stage_rows(c, n_vars, out_cap, &d_out, &d_off));
+    const int rc = encode_calls_bcf_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, use_mask, min_gq, d.cov, d.var_allele_off, key_gt, key_gq, key_cov, d_out,
+                                           out_cap, d_off, bytes_out, gp ? &d.gp : nullptr, key_gp);
+    return fetch_rows(c, rc, n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
+}
+} // namespace
+MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                         int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
+                                         size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
+{
+    return encode_calls_bcf_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, key_gt, key_gq, key_cov, d_out, out_cap,
+                                   d_row_off_out, bytes_out);
+}
 MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
                                   int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
                                   size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
 {
-    const DeviceGuard on_device(c, KEEP);
-    if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off));
-    TRY(check_rows_out(c, out, out_cap, row_off_out, bytes_out));
-    DevCells d;
-    void *d_out, *d_off;
-    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d));
-    TRY(stage_rows(c, n_vars, out_cap, &d_out, &d_off));
-    const int rc = mg_encode_calls_bcf_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, use_mask, min_gq, d.cov, d.var_allele_off, key_gt, key_gq, key_cov, d_out,
-                                              out_cap, d_off, bytes_out);
-    return fetch_rows(c, rc, n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
+    return encode_calls_bcf_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, key_gt, key_gq, key_cov, out, out_cap, row_off_out,
+                                 bytes_out);
+}
+// the same with the float field GP behind the record's last (bcf_kernels.h)
+MG_EXPORT int mg_encode_calls_bcf_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                            int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                                            const void *d_status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap,
+                                            void *d_row_off_out, uint64_t *bytes_out)
+{
+    const GpCells gp{d_probs, d_var_gt_off, d_status};
+    return encode_calls_bcf_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, key_gt, key_gq, key_cov, d_out, out_cap,
+                                   d_row_off_out, bytes_out, &gp, key_gp);
+}
+MG_EXPORT int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                     int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                                     const uint8_t *status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap,
+                                     uint64_t *row_off_out, uint64_t *bytes_out)
+{
+    const GpCells gp{probs, var_gt_off, status};
+    return encode_calls_bcf_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, key_gt, key_gq, key_cov, out, out_cap, row_off_out,
+                                 bytes_out, &gp, key_gp);
 }
 
 // device milliseconds of the most recent mg_encode_calls_bcf* (rows_stats)

@@ -248,7 +248,8 @@ inline void bcf_put_info(std::string &out, size_t shared_at, const BcfHeader &h,
 // rows[g]: group g's block of one record (planes[g] samples, n_fmt fields, each at the type the group chose).  The cohort's block
 // is appended to `out`: per field the key, the descriptor at the widest of the groups' types -- the smallest type that holds the
 // values of all of them -- and the groups' values one behind the other, sign-extended where a group was narrower (GT's missing
-// code 0 and every other value keep their meaning: no group writes a reserved code of its own type).
+// code 0 and every other value keep their meaning: no group writes a reserved code of its own type).  A float field (GP of --gp) has
+// one type: nothing to widen, the groups' values are joined as they are.
 inline void bcf_paste_rows(const std::vector<std::pair<const unsigned char *, size_t>> &rows, const std::vector<uint32_t> &planes, uint32_t n_fmt, std::string &out)
 {
     struct Cur {
@@ -271,13 +272,13 @@ inline void bcf_paste_rows(const std::vector<std::pair<const unsigned char *, si
             p += bcf_width(t);
             return v;
         }
-        void desc(int &t, uint32_t &n)
+        void desc(int &t, uint32_t &n, bool or_float = false)
         {
             need(1);
             const uint32_t d = *p++;
             t = (int)(d & 15);
             n = d >> 4;
-            if (t < 1 || t > 3) throw std::runtime_error("internal: a group's block of the merged output holds a type that is no integer");
+            if ((t < 1 || t > 3) && !(or_float && t == 5)) throw std::runtime_error("internal: a group's block of the merged output holds a type that is no integer");
             if (n == 15) {
                 int t2;
                 uint32_t one;
@@ -298,8 +299,8 @@ inline void bcf_paste_rows(const std::vector<std::pair<const unsigned char *, si
             uint32_t one, n_g;
             cur[g].desc(t1, one);
             const int32_t key_g = cur[g].int_of(t1);
-            cur[g].desc(ts[g], n_g);
-            if (g && (key_g != key || n_g != n)) throw std::runtime_error("internal: the groups' blocks of the merged output disagree");
+            cur[g].desc(ts[g], n_g, true);
+            if (g && (key_g != key || n_g != n || (ts[g] == 5) != (T == 5))) throw std::runtime_error("internal: the groups' blocks of the merged output disagree");
             key = key_g;
             n = n_g;
             T = std::max(T, ts[g]);
@@ -307,7 +308,7 @@ inline void bcf_paste_rows(const std::vector<std::pair<const unsigned char *, si
         bcf_put_typed_int(out, key);
         bcf_put_desc(out, n, T);
         for (size_t g = 0; g < cur.size(); ++g) {
-            const size_t bytes = (size_t)planes[g] * n * bcf_width(ts[g]);
+            const size_t bytes = (size_t)planes[g] * n * (T == 5 ? 4 : bcf_width(ts[g]));
             cur[g].need(bytes);
             if (ts[g] == T) {
                 out.append((const char *)cur[g].p, bytes);

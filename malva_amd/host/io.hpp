@@ -1317,9 +1317,10 @@ inline std::string cleaned_header(const std::vector<std::string> &lines_in, bool
 // header of the multi-sample VCF (call --cohort --merged): the single call's plain header with one column per sample in place of
 // DONOR; verbose: the cells carry a COVS field, declared as FORMAT (INFO stays '.', so neither INFO line of the verbose header);
 // site_tags: INFO carries AC / AN / AF / NS, each declared directly in front of #CHROM unless the panel's header declares that ID;
-// contig_lines (the BCF form of the file, host/bcf_out.hpp): lines that go directly in front of those
+// contig_lines (the BCF form of the file, host/bcf_out.hpp): lines that go directly in front of those; gp (--gp): the cells carry the
+// genotype posteriors, FORMAT GP declared directly behind the COVS line (or where it would stand) unless the panel's header declares it
 inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names, bool site_tags = false,
-                                 const std::vector<std::string> &contig_lines = {})
+                                 const std::vector<std::string> &contig_lines = {}, bool gp = false)
 {
     std::vector<std::string> lines = lines_in;
     const std::string covs = "##FORMAT=<ID=COVS";
@@ -1328,6 +1329,10 @@ inline std::string merged_header(const std::vector<std::string> &lines_in, bool 
     std::string out = cleaned_header(lines, false);
     out.resize(out.size() - std::string("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tDONOR\n").size());
     if (verbose && !declared) out += covs + ",Number=R,Type=Integer,Description=\"Allele coverages\">\n";
+    const std::string gp_id = "##FORMAT=<ID=GP";
+    bool gp_declared = false;
+    for (const auto &l : lines) gp_declared = gp_declared || (l.compare(0, gp_id.size(), gp_id) == 0 && (l[gp_id.size()] == ',' || l[gp_id.size()] == '>'));
+    if (gp && !gp_declared) out += gp_id + ",Number=G,Type=Float,Description=\"Genotype posterior probabilities\">\n";
     for (const auto &l : contig_lines) out += l + "\n";
     if (site_tags) {
         static const char *const tags[4][2] = {{"AC", "A,Type=Integer,Description=\"Allele count in called genotypes, for each ALT allele\""},

@@ -73,7 +73,12 @@ const char *USAGE =
     "                                        manifest order -- the column paste of the per-sample outputs, whatever the grouping;\n"
     "                                        the sample columns are formatted on the GPU.  -o is then optional (both: both are\n"
     "                                        written in one pass).  With -v: INFO stays '.', FORMAT is GT:GQ:COVS and every cell\n"
-    "                                        carries its sample's allele coverages; GTS (the likelihoods) is not carried   [this build]\n"
+    "                                        carries its sample's allele coverages; GTS (the likelihoods) come as GP with --gp [this build]\n"
+    "          --gp                          --merged: every cell carries a further field GP (Number=G, Type=Float; FORMAT is GT:GQ:GP,\n"
+    "                                        with -v GT:GQ:COVS:GP): the posterior probability of every genotype in VCF order -- the\n"
+    "                                        numbers behind GTS= of -v, six decimals -- formatted on the GPU; '.' for a record without\n"
+    "                                        a likelihood list (no coverage, one allele, over-covered).  With and without -v; a cell\n"
+    "                                        masked by --min-gq keeps its GP; in BCF a float32 vector.  The files of -o are not touched [this build]\n"
     "          --min-gq                      --merged: a cell whose GQ is below this integer prints its genotype as missing ('./.',\n"
     "                                        haploid '.'); its :GQ (and :COVS) stay.  The files of -o are not touched        [this build]\n"
     "          --site-tags                   --merged: INFO becomes AC=..;AN=..;AF=..;NS=.. over the called (not masked) cells of the\n"
@@ -122,6 +127,7 @@ struct Options { // argument_parser.hpp:51-66
     int32_t min_gq = 0;
     bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
     std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
+    bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -140,7 +146,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"cohort", no_argument, nullptr, 1003},          {"cohort-group", required_argument, nullptr, 1004},
                                       {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
                                       {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
-                                      {"merged-format", required_argument, nullptr, 1008},
+                                      {"merged-format", required_argument, nullptr, 1008}, {"gp", no_argument, nullptr, 1009},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -205,6 +211,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                 die = true;
             }
             break;
+        case 1009: o.gp = true; break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -236,6 +243,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.merged.empty() && !o.merged_format.empty()) {
         std::cerr << "malva : --merged-format goes with --merged\n";
+        die = true;
+    }
+    if (o.merged.empty() && o.gp) {
+        std::cerr << "malva : --gp goes with --merged\n";
         die = true;
     }
     if (o.cohort && o.gpus > 1) {
@@ -1552,6 +1563,7 @@ int call_main(const Options &o)
     gen.dense_gt = dense_gt;
     const std::string best_default = o.haploid ? "0" : "0/0";
     auto n_gt = [&](uint64_t A) { return o.haploid ? A : A * (A + 1) / 2; };
+    const bool want_probs = o.verbose || o.gp; // the likelihood lists: GTS= of -v, GP of --merged --gp
 
     // One batch: device round trips, then the records' text.  Runs on a worker thread while this thread parses the
     // next batch (the ABI has no thread affinity); batches are handed over one at a time, so output order is kept.
@@ -1567,7 +1579,7 @@ int call_main(const Options &o)
         Timed *t_dev = new Timed("worker: device calls");
         std::unique_lock<std::mutex> device_lock(dev.mu); // (the parsing thread cuts blocks on device 0 meanwhile)
         if (iso.n()) {
-            const size_t n = iso.n(), na = iso.var_allele_off.back(), ng = o.verbose ? iso.var_gt_off.back() : 0;
+            const size_t n = iso.n(), na = iso.var_allele_off.back(), ng = want_probs ? iso.var_gt_off.back() : 0;
             iso.cov.resize(P * na); iso.g1.resize(P * n); iso.g2.resize(P * n); iso.gq.resize(P * n); iso.status.resize(P * n);
             iso.probs.resize(P * ng);
             for (size_t pl = 0; pl < P; ++pl) { // (the fused lone-variant call reads the selected plane)
@@ -1575,12 +1587,12 @@ int call_main(const Options &o)
                 dev.check(mg_call_isolated(dev.ctx, n, iso.pos.data(), iso.var_allele_off.data(), iso.allele_off.data(), iso.pool.data(), iso.pool.size(),
                                            iso.freq.data(), iso.present.data(), iso.flags.data(), o.error_rate, (int)o.max_coverage, o.haploid, iso.cov.data() + pl * na,
                                            iso.g1.data() + pl * n, iso.g2.data() + pl * n, iso.gq.data() + pl * n, iso.status.data() + pl * n,
-                                           o.verbose ? iso.probs.data() + pl * ng : nullptr, o.verbose ? iso.var_gt_off.data() : nullptr),
+                                           want_probs ? iso.probs.data() + pl * ng : nullptr, want_probs ? iso.var_gt_off.data() : nullptr),
                           "mg_call_isolated");
             }
         }
         if (gen.n()) {
-            const size_t n = gen.n(), na = gen.var_allele_off.back(), ng = o.verbose ? gen.var_gt_off.back() : 0;
+            const size_t n = gen.n(), na = gen.var_allele_off.back(), ng = want_probs ? gen.var_gt_off.back() : 0;
             gen.cov.resize(P * na); gen.g1.resize(P * n); gen.g2.resize(P * n); gen.gq.resize(P * n); gen.status.resize(P * n);
             gen.probs.resize(P * ng);
             // panel genotypes of the batch as one [variant][sample] matrix of a1 | a2 << 7 | phased << 14
@@ -1658,7 +1670,7 @@ int call_main(const Options &o)
             for (size_t pl = 0; pl < P; ++pl)
                 dev.check(mg_genotype(dev.ctx, gen.cov.data() + pl * na, gen.freq.data(), gen.var_allele_off.data(), n, o.error_rate, (int)o.max_coverage, o.haploid,
                                       gen.g1.data() + pl * n, gen.g2.data() + pl * n, gen.gq.data() + pl * n, gen.status.data() + pl * n,
-                                      o.verbose ? gen.probs.data() + pl * ng : nullptr, o.verbose ? gen.var_gt_off.data() : nullptr),
+                                      want_probs ? gen.probs.data() + pl * ng : nullptr, want_probs ? gen.var_gt_off.data() : nullptr),
                           "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
         }
         // --merged: the sample columns of both batches as text, made where the genotypes were
@@ -1673,9 +1685,18 @@ int call_main(const Options &o)
                 const size_t bn = b.n();
                 if (!bn) continue;
                 row_off[w].resize(bn + 1);
-                row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0)); // (a guess: the call says what it needs)
-                const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose ? b.var_allele_off.data() : nullptr;
+                row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0) +
+                                   (o.gp ? P * (bn + (bcf_out ? 4 : 9) * (size_t)b.var_gt_off.back()) : 0)); // (a guess: the call says what it needs)
+                const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose || o.gp ? b.var_allele_off.data() : nullptr;
                 dev.check(call_grown(row_text[w], [&](uint64_t *need) {
+                    if (o.gp)
+                        return bcf_out ? mg_encode_calls_bcf_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
+                                                                b.probs.data(), b.var_gt_off.data(), b.status.data(), bcf_hdr.key("GT"), bcf_hdr.key("GQ"),
+                                                                o.verbose ? bcf_hdr.key("COVS") : 0, bcf_hdr.key("GP"), (uint8_t *)row_text[w].data(), row_text[w].size(),
+                                                                row_off[w].data(), need)
+                                       : mg_format_calls_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
+                                                            b.probs.data(), b.var_gt_off.data(), b.status.data(), row_text[w].data(), row_text[w].size(), row_off[w].data(),
+                                                            need);
                     return bcf_out ? mg_encode_calls_bcf(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
                                                          bcf_hdr.key("GT"), bcf_hdr.key("GQ"), o.verbose ? bcf_hdr.key("COVS") : 0,
                                                          (uint8_t *)row_text[w].data(), row_text[w].size(), row_off[w].data(), need)
@@ -1717,7 +1738,7 @@ int call_main(const Options &o)
             std::string &out = outv[outs.size()], &cnt = outv.back();
             std::string plain;
             std::string &rec_out = bcf_direct && bcf_bgzf ? plain : out;
-            const uint32_t n_fmt = o.verbose ? 3 : 2;
+            const uint32_t n_fmt = (o.verbose ? 3 : 2) + (o.gp ? 1 : 0);
             for (const Rec &r : recs) {
                 const int w = r.isolated ? 0 : 1;
                 const char *row = row_text[w].data() + row_off[w][r.slot];
@@ -1742,7 +1763,7 @@ int call_main(const Options &o)
             if (bcf_direct && bcf_bgzf) bgzf_append(plain.data(), plain.size(), out);
         } else if (merged_out) {
             std::string &out = outv[outs.size()], &cnt = outv.back();
-            const char *fixed = o.verbose ? "\tPASS\t.\tGT:GQ:COVS" : "\tPASS\t.\tGT:GQ";
+            const char *fixed = o.verbose ? (o.gp ? "\tPASS\t.\tGT:GQ:COVS:GP" : "\tPASS\t.\tGT:GQ:COVS") : o.gp ? "\tPASS\t.\tGT:GQ:GP" : "\tPASS\t.\tGT:GQ";
             const bool info_here = tags && !cnt_out; // (else INFO stays '.' in the block: the paste pass puts it in)
             for (const Rec &r : recs) {
                 const int w = r.isolated ? 0 : 1;
@@ -1976,14 +1997,14 @@ int call_main(const Options &o)
             if (bcf_out) { // the text header with a ##contig line per reference sequence where the panel's header has none
                 const bool declared = bcf_has_contig_lines(hdr.header_lines);
                 bcf_hdr = bcf_parse_header(merged_header(hdr.header_lines, o.verbose, names, o.site_tags,
-                                                         declared ? std::vector<std::string>() : bcf_contig_lines(refs.names, refs.seqs)),
+                                                         declared ? std::vector<std::string>() : bcf_contig_lines(refs.names, refs.seqs), o.gp),
                                            declared);
                 bcf_samples = samples.size();
                 const std::string head = bcf_hdr.file_head();
                 if (bcf_bgzf) bgzf_append(head.data(), head.size(), merged_head);
                 else merged_head = head;
             } else
-                merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags);
+                merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags, {}, o.gp);
         }
         bool merged_direct = false; // one group: no temporary blocks
         std::vector<uint32_t> group_planes; // the samples of every group, in the order they ran
@@ -2113,7 +2134,7 @@ int call_main(const Options &o)
             const std::vector<uint32_t> &planes = group_planes;
             if (planes.size() != in.size()) throw std::runtime_error("internal: the groups of the merged output and their files disagree");
             const char *short_file = "internal: a group's block of the merged output is short";
-            const uint32_t n_fmt = o.verbose ? 3 : 2;
+            const uint32_t n_fmt = (o.verbose ? 3 : 2) + (o.gp ? 1 : 0);
             std::vector<std::vector<unsigned char>> rows(in.size());
             std::vector<std::pair<const unsigned char *, size_t>> row_of(in.size());
             std::vector<uint32_t> ac, more;

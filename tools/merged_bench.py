@@ -8,6 +8,8 @@ Timed, each the median of --repeats runs with their spread:
                  mg_site_counts and per mg_format_site_info (mg_site_stats) beside them
     merged_bcf   `--cohort --merged PATH --merged-format bcf`, merged_ubcf the same with ubcf: the same two, the bytes written, and
                  the device milliseconds per mg_encode_calls_bcf (mg_bcf_stats) -- on the batches the merged leg formats as text
+    merged_gp    `--cohort --merged PATH --gp`, merged_gp_bcf the same with `--merged-format bcf`: the same two, the bytes written and
+                 the device milliseconds per mg_format_calls_gp / mg_encode_calls_bcf_gp (mg_format_stats / mg_bcf_stats)
     parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick
 The runs alternate (parent, per_sample, merged, parent, ...), so that whatever else the host is doing falls on all three alike.
 merged_equals_paste: the merged file is the column paste of the per-sample files.
@@ -98,13 +100,15 @@ def main():
         legs = {"per_sample": (BIN, ["-o", os.path.join(td, "out")]), "merged": (BIN, ["--merged", os.path.join(td, "merged.vcf")]),
                 "merged_tags": (BIN, ["--merged", os.path.join(td, "merged_tags.vcf"), "--min-gq", str(a.min_gq), "--site-tags"]),
                 "merged_bcf": (BIN, ["--merged", os.path.join(td, "merged.bcf"), "--merged-format", "bcf"]),
-                "merged_ubcf": (BIN, ["--merged", os.path.join(td, "merged.ubcf"), "--merged-format", "ubcf"])}
+                "merged_ubcf": (BIN, ["--merged", os.path.join(td, "merged.ubcf"), "--merged-format", "ubcf"]),
+                "merged_gp": (BIN, ["--merged", os.path.join(td, "merged_gp.vcf"), "--gp"]),
+                "merged_gp_bcf": (BIN, ["--merged", os.path.join(td, "merged_gp.bcf"), "--gp", "--merged-format", "bcf"])}
         if a.parent_bin:
             legs = dict({"parent": (a.parent_bin, ["-o", os.path.join(td, "out_parent")])}, **legs)
         res = {leg: {"wall_s": [], "panel_pass_s": []} for leg in legs}
-        fmt_ms, fmt_calls = {"merged": [], "merged_tags": []}, 0
+        fmt_ms, fmt_calls = {"merged": [], "merged_tags": [], "merged_gp": []}, 0
         site_ms, site_calls = [], [0, 0]
-        bcf_ms, bcf_calls = {"merged_bcf": [], "merged_ubcf": []}, 0
+        bcf_ms, bcf_calls = {"merged_bcf": [], "merged_ubcf": [], "merged_gp_bcf": []}, 0
 
         def run(leg):
             b, dest = legs[leg]
@@ -142,6 +146,7 @@ def main():
         out["format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms["merged"]]) for i, name in enumerate(("length", "scan", "write"))}
         out["tags_min_gq"] = a.min_gq
         out["tags_format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms["merged_tags"]]) for i, name in enumerate(("length", "scan", "write"))}
+        out["gp_format_ms_per_call"] = {name: stat([x[i] for x in fmt_ms["merged_gp"]]) for i, name in enumerate(("length", "scan", "write"))}
         out["site_calls_per_run"] = {"count": site_calls[0], "info": site_calls[1]}
         out["site_ms_per_call"] = {name: stat([x[i] for x in site_ms]) for i, name in enumerate(("count", "info"))}
         out["encode_calls_per_run"] = bcf_calls
@@ -149,6 +154,8 @@ def main():
             out[leg + "_encode_ms_per_call"] = {name: stat([x[i] for x in bcf_ms[leg]]) for i, name in enumerate(("length", "scan", "write"))}
         out["merged_bcf_bytes"] = os.path.getsize(os.path.join(td, "merged.bcf"))
         out["merged_ubcf_bytes"] = os.path.getsize(os.path.join(td, "merged.ubcf"))
+        out["merged_gp_bytes"] = os.path.getsize(os.path.join(td, "merged_gp.vcf"))
+        out["merged_gp_bcf_bytes"] = os.path.getsize(os.path.join(td, "merged_gp.bcf"))
         out["merged_tags_bytes"] = os.path.getsize(os.path.join(td, "merged_tags.vcf"))
         out["merged_bytes"] = os.path.getsize(os.path.join(td, "merged.vcf"))
         out["per_sample_bytes"] = sum(os.path.getsize(os.path.join(td, "out", "s%02d.vcf" % i)) for i in range(S))
