@@ -553,6 +553,40 @@ int mg_format_site_info_device(mg_ctx *ctx, size_t n_vars, const void *d_ac, con
                                void *d_row_off_out, uint64_t *text_bytes_out);
 int mg_site_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- the pair table of a multi-sample call set --------------------------------------
+ * For every pair of planes (samples) and every record where both are called, the joint count of their genotypes: a 3 x 3 table
+ * per pair, from which IBS0/1/2, discordance and a KING-style kinship follow.  There is no reference call to cite: the reference
+ * genotypes one individual per run and has nothing that looks across samples.
+ * mg_pack_dosage: the cells of a batch as bit planes.  gt1 / gt2 / gq, n_planes (1..64) and CALLED exactly as for mg_site_counts:
+ * [n_planes][n_vars] int32, plane-major; gt2 is not read in haploid mode and may be NULL, gq not unless use_mask; a cell is called
+ * unless use_mask != 0 and its gq < min_gq.  var_allele_off ([n_vars + 1]) is required.  planes_out is uint64_t
+ * [n_planes][3][W], W = (n_vars + 63) / 64: bit v & 63 of word v >> 6 of planes_out[p][d] is set exactly when record v has two
+ * alleles (var_allele_off[v + 1] - var_allele_off[v] == 2), the cell (p, v) is called, every allele index the mode reads is 0 or 1,
+ * and the cell's dosage is d -- gt1 + gt2 in diploid mode, 2 * gt1 in haploid mode (the allele stands as a homozygote: class 1 is
+ * empty).  Every other bit is 0, the bits of the last word at and beyond n_vars and every bit of a record that is not biallelic
+ * included: a cell has at most one of its three bits set.  Every word of the output is written, the caller need not clear it;
+ * n_vars == 0 is legal and writes nothing.  The host form synchronises; the device form is asynchronous on the context's stream.
+ * mg_pair_counts: planes_a is [n_a][3][n_words], planes_b [n_b][3][n_words], as mg_pack_dosage lays them out (n_a, n_b 1..64).
+ * counts is uint64_t [n_a][n_b][9]: counts[(i * n_b + j) * 9 + 3 * da + db] = the sum over w of
+ * popcount(A[i][da][w] & B[j][db][w]).  planes_b == NULL: B is A, n_b must equal n_a, and the whole square is filled -- the
+ * result is symmetric under swapping i, j and transposing the 3 x 3 table.  accumulate != 0 adds to what counts holds (the
+ * batches of a pass, the groups of a cohort larger than 64 are summed this way); accumulate == 0 overwrites all n_a * n_b * 9
+ * entries, so n_words == 0 then zeroes them.  n_a or n_b out of range, a NULL counts, a NULL planes_a with n_words > 0,
+ * n_b != n_a with a NULL planes_b: MG_ERR_ARG.  The host form synchronises; the device form is asynchronous on the context's stream.
+ * mg_pairs_stats (waits): ms_out[2], device milliseconds of the most recent mg_pack_dosage* and of the most recent
+ * mg_pair_counts*; 0 for a kind not called yet, MG_ERR_STATE when neither was.
+ * These calls keep their device copies and events apart from the encoders' and the site tags': a call of one kind between two of
+ * another changes nothing in either. */
+int mg_pack_dosage(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                   int32_t min_gq, const uint32_t *var_allele_off, uint64_t *planes_out);
+int mg_pack_dosage_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                          int32_t min_gq, const void *d_var_allele_off, void *d_planes_out);
+int mg_pair_counts(mg_ctx *ctx, size_t n_words, const uint64_t *planes_a, uint32_t n_a, const uint64_t *planes_b, uint32_t n_b, int accumulate,
+                   uint64_t *counts);
+int mg_pair_counts_device(mg_ctx *ctx, size_t n_words, const void *d_planes_a, uint32_t n_a, const void *d_planes_b, uint32_t n_b, int accumulate,
+                          void *d_counts);
+int mg_pairs_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- the sample columns of a multi-sample BCF --------------------------------------
  * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
  * parity with htslib unpinned).  Arrays, n_planes (1..64), the host and _device forms, the stream behaviour and the buffer

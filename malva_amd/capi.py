@@ -119,6 +119,11 @@ def lib():
         "mg_format_site_info": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
         "mg_format_site_info_device": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
         "mg_site_stats": [vp, vp],
+        "mg_pack_dosage": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp],
+        "mg_pack_dosage_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp],
+        "mg_pair_counts": [vp, sz, vp, u32, vp, u32, it, vp],
+        "mg_pair_counts_device": [vp, sz, vp, u32, vp, u32, it, vp],
+        "mg_pairs_stats": [vp, vp],
         "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
@@ -186,7 +191,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_cohort_begin", "mg_cohort_select", "mg_cohort_end", "mg_cohort_info", "mg_cover_blocks_cohort_device", "mg_cohort_stats", "mg_cover_blocks_cohort",
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
-            "mg_format_site_info_device", "mg_site_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
+            "mg_pairs_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -739,6 +745,42 @@ class Context:
         """-> device ms of the most recent site_counts and of the most recent format_site_info"""
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_site_stats(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    # the pair table of a multi-sample call set
+    def pack_dosage(self, gt1, gt2, gq, haploid, var_allele_off, min_gq=None, out=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 -> uint64 [planes, 3, W], W = (n_vars + 63) // 64: bit v & 63 of word v >> 6 of
+        [p, d] is set when (p, v) is a called cell of a biallelic record with allele indexes in {0, 1} and dosage d (haploid:
+        2 * gt1).  min_gq: cells whose gq is below it are not called.  out: the array to fill (every word is overwritten)."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q, vo = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32), a(var_allele_off, np.uint32)
+        planes, n = g1.shape
+        if out is None:
+            out = np.zeros((planes, 3, (n + 63) // 64), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (planes, 3, (n + 63) // 64)
+        self._ck(self._L.mg_pack_dosage(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(vo), _p(out)))
+        return out
+
+    def pair_counts(self, planes_a, planes_b=None, counts=None, overwrite=False):
+        """planes_a [n_a, 3, W], planes_b [n_b, 3, W] (None: B is A) as pack_dosage lays them out -> uint64 [n_a, n_b, 3, 3]:
+        [i, j, da, db] = the bits set in both A[i, da] and B[j, db].  counts given: the sums are added to it (in place) unless
+        overwrite."""
+        A = np.ascontiguousarray(planes_a, dtype=np.uint64)
+        B = None if planes_b is None else np.ascontiguousarray(planes_b, dtype=np.uint64)
+        n_a, _, W = A.shape
+        n_b = n_a if B is None else B.shape[0]
+        assert B is None or B.shape[1:] == (3, W)
+        acc = counts is not None and not overwrite
+        if counts is None:
+            counts = np.zeros((n_a, n_b, 3, 3), dtype=np.uint64)
+        assert counts.dtype == np.uint64 and counts.flags.c_contiguous and counts.shape == (n_a, n_b, 3, 3)
+        self._ck(self._L.mg_pair_counts(self.h, W, _p(A), n_a, _p(B), n_b, int(acc), _p(counts)))
+        return counts
+
+    def pairs_stats(self):
+        """-> device ms of the most recent pack_dosage and of the most recent pair_counts"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.mg_pairs_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
 
     # the sample columns of a multi-sample BCF

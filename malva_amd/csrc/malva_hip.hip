@@ -40,6 +40,7 @@ constexpr int TPB = 256;
 #include "gt_text_kernels.h"
 #include "call_text_kernels.h"
 #include "site_tags_kernels.h"
+#include "pair_kernels.h"
 #include "bcf_kernels.h"
 #include "reads_kernels.h"
 
@@ -160,6 +161,13 @@ struct mg_ctx {
     hipEvent_t ev_cnt[2] = {nullptr, nullptr};        // mg_site_counts*: start and end of the latest call
     bool cnt_stats_valid = false;
     RowStage stage;
+    // the pair table (mg_pack_dosage*, mg_pair_counts*): the events of each kind's latest call and the host forms' device copies, their
+    // own -- no encoder and no site-tag call touches them, and these touch nothing of theirs
+    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_pair[2] = {nullptr, nullptr};
+    bool pack_stats_valid = false, pair_stats_valid = false;
+    struct PairStage {
+        Scratch gt1, gt2, gq, var_allele_off, planes, pa, pb, counts;
+    } pstage;
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -700,6 +708,10 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
             if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->ev_cnt)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev_pack[0], c->ev_pack[1], c->ev_pair[0], c->ev_pair[1]})
+        if (e) hipEventDestroy(e);
+    for (Scratch *q : {&c->pstage.gt1, &c->pstage.gt2, &c->pstage.gq, &c->pstage.var_allele_off, &c->pstage.planes, &c->pstage.pa, &c->pstage.pb, &c->pstage.counts})
+        hipFree(q->p);
     for (Scratch *q : {&c->rp_fmt.len, &c->rp_fmt.meta, &c->rp_info.len, &c->rp_info.meta, &c->rp_bcf.len, &c->rp_bcf.meta, &c->s_bcf_types, &c->stage.gt1, &c->stage.gt2,
                        &c->stage.gq, &c->stage.cov, &c->stage.var_allele_off, &c->stage.ac, &c->stage.ns, &c->stage.out, &c->stage.row_off, &c->stage.probs,
                        &c->stage.var_gt_off, &c->stage.status})
@@ -3358,6 +3370,135 @@ MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
     }
     if (c->rp_info.valid) TRY(rows_stats(c, c->rp_info, "mg_format_site_info", info));
     ms_out[1] = info[0] + info[1] + info[2];
+    return MG_OK;
+}
+
+// ---- the pair table of a multi-sample call set (pair_kernels.h) ------------------------------------------------------------------------
+MG_EXPORT int mg_pack_dosage_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                    int32_t min_gq, const void *d_var_allele_off, void *d_planes_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cells(c, "mg_pack_dosage", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, nullptr, nullptr));
+    if (!d_var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_dosage: var_allele_off is required");
+    if (n_vars && !d_planes_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_pack_dosage: more than 2^32 - 1 records in one call");
+    for (auto &e : c->ev_pack)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->pack_stats_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev_pack[0], c->stream));
+    if (n_vars) {
+        const u64 n_words = ((u64)n_vars + 63) / 64;
+        const PackArgs a{(u64)n_vars, n_words, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u32 *)d_var_allele_off};
+        hipLaunchKernelGGL(pack_dosage_kernel, dim3((unsigned)((n_words + PACK_TPB / 64 - 1) / (PACK_TPB / 64)), n_planes), dim3(PACK_TPB), 0, c->stream, a,
+                           (unsigned long long *)d_planes_out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_pack[1], c->stream));
+    c->pack_stats_valid = true;
+    return MG_OK;
+}
+
+MG_EXPORT int mg_pack_dosage(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                             int32_t min_gq, const uint32_t *var_allele_off, uint64_t *planes_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cells(c, "mg_pack_dosage", n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, nullptr, nullptr));
+    if (!var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_dosage: var_allele_off is required");
+    if (n_vars && !planes_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t cells = 4 * (size_t)n_planes * n_vars, out_bytes = 8 * (size_t)n_planes * 3 * ((n_vars + 63) / 64);
+    void *d1, *d2 = nullptr, *dq = nullptr, *dv, *d_out;
+    TRY(upload(c, c->pstage.gt1, gt1, cells, &d1));
+    if (!haploid) TRY(upload(c, c->pstage.gt2, gt2, cells, &d2));
+    if (use_mask) TRY(upload(c, c->pstage.gq, gq, cells, &dq));
+    TRY(upload(c, c->pstage.var_allele_off, var_allele_off, 4 * (n_vars + 1), &dv));
+    TRY(scratch(c, c->pstage.planes, out_bytes ? out_bytes : 1, &d_out));
+    TRY(mg_pack_dosage_device(c, n_vars, n_planes, haploid, d1, d2, dq, use_mask, min_gq, dv, d_out));
+    if (out_bytes) HIP_TRY(c, hipMemcpyAsync(planes_out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+namespace {
+int check_pairs(mg_ctx *c, size_t n_words, const void *a, uint32_t n_a, const void *b, uint32_t n_b, const void *counts)
+{
+    if (n_a < 1 || n_a > 64 || n_b < 1 || n_b > 64) return fail(c, MG_ERR_ARG, "mg_pair_counts: n_a and n_b are 1..64");
+    if (!b && n_b != n_a) return fail(c, MG_ERR_ARG, "mg_pair_counts: planes_b == NULL means B is A: n_b must equal n_a");
+    if (!counts || (n_words && !a)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_words >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_pair_counts: more than 2^32 - 1 words in one call");
+    return MG_OK;
+}
+// The word axis is cut into runs, one workgroup per tile of pairs and run: as many runs as give about PAIR_TARGET_WGS workgroups -- with
+// one tile (2 planes x 1e7 records) all the parallelism comes from here --, none longer than PAIR_MAX_RUN (the 32-bit sums)
+constexpr u64 PAIR_TARGET_WGS = 2048;
+u64 pair_count_plan(u64 n_words, u32 tiles, u64 *n_runs)
+{
+    const u64 chunks = (n_words + PAIR_CHUNK - 1) / PAIR_CHUNK;
+    u64 runs = std::min<u64>(chunks, std::max<u64>(1, PAIR_TARGET_WGS / tiles));
+    runs = std::max<u64>(runs, (n_words + PAIR_MAX_RUN - 1) / PAIR_MAX_RUN);
+    const u64 run = (chunks + runs - 1) / runs * PAIR_CHUNK; // (whole chunks; at most PAIR_MAX_RUN, itself a multiple of PAIR_CHUNK)
+    *n_runs = (n_words + run - 1) / run;
+    return run;
+}
+} // namespace
+
+MG_EXPORT int mg_pair_counts_device(mg_ctx *c, size_t n_words, const void *d_planes_a, uint32_t n_a, const void *d_planes_b, uint32_t n_b, int accumulate, void *d_counts)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_pairs(c, n_words, d_planes_a, n_a, d_planes_b, n_b, d_counts));
+    for (auto &e : c->ev_pair)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->pair_stats_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev_pair[0], c->stream));
+    if (!accumulate) HIP_TRY(c, hipMemsetAsync(d_counts, 0, 8 * (size_t)n_a * n_b * 9, c->stream));
+    if (n_words) {
+        const u32 tiles_i = (n_a + PAIR_TILE - 1) / PAIR_TILE, tiles_j = (n_b + PAIR_TILE - 1) / PAIR_TILE;
+        const bool symmetric = !d_planes_b;
+        u64 n_runs = 0;
+        const u64 run = pair_count_plan((u64)n_words, symmetric ? tiles_i * (tiles_i + 1) / 2 : tiles_i * tiles_j, &n_runs);
+        const PairArgs a{(u64)n_words, run, (const unsigned long long *)d_planes_a, (const unsigned long long *)(symmetric ? d_planes_a : d_planes_b), n_a, n_b, symmetric};
+        hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)n_runs, tiles_j, tiles_i), dim3(PAIR_TPB), 0, c->stream, a, (unsigned long long *)d_counts);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_pair[1], c->stream));
+    c->pair_stats_valid = true;
+    return MG_OK;
+}
+
+MG_EXPORT int mg_pair_counts(mg_ctx *c, size_t n_words, const uint64_t *planes_a, uint32_t n_a, const uint64_t *planes_b, uint32_t n_b, int accumulate, uint64_t *counts)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_pairs(c, n_words, planes_a, n_a, planes_b, n_b, counts));
+    const size_t count_bytes = 8 * (size_t)n_a * n_b * 9;
+    void *da, *db = nullptr, *d_counts;
+    TRY(upload(c, c->pstage.pa, planes_a, 8 * (size_t)n_a * 3 * n_words, &da));
+    if (planes_b) TRY(upload(c, c->pstage.pb, planes_b, 8 * (size_t)n_b * 3 * n_words, &db));
+    TRY(scratch(c, c->pstage.counts, count_bytes, &d_counts));
+    if (accumulate) HIP_TRY(c, hipMemcpyAsync(d_counts, counts, count_bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(mg_pair_counts_device(c, n_words, da, n_a, db, n_b, accumulate, d_counts));
+    HIP_TRY(c, hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds (waits for them): ms_out[0] the most recent mg_pack_dosage*, [1] the most recent mg_pair_counts*; 0 where there was none
+MG_EXPORT int mg_pairs_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = ms_out[1] = 0.f; // (0: none of that kind yet)
+    if (!c->pack_stats_valid && !c->pair_stats_valid) return fail(c, MG_ERR_STATE, "no mg_pack_dosage or mg_pair_counts yet");
+    if (c->pack_stats_valid) {
+        HIP_TRY(c, hipEventSynchronize(c->ev_pack[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms_out[0], c->ev_pack[0], c->ev_pack[1]));
+    }
+    if (c->pair_stats_valid) {
+        HIP_TRY(c, hipEventSynchronize(c->ev_pair[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms_out[1], c->ev_pair[0], c->ev_pair[1]));
+    }
     return MG_OK;
 }
 

@@ -92,6 +92,11 @@ const char *USAGE =
     "                                        one with some must name every CHROM.  Combines with -1, -v (FORMAT COVS), --min-gq,\n"
     "                                        --site-tags and -o.  Written from the published layout, like the BCF reader: no file\n"
     "                                        written by bcftools was available to compare with (format UNPINNED)          [this build]\n"
+    "          --pairs                       --cohort: PATH receives a tab-separated table, one line per unordered pair of samples in\n"
+    "                                        manifest order: over the biallelic records where both are called (--min-gq applies) the\n"
+    "                                        joint counts N00..N22 of their dosages (0, 1, 2 ALT copies; haploid: 0 or 2), their sum N,\n"
+    "                                        IBS0/1/2 and KING = (N11 - 2 IBS0) / (het A + het B), '.' without heterozygotes.  Counted on\n"
+    "                                        the GPU, whatever the grouping; beside -o and/or --merged                       [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -128,6 +133,7 @@ struct Options { // argument_parser.hpp:51-66
     bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
     std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
     bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
+    std::string pairs;      // --pairs: the table of pairwise genotype sharing
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -147,6 +153,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
                                       {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
                                       {"merged-format", required_argument, nullptr, 1008}, {"gp", no_argument, nullptr, 1009},
+                                      {"pairs", required_argument, nullptr, 1010},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -212,6 +219,13 @@ bool parse_arguments(int argc, char **argv, Options &o)
             }
             break;
         case 1009: o.gp = true; break;
+        case 1010:
+            o.pairs = optarg;
+            if (o.pairs.empty()) {
+                std::cerr << "malva : --pairs takes a path\n";
+                die = true;
+            }
+            break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -251,6 +265,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.cohort && o.gpus > 1) {
         std::cerr << "malva : --cohort does not combine with --gpus > 1\n";
+        die = true;
+    }
+    if (!o.cohort && !o.pairs.empty()) {
+        std::cerr << "malva : --pairs goes with --cohort\n";
         die = true;
     }
     if (!o.cohort && (!o.out_dir.empty() || o.cohort_group)) {
@@ -1503,6 +1521,14 @@ int call_main(const Options &o)
     size_t format_calls = 0;
     double site_ms[2] = {0, 0};               // --site-tags: device milliseconds of the mg_site_counts and of the mg_format_site_info
     size_t site_calls[2] = {0, 0};
+    // --pairs: a group's pair table so far -- [planes][planes][9], summed batch by batch (mg_pair_counts, B = A) -- and, when the cohort runs
+    // as several groups, the file that receives the packed words of the group's batches for the pass over pairs of groups
+    struct PairsRun {
+        std::vector<uint64_t> counts;
+        FILE *pack_out = nullptr;
+    };
+    double pairs_ms[2] = {0, 0};              // device milliseconds of the mg_pack_dosage and of the mg_pair_counts
+    size_t pairs_calls[2] = {0, 0};
     // --merged-format bcf | ubcf: the merged file as BCF2 (host/bcf_out.hpp), a record's per-sample block encoded by mg_encode_calls_bcf
     const bool bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", bcf_bgzf = o.merged_format == "bcf";
     BcfHeader bcf_hdr;
@@ -1550,7 +1576,11 @@ int call_main(const Options &o)
     // --site-tags: the records' allele counts over the group's planes are made beside the columns (mg_site_counts); cnt_out == nullptr: the
     // group is the cohort and INFO is made from them at once (mg_format_site_info), else they go to cnt_out, per record in output order the
     // u32s n_alleles, ns, ac[n_alleles], for the paste pass to sum over the groups.
-    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed, FILE *cnt_out) -> size_t {
+    // pairs (--pairs): every batch's cells are packed into dosage bit planes (mg_pack_dosage) while the batch is in hand and counted against
+    // themselves into pairs->counts; pairs->pack_out, when set, receives per batch and stream -- the lone records', then the others' -- the u64s
+    // stream, n_records and the [planes][3][W] words.
+    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed, FILE *cnt_out,
+                        PairsRun *pairs) -> size_t {
     const size_t P = planes ? planes : 1;
 
     // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
@@ -1727,15 +1757,39 @@ int call_main(const Options &o)
                 if (!cnt_out && !bcf_out) site_info(dev, bn, site_ac[w].data(), site_ns[w].data(), b.var_allele_off.data(), info_text[w], info_off[w]);
             }
         }
+        std::string pack_bytes;
+        if (pairs) {
+            Timed t_pairs("worker: pair table (mg_pack_dosage, mg_pair_counts)");
+            std::vector<uint64_t> words;
+            for (int w = 0; w < 2; ++w) {
+                Batch &b = w ? gen : iso;
+                const size_t bn = b.n(), W = (bn + 63) / 64;
+                if (!bn) continue;
+                words.resize(P * 3 * W);
+                dev.check(mg_pack_dosage(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.var_allele_off.data(),
+                                         words.data()),
+                          "mg_pack_dosage");
+                dev.check(mg_pair_counts(dev.ctx, W, words.data(), (uint32_t)P, nullptr, (uint32_t)P, 1, pairs->counts.data()), "mg_pair_counts");
+                float ms[2] = {0, 0};
+                dev.check(mg_pairs_stats(dev.ctx, ms), "mg_pairs_stats");
+                for (int i = 0; i < 2; ++i) pairs_ms[i] += ms[i], ++pairs_calls[i];
+                if (pairs->pack_out) {
+                    const uint64_t head[2] = {(uint64_t)w, (uint64_t)bn};
+                    pack_bytes.append((const char *)head, 16);
+                    pack_bytes.append((const char *)words.data(), 8 * words.size());
+                }
+            }
+        }
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
-        std::vector<std::string> outv(outs.size() + 2); // (the last two: the merged block, the records' counts for cnt_out)
+        std::vector<std::string> outv(outs.size() + 3); // (the last three: the merged block, the records' counts for cnt_out, the packed words for pairs->pack_out)
+        outv[outs.size() + 2] = std::move(pack_bytes);
         if (merged_out && bcf_out) {
             // BCF: one group -- whole records (l_shared, l_indiv, the shared block with INFO from the counts, the device's row), compressed
             // here when BGZF; several -- per record the first group's shared block without INFO and every group's row, each behind its
             // u32 length, for the paste pass to widen and join (the counts go to cnt_out as for text)
-            std::string &out = outv[outs.size()], &cnt = outv.back();
+            std::string &out = outv[outs.size()], &cnt = outv[outs.size() + 1];
             std::string plain;
             std::string &rec_out = bcf_direct && bcf_bgzf ? plain : out;
             const uint32_t n_fmt = (o.verbose ? 3 : 2) + (o.gp ? 1 : 0);
@@ -1762,7 +1816,7 @@ int call_main(const Options &o)
             }
             if (bcf_direct && bcf_bgzf) bgzf_append(plain.data(), plain.size(), out);
         } else if (merged_out) {
-            std::string &out = outv[outs.size()], &cnt = outv.back();
+            std::string &out = outv[outs.size()], &cnt = outv[outs.size() + 1];
             const char *fixed = o.verbose ? (o.gp ? "\tPASS\t.\tGT:GQ:COVS:GP" : "\tPASS\t.\tGT:GQ:COVS") : o.gp ? "\tPASS\t.\tGT:GQ:GP" : "\tPASS\t.\tGT:GQ";
             const bool info_here = tags && !cnt_out; // (else INFO stays '.' in the block: the paste pass puts it in)
             for (const Rec &r : recs) {
@@ -1842,7 +1896,9 @@ int call_main(const Options &o)
                 if (fwrite(text[pl].data(), 1, text[pl].size(), outs[pl]) != text[pl].size()) throw std::runtime_error("cannot write the output");
             const std::string &block = text[outs.size()];
             if (merged_out && fwrite(block.data(), 1, block.size(), merged_out) != block.size()) throw std::runtime_error("cannot write the merged output");
-            if (cnt_out && fwrite(text.back().data(), 1, text.back().size(), cnt_out) != text.back().size()) throw std::runtime_error("cannot write the merged output's counts");
+            const std::string &cnt = text[outs.size() + 1], &pack = text[outs.size() + 2];
+            if (cnt_out && fwrite(cnt.data(), 1, cnt.size(), cnt_out) != cnt.size()) throw std::runtime_error("cannot write the merged output's counts");
+            if (pairs && pairs->pack_out && fwrite(pack.data(), 1, pack.size(), pairs->pack_out) != pack.size()) throw std::runtime_error("cannot write the pair table's packed calls");
         }
     };
     auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
@@ -1964,7 +2020,7 @@ int call_main(const Options &o)
     }; // vcf_pass
 
     size_t n = 0;
-    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr);
+    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr, nullptr);
     else {
         if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
         Device &dev = devs[0];
@@ -1986,6 +2042,24 @@ int call_main(const Options &o)
                 if (!part.empty()) unlink(part.c_str());
             }
         } merged;
+        // --pairs: the table of the whole cohort, [samples][samples][9], of which the entries i < j are filled: a group's own pairs when its
+        // panel pass ends, the pairs across two groups by the pass behind the last group, from the groups' packed words (PATH.gN.pack.part:
+        // 3 bits per cell).  The table is written as PATH.part and renamed; whatever is left of these files goes when this frame is left.
+        struct PairFiles {
+            std::vector<std::string> pack_paths;
+            std::string part;
+            FILE *open = nullptr;
+            ~PairFiles()
+            {
+                if (open) fclose(open);
+                for (const auto &p : pack_paths) unlink(p.c_str());
+                if (!part.empty()) unlink(part.c_str());
+            }
+        } pair_files;
+        const bool want_pairs = !o.pairs.empty();
+        const size_t S = samples.size();
+        std::vector<uint64_t> pair_table(want_pairs ? S * S * 9 : 0, 0);
+        std::vector<size_t> group_first; // the first sample of every group
         const bool merged_stdout = o.merged == "-";
         const std::string merged_tmp_base = !merged_stdout ? o.merged : std::string(getenv("TMPDIR") && *getenv("TMPDIR") ? getenv("TMPDIR") : "/tmp") + "/malva-geno." + std::to_string((long)getpid()) + ".merged";
         std::string merged_head;
@@ -2021,6 +2095,17 @@ int call_main(const Options &o)
                 dev.check(rc, "mg_cohort_begin");
             }
             group_planes.push_back((uint32_t)g);
+            group_first.push_back(s0);
+            PairsRun pairs_run;
+            if (want_pairs) {
+                pairs_run.counts.assign(g * g * 9, 0);
+                if (g != S) { // (several groups: their pairs across need every group's calls again)
+                    const std::string path = o.pairs + ".g" + std::to_string(pair_files.pack_paths.size()) + ".pack.part";
+                    pair_files.pack_paths.push_back(path);
+                    pairs_run.pack_out = pair_files.open = fopen(path.c_str(), "wb");
+                    if (!pair_files.open) throw std::runtime_error("cannot write " + path);
+                }
+            }
             {
                 Timed t("cohort: table scans");
                 for (size_t i = 0; i < g; ++i) {
@@ -2079,8 +2164,15 @@ int call_main(const Options &o)
                     start_vcf(*again);
                     if (!again->ok()) throw std::runtime_error(again->error);
                 }
-                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0, merged.cnt_open);
+                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0, merged.cnt_open, want_pairs ? &pairs_run : nullptr);
             }
+            if (pair_files.open) {
+                FILE *closing = pair_files.open;
+                pair_files.open = nullptr;
+                if (fclose(closing) != 0) throw std::runtime_error("cannot write the pair table's packed calls");
+            }
+            for (size_t i = 0; want_pairs && i < g; ++i)
+                for (size_t j = i + 1; j < g; ++j) std::copy_n(&pairs_run.counts[(i * g + j) * 9], 9, &pair_table[((s0 + i) * S + s0 + j) * 9]);
             if (merged.cnt_open) {
                 FILE *closing = merged.cnt_open;
                 merged.cnt_open = nullptr;
@@ -2294,6 +2386,75 @@ int call_main(const Options &o)
         if (!o.merged.empty() && !merged_stdout) {
             if (rename(merged.part.c_str(), o.merged.c_str()) != 0) throw std::runtime_error("cannot write " + o.merged);
             merged.part.clear();
+        }
+        if (want_pairs) {
+            Timed t("cohort: pair pass");
+            // the pairs across groups: every group saw the records in the same order and cut them into the same batches -- the panel pass
+            // depends on the panel and on MALVA_GENO_BATCH alone -- so batch b of group gi and batch b of group gj hold the same records
+            const char *short_file = "internal: a group's packed calls for the pair table are short";
+            std::vector<uint64_t> words_a, words_b, cross;
+            for (size_t gi = 0; gi < pair_files.pack_paths.size(); ++gi)
+                for (size_t gj = gi + 1; gj < pair_files.pack_paths.size(); ++gj) {
+                    const size_t ga = group_planes[gi], gb = group_planes[gj];
+                    FILE *fa = fopen(pair_files.pack_paths[gi].c_str(), "rb"), *fb = fopen(pair_files.pack_paths[gj].c_str(), "rb");
+                    struct Close {
+                        FILE *a, *b;
+                        ~Close()
+                        {
+                            if (a) fclose(a);
+                            if (b) fclose(b);
+                        }
+                    } close_both{fa, fb};
+                    if (!fa || !fb) throw std::runtime_error("cannot read " + pair_files.pack_paths[fa ? gj : gi]);
+                    cross.assign(ga * gb * 9, 0);
+                    uint64_t head_a[2], head_b[2];
+                    while (fread(head_a, 8, 2, fa) == 2) {
+                        if (fread(head_b, 8, 2, fb) != 2 || head_b[0] != head_a[0] || head_b[1] != head_a[1]) throw std::runtime_error(short_file);
+                        const size_t W = (size_t)((head_a[1] + 63) / 64);
+                        words_a.resize(ga * 3 * W);
+                        words_b.resize(gb * 3 * W);
+                        if (fread(words_a.data(), 8, words_a.size(), fa) != words_a.size() || fread(words_b.data(), 8, words_b.size(), fb) != words_b.size())
+                            throw std::runtime_error(short_file);
+                        dev.check(mg_pair_counts(dev.ctx, W, words_a.data(), (uint32_t)ga, words_b.data(), (uint32_t)gb, 1, cross.data()), "mg_pair_counts");
+                        float ms[2] = {0, 0};
+                        dev.check(mg_pairs_stats(dev.ctx, ms), "mg_pairs_stats");
+                        pairs_ms[1] += ms[1];
+                        ++pairs_calls[1];
+                    }
+                    if (fread(head_b, 8, 2, fb) != 0) throw std::runtime_error(short_file);
+                    for (size_t i = 0; i < ga; ++i)
+                        std::copy_n(&cross[i * gb * 9], gb * 9, &pair_table[((group_first[gi] + i) * S + group_first[gj]) * 9]);
+                }
+            // the text: the division and the formatting are all the host does
+            std::string text = "#A\tB\tN\tN00\tN01\tN02\tN10\tN11\tN12\tN20\tN21\tN22\tIBS0\tIBS1\tIBS2\tKING\n";
+            char num[64];
+            for (size_t i = 0; i < S; ++i)
+                for (size_t j = i + 1; j < S; ++j) {
+                    const uint64_t *c = &pair_table[(i * S + j) * 9];
+                    uint64_t total = 0;
+                    for (int k = 0; k < 9; ++k) total += c[k];
+                    const uint64_t ibs2 = c[0] + c[4] + c[8], ibs0 = c[2] + c[6], het = (c[3] + c[4] + c[5]) + (c[1] + c[4] + c[7]);
+                    text += samples[i].name + "\t" + samples[j].name + "\t" + std::to_string(total);
+                    for (int k = 0; k < 9; ++k) text += "\t" + std::to_string(c[k]);
+                    text += "\t" + std::to_string(ibs0) + "\t" + std::to_string(total - ibs0 - ibs2) + "\t" + std::to_string(ibs2) + "\t";
+                    if (het) {
+                        snprintf(num, sizeof num, "%.4f", (double)((int64_t)c[4] - 2 * (int64_t)ibs0) / (double)het);
+                        text += num;
+                    } else
+                        text += ".";
+                    text += "\n";
+                }
+            pair_files.part = o.pairs + ".part";
+            FILE *f = fopen(pair_files.part.c_str(), "wb");
+            if (!f) throw std::runtime_error("cannot write " + o.pairs);
+            const bool short_write = fwrite(text.data(), 1, text.size(), f) != text.size();
+            if (fclose(f) != 0 || short_write || rename(pair_files.part.c_str(), o.pairs.c_str()) != 0) throw std::runtime_error("cannot write " + o.pairs);
+            pair_files.part.clear();
+            if (g_timers.on && pairs_calls[1]) {
+                g_timers.add("pairs: pack and count kernels (device)", (pairs_ms[0] + pairs_ms[1]) / 1000.0);
+                fprintf(stderr, "[malva-geno] pairs: %zu mg_pack_dosage, %zu mg_pair_counts, device ms per call: pack %.3f count %.3f\n", pairs_calls[0], pairs_calls[1],
+                        pairs_calls[0] ? pairs_ms[0] / pairs_calls[0] : 0.0, pairs_ms[1] / pairs_calls[1]);
+            }
         }
         if (bcf_calls && g_timers.on) {
             g_timers.add("merged: encode kernels (device)", (bcf_ms[0] + bcf_ms[1] + bcf_ms[2]) / 1000.0);
