@@ -587,6 +587,68 @@ int mg_pair_counts_device(mg_ctx *ctx, size_t n_words, const void *d_planes_a, u
                           void *d_counts);
 int mg_pairs_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- the per-sample table of a multi-sample call set --------------------------------
+ * For every plane (sample) the sums of its cells along the records: call rate, het / hom, Ts / Tv, the GQ sum and histogram, the
+ * coverage and the genotyper's status codes follow from them.  mg_site_counts sums the cell matrix along the samples, per record;
+ * this sums it along the records, per sample.  There is no reference call to cite: the reference genotypes one individual per run.
+ * gt1 / gt2 / gq and n_planes (1..64) exactly as for mg_site_counts: [n_planes][n_vars] int32, plane-major; gt2 is not read in
+ * haploid mode and may be NULL; gq is read always (the histogram).  status is [n_planes][n_vars] bytes, the MG_GT_* codes, or NULL:
+ * the four status slots then stay untouched.  cov is [n_planes][slots] with slots = var_allele_off[n_vars], or NULL: COV_SUM then
+ * stays untouched.  allele_class is [slots], one byte per allele slot -- 0 REF or none, 1 transition, 2 transversion, 3 insertion,
+ * 4 deletion, 5 other; a record's slot 0 is not read -- or NULL: TS .. OTHER then stay untouched.  var_allele_off ([n_vars + 1]) is
+ * required with n_vars > 0.  counts is uint64_t [n_planes][MG_SAMPLE_SLOTS].  With A = var_allele_off[v + 1] - var_allele_off[v],
+ * a cell (p, v) counts as follows:
+ *   RECORDS   every cell
+ *   MASKED    use_mask != 0 and gq < min_gq, decided first
+ *   BAD       not masked, and some allele index the mode reads is outside [0, A) (negative ones included)
+ *   CALLED    neither masked nor bad: RECORDS = MASKED + BAD + CALLED
+ *   HOM_REF   called, every index read is 0
+ *   HET       called, diploid, gt1 != gt2
+ *   HOM_ALT   called, gt1 != 0 and (haploid or gt1 == gt2)
+ *   HET_ALT   called, diploid, gt1 != gt2, both nonzero (a subset of HET)
+ *   TS TV INS DEL OTHER   called: for each DISTINCT nonzero allele index of the cell, 1 to the slot of
+ *             allele_class[var_allele_off[v] + index] (class 0 or above 5: nothing)
+ *   GQ_SUM    called: gq as a signed 64-bit value, added in two's complement
+ *   COV_SUM   every cell, masked ones included: the sum of the record's A coverages of that plane
+ *   ST_NORMAL ST_OVERCOV ST_SINGLE ST_NOCOV   every cell, by status; any other code: nothing
+ *   GQ_0 .. GQ_90   every cell that is not BAD, masked ones included: bin min(max(gq, 0), 99) / 10
+ * Slots 29..31 are reserved: written as 0 without accumulate, left alone with it.  accumulate != 0 adds to what counts holds (the
+ * batches of a pass are summed this way); accumulate == 0 overwrites all n_planes * MG_SAMPLE_SLOTS entries, so n_vars == 0 then
+ * zeroes them.  The sums are integers: the result does not depend on how the records are cut into calls.  n_planes out of
+ * range, a NULL counts, a NULL gt1 / gq / var_allele_off with n_vars > 0, a NULL gt2 in diploid mode: MG_ERR_ARG.  The host form
+ * synchronises; the device form (every array a device pointer) is asynchronous on the context's stream.
+ * mg_sample_stats (waits): ms_out[1], device milliseconds of the most recent mg_sample_counts*; MG_ERR_STATE before the first.
+ * The calls keep their device copies and their events apart from the encoders', the site tags' and the pair table's. */
+#define MG_SAMPLE_SLOTS 32
+#define MG_SS_RECORDS 0
+#define MG_SS_MASKED 1
+#define MG_SS_BAD 2
+#define MG_SS_CALLED 3
+#define MG_SS_HOM_REF 4
+#define MG_SS_HET 5
+#define MG_SS_HOM_ALT 6
+#define MG_SS_HET_ALT 7
+#define MG_SS_TS 8
+#define MG_SS_TV 9
+#define MG_SS_INS 10
+#define MG_SS_DEL 11
+#define MG_SS_OTHER 12
+#define MG_SS_GQ_SUM 13
+#define MG_SS_COV_SUM 14
+#define MG_SS_ST_NORMAL 15
+#define MG_SS_ST_OVERCOV 16
+#define MG_SS_ST_SINGLE 17
+#define MG_SS_ST_NOCOV 18
+#define MG_SS_GQ_0 19      /* .. MG_SS_GQ_0 + 9: GQ 90 and above */
+#define MG_SS_COUNTED 29   /* the slots in use; the rest is reserved */
+int mg_sample_counts(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                     int32_t min_gq, const uint8_t *status, const uint32_t *cov, const uint32_t *var_allele_off, const uint8_t *allele_class, int accumulate,
+                     uint64_t *counts);
+int mg_sample_counts_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                            int32_t min_gq, const void *d_status, const void *d_cov, const void *d_var_allele_off, const void *d_allele_class, int accumulate,
+                            void *d_counts);
+int mg_sample_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- the sample columns of a multi-sample BCF --------------------------------------
  * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
  * parity with htslib unpinned).  Arrays, n_planes (1..64), the host and _device forms, the stream behaviour and the buffer

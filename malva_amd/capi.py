@@ -18,6 +18,7 @@ BF_ALT, BF_CTX = 0, 1
 STREAM_DEFAULT = 1          # MG_STREAM_DEFAULT: HIP's legacy default stream (a NULL handle means the context's own stream)
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 COMM_ID_BYTES = 128
+SAMPLE_SLOTS = 32           # MG_SAMPLE_SLOTS: the counters per plane of mg_sample_counts (MG_SS_*)
 GT_NORMAL, GT_OVERCOV, GT_SINGLE, GT_NOCOV = 0, 1, 2, 3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -124,6 +125,9 @@ def lib():
         "mg_pair_counts": [vp, sz, vp, u32, vp, u32, it, vp],
         "mg_pair_counts_device": [vp, sz, vp, u32, vp, u32, it, vp],
         "mg_pairs_stats": [vp, vp],
+        "mg_sample_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, it, vp],
+        "mg_sample_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, it, vp],
+        "mg_sample_stats": [vp, vp],
         "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
@@ -192,7 +196,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
-            "mg_pairs_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -782,6 +786,33 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_pairs_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
+
+    # the per-sample table of a multi-sample call set
+    def sample_counts(self, gt1, gt2, gq, haploid, var_allele_off, status=None, cov=None, allele_class=None, min_gq=None, counts=None, overwrite=False):
+        """gt1 / gt2 / gq: [planes, n_vars] int32; status [planes, n_vars] uint8, cov [planes, slots] uint32, allele_class [slots] uint8,
+        each or None -> uint64 [planes, SAMPLE_SLOTS], the slots MG_SS_* of include/malva_hip.h.  min_gq: cells whose gq is below it
+        are masked.  counts given: the sums are added to it (in place) unless overwrite."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q, vo = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32), a(var_allele_off, np.uint32)
+        st, cv, ac = a(status, np.uint8), a(cov, np.uint32), a(allele_class, np.uint8)
+        planes, n = g1.shape
+        slots = int(vo[n]) if n else 0
+        assert st is None or st.shape == (planes, n)
+        assert cv is None or cv.shape == (planes, slots)
+        assert ac is None or ac.shape == (slots,)
+        acc = counts is not None and not overwrite
+        if counts is None:
+            counts = np.zeros((planes, SAMPLE_SLOTS), dtype=np.uint64)
+        assert counts.dtype == np.uint64 and counts.flags.c_contiguous and counts.shape == (planes, SAMPLE_SLOTS)
+        self._ck(self._L.mg_sample_counts(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(st), _p(cv), _p(vo),
+                                          _p(ac), int(acc), _p(counts)))
+        return counts
+
+    def sample_stats(self):
+        """-> device ms of the most recent sample_counts"""
+        ms = (C.c_float * 1)()
+        self._ck(self._L.mg_sample_stats(self.h, ms))
+        return float(ms[0])
 
     # the sample columns of a multi-sample BCF
     def encode_calls_bcf(self, gt1, gt2, gq, haploid, keys, cov=None, var_allele_off=None, out_cap=None, min_gq=None):

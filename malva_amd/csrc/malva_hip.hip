@@ -41,6 +41,7 @@ constexpr int TPB = 256;
 #include "call_text_kernels.h"
 #include "site_tags_kernels.h"
 #include "pair_kernels.h"
+#include "sample_kernels.h"
 #include "bcf_kernels.h"
 #include "reads_kernels.h"
 
@@ -168,6 +169,12 @@ struct mg_ctx {
     struct PairStage {
         Scratch gt1, gt2, gq, var_allele_off, planes, pa, pb, counts;
     } pstage;
+    // the per-sample table (mg_sample_counts*): the events of the latest call and the host form's device copies, again its own
+    hipEvent_t ev_sample[2] = {nullptr, nullptr};
+    bool sample_stats_valid = false;
+    struct SampleStage {
+        Scratch gt1, gt2, gq, status, cov, var_allele_off, allele_class, counts;
+    } sstage;
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -710,6 +717,10 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : {c->ev_pack[0], c->ev_pack[1], c->ev_pair[0], c->ev_pair[1]})
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_sample)
+        if (e) hipEventDestroy(e);
+    for (Scratch *q : {&c->sstage.gt1, &c->sstage.gt2, &c->sstage.gq, &c->sstage.status, &c->sstage.cov, &c->sstage.var_allele_off, &c->sstage.allele_class, &c->sstage.counts})
+        hipFree(q->p);
     for (Scratch *q : {&c->pstage.gt1, &c->pstage.gt2, &c->pstage.gq, &c->pstage.var_allele_off, &c->pstage.planes, &c->pstage.pa, &c->pstage.pb, &c->pstage.counts})
         hipFree(q->p);
     for (Scratch *q : {&c->rp_fmt.len, &c->rp_fmt.meta, &c->rp_info.len, &c->rp_info.meta, &c->rp_bcf.len, &c->rp_bcf.meta, &c->s_bcf_types, &c->stage.gt1, &c->stage.gt2,
@@ -3499,6 +3510,90 @@ MG_EXPORT int mg_pairs_stats(mg_ctx *c, float *ms_out)
         HIP_TRY(c, hipEventSynchronize(c->ev_pair[1]));
         HIP_TRY(c, hipEventElapsedTime(&ms_out[1], c->ev_pair[0], c->ev_pair[1]));
     }
+    return MG_OK;
+}
+
+// ---- the per-sample table of a multi-sample call set (sample_kernels.h) -----------------------------------------------------------------
+namespace {
+int check_sample(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, const void *var_allele_off, const void *counts)
+{
+    TRY(check_cells(c, "mg_sample_counts", n_vars, n_planes, haploid, gt1, gt2, gq, true, nullptr, nullptr)); // (gq: the histogram reads it, mask or none)
+    if (!counts || (n_vars && !var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_sample_counts: more than 2^32 - 1 records in one call");
+    return MG_OK;
+}
+// The records are cut into runs, one workgroup per plane and run: as many runs as give about SAMPLE_TARGET_WGS workgroups over all
+// planes -- a chip's worth of waves, and a few dozen atomic adds per counter --, none longer than SAMPLE_MAX_RUN (the 32-bit accumulators)
+constexpr u64 SAMPLE_TARGET_WGS = 2048;
+u64 sample_count_plan(u64 n_vars, u32 n_planes, u64 *n_runs)
+{
+    const u64 chunks = (n_vars + SAMPLE_TPB - 1) / SAMPLE_TPB;
+    u64 runs = std::min<u64>(chunks, std::max<u64>(1, SAMPLE_TARGET_WGS / n_planes));
+    runs = std::max<u64>(runs, (n_vars + SAMPLE_MAX_RUN - 1) / SAMPLE_MAX_RUN);
+    const u64 run = (chunks + runs - 1) / runs * SAMPLE_TPB; // (whole chunks; at most SAMPLE_MAX_RUN, itself a multiple of SAMPLE_TPB)
+    *n_runs = (n_vars + run - 1) / run;
+    return run;
+}
+} // namespace
+
+MG_EXPORT int mg_sample_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                      int32_t min_gq, const void *d_status, const void *d_cov, const void *d_var_allele_off, const void *d_allele_class, int accumulate,
+                                      void *d_counts)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_sample(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, d_var_allele_off, d_counts));
+    for (auto &e : c->ev_sample)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->sample_stats_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev_sample[0], c->stream));
+    if (!accumulate) HIP_TRY(c, hipMemsetAsync(d_counts, 0, 8 * (size_t)n_planes * MG_SAMPLE_SLOTS, c->stream));
+    if (n_vars) {
+        u64 n_runs = 0;
+        const u64 run = sample_count_plan((u64)n_vars, n_planes, &n_runs);
+        const SampleArgs a{(u64)n_vars, run, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u8 *)d_status, (const u32 *)d_cov,
+                           (const u32 *)d_var_allele_off, (const u8 *)d_allele_class};
+        hipLaunchKernelGGL(sample_count_kernel, dim3((unsigned)n_runs, n_planes), dim3(SAMPLE_TPB), 0, c->stream, a, (unsigned long long *)d_counts);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_sample[1], c->stream));
+    c->sample_stats_valid = true;
+    return MG_OK;
+}
+
+MG_EXPORT int mg_sample_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                               int32_t min_gq, const uint8_t *status, const uint32_t *cov, const uint32_t *var_allele_off, const uint8_t *allele_class, int accumulate,
+                               uint64_t *counts)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_sample(c, n_vars, n_planes, haploid, gt1, gt2, gq, var_allele_off, counts));
+    const size_t cells = (size_t)n_planes * n_vars, slots = n_vars ? var_allele_off[n_vars] : 0, count_bytes = 8 * (size_t)n_planes * MG_SAMPLE_SLOTS;
+    void *d1, *d2 = nullptr, *dq, *ds = nullptr, *dc = nullptr, *dv = nullptr, *dk = nullptr, *d_counts;
+    TRY(upload(c, c->sstage.gt1, gt1, 4 * cells, &d1));
+    if (!haploid) TRY(upload(c, c->sstage.gt2, gt2, 4 * cells, &d2));
+    TRY(upload(c, c->sstage.gq, gq, 4 * cells, &dq));
+    if (n_vars) TRY(upload(c, c->sstage.var_allele_off, var_allele_off, 4 * (n_vars + 1), &dv));
+    if (n_vars && status) TRY(upload(c, c->sstage.status, status, cells, &ds));
+    if (n_vars && cov) TRY(upload(c, c->sstage.cov, cov, 4 * (size_t)n_planes * slots, &dc));
+    if (n_vars && allele_class) TRY(upload(c, c->sstage.allele_class, allele_class, slots, &dk));
+    TRY(scratch(c, c->sstage.counts, count_bytes, &d_counts));
+    if (accumulate) HIP_TRY(c, hipMemcpyAsync(d_counts, counts, count_bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(mg_sample_counts_device(c, n_vars, n_planes, haploid, d1, d2, dq, use_mask, min_gq, ds, dc, dv, dk, accumulate, d_counts));
+    HIP_TRY(c, hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds (waits for them) of the most recent mg_sample_counts*
+MG_EXPORT int mg_sample_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = 0.f;
+    if (!c->sample_stats_valid) return fail(c, MG_ERR_STATE, "no mg_sample_counts yet");
+    HIP_TRY(c, hipEventSynchronize(c->ev_sample[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms_out[0], c->ev_sample[0], c->ev_sample[1]));
     return MG_OK;
 }
 

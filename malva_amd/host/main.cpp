@@ -97,6 +97,12 @@ const char *USAGE =
     "                                        joint counts N00..N22 of their dosages (0, 1, 2 ALT copies; haploid: 0 or 2), their sum N,\n"
     "                                        IBS0/1/2 and KING = (N11 - 2 IBS0) / (het A + het B), '.' without heterozygotes.  Counted on\n"
     "                                        the GPU, whatever the grouping; beside -o and/or --merged                       [this build]\n"
+    "          --sample-stats                --cohort: PATH receives a tab-separated table, one line per sample in manifest order: how\n"
+    "                                        many of its cells are called, masked (--min-gq applies) or carry an allele the record lacks,\n"
+    "                                        HOM_REF / HET / HOM_ALT, the called ALT alleles by kind (TS, TV, INS, DEL, OTHER), the GQ sum\n"
+    "                                        and histogram, the coverage sum, the genotyper's status codes, and CALL_RATE, HET_HOM, TSTV,\n"
+    "                                        MEAN_GQ, MEAN_COV ('.' for 0 / 0).  Summed on the GPU, whatever the grouping; beside -o\n"
+    "                                        and/or --merged                                                                 [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -134,6 +140,7 @@ struct Options { // argument_parser.hpp:51-66
     std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
     bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
     std::string pairs;      // --pairs: the table of pairwise genotype sharing
+    std::string sample_stats; // --sample-stats: the per-sample QC table
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -153,7 +160,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
                                       {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
                                       {"merged-format", required_argument, nullptr, 1008}, {"gp", no_argument, nullptr, 1009},
-                                      {"pairs", required_argument, nullptr, 1010},
+                                      {"pairs", required_argument, nullptr, 1010},    {"sample-stats", required_argument, nullptr, 1011},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -226,6 +233,13 @@ bool parse_arguments(int argc, char **argv, Options &o)
                 die = true;
             }
             break;
+        case 1011:
+            o.sample_stats = optarg;
+            if (o.sample_stats.empty()) {
+                std::cerr << "malva : --sample-stats takes a path\n";
+                die = true;
+            }
+            break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -269,6 +283,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (!o.cohort && !o.pairs.empty()) {
         std::cerr << "malva : --pairs goes with --cohort\n";
+        die = true;
+    }
+    if (!o.cohort && !o.sample_stats.empty()) {
+        std::cerr << "malva : --sample-stats goes with --cohort\n";
         die = true;
     }
     if (!o.cohort && (!o.out_dir.empty() || o.cohort_group)) {
@@ -1399,6 +1417,7 @@ struct Rec {
 struct Batch { // inputs of mg_call_isolated (isolated) or mg_lookup_cover + mg_genotype (general)
     std::vector<uint64_t> pos, present;
     std::vector<uint32_t> var_allele_off{0}, allele_off{0};
+    std::vector<uint8_t> allele_class; // --sample-stats: one byte per allele slot (allele_class_of; slot 0 of a record: 0), else empty
     std::vector<char> pool;
     std::vector<float> freq;
     std::vector<uint8_t> flags;
@@ -1425,6 +1444,28 @@ struct Batch { // inputs of mg_call_isolated (isolated) or mg_lookup_cover + mg_
     std::vector<double> probs;
     size_t n() const { return var_allele_off.size() - 1; }
 };
+
+// --sample-stats: the kind of the ALT allele `alt` of a record whose REF is `ref`, from the strings as the record prints them (the class
+// codes of mg_sample_counts: 1 transition, 2 transversion, 3 insertion, 4 deletion, 5 other)
+uint8_t allele_class_of(const std::string &ref, const std::string &alt)
+{
+    if (alt == "*" || (!alt.empty() && alt[0] == '<')) return 5;
+    auto base = [](char c) -> int {
+        switch (c) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'T': case 't': return 3;
+        default: return -1;
+        }
+    };
+    for (char c : alt)
+        if (base(c) < 0) return 5;
+    if (ref.size() == 1 && alt.size() == 1) return base(ref[0]) >= 0 && (base(ref[0]) ^ base(alt[0])) == 2 ? 1 : 2; // (A <-> G: 0 ^ 2, C <-> T: 1 ^ 3)
+    if (alt.size() > ref.size()) return 3;
+    if (alt.size() < ref.size()) return 4;
+    return 5;
+}
 
 int call_main(const Options &o)
 {
@@ -1529,6 +1570,9 @@ int call_main(const Options &o)
     };
     double pairs_ms[2] = {0, 0};              // device milliseconds of the mg_pack_dosage and of the mg_pair_counts
     size_t pairs_calls[2] = {0, 0};
+    const bool want_sample = !o.sample_stats.empty(); // --sample-stats: the batches carry their alleles' classes
+    double sample_ms = 0;                     // device milliseconds of the mg_sample_counts
+    size_t sample_calls = 0;
     // --merged-format bcf | ubcf: the merged file as BCF2 (host/bcf_out.hpp), a record's per-sample block encoded by mg_encode_calls_bcf
     const bool bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", bcf_bgzf = o.merged_format == "bcf";
     BcfHeader bcf_hdr;
@@ -1579,8 +1623,10 @@ int call_main(const Options &o)
     // pairs (--pairs): every batch's cells are packed into dosage bit planes (mg_pack_dosage) while the batch is in hand and counted against
     // themselves into pairs->counts; pairs->pack_out, when set, receives per batch and stream -- the lone records', then the others' -- the u64s
     // stream, n_records and the [planes][3][W] words.
+    // sample_table (--sample-stats): the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand
+    // (mg_sample_counts, accumulate).
     auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed, FILE *cnt_out,
-                        PairsRun *pairs) -> size_t {
+                        PairsRun *pairs, uint64_t *sample_table) -> size_t {
     const size_t P = planes ? planes : 1;
 
     // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
@@ -1780,6 +1826,21 @@ int call_main(const Options &o)
                 }
             }
         }
+        if (sample_table) {
+            Timed t_sample("worker: sample table (mg_sample_counts)");
+            for (int w = 0; w < 2; ++w) {
+                Batch &b = w ? gen : iso;
+                const size_t bn = b.n();
+                if (!bn) continue;
+                dev.check(mg_sample_counts(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.status.data(), b.cov.data(),
+                                           b.var_allele_off.data(), b.allele_class.data(), 1, sample_table),
+                          "mg_sample_counts");
+                float ms = 0;
+                dev.check(mg_sample_stats(dev.ctx, &ms), "mg_sample_stats");
+                sample_ms += ms;
+                ++sample_calls;
+            }
+        }
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
@@ -1965,6 +2026,7 @@ int call_main(const Options &o)
                 iso.pool.insert(iso.pool.end(), al.begin(), al.end());
                 iso.allele_off.push_back((uint32_t)iso.pool.size());
                 iso.freq.push_back(v.frequencies[a]);
+                if (want_sample) iso.allele_class.push_back(a ? allele_class_of(v.ref_sub, al) : (uint8_t)0);
             }
             iso.var_allele_off.push_back(iso.var_allele_off.back() + A);
             iso.var_gt_off.push_back(iso.var_gt_off.back() + n_gt(A));
@@ -1990,6 +2052,7 @@ int call_main(const Options &o)
                     gen.allele_off.push_back((uint32_t)gen.pool.size());
                     gen.canon.push_back((uint8_t)std::min(255, v.allele_index(al)));
                     gen.freq.push_back(v.frequencies[a]);
+                    if (want_sample) gen.allele_class.push_back(a ? allele_class_of(v.ref_sub, al) : (uint8_t)0);
                 }
                 gen.var_allele_off.push_back(gen.var_allele_off.back() + A);
                 gen.var_gt_off.push_back(gen.var_gt_off.back() + n_gt(A));
@@ -2020,7 +2083,7 @@ int call_main(const Options &o)
     }; // vcf_pass
 
     size_t n = 0;
-    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr, nullptr);
+    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr, nullptr, nullptr);
     else {
         if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
         Device &dev = devs[0];
@@ -2060,6 +2123,16 @@ int call_main(const Options &o)
         const size_t S = samples.size();
         std::vector<uint64_t> pair_table(want_pairs ? S * S * 9 : 0, 0);
         std::vector<size_t> group_first; // the first sample of every group
+        // --sample-stats: [samples][MG_SAMPLE_SLOTS]; a sample belongs to one group, whose panel pass sums its row, so the table needs no pass
+        // of its own.  It is written as PATH.part and renamed; what is left of that goes when this frame is left.
+        struct SampleFile {
+            std::string part;
+            ~SampleFile()
+            {
+                if (!part.empty()) unlink(part.c_str());
+            }
+        } sample_file;
+        std::vector<uint64_t> sample_table(want_sample ? S * MG_SAMPLE_SLOTS : 0, 0);
         const bool merged_stdout = o.merged == "-";
         const std::string merged_tmp_base = !merged_stdout ? o.merged : std::string(getenv("TMPDIR") && *getenv("TMPDIR") ? getenv("TMPDIR") : "/tmp") + "/malva-geno." + std::to_string((long)getpid()) + ".merged";
         std::string merged_head;
@@ -2164,7 +2237,8 @@ int call_main(const Options &o)
                     start_vcf(*again);
                     if (!again->ok()) throw std::runtime_error(again->error);
                 }
-                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0, merged.cnt_open, want_pairs ? &pairs_run : nullptr);
+                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0, merged.cnt_open, want_pairs ? &pairs_run : nullptr,
+                             want_sample ? &sample_table[s0 * MG_SAMPLE_SLOTS] : nullptr);
             }
             if (pair_files.open) {
                 FILE *closing = pair_files.open;
@@ -2454,6 +2528,45 @@ int call_main(const Options &o)
                 g_timers.add("pairs: pack and count kernels (device)", (pairs_ms[0] + pairs_ms[1]) / 1000.0);
                 fprintf(stderr, "[malva-geno] pairs: %zu mg_pack_dosage, %zu mg_pair_counts, device ms per call: pack %.3f count %.3f\n", pairs_calls[0], pairs_calls[1],
                         pairs_calls[0] ? pairs_ms[0] / pairs_calls[0] : 0.0, pairs_ms[1] / pairs_calls[1]);
+            }
+        }
+        if (want_sample) {
+            // the text: five divisions per sample and the formatting are all the host does
+            std::string text = "#SAMPLE\tRECORDS\tCALLED\tMASKED\tBAD\tHOM_REF\tHET\tHOM_ALT\tHET_ALT\tTS\tTV\tINS\tDEL\tOTHER\tGQ_SUM\tCOV_SUM\tNORMAL\tOVERCOV\tSINGLE\tNOCOV";
+            for (int b = 0; b < 10; ++b) text += "\tGQ_" + std::to_string(10 * b);
+            text += "\tCALL_RATE\tHET_HOM\tTSTV\tMEAN_GQ\tMEAN_COV\n";
+            char num[64];
+            for (size_t i = 0; i < S; ++i) {
+                const uint64_t *c = &sample_table[i * MG_SAMPLE_SLOTS];
+                text += samples[i].name;
+                for (int k : {MG_SS_RECORDS, MG_SS_CALLED, MG_SS_MASKED, MG_SS_BAD, MG_SS_HOM_REF, MG_SS_HET, MG_SS_HOM_ALT, MG_SS_HET_ALT, MG_SS_TS, MG_SS_TV, MG_SS_INS,
+                              MG_SS_DEL, MG_SS_OTHER})
+                    text += "\t" + std::to_string(c[k]);
+                text += "\t" + std::to_string((int64_t)c[MG_SS_GQ_SUM]);
+                for (int k = MG_SS_COV_SUM; k < MG_SS_COUNTED; ++k) text += "\t" + std::to_string(c[k]);
+                const double ratio[5][2] = {{(double)c[MG_SS_CALLED], (double)c[MG_SS_RECORDS]},
+                                            {(double)c[MG_SS_HET], (double)c[MG_SS_HOM_ALT]},
+                                            {(double)c[MG_SS_TS], (double)c[MG_SS_TV]},
+                                            {(double)(int64_t)c[MG_SS_GQ_SUM], (double)c[MG_SS_CALLED]},
+                                            {(double)c[MG_SS_COV_SUM], (double)c[MG_SS_RECORDS]}};
+                for (const auto &r : ratio) {
+                    if (r[1] != 0) {
+                        snprintf(num, sizeof num, "\t%.4f", r[0] / r[1]);
+                        text += num;
+                    } else
+                        text += "\t.";
+                }
+                text += "\n";
+            }
+            sample_file.part = o.sample_stats + ".part";
+            FILE *f = fopen(sample_file.part.c_str(), "wb");
+            if (!f) throw std::runtime_error("cannot write " + o.sample_stats);
+            const bool short_write = fwrite(text.data(), 1, text.size(), f) != text.size();
+            if (fclose(f) != 0 || short_write || rename(sample_file.part.c_str(), o.sample_stats.c_str()) != 0) throw std::runtime_error("cannot write " + o.sample_stats);
+            sample_file.part.clear();
+            if (g_timers.on && sample_calls) {
+                g_timers.add("sample table: count kernel (device)", sample_ms / 1000.0);
+                fprintf(stderr, "[malva-geno] sample-stats: %zu mg_sample_counts, device ms per call: count %.3f\n", sample_calls, sample_ms / sample_calls);
             }
         }
         if (bcf_calls && g_timers.on) {
