@@ -600,6 +600,72 @@ int fill_geno_params(mg_ctx *c, float error_rate, int max_cov, int haploid, Geno
     return MG_OK;
 }
 
+// genotype_one (geno_dev.h) on the host, every log and exp from libm: for the records of mg_genotype whose total coverage
+// is at or beyond MG_LN_TABLE, where the kernel's ln(n) is the device's log(double) and about one value in a thousand
+// comes out a last bit away from the CPU path.  The operations of gt_value and of the general form of
+// genotype_one in their order; the biallelic form of the kernel is the same sequence unrolled.
+double host_log_binomial(int n, int k)
+{
+    if (n == 0 || n == k || k == 0) return 0.0;
+    const double a = n * std::log((double)n);
+    const double b = k * std::log((double)k);
+    const double c = (n - k) * std::log((double)(n - k));
+    return a - b - c;
+}
+double host_gt_value(const u32 *cov, const float *freq, int A, u32 total, int g1, int g2, float e)
+{
+    double log_prior, log_post;
+    if (g2 < 0 || g1 == g2) {
+        const u32 truth = cov[g1], error = total - truth;
+        log_prior = (double)(2 * std::log(freq[g1])); // float overload, here and below
+        const float t1 = (float)truth * std::log(1 - e);
+        const float t2 = (float)error * std::log(e / (float)(unsigned long)(A - 1));
+        log_post = host_log_binomial((int)(truth + error), (int)truth) + (double)t1 + (double)t2;
+    } else {
+        const u32 t1c = cov[g1], t2c = cov[g2], error = total - t1c - t2c;
+        const float pr = 2 * freq[g1] * freq[g2];
+        log_prior = (double)std::log(pr);
+        const float c_het = std::log((1 - e) / 2);
+        const float t1 = (float)t1c * c_het;
+        const float t2 = (float)t2c * c_het;
+        log_post = host_log_binomial((int)(t1c + t2c + error), (int)(t1c + t2c)) + host_log_binomial((int)(t1c + t2c), (int)t1c) + (double)t1 + (double)t2;
+        if (A > 2) {
+            const float t3 = (float)error * std::log(e / (float)(unsigned long)(A - 2));
+            log_post += (double)t3;
+        }
+    }
+    const double lp = log_prior + log_post;
+    return std::isinf(lp) ? 0.0 : std::exp(lp);
+}
+// one record of status 0: gt1 / gt2 / gq and, if probs != nullptr, the normalised list
+void host_genotype_one(const u32 *cov, const float *freq, int A, u32 total, float e, int haploid, i32 *gt1, i32 *gt2, i32 *gq, double *probs)
+{
+    std::vector<double> val;
+    val.reserve(haploid ? (size_t)A : (size_t)A * (A + 1) / 2);
+    std::vector<int> a1, a2;
+    double sum = 0.0;
+    for (int g1 = 0; g1 < A; ++g1)
+        for (int g2 = haploid ? -1 : g1; g2 < (haploid ? 0 : A); ++g2) {
+            val.push_back(host_gt_value(cov, freq, A, total, g1, g2, e));
+            a1.push_back(g1);
+            a2.push_back(g2);
+            sum += val.back();
+        }
+    double best = 0.0;
+    *gt1 = 0;
+    *gt2 = haploid ? -1 : 0;
+    for (size_t n = 0; n < val.size(); ++n) {
+        const double q = val[n] / sum;
+        if (probs) probs[n] = q;
+        if (q > best) {
+            best = q;
+            *gt1 = a1[n];
+            *gt2 = a2[n];
+        }
+    }
+    *gq = (i32)std::round(best * 100.0);
+}
+
 } // namespace
 
 // ---- lifetime -------------------------------------------------------------------
@@ -2684,6 +2750,15 @@ MG_EXPORT int mg_genotype(mg_ctx *c, const uint32_t *cov, const float *freq, con
     HIP_TRY(c, hipMemcpyAsync(status, d_st, n_vars, hipMemcpyDeviceToHost, c->stream));
     if (probs && ng) HIP_TRY(c, hipMemcpyAsync(probs, d_pr, 8 * ng, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // records that took an ln(n) from the device's log(double): again on the host, with libm (host_genotype_one)
+    for (size_t v = 0; v < n_vars; ++v) {
+        if (status[v] != 0) continue;
+        const uint32_t a0 = var_allele_off[v], A = var_allele_off[v + 1] - a0;
+        int isum = 0;
+        for (uint32_t a = 0; a < A; ++a) isum += (int)cov[a0 + a];
+        if (isum < MG_LN_TABLE) continue;
+        host_genotype_one(cov + a0, freq + a0, (int)A, (u32)isum, error_rate, haploid, gt1 + v, gt2 + v, gq + v, probs ? probs + var_gt_off[v] : nullptr);
+    }
     return MG_OK;
 }
 

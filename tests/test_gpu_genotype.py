@@ -71,6 +71,9 @@ def test_random_coverages_against_oracle(haploid):
         freq[off[v]:off[v + 1]] = f
     ctx = Context(35, 43, 1 << 16)
     g1, g2, gq, st, probs, goff = ctx.genotype(cov, freq, off, EPS, 200, haploid, want_probs=True)
+    # the form every non-verbose run uses: no room for the values, each is computed twice
+    h1, h2, hq, hs, _, _ = ctx.genotype(cov, freq, off, EPS, 200, haploid)
+    assert np.array_equal(h1, g1) and np.array_equal(h2, g2) and np.array_equal(hq, gq) and np.array_equal(hs, st)
     exact = total = 0
     for v in range(n):
         o1, o2, oq, norm, gts = _oracle_variant(cov[off[v]:off[v + 1]], freq[off[v]:off[v + 1]], haploid)
