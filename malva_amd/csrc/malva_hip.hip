@@ -79,18 +79,26 @@ struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
 };
-// What one encoder of a merged batch's rows keeps between its passes and for its stats call (encode_rows)
-struct RowPass {
-    Scratch len, meta;                                       // the rows' lengths (u32); the meta block: the total, "a row beyond 32 bits"
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // start, after the length pass, after the scan, after the write pass
-    bool valid = false;                                      // ev[] are those of a call that ran
+// One timed call of the merged-batch section: its events (the first n of them: start, then the end of each part) and whether they are those
+// of a call that ran (timer_begin, timer_mark, timer_read).  TM_FMT .. TM_BCF are the three row encoders (encode_rows) and index s_enc too.
+struct Timer {
+    int n;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool valid = false;
 };
-// Device copies of the host forms' arguments and results (mg_format_calls*, mg_site_counts, mg_format_site_info, mg_encode_calls_bcf).  One
-// set serves them all: every host form runs on the context's stream and synchronises before it returns, so none outlives its call, and
-// no device form touches it (those own a RowPass, s_bcf_types and s_scan, and read and write the caller's buffers).
-struct RowStage {
-    Scratch gt1, gt2, gq, cov, var_allele_off, ac, ns, out, row_off;
-    Scratch probs, var_gt_off, status; // mg_format_calls_gp, mg_encode_calls_bcf_gp
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*
+enum { ENC_COUNT = TM_BCF + 1 };
+// what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
+// beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
+enum { ES_LEN, ES_META, ES_TYPES, ES_COUNT };
+// Device copies of the host forms' arguments and results, for every host form of the merged-batch section.  One set is enough: the caller
+// serialises the host forms of a context, each runs on the context's stream and synchronises before it returns, so no staged buffer
+// outlives its call; and no device form touches the set (those own s_enc and s_scan, and read and write the caller's buffers).
+enum {
+    ST_GT1, ST_GT2, ST_GQ, ST_COV, ST_VAR_ALLELE_OFF, ST_PROBS, ST_VAR_GT_OFF, ST_STATUS, ST_ALLELE_CLASS, // a batch's cells (stage_cells)
+    ST_AC, ST_NS, ST_PLANES, ST_PA, ST_PB, ST_COUNTS,                                                      // the counting calls' tables
+    ST_OUT, ST_ROW_OFF,                                                                                    // an encoder's rows (stage_rows)
+    ST_COUNT
 };
 
 struct mg_ctx {
@@ -156,25 +164,9 @@ struct mg_ctx {
     u32 *coh_sv_counts = nullptr, *coh_sv_vals = nullptr;
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
     hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
-    // the rows of a merged batch (encode_rows): one pass state per encoder, since each stats call reports its own encoder's latest call
-    RowPass rp_fmt, rp_info, rp_bcf;                  // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*
-    Scratch s_bcf_types;                              // mg_encode_calls_bcf*: the records' type codes, from its length pass to its write pass
-    hipEvent_t ev_cnt[2] = {nullptr, nullptr};        // mg_site_counts*: start and end of the latest call
-    bool cnt_stats_valid = false;
-    RowStage stage;
-    // the pair table (mg_pack_dosage*, mg_pair_counts*): the events of each kind's latest call and the host forms' device copies, their
-    // own -- no encoder and no site-tag call touches them, and these touch nothing of theirs
-    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_pair[2] = {nullptr, nullptr};
-    bool pack_stats_valid = false, pair_stats_valid = false;
-    struct PairStage {
-        Scratch gt1, gt2, gq, var_allele_off, planes, pa, pb, counts;
-    } pstage;
-    // the per-sample table (mg_sample_counts*): the events of the latest call and the host form's device copies, again its own
-    hipEvent_t ev_sample[2] = {nullptr, nullptr};
-    bool sample_stats_valid = false;
-    struct SampleStage {
-        Scratch gt1, gt2, gq, status, cov, var_allele_off, allele_class, counts;
-    } sstage;
+    // the merged-batch section: each stats call reports the latest call of its own kinds, hence a timer per kind
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
+    Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -776,23 +768,12 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     hipFree(c->coh_sv_vals);
     for (auto &e : c->ev_c)
         if (e) hipEventDestroy(e);
-    for (RowPass *rp : {&c->rp_fmt, &c->rp_info, &c->rp_bcf})
-        for (hipEvent_t e : rp->ev)
+    for (Timer &t : c->tm)
+        for (hipEvent_t e : t.ev)
             if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_cnt)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : {c->ev_pack[0], c->ev_pack[1], c->ev_pair[0], c->ev_pair[1]})
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_sample)
-        if (e) hipEventDestroy(e);
-    for (Scratch *q : {&c->sstage.gt1, &c->sstage.gt2, &c->sstage.gq, &c->sstage.status, &c->sstage.cov, &c->sstage.var_allele_off, &c->sstage.allele_class, &c->sstage.counts})
-        hipFree(q->p);
-    for (Scratch *q : {&c->pstage.gt1, &c->pstage.gt2, &c->pstage.gq, &c->pstage.var_allele_off, &c->pstage.planes, &c->pstage.pa, &c->pstage.pb, &c->pstage.counts})
-        hipFree(q->p);
-    for (Scratch *q : {&c->rp_fmt.len, &c->rp_fmt.meta, &c->rp_info.len, &c->rp_info.meta, &c->rp_bcf.len, &c->rp_bcf.meta, &c->s_bcf_types, &c->stage.gt1, &c->stage.gt2,
-                       &c->stage.gq, &c->stage.cov, &c->stage.var_allele_off, &c->stage.ac, &c->stage.ns, &c->stage.out, &c->stage.row_off, &c->stage.probs,
-                       &c->stage.var_gt_off, &c->stage.status})
-        hipFree(q->p);
+    for (auto &enc : c->s_enc)
+        for (Scratch &q : enc) hipFree(q.p);
+    for (Scratch &q : c->stage) hipFree(q.p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3147,25 +3128,62 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
 // ---- the rows of a merged batch: the sample columns as text (call_text_kernels.h), the site tags (site_tags_kernels.h), the sample columns
 // ---- as BCF (bcf_kernels.h) ---------------------------------------------------------------------------------------------------------
 namespace {
-// The argument checks that a host form and its device form share (host pointers there, device pointers here): of whoever reads a batch's
-// cells (gq where reads_gq, cov with var_allele_off or neither; gp, the *_gp entries: var_allele_off with or without cov, and the three
-// arrays of the likelihoods), and of where an encoder's rows go
-struct GpCells {
-    const void *probs, *var_gt_off, *status;
+// A batch's cells as every call of this section takes them, host pointers in a host form and device pointers in a device form: the nine
+// arguments they all share, then what only some have (NULL elsewhere)
+struct Cells {
+    size_t n_vars;
+    uint32_t n_planes;
+    int haploid;
+    const void *gt1, *gt2, *gq;
+    int use_mask;
+    int32_t min_gq;
+    const void *var_allele_off;
+    const void *cov = nullptr, *status = nullptr;       // the encoders and mg_sample_counts*
+    const void *probs = nullptr, *var_gt_off = nullptr; // the *_gp entries (gp set), with status: the three arrays of the likelihoods
+    const void *allele_class = nullptr;                 // mg_sample_counts*
+    bool gp = false;
 };
-int check_cells(mg_ctx *c, const char *who, size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, bool reads_gq,
-                const void *cov, const void *var_allele_off, const GpCells *gp = nullptr)
+// The argument checks that a host form and its device form share: of whoever reads a batch's cells (gq where reads_gq; an encoder: cov with
+// var_allele_off or neither, and with gp var_allele_off with or without cov and the likelihoods), and of where an encoder's rows go
+int check_cells(mg_ctx *c, const char *who, const Cells &x, bool encoder, bool reads_gq)
 {
-    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "%s: n_planes is 1..64", who);
-    if (!gp && (cov != nullptr) != (var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
-    if (gp && (!var_allele_off || !gp->var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
-    if (n_vars && (!gt1 || (!haploid && !gt2) || (reads_gq && !gq))) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (n_vars && gp && (!gp->probs || !gp->status)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (x.n_planes < 1 || x.n_planes > 64) return fail(c, MG_ERR_ARG, "%s: n_planes is 1..64", who);
+    if (encoder && !x.gp && (x.cov != nullptr) != (x.var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
+    if (x.gp && (!x.var_allele_off || !x.var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
+    if (x.n_vars && (!x.gt1 || (!x.haploid && !x.gt2) || (reads_gq && !x.gq))) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (x.n_vars && x.gp && (!x.probs || !x.status)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (x.n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "%s: more than 2^32 - 1 records in one call", who);
     return MG_OK;
 }
 int check_rows_out(mg_ctx *c, const void *out, size_t cap, const void *row_off, const uint64_t *bytes_out)
 {
     if (!row_off || !bytes_out || (!out && cap)) return fail(c, MG_ERR_ARG, "NULL argument");
+    return MG_OK;
+}
+
+// A call's timer: begin before its first work goes on the stream (an empty call counts as a call), mark(i) behind part i (the last mark
+// makes the timer valid), read in the stats call: waits for the call, ms[i] = device milliseconds of part i + 1; 0 where no call has run
+int timer_begin(mg_ctx *c, Timer &t)
+{
+    for (int i = 0; i < t.n; ++i)
+        if (!t.ev[i]) HIP_TRY(c, hipEventCreate(&t.ev[i]));
+    t.valid = false;
+    HIP_TRY(c, hipEventRecord(t.ev[0], c->stream));
+    return MG_OK;
+}
+int timer_mark(mg_ctx *c, Timer &t, int i)
+{
+    HIP_TRY(c, hipEventRecord(t.ev[i], c->stream));
+    if (i == t.n - 1) t.valid = true;
+    return MG_OK;
+}
+int timer_read(mg_ctx *c, const Timer &t, float *ms)
+{
+    if (t.valid) HIP_TRY(c, hipEventSynchronize(t.ev[t.n - 1]));
+    for (int i = 0; i + 1 < t.n; ++i) {
+        ms[i] = 0.f;
+        if (t.valid) HIP_TRY(c, hipEventElapsedTime(&ms[i], t.ev[i], t.ev[i + 1]));
+    }
     return MG_OK;
 }
 
@@ -3180,42 +3198,38 @@ void fmt_scan(mg_ctx *c, const void *d_len, u64 n, u64 n_part, void *part, void 
 inline dim3 fmt_len_grid(u64 n) { return dim3((unsigned)((n + FMT_TPB / 64 - 1) / (FMT_TPB / 64))); } // a wave per record
 inline dim3 fmt_write_grid(u64 n) { return dim3((unsigned)((n + FMT_ROWS - 1) / FMT_ROWS)); }         // FMT_ROWS records per workgroup
 
-// The device forms of the three encoders (mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*) differ in their two kernels alone:
-// a length pass, the scan of the lengths into d_row_off[n_rows + 1], a write pass into d_out[cap], the four events of the stats call between
-// them.  launch_len(len, meta) and launch_write(row_off) launch the encoder's kernel of that pass (launch_len may take scratch first, hence
-// its return code).  More than cap bytes: MG_ERR_LIMIT with *bytes_out set, row_off whole, nothing written at or behind cap.
+// The device forms of the three encoders (enc: TM_FMT, TM_INFO, TM_BCF) differ in their two kernels alone: a length pass, the scan of the
+// lengths into d_row_off[n_rows + 1], a write pass into d_out[cap], the four events of the stats call between them.  launch_len(len, meta)
+// and launch_write(row_off) launch the encoder's kernel of that pass (launch_len may take scratch first, hence its return code).  More than
+// cap bytes: MG_ERR_LIMIT with *bytes_out set, row_off whole, nothing written at or behind cap.
 template <class LaunchLen, class LaunchWrite>
-int encode_rows(mg_ctx *c, RowPass &rp, const char *who, size_t n_rows, void *d_out, size_t cap, void *d_row_off, uint64_t *bytes_out, LaunchLen launch_len,
+int encode_rows(mg_ctx *c, int enc, const char *who, size_t n_rows, void *d_out, size_t cap, void *d_row_off, uint64_t *bytes_out, LaunchLen launch_len,
                 LaunchWrite launch_write)
 {
     TRY(check_rows_out(c, d_out, cap, d_row_off, bytes_out));
-    if (n_rows >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "%s: more than 2^32 - 1 records in one call", who);
-    for (auto &e : rp.ev)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    rp.valid = false;
+    if (n_rows >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "%s: more than 2^32 - 1 records in one call", who); // (mg_format_site_info*: rows without cells)
+    Timer &t = c->tm[enc];
+    TRY(timer_begin(c, t));
     *bytes_out = 0;
-    HIP_TRY(c, hipEventRecord(rp.ev[0], c->stream));
     if (n_rows == 0) {
         HIP_TRY(c, hipMemsetAsync(d_row_off, 0, 8, c->stream));
-        for (int i = 1; i < 4; ++i) HIP_TRY(c, hipEventRecord(rp.ev[i], c->stream));
-        rp.valid = true;
+        for (int i = 1; i < 4; ++i) TRY(timer_mark(c, t, i));
         return MG_OK;
     }
     void *d_len, *d_meta, *part;
-    TRY(scratch(c, rp.len, 4 * n_rows, &d_len));
-    TRY(scratch(c, rp.meta, 16, &d_meta));
+    TRY(scratch(c, c->s_enc[enc][ES_LEN], 4 * n_rows, &d_len));
+    TRY(scratch(c, c->s_enc[enc][ES_META], 16, &d_meta));
     const u64 n_part = (n_rows + SCAN_CHUNK - 1) / SCAN_CHUNK;
     TRY(scratch(c, c->s_scan, 8 * n_part, &part));
     unsigned long long *meta = (unsigned long long *)d_meta;
     HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
     TRY(launch_len((u32 *)d_len, meta));
-    HIP_TRY(c, hipEventRecord(rp.ev[1], c->stream));
+    TRY(timer_mark(c, t, 1));
     fmt_scan(c, d_len, (u64)n_rows, n_part, part, d_row_off, meta);
-    HIP_TRY(c, hipEventRecord(rp.ev[2], c->stream));
+    TRY(timer_mark(c, t, 2));
     launch_write((const unsigned long long *)d_row_off);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(rp.ev[3], c->stream));
-    rp.valid = true;
+    TRY(timer_mark(c, t, 3));
     unsigned long long total = 0;
     HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3226,42 +3240,41 @@ int encode_rows(mg_ctx *c, RowPass &rp, const char *who, size_t n_rows, void *d_
 }
 
 // device milliseconds of an encoder's most recent call (waits for it): ms_out[0] length pass, [1] scan, [2] write pass
-int rows_stats(mg_ctx *c, RowPass &rp, const char *who, float *ms_out)
+int rows_stats(mg_ctx *c, int enc, const char *who, float *ms_out)
 {
-    if (!rp.valid) return fail(c, MG_ERR_STATE, "no %s yet", who);
-    HIP_TRY(c, hipEventSynchronize(rp.ev[3]));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], rp.ev[i], rp.ev[i + 1]));
-    return MG_OK;
+    if (!c->tm[enc].valid) return fail(c, MG_ERR_STATE, "no %s yet", who);
+    return timer_read(c, c->tm[enc], ms_out);
 }
 
-// the host forms' way in: a batch's cells go up (gt1, gt2 unless haploid, gq, cov and var_allele_off where given), the rows get a place
-struct DevCells {
-    void *gt1 = nullptr, *gt2 = nullptr, *gq = nullptr, *cov = nullptr, *var_allele_off = nullptr;
-    GpCells gp{nullptr, nullptr, nullptr};
-};
-int stage_cells(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, const uint32_t *cov,
-                const uint32_t *var_allele_off, DevCells *d, const GpCells *gp = nullptr)
+// The host forms' way in: a batch's cells go up, *d = h with device pointers.  gt1; gt2 unless haploid; gq where given and read (always, or
+// under the mask alone); whatever else is given -- at n_vars == 0 only when_empty (the encoders and mg_pack_dosage, who take var_allele_off
+// [0 .. n_vars] as it comes; mg_site_counts and mg_sample_counts do not read it then).  cov and allele_class are sized from
+// var_allele_off[n_vars], probs from var_gt_off[n_vars].  What is not uploaded is NULL on the device side.
+int stage_cells(mg_ctx *c, const Cells &h, Cells *d, bool always_gq, bool when_empty)
 {
-    RowStage &s = c->stage;
-    const size_t cells = 4 * (size_t)n_planes * n_vars;
-    TRY(upload(c, s.gt1, gt1, cells, &d->gt1));
-    if (!haploid) TRY(upload(c, s.gt2, gt2, cells, &d->gt2));
-    if (gq) TRY(upload(c, s.gq, gq, cells, &d->gq));
-    if (cov) TRY(upload(c, s.cov, cov, 4 * (size_t)n_planes * var_allele_off[n_vars], &d->cov));
-    if (var_allele_off) TRY(upload(c, s.var_allele_off, var_allele_off, 4 * (n_vars + 1), &d->var_allele_off));
-    if (gp) {
-        void *probs, *var_gt_off, *status;
-        TRY(upload(c, s.probs, gp->probs, 8 * (size_t)n_planes * ((const uint64_t *)gp->var_gt_off)[n_vars], &probs));
-        TRY(upload(c, s.var_gt_off, gp->var_gt_off, 8 * (n_vars + 1), &var_gt_off));
-        TRY(upload(c, s.status, gp->status, (size_t)n_planes * n_vars, &status));
-        d->gp = GpCells{probs, var_gt_off, status};
-    }
-    return MG_OK;
+    *d = h;
+    auto up = [&](int slot, const void *host, bool wanted, size_t bytes, const void **dev) -> int {
+        void *p = nullptr;
+        if (host && wanted) TRY(upload(c, c->stage[slot], host, bytes, &p));
+        *dev = p;
+        return MG_OK;
+    };
+    const bool rest = h.n_vars || when_empty;
+    const size_t cells = (size_t)h.n_planes * h.n_vars, slots = h.var_allele_off && rest ? ((const uint32_t *)h.var_allele_off)[h.n_vars] : 0;
+    TRY(up(ST_GT1, h.gt1, true, 4 * cells, &d->gt1));
+    TRY(up(ST_GT2, h.gt2, !h.haploid, 4 * cells, &d->gt2));
+    TRY(up(ST_GQ, h.gq, always_gq || h.use_mask, 4 * cells, &d->gq));
+    TRY(up(ST_COV, h.cov, rest, 4 * (size_t)h.n_planes * slots, &d->cov));
+    TRY(up(ST_VAR_ALLELE_OFF, h.var_allele_off, rest, 4 * (h.n_vars + 1), &d->var_allele_off));
+    TRY(up(ST_PROBS, h.probs, h.gp, 8 * (size_t)h.n_planes * (h.gp ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->probs));
+    TRY(up(ST_VAR_GT_OFF, h.var_gt_off, h.gp, 8 * (h.n_vars + 1), &d->var_gt_off));
+    TRY(up(ST_STATUS, h.status, rest, cells, &d->status));
+    return up(ST_ALLELE_CLASS, h.allele_class, rest, slots, &d->allele_class);
 }
 int stage_rows(mg_ctx *c, size_t n_rows, size_t cap, void **d_out, void **d_row_off)
 {
-    TRY(scratch(c, c->stage.out, cap ? cap : 1, d_out));
-    return scratch(c, c->stage.row_off, 8 * (n_rows + 1), d_row_off);
+    TRY(scratch(c, c->stage[ST_OUT], cap ? cap : 1, d_out));
+    return scratch(c, c->stage[ST_ROW_OFF], 8 * (n_rows + 1), d_row_off);
 }
 // the host forms' way out, behind the device form that returned rc: row_off and the rows come down (rows that do not fit, MG_ERR_LIMIT with
 // *bytes_out set: row_off and the first cap bytes are still the caller's)
@@ -3275,84 +3288,79 @@ int fetch_rows(mg_ctx *c, int rc, size_t n_rows, const void *d_out, const void *
     return rc;
 }
 
-int format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int masked, int32_t min_gq,
-                        const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out,
-                        const GpCells *gp = nullptr)
+int format_calls_device(mg_ctx *c, const Cells &x, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off, gp));
-    const FmtArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
-                    masked, min_gq, gp ? (const double *)gp->probs : nullptr, gp ? (const u64 *)gp->var_gt_off : nullptr, gp ? (const u8 *)gp->status : nullptr};
+    TRY(check_cells(c, "mg_format_calls", x, true, true));
+    const FmtArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, (const u32 *)x.cov, (const u32 *)x.var_allele_off,
+                    x.use_mask, x.min_gq, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status};
     return encode_rows(
-        c, c->rp_fmt, "mg_format_calls", n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
+        c, TM_FMT, "mg_format_calls", x.n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
-            hipLaunchKernelGGL(gp ? fmt_len_kernel<true> : fmt_len_kernel<false>, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
+            hipLaunchKernelGGL(x.gp ? fmt_len_kernel<true> : fmt_len_kernel<false>, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
             return MG_OK;
         },
         [&](const unsigned long long *row_off) {
-            hipLaunchKernelGGL(gp ? fmt_write_kernel<true> : fmt_write_kernel<false>, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off, (char *)d_text_out,
-                               (u64)text_cap);
+            hipLaunchKernelGGL(x.gp ? fmt_write_kernel<true> : fmt_write_kernel<false>, fmt_write_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off,
+                               (char *)d_text_out, (u64)text_cap);
         });
 }
 
-int format_calls_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int masked, int32_t min_gq,
-                      const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out,
-                      const GpCells *gp = nullptr)
+int format_calls_host(mg_ctx *c, const Cells &x, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_format_calls", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off, gp));
+    TRY(check_cells(c, "mg_format_calls", x, true, true));
     TRY(check_rows_out(c, text_out, text_cap, row_off_out, text_bytes_out));
-    DevCells d;
+    Cells d;
     void *d_text, *d_off;
-    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d, gp));
-    TRY(stage_rows(c, n_vars, text_cap, &d_text, &d_off));
-    const int rc = format_calls_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, masked, min_gq, d.cov, d.var_allele_off, d_text, text_cap, d_off, text_bytes_out,
-                                       gp ? &d.gp : nullptr);
-    return fetch_rows(c, rc, n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
+    TRY(stage_cells(c, x, &d, true, true));
+    TRY(stage_rows(c, x.n_vars, text_cap, &d_text, &d_off));
+    const int rc = format_calls_device(c, d, d_text, text_cap, d_off, text_bytes_out);
+    return fetch_rows(c, rc, x.n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
 }
 } // namespace
 MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
                                      const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
                                      uint64_t *text_bytes_out)
 {
-    return format_calls_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 0, 0, d_cov, d_var_allele_off, d_text_out, text_cap, d_row_off_out, text_bytes_out);
+    return format_calls_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 0, 0, d_var_allele_off, d_cov}, d_text_out, text_cap, d_row_off_out, text_bytes_out);
 }
 MG_EXPORT int mg_format_calls(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
                               const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
                               uint64_t *text_bytes_out)
 {
-    return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, 0, 0, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out);
+    return format_calls_host(c, Cells{n_vars, n_planes, haploid, gt1, gt2, gq, 0, 0, var_allele_off, cov}, text_out, text_cap, row_off_out, text_bytes_out);
 }
 // the same with the genotype of every cell whose gq < min_gq printed as missing
 MG_EXPORT int mg_format_calls_masked_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
                                             int32_t min_gq, const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
                                             void *d_row_off_out, uint64_t *text_bytes_out)
 {
-    return format_calls_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 1, min_gq, d_cov, d_var_allele_off, d_text_out, text_cap, d_row_off_out, text_bytes_out);
+    return format_calls_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 1, min_gq, d_var_allele_off, d_cov}, d_text_out, text_cap, d_row_off_out,
+                               text_bytes_out);
 }
 MG_EXPORT int mg_format_calls_masked(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
                                      int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
                                      uint64_t *row_off_out, uint64_t *text_bytes_out)
 {
-    return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, 1, min_gq, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out);
+    return format_calls_host(c, Cells{n_vars, n_planes, haploid, gt1, gt2, gq, 1, min_gq, var_allele_off, cov}, text_out, text_cap, row_off_out, text_bytes_out);
 }
 // the same with the field GP behind every cell's last: the record's likelihoods in VCF genotype order (call_text_kernels.h)
 MG_EXPORT int mg_format_calls_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                         int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
                                         const void *d_status, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
 {
-    const GpCells gp{d_probs, d_var_gt_off, d_status};
-    return format_calls_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask != 0, min_gq, d_cov, d_var_allele_off, d_text_out, text_cap, d_row_off_out,
-                               text_bytes_out, &gp);
+    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask != 0, min_gq, d_var_allele_off, d_cov, d_status, d_probs, d_var_gt_off, nullptr, true};
+    return format_calls_device(c, x, d_text_out, text_cap, d_row_off_out, text_bytes_out);
 }
 MG_EXPORT int mg_format_calls_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
                                  int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
                                  const uint8_t *status, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
 {
-    const GpCells gp{probs, var_gt_off, status};
-    return format_calls_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, cov, var_allele_off, text_out, text_cap, row_off_out, text_bytes_out, &gp);
+    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, true};
+    return format_calls_host(c, x, text_out, text_cap, row_off_out, text_bytes_out);
 }
 
 // device milliseconds of the most recent mg_format_calls* (rows_stats)
@@ -3360,29 +3368,30 @@ MG_EXPORT int mg_format_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    return rows_stats(c, c->rp_fmt, "mg_format_calls", ms_out);
+    return rows_stats(c, TM_FMT, "mg_format_calls", ms_out);
 }
 
-MG_EXPORT int mg_site_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                    int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_ac, void *d_ns)
+namespace {
+int site_counts_device(mg_ctx *c, const Cells &x, int accumulate, void *d_ac, void *d_ns)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_site_counts", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, nullptr, nullptr));
-    if (n_vars && (!d_var_allele_off || !d_ns)) return fail(c, MG_ERR_ARG, "NULL argument"); // (d_ac may be: records without slots)
-    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_site_counts: more than 2^32 - 1 records in one call");
-    for (auto &e : c->ev_cnt)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->cnt_stats_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_cnt[0], c->stream));
-    if (n_vars) {
-        const SiteArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u32 *)d_var_allele_off, accumulate};
-        hipLaunchKernelGGL(site_count_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_ac, (u32 *)d_ns);
+    TRY(check_cells(c, "mg_site_counts", x, false, x.use_mask));
+    if (x.n_vars && (!x.var_allele_off || !d_ns)) return fail(c, MG_ERR_ARG, "NULL argument"); // (d_ac may be: records without slots)
+    TRY(timer_begin(c, c->tm[TM_SITE]));
+    if (x.n_vars) {
+        const SiteArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, x.use_mask, x.min_gq,
+                         (const u32 *)x.var_allele_off, accumulate};
+        hipLaunchKernelGGL(site_count_kernel, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_ac, (u32 *)d_ns);
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipEventRecord(c->ev_cnt[1], c->stream));
-    c->cnt_stats_valid = true;
-    return MG_OK;
+    return timer_mark(c, c->tm[TM_SITE], 1);
+}
+} // namespace
+MG_EXPORT int mg_site_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                    int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_ac, void *d_ns)
+{
+    return site_counts_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off}, accumulate, d_ac, d_ns);
 }
 
 MG_EXPORT int mg_site_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -3390,18 +3399,19 @@ MG_EXPORT int mg_site_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int ha
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_site_counts", n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, nullptr, nullptr));
+    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off};
+    TRY(check_cells(c, "mg_site_counts", x, false, use_mask));
     if (n_vars && !var_allele_off) return fail(c, MG_ERR_ARG, "NULL argument");
     const size_t slots = n_vars ? var_allele_off[n_vars] : 0;
     if (n_vars && (!ns || (slots && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
-    DevCells d;
+    Cells d;
     void *d_ac, *d_ns;
-    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, use_mask ? gq : nullptr, nullptr, n_vars ? var_allele_off : nullptr, &d));
-    TRY(scratch(c, c->stage.ac, slots ? 4 * slots : 1, &d_ac));
-    TRY(scratch(c, c->stage.ns, n_vars ? 4 * n_vars : 1, &d_ns));
+    TRY(stage_cells(c, x, &d, false, false));
+    TRY(scratch(c, c->stage[ST_AC], slots ? 4 * slots : 1, &d_ac));
+    TRY(scratch(c, c->stage[ST_NS], n_vars ? 4 * n_vars : 1, &d_ns));
     if (accumulate && slots) HIP_TRY(c, hipMemcpyAsync(d_ac, ac, 4 * slots, hipMemcpyHostToDevice, c->stream));
     if (accumulate && n_vars) HIP_TRY(c, hipMemcpyAsync(d_ns, ns, 4 * n_vars, hipMemcpyHostToDevice, c->stream));
-    TRY(mg_site_counts_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, use_mask, min_gq, d.var_allele_off, accumulate, d_ac, d_ns));
+    TRY(site_counts_device(c, d, accumulate, d_ac, d_ns));
     if (slots) HIP_TRY(c, hipMemcpyAsync(ac, d_ac, 4 * slots, hipMemcpyDeviceToHost, c->stream));
     if (n_vars) HIP_TRY(c, hipMemcpyAsync(ns, d_ns, 4 * n_vars, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3416,7 +3426,7 @@ MG_EXPORT int mg_format_site_info_device(mg_ctx *c, size_t n_vars, const void *d
     if (n_vars && (!d_ns || !d_var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
     const InfoArgs a{(u64)n_vars, (const u32 *)d_ac, (const u32 *)d_ns, (const u32 *)d_var_allele_off};
     return encode_rows(
-        c, c->rp_info, "mg_format_site_info", n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
+        c, TM_INFO, "mg_format_site_info", n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
             hipLaunchKernelGGL(info_len_kernel, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
             return MG_OK;
@@ -3434,9 +3444,9 @@ MG_EXPORT int mg_format_site_info(mg_ctx *c, size_t n_vars, const uint32_t *ac, 
     TRY(check_rows_out(c, text_out, text_cap, row_off_out, text_bytes_out));
     if (n_vars && (!ns || !var_allele_off || (var_allele_off[n_vars] && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
     void *d_ac, *d_ns, *d_vao, *d_text, *d_off;
-    TRY(upload(c, c->stage.ac, ac, n_vars ? 4 * (size_t)var_allele_off[n_vars] : 0, &d_ac));
-    TRY(upload(c, c->stage.ns, ns, 4 * n_vars, &d_ns));
-    TRY(upload(c, c->stage.var_allele_off, var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
+    TRY(upload(c, c->stage[ST_AC], ac, n_vars ? 4 * (size_t)var_allele_off[n_vars] : 0, &d_ac));
+    TRY(upload(c, c->stage[ST_NS], ns, 4 * n_vars, &d_ns));
+    TRY(upload(c, c->stage[ST_VAR_ALLELE_OFF], var_allele_off, n_vars ? 4 * (n_vars + 1) : 0, &d_vao));
     TRY(stage_rows(c, n_vars, text_cap, &d_text, &d_off));
     const int rc = mg_format_site_info_device(c, n_vars, d_ac, d_ns, d_vao, d_text, text_cap, d_off, text_bytes_out);
     return fetch_rows(c, rc, n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
@@ -3447,42 +3457,39 @@ MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    if (!c->cnt_stats_valid && !c->rp_info.valid) return fail(c, MG_ERR_STATE, "no mg_site_counts or mg_format_site_info yet");
-    float info[3] = {0.f, 0.f, 0.f}; // (0: none of that kind yet)
-    ms_out[0] = 0.f;
-    if (c->cnt_stats_valid) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_cnt[1]));
-        HIP_TRY(c, hipEventElapsedTime(&ms_out[0], c->ev_cnt[0], c->ev_cnt[1]));
-    }
-    if (c->rp_info.valid) TRY(rows_stats(c, c->rp_info, "mg_format_site_info", info));
+    if (!c->tm[TM_SITE].valid && !c->tm[TM_INFO].valid) return fail(c, MG_ERR_STATE, "no mg_site_counts or mg_format_site_info yet");
+    float info[3];
+    TRY(timer_read(c, c->tm[TM_SITE], &ms_out[0]));
+    TRY(timer_read(c, c->tm[TM_INFO], info));
     ms_out[1] = info[0] + info[1] + info[2];
     return MG_OK;
 }
 
 // ---- the pair table of a multi-sample call set (pair_kernels.h) ------------------------------------------------------------------------
-MG_EXPORT int mg_pack_dosage_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                    int32_t min_gq, const void *d_var_allele_off, void *d_planes_out)
+namespace {
+int pack_dosage_device(mg_ctx *c, const Cells &x, void *d_planes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_pack_dosage", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, nullptr, nullptr));
-    if (!d_var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_dosage: var_allele_off is required");
-    if (n_vars && !d_planes_out) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_pack_dosage: more than 2^32 - 1 records in one call");
-    for (auto &e : c->ev_pack)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->pack_stats_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_pack[0], c->stream));
-    if (n_vars) {
-        const u64 n_words = ((u64)n_vars + 63) / 64;
-        const PackArgs a{(u64)n_vars, n_words, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u32 *)d_var_allele_off};
-        hipLaunchKernelGGL(pack_dosage_kernel, dim3((unsigned)((n_words + PACK_TPB / 64 - 1) / (PACK_TPB / 64)), n_planes), dim3(PACK_TPB), 0, c->stream, a,
+    TRY(check_cells(c, "mg_pack_dosage", x, false, x.use_mask));
+    if (!x.var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_dosage: var_allele_off is required");
+    if (x.n_vars && !d_planes_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    TRY(timer_begin(c, c->tm[TM_PACK]));
+    if (x.n_vars) {
+        const u64 n_words = ((u64)x.n_vars + 63) / 64;
+        const PackArgs a{(u64)x.n_vars, n_words, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, x.use_mask, x.min_gq,
+                         (const u32 *)x.var_allele_off};
+        hipLaunchKernelGGL(pack_dosage_kernel, dim3((unsigned)((n_words + PACK_TPB / 64 - 1) / (PACK_TPB / 64)), x.n_planes), dim3(PACK_TPB), 0, c->stream, a,
                            (unsigned long long *)d_planes_out);
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipEventRecord(c->ev_pack[1], c->stream));
-    c->pack_stats_valid = true;
-    return MG_OK;
+    return timer_mark(c, c->tm[TM_PACK], 1);
+}
+} // namespace
+MG_EXPORT int mg_pack_dosage_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                    int32_t min_gq, const void *d_var_allele_off, void *d_planes_out)
+{
+    return pack_dosage_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off}, d_planes_out);
 }
 
 MG_EXPORT int mg_pack_dosage(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -3490,17 +3497,16 @@ MG_EXPORT int mg_pack_dosage(mg_ctx *c, size_t n_vars, uint32_t n_planes, int ha
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_pack_dosage", n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, nullptr, nullptr));
+    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off};
+    TRY(check_cells(c, "mg_pack_dosage", x, false, use_mask));
     if (!var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_dosage: var_allele_off is required");
     if (n_vars && !planes_out) return fail(c, MG_ERR_ARG, "NULL argument");
-    const size_t cells = 4 * (size_t)n_planes * n_vars, out_bytes = 8 * (size_t)n_planes * 3 * ((n_vars + 63) / 64);
-    void *d1, *d2 = nullptr, *dq = nullptr, *dv, *d_out;
-    TRY(upload(c, c->pstage.gt1, gt1, cells, &d1));
-    if (!haploid) TRY(upload(c, c->pstage.gt2, gt2, cells, &d2));
-    if (use_mask) TRY(upload(c, c->pstage.gq, gq, cells, &dq));
-    TRY(upload(c, c->pstage.var_allele_off, var_allele_off, 4 * (n_vars + 1), &dv));
-    TRY(scratch(c, c->pstage.planes, out_bytes ? out_bytes : 1, &d_out));
-    TRY(mg_pack_dosage_device(c, n_vars, n_planes, haploid, d1, d2, dq, use_mask, min_gq, dv, d_out));
+    const size_t out_bytes = 8 * (size_t)n_planes * 3 * ((n_vars + 63) / 64);
+    Cells d;
+    void *d_out;
+    TRY(stage_cells(c, x, &d, false, true));
+    TRY(scratch(c, c->stage[ST_PLANES], out_bytes ? out_bytes : 1, &d_out));
+    TRY(pack_dosage_device(c, d, d_out));
     if (out_bytes) HIP_TRY(c, hipMemcpyAsync(planes_out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MG_OK;
@@ -3534,10 +3540,7 @@ MG_EXPORT int mg_pair_counts_device(mg_ctx *c, size_t n_words, const void *d_pla
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
     TRY(check_pairs(c, n_words, d_planes_a, n_a, d_planes_b, n_b, d_counts));
-    for (auto &e : c->ev_pair)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->pair_stats_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_pair[0], c->stream));
+    TRY(timer_begin(c, c->tm[TM_PAIR]));
     if (!accumulate) HIP_TRY(c, hipMemsetAsync(d_counts, 0, 8 * (size_t)n_a * n_b * 9, c->stream));
     if (n_words) {
         const u32 tiles_i = (n_a + PAIR_TILE - 1) / PAIR_TILE, tiles_j = (n_b + PAIR_TILE - 1) / PAIR_TILE;
@@ -3548,9 +3551,7 @@ MG_EXPORT int mg_pair_counts_device(mg_ctx *c, size_t n_words, const void *d_pla
         hipLaunchKernelGGL(pair_count_kernel, dim3((unsigned)n_runs, tiles_j, tiles_i), dim3(PAIR_TPB), 0, c->stream, a, (unsigned long long *)d_counts);
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipEventRecord(c->ev_pair[1], c->stream));
-    c->pair_stats_valid = true;
-    return MG_OK;
+    return timer_mark(c, c->tm[TM_PAIR], 1);
 }
 
 MG_EXPORT int mg_pair_counts(mg_ctx *c, size_t n_words, const uint64_t *planes_a, uint32_t n_a, const uint64_t *planes_b, uint32_t n_b, int accumulate, uint64_t *counts)
@@ -3560,9 +3561,9 @@ MG_EXPORT int mg_pair_counts(mg_ctx *c, size_t n_words, const uint64_t *planes_a
     TRY(check_pairs(c, n_words, planes_a, n_a, planes_b, n_b, counts));
     const size_t count_bytes = 8 * (size_t)n_a * n_b * 9;
     void *da, *db = nullptr, *d_counts;
-    TRY(upload(c, c->pstage.pa, planes_a, 8 * (size_t)n_a * 3 * n_words, &da));
-    if (planes_b) TRY(upload(c, c->pstage.pb, planes_b, 8 * (size_t)n_b * 3 * n_words, &db));
-    TRY(scratch(c, c->pstage.counts, count_bytes, &d_counts));
+    TRY(upload(c, c->stage[ST_PA], planes_a, 8 * (size_t)n_a * 3 * n_words, &da));
+    if (planes_b) TRY(upload(c, c->stage[ST_PB], planes_b, 8 * (size_t)n_b * 3 * n_words, &db));
+    TRY(scratch(c, c->stage[ST_COUNTS], count_bytes, &d_counts));
     if (accumulate) HIP_TRY(c, hipMemcpyAsync(d_counts, counts, count_bytes, hipMemcpyHostToDevice, c->stream));
     TRY(mg_pair_counts_device(c, n_words, da, n_a, db, n_b, accumulate, d_counts));
     HIP_TRY(c, hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -3575,26 +3576,18 @@ MG_EXPORT int mg_pairs_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    ms_out[0] = ms_out[1] = 0.f; // (0: none of that kind yet)
-    if (!c->pack_stats_valid && !c->pair_stats_valid) return fail(c, MG_ERR_STATE, "no mg_pack_dosage or mg_pair_counts yet");
-    if (c->pack_stats_valid) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_pack[1]));
-        HIP_TRY(c, hipEventElapsedTime(&ms_out[0], c->ev_pack[0], c->ev_pack[1]));
-    }
-    if (c->pair_stats_valid) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_pair[1]));
-        HIP_TRY(c, hipEventElapsedTime(&ms_out[1], c->ev_pair[0], c->ev_pair[1]));
-    }
-    return MG_OK;
+    ms_out[0] = ms_out[1] = 0.f; // (also where it fails)
+    if (!c->tm[TM_PACK].valid && !c->tm[TM_PAIR].valid) return fail(c, MG_ERR_STATE, "no mg_pack_dosage or mg_pair_counts yet");
+    TRY(timer_read(c, c->tm[TM_PACK], &ms_out[0]));
+    return timer_read(c, c->tm[TM_PAIR], &ms_out[1]);
 }
 
 // ---- the per-sample table of a multi-sample call set (sample_kernels.h) -----------------------------------------------------------------
 namespace {
-int check_sample(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, const void *var_allele_off, const void *counts)
+int check_sample(mg_ctx *c, const Cells &x, const void *counts)
 {
-    TRY(check_cells(c, "mg_sample_counts", n_vars, n_planes, haploid, gt1, gt2, gq, true, nullptr, nullptr)); // (gq: the histogram reads it, mask or none)
-    if (!counts || (n_vars && !var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_sample_counts: more than 2^32 - 1 records in one call");
+    TRY(check_cells(c, "mg_sample_counts", x, false, true)); // (gq: the histogram reads it, mask or none)
+    if (!counts || (x.n_vars && !x.var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
     return MG_OK;
 }
 // The records are cut into runs, one workgroup per plane and run: as many runs as give about SAMPLE_TARGET_WGS workgroups over all
@@ -3609,31 +3602,31 @@ u64 sample_count_plan(u64 n_vars, u32 n_planes, u64 *n_runs)
     *n_runs = (n_vars + run - 1) / run;
     return run;
 }
-} // namespace
 
+int sample_counts_device(mg_ctx *c, const Cells &x, int accumulate, void *d_counts)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_sample(c, x, d_counts));
+    TRY(timer_begin(c, c->tm[TM_SAMPLE]));
+    if (!accumulate) HIP_TRY(c, hipMemsetAsync(d_counts, 0, 8 * (size_t)x.n_planes * MG_SAMPLE_SLOTS, c->stream));
+    if (x.n_vars) {
+        u64 n_runs = 0;
+        const u64 run = sample_count_plan((u64)x.n_vars, x.n_planes, &n_runs);
+        const SampleArgs a{(u64)x.n_vars, run, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, x.use_mask, x.min_gq, (const u8 *)x.status,
+                           (const u32 *)x.cov, (const u32 *)x.var_allele_off, (const u8 *)x.allele_class};
+        hipLaunchKernelGGL(sample_count_kernel, dim3((unsigned)n_runs, x.n_planes), dim3(SAMPLE_TPB), 0, c->stream, a, (unsigned long long *)d_counts);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_SAMPLE], 1);
+}
+} // namespace
 MG_EXPORT int mg_sample_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                       int32_t min_gq, const void *d_status, const void *d_cov, const void *d_var_allele_off, const void *d_allele_class, int accumulate,
                                       void *d_counts)
 {
-    const DeviceGuard on_device(c, LAZY);
-    if (!c) return MG_ERR_ARG;
-    TRY(check_sample(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, d_var_allele_off, d_counts));
-    for (auto &e : c->ev_sample)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->sample_stats_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_sample[0], c->stream));
-    if (!accumulate) HIP_TRY(c, hipMemsetAsync(d_counts, 0, 8 * (size_t)n_planes * MG_SAMPLE_SLOTS, c->stream));
-    if (n_vars) {
-        u64 n_runs = 0;
-        const u64 run = sample_count_plan((u64)n_vars, n_planes, &n_runs);
-        const SampleArgs a{(u64)n_vars, run, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, use_mask, min_gq, (const u8 *)d_status, (const u32 *)d_cov,
-                           (const u32 *)d_var_allele_off, (const u8 *)d_allele_class};
-        hipLaunchKernelGGL(sample_count_kernel, dim3((unsigned)n_runs, n_planes), dim3(SAMPLE_TPB), 0, c->stream, a, (unsigned long long *)d_counts);
-        HIP_TRY(c, hipGetLastError());
-    }
-    HIP_TRY(c, hipEventRecord(c->ev_sample[1], c->stream));
-    c->sample_stats_valid = true;
-    return MG_OK;
+    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov, d_status, nullptr, nullptr, d_allele_class};
+    return sample_counts_device(c, x, accumulate, d_counts);
 }
 
 MG_EXPORT int mg_sample_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -3642,19 +3635,15 @@ MG_EXPORT int mg_sample_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int 
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    TRY(check_sample(c, n_vars, n_planes, haploid, gt1, gt2, gq, var_allele_off, counts));
-    const size_t cells = (size_t)n_planes * n_vars, slots = n_vars ? var_allele_off[n_vars] : 0, count_bytes = 8 * (size_t)n_planes * MG_SAMPLE_SLOTS;
-    void *d1, *d2 = nullptr, *dq, *ds = nullptr, *dc = nullptr, *dv = nullptr, *dk = nullptr, *d_counts;
-    TRY(upload(c, c->sstage.gt1, gt1, 4 * cells, &d1));
-    if (!haploid) TRY(upload(c, c->sstage.gt2, gt2, 4 * cells, &d2));
-    TRY(upload(c, c->sstage.gq, gq, 4 * cells, &dq));
-    if (n_vars) TRY(upload(c, c->sstage.var_allele_off, var_allele_off, 4 * (n_vars + 1), &dv));
-    if (n_vars && status) TRY(upload(c, c->sstage.status, status, cells, &ds));
-    if (n_vars && cov) TRY(upload(c, c->sstage.cov, cov, 4 * (size_t)n_planes * slots, &dc));
-    if (n_vars && allele_class) TRY(upload(c, c->sstage.allele_class, allele_class, slots, &dk));
-    TRY(scratch(c, c->sstage.counts, count_bytes, &d_counts));
+    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov, status, nullptr, nullptr, allele_class};
+    TRY(check_sample(c, x, counts));
+    const size_t count_bytes = 8 * (size_t)n_planes * MG_SAMPLE_SLOTS;
+    Cells d;
+    void *d_counts;
+    TRY(stage_cells(c, x, &d, true, false));
+    TRY(scratch(c, c->stage[ST_COUNTS], count_bytes, &d_counts));
     if (accumulate) HIP_TRY(c, hipMemcpyAsync(d_counts, counts, count_bytes, hipMemcpyHostToDevice, c->stream));
-    TRY(mg_sample_counts_device(c, n_vars, n_planes, haploid, d1, d2, dq, use_mask, min_gq, ds, dc, dv, dk, accumulate, d_counts));
+    TRY(sample_counts_device(c, d, accumulate, d_counts));
     HIP_TRY(c, hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MG_OK;
@@ -3665,69 +3654,64 @@ MG_EXPORT int mg_sample_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    ms_out[0] = 0.f;
-    if (!c->sample_stats_valid) return fail(c, MG_ERR_STATE, "no mg_sample_counts yet");
-    HIP_TRY(c, hipEventSynchronize(c->ev_sample[1]));
-    HIP_TRY(c, hipEventElapsedTime(&ms_out[0], c->ev_sample[0], c->ev_sample[1]));
-    return MG_OK;
+    ms_out[0] = 0.f; // (also where it fails)
+    if (!c->tm[TM_SAMPLE].valid) return fail(c, MG_ERR_STATE, "no mg_sample_counts yet");
+    return timer_read(c, c->tm[TM_SAMPLE], ms_out);
 }
 
 namespace {
-int encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask, int32_t min_gq,
-                            const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out, size_t out_cap,
-                            void *d_row_off_out, uint64_t *bytes_out, const GpCells *gp = nullptr, int32_t key_gp = 0)
+int encode_calls_bcf_device(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap, void *d_row_off_out,
+                            uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, true, d_cov, d_var_allele_off, gp));
-    if (key_gt < 0 || key_gq < 0 || (d_cov && key_cov < 0) || (gp && key_gp < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
-    const BcfArgs a{(u64)n_vars, n_planes, haploid, (const i32 *)d_gt1, (const i32 *)d_gt2, (const i32 *)d_gq, (const u32 *)d_cov, (const u32 *)d_var_allele_off,
-                    use_mask, min_gq, key_gt, key_gq, key_cov, gp ? (const double *)gp->probs : nullptr, gp ? (const u64 *)gp->var_gt_off : nullptr,
-                    gp ? (const u8 *)gp->status : nullptr, key_gp};
+    TRY(check_cells(c, "mg_encode_calls_bcf", x, true, true));
+    if (key_gt < 0 || key_gq < 0 || (x.cov && key_cov < 0) || (x.gp && key_gp < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
+    const BcfArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, (const u32 *)x.cov, (const u32 *)x.var_allele_off,
+                    x.use_mask, x.min_gq, key_gt, key_gq, key_cov, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, key_gp};
     void *d_types = nullptr; // the records' type codes: what the length pass found, for the write pass
     return encode_rows(
-        c, c->rp_bcf, "mg_encode_calls_bcf", n_vars, d_out, out_cap, d_row_off_out, bytes_out,
+        c, TM_BCF, "mg_encode_calls_bcf", x.n_vars, d_out, out_cap, d_row_off_out, bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
-            TRY(scratch(c, c->s_bcf_types, 3 * n_vars, &d_types));
-            hipLaunchKernelGGL(gp ? bcf_len_kernel<true> : bcf_len_kernel<false>, fmt_len_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types, meta);
+            TRY(scratch(c, c->s_enc[TM_BCF][ES_TYPES], 3 * x.n_vars, &d_types));
+            hipLaunchKernelGGL(x.gp ? bcf_len_kernel<true> : bcf_len_kernel<false>, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types,
+                               meta);
             return MG_OK;
         },
         [&](const unsigned long long *row_off) {
-            hipLaunchKernelGGL(gp ? bcf_write_kernel<true> : bcf_write_kernel<false>, fmt_write_grid(n_vars), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types,
-                               row_off, (char *)d_out, (u64)out_cap);
+            hipLaunchKernelGGL(x.gp ? bcf_write_kernel<true> : bcf_write_kernel<false>, fmt_write_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a,
+                               (const unsigned char *)d_types, row_off, (char *)d_out, (u64)out_cap);
         });
 }
 
-int encode_calls_bcf_host(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask, int32_t min_gq,
-                          const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out, size_t out_cap,
-                          uint64_t *row_off_out, uint64_t *bytes_out, const GpCells *gp = nullptr, int32_t key_gp = 0)
+int encode_calls_bcf_host(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap, uint64_t *row_off_out,
+                          uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    TRY(check_cells(c, "mg_encode_calls_bcf", n_vars, n_planes, haploid, gt1, gt2, gq, true, cov, var_allele_off, gp));
+    TRY(check_cells(c, "mg_encode_calls_bcf", x, true, true));
     TRY(check_rows_out(c, out, out_cap, row_off_out, bytes_out));
-    DevCells d;
+    Cells d;
     void *d_out, *d_off;
-    TRY(stage_cells(c, n_vars, n_planes, haploid, gt1, gt2, gq, cov, var_allele_off, &d, gp));
-    TRY(stage_rows(c, n_vars, out_cap, &d_out, &d_off));
-    const int rc = encode_calls_bcf_device(c, n_vars, n_planes, haploid, d.gt1, d.gt2, d.gq, use_mask, min_gq, d.cov, d.var_allele_off, key_gt, key_gq, key_cov, d_out,
-                                           out_cap, d_off, bytes_out, gp ? &d.gp : nullptr, key_gp);
-    return fetch_rows(c, rc, n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
+    TRY(stage_cells(c, x, &d, true, true));
+    TRY(stage_rows(c, x.n_vars, out_cap, &d_out, &d_off));
+    const int rc = encode_calls_bcf_device(c, d, key_gt, key_gq, key_cov, key_gp, d_out, out_cap, d_off, bytes_out);
+    return fetch_rows(c, rc, x.n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
 }
 } // namespace
 MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                          int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
                                          size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
 {
-    return encode_calls_bcf_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, key_gt, key_gq, key_cov, d_out, out_cap,
-                                   d_row_off_out, bytes_out);
+    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov};
+    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, 0, d_out, out_cap, d_row_off_out, bytes_out);
 }
 MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
                                   int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
                                   size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
 {
-    return encode_calls_bcf_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, key_gt, key_gq, key_cov, out, out_cap, row_off_out,
-                                 bytes_out);
+    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov};
+    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, 0, out, out_cap, row_off_out, bytes_out);
 }
 // the same with the float field GP behind the record's last (bcf_kernels.h)
 MG_EXPORT int mg_encode_calls_bcf_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
@@ -3735,18 +3719,16 @@ MG_EXPORT int mg_encode_calls_bcf_gp_device(mg_ctx *c, size_t n_vars, uint32_t n
                                             const void *d_status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap,
                                             void *d_row_off_out, uint64_t *bytes_out)
 {
-    const GpCells gp{d_probs, d_var_gt_off, d_status};
-    return encode_calls_bcf_device(c, n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, key_gt, key_gq, key_cov, d_out, out_cap,
-                                   d_row_off_out, bytes_out, &gp, key_gp);
+    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov, d_status, d_probs, d_var_gt_off, nullptr, true};
+    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, key_gp, d_out, out_cap, d_row_off_out, bytes_out);
 }
 MG_EXPORT int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
                                      int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
                                      const uint8_t *status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap,
                                      uint64_t *row_off_out, uint64_t *bytes_out)
 {
-    const GpCells gp{probs, var_gt_off, status};
-    return encode_calls_bcf_host(c, n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, key_gt, key_gq, key_cov, out, out_cap, row_off_out,
-                                 bytes_out, &gp, key_gp);
+    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, true};
+    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, key_gp, out, out_cap, row_off_out, bytes_out);
 }
 
 // device milliseconds of the most recent mg_encode_calls_bcf* (rows_stats)
@@ -3754,7 +3736,7 @@ MG_EXPORT int mg_bcf_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    return rows_stats(c, c->rp_bcf, "mg_encode_calls_bcf", ms_out);
+    return rows_stats(c, TM_BCF, "mg_encode_calls_bcf", ms_out);
 }
 
 // timing and counts of the most recent mg_cover_blocks_device (waits for it)
