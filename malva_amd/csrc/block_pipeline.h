@@ -347,6 +347,9 @@ __device__ bool fw_walk(const BlockBatch &B, int b0, int b1, int i, int step, Fw
     bool halt = false;
     for (int j = i + step; j >= b0 && j < b1 && !halt; j += step) {
         if (j - i > FW_REACH || i - j > FW_REACH) return false; // (the reference walks to the block's end: so does the workgroup kernel)
+        // a block that steps back in position (an unsorted file): get_ref_subs (var_block.hpp:682-702) then takes the rest of the
+        // sequence for the negative gap between two members -- the host enumerator's case, by way of the workgroup kernel
+        if (step > 0 ? B.pos[j] < B.pos[j - 1] : B.pos[j] > B.pos[j + 1]) return false;
         if (!B.present[j]) continue;
         if (ov(i, j)) continue;
         const int gain = (int)B.ref_size[j] - (int)B.min_size[j];

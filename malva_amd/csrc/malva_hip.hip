@@ -2915,7 +2915,9 @@ template <int MODE> int blocks_tier2(BlocksRun &R, u32 *d_cov, u8 *d_overflow, u
             hipLaunchKernelGGL(fw_picks_kernel<true>, dim3(R.cus * 4), dim3(TPB), 0, c->stream, R.B, W, 64, cap_eff);
         } else {
             hipLaunchKernelGGL(fw_picks_kernel<false>, dim3(R.cus * 6), dim3(TPB), 0, c->stream, R.B, W, G, cap_eff);
-            if (G < 64) hipLaunchKernelGGL(fw_picks_kernel<true>, dim3(R.cus * 4), dim3(TPB), 0, c->stream, R.B, W, 64, cap_eff);
+            // (at G = 64 too: a chain that outgrew the whole set was LISTED by the launch above, and only this one hands its record on to
+            //  tier 3 -- without it the record kept a coverage of zero and no flag: tests/test_gpu_block_edges.py C-share-40-385)
+            hipLaunchKernelGGL(fw_picks_kernel<true>, dim3(R.cus * 4), dim3(TPB), 0, c->stream, R.B, W, 64, cap_eff);
         }
         hipLaunchKernelGGL(fw_eval_kernel<MODE>, dim3(R.cus * 8), dim3(TPB), 0, c->stream, R.B, W, view(c, MG_BF_ALT), view(c), d_cov, d_overflow, d_cursor, row0,
                            d_evaluated);

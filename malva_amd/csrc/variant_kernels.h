@@ -313,7 +313,21 @@ __device__ __forceinline__ bool iso_index_body(const u8 *reference, u64 site_off
         const int alen = (int)(allele_off[a0 + a + 1] - allele_off[a0 + a]);
         const int mp = k / 2 - alen / 2, ms = (k + 1) / 2 - (alen - alen / 2);
         if (mp < 0 || ms < 0) return false; // an allele of k bases or more: not this kernel's case
-        if ((lbad >> (lmax - mp)) != 0 || (ms != 0 && (rbad & ((1ULL << ms) - 1)) != 0)) return false;
+        if ((lbad >> (lmax - mp)) != 0 || (ms != 0 && (rbad & ((1ULL << ms) - 1)) != 0)) {
+            // (the masks know four bases at a time: look at the window's own bases before giving the record up)
+            bool in_window = false;
+            for (int x = 1; x <= mp; ++x) {
+                bool o;
+                acgt_code(site[-x], &o);
+                in_window |= !o;
+            }
+            for (int x = 0; x < ms; ++x) {
+                bool o;
+                acgt_code(site[ref_size + x], &o);
+                in_window |= !o;
+            }
+            if (in_window) return false;
+        }
         const u8 *al = pool + allele_off[a0 + a];
         U128 L{0, 0};
         bool fast = true;
@@ -529,7 +543,7 @@ struct PanelView {
     u32 n_samples;
 };
 
-__device__ bool bk_chains(const BlockBatch &B, int b0, int b1, int i, int step, bool sorted, int max_gain, BkChains *out)
+__device__ bool bk_chains(const BlockBatch &B, int b0, int b1, int i, int step, int max_gain, BkChains *out)
 {
     const int k = B.k;
     auto ov = [&](int x, int y) { // overlapping(left, right) with (x, y) given in scan order
@@ -545,17 +559,16 @@ __device__ bool bk_chains(const BlockBatch &B, int b0, int b1, int i, int step, 
     // The reference walks to the end of the block whatever happens (var_block.hpp:436-525: O(B) per variant, O(B^2) per
     // block).  Nothing can join a chain once the walk is beyond the reach of every chain -- positions only move away and
     // a chain's reach grows only when something joins -- so with sorted positions the walk stops there: same chains.
-    // (`sorted`: positions never decrease along the block, `max_gain`: its largest ref_size - min_size -- the workgroup looks)
+    // (The block IS sorted: the workgroup looks, and leaves a block that steps back to the host.  `max_gain`: the block's
+    // largest ref_size - min_size, which the workgroup finds in the same look.)
     for (int j = i + step; j >= b0 && j < b1 && !halt; j += step) {
-        if (sorted) {
-            int max_sum = 0;
-            for (int c = 0; c < out->n; ++c) max_sum = max(max_sum, out->sum[c]);
-            // (the same float test as `nr`, on the largest left side any chain can still present: it is monotone in both
-            // arguments, so beyond the first position it rejects it rejects everything)
-            if (step > 0 ? !near_f32(B.pos[i] + (int)B.ref_size[i] - (int)B.min_size[i] - 1 + max_sum, k, B.pos[j])
-                         : !near_f32(B.pos[j] + max_gain - 1 + max_sum, k, B.pos[i]))
-                break;
-        }
+        int max_sum = 0;
+        for (int c = 0; c < out->n; ++c) max_sum = max(max_sum, out->sum[c]);
+        // (the same float test as `nr`, on the largest left side any chain can still present: it is monotone in both
+        // arguments, so beyond the first position it rejects it rejects everything)
+        if (step > 0 ? !near_f32(B.pos[i] + (int)B.ref_size[i] - (int)B.min_size[i] - 1 + max_sum, k, B.pos[j])
+                     : !near_f32(B.pos[j] + max_gain - 1 + max_sum, k, B.pos[i]))
+            break;
         if (!B.present[j]) continue;
         if (ov(i, j)) continue;
         const int gain = (int)B.ref_size[j] - (int)B.min_size[j];
@@ -736,9 +749,13 @@ __global__ void __launch_bounds__(TPB) cover_blocks_kernel(BlockBatch B, const u
         if (un) sh_unsorted = 1;
     }
     __syncthreads();
+    // a block that steps back in position: the reference takes the rest of the sequence for a negative gap between two members of a
+    // chain (get_ref_subs, var_block.hpp:682-702: a negative count as a size_t) -- left to the host enumerator, which follows it
+    if (sh_unsorted && threadIdx.x == 0) sh_bad = 1;
+    __syncthreads();
     // the two walks (get_combs_on_the_left / _right) are independent: one lane of wave 0 and one of wave 1 take one each
     if (sh_eligible && !sh_bad && (threadIdx.x == 0 || threadIdx.x == 64))
-        if (!bk_chains(B, b0, b1, g, threadIdx.x == 0 ? -1 : +1, !sh_unsorted, sh_max_gain, threadIdx.x == 0 ? &sh_left : &sh_right)) atomicOr(&sh_bad, 1);
+        if (!bk_chains(B, b0, b1, g, threadIdx.x == 0 ? -1 : +1, sh_max_gain, threadIdx.x == 0 ? &sh_left : &sh_right)) atomicOr(&sh_bad, 1);
     __syncthreads();
     if (sh_bad) {
         if (threadIdx.x == 0) overflow[g] = 1;
