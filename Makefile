@@ -61,7 +61,14 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
 
+# the host side of --cohort-priors (option values, --priors-out) under AddressSanitizer and UBSan: a stand-alone program, run on the CPU
+sanitize-host: bin/cohort_priors_host_check
+	bin/cohort_priors_host_check bin
+bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
+
 clean:
 	rm -rf malva_amd/lib bin oracle/libmalva_oracle.so oracle/_ref
 
-.PHONY: all lib cli oracle ref microbench clean
+.PHONY: all lib cli oracle ref microbench sanitize-host clean

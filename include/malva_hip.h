@@ -649,6 +649,57 @@ int mg_sample_counts_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int h
                             void *d_counts);
 int mg_sample_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- allele priors re-estimated from the cohort -------------------------------------
+ * mg_genotype_cohort: the batch's allele frequencies are re-estimated from all of its planes (a few EM steps from the panel's
+ * priors, anchored to them), then every cell is genotyped under the result.  The reference genotypes one individual and has no
+ * such step: there is NO reference call to cite for the estimate.  The per-cell part is mg_genotype's -- VB::genotype
+ * (var_block.hpp:224-330) and the normalise / first-strict-max / GQ step (:366-394).
+ * Inputs as for mg_genotype, plus planes: cov is [n_planes][slots] uint32, plane-major, slots = var_allele_off[n_vars]; freq is
+ * [slots] float, the panel's priors f0; error_rate, max_cov, haploid; iters T (0..64); weight w (finite, >= 0).  n_planes 1..64.
+ * For a record with A alleles, ploidy = 1 in haploid mode, else 2.
+ *   Status.  The status of a plane's cell is the one mg_genotype gives it (MG_GT_*); it depends on the coverages alone.
+ *   Which records.  A record is re-estimated when 2 <= A <= MG_PRIOR_MAX_ALLELES and T > 0.  Any other record keeps f = f0,
+ *   reports n_informative = 0 and is genotyped exactly as mg_genotype genotypes it.
+ *   Iteration t = 1..T starts from f = f_{t-1}, f_0 = f0.
+ *     Posteriors.  For every plane p whose status is MG_GT_NORMAL: the raw values of all genotypes in the reference's list order
+ *     (a outer, c >= a inner; haploid: the alleles) under f, and their sum 0.0 + v0 + v1 + .., left to right, exactly as
+ *     mg_genotype makes them.  Plane p COUNTS in this iteration when that sum is finite and > 0; its posteriors are q_g = v_g / sum.
+ *     Expected copies.  For each allele a, e_p[a] starts at 0.0 and walks the genotype list in order: + 2.0 * q_g for the
+ *     homozygous genotype of a, + q_g for every heterozygous genotype that contains a; in haploid mode + q_g for genotype a.  A
+ *     plane that does not count has e_p[a] = +0.0.
+ *     Sum over planes, in a fixed tree order.  P' is the smallest power of two >= n_planes; x[i] = e_i[a] for i < n_planes and
+ *     +0.0 above; for s = P'/2, P'/4, .., 1: x[i] = x[i] + x[i + s] for i < s; c[a] = x[0].  n is the number of planes that count.
+ *     Update.  n == 0: the frequencies stay as they are.  Otherwise for every ALT allele a >= 1:
+ *       f_t[a] = (float)((c[a] + w * (double)f0[a]) / ((double)(ploidy * n) + w))
+ *     -- the multiply, the add, the divide and the cast each rounded on its own -- and the REF allele follows the panel
+ *     parser's rule: acc = 0.0 (double), plus 0.f, plus the ALT values f_t[1], f_t[2], .. in order; f_t[0] = (float)(1.0 - acc),
+ *     or 0.0f when that is negative.
+ *   w anchors the estimate to the panel's prior with the weight of w allele copies (a MAP estimate under a Dirichlet prior); it
+ *   keeps a small cohort from driving a frequency to an absorbing 0.  A record whose f_t equals f_{t-1} bit for bit stops early:
+ *   the following iterations would repeat it.
+ * Outputs after T iterations: freq_out[slots] = f_T; n_informative[v] = n of the last iteration that ran; gt1 / gt2 / gq / status
+ * [n_planes][n_vars], every plane's cell as mg_genotype makes it from (cov_p, f_T); probs (optional, with var_gt_off
+ * [n_vars + 1]) [n_planes][var_gt_off[n_vars]], laid out as mg_format_calls_gp reads it.
+ * Numerics: nothing is contracted into an FMA; every logf and exp is mg_genotype's restatement of the host libm's, every ln(n)
+ * for n < 65536 its host-made table, so with every record's total coverage below 65536 the whole result is bit-identical to a
+ * CPU restatement of the above.  At or beyond that total: the cells of a record the entry does not re-estimate are computed
+ * again on the host with libm by the host form (as in mg_genotype) and are bit-identical at every total; a re-estimated record
+ * uses the device's log(double) there, in both forms, as mg_genotype_device does -- with at most 8 alleles that takes a
+ * max_cov of 8192 or more.
+ * n_vars == 0 is legal.  iters > 64, a negative or non-finite weight, n_planes out of range, a NULL required array with
+ * n_vars > 0, probs without var_gt_off: MG_ERR_ARG, nothing written.  The context need not be in cohort mode: the call reads
+ * arrays and no counters.  The host form synchronises; the device form (every array a device pointer) is asynchronous on the
+ * context's stream.  mg_cohort_prior_stats (waits): ms_out[1], device milliseconds of the most recent mg_genotype_cohort*;
+ * MG_ERR_STATE before the first. */
+#define MG_PRIOR_MAX_ALLELES 8
+int mg_genotype_cohort(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, const uint32_t *cov, const float *freq, const uint32_t *var_allele_off,
+                       float error_rate, int max_cov, int haploid, uint32_t iters, double weight, float *freq_out, uint32_t *n_informative,
+                       int32_t *gt1, int32_t *gt2, int32_t *gq, uint8_t *status, double *probs, const uint64_t *var_gt_off);
+int mg_genotype_cohort_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, const void *d_cov, const void *d_freq, const void *d_var_allele_off,
+                              float error_rate, int max_cov, int haploid, uint32_t iters, double weight, void *d_freq_out, void *d_n_informative,
+                              void *d_gt1, void *d_gt2, void *d_gq, void *d_status, void *d_probs, const void *d_var_gt_off);
+int mg_cohort_prior_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- the sample columns of a multi-sample BCF --------------------------------------
  * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
  * parity with htslib unpinned).  Arrays, n_planes (1..64), the host and _device forms, the stream behaviour and the buffer

@@ -128,6 +128,9 @@ def lib():
         "mg_sample_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, it, vp],
         "mg_sample_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, it, vp],
         "mg_sample_stats": [vp, vp],
+        "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mg_cohort_prior_stats": [vp, vp],
         "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
@@ -196,7 +199,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
-            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -812,6 +815,42 @@ class Context:
         """-> device ms of the most recent sample_counts"""
         ms = (C.c_float * 1)()
         self._ck(self._L.mg_sample_stats(self.h, ms))
+        return float(ms[0])
+
+    # allele priors re-estimated from the planes of a batch, and the cells genotyped under them
+    def genotype_cohort(self, cov, freq, var_allele_off, error_rate, max_cov, haploid, iters=5, weight=1.0, want_probs=False):
+        """cov: [planes, slots] uint32; freq: [slots] float32 -> (freq_out [slots] float32, n_informative [n_vars] uint32, gt1, gt2, gq
+        [planes, n_vars] int32, status [planes, n_vars] uint8, probs [planes, var_gt_off[-1]] float64 or None, var_gt_off or None): the
+        definition is mg_genotype_cohort's in include/malva_hip.h"""
+        cov = np.ascontiguousarray(cov, dtype=np.uint32)
+        freq = np.ascontiguousarray(freq, dtype=np.float32)
+        vo = np.ascontiguousarray(var_allele_off, dtype=np.uint32)
+        planes, n = cov.shape[0], len(vo) - 1
+        assert cov.shape == (planes, int(vo[n])) and freq.shape == (int(vo[n]),)
+        fo, ni = np.zeros(len(freq), dtype=np.float32), np.zeros(n, dtype=np.uint32)
+        g1, g2, gq = (np.zeros((planes, n), dtype=np.int32) for _ in range(3))
+        st = np.zeros((planes, n), dtype=np.uint8)
+        probs = goff = None
+        if want_probs:
+            A = np.diff(vo.astype(np.int64))
+            goff = np.zeros(n + 1, dtype=np.uint64)
+            goff[1:] = np.cumsum(A if haploid else A * (A + 1) // 2)
+            probs = np.zeros((planes, int(goff[-1])), dtype=np.float64)
+        self._ck(self._L.mg_genotype_cohort(self.h, n, planes, _p(cov), _p(freq), _p(vo), C.c_float(error_rate), max_cov, int(haploid), int(iters), float(weight),
+                                            _p(fo), _p(ni), _p(g1), _p(g2), _p(gq), _p(st), _p(probs), _p(goff)))
+        return fo, ni, g1, g2, gq, st, probs, goff
+
+    def genotype_cohort_device(self, n_vars, planes, d_cov, d_freq, d_var_allele_off, error_rate, max_cov, haploid, iters, weight, d_freq_out, d_n_informative,
+                               d_g1, d_g2, d_gq, d_st, d_probs=None, d_gt_off=None):
+        v = C.c_void_p
+        self._ck(self._L.mg_genotype_cohort_device(self.h, n_vars, planes, v(d_cov), v(d_freq), v(d_var_allele_off), C.c_float(error_rate), max_cov, int(haploid),
+                                                   int(iters), float(weight), v(d_freq_out), v(d_n_informative), v(d_g1), v(d_g2), v(d_gq), v(d_st), v(d_probs),
+                                                   v(d_gt_off)))
+
+    def cohort_prior_stats(self):
+        """-> device ms of the most recent genotype_cohort"""
+        ms = (C.c_float * 1)()
+        self._ck(self._L.mg_cohort_prior_stats(self.h, ms))
         return float(ms[0])
 
     # the sample columns of a multi-sample BCF

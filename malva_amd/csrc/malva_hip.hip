@@ -42,6 +42,7 @@ constexpr int TPB = 256;
 #include "site_tags_kernels.h"
 #include "pair_kernels.h"
 #include "sample_kernels.h"
+#include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
 #include "reads_kernels.h"
 
@@ -86,7 +87,7 @@ struct Timer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -98,6 +99,7 @@ enum {
     ST_GT1, ST_GT2, ST_GQ, ST_COV, ST_VAR_ALLELE_OFF, ST_PROBS, ST_VAR_GT_OFF, ST_STATUS, ST_ALLELE_CLASS, // a batch's cells (stage_cells)
     ST_AC, ST_NS, ST_PLANES, ST_PA, ST_PB, ST_COUNTS,                                                      // the counting calls' tables
     ST_OUT, ST_ROW_OFF,                                                                                    // an encoder's rows (stage_rows)
+    ST_FREQ, ST_FREQ_OUT, ST_NINF,                                                                         // mg_genotype_cohort's priors
     ST_COUNT
 };
 
@@ -165,7 +167,7 @@ struct mg_ctx {
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
     hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
     // the merged-batch section: each stats call reports the latest call of its own kinds, hence a timer per kind
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -3659,6 +3661,109 @@ MG_EXPORT int mg_sample_stats(mg_ctx *c, float *ms_out)
     ms_out[0] = 0.f; // (also where it fails)
     if (!c->tm[TM_SAMPLE].valid) return fail(c, MG_ERR_STATE, "no mg_sample_counts yet");
     return timer_read(c, c->tm[TM_SAMPLE], ms_out);
+}
+
+// ---- allele priors re-estimated from the planes of a batch (cohort_prior_kernels.h) ------------------------------------------------------
+namespace {
+int check_cohort_prior(mg_ctx *c, size_t n_vars, uint32_t n_planes, const void *cov, const void *freq, const void *var_allele_off, uint32_t iters, double weight,
+                       const void *freq_out, const void *n_informative, const void *gt1, const void *gt2, const void *gq, const void *status, const void *probs,
+                       const void *var_gt_off)
+{
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_genotype_cohort takes 1..64 planes");
+    if (iters > 64) return fail(c, MG_ERR_ARG, "mg_genotype_cohort takes at most 64 iterations");
+    if (!std::isfinite(weight) || weight < 0) return fail(c, MG_ERR_ARG, "mg_genotype_cohort takes a finite weight >= 0");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_genotype_cohort: more than 2^32 - 1 records in one call");
+    if (n_vars && (!cov || !freq || !var_allele_off || !freq_out || !n_informative || !gt1 || !gt2 || !gq || !status)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (probs && !var_gt_off) return fail(c, MG_ERR_ARG, "probs needs var_gt_off");
+    return MG_OK;
+}
+} // namespace
+
+MG_EXPORT int mg_genotype_cohort_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, const void *d_cov, const void *d_freq, const void *d_var_allele_off, float error_rate,
+                                        int max_cov, int haploid, uint32_t iters, double weight, void *d_freq_out, void *d_n_informative, void *d_gt1, void *d_gt2,
+                                        void *d_gq, void *d_status, void *d_probs, const void *d_var_gt_off)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cohort_prior(c, n_vars, n_planes, d_cov, d_freq, d_var_allele_off, iters, weight, d_freq_out, d_n_informative, d_gt1, d_gt2, d_gq, d_status, d_probs,
+                           d_var_gt_off));
+    GenoParams p;
+    if (n_vars) TRY(fill_geno_params(c, error_rate, max_cov, haploid, &p)); // (may synchronise: before the timer starts)
+    TRY(timer_begin(c, c->tm[TM_PRIOR]));
+    if (n_vars) {
+        u32 seg_log2 = 0;
+        while ((1u << seg_log2) < n_planes) ++seg_log2;
+        const u32 run = std::max<u32>(PRIOR_TPB >> seg_log2, PRIOR_MIN_RUN); // a multiple of the 256 >> seg_log2 records four waves hold at a time
+        const PriorArgs a{(u64)n_vars, n_planes, seg_log2, run, iters, weight, (const u32 *)d_cov, (const float *)d_freq, (const u32 *)d_var_allele_off,
+                          (float *)d_freq_out, (u32 *)d_n_informative, (i32 *)d_gt1, (i32 *)d_gt2, (i32 *)d_gq, (u8 *)d_status, (double *)d_probs,
+                          (const u64 *)d_var_gt_off};
+        hipLaunchKernelGGL(cohort_prior_kernel, dim3((unsigned)((n_vars + run - 1) / run)), dim3(PRIOR_TPB), 0, c->stream, a, p);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_PRIOR], 1);
+}
+
+MG_EXPORT int mg_genotype_cohort(mg_ctx *c, size_t n_vars, uint32_t n_planes, const uint32_t *cov, const float *freq, const uint32_t *var_allele_off, float error_rate,
+                                 int max_cov, int haploid, uint32_t iters, double weight, float *freq_out, uint32_t *n_informative, int32_t *gt1, int32_t *gt2,
+                                 int32_t *gq, uint8_t *status, double *probs, const uint64_t *var_gt_off)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cohort_prior(c, n_vars, n_planes, cov, freq, var_allele_off, iters, weight, freq_out, n_informative, gt1, gt2, gq, status, probs, var_gt_off));
+    const size_t na = n_vars ? var_allele_off[n_vars] : 0, ng = probs && n_vars ? var_gt_off[n_vars] : 0, cells = (size_t)n_planes * n_vars;
+    void *d_cov = nullptr, *d_freq = nullptr, *d_off = nullptr, *d_fo = nullptr, *d_ni = nullptr, *d_g1 = nullptr, *d_g2 = nullptr, *d_gq = nullptr, *d_st = nullptr,
+         *d_pr = nullptr, *d_go = nullptr;
+    if (n_vars) {
+        TRY(upload(c, c->stage[ST_COV], cov, 4 * (size_t)n_planes * na, &d_cov));
+        TRY(upload(c, c->stage[ST_FREQ], freq, 4 * na, &d_freq));
+        TRY(upload(c, c->stage[ST_VAR_ALLELE_OFF], var_allele_off, 4 * (n_vars + 1), &d_off));
+        TRY(scratch(c, c->stage[ST_FREQ_OUT], 4 * (na ? na : 1), &d_fo));
+        TRY(scratch(c, c->stage[ST_NINF], 4 * n_vars, &d_ni));
+        TRY(scratch(c, c->stage[ST_GT1], 4 * cells, &d_g1));
+        TRY(scratch(c, c->stage[ST_GT2], 4 * cells, &d_g2));
+        TRY(scratch(c, c->stage[ST_GQ], 4 * cells, &d_gq));
+        TRY(scratch(c, c->stage[ST_STATUS], cells, &d_st));
+        if (probs) {
+            TRY(scratch(c, c->stage[ST_PROBS], 8 * ((size_t)n_planes * ng ? (size_t)n_planes * ng : 1), &d_pr));
+            TRY(upload(c, c->stage[ST_VAR_GT_OFF], var_gt_off, 8 * (n_vars + 1), &d_go));
+        }
+    }
+    TRY(mg_genotype_cohort_device(c, n_vars, n_planes, d_cov, d_freq, d_off, error_rate, max_cov, haploid, iters, weight, d_fo, d_ni, d_g1, d_g2, d_gq, d_st, d_pr, d_go));
+    if (!n_vars) return MG_OK;
+    if (na) HIP_TRY(c, hipMemcpyAsync(freq_out, d_fo, 4 * na, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(n_informative, d_ni, 4 * n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(gt1, d_g1, 4 * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(gt2, d_g2, 4 * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(gq, d_gq, 4 * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(status, d_st, cells, hipMemcpyDeviceToHost, c->stream));
+    if (probs && ng) HIP_TRY(c, hipMemcpyAsync(probs, d_pr, 8 * (size_t)n_planes * ng, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // cells of the records the entry does not re-estimate that took an ln(n) from the device's log(double): again on the host, with libm, as in
+    // mg_genotype (a re-estimated record keeps the device's values: reaching MG_LN_TABLE with at most 8 alleles takes a max_cov of 8192)
+    for (size_t v = 0; v < n_vars; ++v) {
+        const uint32_t a0 = var_allele_off[v], A = var_allele_off[v + 1] - a0;
+        if (iters > 0 && A >= 2 && A <= MG_PRIOR_MAX_ALLELES) continue;
+        for (size_t pl = 0; pl < n_planes; ++pl) {
+            const size_t cell = pl * n_vars + v;
+            if (status[cell] != 0) continue;
+            const uint32_t *cv = cov + pl * na + a0;
+            int isum = 0;
+            for (uint32_t al = 0; al < A; ++al) isum += (int)cv[al];
+            if (isum < MG_LN_TABLE) continue;
+            host_genotype_one(cv, freq + a0, (int)A, (u32)isum, error_rate, haploid, gt1 + cell, gt2 + cell, gq + cell, probs ? probs + pl * ng + var_gt_off[v] : nullptr);
+        }
+    }
+    return MG_OK;
+}
+
+// device milliseconds (waits for them) of the most recent mg_genotype_cohort*
+MG_EXPORT int mg_cohort_prior_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = 0.f; // (also where it fails)
+    if (!c->tm[TM_PRIOR].valid) return fail(c, MG_ERR_STATE, "no mg_genotype_cohort yet");
+    return timer_read(c, c->tm[TM_PRIOR], ms_out);
 }
 
 namespace {

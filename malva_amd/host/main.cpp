@@ -29,6 +29,7 @@
 #include "reads.hpp"
 #include "cohort.hpp"
 #include "bcf_out.hpp"
+#include "cohort_priors.hpp"
 extern "C" {
 #include "malva_hip.h"
 }
@@ -103,6 +104,21 @@ const char *USAGE =
     "                                        and histogram, the coverage sum, the genotyper's status codes, and CALL_RATE, HET_HOM, TSTV,\n"
     "                                        MEAN_GQ, MEAN_COV ('.' for 0 / 0).  Summed on the GPU, whatever the grouping; beside -o\n"
     "                                        and/or --merged                                                                 [this build]\n"
+    "          --cohort-priors               --cohort: the allele priors of every record are re-estimated from ALL samples of the cohort\n"
+    "                                        before the genotypes are made -- a few EM steps from the panel's AF (or -u's uniform\n"
+    "                                        prior), anchored to it -- and every sample is genotyped under the cohort's frequencies.\n"
+    "                                        Records of 2..8 alleles; estimated on the GPU.  Every output (-o, --merged in text and\n"
+    "                                        BCF, --gp, -v, --min-gq, --site-tags, --pairs, --sample-stats) is made from the new\n"
+    "                                        calls.  The cohort must run as ONE group: more than 64 samples, a --cohort-group below\n"
+    "                                        the cohort, or a cohort that does not fit beside the index is an error     [this build]\n"
+    "          --prior-iters                 --cohort-priors: EM iterations, 0..64 (default:5; 0: the panel's priors, every output as\n"
+    "                                        without --cohort-priors).  The default is a design choice, not a measurement [this build]\n"
+    "          --prior-weight                --cohort-priors: the panel's prior counts as this many allele copies beside the cohort's,\n"
+    "                                        a number >= 0 (default:1; 0: the cohort alone, a frequency may then reach 0 and stay).\n"
+    "                                        The default is a design choice, not a measurement                         [this build]\n"
+    "          --priors-out                  --cohort-priors: PATH receives a tab-separated table, one line per output record in output\n"
+    "                                        order: CHROM POS ID REF ALT PANEL_AF COHORT_AF N_INFORMATIVE -- the two AF columns are comma\n"
+    "                                        lists over the ALT alleles, N_INFORMATIVE the samples whose reads entered the estimate [this build]\n"
     "\n"
     "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
     "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
@@ -141,6 +157,7 @@ struct Options { // argument_parser.hpp:51-66
     bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
     std::string pairs;      // --pairs: the table of pairwise genotype sharing
     std::string sample_stats; // --sample-stats: the per-sample QC table
+    PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
 };
 
 bool parse_arguments(int argc, char **argv, Options &o)
@@ -161,6 +178,8 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
                                       {"merged-format", required_argument, nullptr, 1008}, {"gp", no_argument, nullptr, 1009},
                                       {"pairs", required_argument, nullptr, 1010},    {"sample-stats", required_argument, nullptr, 1011},
+                                      {"cohort-priors", no_argument, nullptr, 1012},  {"prior-iters", required_argument, nullptr, 1013},
+                                      {"prior-weight", required_argument, nullptr, 1014}, {"priors-out", required_argument, nullptr, 1015},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -240,6 +259,25 @@ bool parse_arguments(int argc, char **argv, Options &o)
                 die = true;
             }
             break;
+        case 1012: o.priors.on = true; break;
+        case 1013:
+            if (!parse_prior_iters(optarg, o.priors)) {
+                std::cerr << "malva : --prior-iters takes a whole number 0..64\n";
+                die = true;
+            }
+            break;
+        case 1014:
+            if (!parse_prior_weight(optarg, o.priors)) {
+                std::cerr << "malva : --prior-weight takes a finite number >= 0\n";
+                die = true;
+            }
+            break;
+        case 1015:
+            if (!parse_priors_out(optarg, o.priors)) {
+                std::cerr << "malva : --priors-out takes a path\n";
+                die = true;
+            }
+            break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -287,6 +325,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (!o.cohort && !o.sample_stats.empty()) {
         std::cerr << "malva : --sample-stats goes with --cohort\n";
+        die = true;
+    }
+    if (const std::string why = check_prior_options(o.priors, o.cohort); !why.empty()) {
+        std::cerr << "malva : " << why << "\n";
         die = true;
     }
     if (!o.cohort && (!o.out_dir.empty() || o.cohort_group)) {
@@ -1442,6 +1484,8 @@ struct Batch { // inputs of mg_call_isolated (isolated) or mg_lookup_cover + mg_
     std::vector<int32_t> g1, g2, gq;
     std::vector<uint8_t> status;
     std::vector<double> probs;
+    std::vector<float> freq_out;   // --cohort-priors: the re-estimated frequencies, as freq
+    std::vector<uint32_t> n_inf;   // --cohort-priors: per record, the planes that counted
     size_t n() const { return var_allele_off.size() - 1; }
 };
 
@@ -1502,6 +1546,10 @@ int call_main(const Options &o)
         else samples.push_back({std::string(), resolve_sample_input(o.kmc_path, o.ref_k, MG_MAX_PACKED_K)});
     } catch (const std::exception &e) {
         return fail_early(e.what());
+    }
+    if (o.priors.on) { // (the sizes already tell: before any device is created, before anything is written)
+        const std::string why = prior_group_error(samples.size(), o.cohort_group);
+        if (!why.empty()) return fail_early("ERROR: " + why);
     }
     // --gpus N: one context per device -d .. -d+N-1.  MALVA_GENO_SHARE_DEVICE=1 puts all N contexts on device -d: the
     // N-way layout (sharded scan, exchange, split genotyping) rehearsed on a one-GPU box, the exchange then being a
@@ -1573,6 +1621,9 @@ int call_main(const Options &o)
     const bool want_sample = !o.sample_stats.empty(); // --sample-stats: the batches carry their alleles' classes
     double sample_ms = 0;                     // device milliseconds of the mg_sample_counts
     size_t sample_calls = 0;
+    double prior_ms = 0;                      // --cohort-priors: device milliseconds of the mg_genotype_cohort
+    size_t prior_calls = 0;
+    PriorsFile priors_file;                   // --priors-out
     // --merged-format bcf | ubcf: the merged file as BCF2 (host/bcf_out.hpp), a record's per-sample block encoded by mg_encode_calls_bcf
     const bool bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", bcf_bgzf = o.merged_format == "bcf";
     BcfHeader bcf_hdr;
@@ -1625,6 +1676,8 @@ int call_main(const Options &o)
     // stream, n_records and the [planes][3][W] words.
     // sample_table (--sample-stats): the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand
     // (mg_sample_counts, accumulate).
+    // --cohort-priors: a batch's coverages are made as always; its frequencies are then re-estimated over all planes and every plane genotyped
+    // under them by ONE mg_genotype_cohort per batch kind, whose arrays everything below reads; priors_file, when open, gets a line per record.
     auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed, FILE *cnt_out,
                         PairsRun *pairs, uint64_t *sample_table) -> size_t {
     const size_t P = planes ? planes : 1;
@@ -1667,6 +1720,22 @@ int call_main(const Options &o)
                           "mg_call_isolated");
             }
         }
+        auto cohort_priors = [&](Batch &b) { // the batch's priors from all of its planes, and the planes' calls under them
+            Timed t_prior("worker: cohort priors (mg_genotype_cohort)");
+            const size_t n = b.n(), ng = want_probs ? b.var_gt_off.back() : 0;
+            b.freq_out.resize(b.freq.size());
+            b.n_inf.resize(n);
+            b.probs.resize(P * ng);
+            dev.check(mg_genotype_cohort(dev.ctx, n, (uint32_t)P, b.cov.data(), b.freq.data(), b.var_allele_off.data(), o.error_rate, (int)o.max_coverage, o.haploid,
+                                         o.priors.iters, o.priors.weight, b.freq_out.data(), b.n_inf.data(), b.g1.data(), b.g2.data(), b.gq.data(), b.status.data(),
+                                         want_probs ? b.probs.data() : nullptr, want_probs ? b.var_gt_off.data() : nullptr),
+                      "mg_genotype_cohort");
+            float ms = 0;
+            dev.check(mg_cohort_prior_stats(dev.ctx, &ms), "mg_cohort_prior_stats");
+            prior_ms += ms;
+            ++prior_calls;
+        };
+        if (iso.n() && o.priors.on) cohort_priors(iso); // (mg_call_isolated made the coverages; its calls are replaced)
         if (gen.n()) {
             const size_t n = gen.n(), na = gen.var_allele_off.back(), ng = want_probs ? gen.var_gt_off.back() : 0;
             gen.cov.resize(P * na); gen.g1.resize(P * n); gen.g2.resize(P * n); gen.gq.resize(P * n); gen.status.resize(P * n);
@@ -1743,6 +1812,8 @@ int call_main(const Options &o)
                 }
             }
             if (n_fallback) std::cerr << "[malva-geno] " << n_fallback << " block(s) enumerated on the host" << std::endl;
+            if (o.priors.on) cohort_priors(gen);
+            else
             for (size_t pl = 0; pl < P; ++pl)
                 dev.check(mg_genotype(dev.ctx, gen.cov.data() + pl * na, gen.freq.data(), gen.var_allele_off.data(), n, o.error_rate, (int)o.max_coverage, o.haploid,
                                       gen.g1.data() + pl * n, gen.g2.data() + pl * n, gen.gq.data() + pl * n, gen.status.data() + pl * n,
@@ -1844,8 +1915,13 @@ int call_main(const Options &o)
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
-        std::vector<std::string> outv(outs.size() + 3); // (the last three: the merged block, the records' counts for cnt_out, the packed words for pairs->pack_out)
+        std::vector<std::string> outv(outs.size() + 4); // (the last four: the merged block, the records' counts for cnt_out, the packed words for pairs->pack_out, the lines of --priors-out)
         outv[outs.size() + 2] = std::move(pack_bytes);
+        if (priors_file.f)
+            for (const Rec &r : recs) {
+                const Batch &b = r.isolated ? iso : gen;
+                priors_row(outv[outs.size() + 3], r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
+            }
         if (merged_out && bcf_out) {
             // BCF: one group -- whole records (l_shared, l_indiv, the shared block with INFO from the counts, the device's row), compressed
             // here when BGZF; several -- per record the first group's shared block without INFO and every group's row, each behind its
@@ -1960,6 +2036,7 @@ int call_main(const Options &o)
             const std::string &cnt = text[outs.size() + 1], &pack = text[outs.size() + 2];
             if (cnt_out && fwrite(cnt.data(), 1, cnt.size(), cnt_out) != cnt.size()) throw std::runtime_error("cannot write the merged output's counts");
             if (pairs && pairs->pack_out && fwrite(pack.data(), 1, pack.size(), pairs->pack_out) != pack.size()) throw std::runtime_error("cannot write the pair table's packed calls");
+            priors_file.write(text[outs.size() + 3].data(), text[outs.size() + 3].size());
         }
     };
     auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
@@ -2085,7 +2162,6 @@ int call_main(const Options &o)
     size_t n = 0;
     if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr, nullptr, nullptr);
     else {
-        if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
         Device &dev = devs[0];
         // --merged: a cohort that runs as ONE group writes its lines straight to the output (PATH.part, renamed at the end; stdout as it
         // is).  Otherwise every group writes its block to a temporary file -- the first the header and whole lines, the others their
@@ -2161,12 +2237,15 @@ int call_main(const Options &o)
             {
                 Timed t("cohort: planes");
                 int rc = mg_cohort_begin(dev.ctx, (uint32_t)g);
+                if (rc == MG_ERR_NOMEM && o.priors.on && g > 1) throw std::runtime_error(prior_memory_error(samples.size())); // (no smaller groups: nothing has been written)
                 while (rc == MG_ERR_NOMEM && !o.cohort_group && g > 1) { // (as many as fit beside the index)
                     G = g = (g + 1) / 2;
                     rc = mg_cohort_begin(dev.ctx, (uint32_t)g);
                 }
                 dev.check(rc, "mg_cohort_begin");
             }
+            if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
+            if (o.priors.on && !o.priors.out.empty()) priors_file.open(o.priors.out); // (one group: opened once)
             group_planes.push_back((uint32_t)g);
             group_first.push_back(s0);
             PairsRun pairs_run;
@@ -2568,6 +2647,11 @@ int call_main(const Options &o)
                 g_timers.add("sample table: count kernel (device)", sample_ms / 1000.0);
                 fprintf(stderr, "[malva-geno] sample-stats: %zu mg_sample_counts, device ms per call: count %.3f\n", sample_calls, sample_ms / sample_calls);
             }
+        }
+        priors_file.finish();
+        if (g_timers.on && prior_calls) {
+            g_timers.add("cohort priors: kernel (device)", prior_ms / 1000.0);
+            fprintf(stderr, "[malva-geno] cohort-priors: %zu mg_genotype_cohort, device ms per call: %.3f\n", prior_calls, prior_ms / prior_calls);
         }
         if (bcf_calls && g_timers.on) {
             g_timers.add("merged: encode kernels (device)", (bcf_ms[0] + bcf_ms[1] + bcf_ms[2]) / 1000.0);
