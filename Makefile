@@ -62,11 +62,15 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
 
 # the host side of --cohort-priors (option values, --priors-out) under AddressSanitizer and UBSan: a stand-alone program, run on the CPU
-sanitize-host: bin/cohort_priors_host_check
+sanitize-host: bin/cohort_priors_host_check bin/cohort_out_host_check
 	bin/cohort_priors_host_check bin
-bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp
+	bin/cohort_out_host_check bin
+bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
+bin/cohort_out_host_check: tools/cohort_out_host_check.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
 
 clean:
 	rm -rf malva_amd/lib bin oracle/libmalva_oracle.so oracle/_ref

@@ -1,0 +1,270 @@
+// cohort_out.hpp -- the host-only half of the outputs of `call --cohort`: the streams a group leaves for the passes behind the last group
+// (the records' site counts, the packed calls), the two paste passes over the groups' blocks of the merged output, and the text of the --pairs and
+// --sample-stats tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp drives this file alone).
+#pragma once
+#include <deque>
+
+#include "../../include/malva_hip.h" // (the MG_SS_* slots of the sample table; nothing here calls the library)
+#include "bcf_out.hpp"
+#include "part_file.hpp"
+
+namespace malva {
+
+// the groups' scratch files, open for reading as long as this object lives
+struct GroupFiles {
+    std::vector<FILE *> f;
+    GroupFiles() = default;
+    GroupFiles(const GroupFiles &) = delete;
+    ~GroupFiles() { for (FILE *in : f) fclose(in); }
+    void open(const std::string &path)
+    {
+        FILE *in = fopen(path.c_str(), "rb");
+        if (!in) throw std::runtime_error("cannot read " + path);
+        f.push_back(in);
+    }
+    void open(const std::deque<PartFile> &files) { for (const auto &p : files) open(p.path); }
+};
+
+// ---- the records' site counts (--site-tags in several groups) ---------------------------------------------------------------------
+// per record, in output order, the u32s n_alleles, ns, ac[n_alleles]
+inline void put_site_counts(std::string &out, uint32_t n_alleles, uint32_t ns, const uint32_t *ac)
+{
+    const uint32_t head[2] = {n_alleles, ns};
+    out.append((const char *)head, 8);
+    out.append((const char *)ac, 4 * (size_t)n_alleles);
+}
+// the groups' streams read in step and summed
+struct SiteCountsReader {
+    GroupFiles in;
+    std::vector<uint32_t> more;
+    const char *short_file = "internal: a group's counts for the merged output are short";
+    explicit SiteCountsReader(const std::deque<PartFile> &files) { in.open(files); }
+    // the next record: its alleles, the groups' ns summed, their ac summed and appended to `ac`; false where the first group's file ends
+    bool next(uint32_t &n_alleles, uint32_t &ns, std::vector<uint32_t> &ac)
+    {
+        uint32_t head[2], h[2];
+        if (fread(head, 4, 2, in.f[0]) != 2) return false;
+        const size_t A = head[0], at = ac.size();
+        ac.resize(at + A);
+        if (A && fread(&ac[at], 4, A, in.f[0]) != A) throw std::runtime_error(short_file);
+        more.resize(A);
+        for (size_t gi = 1; gi < in.f.size(); ++gi) {
+            if (fread(h, 4, 2, in.f[gi]) != 2 || h[0] != A || (A && fread(more.data(), 4, A, in.f[gi]) != A)) throw std::runtime_error(short_file);
+            head[1] += h[1];
+            for (size_t a = 0; a < A; ++a) ac[at + a] += more[a];
+        }
+        n_alleles = head[0];
+        ns = head[1];
+        return true;
+    }
+    // up to `most` records as mg_format_site_info takes them (var_allele_off starts at 0); at least one, or the streams are short
+    void next_batch(size_t most, std::vector<uint32_t> &ac, std::vector<uint32_t> &ns, std::vector<uint32_t> &var_allele_off)
+    {
+        ac.clear();
+        ns.clear();
+        var_allele_off.assign(1, 0u);
+        uint32_t A, n;
+        while (ns.size() < most && next(A, n, ac)) {
+            ns.push_back(n);
+            var_allele_off.push_back((uint32_t)ac.size());
+        }
+        if (ns.empty()) throw std::runtime_error(short_file);
+    }
+};
+
+// ---- the packed calls (--pairs in several groups) ---------------------------------------------------------------------------------
+// per batch and stream the u64s stream, n_records, then the [planes][3][W] words of mg_pack_dosage, W = ceil(n_records / 64)
+inline void put_pack_batch(std::string &out, uint64_t stream, uint64_t n_records, const std::vector<uint64_t> &words)
+{
+    const uint64_t head[2] = {stream, n_records};
+    out.append((const char *)head, 16);
+    out.append((const char *)words.data(), 8 * words.size());
+}
+// Two groups' files walked in step: every group saw the records in the same order and cut them into the same batches, so batch b of
+// the one and batch b of the other hold the same records.  count(W, words_a, words_b) gets each pair of batches.
+template <class Count> void walk_pack_pair(const std::string &path_a, size_t planes_a, const std::string &path_b, size_t planes_b, Count &&count)
+{
+    const char *short_file = "internal: a group's packed calls for the pair table are short";
+    GroupFiles in;
+    in.open(path_a);
+    in.open(path_b);
+    FILE *fa = in.f[0], *fb = in.f[1];
+    std::vector<uint64_t> words_a, words_b;
+    uint64_t head_a[2], head_b[2];
+    while (fread(head_a, 8, 2, fa) == 2) {
+        if (fread(head_b, 8, 2, fb) != 2 || head_b[0] != head_a[0] || head_b[1] != head_a[1]) throw std::runtime_error(short_file);
+        const size_t W = (size_t)((head_a[1] + 63) / 64);
+        words_a.resize(planes_a * 3 * W);
+        words_b.resize(planes_b * 3 * W);
+        if (fread(words_a.data(), 8, words_a.size(), fa) != words_a.size() || fread(words_b.data(), 8, words_b.size(), fb) != words_b.size())
+            throw std::runtime_error(short_file);
+        count(W, words_a.data(), words_b.data());
+    }
+    if (fread(head_b, 8, 2, fb) != 0) throw std::runtime_error(short_file);
+}
+
+// ---- the tables' text: the divisions and the formatting are all the host does ------------------------------------------------------
+// table: [samples][samples][9], of which the entries i < j are read
+inline std::string pair_table_text(const std::vector<std::string> &names, const uint64_t *table)
+{
+    std::string text = "#A\tB\tN\tN00\tN01\tN02\tN10\tN11\tN12\tN20\tN21\tN22\tIBS0\tIBS1\tIBS2\tKING\n";
+    char num[64];
+    const size_t S = names.size();
+    for (size_t i = 0; i < S; ++i)
+        for (size_t j = i + 1; j < S; ++j) {
+            const uint64_t *c = &table[(i * S + j) * 9];
+            uint64_t total = 0;
+            for (int k = 0; k < 9; ++k) total += c[k];
+            const uint64_t ibs2 = c[0] + c[4] + c[8], ibs0 = c[2] + c[6], het = (c[3] + c[4] + c[5]) + (c[1] + c[4] + c[7]);
+            text += names[i] + "\t" + names[j] + "\t" + std::to_string(total);
+            for (int k = 0; k < 9; ++k) text += "\t" + std::to_string(c[k]);
+            text += "\t" + std::to_string(ibs0) + "\t" + std::to_string(total - ibs0 - ibs2) + "\t" + std::to_string(ibs2) + "\t";
+            if (het) {
+                snprintf(num, sizeof num, "%.4f", (double)((int64_t)c[4] - 2 * (int64_t)ibs0) / (double)het);
+                text += num;
+            } else
+                text += ".";
+            text += "\n";
+        }
+    return text;
+}
+// table: [samples][MG_SAMPLE_SLOTS]
+inline std::string sample_table_text(const std::vector<std::string> &names, const uint64_t *table)
+{
+    std::string text = "#SAMPLE\tRECORDS\tCALLED\tMASKED\tBAD\tHOM_REF\tHET\tHOM_ALT\tHET_ALT\tTS\tTV\tINS\tDEL\tOTHER\tGQ_SUM\tCOV_SUM\tNORMAL\tOVERCOV\tSINGLE\tNOCOV";
+    for (int b = 0; b < 10; ++b) text += "\tGQ_" + std::to_string(10 * b);
+    text += "\tCALL_RATE\tHET_HOM\tTSTV\tMEAN_GQ\tMEAN_COV\n";
+    char num[64];
+    for (size_t i = 0; i < names.size(); ++i) {
+        const uint64_t *c = &table[i * MG_SAMPLE_SLOTS];
+        text += names[i];
+        for (int k : {MG_SS_RECORDS, MG_SS_CALLED, MG_SS_MASKED, MG_SS_BAD, MG_SS_HOM_REF, MG_SS_HET, MG_SS_HOM_ALT, MG_SS_HET_ALT, MG_SS_TS, MG_SS_TV, MG_SS_INS,
+                      MG_SS_DEL, MG_SS_OTHER})
+            text += "\t" + std::to_string(c[k]);
+        text += "\t" + std::to_string((int64_t)c[MG_SS_GQ_SUM]);
+        for (int k = MG_SS_COV_SUM; k < MG_SS_COUNTED; ++k) text += "\t" + std::to_string(c[k]);
+        const double ratio[5][2] = {{(double)c[MG_SS_CALLED], (double)c[MG_SS_RECORDS]},
+                                    {(double)c[MG_SS_HET], (double)c[MG_SS_HOM_ALT]},
+                                    {(double)c[MG_SS_TS], (double)c[MG_SS_TV]},
+                                    {(double)(int64_t)c[MG_SS_GQ_SUM], (double)c[MG_SS_CALLED]},
+                                    {(double)c[MG_SS_COV_SUM], (double)c[MG_SS_RECORDS]}};
+        for (const auto &r : ratio) {
+            if (r[1] != 0) {
+                snprintf(num, sizeof num, "\t%.4f", r[0] / r[1]);
+                text += num;
+            } else
+                text += "\t.";
+        }
+        text += "\n";
+    }
+    return text;
+}
+
+// ---- the paste passes over the groups' blocks of the merged output -----------------------------------------------------------------
+// Both read in[g], group g's block, and hand the output to sink(data, n) about a MiB at a time.
+//
+// Text: line i of the output = line i of every group's block, one behind the other (the header lines of the first block have no
+// counterpart in the others).  site_tags: INFO, the eighth column, is the first block's '.' and is replaced by the next string of
+// next_infos(text, off), which hands out the strings of as many records as it likes (off: their n + 1 offsets into text), n >= 1.
+template <class Infos, class Sink> void paste_text_groups(const std::vector<FILE *> &in, bool site_tags, Infos &&next_infos, Sink &&sink)
+{
+    std::vector<char> info_text;
+    std::vector<uint64_t> info_off(1, 0);
+    size_t info_at = 0;
+    char *line = nullptr;
+    size_t line_cap = 0;
+    struct FreeLine {
+        char *&p;
+        ~FreeLine() { free(p); }
+    } free_line{line};
+    std::string out;
+    for (;;) {
+        ssize_t len = getline(&line, &line_cap, in[0]);
+        if (len < 0) break;
+        const bool record = line[0] != '#';
+        if (record && len && line[len - 1] == '\n') --len;
+        if (record && site_tags) {
+            if (info_at + 1 == info_off.size()) {
+                next_infos(info_text, info_off);
+                info_at = 0;
+            }
+            const char *at = line;
+            for (int t = 0; t < 7 && at; ++t) {
+                at = (const char *)memchr(at, '\t', (size_t)(line + len - at));
+                if (at) ++at;
+            }
+            if (!at || line + len - at < 2 || at[0] != '.' || at[1] != '\t') throw std::runtime_error("internal: a line of the merged output's first block has no INFO column");
+            out.append(line, (size_t)(at - line));
+            out.append(info_text.data() + info_off[info_at], info_text.data() + info_off[info_at + 1]);
+            out.append(at + 1, (size_t)(line + len - at - 1));
+            ++info_at;
+        } else
+            out.append(line, (size_t)len);
+        for (size_t gi = 1; record && gi < in.size(); ++gi) {
+            ssize_t more = getline(&line, &line_cap, in[gi]);
+            if (more <= 0) throw std::runtime_error("internal: a group's block of the merged output is short");
+            if (gi + 1 < in.size() && line[more - 1] == '\n') --more;
+            out.append(line, (size_t)more);
+        }
+        if (out.size() >= (1u << 20)) {
+            sink(out.data(), out.size());
+            out.clear();
+        }
+    }
+    sink(out.data(), out.size());
+}
+
+// BCF: record i of the output = the first group's shared block -- n_fmt and the cohort's n_samples put right, INFO from the summed
+// counts when `counts` is given -- and the groups' per-sample blocks joined field by field (bcf_paste_rows: planes[g] samples in
+// group g), framed by l_shared and l_indiv.  bgzf: every piece leaves as whole BGZF members, and the empty member ends the stream.
+template <class Sink>
+void paste_bcf_groups(const std::vector<FILE *> &in, const std::vector<uint32_t> &planes, uint32_t n_fmt, uint32_t n_samples, const BcfHeader &hdr, SiteCountsReader *counts,
+                      bool bgzf, Sink &&sink)
+{
+    if (planes.size() != in.size()) throw std::runtime_error("internal: the groups of the merged output and their files disagree");
+    const char *short_file = "internal: a group's block of the merged output is short";
+    std::vector<std::vector<unsigned char>> rows(in.size());
+    std::vector<std::pair<const unsigned char *, size_t>> row_of(in.size());
+    std::vector<uint32_t> ac;
+    std::string out, shared, indiv;
+    auto flush = [&]() {
+        std::string packed;
+        if (bgzf) bgzf_append(out.data(), out.size(), packed);
+        const std::string &bytes = bgzf ? packed : out;
+        sink(bytes.data(), bytes.size());
+        out.clear();
+    };
+    for (;;) {
+        uint32_t l_shared;
+        if (fread(&l_shared, 4, 1, in[0]) != 1) break;
+        if (l_shared < 24) throw std::runtime_error(short_file);
+        shared.resize(l_shared);
+        if (fread(&shared[0], 1, l_shared, in[0]) != l_shared) throw std::runtime_error(short_file);
+        for (size_t gi = 0; gi < in.size(); ++gi) {
+            uint32_t l_row;
+            if (fread(&l_row, 4, 1, in[gi]) != 1) throw std::runtime_error(short_file);
+            rows[gi].resize(l_row);
+            if (l_row && fread(rows[gi].data(), 1, l_row, in[gi]) != l_row) throw std::runtime_error(short_file);
+            row_of[gi] = {rows[gi].data(), l_row};
+        }
+        const uint32_t nfs = n_fmt << 24 | n_samples;
+        memcpy(&shared[20], &nfs, 4);
+        if (counts) {
+            uint32_t A, ns;
+            ac.clear();
+            if (!counts->next(A, ns, ac)) throw std::runtime_error(counts->short_file);
+            bcf_put_info(shared, 0, hdr, ac.data(), A, ns);
+        }
+        indiv.clear();
+        bcf_paste_rows(row_of, planes, n_fmt, indiv);
+        bcf_put_u32(out, (uint32_t)shared.size());
+        bcf_put_u32(out, (uint32_t)indiv.size());
+        out += shared;
+        out += indiv;
+        if (out.size() >= (1u << 20)) flush();
+    }
+    flush();
+    if (bgzf) sink(bgzf_eof().data(), bgzf_eof().size());
+}
+
+} // namespace malva

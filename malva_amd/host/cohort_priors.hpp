@@ -9,7 +9,8 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
-#include <unistd.h>
+
+#include "part_file.hpp"
 
 struct PriorOptions {
     bool on = false;      // --cohort-priors
@@ -95,36 +96,11 @@ inline void priors_row(std::string &out, const std::string &prefix, uint32_t n_a
 }
 inline const char *priors_header() { return "#CHROM\tPOS\tID\tREF\tALT\tPANEL_AF\tCOHORT_AF\tN_INFORMATIVE\n"; }
 
-// PATH is written as PATH.part and takes its name when the run is complete; whatever is left of PATH.part goes with this object
-struct PriorsFile {
-    std::string path, part;
-    FILE *f = nullptr;
+// the table's file: a PartFile (PATH.part, renamed when the run is complete) that starts with the header line
+struct PriorsFile : PartFile {
     void open(const std::string &p)
     {
-        path = p;
-        part = p + ".part";
-        f = fopen(part.c_str(), "wb");
-        if (!f) {
-            part.clear();
-            throw std::runtime_error("cannot write " + path);
-        }
+        PartFile::open(p);
         write(priors_header(), strlen(priors_header()));
-    }
-    void write(const char *data, size_t n)
-    {
-        if (f && fwrite(data, 1, n, f) != n) throw std::runtime_error("cannot write " + path);
-    }
-    void finish()
-    {
-        if (!f) return;
-        FILE *closing = f;
-        f = nullptr;
-        if (fclose(closing) != 0 || rename(part.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot write " + path);
-        part.clear();
-    }
-    ~PriorsFile()
-    {
-        if (f) fclose(f);
-        if (!part.empty()) unlink(part.c_str());
     }
 };

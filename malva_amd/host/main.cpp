@@ -30,6 +30,7 @@
 #include "cohort.hpp"
 #include "bcf_out.hpp"
 #include "cohort_priors.hpp"
+#include "cohort_out.hpp"
 extern "C" {
 #include "malva_hip.h"
 }
@@ -1614,7 +1615,7 @@ int call_main(const Options &o)
     // as several groups, the file that receives the packed words of the group's batches for the pass over pairs of groups
     struct PairsRun {
         std::vector<uint64_t> counts;
-        FILE *pack_out = nullptr;
+        PartFile *pack_out = nullptr;
     };
     double pairs_ms[2] = {0, 0};              // device milliseconds of the mg_pack_dosage and of the mg_pair_counts
     size_t pairs_calls[2] = {0, 0};
@@ -1663,23 +1664,37 @@ int call_main(const Options &o)
         ++site_calls[1];
     };
 
-    // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to outs[0] (stdout).  planes > 0: the
-    // context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
-    // only the INFO and GT:GQ fields per sample; sample p's text goes to outs[p] (outs empty: no per-sample text).  merged_out (--merged):
-    // the group's block of the multi-sample VCF -- a record's sample columns come as text from the device (mg_format_calls), behind the
-    // record's fixed columns when merged_fixed, else on their own (a later group's columns, pasted behind the first group's lines at the end).
-    // --site-tags: the records' allele counts over the group's planes are made beside the columns (mg_site_counts); cnt_out == nullptr: the
-    // group is the cohort and INFO is made from them at once (mg_format_site_info), else they go to cnt_out, per record in output order the
-    // u32s n_alleles, ns, ac[n_alleles], for the paste pass to sum over the groups.
-    // pairs (--pairs): every batch's cells are packed into dosage bit planes (mg_pack_dosage) while the batch is in hand and counted against
-    // themselves into pairs->counts; pairs->pack_out, when set, receives per batch and stream -- the lone records', then the others' -- the u64s
-    // stream, n_records and the [planes][3][W] words.
-    // sample_table (--sample-stats): the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand
-    // (mg_sample_counts, accumulate).
+    // Where one pass over the panel leaves what it makes; a member that is not set: the pass does not make it.
+    struct PassOut {
+        std::deque<PartFile> per_sample; // sample p's text goes to per_sample[p] (empty: no per-sample text); they go with this object
+        // --merged: the group's block of the multi-sample VCF -- a record's sample columns come as text from the device (mg_format_calls), behind
+        // the record's fixed columns when merged_fixed, else on their own (a later group's columns, pasted behind the first group's lines at the end)
+        PartFile *merged = nullptr;
+        bool merged_fixed = false;
+        // --site-tags: the records' allele counts over the group's planes are made beside the columns (mg_site_counts); not set: the group is the
+        // cohort and INFO is made from them at once (mg_format_site_info), else they go here (put_site_counts) for the paste pass to sum over the groups
+        PartFile *site_counts = nullptr;
+        // --pairs: every batch's cells are packed into dosage bit planes (mg_pack_dosage) while the batch is in hand and counted against themselves
+        // into pairs->counts; pairs->pack_out, when set, receives per batch and stream -- the lone records', then the others' -- the words (put_pack_batch)
+        PairsRun *pairs = nullptr;
+        // --sample-stats: the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand (mg_sample_counts, accumulate)
+        uint64_t *sample_table = nullptr;
+    };
+    struct BatchText { // the text of one batch, as its worker hands it over
+        std::vector<std::string> per_sample;
+        std::string merged, site_counts, pack, priors; // priors: the lines of --priors-out
+    };
+    // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to to.per_sample[0] (stdout).  planes > 0:
+    // the context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
+    // only the INFO and GT:GQ fields per sample.
     // --cohort-priors: a batch's coverages are made as always; its frequencies are then re-estimated over all planes and every plane genotyped
     // under them by ONE mg_genotype_cohort per batch kind, whose arrays everything below reads; priors_file, when open, gets a line per record.
-    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, const std::vector<FILE *> &outs, FILE *merged_out, const bool merged_fixed, FILE *cnt_out,
-                        PairsRun *pairs, uint64_t *sample_table) -> size_t {
+    auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, PassOut &to) -> size_t {
+    std::deque<PartFile> &outs = to.per_sample;
+    PartFile *const merged_out = to.merged, *const cnt_out = to.site_counts;
+    const bool merged_fixed = to.merged_fixed;
+    PairsRun *const pairs = to.pairs;
+    uint64_t *const sample_table = to.sample_table;
     const size_t P = planes ? planes : 1;
 
     // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
@@ -1701,7 +1716,7 @@ int call_main(const Options &o)
         Batch iso, gen;
         size_t device = 0; // batches go round the devices: after the exchange every one of them holds the whole table's counters
     };
-    auto process = [&](Job &job) -> std::vector<std::string> {
+    auto process = [&](Job &job) -> BatchText {
         std::vector<Rec> &recs = job.recs;
         Batch &iso = job.iso, &gen = job.gen;
         Device &dev = devs[job.device];
@@ -1890,11 +1905,7 @@ int call_main(const Options &o)
                 float ms[2] = {0, 0};
                 dev.check(mg_pairs_stats(dev.ctx, ms), "mg_pairs_stats");
                 for (int i = 0; i < 2; ++i) pairs_ms[i] += ms[i], ++pairs_calls[i];
-                if (pairs->pack_out) {
-                    const uint64_t head[2] = {(uint64_t)w, (uint64_t)bn};
-                    pack_bytes.append((const char *)head, 16);
-                    pack_bytes.append((const char *)words.data(), 8 * words.size());
-                }
+                if (pairs->pack_out) put_pack_batch(pack_bytes, (uint64_t)w, bn, words);
             }
         }
         if (sample_table) {
@@ -1915,18 +1926,20 @@ int call_main(const Options &o)
         device_lock.unlock(); // the records' text needs no device
         delete t_dev;
         Timed t_text("worker: records' text");
-        std::vector<std::string> outv(outs.size() + 4); // (the last four: the merged block, the records' counts for cnt_out, the packed words for pairs->pack_out, the lines of --priors-out)
-        outv[outs.size() + 2] = std::move(pack_bytes);
-        if (priors_file.f)
-            for (const Rec &r : recs) {
-                const Batch &b = r.isolated ? iso : gen;
-                priors_row(outv[outs.size() + 3], r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
-            }
+        BatchText text;
+        text.per_sample.resize(outs.size());
+        text.pack = std::move(pack_bytes);
+        for (const Rec &r : recs) {
+            const Batch &b = r.isolated ? iso : gen;
+            const int w = r.isolated ? 0 : 1;
+            if (priors_file.f) priors_row(text.priors, r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
+            if (tags && cnt_out) put_site_counts(text.site_counts, r.n_alleles, site_ns[w][r.slot], site_ac[w].data() + r.allele0);
+        }
         if (merged_out && bcf_out) {
             // BCF: one group -- whole records (l_shared, l_indiv, the shared block with INFO from the counts, the device's row), compressed
             // here when BGZF; several -- per record the first group's shared block without INFO and every group's row, each behind its
             // u32 length, for the paste pass to widen and join (the counts go to cnt_out as for text)
-            std::string &out = outv[outs.size()], &cnt = outv[outs.size() + 1];
+            std::string &out = text.merged;
             std::string plain;
             std::string &rec_out = bcf_direct && bcf_bgzf ? plain : out;
             const uint32_t n_fmt = (o.verbose ? 3 : 2) + (o.gp ? 1 : 0);
@@ -1945,15 +1958,10 @@ int call_main(const Options &o)
                 }
                 if (!bcf_direct) bcf_put_u32(rec_out, l_indiv);
                 rec_out.append(row, l_indiv);
-                if (tags && cnt_out) {
-                    const uint32_t head[2] = {r.n_alleles, site_ns[w][r.slot]};
-                    cnt.append((const char *)head, 8);
-                    cnt.append((const char *)(site_ac[w].data() + r.allele0), 4 * (size_t)r.n_alleles);
-                }
             }
             if (bcf_direct && bcf_bgzf) bgzf_append(plain.data(), plain.size(), out);
         } else if (merged_out) {
-            std::string &out = outv[outs.size()], &cnt = outv[outs.size() + 1];
+            std::string &out = text.merged;
             const char *fixed = o.verbose ? (o.gp ? "\tPASS\t.\tGT:GQ:COVS:GP" : "\tPASS\t.\tGT:GQ:COVS") : o.gp ? "\tPASS\t.\tGT:GQ:GP" : "\tPASS\t.\tGT:GQ";
             const bool info_here = tags && !cnt_out; // (else INFO stays '.' in the block: the paste pass puts it in)
             for (const Rec &r : recs) {
@@ -1968,11 +1976,6 @@ int call_main(const Options &o)
                     out += fixed;
                 }
                 out.append(row_text[w].data() + row_off[w][r.slot], row_text[w].data() + row_off[w][r.slot + 1]);
-                if (tags && cnt_out) {
-                    const uint32_t head[2] = {r.n_alleles, site_ns[w][r.slot]};
-                    cnt.append((const char *)head, 8);
-                    cnt.append((const char *)(site_ac[w].data() + r.allele0), 4 * (size_t)r.n_alleles);
-                }
             }
         }
         char num[64];
@@ -1980,7 +1983,7 @@ int call_main(const Options &o)
         for (const Rec &r : recs) // output_variants, var_block.hpp:337-396
           for (size_t pl = 0; pl < P; ++pl) {
             const Batch &b = r.isolated ? iso : gen;
-            std::string &out = outv[pl];
+            std::string &out = text.per_sample[pl];
             const size_t bn = b.n(), bna = b.var_allele_off.back(), bng = b.probs.size() / P;
             out += r.prefix;
             out += "\tPASS\t";
@@ -2019,24 +2022,21 @@ int call_main(const Options &o)
             out += gname(b.g1[pl * bn + r.slot], b.g2[pl * bn + r.slot]); // early-outs and "nothing beats 0.0" come back as 0 / 0/0
             out += ":" + std::to_string(b.gq[pl * bn + r.slot]) + "\n";
           }
-        return outv;
+        return text;
     };
     // as many batches in flight as there are devices; their text leaves in submission order
-    std::deque<std::future<std::vector<std::string>>> in_flight;
+    std::deque<std::future<BatchText>> in_flight;
     size_t jobs_started = 0;
     auto drain = [&](size_t keep) {
         Timed t_drain("main: wait for worker + write");
         while (in_flight.size() > keep) {
-            const std::vector<std::string> text = in_flight.front().get(); // (or the batch's exception comes back here)
+            const BatchText text = in_flight.front().get(); // (or the batch's exception comes back here)
             in_flight.pop_front();
-            for (size_t pl = 0; pl < outs.size(); ++pl)
-                if (fwrite(text[pl].data(), 1, text[pl].size(), outs[pl]) != text[pl].size()) throw std::runtime_error("cannot write the output");
-            const std::string &block = text[outs.size()];
-            if (merged_out && fwrite(block.data(), 1, block.size(), merged_out) != block.size()) throw std::runtime_error("cannot write the merged output");
-            const std::string &cnt = text[outs.size() + 1], &pack = text[outs.size() + 2];
-            if (cnt_out && fwrite(cnt.data(), 1, cnt.size(), cnt_out) != cnt.size()) throw std::runtime_error("cannot write the merged output's counts");
-            if (pairs && pairs->pack_out && fwrite(pack.data(), 1, pack.size(), pairs->pack_out) != pack.size()) throw std::runtime_error("cannot write the pair table's packed calls");
-            priors_file.write(text[outs.size() + 3].data(), text[outs.size() + 3].size());
+            for (size_t pl = 0; pl < outs.size(); ++pl) outs[pl].write(text.per_sample[pl], "cannot write the output");
+            if (merged_out) merged_out->write(text.merged, "cannot write the merged output");
+            if (cnt_out) cnt_out->write(text.site_counts, "cannot write the merged output's counts");
+            if (pairs && pairs->pack_out) pairs->pack_out->write(text.pack, "cannot write the pair table's packed calls");
+            priors_file.write(text.priors);
         }
     };
     auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
@@ -2153,70 +2153,56 @@ int call_main(const Options &o)
     }, &devs[0]);
     run_and_print();
     drain(0);
-    for (FILE *f : outs) fflush(f);
-    if (merged_out) fflush(merged_out);
-    if (cnt_out) fflush(cnt_out);
+    for (PartFile &f : outs) fflush(f.f);
+    if (merged_out) fflush(merged_out->f);
+    if (cnt_out) fflush(cnt_out->f);
     return n;
     }; // vcf_pass
 
     size_t n = 0;
-    if (!o.cohort) n = vcf_pass(*vcf_first, 0, std::vector<FILE *>{stdout}, nullptr, false, nullptr, nullptr, nullptr);
-    else {
+    if (!o.cohort) {
+        PassOut to;
+        to.per_sample.emplace_back();
+        to.per_sample[0].open("-", PartFile::STDOUT);
+        n = vcf_pass(*vcf_first, 0, to);
+    } else {
         Device &dev = devs[0];
-        // --merged: a cohort that runs as ONE group writes its lines straight to the output (PATH.part, renamed at the end; stdout as it
-        // is).  Otherwise every group writes its block to a temporary file -- the first the header and whole lines, the others their
-        // sample columns alone -- beside the output, or under $TMPDIR when that is stdout, and a last pass pastes them line by line.
-        // Whatever is left of them is removed when this frame is left, on success and on error.
-        struct MergedFiles {
-            std::vector<std::string> paths; // temporary files, the first group's first
-            std::vector<std::string> cnt_paths; // --site-tags: the groups' counts (PATH.gN.cnt.part)
-            std::string part;               // PATH.part
-            FILE *open = nullptr, *cnt_open = nullptr;
-            ~MergedFiles()
-            {
-                if (open && open != stdout) fclose(open);
-                if (cnt_open) fclose(cnt_open);
-                for (const auto &p : paths) unlink(p.c_str());
-                for (const auto &p : cnt_paths) unlink(p.c_str());
-                if (!part.empty()) unlink(part.c_str());
-            }
-        } merged;
-        // --pairs: the table of the whole cohort, [samples][samples][9], of which the entries i < j are filled: a group's own pairs when its
-        // panel pass ends, the pairs across two groups by the pass behind the last group, from the groups' packed words (PATH.gN.pack.part:
-        // 3 bits per cell).  The table is written as PATH.part and renamed; whatever is left of these files goes when this frame is left.
-        struct PairFiles {
-            std::vector<std::string> pack_paths;
-            std::string part;
-            FILE *open = nullptr;
-            ~PairFiles()
-            {
-                if (open) fclose(open);
-                for (const auto &p : pack_paths) unlink(p.c_str());
-                if (!part.empty()) unlink(part.c_str());
-            }
-        } pair_files;
+        // --merged: a cohort that runs as ONE group writes its lines straight to the output (PATH.part, renamed at the end; stdout as it is).
+        // Otherwise every group writes its block to a scratch file -- the first the header and whole lines, the others their sample columns
+        // alone -- beside the output, or under $TMPDIR when that is stdout, and with --site-tags its records' counts to another (PATH.gN.cnt.part);
+        // a last pass pastes them (host/cohort_out.hpp).  Whatever is left of these files goes when this frame is left, on success and on error.
+        std::deque<PartFile> merged_blocks, merged_counts; // the first group's first
+        PartFile merged_file;
+        // --pairs: the table of the whole cohort, [samples][samples][9], of which the entries i < j are filled: a group's own pairs when its panel
+        // pass ends, the pairs across two groups by the pass behind the last group, from the groups' packed words (PATH.gN.pack.part: 3 bits per cell)
+        std::deque<PartFile> pack_files;
         const bool want_pairs = !o.pairs.empty();
         const size_t S = samples.size();
         std::vector<uint64_t> pair_table(want_pairs ? S * S * 9 : 0, 0);
         std::vector<size_t> group_first; // the first sample of every group
-        // --sample-stats: [samples][MG_SAMPLE_SLOTS]; a sample belongs to one group, whose panel pass sums its row, so the table needs no pass
-        // of its own.  It is written as PATH.part and renamed; what is left of that goes when this frame is left.
-        struct SampleFile {
-            std::string part;
-            ~SampleFile()
-            {
-                if (!part.empty()) unlink(part.c_str());
-            }
-        } sample_file;
+        // --sample-stats: [samples][MG_SAMPLE_SLOTS]; a sample belongs to one group, whose panel pass sums its row, so the table needs no pass of its own
         std::vector<uint64_t> sample_table(want_sample ? S * MG_SAMPLE_SLOTS : 0, 0);
+        std::vector<std::string> names;
+        for (const auto &sm : samples) names.push_back(sm.name);
         const bool merged_stdout = o.merged == "-";
         const std::string merged_tmp_base = !merged_stdout ? o.merged : std::string(getenv("TMPDIR") && *getenv("TMPDIR") ? getenv("TMPDIR") : "/tmp") + "/malva-geno." + std::to_string((long)getpid()) + ".merged";
+        auto open_merged = [&]() -> PartFile & { // (a failure names the file that could not be made)
+            try {
+                merged_file.open(o.merged, merged_stdout ? PartFile::STDOUT : PartFile::RENAMED);
+            } catch (const std::runtime_error &) {
+                throw std::runtime_error("cannot write " + o.merged + ".part");
+            }
+            return merged_file;
+        };
+        auto open_scratch = [](std::deque<PartFile> &files, const std::string &base, const char *ext) -> PartFile & { // the next group's BASE.gN<ext>
+            files.emplace_back();
+            files.back().open(base + ".g" + std::to_string(files.size() - 1) + ext, PartFile::SCRATCH);
+            return files.back();
+        };
         std::string merged_head;
         if (!o.merged.empty()) {
             VcfReader hdr(o.vcf_path, "-");
             if (!hdr.ok()) throw std::runtime_error(hdr.error);
-            std::vector<std::string> names;
-            for (const auto &sm : samples) names.push_back(sm.name);
             if (bcf_out) { // the text header with a ##contig line per reference sequence where the panel's header has none
                 const bool declared = bcf_has_contig_lines(hdr.header_lines);
                 bcf_hdr = bcf_parse_header(merged_header(hdr.header_lines, o.verbose, names, o.site_tags,
@@ -2251,12 +2237,7 @@ int call_main(const Options &o)
             PairsRun pairs_run;
             if (want_pairs) {
                 pairs_run.counts.assign(g * g * 9, 0);
-                if (g != S) { // (several groups: their pairs across need every group's calls again)
-                    const std::string path = o.pairs + ".g" + std::to_string(pair_files.pack_paths.size()) + ".pack.part";
-                    pair_files.pack_paths.push_back(path);
-                    pairs_run.pack_out = pair_files.open = fopen(path.c_str(), "wb");
-                    if (!pair_files.open) throw std::runtime_error("cannot write " + path);
-                }
+                if (g != S) pairs_run.pack_out = &open_scratch(pack_files, o.pairs, ".pack.part"); // (several groups: their pairs across need every group's calls again)
             }
             {
                 Timed t("cohort: table scans");
@@ -2265,48 +2246,21 @@ int call_main(const Options &o)
                     scan_sample(samples[s0 + i].input);
                 }
             }
-            // a group's files are written as NAME.vcf.part and take their names when the group is complete: a failure on the way
-            // leaves no truncated NAME.vcf behind
-            struct Parts {
-                std::vector<std::string> paths;
-                std::vector<FILE *> files;
-                bool done = false;
-                ~Parts()
-                {
-                    if (done) return;
-                    for (FILE *f : files)
-                        if (f) fclose(f);
-                    for (const auto &p : paths) unlink((p + ".part").c_str());
-                }
-            } parts;
-            std::vector<FILE *> &outs = parts.files;
+            PassOut to; // (a group's files are written as NAME.vcf.part: a failure on the way leaves no truncated NAME.vcf behind)
+            to.merged_fixed = s0 == 0;
+            to.pairs = want_pairs ? &pairs_run : nullptr;
+            to.sample_table = want_sample ? &sample_table[s0 * MG_SAMPLE_SLOTS] : nullptr;
             for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
-                const std::string path = o.out_dir + "/" + samples[s0 + i].name + ".vcf";
-                FILE *f = fopen((path + ".part").c_str(), "wb");
-                if (!f) throw std::runtime_error("cannot write " + path);
-                parts.paths.push_back(path);
-                outs.push_back(f);
-                if (fwrite(header_text.data(), 1, header_text.size(), f) != header_text.size()) throw std::runtime_error("cannot write " + path);
+                to.per_sample.emplace_back();
+                to.per_sample.back().open(o.out_dir + "/" + samples[s0 + i].name + ".vcf");
+                to.per_sample.back().write(header_text);
             }
             if (!o.merged.empty()) {
                 if (s0 == 0) bcf_direct = merged_direct = g == samples.size();
-                if (merged_direct && merged_stdout) merged.open = stdout;
-                else {
-                    const std::string path = merged_direct ? o.merged + ".part" : merged_tmp_base + ".g" + std::to_string(merged.paths.size()) + (bcf_out ? ".bcf.part" : ".part");
-                    if (merged_direct) merged.part = path;
-                    else merged.paths.push_back(path);
-                    merged.open = fopen(path.c_str(), "wb");
-                    if (!merged.open) throw std::runtime_error("cannot write " + path);
-                }
-                if (o.site_tags && !merged_direct) {
-                    const std::string path = merged_tmp_base + ".g" + std::to_string(merged.cnt_paths.size()) + ".cnt.part";
-                    merged.cnt_paths.push_back(path);
-                    merged.cnt_open = fopen(path.c_str(), "wb");
-                    if (!merged.cnt_open) throw std::runtime_error("cannot write " + path);
-                }
+                to.merged = merged_direct ? &open_merged() : &open_scratch(merged_blocks, merged_tmp_base, bcf_out ? ".bcf.part" : ".part");
+                if (o.site_tags && !merged_direct) to.site_counts = &open_scratch(merged_counts, merged_tmp_base, ".cnt.part");
                 // (BCF in several groups: the header goes in front of the pasted records, the groups' files hold records alone)
-                if (s0 == 0 && (!bcf_out || merged_direct) && fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size())
-                    throw std::runtime_error("cannot write the merged output");
+                if (s0 == 0 && (!bcf_out || merged_direct)) to.merged->write(merged_head, "cannot write the merged output");
             }
             {
                 Timed t("cohort: panel pass");
@@ -2316,293 +2270,62 @@ int call_main(const Options &o)
                     start_vcf(*again);
                     if (!again->ok()) throw std::runtime_error(again->error);
                 }
-                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, outs, merged.open, s0 == 0, merged.cnt_open, want_pairs ? &pairs_run : nullptr,
-                             want_sample ? &sample_table[s0 * MG_SAMPLE_SLOTS] : nullptr);
+                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, to);
             }
-            if (pair_files.open) {
-                FILE *closing = pair_files.open;
-                pair_files.open = nullptr;
-                if (fclose(closing) != 0) throw std::runtime_error("cannot write the pair table's packed calls");
-            }
+            if (pairs_run.pack_out) pairs_run.pack_out->close("cannot write the pair table's packed calls");
             for (size_t i = 0; want_pairs && i < g; ++i)
                 for (size_t j = i + 1; j < g; ++j) std::copy_n(&pairs_run.counts[(i * g + j) * 9], 9, &pair_table[((s0 + i) * S + s0 + j) * 9]);
-            if (merged.cnt_open) {
-                FILE *closing = merged.cnt_open;
-                merged.cnt_open = nullptr;
-                if (fclose(closing) != 0) throw std::runtime_error("cannot write the merged output's counts");
+            if (to.site_counts) to.site_counts->close("cannot write the merged output's counts");
+            if (to.merged) {
+                if (bcf_out && bcf_bgzf && merged_direct) to.merged->write(bgzf_eof(), "cannot write the merged output");
+                to.merged->close("cannot write the merged output");
             }
-            if (merged.open) {
-                const std::string tail = bcf_out && bcf_bgzf && merged_direct ? bgzf_eof() : std::string();
-                const bool short_write = fwrite(tail.data(), 1, tail.size(), merged.open) != tail.size();
-                FILE *closing = merged.open;
-                merged.open = nullptr;
-                if (((closing == stdout ? fflush(closing) : fclose(closing)) != 0) || short_write) throw std::runtime_error("cannot write the merged output");
-            }
-            for (FILE *&f : outs) {
-                FILE *closing = f;
-                f = nullptr;
-                if (fclose(closing) != 0) throw std::runtime_error("cannot write the output");
-            }
-            for (const auto &p : parts.paths)
-                if (rename((p + ".part").c_str(), p.c_str()) != 0) throw std::runtime_error("cannot write " + p);
-            parts.done = true;
+            // the group's files take their names when the group is complete, and only after every one of them is closed
+            for (PartFile &f : to.per_sample) f.close("cannot write the output");
+            for (PartFile &f : to.per_sample) f.finish();
             dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
             s0 += g;
         }
-        if (!o.merged.empty() && !merged_direct && bcf_out) {
-            // record i of the output = the first group's shared block (n_sample put right, INFO from the summed counts) and the groups'
-            // per-sample blocks joined field by field at the widest type a group chose (bcf_paste_rows)
+        if (!o.merged.empty() && !merged_direct) { // the groups' blocks pasted record by record (host/cohort_out.hpp)
             Timed t("cohort: merged paste");
-            std::vector<FILE *> in, cnt_in;
-            struct CloseAll {
-                std::vector<FILE *> &v;
-                ~CloseAll()
-                {
-                    for (FILE *f : v) fclose(f);
-                }
-            } close_all{in}, close_cnt{cnt_in};
-            auto open_all = [](const std::vector<std::string> &paths, std::vector<FILE *> &files) {
-                for (const auto &p : paths) {
-                    FILE *f = fopen(p.c_str(), "rb");
-                    if (!f) throw std::runtime_error("cannot read " + p);
-                    files.push_back(f);
-                }
-            };
-            open_all(merged.cnt_paths, cnt_in);
-            open_all(merged.paths, in);
-            if (!merged_stdout) {
-                merged.part = o.merged + ".part";
-                merged.open = fopen(merged.part.c_str(), "wb");
-                if (!merged.open) throw std::runtime_error("cannot write " + merged.part);
-            } else
-                merged.open = stdout;
-            const std::vector<uint32_t> &planes = group_planes;
-            if (planes.size() != in.size()) throw std::runtime_error("internal: the groups of the merged output and their files disagree");
-            const char *short_file = "internal: a group's block of the merged output is short";
-            const uint32_t n_fmt = (o.verbose ? 3 : 2) + (o.gp ? 1 : 0);
-            std::vector<std::vector<unsigned char>> rows(in.size());
-            std::vector<std::pair<const unsigned char *, size_t>> row_of(in.size());
-            std::vector<uint32_t> ac, more;
-            std::string out, shared, indiv;
-            auto flush = [&]() {
-                std::string packed;
-                if (bcf_bgzf) bgzf_append(out.data(), out.size(), packed);
-                const std::string &bytes = bcf_bgzf ? packed : out;
-                if (fwrite(bytes.data(), 1, bytes.size(), merged.open) != bytes.size()) throw std::runtime_error("cannot write the merged output");
-                out.clear();
-            };
-            if (fwrite(merged_head.data(), 1, merged_head.size(), merged.open) != merged_head.size()) throw std::runtime_error("cannot write the merged output");
-            for (;;) {
-                uint32_t l_shared;
-                if (fread(&l_shared, 4, 1, in[0]) != 1) break;
-                if (l_shared < 24) throw std::runtime_error(short_file);
-                shared.resize(l_shared);
-                if (fread(&shared[0], 1, l_shared, in[0]) != l_shared) throw std::runtime_error(short_file);
-                for (size_t gi = 0; gi < in.size(); ++gi) {
-                    uint32_t l_row;
-                    if (fread(&l_row, 4, 1, in[gi]) != 1) throw std::runtime_error(short_file);
-                    rows[gi].resize(l_row);
-                    if (l_row && fread(rows[gi].data(), 1, l_row, in[gi]) != l_row) throw std::runtime_error(short_file);
-                    row_of[gi] = {rows[gi].data(), l_row};
-                }
-                const uint32_t nfs = n_fmt << 24 | (uint32_t)bcf_samples;
-                memcpy(&shared[20], &nfs, 4);
-                if (o.site_tags) {
-                    uint32_t head[2] = {0, 0}, next[2];
-                    for (size_t gi = 0; gi < cnt_in.size(); ++gi) {
-                        if (fread(next, 4, 2, cnt_in[gi]) != 2 || (gi && next[0] != head[0])) throw std::runtime_error("internal: a group's counts for the merged output are short");
-                        const size_t A = next[0];
-                        more.resize(A);
-                        if (A && fread(more.data(), 4, A, cnt_in[gi]) != A) throw std::runtime_error("internal: a group's counts for the merged output are short");
-                        if (!gi) ac.assign(A, 0u);
-                        for (size_t a = 0; a < A; ++a) ac[a] += more[a];
-                        head[0] = next[0];
-                        head[1] += next[1];
-                    }
-                    bcf_put_info(shared, 0, bcf_hdr, ac.data(), head[0], head[1]);
-                }
-                indiv.clear();
-                bcf_paste_rows(row_of, planes, n_fmt, indiv);
-                bcf_put_u32(out, (uint32_t)shared.size());
-                bcf_put_u32(out, (uint32_t)indiv.size());
-                out += shared;
-                out += indiv;
-                if (out.size() >= (1u << 20)) flush();
+            SiteCountsReader counts(merged_counts);
+            GroupFiles in;
+            in.open(merged_blocks);
+            open_merged();
+            auto sink = [&](const char *data, size_t n) { merged_file.write(data, n, "cannot write the merged output"); };
+            if (bcf_out) {
+                sink(merged_head.data(), merged_head.size());
+                paste_bcf_groups(in.f, group_planes, (o.verbose ? 3 : 2) + (o.gp ? 1 : 0), (uint32_t)bcf_samples, bcf_hdr, o.site_tags ? &counts : nullptr, bcf_bgzf, sink);
+            } else {
+                // --site-tags: the groups' counts summed, 65,536 records at a time (MALVA_GENO_BATCH, when set: tests), and their INFO strings made on the device
+                const size_t paste_batch = getenv("MALVA_GENO_BATCH") ? (size_t)std::max(1L, atol(getenv("MALVA_GENO_BATCH"))) : 65536;
+                std::vector<uint32_t> p_ac, p_ns, p_vao;
+                paste_text_groups(in.f, o.site_tags, [&](std::vector<char> &text, std::vector<uint64_t> &off) {
+                    counts.next_batch(paste_batch, p_ac, p_ns, p_vao);
+                    site_info(dev, p_ns.size(), p_ac.data(), p_ns.data(), p_vao.data(), text, off);
+                }, sink);
             }
-            flush();
-            const std::string tail = bcf_bgzf ? bgzf_eof() : std::string();
-            const bool short_write = fwrite(tail.data(), 1, tail.size(), merged.open) != tail.size();
-            FILE *closing = merged.open;
-            merged.open = nullptr;
-            if (((closing == stdout ? fflush(closing) : fclose(closing)) != 0) || short_write) throw std::runtime_error("cannot write the merged output");
-        } else if (!o.merged.empty() && !merged_direct) { // line i of the output = line i of every group's block, one behind the other
-            Timed t("cohort: merged paste");
-            std::vector<FILE *> in, cnt_in;
-            struct CloseAll {
-                std::vector<FILE *> &v;
-                ~CloseAll()
-                {
-                    for (FILE *f : v) fclose(f);
-                }
-            } close_all{in}, close_cnt{cnt_in};
-            for (const auto &p : merged.cnt_paths) {
-                cnt_in.push_back(fopen(p.c_str(), "rb"));
-                if (!cnt_in.back()) {
-                    cnt_in.pop_back();
-                    throw std::runtime_error("cannot read " + p);
-                }
-            }
-            // --site-tags: the groups' counts summed, 65,536 records at a time (MALVA_GENO_BATCH, when set: tests), and their INFO strings made on the device
-            const size_t paste_batch = getenv("MALVA_GENO_BATCH") ? (size_t)std::max(1L, atol(getenv("MALVA_GENO_BATCH"))) : 65536;
-            std::vector<uint32_t> p_ac, p_ns, p_vao, p_more;
-            std::vector<char> p_text;
-            std::vector<uint64_t> p_off;
-            size_t p_at = 0;
-            auto next_infos = [&]() {
-                const char *short_file = "internal: a group's counts for the merged output are short";
-                p_ac.clear();
-                p_ns.clear();
-                p_vao.assign(1, 0u);
-                uint32_t head[2], more[2];
-                while (p_ns.size() < paste_batch && fread(head, 4, 2, cnt_in[0]) == 2) {
-                    const size_t A = head[0], at = p_ac.size();
-                    p_ac.resize(at + A);
-                    if (A && fread(&p_ac[at], 4, A, cnt_in[0]) != A) throw std::runtime_error(short_file);
-                    p_more.resize(A);
-                    for (size_t gi = 1; gi < cnt_in.size(); ++gi) {
-                        if (fread(more, 4, 2, cnt_in[gi]) != 2 || more[0] != A || (A && fread(p_more.data(), 4, A, cnt_in[gi]) != A)) throw std::runtime_error(short_file);
-                        head[1] += more[1];
-                        for (size_t a = 0; a < A; ++a) p_ac[at + a] += p_more[a];
-                    }
-                    p_ns.push_back(head[1]);
-                    p_vao.push_back((uint32_t)p_ac.size());
-                }
-                if (p_ns.empty()) throw std::runtime_error(short_file);
-                site_info(dev, p_ns.size(), p_ac.data(), p_ns.data(), p_vao.data(), p_text, p_off);
-                p_at = 0;
-            };
-            for (const auto &p : merged.paths) {
-                in.push_back(fopen(p.c_str(), "rb"));
-                if (!in.back()) {
-                    in.pop_back();
-                    throw std::runtime_error("cannot read " + p);
-                }
-            }
-            if (!merged_stdout) {
-                merged.part = o.merged + ".part";
-                merged.open = fopen(merged.part.c_str(), "wb");
-                if (!merged.open) throw std::runtime_error("cannot write " + merged.part);
-            } else
-                merged.open = stdout;
-            char *line = nullptr;
-            size_t line_cap = 0;
-            struct FreeLine {
-                char *&p;
-                ~FreeLine() { free(p); }
-            } free_line{line};
-            std::string out;
-            for (;;) { // (the header lines of the first block have no counterpart in the others)
-                ssize_t len = getline(&line, &line_cap, in[0]);
-                if (len < 0) break;
-                const bool record = line[0] != '#';
-                if (record && len && line[len - 1] == '\n') --len;
-                if (record && o.site_tags) { // INFO, the eighth column, is the block's '.'
-                    if (p_at == p_ns.size()) next_infos();
-                    const char *at = line;
-                    for (int t = 0; t < 7 && at; ++t) {
-                        at = (const char *)memchr(at, '\t', (size_t)(line + len - at));
-                        if (at) ++at;
-                    }
-                    if (!at || line + len - at < 2 || at[0] != '.' || at[1] != '\t') throw std::runtime_error("internal: a line of the merged output's first block has no INFO column");
-                    out.append(line, (size_t)(at - line));
-                    out.append(p_text.data() + p_off[p_at], p_text.data() + p_off[p_at + 1]);
-                    out.append(at + 1, (size_t)(line + len - at - 1));
-                    ++p_at;
-                } else
-                    out.append(line, (size_t)len);
-                for (size_t gi = 1; record && gi < in.size(); ++gi) {
-                    ssize_t more = getline(&line, &line_cap, in[gi]);
-                    if (more <= 0) throw std::runtime_error("internal: a group's block of the merged output is short");
-                    if (gi + 1 < in.size() && line[more - 1] == '\n') --more;
-                    out.append(line, (size_t)more);
-                }
-                if (out.size() >= (1u << 20)) {
-                    if (fwrite(out.data(), 1, out.size(), merged.open) != out.size()) throw std::runtime_error("cannot write the merged output");
-                    out.clear();
-                }
-            }
-            if (fwrite(out.data(), 1, out.size(), merged.open) != out.size()) throw std::runtime_error("cannot write the merged output");
-            FILE *closing = merged.open;
-            merged.open = nullptr;
-            if ((closing == stdout ? fflush(closing) : fclose(closing)) != 0) throw std::runtime_error("cannot write the merged output");
+            merged_file.close("cannot write the merged output");
         }
-        if (!o.merged.empty() && !merged_stdout) {
-            if (rename(merged.part.c_str(), o.merged.c_str()) != 0) throw std::runtime_error("cannot write " + o.merged);
-            merged.part.clear();
-        }
+        if (!o.merged.empty()) merged_file.finish();
         if (want_pairs) {
             Timed t("cohort: pair pass");
-            // the pairs across groups: every group saw the records in the same order and cut them into the same batches -- the panel pass
-            // depends on the panel and on MALVA_GENO_BATCH alone -- so batch b of group gi and batch b of group gj hold the same records
-            const char *short_file = "internal: a group's packed calls for the pair table are short";
-            std::vector<uint64_t> words_a, words_b, cross;
-            for (size_t gi = 0; gi < pair_files.pack_paths.size(); ++gi)
-                for (size_t gj = gi + 1; gj < pair_files.pack_paths.size(); ++gj) {
+            std::vector<uint64_t> cross; // the pairs across two groups, from the groups' packed words
+            for (size_t gi = 0; gi < pack_files.size(); ++gi)
+                for (size_t gj = gi + 1; gj < pack_files.size(); ++gj) {
                     const size_t ga = group_planes[gi], gb = group_planes[gj];
-                    FILE *fa = fopen(pair_files.pack_paths[gi].c_str(), "rb"), *fb = fopen(pair_files.pack_paths[gj].c_str(), "rb");
-                    struct Close {
-                        FILE *a, *b;
-                        ~Close()
-                        {
-                            if (a) fclose(a);
-                            if (b) fclose(b);
-                        }
-                    } close_both{fa, fb};
-                    if (!fa || !fb) throw std::runtime_error("cannot read " + pair_files.pack_paths[fa ? gj : gi]);
                     cross.assign(ga * gb * 9, 0);
-                    uint64_t head_a[2], head_b[2];
-                    while (fread(head_a, 8, 2, fa) == 2) {
-                        if (fread(head_b, 8, 2, fb) != 2 || head_b[0] != head_a[0] || head_b[1] != head_a[1]) throw std::runtime_error(short_file);
-                        const size_t W = (size_t)((head_a[1] + 63) / 64);
-                        words_a.resize(ga * 3 * W);
-                        words_b.resize(gb * 3 * W);
-                        if (fread(words_a.data(), 8, words_a.size(), fa) != words_a.size() || fread(words_b.data(), 8, words_b.size(), fb) != words_b.size())
-                            throw std::runtime_error(short_file);
-                        dev.check(mg_pair_counts(dev.ctx, W, words_a.data(), (uint32_t)ga, words_b.data(), (uint32_t)gb, 1, cross.data()), "mg_pair_counts");
+                    walk_pack_pair(pack_files[gi].path, ga, pack_files[gj].path, gb, [&](size_t W, const uint64_t *words_a, const uint64_t *words_b) {
+                        dev.check(mg_pair_counts(dev.ctx, W, words_a, (uint32_t)ga, words_b, (uint32_t)gb, 1, cross.data()), "mg_pair_counts");
                         float ms[2] = {0, 0};
                         dev.check(mg_pairs_stats(dev.ctx, ms), "mg_pairs_stats");
                         pairs_ms[1] += ms[1];
                         ++pairs_calls[1];
-                    }
-                    if (fread(head_b, 8, 2, fb) != 0) throw std::runtime_error(short_file);
+                    });
                     for (size_t i = 0; i < ga; ++i)
                         std::copy_n(&cross[i * gb * 9], gb * 9, &pair_table[((group_first[gi] + i) * S + group_first[gj]) * 9]);
                 }
-            // the text: the division and the formatting are all the host does
-            std::string text = "#A\tB\tN\tN00\tN01\tN02\tN10\tN11\tN12\tN20\tN21\tN22\tIBS0\tIBS1\tIBS2\tKING\n";
-            char num[64];
-            for (size_t i = 0; i < S; ++i)
-                for (size_t j = i + 1; j < S; ++j) {
-                    const uint64_t *c = &pair_table[(i * S + j) * 9];
-                    uint64_t total = 0;
-                    for (int k = 0; k < 9; ++k) total += c[k];
-                    const uint64_t ibs2 = c[0] + c[4] + c[8], ibs0 = c[2] + c[6], het = (c[3] + c[4] + c[5]) + (c[1] + c[4] + c[7]);
-                    text += samples[i].name + "\t" + samples[j].name + "\t" + std::to_string(total);
-                    for (int k = 0; k < 9; ++k) text += "\t" + std::to_string(c[k]);
-                    text += "\t" + std::to_string(ibs0) + "\t" + std::to_string(total - ibs0 - ibs2) + "\t" + std::to_string(ibs2) + "\t";
-                    if (het) {
-                        snprintf(num, sizeof num, "%.4f", (double)((int64_t)c[4] - 2 * (int64_t)ibs0) / (double)het);
-                        text += num;
-                    } else
-                        text += ".";
-                    text += "\n";
-                }
-            pair_files.part = o.pairs + ".part";
-            FILE *f = fopen(pair_files.part.c_str(), "wb");
-            if (!f) throw std::runtime_error("cannot write " + o.pairs);
-            const bool short_write = fwrite(text.data(), 1, text.size(), f) != text.size();
-            if (fclose(f) != 0 || short_write || rename(pair_files.part.c_str(), o.pairs.c_str()) != 0) throw std::runtime_error("cannot write " + o.pairs);
-            pair_files.part.clear();
+            PartFile::put(o.pairs, pair_table_text(names, pair_table.data()));
             if (g_timers.on && pairs_calls[1]) {
                 g_timers.add("pairs: pack and count kernels (device)", (pairs_ms[0] + pairs_ms[1]) / 1000.0);
                 fprintf(stderr, "[malva-geno] pairs: %zu mg_pack_dosage, %zu mg_pair_counts, device ms per call: pack %.3f count %.3f\n", pairs_calls[0], pairs_calls[1],
@@ -2610,39 +2333,7 @@ int call_main(const Options &o)
             }
         }
         if (want_sample) {
-            // the text: five divisions per sample and the formatting are all the host does
-            std::string text = "#SAMPLE\tRECORDS\tCALLED\tMASKED\tBAD\tHOM_REF\tHET\tHOM_ALT\tHET_ALT\tTS\tTV\tINS\tDEL\tOTHER\tGQ_SUM\tCOV_SUM\tNORMAL\tOVERCOV\tSINGLE\tNOCOV";
-            for (int b = 0; b < 10; ++b) text += "\tGQ_" + std::to_string(10 * b);
-            text += "\tCALL_RATE\tHET_HOM\tTSTV\tMEAN_GQ\tMEAN_COV\n";
-            char num[64];
-            for (size_t i = 0; i < S; ++i) {
-                const uint64_t *c = &sample_table[i * MG_SAMPLE_SLOTS];
-                text += samples[i].name;
-                for (int k : {MG_SS_RECORDS, MG_SS_CALLED, MG_SS_MASKED, MG_SS_BAD, MG_SS_HOM_REF, MG_SS_HET, MG_SS_HOM_ALT, MG_SS_HET_ALT, MG_SS_TS, MG_SS_TV, MG_SS_INS,
-                              MG_SS_DEL, MG_SS_OTHER})
-                    text += "\t" + std::to_string(c[k]);
-                text += "\t" + std::to_string((int64_t)c[MG_SS_GQ_SUM]);
-                for (int k = MG_SS_COV_SUM; k < MG_SS_COUNTED; ++k) text += "\t" + std::to_string(c[k]);
-                const double ratio[5][2] = {{(double)c[MG_SS_CALLED], (double)c[MG_SS_RECORDS]},
-                                            {(double)c[MG_SS_HET], (double)c[MG_SS_HOM_ALT]},
-                                            {(double)c[MG_SS_TS], (double)c[MG_SS_TV]},
-                                            {(double)(int64_t)c[MG_SS_GQ_SUM], (double)c[MG_SS_CALLED]},
-                                            {(double)c[MG_SS_COV_SUM], (double)c[MG_SS_RECORDS]}};
-                for (const auto &r : ratio) {
-                    if (r[1] != 0) {
-                        snprintf(num, sizeof num, "\t%.4f", r[0] / r[1]);
-                        text += num;
-                    } else
-                        text += "\t.";
-                }
-                text += "\n";
-            }
-            sample_file.part = o.sample_stats + ".part";
-            FILE *f = fopen(sample_file.part.c_str(), "wb");
-            if (!f) throw std::runtime_error("cannot write " + o.sample_stats);
-            const bool short_write = fwrite(text.data(), 1, text.size(), f) != text.size();
-            if (fclose(f) != 0 || short_write || rename(sample_file.part.c_str(), o.sample_stats.c_str()) != 0) throw std::runtime_error("cannot write " + o.sample_stats);
-            sample_file.part.clear();
+            PartFile::put(o.sample_stats, sample_table_text(names, sample_table.data()));
             if (g_timers.on && sample_calls) {
                 g_timers.add("sample table: count kernel (device)", sample_ms / 1000.0);
                 fprintf(stderr, "[malva-geno] sample-stats: %zu mg_sample_counts, device ms per call: count %.3f\n", sample_calls, sample_ms / sample_calls);
