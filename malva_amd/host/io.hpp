@@ -1043,7 +1043,10 @@ class VcfReader {
                                 bool neg = false;
                                 if (*q == '-' || *q == '+') neg = *q++ == '-';
                                 long acc = 0;
-                                while (q < c && *q >= '0' && *q <= '9') acc = acc * 10 + (*q++ - '0');
+                                while (q < c && *q >= '0' && *q <= '9') {
+                                    acc = acc * 10 + (*q++ - '0');
+                                    if (acc > 1000000) acc = 1000000; // (as gt_column on the device: far beyond any allele number, and no digit string overflows)
+                                }
                                 val = (int)(neg ? -acc : acc);
                             }
                             put(val, ph);

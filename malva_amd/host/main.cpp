@@ -450,7 +450,10 @@ inline bool device_gt_wanted(const VcfReader &vcf)
     return vcf.keep.size() >= 1024;
 }
 // The records of one cut batch, block of text by block of text: mg_decode_gt_text over the spans, the entries back into the records.
-inline void decode_deferred(std::vector<Variant> &kept, Device &dev, VcfReader &vcf, const Options &o)
+struct GtDecodeCount {
+    size_t records = 0, calls = 0, on_host = 0; // records decoded on the device, in so many calls; of them, handed to the host decoder after all
+};
+inline void decode_deferred(std::vector<Variant> &kept, Device &dev, VcfReader &vcf, const Options &o, GtDecodeCount &count)
 {
     std::vector<uint64_t> off, mask;
     std::vector<uint32_t> len, sp_off, mx, ss;
@@ -485,6 +488,8 @@ inline void decode_deferred(std::vector<Variant> &kept, Device &dev, VcfReader &
             sg.resize(n_entries);
             dev.check(mg_decode_gt_entries(dev.ctx, ss.data(), sg.data()), "mg_decode_gt_entries");
         }
+        count.records += n;
+        ++count.calls;
         for (size_t r = 0; r < n; ++r) {
             Variant &v = kept[a + r];
             v.sp_default = dflt;
@@ -492,6 +497,7 @@ inline void decode_deferred(std::vector<Variant> &kept, Device &dev, VcfReader &
             v.max_allele = mx[r];
             if (mx[r] > 127) { // an allele number the 7-bit words cannot hold: this record is decoded here after all
                 vcf.genotypes_on_host(v);
+                ++count.on_host;
                 continue;
             }
             v.sp_sample.assign(ss.begin() + sp_off[r], ss.begin() + sp_off[r + 1]);
@@ -570,6 +576,7 @@ template <class F> size_t for_each_block(VcfReader &vcf, const Options &o, const
         std::vector<uint32_t> ref_size, min_size, cid, off;
         size_t i = 0, cells = 0, n_cut_blocks = 0, n_batches = 0;
         bool more = true, seen_kept = false;
+        GtDecodeCount gt_count;
         Variant v;
         while (more) {
             kept.clear();
@@ -588,7 +595,7 @@ template <class F> size_t for_each_block(VcfReader &vcf, const Options &o, const
             }
             delete t_parse;
             if (kept.empty()) continue;
-            decode_deferred(kept, *cutter, vcf, o);
+            decode_deferred(kept, *cutter, vcf, o, gt_count);
             const bool carry = !vb.empty();
             const size_t n = kept.size() + (carry ? 1 : 0);
             pos.resize(n); ref_size.resize(n); min_size.resize(n); cid.resize(n); off.resize(n + 1);
@@ -637,6 +644,9 @@ template <class F> size_t for_each_block(VcfReader &vcf, const Options &o, const
             vb.clear();
         }
         std::cerr << "[malva-geno] " << n_cut_blocks << " block(s) cut on the device in " << n_batches << " batch(es)" << std::endl;
+        if (gt_count.calls)
+            std::cerr << "[malva-geno] sample columns of " << gt_count.records << " record(s) decoded on the device in " << gt_count.calls << " call(s), "
+                      << gt_count.on_host << " of them handed to the host decoder" << std::endl;
         return i;
     }
     Block vb((int)o.k);
@@ -2067,6 +2077,7 @@ int call_main(const Options &o)
     auto prefix_of = [&](Variant &v) { return std::move(v.text_prefix); }; // (made by the thread that decoded the record)
 
     const bool iso_path = getenv("MALVA_GENO_ISO_PATH") && atoi(getenv("MALVA_GENO_ISO_PATH")) != 0;
+    const bool host_enum = getenv("MALVA_GENO_HOST_ENUM") != nullptr; // (every block goes to the host enumerator: every record is kept for it)
     std::string base_name;
     bool base_known = false, base_found = false;
     uint64_t base_value = 0;
@@ -2109,11 +2120,18 @@ int call_main(const Options &o)
             iso.var_gt_off.push_back(iso.var_gt_off.back() + n_gt(A));
         } else {
             // main.cpp:556-557: extract_kmers + set_coverages happen on the device for the whole batch of blocks
+            // A record of more than 127 alleles sends its whole batch to the host enumerator (gen.wide_alleles), which needs every record
+            // kept: its block is a batch of its own.  The records in front of it, the lone ones a small panel has let go of among them,
+            // leave first, and the batch is closed again behind the block, so that no other block follows it to the host.
+            bool wide = false;
+            for (const Variant &v : vb.vars) wide = wide || v.n_alleles() > 127;
+            if (wide && !recs.empty()) run_and_print();
+            if (wide) gen.wide_alleles = true;
             gen.blk_base.push_back(base_value);
             gen.blk_len.push_back((uint32_t)reference.size());
             // a record tier 1 is sure to take (the device's own test, block_pipeline.h: classify_lone) can never be handed back:
             // with its genotype words made here, nothing of it needs keeping
-            const bool sure_lone = gen.dense_gt && o.k <= MG_MAX_PACKED_K && vb.is_lone_short() && base_found && vb.vars[0].ref_pos >= (int)o.k / 2 &&
+            const bool sure_lone = gen.dense_gt && !gen.wide_alleles && !host_enum && o.k <= MG_MAX_PACKED_K && vb.is_lone_short() && base_found && vb.vars[0].ref_pos >= (int)o.k / 2 &&
                                    (long)vb.vars[0].ref_pos + vb.vars[0].ref_size + (long)(o.k + 1) / 2 <= (long)reference.size();
             for (Variant &v : vb.vars) {
                 const uint32_t A = (uint32_t)v.n_alleles();
@@ -2147,6 +2165,7 @@ int call_main(const Options &o)
             }
             gen.blk_var_off.push_back((uint32_t)gen.n());
             gen.block_ref.push_back(&reference);
+            if (wide) run_and_print();
         }
         if (gen.genotype_cells >= (200u << 20)) run_and_print(); // bound the panel genotypes held in memory
         if (recs.size() >= batch_records) run_and_print();

@@ -402,3 +402,188 @@ def test_k_above_64_goes_through_the_bytewise_forms(tmp_path, k, ref_k, haploid)
     strip = lambda s: re.sub(r";GTS=[^\t]*", "", s)
     assert strip(got) == strip(want)
     assert sum(1 for l in got.split("\n") if l and not l.startswith("#") and not l.endswith(":0")) > 10
+
+
+# ---- panels that take the device decode of their sample columns by themselves (tests/gt_call_panels.py) ----------------------
+def _env(**kw):
+    env = {k: v for k, v in os.environ.items() if k not in ("MALVA_GENO_GT_DEVICE", "MALVA_GENO_CUT_BATCH", "MALVA_GENO_HOST_ENUM", "MALVA_GENO_BATCH")}
+    env.update(kw)
+    return env
+
+
+def _cli_err(args, env):
+    """one run -> (stdout, stderr)"""
+    r = subprocess.run([BIN] + args, capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r.stdout, r.stderr
+
+
+def _index_and_call(args, prefix, env):
+    """`index` then `call -v` -> (index keys, both filters, the output, stderr of index, stderr of call)"""
+    from oracle import index_file
+    _, err_index = _cli_err(["index"] + args, env)
+    filt, keys = index_file.read_index(prefix + ".vcf.c43.k35.malvax.zst")
+    out, err_call = _cli_err(["call"] + args, env)
+    return keys, filt, out, err_index, err_call
+
+
+def _same_run(a, b):
+    import numpy as np
+    assert a[0] == b[0] and len(a[0]) > 50                               # the same index: keys, and both filters' set bits
+    for x, y in zip(a[1], b[1]):
+        assert x[:2] == y[:2] and np.array_equal(x[2], y[2])
+    assert a[2] == b[2]
+
+
+def _decoded_on_device(err):
+    """what the run says of its sample columns -> (records decoded on the device, calls, records handed to the host decoder), or None"""
+    m = re.search(r"sample columns of (\d+) record\(s\) decoded on the device in (\d+) call\(s\), (\d+) of them handed to the host decoder", err)
+    return tuple(int(x) for x in m.groups()) if m else None
+
+
+def _host_blocks(err_call):
+    """blocks `call` enumerated on the host"""
+    return sum(int(x) for x in re.findall(r"(\d+) block\(s\) enumerated on the host", err_call))
+
+
+def _panel_runs(tmp, wide):
+    """the panel, its table, its host-decoded run (MALVA_GENO_GT_DEVICE=0), which equals the oracle pipeline"""
+    import gt_call_panels as gcp
+    from malva_amd import synth
+    cp = gcp.call_panel(str(tmp / "p"), wide=wide)
+    hi, lo, cnt = synth.flat_kmer_table(cp.panel, 40_000, 35, 43, seed=5)
+    rows = synth.unpack_ascii(hi, lo, 43)
+    table = str(tmp / "donor.kmers")
+    with open(table + ".txt", "w") as fh:
+        for r, c in zip(rows, cnt):
+            fh.write("%s\t%d\n" % (bytes(r[:43]).decode(), int(c)))
+    args = ["-k", "35", "-r", "43", "-b", "1", "-v", cp.prefix + ".fa", cp.prefix + ".vcf", table]
+    host = _index_and_call(args, cp.prefix, _env(MALVA_GENO_GT_DEVICE="0"))
+    assert _decoded_on_device(host[3]) is None and _decoded_on_device(host[4]) is None
+    opt = pipeline.Options(haploid=False, verbose=True, k=35, ref_k=43, bf_size=1 << 33)
+    t0 = time.time()
+    idx = pipeline.index(cp.prefix + ".fa", cp.prefix + ".vcf", opt)
+    kmers = [(l.split()[0].encode(), int(l.split()[1])) for l in open(table + ".txt")]
+    want = pipeline.call(cp.prefix + ".fa", cp.prefix + ".vcf", idx, kmers, opt)
+    print("oracle: %.1f s for the %s panel" % (time.time() - t0, "wide" if wide else "plain"))
+    strip = lambda s: re.sub(r";GTS=[^\t]*", "", s)
+    assert strip(host[2]) == strip(want)
+    assert sum(1 for l in host[2].split("\n") if l and not l.startswith("#") and not l.endswith(":0")) > 20
+    return dict(cp=cp, tmp=tmp, table=table, args=args, host=host, kmers=kmers)
+
+
+@pytest.fixture(scope="module")
+def plain_panel(tmp_path_factory):
+    """1,030 diploid samples, 2,200 records in one block of text, no record of more than two alleles.  The oracle took 8.0 s to index and
+    10.5 s to call such a panel on the CPU this was written on, 6.8 s for both beside the GPU."""
+    return _panel_runs(tmp_path_factory.mktemp("plain_panel"), False)
+
+
+@pytest.fixture(scope="module")
+def wide_panel(tmp_path_factory):
+    """the same panel with two of its records given 130 ALT alleles (the oracle's cost is the plain panel's)"""
+    return _panel_runs(tmp_path_factory.mktemp("wide_panel"), True)
+
+
+def test_device_decode_by_itself_with_two_default_words_in_one_panel_batch(plain_panel):
+    """(a) runs of 300 records in which 0/0 and 0|0 take turns as the commonest word, decoded 100 records a call: every decode call
+    chooses its own default word, the panel batch (all 2,200 records: no record here sends a batch to the host) one of the two, and
+    pack_genotypes re-bases the records of the other kind for mg_cover_blocks_sparse / mg_index_blocks_sparse, which take nearly every
+    block.  MALVA_GENO_HOST_ENUM=1 is then a second way to the same bytes: the pairs rebuilt from each record's own entries."""
+    import gt_call_panels as gcp
+    import gt_text_cases as gtc
+    from malva_amd import Context
+    cp = plain_panel["cp"]
+    raw, off, ln, gi = gtc._spans(cp.prefix + ".vcf")
+    with Context(35, 43, 1 << 16) as ctx:
+        first = ctx.decode_gt_text(raw, off[:100], ln[:100], gi[:100], gcp.CALL_SAMPLES)[0]
+        second = ctx.decode_gt_text(raw, off[300:400], ln[300:400], gi[300:400], gcp.CALL_SAMPLES)[0]
+    assert (first, second) == (0, 1 << 14)
+    dev = _env(MALVA_GENO_CUT_BATCH=str(gcp.CALL_CUT_BATCH))
+    got = _index_and_call(plain_panel["args"], cp.prefix, dev)
+    calls = gcp.CALL_RECORDS // gcp.CALL_CUT_BATCH
+    assert _decoded_on_device(got[3]) == (gcp.CALL_RECORDS, calls, 0) and _decoded_on_device(got[4]) == (gcp.CALL_RECORDS, calls, 0)
+    general = re.search(r"(\d+) general block\(s\): (\d+) enumerated on the device", got[3])
+    assert general and int(general.group(2)) > 20 and int(general.group(2)) > 0.9 * int(general.group(1))       # index: the clusters, nine in ten on the device at least
+    n_blocks = int(re.search(r"(\d+) block\(s\) cut on the device", got[4]).group(1))
+    assert n_blocks > 2000 and _host_blocks(got[4]) < n_blocks // 10     # call: nine blocks in ten at least covered on the device, from the re-based entries
+    _same_run(got, _index_and_call(plain_panel["args"], cp.prefix, dict(dev, MALVA_GENO_GT_DEVICE="0")))
+    assert got[2] == plain_panel["host"][2]
+    out, err = _cli_err(["call"] + plain_panel["args"], dict(dev, MALVA_GENO_HOST_ENUM="1"))
+    assert _host_blocks(err) == n_blocks and out == got[2]
+
+
+def test_device_decode_hands_records_with_alleles_above_127_back_to_the_host(wide_panel):
+    """(b) the whole block of text in one decode call (2,200 records: more than either kernel's grid); the two records of 130 ALT
+    alleles, one alone and one inside a cluster, go back to genotypes_on_host alone and come out as on the host path"""
+    import gt_call_panels as gcp
+    cp = wide_panel["cp"]
+    dev = _index_and_call(wide_panel["args"], cp.prefix, _env())
+    assert _decoded_on_device(dev[3]) == (gcp.CALL_RECORDS, 1, 2) and _decoded_on_device(dev[4]) == (gcp.CALL_RECORDS, 1, 2)
+    n_blocks = int(re.search(r"(\d+) block\(s\) cut on the device", dev[4]).group(1))
+    assert 2 <= _host_blocks(dev[4]) < 2 + n_blocks // 10                # the two blocks of the wide records, and no batch that follows them to the host
+    _same_run(dev, wide_panel["host"])
+    recs = [l for l in dev[2].split("\n") if l and not l.startswith("#")]
+    assert len(recs) == gcp.CALL_RECORDS
+    for v in (cp.wide_lone, cp.wide_clustered):
+        assert recs[v].split("\t")[4].count(",") == gcp.WIDE_ALTS - 1
+    out, err = _cli_err(["call"] + wide_panel["args"], _env(MALVA_GENO_HOST_ENUM="1"))
+    assert _host_blocks(err) == n_blocks and out == dev[2]
+
+
+def test_device_decode_of_five_kept_samples_of_the_wide_panel(wide_panel):
+    """(c) -s keeping 5 of the 1,030 columns, the last among them.  (Five kept samples do not take the device path by themselves:
+    MALVA_GENO_GT_DEVICE=1 asks for it.)  The oracle took 0.7 s more for this one.  With so few samples the host-decoded `call` makes
+    the genotype words itself and lets go of the lone records; a record of 131 alleles sends its batch to the host enumerator, which
+    once found those lone records gone ("the device handed back a record tier 1 should have taken"), as MALVA_GENO_HOST_ENUM=1 would have."""
+    import gt_call_panels as gcp
+    cp = wide_panel["cp"]
+    sfile = str(wide_panel["tmp"] / "keep.txt")
+    with open(sfile, "w") as fh:
+        fh.write("S1029\nS6\nS300\nS5\nS777\n")
+    args = wide_panel["args"][:7] + ["-s", sfile] + wide_panel["args"][7:]
+    host_env = _env(MALVA_GENO_GT_DEVICE="0", MALVA_GENO_VCF_POOL="1")
+    host = _index_and_call(args, cp.prefix, host_env)
+    assert _decoded_on_device(host[4]) is None
+    dev = _index_and_call(args, cp.prefix, _env(MALVA_GENO_GT_DEVICE="1", MALVA_GENO_VCF_POOL="1"))
+    assert _decoded_on_device(dev[4]) == (gcp.CALL_RECORDS, 1, 2)
+    _same_run(dev, host)
+    n_blocks = int(re.search(r"(\d+) block\(s\) cut on the device", host[4]).group(1))
+    assert 2 <= _host_blocks(host[4]) < 2 + n_blocks // 10
+    out, err = _cli_err(["call"] + args, dict(host_env, MALVA_GENO_HOST_ENUM="1"))     # (every block to the host enumerator: no lone record let go)
+    assert _host_blocks(err) == n_blocks and out == host[2]
+    opt = pipeline.Options(haploid=False, verbose=True, k=35, ref_k=43, bf_size=1 << 33, samples=sfile)
+    t0 = time.time()
+    idx = pipeline.index(cp.prefix + ".fa", cp.prefix + ".vcf", opt)
+    want = pipeline.call(cp.prefix + ".fa", cp.prefix + ".vcf", idx, wide_panel["kmers"], opt)
+    print("oracle: %.1f s for five kept samples" % (time.time() - t0))
+    strip = lambda s: re.sub(r";GTS=[^\t]*", "", s)
+    assert strip(host[2]) == strip(want)
+    assert strip(host[2]) != strip(wide_panel["host"][2])                # (the subset changes the result)
+
+
+@pytest.mark.parametrize("allele", ["5", "128", "32768", "2147483648", "4294967296"])
+def test_allele_beyond_the_alt_list_is_refused_on_both_decode_paths(tmp_path, allele):
+    """(d) a record of 3 alleles whose sample 7 carries `allele`|0: `call` stops with the record's name on either path.  (The host
+    decoder once read 4294967296 as allele 0 and 2147483648 as a negative number, which reads as 0 too.)"""
+    import numpy as np
+    import gt_call_panels as gcp
+    assert allele in gcp.BEYOND_ALLELES
+    prefix = str(tmp_path / "b")
+    lines, at = gcp.beyond_panel(prefix)
+    table = str(tmp_path / "t.kmers")
+    with open(table + ".txt", "w") as fh:
+        for row in np.random.default_rng(3).choice(list("ACGT"), size=(200, 43)):
+            fh.write("".join(row) + "\t5\n")
+    args = ["-k", "35", "-r", "43", "-b", "1", "-v", prefix + ".fa", prefix + ".vcf", table]
+    gcp.write_beyond(prefix, lines, at, None)
+    run_cli(["index"] + args, env=_env())                                # (the index of the panel while the allele is still inside the list)
+    good, err = _cli_err(["call"] + args, _env())
+    assert _decoded_on_device(err) == (gcp.BEYOND_RECORDS, 1, 0)         # 1,030 samples: the device path by itself
+    host, err = _cli_err(["call"] + args, _env(MALVA_GENO_GT_DEVICE="0"))
+    assert _decoded_on_device(err) is None and good == host and good.count("\n") > gcp.BEYOND_RECORDS
+    seq, pos = gcp.write_beyond(prefix, lines, at, allele)
+    for env in (_env(), _env(MALVA_GENO_GT_DEVICE="0")):
+        r = subprocess.run([BIN, "call"] + args, capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode != 0, "allele %s of a record of 3 alleles went through" % allele
+        assert "GT allele beyond the kept ALT list at %s:%d" % (seq, pos) in r.stderr, r.stderr[-2000:]

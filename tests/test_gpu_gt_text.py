@@ -5,73 +5,10 @@ GT behind other FORMAT keys, short records, a sample subset, haploid mode."""
 import numpy as np
 import pytest
 
+from gt_text_cases import _dense, _expected, _spans, _write
 from malva_amd import Context
-from oracle import model
 
 pytestmark = pytest.mark.gpu
-
-
-def _write(path, records, n_samples, fmt_of=lambda i: "GT", pad=False):
-    """pad: records with fewer sample columns than the header are completed with "." -- what the product reads them as;
-    the oracle's reader (like htslib) has no opinion on such a record, so it is given the completed one"""
-    if pad:
-        records = [(list(c) if c is not None else []) + ["."] * (n_samples - (len(c) if c is not None else 0)) for c in records]
-    with open(path, "w") as fh:
-        fh.write("##fileformat=VCFv4.2\n##INFO=<ID=AF,Number=A,Type=Float,Description=\"af\">\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"g\">\n")
-        fh.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join("S%d" % i for i in range(n_samples)) + "\n")
-        for i, cells in enumerate(records):
-            fh.write("1\t%d\t.\tA\tC,G,T\t.\t.\tAF=0.1,0.1,0.1\t%s\t%s\n" % (100 + 40 * i, fmt_of(i), "\t".join(cells)) if cells is not None else
-                     "1\t%d\t.\tA\tC,G,T\t.\t.\tAF=0.1,0.1,0.1\t%s\n" % (100 + 40 * i, fmt_of(i)))
-
-
-def _spans(path):
-    """what the host side of the decode does: per record line, where its sample columns start and end, and where GT sits in FORMAT"""
-    raw = open(path, "rb").read()
-    off, ln, gi = [], [], []
-    at = 0
-    for line in raw.split(b"\n"):
-        if line and not line.startswith(b"#"):
-            cols = line.split(b"\t", 9)
-            gi.append(cols[8].split(b":").index(b"GT"))
-            if len(cols) > 9:
-                off.append(at + len(line) - len(cols[9]))
-                ln.append(len(cols[9]))
-            else:
-                off.append(at + len(line))
-                ln.append(0)
-        at += len(line) + 1
-    return raw, np.array(off, np.uint64), np.array(ln, np.uint32), np.array(gi, np.int32)
-
-
-def _expected(path, samples_file, haploid):
-    rd = model.VCFReader(path, samples_file or "-")
-    words, masks, mx = [], [], []
-    for v in rd.records():
-        w = []
-        m = 0
-        big = 0
-        for (a1, a2), ph in zip(v.genotypes, v.phasing):
-            w.append((a1 & 127) | (1 << 14) if haploid else (a1 & 127) | (a2 & 127) << 7 | int(ph) << 14)
-            m |= 1 << (a1 & 63)
-            if not haploid:
-                m |= 1 << (a2 & 63)
-            big = max(big, a1, a2)
-        words.append(np.array(w, np.uint16))
-        masks.append(m)
-        mx.append(big)
-    return words, masks, mx
-
-
-def _dense(n_keep, dflt, sp_off, ss, sg):
-    out = []
-    for r in range(len(sp_off) - 1):
-        w = np.full(n_keep, dflt, np.uint16)
-        e0, e1 = int(sp_off[r]), int(sp_off[r + 1])
-        assert np.all(np.diff(ss[e0:e1].astype(np.int64)) > 0)          # ascending samples inside a record
-        assert np.all(sg[e0:e1] != dflt)                                 # only the words that differ from the default
-        w[ss[e0:e1]] = sg[e0:e1]
-        out.append(w)
-    return out
 
 
 @pytest.mark.parametrize("haploid", [False, True])
