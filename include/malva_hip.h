@@ -755,8 +755,11 @@ int mg_bf_import(mg_ctx *ctx, int which, int mode, uint64_t size_bits, const uin
 int mg_bf_export_sparse(mg_ctx *ctx, int which, uint64_t *positions_out, uint16_t *counts_out);
 int mg_bf_import_sparse(mg_ctx *ctx, int which, int mode, uint64_t size_bits, const uint64_t *positions,
                         const uint16_t *counts, uint64_t n);
-/* KMAP: n keys as NUL-terminated rows of `stride` bytes + values */
+/* KMAP: n keys as NUL-terminated rows of `stride` bytes + values.  stride >= k + 1, and beyond the longest key of another
+ * length the map holds (MG_ERR_ARG otherwise: a key cut short would name another key); MG_MAX_KMER + 1 always fits */
 int mg_map_export(mg_ctx *ctx, char *rows_out, size_t stride, int32_t *vals_out);
+/* KMAP::add_key of every row, then the key of row i set to vals[i] (vals may be NULL: insert only).  A file may repeat a key
+ * or name one that is already present: the last row that names a key gives its value, as when the reference reads row by row. */
 int mg_map_import(mg_ctx *ctx, const char *rows, size_t stride, size_t n, const int32_t *vals);
 
 /* ---- introspection for tests / profiling ---------------------------------- */
@@ -766,6 +769,14 @@ int mg_debug_bf_index(mg_ctx *ctx, int which, const char *rows, size_t stride, s
 /* same from packed k-mers of length klen (1..64), MSB-first right-aligned */
 int mg_debug_packed_index(mg_ctx *ctx, int which, const uint64_t *hi, const uint64_t *lo, size_t n, uint32_t klen,
                           uint64_t *idx_out);
+/* the exclusive scan mg_bf_finalize runs over its tile sums, on n values of the caller's: x is replaced by its exclusive prefix
+ * (each entry modulo 2^32, as the kernel stores it), *total by the sum of all of them in 64 bits.  n == 0 gives a total of 0. */
+int mg_debug_tile_scan(mg_ctx *ctx, uint32_t *x, uint64_t n, uint64_t *total);
+/* the filter's directory inside the records as the call-time lookups read it: for each slot idx[i] of `bf` (MG_BF_ALT), the
+ * counter index (rank) of its bit or -1 when the bit is clear, and the u16 counter the genotyping would read (0 when clear),
+ * through the context's current views -- so the counters come from the records' copies whenever those are live.
+ * MG_ERR_STATE unless `bf` is finalised, MG_ERR_ARG for a slot at or beyond the filter's size. */
+int mg_debug_bucket_count(mg_ctx *ctx, const uint64_t *idx, uint64_t n, int64_t *rank_out, uint32_t *count_out);
 /* timing of the first chunk of the most recent mg_kmc_scan* in milliseconds (HIP
  * events on the context's stream): ms_out[0] filter kernel, [1] probe kernel,
  * [2] hit kernel (with the ticket form [0] is its two passes together); rows_out[0] = rows that passed the gate (last chunk),

@@ -15,6 +15,9 @@ import sys
 import numpy as np
 
 BF_ALT, BF_CTX = 0, 1
+MG_ERR_ARG = -1
+MG_MAX_KMER = 128
+MAX_ROW = (MG_MAX_KMER + 1 + 7) // 8 * 8   # 136: MG_MAX_KMER bytes + NUL, rounded to 8 (the stride the command line uses)
 STREAM_DEFAULT = 1          # MG_STREAM_DEFAULT: HIP's legacy default stream (a NULL handle means the context's own stream)
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 COMM_ID_BYTES = 128
@@ -172,6 +175,8 @@ def lib():
         "mg_map_import": [vp, vp, sz, sz, vp],
         "mg_debug_bf_index": [vp, it, vp, sz, sz, vp],
         "mg_debug_packed_index": [vp, it, vp, vp, sz, u32, vp],
+        "mg_debug_tile_scan": [vp, vp, u64, vp],
+        "mg_debug_bucket_count": [vp, vp, u64, vp, vp],
         "mg_scan_stats": [vp, vp, vp],
         "mg_blocks_stats": [vp, vp, vp],
         "mg_set_option": [vp, cp, i64],
@@ -206,7 +211,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_index_isolated",
             "mg_lookup_cover", "mg_cover_blocks", "mg_index_blocks", "mg_cover_blocks_sparse", "mg_index_blocks_sparse", "mg_genotype", "mg_reference_upload", "mg_call_isolated", "mg_call_isolated_device",
             "mg_bf_export", "mg_bf_import", "mg_bf_export_sparse", "mg_bf_import_sparse", "mg_map_export", "mg_map_import", "mg_debug_bf_index",
-            "mg_debug_packed_index", "mg_scan_stats", "mg_blocks_stats", "mg_set_option", "mg_get_option"]
+            "mg_debug_packed_index", "mg_debug_tile_scan", "mg_debug_bucket_count", "mg_scan_stats", "mg_blocks_stats", "mg_set_option", "mg_get_option"]
 
 
 def _p(a):
@@ -385,6 +390,21 @@ class Context:
         self._ck(self._L.mg_debug_packed_index(self.h, which, _p(hi), _p(lo), hi.shape[0], klen, _p(out)))
         return out
 
+    def tile_scan(self, x):
+        """finalize's scan of its tile sums on the caller's values: (exclusive prefix modulo 2^32, total)"""
+        x = np.array(x, dtype=np.uint32)
+        total = C.c_uint64()
+        self._ck(self._L.mg_debug_tile_scan(self.h, _p(x) if x.size else None, x.size, C.byref(total)))
+        return x, total.value
+
+    def bucket_count(self, idx):
+        """(rank or -1, u16 counter) of filter slots of `bf` as the call-time lookups read them from the records"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        rank = np.zeros(idx.size, dtype=np.int64)
+        count = np.zeros(idx.size, dtype=np.uint32)
+        self._ck(self._L.mg_debug_bucket_count(self.h, _p(idx), idx.size, _p(rank), _p(count)))
+        return rank, count
+
     def bf_export(self, which):
         size, nset, mode = self.bf_info(which)
         words = np.zeros((size + 63) // 64, dtype=np.uint64)
@@ -440,11 +460,14 @@ class Context:
 
     def map_export(self):
         n = self.map_size()
+        vals = np.zeros(n, dtype=np.int32)
         stride = (self.k + 1 + 7) // 8 * 8
         rows = np.zeros((n, stride), dtype=np.uint8)
-        vals = np.zeros(n, dtype=np.int32)
-        if n:
-            self._ck(self._L.mg_map_export(self.h, _p(rows), stride, _p(vals)))
+        rc = self._L.mg_map_export(self.h, _p(rows), stride, _p(vals)) if n else 0
+        if rc == MG_ERR_ARG and stride < MAX_ROW:                # a key longer than k in the host's list: the widest row always fits
+            rows = np.zeros((n, MAX_ROW), dtype=np.uint8)
+            rc = self._L.mg_map_export(self.h, _p(rows), MAX_ROW, _p(vals))
+        self._ck(rc)
         keys = [bytes(r).split(b"\0", 1)[0] for r in rows]
         return keys, vals
 

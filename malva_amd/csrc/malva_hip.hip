@@ -4524,10 +4524,9 @@ void unpack_lform(u64 lo, u64 hi, u32 k, char *out)
 }
 } // namespace
 
-// Regular keys all have length k (a shorter or longer pure-ACGT key cannot be
-// told apart once packed, so mg_map_insert of a row whose length != k is irregular
-// from the table's point of view only if it holds a non-ACGT byte; rows are
-// expected to be k long, as every signature k-mer of the reference is).
+// The table's keys first (all k long: pack_regular sends every row of another length, pure ACGT or not, to the host's
+// list, because a shorter or longer key cannot be told apart once packed), then the host's list.  Rows are expected to be
+// k long, as every signature k-mer of the reference is; a key of the list that is longer needs a wider row than k + 1.
 MG_EXPORT int mg_map_export(mg_ctx *c, char *rows_out, size_t stride, int32_t *vals_out)
 {
     const DeviceGuard on_device(c, KEEP);
@@ -4537,6 +4536,9 @@ MG_EXPORT int mg_map_export(mg_ctx *c, char *rows_out, size_t stride, int32_t *v
     TRY(map_dump(c, &lo, &hi, &ids));
     if (!rows_out && !vals_out) return MG_OK;
     if (stride < c->k + 1) return fail(c, MG_ERR_ARG, "stride %zu < k+1", stride);
+    if (rows_out)
+        for (auto &kv : c->map.irregular) // (a key other than k long: a row that cut it short would name another key)
+            if (kv.first.size() + 1 > stride) return fail(c, MG_ERR_ARG, "stride %zu < a key of %zu bytes + NUL", stride, kv.first.size());
     std::vector<u32> vals(c->map.rows_total);
     if (c->map.rows_total && c->coh_planes) { // the selected plane
         void *d32;
@@ -4572,10 +4574,24 @@ MG_EXPORT int mg_map_import(mg_ctx *c, const char *rows, size_t stride, size_t n
     TRY(mg_map_insert(c, rows, stride, n));
     if (vals) {
         // values go through a lookup of each key (a file may repeat a key, or name one that was already present:
-        // the counter of a key is the one its first insertion row owns); irregular rows live in the host list
-        // under the canonical form KMAP::canonical gives them (kmap.hpp:86-97)
+        // the counter of a key is the one its first insertion row owns, and the last row that names the key gives
+        // its value); irregular rows live in the host list under the canonical form KMAP::canonical gives them
+        // (kmap.hpp:86-97), and the loop below takes them in row order
         std::vector<u8> irr(n);
-        TRY(run_rows<OP_MAP_SET>(c, 0, rows, stride, n, vals, nullptr, nullptr, 0, irr.data()));
+        void *d_rows, *d_vals, *d_last, *d_irr;
+        const u64 n_ids = c->map.rows_total; // (>= n: the insert above has counted these rows)
+        TRY(upload(c, c->s_rows, rows, stride * n, &d_rows));
+        TRY(upload(c, c->s_aux, vals, 4 * n, &d_vals));
+        TRY(scratch(c, c->s_misc[7], 4 * n_ids, &d_last));
+        TRY(scratch(c, c->s_irr, n, &d_irr));
+        HIP_TRY(c, hipMemsetAsync(d_last, 0, 4 * n_ids, c->stream));
+        hipLaunchKernelGGL(map_set_kernel<0>, dim3(nblocks(n)), dim3(TPB), 0, c->stream, (const u8 *)d_rows, stride, n, view(c), view(c, MG_BF_ALT),
+                           (const u32 *)d_vals, (u32 *)d_last, (u8 *)d_irr);
+        hipLaunchKernelGGL(map_set_kernel<1>, dim3(nblocks(n)), dim3(TPB), 0, c->stream, (const u8 *)d_rows, stride, n, view(c), view(c, MG_BF_ALT),
+                           (const u32 *)d_vals, (u32 *)d_last, (u8 *)d_irr);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(irr.data(), d_irr, n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (size_t i = 0; i < n; ++i)
             if (irr[i]) {
                 auto it = c->map.irregular.find(host_irregular_key(rows + i * stride, stride));
@@ -4928,5 +4944,58 @@ MG_EXPORT int mg_reads_stats(mg_ctx *c, float *ms_out, uint64_t *counts_out)
         counts_out[3] = R.passes;
         counts_out[4] = R.n_kept;
     }
+    return MG_OK;
+}
+
+// ---- introspection of the stores (tests): kept last, so that no other kernel moves in the code object -----------------------
+
+namespace {
+// what the call-time lookups read of the directory inside the records, one thread per filter slot (mg_debug_bucket_count)
+__global__ void __launch_bounds__(TPB) bucket_debug_kernel(MapView m, BFView bf, const u64 *idx, u64 n, long long *rank, u32 *count)
+{
+    const u64 i = (u64)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    rank[i] = bucket_rank(m, idx[i]);
+    count[i] = bucket_count(m, bf, idx[i]);
+}
+} // namespace
+
+// launch_tile_scan on the caller's values, with the buffers mg_bf_finalize gives it
+MG_EXPORT int mg_debug_tile_scan(mg_ctx *c, uint32_t *x, uint64_t n, uint64_t *total)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if ((n && !x) || !total) return fail(c, MG_ERR_ARG, "x or total is NULL");
+    void *d_tiles;
+    TRY(upload(c, c->s_misc[1], x, n * 4, &d_tiles));
+    unsigned long long *d_total = c->d_hit_count, t = 0;
+    TRY(launch_tile_scan(c, (u32 *)d_tiles, n, d_total));
+    if (n) HIP_TRY(c, hipMemcpyAsync(x, d_tiles, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&t, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *total = t;
+    return MG_OK;
+}
+// bucket_rank / bucket_count of filter slots, through the views a lookup launched now would get
+MG_EXPORT int mg_debug_bucket_count(mg_ctx *c, const uint64_t *idx, uint64_t n, int64_t *rank_out, uint32_t *count_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    const BFState &b = c->bf[MG_BF_ALT];
+    if (!b.mode || !c->map.slots) return fail(c, MG_ERR_STATE, "mg_debug_bucket_count needs `bf` finalised (the directory is written then)");
+    if (n == 0) return MG_OK;
+    if (!idx || !rank_out || !count_out) return fail(c, MG_ERR_ARG, "NULL pointer");
+    for (u64 i = 0; i < n; ++i)
+        if (idx[i] >= b.size) return fail(c, MG_ERR_ARG, "slot %llu is outside the filter (%llu bits)", (unsigned long long)idx[i], (unsigned long long)b.size);
+    void *d_idx, *d_rank, *d_count;
+    TRY(upload(c, c->s_misc[5], idx, n * 8, &d_idx));
+    TRY(scratch(c, c->s_misc[6], n * 8, &d_rank));
+    TRY(scratch(c, c->s_out, n * 4, &d_count));
+    hipLaunchKernelGGL(bucket_debug_kernel, dim3(nblocks(n)), dim3(TPB), 0, c->stream, view(c), view(c, MG_BF_ALT), (const u64 *)d_idx, (u64)n, (long long *)d_rank,
+                       (u32 *)d_count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(rank_out, d_rank, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(count_out, d_count, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MG_OK;
 }

@@ -34,7 +34,7 @@ template <class CAN> __device__ __forceinline__ bool pack_regular(const CAN &c, 
     return true;
 }
 
-enum RowOp { OP_BF_INSERT, OP_BF_TEST, OP_BF_INC, OP_BF_GET, OP_BF_INDEX, OP_MAP_TEST, OP_MAP_INC, OP_MAP_GET, OP_MAP_SET, OP_WEIGHT };
+enum RowOp { OP_BF_INSERT, OP_BF_TEST, OP_BF_INC, OP_BF_GET, OP_BF_INDEX, OP_MAP_TEST, OP_MAP_INC, OP_MAP_GET, OP_WEIGHT };
 
 // One thread per row.  H4/H5/H7/H8 (bloom_filter.hpp:81-125) and H9
 // (kmap.hpp:99-131) in batch form, plus the mixed lookup of set_coverages
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(TPB) rows_kernel(const u8 *rows, size_t stride
     const u8 *row = rows + i * stride;
     const int k = row_len(row, (int)stride);
     CanonBytes<RowIn> can(RowIn{row}, k);
-    bool want_map = OP == OP_MAP_TEST || OP == OP_MAP_INC || OP == OP_MAP_GET || OP == OP_MAP_SET;
+    bool want_map = OP == OP_MAP_TEST || OP == OP_MAP_INC || OP == OP_MAP_GET;
     if (OP == OP_WEIGHT) want_map = is_ref[i] != 0;
     if (want_map) {
         U128 key;
@@ -61,7 +61,6 @@ __global__ void __launch_bounds__(TPB) rows_kernel(const u8 *rows, size_t stride
         if (irregular) irregular[i] = regular ? 0 : 1;
         if (OP == OP_MAP_TEST) ((u8 *)out)[i] = s >= 0;
         if (OP == OP_MAP_INC && s >= 0) atomicAdd(map_cell(map, (u32)s), counters[i]);
-        if (OP == OP_MAP_SET && s >= 0) *map_cell(map, (u32)s) = counters[i]; // index load: the stored value of an imported key
         if (OP == OP_MAP_GET || OP == OP_WEIGHT) ((i32 *)out)[i] = s >= 0 ? (i32)*map_cell(map, (u32)s) : 0;
         return;
     }
@@ -136,6 +135,29 @@ __global__ void __launch_bounds__(TPB) map_insert_kernel(const u8 *rows, size_t 
     irregular[i] = regular ? 0 : 1;
     if (!regular) return;
     map_insert_key(map, bf, key, xxh3_bytes(can, k), row0 + (u32)i, row0);
+}
+
+// mg_map_import's values: the key of row i set to vals[i], the LAST row that names a key deciding, as when the reference reads
+// a file row by row.  PASS 0: last[id] = the largest row + 1 that names the key (`last` zeroed, one entry per counter);
+// PASS 1: that row writes.  irregular[] as map_insert_kernel leaves it.
+template <int PASS>
+__global__ void __launch_bounds__(TPB) map_set_kernel(const u8 *rows, size_t stride, size_t n, MapView map, BFView bf, const u32 *vals,
+                                                      u32 *last, u8 *irregular)
+{
+    const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const u8 *row = rows + i * stride;
+    const int k = row_len(row, (int)stride);
+    CanonBytes<RowIn> can(RowIn{row}, k);
+    U128 key;
+    const bool regular = pack_regular(can, k, (int)map.klen, &key);
+    if (PASS == 0) irregular[i] = regular ? 0 : 1;
+    if (!regular) return;
+    const u64 h = xxh3_bytes(can, k);
+    const long long s = map_find_id(map, key, h, mod_size(h, bf.mod));
+    if (s < 0) return;
+    if (PASS == 0) atomicMax(&last[s], (u32)i + 1u);
+    else if (last[s] == (u32)i + 1u) *map_cell(map, (u32)s) = vals[i];
 }
 
 __global__ void __launch_bounds__(TPB) map_clear_kernel(MapSlot *slots, u64 cap)
