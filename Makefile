@@ -61,14 +61,20 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
 
-# the host side of --cohort-priors (option values, --priors-out) under AddressSanitizer and UBSan: a stand-alone program, run on the CPU
-sanitize-host: bin/cohort_priors_host_check bin/cohort_out_host_check
+# the host side of --cohort-priors (option values, --priors-out), of the cohort's outputs and of the panel batches and their text under
+# AddressSanitizer and UBSan: stand-alone programs, run on the CPU
+sanitize-host: bin/cohort_priors_host_check bin/cohort_out_host_check bin/call_batch_host_check
 	bin/cohort_priors_host_check bin
 	bin/cohort_out_host_check bin
+	bin/call_batch_host_check
 bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
 bin/cohort_out_host_check: tools/cohort_out_host_check.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
+bin/call_batch_host_check: tools/call_batch_host_check.cpp malva_amd/host/panel_batch.hpp malva_amd/host/call_text.hpp malva_amd/host/block.hpp malva_amd/host/io.hpp \
+                           malva_amd/host/bcf_out.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
 

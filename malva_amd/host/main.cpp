@@ -31,6 +31,7 @@
 #include "bcf_out.hpp"
 #include "cohort_priors.hpp"
 #include "cohort_out.hpp"
+#include "call_text.hpp"
 extern "C" {
 #include "malva_hip.h"
 }
@@ -414,27 +415,6 @@ template <class Call> int call_grown(std::vector<char> &buf, Call call)
     }
 }
 
-constexpr size_t STRIDE = 136; // MG_MAX_KMER + NUL, rounded to 8
-
-// fixed-stride ASCII rows for the batch calls
-struct Rows {
-    std::vector<char> data;
-    size_t n = 0;
-    void add(const std::string &kmer)
-    {
-        if (kmer.empty() || kmer.size() > MG_MAX_KMER) throw std::runtime_error("signature k-mer of length " + std::to_string(kmer.size()) + " (1.." +
-                                                                                std::to_string(MG_MAX_KMER) + " supported)");
-        data.resize(data.size() + STRIDE, 0);
-        memcpy(&data[n * STRIDE], kmer.data(), kmer.size());
-        ++n;
-    }
-    void clear()
-    {
-        data.clear();
-        n = 0;
-    }
-};
-
 // main.cpp:407 / :456: <vcf>.c<ref_k>.k<k>.malvax + ".zst" (the reference's container) or ".hipz" (this build's compact one)
 std::string index_path(const Options &o, const char *suffix)
 {
@@ -525,22 +505,6 @@ inline void genotypes_from_entries(Variant &v)
 inline void genotypes_from_entries(Block &b)
 {
     for (Variant &v : b.vars) genotypes_from_entries(v);
-}
-// build_alleles_combs on a chain of one (var_block.hpp:734-786): the (canonical) alleles some kept haplotype carries
-inline uint64_t carried_mask(const Variant &v, bool haploid)
-{
-    uint64_t mask = 0;
-    if (v.gt_deferred) {
-        if (v.max_allele >= (uint32_t)v.n_alleles()) (void)v.alts.at(v.max_allele); // (throws what the loop below would)
-        for (int a = 0; a < v.n_alleles() && a < 64; ++a)
-            if ((v.raw_mask >> a) & 1) mask |= 1ULL << v.allele_index(v.allele(a));
-        return mask;
-    }
-    for (size_t g = 0; g < v.genotypes.size(); ++g) {
-        mask |= 1ULL << v.allele_index(v.allele(v.genotypes[g].first));
-        if (!haploid) mask |= 1ULL << v.allele_index(v.allele(v.genotypes[g].second));
-    }
-    return mask;
 }
 
 // The record loop shared by index_main (main.cpp:309-370) and call_main (:522-579).  on_block(block, reference
@@ -680,112 +644,6 @@ template <class F> size_t for_each_block(VcfReader &vcf, const Options &o, const
         vb.clear();
     }
     return i;
-}
-
-// ---- the panel genotypes of a batch of blocks, as the device takes them ---------------------------------------------------
-// Dense: one [variant][sample] matrix of a1 | a2 << 7 | phased << 14.  Sparse (panels of more than SPARSE_GT_SAMPLES samples:
-// nearly every genotype of such a panel is 0|0): per variant only the samples that carry anything else, in sample order --
-// what crosses PCIe for the 27,934-sample SARS-CoV-2 panel drops from 56 KB per record to a few bytes per carrier.
-constexpr uint32_t SPARSE_GT_SAMPLES = 64;
-struct PanelGenotypes {
-    bool sparse = false;
-    std::vector<uint16_t> gt;                 // dense
-    std::vector<uint32_t> sp_off{0}, sp_sample; // sparse
-    std::vector<uint16_t> sp_gt;
-    uint16_t sp_default = (uint16_t)(1u << 14);
-    size_t bytes() const { return sparse ? 4 * sp_off.size() + 6 * sp_sample.size() : 2 * gt.size(); }
-};
-// one sample's genotype as the device takes it: a1 | a2 << 7 | phased << 14
-inline uint16_t genotype_word(const Variant &v, size_t s_, bool haploid)
-{
-    const auto &p2 = v.genotypes[s_];
-    if (p2.first >= v.n_alleles() || p2.second >= v.n_alleles())
-        throw std::runtime_error("GT allele beyond the kept ALT list at " + v.seq_name + ":" + std::to_string(v.ref_pos + 1) +
-                                 " (the reference reads out of bounds here)");
-    if (haploid) return (uint16_t)(p2.first | (1u << 14));
-    return (uint16_t)(p2.first | (p2.second << 7) | ((v.phasing[s_] ? 1 : 0) << 14));
-}
-inline PanelGenotypes pack_genotypes(const std::vector<const Variant *> &vars, size_t n_vars, uint32_t n_samples, bool haploid)
-{
-    PanelGenotypes g;
-    g.sparse = n_samples > SPARSE_GT_SAMPLES;
-    for (const Variant *vp : vars) g.sparse = g.sparse || vp->gt_deferred; // (records decoded on the device arrive in the sparse form whatever the panel's size)
-    if (!g.sparse) g.gt.assign(n_vars * n_samples, 0);
-    // haploid mode reads the first allele only (var_block.hpp:751): the word is reduced to it, so that a ploidy-1 panel --
-    // whose second "allele" is whatever htslib's layout puts behind the first -- is as sparse as it looks
-    auto word = [&](const Variant &v, size_t s_) -> uint16_t { return genotype_word(v, s_, haploid); };
-    if (g.sparse) { // the default word: 0|0 phased or 0/0 unphased, whichever the batch holds more of (a sample of it decides)
-        size_t phased0 = 0, unphased0 = 0, seen = 0;
-        for (const Variant *vp : vars) {
-            const Variant &v = *vp;
-            if (v.gt_deferred) { // decoded on the device: its batch's default stands for its samples
-                (v.sp_default ? phased0 : unphased0) += 64;
-                seen += 64;
-            } else
-                for (size_t s_ = 0; s_ < v.genotypes.size() && seen < 200000; s_ += 7, ++seen) {
-                    const uint16_t w = word(v, s_);
-                    phased0 += w == (1u << 14);
-                    unphased0 += w == 0;
-                }
-            if (seen >= 200000) break;
-        }
-        g.sp_default = unphased0 > phased0 ? 0 : (uint16_t)(1u << 14);
-    }
-    size_t row = 0;
-    for (const Variant *vp : vars)
-        {
-            const Variant &v = *vp;
-            if (v.gt_deferred) { // already the sparse layout (mg_decode_gt_text), against its own batch's default
-                if (!g.sparse) throw std::runtime_error("internal: deferred genotypes on a panel of few samples");
-                if (v.max_allele >= (uint32_t)v.n_alleles())
-                    throw std::runtime_error("GT allele beyond the kept ALT list at " + v.seq_name + ":" + std::to_string(v.ref_pos + 1) +
-                                             " (the reference reads out of bounds here)");
-                if (v.sp_default == g.sp_default) {
-                    g.sp_sample.insert(g.sp_sample.end(), v.sp_sample.begin(), v.sp_sample.end());
-                    g.sp_gt.insert(g.sp_gt.end(), v.sp_gt.begin(), v.sp_gt.end());
-                } else { // (a panel that mixes phased and unphased records: the samples WITHOUT an entry are the ones that differ here)
-                    size_t e = 0;
-                    for (uint32_t s_ = 0; s_ < v.n_kept; ++s_) {
-                        uint16_t w = v.sp_default;
-                        if (e < v.sp_sample.size() && v.sp_sample[e] == s_) w = v.sp_gt[e++];
-                        if (w != g.sp_default) {
-                            g.sp_sample.push_back(s_);
-                            g.sp_gt.push_back(w);
-                        }
-                    }
-                }
-                g.sp_off.push_back((uint32_t)g.sp_sample.size());
-                ++row;
-                continue;
-            }
-            for (size_t s_ = 0; s_ < v.genotypes.size(); ++s_) {
-                const uint16_t w = word(v, s_);
-                if (!g.sparse) g.gt[row * n_samples + s_] = w;
-                else if (w != g.sp_default) {
-                    g.sp_sample.push_back((uint32_t)s_);
-                    g.sp_gt.push_back(w);
-                }
-            }
-            if (g.sparse) g.sp_off.push_back((uint32_t)g.sp_sample.size());
-            ++row;
-        }
-    return g;
-}
-
-inline PanelGenotypes pack_genotypes(const std::vector<Block> &blocks, size_t n_vars, uint32_t n_samples, bool haploid)
-{
-    std::vector<const Variant *> vars;
-    vars.reserve(n_vars);
-    for (const Block &b : blocks)
-        for (const Variant &v : b.vars) vars.push_back(&v);
-    return pack_genotypes(vars, n_vars, n_samples, haploid);
-}
-inline PanelGenotypes pack_genotypes(const std::vector<Variant> &records, size_t n_vars, uint32_t n_samples, bool haploid)
-{
-    std::vector<const Variant *> vars;
-    vars.reserve(records.size());
-    for (const Variant &v : records) vars.push_back(&v);
-    return pack_genotypes(vars, n_vars, n_samples, haploid);
 }
 
 // ---- index file (index_file.hpp): payload out of / into the contexts ---------------------------------------------------
@@ -961,11 +819,7 @@ int index_main(const Options &o)
     // outside ACGT) are enumerated by all host cores and inserted through the batch calls.
     std::map<std::string, uint64_t> contig_base;
     {
-        std::string all;
-        for (const auto &name : refs.names) {
-            contig_base[name] = all.size();
-            all += refs.seqs.at(name);
-        }
+        const std::string all = concat_reference(refs, contig_base);
         dev.check(mg_reference_upload(dev.ctx, all.data(), all.size()), "mg_reference_upload");
     }
     const bool host_only = o.k > MG_MAX_PACKED_K || getenv("MALVA_GENO_HOST_ENUM"); // the variable forces the host enumerator (tests)
@@ -979,48 +833,29 @@ int index_main(const Options &o)
         n_general_blocks += nb;
         std::vector<uint8_t> redo(nb, host_only ? 1 : 0);
         if (!host_only) {
-            std::vector<uint64_t> blk_base;
-            std::vector<uint32_t> blk_len, blk_var_off{0}, ref_size, min_size, var_allele_off{0}, allele_off{0};
-            std::vector<int32_t> ipos;
-            std::vector<uint8_t> is_present, canon;
-            std::vector<char> pool;
-            bool device_ok = true;
+            BlockArrays ba;
             for (size_t b = 0; b < nb; ++b) {
-                blk_base.push_back(waiting_base[b]);
-                blk_len.push_back((uint32_t)waiting_ref[b]->size());
-                for (const Variant &v : waiting[b].vars) {
-                    const uint32_t A = (uint32_t)v.n_alleles();
-                    if (A > 127) device_ok = false;
-                    ipos.push_back(v.ref_pos);
-                    ref_size.push_back((uint32_t)v.ref_size);
-                    min_size.push_back((uint32_t)v.min_size);
-                    is_present.push_back(v.is_present);
-                    for (uint32_t a = 0; a < A; ++a) {
-                        const std::string &al = v.allele((int)a);
-                        pool.insert(pool.end(), al.begin(), al.end());
-                        allele_off.push_back((uint32_t)pool.size());
-                        canon.push_back((uint8_t)std::min(255, v.allele_index(al)));
-                    }
-                    var_allele_off.push_back(var_allele_off.back() + A);
-                }
-                blk_var_off.push_back((uint32_t)ipos.size());
+                ba.open_block(waiting_base[b], waiting_ref[b]->size());
+                for (const Variant &v : waiting[b].vars) ba.add(v);
+                ba.close_block();
             }
-            const size_t nv = ipos.size();
+            const bool device_ok = !ba.wide_alleles;
+            const size_t nv = ba.ipos.size();
             const uint32_t n_samples = (uint32_t)vcf.keep.size();
             const PanelGenotypes pg = pack_genotypes(waiting, nv, n_samples, o.haploid);
             std::vector<uint8_t> overflow(nv, 1);
             if (device_ok && pg.sparse)
-                dev.check(mg_index_blocks_sparse(dev.ctx, nb, blk_base.data(), blk_len.data(), blk_var_off.data(), nv, ipos.data(), ref_size.data(), min_size.data(),
-                                                 is_present.data(), var_allele_off.data(), allele_off.data(), pool.data(), pool.size(), canon.data(), pg.sp_off.data(),
+                dev.check(mg_index_blocks_sparse(dev.ctx, nb, ba.blk_base.data(), ba.blk_len.data(), ba.blk_var_off.data(), nv, ba.ipos.data(), ba.ref_size.data(), ba.min_size.data(),
+                                                 ba.is_present.data(), ba.var_allele_off.data(), ba.allele_off.data(), ba.pool.data(), ba.pool.size(), ba.canon.data(), pg.sp_off.data(),
                                                  pg.sp_sample.data(), pg.sp_gt.data(), pg.sp_default, n_samples, o.haploid, overflow.data()),
                           "mg_index_blocks_sparse");
             else if (device_ok)
-                dev.check(mg_index_blocks(dev.ctx, nb, blk_base.data(), blk_len.data(), blk_var_off.data(), nv, ipos.data(), ref_size.data(), min_size.data(),
-                                          is_present.data(), var_allele_off.data(), allele_off.data(), pool.data(), pool.size(), canon.data(), pg.gt.data(),
+                dev.check(mg_index_blocks(dev.ctx, nb, ba.blk_base.data(), ba.blk_len.data(), ba.blk_var_off.data(), nv, ba.ipos.data(), ba.ref_size.data(), ba.min_size.data(),
+                                          ba.is_present.data(), ba.var_allele_off.data(), ba.allele_off.data(), ba.pool.data(), ba.pool.size(), ba.canon.data(), pg.gt.data(),
                                           n_samples, o.haploid, overflow.data()),
                           "mg_index_blocks");
             for (size_t b = 0; b < nb; ++b)
-                for (uint32_t v = blk_var_off[b]; v < blk_var_off[b + 1]; ++v) redo[b] = redo[b] || overflow[v];
+                for (uint32_t v = ba.blk_var_off[b]; v < ba.blk_var_off[b + 1]; ++v) redo[b] = redo[b] || overflow[v];
         }
         std::vector<size_t> todo;
         for (size_t b = 0; b < nb; ++b)
@@ -1066,15 +901,10 @@ int index_main(const Options &o)
     // DEVICE too, a batch at a time (mg_index_isolated: signature assembly from the uploaded reference, exact-map insert /
     // filter bit); the host keeps the few the device hands back (a base outside ACGT in the window) and those whose
     // right flank a contig end clips (the reference then makes a shorter k-mer, var_block.hpp:187).
-    struct LoneBatch {
-        std::vector<uint64_t> pos, present;
-        std::vector<uint32_t> var_allele_off{0}, allele_off{0};
-        std::vector<char> pool;
-        std::vector<uint8_t> flags;
+    struct LoneBatch : LoneArrays {
         std::vector<Block> blocks; // kept for the variants handed back
         std::vector<const std::string *> refs;
         size_t cells = 0;
-        size_t n() const { return pos.size(); }
     } lone;
     size_t n_lone_device = 0, n_lone_host = 0;
     auto index_lone = [&]() {
@@ -1098,25 +928,14 @@ int index_main(const Options &o)
     const size_t n = for_each_block(vcf, o, refs, true, &used, [&](Block &vb, const std::string &seq_name, const std::string &reference) {
         if (vb.is_lone_short()) {
             const Variant &v = vb.vars[0];
-            const bool on_device = !host_only && contig_base.count(seq_name) && v.n_alleles() <= 64 &&
-                                   (long)v.ref_pos + v.ref_size + (long)(o.k + 1) / 2 <= (long)reference.size();
+            const bool on_device = !host_only && contig_base.count(seq_name) && v.n_alleles() <= 64 && right_flank_fits(v, o.k, reference.size());
             if (!on_device) { // one k-mer per carried allele, no containers
                 genotypes_from_entries(vb);
                 vb.extract_lone(reference, o.haploid, [&](int a, const std::string &kmer) { (a == 0 ? ref_rows : alt_rows).add(kmer); });
                 flush(false);
                 return;
             }
-            const bool eligible = v.is_present && v.ref_pos >= (int)o.k && v.ref_pos <= (int)reference.size() - (int)o.k; // var_block.hpp:104
-            const uint64_t mask = eligible ? carried_mask(v, o.haploid) : 0;
-            lone.pos.push_back(contig_base.at(seq_name) + (uint64_t)std::max(v.ref_pos, 0));
-            lone.present.push_back(mask);
-            lone.flags.push_back(eligible ? 1 : 0);
-            for (uint32_t a = 0; a < (uint32_t)v.n_alleles(); ++a) {
-                const std::string &al = v.allele((int)a);
-                lone.pool.insert(lone.pool.end(), al.begin(), al.end());
-                lone.allele_off.push_back((uint32_t)lone.pool.size());
-            }
-            lone.var_allele_off.push_back(lone.var_allele_off.back() + (uint32_t)v.n_alleles());
+            lone.add(v, contig_base.at(seq_name), o.k, reference.size(), o.haploid);
             lone.cells += v.n_genotypes();
             lone.refs.push_back(&reference);
             lone.blocks.push_back(std::move(vb));
@@ -1458,70 +1277,6 @@ void count_reads(std::vector<Device> &devs, const Options &o, const std::vector<
               << o.max_count << ", " << cn[3] << " pass(es))" << (devs.size() > 1 ? " on " + std::to_string(devs.size()) + " devices" : std::string()) << std::endl;
 }
 
-// one output record waiting for its device results
-struct Rec {
-    std::string prefix; // CHROM .. QUAL columns
-    uint32_t n_alleles;
-    bool isolated;
-    size_t slot;     // variant index inside its batch
-    size_t allele0;  // first allele slot inside its batch
-    size_t gt0;      // first genotype slot inside its batch
-};
-struct Batch { // inputs of mg_call_isolated (isolated) or mg_lookup_cover + mg_genotype (general)
-    std::vector<uint64_t> pos, present;
-    std::vector<uint32_t> var_allele_off{0}, allele_off{0};
-    std::vector<uint8_t> allele_class; // --sample-stats: one byte per allele slot (allele_class_of; slot 0 of a record: 0), else empty
-    std::vector<char> pool;
-    std::vector<float> freq;
-    std::vector<uint8_t> flags;
-    Rows rows;
-    std::vector<uint8_t> is_ref;
-    std::vector<uint64_t> sig_kmer_off{0}, allele_sig_off{0}, var_gt_off{0};
-    // general blocks, enumerated on the device (mg_cover_blocks); the records are kept until the batch has run, for the
-    // panel genotypes and for the blocks the device hands back (a Block is rebuilt for those alone: one vector per block
-    // kept alive cost a malloc per lone record once every block came this way)
-    std::vector<Variant> vars;
-    std::vector<int32_t> var_slot;  // record -> its place in `vars`, or -1: a lone record the device cannot hand back, not kept
-    std::vector<uint16_t> gt_dense; // a panel of few samples: the genotype words, made as the records are batched (else packed from `vars` by the worker)
-    bool dense_gt = false, wide_alleles = false;
-    std::vector<const std::string *> block_ref;
-    std::vector<uint64_t> blk_base;
-    std::vector<uint32_t> blk_len, blk_var_off{0}, ref_size, min_size;
-    std::vector<int32_t> ipos;
-    std::vector<uint8_t> is_present, canon;
-    size_t genotype_cells = 0;
-    // results
-    std::vector<uint32_t> cov;
-    std::vector<int32_t> g1, g2, gq;
-    std::vector<uint8_t> status;
-    std::vector<double> probs;
-    std::vector<float> freq_out;   // --cohort-priors: the re-estimated frequencies, as freq
-    std::vector<uint32_t> n_inf;   // --cohort-priors: per record, the planes that counted
-    size_t n() const { return var_allele_off.size() - 1; }
-};
-
-// --sample-stats: the kind of the ALT allele `alt` of a record whose REF is `ref`, from the strings as the record prints them (the class
-// codes of mg_sample_counts: 1 transition, 2 transversion, 3 insertion, 4 deletion, 5 other)
-uint8_t allele_class_of(const std::string &ref, const std::string &alt)
-{
-    if (alt == "*" || (!alt.empty() && alt[0] == '<')) return 5;
-    auto base = [](char c) -> int {
-        switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': return 3;
-        default: return -1;
-        }
-    };
-    for (char c : alt)
-        if (base(c) < 0) return 5;
-    if (ref.size() == 1 && alt.size() == 1) return base(ref[0]) >= 0 && (base(ref[0]) ^ base(alt[0])) == 2 ? 1 : 2; // (A <-> G: 0 ^ 2, C <-> T: 1 ^ 3)
-    if (alt.size() > ref.size()) return 3;
-    if (alt.size() < ref.size()) return 4;
-    return 5;
-}
-
 int call_main(const Options &o)
 {
     // Start-up runs three things side by side: the FASTA (host), the index file (host) and the devices (HIP start-up is
@@ -1608,11 +1363,7 @@ int call_main(const Options &o)
     // concatenated reference for the fused isolated path
     std::map<std::string, uint64_t> contig_base;
     {
-        std::string all;
-        for (const auto &name : refs.names) {
-            contig_base[name] = all.size();
-            all += refs.seqs.at(name);
-        }
+        const std::string all = concat_reference(refs, contig_base);
         Timed t("startup: reference upload");
         on_all_devices(devs, [&](Device &d, size_t) { d.check(mg_reference_upload(d.ctx, all.data(), all.size()), "mg_reference_upload"); });
     }
@@ -1707,16 +1458,6 @@ int call_main(const Options &o)
     uint64_t *const sample_table = to.sample_table;
     const size_t P = planes ? planes : 1;
 
-    // records per device round trip; MALVA_GENO_BATCH exists so tests can force many small batches
-    const size_t batch_records = getenv("MALVA_GENO_BATCH") ? (size_t)std::max(1L, atol(getenv("MALVA_GENO_BATCH"))) : 200000;
-    std::vector<Rec> recs;
-    Batch iso, gen;
-    // few samples and every record's genotypes decoded on the host: the words are made while batching
-    const size_t n_samples_kept = vcf.keep.size();
-    const bool dense_gt = n_samples_kept <= SPARSE_GT_SAMPLES && !vcf.defer_genotypes;
-    gen.dense_gt = dense_gt;
-    const std::string best_default = o.haploid ? "0" : "0/0";
-    auto n_gt = [&](uint64_t A) { return o.haploid ? A : A * (A + 1) / 2; };
     const bool want_probs = o.verbose || o.gp; // the likelihood lists: GTS= of -v, GP of --merged --gp
 
     // One batch: device round trips, then the records' text.  Runs on a worker thread while this thread parses the
@@ -1770,7 +1511,7 @@ int call_main(const Options &o)
             std::vector<uint8_t> overflow(n, 0);
             bool device_ok = o.k <= MG_MAX_PACKED_K && !getenv("MALVA_GENO_HOST_ENUM"); // the variable forces the host enumerator (tests)
             if (gen.wide_alleles) device_ok = false;
-            const size_t n_blocks = gen.blk_var_off.size() - 1;
+            const size_t n_blocks = gen.n_blocks();
             PanelGenotypes pg;
             if (gen.dense_gt) pg.gt = std::move(gen.gt_dense);
             else pg = pack_genotypes(gen.vars, n, n_samples, o.haploid); // (every record of such a batch is kept)
@@ -1811,28 +1552,12 @@ int call_main(const Options &o)
                     blk.add(std::move(gen.vars[(size_t)gen.var_slot[v]]));
                 }
                 genotypes_from_entries(blk);
-                const auto sigs = blk.extract(*gen.block_ref[b], o.haploid);
-                Rows rows;
-                std::vector<uint8_t> is_ref;
-                std::vector<uint64_t> sig_off{0}, al_off{0};
-                for (size_t vi = 0; vi < blk.vars.size(); ++vi)
-                    for (int a = 0; a < blk.vars[vi].n_alleles(); ++a) {
-                        auto it = sigs[vi].find(a);
-                        if (it != sigs[vi].end())
-                            for (const auto &sig : it->second) {
-                                for (const auto &kmer : sig) {
-                                    rows.add(kmer);
-                                    is_ref.push_back(a == 0);
-                                }
-                                sig_off.push_back(rows.n);
-                            }
-                        al_off.push_back(sig_off.size() - 1);
-                    }
+                const SignatureRows s = signature_rows(blk, blk.extract(*gen.block_ref[b], o.haploid));
                 const size_t slot0 = gen.var_allele_off[gen.blk_var_off[b]];
                 for (size_t pl = 0; pl < P; ++pl) { // (enumerated once; the lookups read the selected plane)
                     if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
-                    dev.check(mg_lookup_cover(dev.ctx, rows.data.data(), STRIDE, rows.n, is_ref.data(), sig_off.data(), sig_off.size() - 1, al_off.data(),
-                                              al_off.size() - 1, gen.cov.data() + pl * na + slot0),
+                    dev.check(mg_lookup_cover(dev.ctx, s.rows.data.data(), STRIDE, s.rows.n, s.is_ref.data(), s.sig_off.data(), s.sig_off.size() - 1, s.al_off.data(),
+                                              s.al_off.size() - 1, gen.cov.data() + pl * na + slot0),
                               "mg_lookup_cover");
                 }
             }
@@ -1945,93 +1670,10 @@ int call_main(const Options &o)
             if (priors_file.f) priors_row(text.priors, r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
             if (tags && cnt_out) put_site_counts(text.site_counts, r.n_alleles, site_ns[w][r.slot], site_ac[w].data() + r.allele0);
         }
-        if (merged_out && bcf_out) {
-            // BCF: one group -- whole records (l_shared, l_indiv, the shared block with INFO from the counts, the device's row), compressed
-            // here when BGZF; several -- per record the first group's shared block without INFO and every group's row, each behind its
-            // u32 length, for the paste pass to widen and join (the counts go to cnt_out as for text)
-            std::string &out = text.merged;
-            std::string plain;
-            std::string &rec_out = bcf_direct && bcf_bgzf ? plain : out;
-            const uint32_t n_fmt = (o.verbose ? 3 : 2) + (o.gp ? 1 : 0);
-            for (const Rec &r : recs) {
-                const int w = r.isolated ? 0 : 1;
-                const char *row = row_text[w].data() + row_off[w][r.slot];
-                const uint32_t l_indiv = (uint32_t)(row_off[w][r.slot + 1] - row_off[w][r.slot]);
-                if (merged_fixed) {
-                    const size_t at = rec_out.size();
-                    rec_out.append(bcf_direct ? 8 : 4, '\0');
-                    bcf_put_shared(rec_out, bcf_hdr, r.prefix, n_fmt, (uint32_t)(bcf_direct ? P : 0));
-                    if (bcf_direct && tags) bcf_put_info(rec_out, at + 8, bcf_hdr, site_ac[w].data() + r.allele0, r.n_alleles, site_ns[w][r.slot]);
-                    const uint32_t l_shared = (uint32_t)(rec_out.size() - at - (bcf_direct ? 8 : 4));
-                    memcpy(&rec_out[at], &l_shared, 4);
-                    if (bcf_direct) memcpy(&rec_out[at + 4], &l_indiv, 4);
-                }
-                if (!bcf_direct) bcf_put_u32(rec_out, l_indiv);
-                rec_out.append(row, l_indiv);
-            }
-            if (bcf_direct && bcf_bgzf) bgzf_append(plain.data(), plain.size(), out);
-        } else if (merged_out) {
-            std::string &out = text.merged;
-            const char *fixed = o.verbose ? (o.gp ? "\tPASS\t.\tGT:GQ:COVS:GP" : "\tPASS\t.\tGT:GQ:COVS") : o.gp ? "\tPASS\t.\tGT:GQ:GP" : "\tPASS\t.\tGT:GQ";
-            const bool info_here = tags && !cnt_out; // (else INFO stays '.' in the block: the paste pass puts it in)
-            for (const Rec &r : recs) {
-                const int w = r.isolated ? 0 : 1;
-                if (merged_fixed && info_here) {
-                    out += r.prefix;
-                    out += "\tPASS\t";
-                    out.append(info_text[w].data() + info_off[w][r.slot], info_text[w].data() + info_off[w][r.slot + 1]);
-                    out += fixed + 7; // (behind "\tPASS\t.")
-                } else if (merged_fixed) {
-                    out += r.prefix;
-                    out += fixed;
-                }
-                out.append(row_text[w].data() + row_off[w][r.slot], row_text[w].data() + row_off[w][r.slot + 1]);
-            }
-        }
-        char num[64];
-        if (!outs.empty())
-        for (const Rec &r : recs) // output_variants, var_block.hpp:337-396
-          for (size_t pl = 0; pl < P; ++pl) {
-            const Batch &b = r.isolated ? iso : gen;
-            std::string &out = text.per_sample[pl];
-            const size_t bn = b.n(), bna = b.var_allele_off.back(), bng = b.probs.size() / P;
-            out += r.prefix;
-            out += "\tPASS\t";
-            const uint32_t *cov = &b.cov[pl * bna + r.allele0];
-            const uint8_t st = b.status[pl * bn + r.slot];
-            auto gname = [&](int a, int c) { return o.haploid ? std::to_string(a) : std::to_string(a) + "/" + std::to_string(c); };
-            if (o.verbose) {
-                out += "COVS=";
-                for (uint32_t a = 0; a < r.n_alleles; ++a) {
-                    out += std::to_string((int)cov[a]);
-                    out += a + 1 < r.n_alleles ? "," : "";
-                }
-                out += ";GTS=";
-                if (st == MG_GT_NORMAL) {
-                    size_t q = pl * bng + r.gt0;
-                    bool first = true;
-                    for (uint32_t a = 0; a < r.n_alleles; ++a)
-                        for (uint32_t c = a; c < (o.haploid ? a + 1 : r.n_alleles); ++c, ++q) {
-                            if (std::isnan(b.probs[q])) snprintf(num, sizeof num, "-nan"); // 0.0/0.0 on x86, as the reference prints it
-                            else snprintf(num, sizeof num, "%f", b.probs[q]);               // std::to_string(double)
-                            out += (first ? "" : ",") + gname((int)a, (int)c) + ":" + num;
-                            first = false;
-                        }
-                } else {
-                    // early-outs: one (best_geno, 0) per over-covered allele, or a single entry; 0/0 prints -nan
-                    size_t entries = 1;
-                    if (st == MG_GT_OVERCOV) {
-                        entries = 0;
-                        for (uint32_t a = 0; a < r.n_alleles; ++a) entries += (int)cov[a] > (int)o.max_coverage;
-                    }
-                    for (size_t e = 0; e < entries; ++e) out += (e ? "," : "") + best_default + (st == MG_GT_SINGLE ? ":1.000000" : ":-nan");
-                }
-            } else
-                out += ".";
-            out += "\tGT:GQ\t";
-            out += gname(b.g1[pl * bn + r.slot], b.g2[pl * bn + r.slot]); // early-outs and "nothing beats 0.0" come back as 0 / 0/0
-            out += ":" + std::to_string(b.gq[pl * bn + r.slot]) + "\n";
-          }
+        if (merged_out && bcf_out)
+            merged_bcf_records(text.merged, recs, row_text, row_off, site_ac, site_ns, bcf_hdr, (o.verbose ? 3 : 2) + (o.gp ? 1 : 0), (uint32_t)P, merged_fixed, bcf_direct, tags, bcf_bgzf);
+        else if (merged_out) merged_text_lines(text.merged, recs, row_text, row_off, info_text, info_off, o.verbose, o.gp, merged_fixed, tags && !cnt_out); // (INFO stays '.' in a block: the paste pass puts it in)
+        if (!outs.empty()) per_sample_lines(text.per_sample, recs, iso, gen, P, o.haploid, o.verbose, o.max_coverage);
         return text;
     };
     // as many batches in flight as there are devices; their text leaves in submission order
@@ -2049,128 +1691,18 @@ int call_main(const Options &o)
             priors_file.write(text.priors);
         }
     };
-    auto reserve_general = [&](Batch &b) { // (a batch's vectors at their final size at once: fifteen of them grew by doubling, record by record)
-        const size_t n = batch_records + 64;
-        for (auto *v32 : {&b.blk_len, &b.blk_var_off, &b.ref_size, &b.min_size, &b.var_allele_off}) v32->reserve(n + 1);
-        b.allele_off.reserve(2 * n + 1);
-        b.blk_base.reserve(n); b.ipos.reserve(n); b.is_present.reserve(n); b.canon.reserve(2 * n); b.freq.reserve(2 * n); b.pool.reserve(4 * n);
-        b.var_gt_off.reserve(n + 1); b.var_slot.reserve(n); b.block_ref.reserve(n);
-        if (b.dense_gt) b.gt_dense.reserve(n * n_samples_kept);
-    };
-    reserve_general(gen);
-    auto run_and_print = [&]() {
+    auto run_and_print = [&](std::vector<Rec> &&recs, Batch &&iso, Batch &&gen) {
         drain(devs.size() - 1);
-        auto job = std::make_shared<Job>();
-        job->recs = std::move(recs);
-        job->iso = std::move(iso);
-        job->gen = std::move(gen);
-        job->device = jobs_started++ % devs.size();
-        recs.clear();
-        iso = Batch();
-        gen = Batch();
-        gen.dense_gt = dense_gt;
-        reserve_general(gen);
-        recs.reserve(batch_records + 64);
+        auto job = std::make_shared<Job>(Job{std::move(recs), std::move(iso), std::move(gen), jobs_started++ % devs.size()});
         in_flight.push_back(std::async(std::launch::async, [&process, job]() { return process(*job); }));
     };
-
-    auto prefix_of = [&](Variant &v) { return std::move(v.text_prefix); }; // (made by the thread that decoded the record)
-
     const bool iso_path = getenv("MALVA_GENO_ISO_PATH") && atoi(getenv("MALVA_GENO_ISO_PATH")) != 0;
-    const bool host_enum = getenv("MALVA_GENO_HOST_ENUM") != nullptr; // (every block goes to the host enumerator: every record is kept for it)
-    std::string base_name;
-    bool base_known = false, base_found = false;
-    uint64_t base_value = 0;
-    const size_t n = for_each_block(vcf, o, refs, false, nullptr, [&](Block &vb, const std::string &seq_name, const std::string &reference) {
-        // The fused kernel reads ceil(k/2) bases to the right of the REF allele.  A lone variant whose right flank
-        // would cross the contig end (a deletion longer than about k/2 within k of it) gets a CLIPPED, shorter
-        // k-mer in the reference (std::string(reference, pos, n), var_block.hpp:187) and in extract_lone at index
-        // time: such a variant takes the general path, whose device enumerator hands clipped windows to the host.
-        if (!base_known || seq_name != base_name) { // (as ref_of: one map lookup per sequence, not per record)
-            auto cb = contig_base.find(seq_name);
-            base_found = cb != contig_base.end();
-            base_value = base_found ? cb->second : 0;
-            base_name = seq_name;
-            base_known = true;
-        }
-        // Every block takes the resident record loop (mg_cover_blocks: the panel batch goes up once, then tier 1 for the lone
-        // records -- classification and the panel's genotypes gathered on the device --, tiers 2 and 3 for the others: the
-        // kernels bench.py times).  MALVA_GENO_ISO_PATH=1 keeps the older split, where a lone record goes through the fused
-        // mg_call_isolated with a presence mask made here (tests run both: same bytes).
-        // (k beyond the packed forms: exact-map keys live in the context's host-side list, which only the ASCII batch lookups reach)
-        const bool lone = iso_path && o.k <= MG_MAX_PACKED_K && vb.is_lone_short() && base_found &&
-                          (long)vb.vars[0].ref_pos + vb.vars[0].ref_size + (long)(o.k + 1) / 2 <= (long)reference.size();
-        if (lone) {
-            Variant &v = vb.vars[0];
-            const uint32_t A = (uint32_t)v.n_alleles();
-            recs.push_back({prefix_of(v), A, true, iso.n(), iso.var_allele_off.back(), iso.var_gt_off.back()});
-            const bool eligible = v.is_present && v.ref_pos >= (int)o.k && v.ref_pos <= (int)reference.size() - (int)o.k; // var_block.hpp:104
-            const uint64_t mask = eligible ? carried_mask(v, o.haploid) : 0;
-            iso.pos.push_back(base_value + (uint64_t)std::max(v.ref_pos, 0));
-            iso.present.push_back(mask);
-            iso.flags.push_back(eligible ? 1 : 0);
-            for (uint32_t a = 0; a < A; ++a) {
-                const std::string &al = v.allele((int)a);
-                iso.pool.insert(iso.pool.end(), al.begin(), al.end());
-                iso.allele_off.push_back((uint32_t)iso.pool.size());
-                iso.freq.push_back(v.frequencies[a]);
-                if (want_sample) iso.allele_class.push_back(a ? allele_class_of(v.ref_sub, al) : (uint8_t)0);
-            }
-            iso.var_allele_off.push_back(iso.var_allele_off.back() + A);
-            iso.var_gt_off.push_back(iso.var_gt_off.back() + n_gt(A));
-        } else {
-            // main.cpp:556-557: extract_kmers + set_coverages happen on the device for the whole batch of blocks
-            // A record of more than 127 alleles sends its whole batch to the host enumerator (gen.wide_alleles), which needs every record
-            // kept: its block is a batch of its own.  The records in front of it, the lone ones a small panel has let go of among them,
-            // leave first, and the batch is closed again behind the block, so that no other block follows it to the host.
-            bool wide = false;
-            for (const Variant &v : vb.vars) wide = wide || v.n_alleles() > 127;
-            if (wide && !recs.empty()) run_and_print();
-            if (wide) gen.wide_alleles = true;
-            gen.blk_base.push_back(base_value);
-            gen.blk_len.push_back((uint32_t)reference.size());
-            // a record tier 1 is sure to take (the device's own test, block_pipeline.h: classify_lone) can never be handed back:
-            // with its genotype words made here, nothing of it needs keeping
-            const bool sure_lone = gen.dense_gt && !gen.wide_alleles && !host_enum && o.k <= MG_MAX_PACKED_K && vb.is_lone_short() && base_found && vb.vars[0].ref_pos >= (int)o.k / 2 &&
-                                   (long)vb.vars[0].ref_pos + vb.vars[0].ref_size + (long)(o.k + 1) / 2 <= (long)reference.size();
-            for (Variant &v : vb.vars) {
-                const uint32_t A = (uint32_t)v.n_alleles();
-                if (A > 127) gen.wide_alleles = true;
-                recs.push_back({prefix_of(v), A, false, gen.n(), gen.var_allele_off.back(), gen.var_gt_off.back()});
-                gen.ipos.push_back(v.ref_pos);
-                gen.ref_size.push_back((uint32_t)v.ref_size);
-                gen.min_size.push_back((uint32_t)v.min_size);
-                gen.is_present.push_back(v.is_present);
-                for (uint32_t a = 0; a < A; ++a) {
-                    const std::string &al = v.allele((int)a);
-                    gen.pool.insert(gen.pool.end(), al.begin(), al.end());
-                    gen.allele_off.push_back((uint32_t)gen.pool.size());
-                    gen.canon.push_back((uint8_t)std::min(255, v.allele_index(al)));
-                    gen.freq.push_back(v.frequencies[a]);
-                    if (want_sample) gen.allele_class.push_back(a ? allele_class_of(v.ref_sub, al) : (uint8_t)0);
-                }
-                gen.var_allele_off.push_back(gen.var_allele_off.back() + A);
-                gen.var_gt_off.push_back(gen.var_gt_off.back() + n_gt(A));
-                gen.genotype_cells += v.n_genotypes();
-                if (gen.dense_gt) { // one row of n_samples words per record (a record whose genotypes were not read -- it carries nothing -- keeps a row of zeros)
-                    const size_t have = std::min(v.genotypes.size(), n_samples_kept);
-                    for (size_t s_ = 0; s_ < have; ++s_) gen.gt_dense.push_back(genotype_word(v, s_, o.haploid));
-                    gen.gt_dense.resize(gen.gt_dense.size() + (n_samples_kept - have), 0);
-                }
-                if (sure_lone) gen.var_slot.push_back(-1);
-                else {
-                    gen.var_slot.push_back((int32_t)gen.vars.size());
-                    gen.vars.push_back(std::move(v)); // (the caller clears the block: its vector is used again)
-                }
-            }
-            gen.blk_var_off.push_back((uint32_t)gen.n());
-            gen.block_ref.push_back(&reference);
-            if (wide) run_and_print();
-        }
-        if (gen.genotype_cells >= (200u << 20)) run_and_print(); // bound the panel genotypes held in memory
-        if (recs.size() >= batch_records) run_and_print();
-    }, &devs[0]);
-    run_and_print();
+    const BatchRules rules{o.k, o.haploid, vcf.keep.size() <= SPARSE_GT_SAMPLES && !vcf.defer_genotypes, vcf.keep.size(), iso_path, getenv("MALVA_GENO_HOST_ENUM") != nullptr,
+                           want_sample, geno_batch_records(200000)};
+    BatchBuilder<decltype(run_and_print)> batches(rules, contig_base, run_and_print); // (which records a batch keeps, when it closes: host/panel_batch.hpp)
+    const size_t n = for_each_block(vcf, o, refs, false, nullptr,
+                                    [&](Block &vb, const std::string &seq_name, const std::string &reference) { batches.add_block(vb, seq_name, reference); }, &devs[0]);
+    batches.flush();
     drain(0);
     for (PartFile &f : outs) fflush(f.f);
     if (merged_out) fflush(merged_out->f);
@@ -2317,7 +1849,7 @@ int call_main(const Options &o)
                 paste_bcf_groups(in.f, group_planes, (o.verbose ? 3 : 2) + (o.gp ? 1 : 0), (uint32_t)bcf_samples, bcf_hdr, o.site_tags ? &counts : nullptr, bcf_bgzf, sink);
             } else {
                 // --site-tags: the groups' counts summed, 65,536 records at a time (MALVA_GENO_BATCH, when set: tests), and their INFO strings made on the device
-                const size_t paste_batch = getenv("MALVA_GENO_BATCH") ? (size_t)std::max(1L, atol(getenv("MALVA_GENO_BATCH"))) : 65536;
+                const size_t paste_batch = geno_batch_records(65536);
                 std::vector<uint32_t> p_ac, p_ns, p_vao;
                 paste_text_groups(in.f, o.site_tags, [&](std::vector<char> &text, std::vector<uint64_t> &off) {
                     counts.next_batch(paste_batch, p_ac, p_ns, p_vao);
