@@ -61,13 +61,17 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
 
-# the host side of --cohort-priors (option values, --priors-out), of the cohort's outputs and of the panel batches and their text under
+# the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs and of the panel batches and their text under
 # AddressSanitizer and UBSan: stand-alone programs, run on the CPU
-sanitize-host: bin/cohort_priors_host_check bin/cohort_out_host_check bin/call_batch_host_check
+sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/call_batch_host_check
 	bin/cohort_priors_host_check bin
+	bin/cohort_priors_groups_host_check bin
 	bin/cohort_out_host_check bin
 	bin/call_batch_host_check
-bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp
+bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
+bin/cohort_priors_groups_host_check: tools/cohort_priors_groups_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
 bin/cohort_out_host_check: tools/cohort_out_host_check.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h

@@ -700,6 +700,39 @@ int mg_genotype_cohort_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, con
                               void *d_gt1, void *d_gt2, void *d_gq, void *d_status, void *d_probs, const void *d_var_gt_off);
 int mg_cohort_prior_stats(mg_ctx *ctx, float *ms_out);
 
+/* mg_estimate_priors: the estimate of mg_genotype_cohort alone, for 1..MG_PRIOR_WIDE_MAX_PLANES planes; it makes no calls.
+ * Everything in the definition above stays as it is -- which records are re-estimated, status, posteriors, the expected copies
+ * per plane, the update with its separately rounded operations, the REF rule, n == 0, the early stop, n_informative = n of the
+ * last iteration that ran.  Only the sum over planes is extended:
+ *   Planes are taken in the order given and cut into chunks of 64: chunk j holds planes 64j .. min(64j + 64, P) - 1.
+ *   C_j[a] is the fixed tree above over the chunk's planes, padded with +0.0 to the smallest power of two >= the chunk's plane
+ *   count.  c[a] = C_0[a], then c[a] = c[a] + C_j[a] for j = 1, 2, .. in order, each add rounded on its own.  n is the integer
+ *   count of the planes that count over all chunks.
+ * For P <= 64 this is mg_genotype_cohort's sum, bit for bit.  Every e_p[a] is >= +0.0 and x + (+0.0) = x for such x, so padding
+ * a short chunk to 64 lanes gives the same C_j as padding it to its own power of two: the kernel runs every chunk at segment
+ * width 64 when P > 64.  The order is fixed so that the result is reproducible and does not depend on how a caller groups its
+ * planes; chunks are cut on the plane index alone.
+ * Outputs: freq_out[slots] = f_T; n_informative[n_vars].  A record that is not re-estimated (A < 2, A > MG_PRIOR_MAX_ALLELES,
+ * T = 0) gets freq_out = f0 and n_informative = 0.  Nothing outside freq_out[0 .. slots) and n_informative[0 .. n_vars) is
+ * written.  The cells are genotyped afterwards, per group of <= 64 planes, by mg_genotype_cohort(iters = 0, freq = f_T), which
+ * genotypes each cell exactly as mg_genotype does from (cov_p, f_T) -- what mg_genotype_cohort(iters = T)'s last step does.  One
+ * limit: with iters = 0 the host form of mg_genotype_cohort recomputes the cells of a record at or above a total coverage of
+ * 65536 with libm, where mg_genotype_cohort(iters = T) keeps the device's log(double) for a re-estimated record; the two-step
+ * result equals the one-step result bit for bit for totals < 65536 (leaving that range takes a max_cov of 8192 or more).
+ * Numerics are mg_genotype_cohort's: no FMA contraction, its logf and exp, the host-made ln(n) table; with every record's total
+ * coverage below 65536 the result is bit-identical to a CPU restatement, beyond that it uses the device's log(double).
+ * MG_PRIOR_WIDE_MAX_PLANES is a design choice (256 chunks), not a limit of the method.
+ * n_vars == 0 is legal.  iters > 64, a negative or non-finite weight, n_planes 0 or above MG_PRIOR_WIDE_MAX_PLANES, a NULL
+ * required array with n_vars > 0: MG_ERR_ARG, nothing written.  The host form synchronises; the device form (every array a
+ * device pointer) is asynchronous on the context's stream.  mg_estimate_priors_stats (waits): ms_out[1], device milliseconds of
+ * the most recent mg_estimate_priors* (an event pair of its own); MG_ERR_STATE before the first. */
+#define MG_PRIOR_WIDE_MAX_PLANES 16384
+int mg_estimate_priors(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, const uint32_t *cov, const float *freq, const uint32_t *var_allele_off,
+                       float error_rate, int max_cov, int haploid, uint32_t iters, double weight, float *freq_out, uint32_t *n_informative);
+int mg_estimate_priors_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, const void *d_cov, const void *d_freq, const void *d_var_allele_off,
+                              float error_rate, int max_cov, int haploid, uint32_t iters, double weight, void *d_freq_out, void *d_n_informative);
+int mg_estimate_priors_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- the sample columns of a multi-sample BCF --------------------------------------
  * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
  * parity with htslib unpinned).  Arrays, n_planes (1..64), the host and _device forms, the stream behaviour and the buffer

@@ -134,6 +134,9 @@ def lib():
         "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_cohort_prior_stats": [vp, vp],
+        "mg_estimate_priors": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp],
+        "mg_estimate_priors_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp],
+        "mg_estimate_priors_stats": [vp, vp],
         "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
@@ -204,7 +207,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
-            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -874,6 +877,31 @@ class Context:
         """-> device ms of the most recent genotype_cohort"""
         ms = (C.c_float * 1)()
         self._ck(self._L.mg_cohort_prior_stats(self.h, ms))
+        return float(ms[0])
+
+    # the estimate alone, for any number of planes
+    def estimate_priors(self, cov, freq, var_allele_off, error_rate, max_cov, haploid, iters=5, weight=1.0):
+        """cov: [planes, slots] uint32 (1..MG_PRIOR_WIDE_MAX_PLANES planes); freq: [slots] float32 -> (freq_out [slots] float32,
+        n_informative [n_vars] uint32): the definition is mg_estimate_priors' in include/malva_hip.h"""
+        cov = np.ascontiguousarray(cov, dtype=np.uint32)
+        freq = np.ascontiguousarray(freq, dtype=np.float32)
+        vo = np.ascontiguousarray(var_allele_off, dtype=np.uint32)
+        planes, n = cov.shape[0], len(vo) - 1
+        assert cov.shape == (planes, int(vo[n])) and freq.shape == (int(vo[n]),)
+        fo, ni = np.zeros(len(freq), dtype=np.float32), np.zeros(n, dtype=np.uint32)
+        self._ck(self._L.mg_estimate_priors(self.h, n, planes, _p(cov), _p(freq), _p(vo), C.c_float(error_rate), max_cov, int(haploid), int(iters), float(weight),
+                                            _p(fo), _p(ni)))
+        return fo, ni
+
+    def estimate_priors_device(self, n_vars, planes, d_cov, d_freq, d_var_allele_off, error_rate, max_cov, haploid, iters, weight, d_freq_out, d_n_informative):
+        v = C.c_void_p
+        self._ck(self._L.mg_estimate_priors_device(self.h, n_vars, planes, v(d_cov), v(d_freq), v(d_var_allele_off), C.c_float(error_rate), max_cov, int(haploid),
+                                                   int(iters), float(weight), v(d_freq_out), v(d_n_informative)))
+
+    def estimate_priors_stats(self):
+        """-> device ms of the most recent estimate_priors"""
+        ms = (C.c_float * 1)()
+        self._ck(self._L.mg_estimate_priors_stats(self.h, ms))
         return float(ms[0])
 
     # the sample columns of a multi-sample BCF

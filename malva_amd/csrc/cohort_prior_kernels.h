@@ -19,6 +19,7 @@
 //                          threads along the records (lanes are planes: stored directly, every lane of a store would hit its own line)
 // No lane leaves before the last cross-lane operation: idle lanes, finished segments and records that are not re-estimated carry
 // +0.0 through the exchange.  No floating-point atomic anywhere.
+// cohort_prior_wide_kernel (below): the estimate alone for any number of planes, the sum over planes continued across chunks of 64.
 #pragma once
 
 constexpr int PRIOR_TPB = 256;
@@ -263,5 +264,238 @@ __global__ void __launch_bounds__(PRIOR_TPB) cohort_prior_kernel(PriorArgs a, Ge
         a.gt2[cell] = s_call[1][pl * ostride + j];
         a.gq[cell] = s_call[2][pl * ostride + j];
         a.status[cell] = s_stat[pl * ostride + j];
+    }
+}
+
+// ---- the estimate alone, for any number of planes (mg_estimate_priors) -------------------------------------------------------------------
+// The same estimate with the sum over planes extended past one wave: planes are cut into chunks of 64 in the order given, a chunk's
+// tree C_j is the butterfly above, and the record's c[a] = C_0[a] + C_1[a] + .. in chunk order, each add rounded on its own
+// (include/malva_hip.h, mg_estimate_priors).  No calls: the cells are genotyped afterwards by mg_genotype_cohort(iters = 0, freq = f_T).
+//
+// Shape.  Up to 64 planes: the segment widths, the run and the LDS staging of cohort_prior_kernel, one chunk, the run staged once.
+// Beyond: every chunk runs at segment width 64 (e >= +0.0 and x + (+0.0) = x for such x, so padding a short chunk to 64 lanes gives
+// the C_j of its own power of two), a wave holds one record at a time and a workgroup a run of 16.  Records are independent, so the
+// whole EM of a record stays inside the workgroup that owns its run:
+//   iteration (outer)      left by the whole workgroup once none of the run's records still iterates (__syncthreads_or)
+//     chunk (inner)        P > 64: the workgroup stages the chunk's rows of the run into s_cov, between two barriers
+//       records of the run, 256 / W at a time: status and the prior-free parts from the coverages (recomputed: they cannot stay in
+//                          registers across chunks), the copies, the butterfly, and c = c + C_j by every lane of the segment alike;
+//                          behind the last chunk the update
+// What a record carries from chunk to chunk and from iteration to iteration lies in LDS, written by every lane of its segment with
+// the same value: f (s_f), the running c and n (s_c, s_n: only P > 64 needs them, where the run is 16), live and the last n.
+// Trip counts: iterations and chunks are workgroup-uniform, the records' steps and the alleles' (amax) wave-uniform; a finished
+// record, an idle lane and a plane that does not count carry +0.0 through the exchange, no lane leaves early.  One launch, no global
+// intermediates, no floating-point atomic.
+constexpr u32 PRIOR_WIDE_RUN = 16; // records per workgroup beyond 64 planes (s_c, s_n)
+
+struct PriorWideArgs {
+    u64 n_vars;
+    u32 n_planes, seg_log2, run, iters, n_chunks;
+    double weight;
+    const u32 *cov;    // [n_planes][slots]
+    const float *freq; // [slots]
+    const u32 *vao;    // [n_vars + 1]
+    float *freq_out;   // [slots]
+    u32 *n_inf;        // [n_vars]
+};
+
+__global__ void __launch_bounds__(PRIOR_TPB) cohort_prior_wide_kernel(PriorWideArgs a, GenoParams p)
+{
+    __shared__ u32 s_cov[PRIOR_COV_CAP];
+    __shared__ float s_f[PRIOR_TPB * MG_PRIOR_MAX_ALLELES];  // [record of the run][allele]: the record's current frequencies
+    __shared__ double s_e[MG_PRIOR_MAX_ALLELES * PRIOR_TPB]; // [allele][thread]: a lane's expected copies (A > 2)
+    __shared__ double s_c[PRIOR_WIDE_RUN * MG_PRIOR_MAX_ALLELES]; // [record of the run][allele]: C_0 + .. + C_j so far (P > 64)
+    __shared__ u32 s_n[PRIOR_WIDE_RUN];                      // the planes that count so far in this iteration (P > 64)
+    __shared__ u32 s_vao[PRIOR_TPB + 1];                     // the run's allele offsets
+    __shared__ u32 s_nlast[PRIOR_TPB];                       // n of the last iteration the record ran
+    __shared__ u8 s_live[PRIOR_TPB];                         // the record still iterates
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 W = 1u << a.seg_log2, plane = lane & (W - 1), seg_base = lane & ~(W - 1), R = 64u >> a.seg_log2;
+    const u64 seg_mask = W == 64 ? ~0ull : ((1ull << W) - 1) << seg_base;
+    const u64 slots = a.vao[a.n_vars];
+    const u64 v0 = (u64)blockIdx.x * a.run, v1 = v0 + a.run < a.n_vars ? v0 + a.run : a.n_vars;
+    const u32 run_len = (u32)(v1 - v0);
+    const u32 a_lo = a.vao[v0], span = a.vao[v1] - a_lo, stride = span | 1; // (odd: the planes of a record fall on different banks)
+    const u32 rows_max = a.n_planes < 64 ? a.n_planes : 64;                 // the planes of a full chunk
+    const bool use_lds = (u64)rows_max * stride <= PRIOR_COV_CAP;
+    const bool wide = a.n_chunks > 1;
+    for (u32 r = tid; r <= run_len; r += PRIOR_TPB) s_vao[r] = a.vao[v0 + r];
+    __syncthreads();
+    if (tid < run_len) { // (run <= PRIOR_TPB)
+        const u32 a0 = s_vao[tid];
+        const int A = (int)(s_vao[tid + 1] - a0);
+        const bool elig = A >= 2 && A <= MG_PRIOR_MAX_ALLELES && a.iters > 0;
+        if (elig)
+            for (int al = 0; al < A; ++al) s_f[tid * MG_PRIOR_MAX_ALLELES + al] = a.freq[a0 + al];
+        s_live[tid] = elig;
+        s_nlast[tid] = 0;
+    }
+    if (!wide && use_lds)
+        for (u32 idx = tid; idx < a.n_planes * span; idx += PRIOR_TPB) {
+            const u32 pl = idx / span, j = idx - pl * span;
+            s_cov[pl * stride + j] = a.cov[pl * slots + a_lo + j];
+        }
+    const int hap = p.haploid;
+    const u32 ploidy = hap ? 1u : 2u;
+    const int G2 = hap ? 2 : 3; // genotypes of a biallelic record
+    for (u32 t = 0; t < a.iters; ++t) {
+        __syncthreads(); // behind the set-up and the last iteration's updates: s_live is read across waves
+        if (!__syncthreads_or(tid < run_len && s_live[tid])) break;
+        for (u32 ch = 0; ch < a.n_chunks; ++ch) {
+            const u32 p_lo = ch * 64, rows = a.n_planes - p_lo < 64 ? a.n_planes - p_lo : 64;
+            if (wide) {
+                __syncthreads(); // the chunk before has been read
+                if (use_lds)
+                    for (u32 idx = tid; idx < rows * span; idx += PRIOR_TPB) {
+                        const u32 pl = idx / span, j = idx - pl * span;
+                        s_cov[pl * stride + j] = a.cov[(u64)(p_lo + pl) * slots + a_lo + j];
+                    }
+                __syncthreads();
+            }
+            const bool mine = plane < rows; // this lane has a cell in this chunk
+            const bool last = ch + 1 == a.n_chunks;
+            for (u32 k = 0; k < a.run; k += 4 * R) {
+                const u32 rec = k + wave * R + (lane >> a.seg_log2);
+                const bool seg_ok = rec < run_len;
+                u32 a0 = 0;
+                int A = 0;
+                if (seg_ok) {
+                    a0 = s_vao[rec];
+                    A = (int)(s_vao[rec + 1] - a0);
+                }
+                const bool live = seg_ok && A >= 2 && A <= MG_PRIOR_MAX_ALLELES && s_live[rec]; // (the whole segment agrees)
+                const u32 row = mine ? plane : 0, rel = seg_ok ? a0 - a_lo : 0; // (a lane without a cell never reads through covp)
+                const u32 *covp = use_lds ? &s_cov[row * stride + rel] : a.cov + (u64)(p_lo + row) * slots + a_lo + rel;
+                float *fseg = &s_f[rec * MG_PRIOR_MAX_ALLELES];
+                const bool two = live && A == 2;
+                // the cell's status from its coverages, and what does not depend on the prior
+                bool normal = false;
+                u32 total = 0;
+                float f0r = 1.f, f1r = 1.f; // A == 2: the record's frequencies
+                double post0 = 0.0, post1 = 0.0, post2 = 0.0;
+                if (two) {
+                    f0r = fseg[0];
+                    f1r = fseg[1];
+                }
+                if (live && mine) {
+                    bool over = false;
+                    int isum = 0;
+                    for (int al = 0; al < A; ++al) {
+                        over |= (int)covp[al] > p.max_cov;
+                        isum += (int)covp[al];
+                    }
+                    total = (u32)isum;
+                    normal = !over && total != 0;
+                    if (two && normal) {
+                        const u32 c0 = covp[0], c1 = covp[1];
+                        post0 = prior_post_hom(c0, total, 2, p);
+                        if (hap) post1 = prior_post_hom(c1, total, 2, p);
+                        else {
+                            post1 = prior_post_het(c0, c1, total, 2, p);
+                            post2 = prior_post_hom(c1, total, 2, p);
+                        }
+                    }
+                }
+                int amax = MG_PRIOR_MAX_ALLELES; // the largest A among the wave's records that still iterate
+                while (amax > 2 && !__any(live && A >= amax)) --amax;
+                // A == 2: the log priors, genotype g by lane g of the segment (W < G2: in several passes)
+                double L0 = 0.0, L1 = 0.0, L2 = 0.0;
+                if (__any(two))
+                    for (u32 base = 0; base < (u32)G2; base += W) {
+                        const u32 g = base + plane;
+                        const bool het = !hap && g == 1;
+                        const float x = het ? 2 * f0r * f1r : (g == 0 ? f0r : f1r);
+                        const float l = logf_ref(x);
+                        const double m = het ? (double)l : (double)(2 * l);
+                        if (base <= 0 && 0 < base + W) L0 = __shfl(m, (int)(seg_base + 0 - base));
+                        if (base <= 1 && 1 < base + W) L1 = __shfl(m, (int)(seg_base + 1 - base));
+                        if (G2 > 2 && base <= 2 && 2 < base + W) L2 = __shfl(m, (int)(seg_base + 2 - base));
+                    }
+                // posteriors and expected copies of this lane's cell
+                bool counts = false;
+                double e1 = 0.0;
+                if (live && mine && normal) {
+                    if (two) {
+                        const double w0 = prior_value(L0, post0), w1 = prior_value(L1, post1);
+                        if (hap) {
+                            const double sum = 0.0 + w0 + w1;
+                            counts = isfinite(sum) && sum > 0;
+                            if (counts) e1 = 0.0 + w1 / sum;
+                        } else {
+                            const double w2 = prior_value(L2, post2);
+                            const double sum = 0.0 + w0 + w1 + w2;
+                            counts = isfinite(sum) && sum > 0;
+                            if (counts) {
+                                e1 = 0.0 + w1 / sum;
+                                e1 = e1 + 2.0 * (w2 / sum);
+                            }
+                        }
+                    } else {
+                        double sum = 0.0;
+                        for (int g1 = 0; g1 < A; ++g1)
+                            for (int g2 = hap ? -1 : g1; g2 < (hap ? 0 : A); ++g2) sum += gt_value(covp, fseg, A, total, g1, g2, p);
+                        counts = isfinite(sum) && sum > 0;
+                        if (counts) {
+                            for (int al = 0; al < A; ++al) s_e[al * PRIOR_TPB + tid] = 0.0;
+                            for (int g1 = 0; g1 < A; ++g1)
+                                for (int g2 = hap ? -1 : g1; g2 < (hap ? 0 : A); ++g2) {
+                                    const double q = gt_value(covp, fseg, A, total, g1, g2, p) / sum;
+                                    if (hap) s_e[g1 * PRIOR_TPB + tid] += q;
+                                    else if (g1 == g2) s_e[g1 * PRIOR_TPB + tid] += 2.0 * q;
+                                    else {
+                                        s_e[g1 * PRIOR_TPB + tid] += q;
+                                        s_e[g2 * PRIOR_TPB + tid] += q;
+                                    }
+                                }
+                        }
+                    }
+                }
+                // n and c over the chunks so far (rec < PRIOR_WIDE_RUN wherever there is more than one chunk)
+                u32 n = (u32)__popcll(__ballot(counts) & seg_mask);
+                if (ch > 0) n += s_n[rec];
+                if (wide && !last && live) s_n[rec] = n;
+                const bool upd = live && last && n > 0;
+                bool changed = false;
+                double acc = 0.0;
+                acc += 0.f;
+                for (int al = 1; al < amax; ++al) {
+                    double x = 0.0;
+                    if (counts && al < A) x = two ? e1 : s_e[al * PRIOR_TPB + tid];
+                    for (u32 s = W >> 1; s; s >>= 1) x = x + __shfl_xor(x, (int)s);
+                    double c = __shfl(x, (int)seg_base);
+                    if (live && al < A) {
+                        if (ch > 0) c = s_c[rec * MG_PRIOR_MAX_ALLELES + al] + c;
+                        if (wide && !last) s_c[rec * MG_PRIOR_MAX_ALLELES + al] = c;
+                    }
+                    if (upd && al < A) {
+                        const double f0a = (double)a.freq[a0 + al];
+                        const double wf = a.weight * f0a;
+                        const double num = c + wf;
+                        const double den = (double)(ploidy * n) + a.weight;
+                        const float fn = (float)(num / den);
+                        changed |= __float_as_uint(fn) != __float_as_uint(fseg[al]);
+                        fseg[al] = fn;
+                        acc += fn;
+                    }
+                }
+                if (live && last) {
+                    s_nlast[rec] = n;
+                    if (upd) {
+                        const float fr = prior_ref_freq(acc);
+                        changed |= __float_as_uint(fr) != __float_as_uint(fseg[0]);
+                        fseg[0] = fr;
+                    }
+                    s_live[rec] = changed; // n == 0 or a repeat: every later iteration would give the same again
+                }
+            }
+        }
+    }
+    // the records' frequencies and n, threads along the records
+    __syncthreads();
+    if (tid < run_len) {
+        const u32 a0 = s_vao[tid], A = s_vao[tid + 1] - a0;
+        const bool elig = A >= 2 && A <= MG_PRIOR_MAX_ALLELES && a.iters > 0;
+        for (u32 al = 0; al < A; ++al) a.freq_out[a0 + al] = elig ? s_f[tid * MG_PRIOR_MAX_ALLELES + al] : a.freq[a0 + al];
+        a.n_inf[v0 + tid] = s_nlast[tid];
     }
 }

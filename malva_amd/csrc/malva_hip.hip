@@ -87,7 +87,7 @@ struct Timer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -167,7 +167,7 @@ struct mg_ctx {
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
     hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
     // the merged-batch section: each stats call reports the latest call of its own kinds, hence a timer per kind
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -3764,6 +3764,77 @@ MG_EXPORT int mg_cohort_prior_stats(mg_ctx *c, float *ms_out)
     ms_out[0] = 0.f; // (also where it fails)
     if (!c->tm[TM_PRIOR].valid) return fail(c, MG_ERR_STATE, "no mg_genotype_cohort yet");
     return timer_read(c, c->tm[TM_PRIOR], ms_out);
+}
+
+// ---- the estimate alone, for any number of planes (cohort_prior_wide_kernel) ---------------------------------------------------------------
+namespace {
+int check_estimate_priors(mg_ctx *c, size_t n_vars, uint32_t n_planes, const void *cov, const void *freq, const void *var_allele_off, uint32_t iters, double weight,
+                          const void *freq_out, const void *n_informative)
+{
+    if (n_planes < 1 || n_planes > MG_PRIOR_WIDE_MAX_PLANES) return fail(c, MG_ERR_ARG, "mg_estimate_priors takes 1..16384 planes");
+    if (iters > 64) return fail(c, MG_ERR_ARG, "mg_estimate_priors takes at most 64 iterations");
+    if (!std::isfinite(weight) || weight < 0) return fail(c, MG_ERR_ARG, "mg_estimate_priors takes a finite weight >= 0");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_estimate_priors: more than 2^32 - 1 records in one call");
+    if (n_vars && (!cov || !freq || !var_allele_off || !freq_out || !n_informative)) return fail(c, MG_ERR_ARG, "NULL argument");
+    return MG_OK;
+}
+} // namespace
+
+MG_EXPORT int mg_estimate_priors_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, const void *d_cov, const void *d_freq, const void *d_var_allele_off, float error_rate,
+                                        int max_cov, int haploid, uint32_t iters, double weight, void *d_freq_out, void *d_n_informative)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_estimate_priors(c, n_vars, n_planes, d_cov, d_freq, d_var_allele_off, iters, weight, d_freq_out, d_n_informative));
+    GenoParams p;
+    if (n_vars) TRY(fill_geno_params(c, error_rate, max_cov, haploid, &p)); // (may synchronise: before the timer starts)
+    TRY(timer_begin(c, c->tm[TM_ESTIMATE]));
+    if (n_vars) {
+        // up to 64 planes: mg_genotype_cohort's segment widths and run; beyond: chunks of 64 planes at width 64, a run of PRIOR_WIDE_RUN
+        const u32 n_chunks = (n_planes + 63) / 64;
+        u32 seg_log2 = 0;
+        while ((1u << seg_log2) < std::min<u32>(n_planes, 64)) ++seg_log2;
+        const u32 run = n_chunks > 1 ? PRIOR_WIDE_RUN : std::max<u32>(PRIOR_TPB >> seg_log2, PRIOR_MIN_RUN);
+        static_assert(PRIOR_WIDE_RUN % 4 == 0 && PRIOR_WIDE_RUN <= PRIOR_TPB, "four waves, a record each at a time");
+        const PriorWideArgs a{(u64)n_vars, n_planes, seg_log2, run, iters, n_chunks, weight, (const u32 *)d_cov, (const float *)d_freq, (const u32 *)d_var_allele_off,
+                              (float *)d_freq_out, (u32 *)d_n_informative};
+        hipLaunchKernelGGL(cohort_prior_wide_kernel, dim3((unsigned)((n_vars + run - 1) / run)), dim3(PRIOR_TPB), 0, c->stream, a, p);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_ESTIMATE], 1);
+}
+
+MG_EXPORT int mg_estimate_priors(mg_ctx *c, size_t n_vars, uint32_t n_planes, const uint32_t *cov, const float *freq, const uint32_t *var_allele_off, float error_rate,
+                                 int max_cov, int haploid, uint32_t iters, double weight, float *freq_out, uint32_t *n_informative)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_estimate_priors(c, n_vars, n_planes, cov, freq, var_allele_off, iters, weight, freq_out, n_informative));
+    const size_t na = n_vars ? var_allele_off[n_vars] : 0;
+    void *d_cov = nullptr, *d_freq = nullptr, *d_off = nullptr, *d_fo = nullptr, *d_ni = nullptr;
+    if (n_vars) {
+        TRY(upload(c, c->stage[ST_COV], cov, 4 * (size_t)n_planes * na, &d_cov));
+        TRY(upload(c, c->stage[ST_FREQ], freq, 4 * na, &d_freq));
+        TRY(upload(c, c->stage[ST_VAR_ALLELE_OFF], var_allele_off, 4 * (n_vars + 1), &d_off));
+        TRY(scratch(c, c->stage[ST_FREQ_OUT], 4 * (na ? na : 1), &d_fo));
+        TRY(scratch(c, c->stage[ST_NINF], 4 * n_vars, &d_ni));
+    }
+    TRY(mg_estimate_priors_device(c, n_vars, n_planes, d_cov, d_freq, d_off, error_rate, max_cov, haploid, iters, weight, d_fo, d_ni));
+    if (!n_vars) return MG_OK;
+    if (na) HIP_TRY(c, hipMemcpyAsync(freq_out, d_fo, 4 * na, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(n_informative, d_ni, 4 * n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds (waits for them) of the most recent mg_estimate_priors*
+MG_EXPORT int mg_estimate_priors_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = 0.f; // (also where it fails)
+    if (!c->tm[TM_ESTIMATE].valid) return fail(c, MG_ERR_STATE, "no mg_estimate_priors yet");
+    return timer_read(c, c->tm[TM_ESTIMATE], ms_out);
 }
 
 namespace {

@@ -112,7 +112,16 @@ const char *USAGE =
     "                                        Records of 2..8 alleles; estimated on the GPU.  Every output (-o, --merged in text and\n"
     "                                        BCF, --gp, -v, --min-gq, --site-tags, --pairs, --sample-stats) is made from the new\n"
     "                                        calls.  The cohort must run as ONE group: more than 64 samples, a --cohort-group below\n"
-    "                                        the cohort, or a cohort that does not fit beside the index is an error     [this build]\n"
+    "                                        the cohort, or a cohort that does not fit beside the index is an error -- unless\n"
+    "                                        --prior-groups is given                                                    [this build]\n"
+    "          --prior-groups                --cohort-priors: the cohort may run as several groups -- more than 64 samples (at most\n"
+    "                                        16384), a --cohort-group below the cohort, or as many samples at once as fit beside the\n"
+    "                                        index.  Every group first leaves its coverages in a scratch file beside the output (under\n"
+    "                                        $TMPDIR for stdout; 4 B x allele slots x samples of disk, removed at the end), the\n"
+    "                                        frequencies are estimated from all of them on the GPU, then every group is genotyped under\n"
+    "                                        them.  Every output is byte for byte the one-group run's while every record's total\n"
+    "                                        coverage stays below 65536 (leaving that range takes a --max-coverage of 8192 or more).\n"
+    "                                        A cohort that runs as one group anyway takes the one-group path               [this build]\n"
     "          --prior-iters                 --cohort-priors: EM iterations, 0..64 (default:5; 0: the panel's priors, every output as\n"
     "                                        without --cohort-priors).  The default is a design choice, not a measurement [this build]\n"
     "          --prior-weight                --cohort-priors: the panel's prior counts as this many allele copies beside the cohort's,\n"
@@ -182,6 +191,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"pairs", required_argument, nullptr, 1010},    {"sample-stats", required_argument, nullptr, 1011},
                                       {"cohort-priors", no_argument, nullptr, 1012},  {"prior-iters", required_argument, nullptr, 1013},
                                       {"prior-weight", required_argument, nullptr, 1014}, {"priors-out", required_argument, nullptr, 1015},
+                                      {"prior-groups", no_argument, nullptr, 1016},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -280,6 +290,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                 die = true;
             }
             break;
+        case 1016: o.priors.groups = true; break;
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -1314,7 +1325,7 @@ int call_main(const Options &o)
         return fail_early(e.what());
     }
     if (o.priors.on) { // (the sizes already tell: before any device is created, before anything is written)
-        const std::string why = prior_group_error(samples.size(), o.cohort_group);
+        const std::string why = o.priors.groups ? prior_groups_error(samples.size()) : prior_group_error(samples.size(), o.cohort_group);
         if (!why.empty()) return fail_early("ERROR: " + why);
     }
     // --gpus N: one context per device -d .. -d+N-1.  MALVA_GENO_SHARE_DEVICE=1 puts all N contexts on device -d: the
@@ -1385,6 +1396,8 @@ int call_main(const Options &o)
     size_t sample_calls = 0;
     double prior_ms = 0;                      // --cohort-priors: device milliseconds of the mg_genotype_cohort
     size_t prior_calls = 0;
+    double estimate_ms = 0;                   // --prior-groups: device milliseconds of the mg_estimate_priors
+    size_t estimate_calls = 0;
     PriorsFile priors_file;                   // --priors-out
     // --merged-format bcf | ubcf: the merged file as BCF2 (host/bcf_out.hpp), a record's per-sample block encoded by mg_encode_calls_bcf
     const bool bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", bcf_bgzf = o.merged_format == "bcf";
@@ -1440,22 +1453,33 @@ int call_main(const Options &o)
         PairsRun *pairs = nullptr;
         // --sample-stats: the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand (mg_sample_counts, accumulate)
         uint64_t *sample_table = nullptr;
+        // --prior-groups, a cohort in several groups (host/cohort_priors.hpp).  prior_cov: the coverage pass -- the batches' coverages go here
+        // (put_cov_batch; the first group's with the records' offsets and panel priors), and the pass makes no calls and nothing else.
+        // prior_in: the output pass -- the batches' coverages and the cohort's frequencies come from here instead of the counters, and the
+        // cells are genotyped under them by mg_genotype_cohort(iters = 0)
+        PartFile *prior_cov = nullptr;
+        bool prior_cov_panel = false;
+        PriorGroupInput *prior_in = nullptr;
     };
     struct BatchText { // the text of one batch, as its worker hands it over
         std::vector<std::string> per_sample;
-        std::string merged, site_counts, pack, priors; // priors: the lines of --priors-out
+        std::string merged, site_counts, pack, priors, prior_cov; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
     };
     // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to to.per_sample[0] (stdout).  planes > 0:
     // the context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
     // only the INFO and GT:GQ fields per sample.
     // --cohort-priors: a batch's coverages are made as always; its frequencies are then re-estimated over all planes and every plane genotyped
     // under them by ONE mg_genotype_cohort per batch kind, whose arrays everything below reads; priors_file, when open, gets a line per record.
+    // --prior-groups with a cohort in several groups: the pass runs twice per group -- to.prior_cov: up to the coverages, which it writes and
+    // nothing else; to.prior_in: coverages and the cohort's frequencies read back, the cells genotyped under them, everything below as always.
     auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, PassOut &to) -> size_t {
     std::deque<PartFile> &outs = to.per_sample;
     PartFile *const merged_out = to.merged, *const cnt_out = to.site_counts;
     const bool merged_fixed = to.merged_fixed;
     PairsRun *const pairs = to.pairs;
     uint64_t *const sample_table = to.sample_table;
+    PartFile *const prior_cov = to.prior_cov;
+    PriorGroupInput *const prior_in = to.prior_in;
     const size_t P = planes ? planes : 1;
 
     const bool want_probs = o.verbose || o.gp; // the likelihood lists: GTS= of -v, GP of --merged --gp
@@ -1477,7 +1501,7 @@ int call_main(const Options &o)
             const size_t n = iso.n(), na = iso.var_allele_off.back(), ng = want_probs ? iso.var_gt_off.back() : 0;
             iso.cov.resize(P * na); iso.g1.resize(P * n); iso.g2.resize(P * n); iso.gq.resize(P * n); iso.status.resize(P * n);
             iso.probs.resize(P * ng);
-            for (size_t pl = 0; pl < P; ++pl) { // (the fused lone-variant call reads the selected plane)
+            for (size_t pl = 0; pl < P && !prior_in; ++pl) { // (the fused lone-variant call reads the selected plane)
                 if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
                 dev.check(mg_call_isolated(dev.ctx, n, iso.pos.data(), iso.var_allele_off.data(), iso.allele_off.data(), iso.pool.data(), iso.pool.size(),
                                            iso.freq.data(), iso.present.data(), iso.flags.data(), o.error_rate, (int)o.max_coverage, o.haploid, iso.cov.data() + pl * na,
@@ -1492,8 +1516,12 @@ int call_main(const Options &o)
             b.freq_out.resize(b.freq.size());
             b.n_inf.resize(n);
             b.probs.resize(P * ng);
-            dev.check(mg_genotype_cohort(dev.ctx, n, (uint32_t)P, b.cov.data(), b.freq.data(), b.var_allele_off.data(), o.error_rate, (int)o.max_coverage, o.haploid,
-                                         o.priors.iters, o.priors.weight, b.freq_out.data(), b.n_inf.data(), b.g1.data(), b.g2.data(), b.gq.data(), b.status.data(),
+            // the output pass of a cohort in several groups: freq_out and n_inf hold the cohort's estimate; the cells under it, nothing re-estimated
+            const std::vector<float> f_t = prior_in ? b.freq_out : std::vector<float>();
+            std::vector<uint32_t> no_n(prior_in ? n : 0);
+            dev.check(mg_genotype_cohort(dev.ctx, n, (uint32_t)P, b.cov.data(), prior_in ? f_t.data() : b.freq.data(), b.var_allele_off.data(), o.error_rate,
+                                         (int)o.max_coverage, o.haploid, prior_in ? 0 : o.priors.iters, o.priors.weight, b.freq_out.data(),
+                                         prior_in ? no_n.data() : b.n_inf.data(), b.g1.data(), b.g2.data(), b.gq.data(), b.status.data(),
                                          want_probs ? b.probs.data() : nullptr, want_probs ? b.var_gt_off.data() : nullptr),
                       "mg_genotype_cohort");
             float ms = 0;
@@ -1501,74 +1529,87 @@ int call_main(const Options &o)
             prior_ms += ms;
             ++prior_calls;
         };
-        if (iso.n() && o.priors.on) cohort_priors(iso); // (mg_call_isolated made the coverages; its calls are replaced)
+        if (iso.n() && o.priors.on && !prior_cov) cohort_priors(iso); // (mg_call_isolated made the coverages; its calls are replaced)
         if (gen.n()) {
             const size_t n = gen.n(), na = gen.var_allele_off.back(), ng = want_probs ? gen.var_gt_off.back() : 0;
             gen.cov.resize(P * na); gen.g1.resize(P * n); gen.g2.resize(P * n); gen.gq.resize(P * n); gen.status.resize(P * n);
             gen.probs.resize(P * ng);
-            // panel genotypes of the batch as one [variant][sample] matrix of a1 | a2 << 7 | phased << 14
-            const uint32_t n_samples = (uint32_t)vcf.keep.size();
-            std::vector<uint8_t> overflow(n, 0);
-            bool device_ok = o.k <= MG_MAX_PACKED_K && !getenv("MALVA_GENO_HOST_ENUM"); // the variable forces the host enumerator (tests)
-            if (gen.wide_alleles) device_ok = false;
-            const size_t n_blocks = gen.n_blocks();
-            PanelGenotypes pg;
-            if (gen.dense_gt) pg.gt = std::move(gen.gt_dense);
-            else pg = pack_genotypes(gen.vars, n, n_samples, o.haploid); // (every record of such a batch is kept)
-            gt_bytes_uploaded += pg.bytes();
-            if (device_ok && planes) // the batch goes up once and is covered for every plane (cov: [planes][na])
-                dev.check(mg_cover_blocks_cohort(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                                 gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                                 gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sparse ? nullptr : pg.gt.data(),
-                                                 pg.sparse ? pg.sp_off.data() : nullptr, pg.sparse ? pg.sp_sample.data() : nullptr,
-                                                 pg.sparse ? pg.sp_gt.data() : nullptr, pg.sparse ? pg.sp_default : (uint16_t)0, n_samples, o.haploid, gen.cov.data(),
-                                                 overflow.data()),
-                          "mg_cover_blocks_cohort");
-            else if (device_ok && pg.sparse)
-                dev.check(mg_cover_blocks_sparse(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                                 gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                                 gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sp_off.data(), pg.sp_sample.data(),
-                                                 pg.sp_gt.data(), pg.sp_default, n_samples, o.haploid, gen.cov.data(), overflow.data()),
-                          "mg_cover_blocks_sparse"); // extract_kmers + set_coverages, main.cpp:556-557
-            else if (device_ok)
-                dev.check(mg_cover_blocks(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                          gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                          gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.gt.data(), n_samples, o.haploid,
-                                          gen.cov.data(), overflow.data()),
-                          "mg_cover_blocks"); // extract_kmers + set_coverages, main.cpp:556-557
-            else
-                std::fill(overflow.begin(), overflow.end(), 1);
-            // blocks the device handed back (a capacity was exceeded, or a window was clipped by a contig end):
-            // host enumerator + mg_lookup_cover for exactly those blocks
-            size_t n_fallback = 0;
-            for (size_t b = 0; b < n_blocks; ++b) {
-                bool redo = false;
-                for (uint32_t v = gen.blk_var_off[b]; v < gen.blk_var_off[b + 1]; ++v) redo = redo || overflow[v];
-                if (!redo) continue;
-                ++n_fallback;
-                Block blk((int)o.k); // (rebuilt from the batch's records: nothing reads them after this)
-                for (uint32_t v = gen.blk_var_off[b]; v < gen.blk_var_off[b + 1]; ++v) {
-                    if (gen.var_slot[v] < 0) throw std::runtime_error("internal: the device handed back a record tier 1 should have taken");
-                    blk.add(std::move(gen.vars[(size_t)gen.var_slot[v]]));
+            if (!prior_in) { // (the output pass of a cohort in several groups has the coverages from the group's file)
+                // panel genotypes of the batch as one [variant][sample] matrix of a1 | a2 << 7 | phased << 14
+                const uint32_t n_samples = (uint32_t)vcf.keep.size();
+                std::vector<uint8_t> overflow(n, 0);
+                bool device_ok = o.k <= MG_MAX_PACKED_K && !getenv("MALVA_GENO_HOST_ENUM"); // the variable forces the host enumerator (tests)
+                if (gen.wide_alleles) device_ok = false;
+                const size_t n_blocks = gen.n_blocks();
+                PanelGenotypes pg;
+                if (gen.dense_gt) pg.gt = std::move(gen.gt_dense);
+                else pg = pack_genotypes(gen.vars, n, n_samples, o.haploid); // (every record of such a batch is kept)
+                gt_bytes_uploaded += pg.bytes();
+                if (device_ok && planes) // the batch goes up once and is covered for every plane (cov: [planes][na])
+                    dev.check(mg_cover_blocks_cohort(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
+                                                     gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
+                                                     gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sparse ? nullptr : pg.gt.data(),
+                                                     pg.sparse ? pg.sp_off.data() : nullptr, pg.sparse ? pg.sp_sample.data() : nullptr,
+                                                     pg.sparse ? pg.sp_gt.data() : nullptr, pg.sparse ? pg.sp_default : (uint16_t)0, n_samples, o.haploid, gen.cov.data(),
+                                                     overflow.data()),
+                              "mg_cover_blocks_cohort");
+                else if (device_ok && pg.sparse)
+                    dev.check(mg_cover_blocks_sparse(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
+                                                     gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
+                                                     gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sp_off.data(), pg.sp_sample.data(),
+                                                     pg.sp_gt.data(), pg.sp_default, n_samples, o.haploid, gen.cov.data(), overflow.data()),
+                              "mg_cover_blocks_sparse"); // extract_kmers + set_coverages, main.cpp:556-557
+                else if (device_ok)
+                    dev.check(mg_cover_blocks(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
+                                              gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
+                                              gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.gt.data(), n_samples, o.haploid,
+                                              gen.cov.data(), overflow.data()),
+                              "mg_cover_blocks"); // extract_kmers + set_coverages, main.cpp:556-557
+                else
+                    std::fill(overflow.begin(), overflow.end(), 1);
+                // blocks the device handed back (a capacity was exceeded, or a window was clipped by a contig end):
+                // host enumerator + mg_lookup_cover for exactly those blocks
+                size_t n_fallback = 0;
+                for (size_t b = 0; b < n_blocks; ++b) {
+                    bool redo = false;
+                    for (uint32_t v = gen.blk_var_off[b]; v < gen.blk_var_off[b + 1]; ++v) redo = redo || overflow[v];
+                    if (!redo) continue;
+                    ++n_fallback;
+                    Block blk((int)o.k); // (rebuilt from the batch's records: nothing reads them after this)
+                    for (uint32_t v = gen.blk_var_off[b]; v < gen.blk_var_off[b + 1]; ++v) {
+                        if (gen.var_slot[v] < 0) throw std::runtime_error("internal: the device handed back a record tier 1 should have taken");
+                        blk.add(std::move(gen.vars[(size_t)gen.var_slot[v]]));
+                    }
+                    genotypes_from_entries(blk);
+                    const SignatureRows s = signature_rows(blk, blk.extract(*gen.block_ref[b], o.haploid));
+                    const size_t slot0 = gen.var_allele_off[gen.blk_var_off[b]];
+                    for (size_t pl = 0; pl < P; ++pl) { // (enumerated once; the lookups read the selected plane)
+                        if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
+                        dev.check(mg_lookup_cover(dev.ctx, s.rows.data.data(), STRIDE, s.rows.n, s.is_ref.data(), s.sig_off.data(), s.sig_off.size() - 1, s.al_off.data(),
+                                                  s.al_off.size() - 1, gen.cov.data() + pl * na + slot0),
+                                  "mg_lookup_cover");
+                    }
                 }
-                genotypes_from_entries(blk);
-                const SignatureRows s = signature_rows(blk, blk.extract(*gen.block_ref[b], o.haploid));
-                const size_t slot0 = gen.var_allele_off[gen.blk_var_off[b]];
-                for (size_t pl = 0; pl < P; ++pl) { // (enumerated once; the lookups read the selected plane)
-                    if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
-                    dev.check(mg_lookup_cover(dev.ctx, s.rows.data.data(), STRIDE, s.rows.n, s.is_ref.data(), s.sig_off.data(), s.sig_off.size() - 1, s.al_off.data(),
-                                              s.al_off.size() - 1, gen.cov.data() + pl * na + slot0),
-                              "mg_lookup_cover");
-                }
+                if (n_fallback) std::cerr << "[malva-geno] " << n_fallback << " block(s) enumerated on the host" << std::endl;
             }
-            if (n_fallback) std::cerr << "[malva-geno] " << n_fallback << " block(s) enumerated on the host" << std::endl;
-            if (o.priors.on) cohort_priors(gen);
+            if (prior_cov) {} // (the coverage pass makes no calls)
+            else if (o.priors.on) cohort_priors(gen);
             else
             for (size_t pl = 0; pl < P; ++pl)
                 dev.check(mg_genotype(dev.ctx, gen.cov.data() + pl * na, gen.freq.data(), gen.var_allele_off.data(), n, o.error_rate, (int)o.max_coverage, o.haploid,
                                       gen.g1.data() + pl * n, gen.g2.data() + pl * n, gen.gq.data() + pl * n, gen.status.data() + pl * n,
                                       want_probs ? gen.probs.data() + pl * ng : nullptr, want_probs ? gen.var_gt_off.data() : nullptr),
                           "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
+        }
+        if (prior_cov) { // the coverage pass: the batches' coverages for the estimate pass, and nothing else
+            BatchText text;
+            for (int w = 0; w < 2; ++w) {
+                const Batch &b = w ? gen : iso;
+                if (b.n()) put_cov_batch(text.prior_cov, (uint64_t)w, b.n(), b.var_allele_off.data(), b.freq.data(), to.prior_cov_panel, P, b.cov.data());
+            }
+            device_lock.unlock();
+            delete t_dev;
+            return text;
         }
         // --merged: the sample columns of both batches as text, made where the genotypes were
         std::vector<char> row_text[2], info_text[2];
@@ -1689,10 +1730,14 @@ int call_main(const Options &o)
             if (cnt_out) cnt_out->write(text.site_counts, "cannot write the merged output's counts");
             if (pairs && pairs->pack_out) pairs->pack_out->write(text.pack, "cannot write the pair table's packed calls");
             priors_file.write(text.priors);
+            if (prior_cov) prior_cov->write(text.prior_cov, "cannot write the coverages for the cohort's priors");
         }
     };
     auto run_and_print = [&](std::vector<Rec> &&recs, Batch &&iso, Batch &&gen) {
         drain(devs.size() - 1);
+        if (prior_in) // (read here, on the one thread that hands the batches over: the streams keep the batches' order)
+            for (Batch *b : {&iso, &gen})
+                if (b->n()) prior_in->next(b == &gen, b->n(), b->var_allele_off.back(), b->cov, b->freq_out, b->n_inf);
         auto job = std::make_shared<Job>(Job{std::move(recs), std::move(iso), std::move(gen), jobs_started++ % devs.size()});
         in_flight.push_back(std::async(std::launch::async, [&process, job]() { return process(*job); }));
     };
@@ -1704,6 +1749,7 @@ int call_main(const Options &o)
                                     [&](Block &vb, const std::string &seq_name, const std::string &reference) { batches.add_block(vb, seq_name, reference); }, &devs[0]);
     batches.flush();
     drain(0);
+    if (prior_in) prior_in->done();
     for (PartFile &f : outs) fflush(f.f);
     if (merged_out) fflush(merged_out->f);
     if (cnt_out) fflush(cnt_out->f);
@@ -1769,12 +1815,21 @@ int call_main(const Options &o)
         bool merged_direct = false; // one group: no temporary blocks
         std::vector<uint32_t> group_planes; // the samples of every group, in the order they ran
         size_t G = o.cohort_group ? (size_t)o.cohort_group : std::min<size_t>(samples.size(), 64);
-        for (size_t s0 = 0; s0 < samples.size();) {
-            size_t g = std::min(G, samples.size() - s0);
-            {
+        // --cohort-priors --prior-groups with a cohort in several groups: every group runs twice.  Its COVERAGE pass holds the samples' counters
+        // and leaves the batches' coverages in BASE.gN.cov.part; the estimate pass behind the last group makes BASE.freq.part from all of them
+        // (host/cohort_priors.hpp); its OUTPUT pass reads both, needs no counters and makes what a WHOLE group makes.  BASE: the merged output's
+        // scratch base, else a name inside -o's directory.
+        enum GroupPass { WHOLE, COVERAGE, OUTPUT };
+        std::deque<PartFile> prior_cov_files;
+        PartFile prior_freq_file;
+        const std::string prior_base = !o.merged.empty() ? merged_tmp_base : o.out_dir + "/malva-geno.priors";
+        bool prior_split = false;
+        auto run_group = [&](const size_t s0, const GroupPass pass) -> size_t { // -> the group's samples
+            size_t g = pass == OUTPUT ? group_planes[group_first.size()] : std::min(G, samples.size() - s0);
+            if (pass != OUTPUT) {
                 Timed t("cohort: planes");
                 int rc = mg_cohort_begin(dev.ctx, (uint32_t)g);
-                if (rc == MG_ERR_NOMEM && o.priors.on && g > 1) throw std::runtime_error(prior_memory_error(samples.size())); // (no smaller groups: nothing has been written)
+                if (rc == MG_ERR_NOMEM && o.priors.on && !o.priors.groups && g > 1) throw std::runtime_error(prior_memory_error(samples.size())); // (no smaller groups: nothing has been written)
                 while (rc == MG_ERR_NOMEM && !o.cohort_group && g > 1) { // (as many as fit beside the index)
                     G = g = (g + 1) / 2;
                     rc = mg_cohort_begin(dev.ctx, (uint32_t)g);
@@ -1782,22 +1837,55 @@ int call_main(const Options &o)
                 dev.check(rc, "mg_cohort_begin");
             }
             if (!o.out_dir.empty() && mkdir(o.out_dir.c_str(), 0777) != 0 && errno != EEXIST) throw std::runtime_error("cannot create " + o.out_dir);
-            if (o.priors.on && !o.priors.out.empty()) priors_file.open(o.priors.out); // (one group: opened once)
-            group_planes.push_back((uint32_t)g);
+            GroupPass mode = pass;
+            if (pass == WHOLE && s0 == 0 && o.priors.on && o.priors.groups && g < samples.size()) mode = COVERAGE, prior_split = true;
+            else if (pass == WHOLE && prior_split) mode = COVERAGE;
+            PassOut to; // (a group's files are written as NAME.vcf.part: a failure on the way leaves no truncated NAME.vcf behind)
+            if (mode == COVERAGE) { // (nothing of the outputs exists yet)
+                group_planes.push_back((uint32_t)g);
+                {
+                    Timed t("cohort: table scans");
+                    for (size_t i = 0; i < g; ++i) {
+                        dev.check(mg_cohort_select(dev.ctx, (uint32_t)i), "mg_cohort_select");
+                        scan_sample(samples[s0 + i].input);
+                    }
+                }
+                to.prior_cov = &open_scratch(prior_cov_files, prior_base, ".cov.part");
+                to.prior_cov_panel = s0 == 0;
+                {
+                    Timed t("cohort: coverage pass");
+                    std::unique_ptr<VcfReader> again;
+                    if (s0) {
+                        again.reset(new VcfReader(o.vcf_path, o.samples));
+                        start_vcf(*again);
+                        if (!again->ok()) throw std::runtime_error(again->error);
+                    }
+                    n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, to);
+                }
+                to.prior_cov->close("cannot write the coverages for the cohort's priors");
+                dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
+                return g;
+            }
+            if (o.priors.on && !o.priors.out.empty() && s0 == 0) priors_file.open(o.priors.out); // (the first group writes the table: every group has the cohort's values)
+            if (mode == WHOLE) group_planes.push_back((uint32_t)g);
             group_first.push_back(s0);
+            PriorGroupInput prior_in;
+            if (mode == OUTPUT) {
+                prior_in.open(prior_cov_files[group_first.size() - 1].path, prior_freq_file.path, g);
+                to.prior_in = &prior_in;
+            }
             PairsRun pairs_run;
             if (want_pairs) {
                 pairs_run.counts.assign(g * g * 9, 0);
                 if (g != S) pairs_run.pack_out = &open_scratch(pack_files, o.pairs, ".pack.part"); // (several groups: their pairs across need every group's calls again)
             }
-            {
+            if (mode == WHOLE) {
                 Timed t("cohort: table scans");
                 for (size_t i = 0; i < g; ++i) {
                     dev.check(mg_cohort_select(dev.ctx, (uint32_t)i), "mg_cohort_select");
                     scan_sample(samples[s0 + i].input);
                 }
             }
-            PassOut to; // (a group's files are written as NAME.vcf.part: a failure on the way leaves no truncated NAME.vcf behind)
             to.merged_fixed = s0 == 0;
             to.pairs = want_pairs ? &pairs_run : nullptr;
             to.sample_table = want_sample ? &sample_table[s0 * MG_SAMPLE_SLOTS] : nullptr;
@@ -1814,15 +1902,16 @@ int call_main(const Options &o)
                 if (s0 == 0 && (!bcf_out || merged_direct)) to.merged->write(merged_head, "cannot write the merged output");
             }
             {
-                Timed t("cohort: panel pass");
+                Timed t(mode == OUTPUT ? "cohort: output pass" : "cohort: panel pass");
                 std::unique_ptr<VcfReader> again;
-                if (s0) { // (the panel does not stay resident across groups: it is read again)
+                if (s0 || mode == OUTPUT) { // (the panel does not stay resident across groups: it is read again)
                     again.reset(new VcfReader(o.vcf_path, o.samples));
                     start_vcf(*again);
                     if (!again->ok()) throw std::runtime_error(again->error);
                 }
-                n = vcf_pass(s0 ? *again : *vcf_first, (uint32_t)g, to);
+                n = vcf_pass(again ? *again : *vcf_first, (uint32_t)g, to);
             }
+            priors_file.close(); // (a later group adds nothing; the table takes its name at the end)
             if (pairs_run.pack_out) pairs_run.pack_out->close("cannot write the pair table's packed calls");
             for (size_t i = 0; want_pairs && i < g; ++i)
                 for (size_t j = i + 1; j < g; ++j) std::copy_n(&pairs_run.counts[(i * g + j) * 9], 9, &pair_table[((s0 + i) * S + s0 + j) * 9]);
@@ -1834,8 +1923,30 @@ int call_main(const Options &o)
             // the group's files take their names when the group is complete, and only after every one of them is closed
             for (PartFile &f : to.per_sample) f.close("cannot write the output");
             for (PartFile &f : to.per_sample) f.finish();
-            dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
-            s0 += g;
+            if (mode == WHOLE) dev.check(mg_cohort_end(dev.ctx), "mg_cohort_end");
+            return g;
+        }; // run_group
+        for (size_t s0 = 0; s0 < samples.size();) s0 += run_group(s0, WHOLE);
+        if (prior_split) {
+            {
+                Timed t("cohort: estimate pass");
+                std::vector<std::string> paths;
+                for (const PartFile &f : prior_cov_files) paths.push_back(f.path);
+                prior_freq_file.open(prior_base + ".freq.part", PartFile::SCRATCH);
+                walk_prior_groups(paths, group_planes, prior_range_bytes(),
+                                  [&](size_t nr, size_t planes, const uint32_t *cov, const float *f0, const uint32_t *var_allele_off, float *f_t, uint32_t *n_inf) {
+                                      dev.check(mg_estimate_priors(dev.ctx, nr, (uint32_t)planes, cov, f0, var_allele_off, o.error_rate, (int)o.max_coverage, o.haploid,
+                                                                   o.priors.iters, o.priors.weight, f_t, n_inf),
+                                                "mg_estimate_priors");
+                                      float ms = 0;
+                                      dev.check(mg_estimate_priors_stats(dev.ctx, &ms), "mg_estimate_priors_stats");
+                                      estimate_ms += ms;
+                                      ++estimate_calls;
+                                  },
+                                  [&](const std::string &bytes) { prior_freq_file.write(bytes, "cannot write the cohort's priors"); });
+                prior_freq_file.close("cannot write the cohort's priors");
+            }
+            for (size_t s0 = 0; s0 < samples.size();) s0 += run_group(s0, OUTPUT);
         }
         if (!o.merged.empty() && !merged_direct) { // the groups' blocks pasted record by record (host/cohort_out.hpp)
             Timed t("cohort: merged paste");
@@ -1894,6 +2005,10 @@ int call_main(const Options &o)
         if (g_timers.on && prior_calls) {
             g_timers.add("cohort priors: kernel (device)", prior_ms / 1000.0);
             fprintf(stderr, "[malva-geno] cohort-priors: %zu mg_genotype_cohort, device ms per call: %.3f\n", prior_calls, prior_ms / prior_calls);
+        }
+        if (g_timers.on && estimate_calls) {
+            g_timers.add("cohort priors: estimate kernel (device)", estimate_ms / 1000.0);
+            fprintf(stderr, "[malva-geno] cohort-priors: %zu mg_estimate_priors, device ms per call: %.3f\n", estimate_calls, estimate_ms / estimate_calls);
         }
         if (bcf_calls && g_timers.on) {
             g_timers.add("merged: encode kernels (device)", (bcf_ms[0] + bcf_ms[1] + bcf_ms[2]) / 1000.0);
