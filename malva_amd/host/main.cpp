@@ -6,6 +6,7 @@
 // libmalva_hip.so through include/malva_hip.h.  There is no CPU implementation of
 // those in this program: without a GPU it stops at mg_create.
 #include <fcntl.h>
+#include <functional>
 #include <future>
 #include <getopt.h>
 #include <sys/mman.h>
@@ -31,10 +32,7 @@
 #include "bcf_out.hpp"
 #include "cohort_priors.hpp"
 #include "cohort_out.hpp"
-#include "call_text.hpp"
-extern "C" {
-#include "malva_hip.h"
-}
+#include "call_worker.hpp"
 
 using namespace malva;
 
@@ -146,30 +144,6 @@ const char *USAGE =
     "  published layouts and checked against an independent second implementation only: no file written by KMC, bcftools or the\n"
     "  reference binary was available to this build (formats UNPINNED).  When in doubt convert: `kmc_tools transform <db> dump`,\n"
     "  `bcftools view -Ov`, and let this build write its own index.\n";
-
-struct Options { // argument_parser.hpp:51-66
-    unsigned k = 35, ref_k = 43;
-    float error_rate = 0.001f;
-    std::string samples = "-", freq_key = "AF";
-    unsigned max_coverage = 200;
-    uint64_t bf_size = 1ULL << 35;
-    bool strip_chr = false, uniform = false, verbose = false, haploid = false;
-    int device = 0, gpus = 1;
-    uint32_t min_count = 2, max_count = 255; // READS: KMC's -ci / -cs defaults (MALVA:107)
-    std::string fasta_path, vcf_path, kmc_path;
-    bool cohort = false;    // kmc_path is a manifest (host/cohort.hpp)
-    std::string out_dir;    // -o
-    int cohort_group = 0;   // 0: as many as fit, at most 64
-    std::string merged;     // --merged: the multi-sample VCF ("-": stdout)
-    bool use_min_gq = false; // --min-gq: cells of the merged output below it print a missing genotype
-    int32_t min_gq = 0;
-    bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
-    std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
-    bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
-    std::string pairs;      // --pairs: the table of pairwise genotype sharing
-    std::string sample_stats; // --sample-stats: the per-sample QC table
-    PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
-};
 
 bool parse_arguments(int argc, char **argv, Options &o)
 {
@@ -360,33 +334,6 @@ bool parse_arguments(int argc, char **argv, Options &o)
     return true;
 }
 
-// MALVA_GENO_TIMERS=1: where the host threads spend their time, summed per label, printed at exit (profiles/*cli*)
-struct Timers {
-    bool on = getenv("MALVA_GENO_TIMERS") != nullptr;
-    std::mutex mu;
-    std::map<std::string, double> acc;
-    void add(const char *what, double s)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        acc[what] += s;
-    }
-    ~Timers()
-    {
-        if (!on) return;
-        for (const auto &kv : acc) fprintf(stderr, "[malva-geno/timer] %-28s %.3fs\n", kv.first.c_str(), kv.second);
-    }
-};
-Timers g_timers;
-struct Timed {
-    const char *what;
-    std::chrono::steady_clock::time_point t0;
-    explicit Timed(const char *w) : what(w), t0(std::chrono::steady_clock::now()) {}
-    ~Timed()
-    {
-        if (g_timers.on) g_timers.add(what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    }
-};
-
 // pelapsed(), main.cpp:93-115
 auto t_start = std::chrono::steady_clock::now();
 auto t_last = t_start;
@@ -402,28 +349,6 @@ void pelapsed(const std::string &s, bool rollback = false)
              ru.ru_utime.tv_sec + ru.ru_utime.tv_usec * 1e-6, s.c_str(), ru.ru_maxrss / 1024);
     std::cerr << buf << (rollback ? "\r" : "\n");
     t_last = now;
-}
-
-struct Device {
-    mg_ctx *ctx = nullptr;
-    std::mutex mu; // calls on one context are serialised by the caller (include/malva_hip.h): held by whoever drives the context from a second thread
-    ~Device() { mg_destroy(ctx); }
-    void check(int rc, const char *what)
-    {
-        if (rc != MG_OK) throw std::runtime_error(std::string(what) + ": " + mg_last_error(ctx));
-    }
-};
-
-// A call that fills `buf` and says in *need what it takes (mg_format_calls, mg_format_site_info, mg_encode_calls_bcf): made again with
-// the buffer grown while it answers MG_ERR_LIMIT with a larger need -> its last return code
-template <class Call> int call_grown(std::vector<char> &buf, Call call)
-{
-    for (;;) {
-        uint64_t need = 0;
-        const int rc = call(&need);
-        if (rc != MG_ERR_LIMIT || need <= buf.size()) return rc;
-        buf.resize(need);
-    }
 }
 
 // main.cpp:407 / :456: <vcf>.c<ref_k>.k<k>.malvax + ".zst" (the reference's container) or ".hipz" (this build's compact one)
@@ -497,25 +422,6 @@ inline void decode_deferred(std::vector<Variant> &kept, Device &dev, VcfReader &
         }
         a = b;
     }
-}
-// v.genotypes / v.phasing of a deferred record, for the host enumerator (a block the device handed back, dump-kmers' cousin paths)
-inline void genotypes_from_entries(Variant &v)
-{
-    if (!v.gt_deferred) return;
-    const auto pair_of = [](uint16_t w) { return std::make_pair((int)(w & 127), (int)((w >> 7) & 127)); };
-    v.genotypes.assign(v.n_kept, pair_of(v.sp_default));
-    v.phasing.assign(v.n_kept, (uint8_t)((v.sp_default >> 14) & 1));
-    for (size_t e = 0; e < v.sp_sample.size(); ++e) {
-        v.genotypes[v.sp_sample[e]] = pair_of(v.sp_gt[e]);
-        v.phasing[v.sp_sample[e]] = (uint8_t)((v.sp_gt[e] >> 14) & 1);
-    }
-    v.gt_deferred = false;
-    v.sp_sample.clear();
-    v.sp_gt.clear();
-}
-inline void genotypes_from_entries(Block &b)
-{
-    for (Variant &v : b.vars) genotypes_from_entries(v);
 }
 
 // The record loop shared by index_main (main.cpp:309-370) and call_main (:522-579).  on_block(block, reference
@@ -1378,34 +1284,12 @@ int call_main(const Options &o)
         Timed t("startup: reference upload");
         on_all_devices(devs, [&](Device &d, size_t) { d.check(mg_reference_upload(d.ctx, all.data(), all.size()), "mg_reference_upload"); });
     }
-    std::atomic<size_t> gt_bytes_uploaded{0}; // panel genotypes handed to mg_cover_blocks[_sparse], all batches
-    double format_ms[3] = {0, 0, 0};          // --merged: device milliseconds of the mg_format_calls (length pass, scan, write pass; one worker at a time)
-    size_t format_calls = 0;
-    double site_ms[2] = {0, 0};               // --site-tags: device milliseconds of the mg_site_counts and of the mg_format_site_info
-    size_t site_calls[2] = {0, 0};
-    // --pairs: a group's pair table so far -- [planes][planes][9], summed batch by batch (mg_pair_counts, B = A) -- and, when the cohort runs
-    // as several groups, the file that receives the packed words of the group's batches for the pass over pairs of groups
-    struct PairsRun {
-        std::vector<uint64_t> counts;
-        PartFile *pack_out = nullptr;
-    };
-    double pairs_ms[2] = {0, 0};              // device milliseconds of the mg_pack_dosage and of the mg_pair_counts
-    size_t pairs_calls[2] = {0, 0};
+    CallTimes times;                          // the batch calls' device time, all passes (the workers' batch by batch, added as their text is taken)
     const bool want_sample = !o.sample_stats.empty(); // --sample-stats: the batches carry their alleles' classes
-    double sample_ms = 0;                     // device milliseconds of the mg_sample_counts
-    size_t sample_calls = 0;
-    double prior_ms = 0;                      // --cohort-priors: device milliseconds of the mg_genotype_cohort
-    size_t prior_calls = 0;
-    double estimate_ms = 0;                   // --prior-groups: device milliseconds of the mg_estimate_priors
-    size_t estimate_calls = 0;
     PriorsFile priors_file;                   // --priors-out
-    // --merged-format bcf | ubcf: the merged file as BCF2 (host/bcf_out.hpp), a record's per-sample block encoded by mg_encode_calls_bcf
-    const bool bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", bcf_bgzf = o.merged_format == "bcf";
-    BcfHeader bcf_hdr;
-    bool bcf_direct = false;                  // the cohort runs as one group: whole records leave the workers
-    size_t bcf_samples = 0;                   // the cohort's samples
-    double bcf_ms[3] = {0, 0, 0};             // device milliseconds of the mg_encode_calls_bcf (length pass, scan, write pass)
-    size_t bcf_calls = 0;
+    MergedFormat merged_fmt;                  // --merged-format bcf | ubcf
+    merged_fmt.bcf_out = !o.merged.empty() && !o.merged_format.empty() && o.merged_format != "vcf", merged_fmt.bcf_bgzf = o.merged_format == "bcf";
+    const bool bcf_out = merged_fmt.bcf_out, bcf_bgzf = merged_fmt.bcf_bgzf;
     std::string header_text;
     {
         VcfReader hdr(o.vcf_path, "-");
@@ -1425,336 +1309,18 @@ int call_main(const Options &o)
     }
     pelapsed("VCF parsing and genotyping");
 
-    // --site-tags: the INFO strings of n records from their counts (mg_format_site_info), whoever holds the device
-    auto site_info = [&](Device &dev, size_t n, const uint32_t *ac, const uint32_t *ns, const uint32_t *var_allele_off, std::vector<char> &text,
-                         std::vector<uint64_t> &off) {
-        off.resize(n + 1);
-        text.resize(n * 40); // (a guess: the call says what it needs)
-        dev.check(call_grown(text, [&](uint64_t *need) { return mg_format_site_info(dev.ctx, n, ac, ns, var_allele_off, text.data(), text.size(), off.data(), need); }),
-                  "mg_format_site_info");
-        float ms[2] = {0, 0};
-        dev.check(mg_site_stats(dev.ctx, ms), "mg_site_stats");
-        site_ms[1] += ms[1];
-        ++site_calls[1];
-    };
-
-    // Where one pass over the panel leaves what it makes; a member that is not set: the pass does not make it.
-    struct PassOut {
-        std::deque<PartFile> per_sample; // sample p's text goes to per_sample[p] (empty: no per-sample text); they go with this object
-        // --merged: the group's block of the multi-sample VCF -- a record's sample columns come as text from the device (mg_format_calls), behind
-        // the record's fixed columns when merged_fixed, else on their own (a later group's columns, pasted behind the first group's lines at the end)
-        PartFile *merged = nullptr;
-        bool merged_fixed = false;
-        // --site-tags: the records' allele counts over the group's planes are made beside the columns (mg_site_counts); not set: the group is the
-        // cohort and INFO is made from them at once (mg_format_site_info), else they go here (put_site_counts) for the paste pass to sum over the groups
-        PartFile *site_counts = nullptr;
-        // --pairs: every batch's cells are packed into dosage bit planes (mg_pack_dosage) while the batch is in hand and counted against themselves
-        // into pairs->counts; pairs->pack_out, when set, receives per batch and stream -- the lone records', then the others' -- the words (put_pack_batch)
-        PairsRun *pairs = nullptr;
-        // --sample-stats: the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand (mg_sample_counts, accumulate)
-        uint64_t *sample_table = nullptr;
-        // --prior-groups, a cohort in several groups (host/cohort_priors.hpp).  prior_cov: the coverage pass -- the batches' coverages go here
-        // (put_cov_batch; the first group's with the records' offsets and panel priors), and the pass makes no calls and nothing else.
-        // prior_in: the output pass -- the batches' coverages and the cohort's frequencies come from here instead of the counters, and the
-        // cells are genotyped under them by mg_genotype_cohort(iters = 0)
-        PartFile *prior_cov = nullptr;
-        bool prior_cov_panel = false;
-        PriorGroupInput *prior_in = nullptr;
-    };
-    struct BatchText { // the text of one batch, as its worker hands it over
-        std::vector<std::string> per_sample;
-        std::string merged, site_counts, pack, priors, prior_cov; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
-    };
-    // One pass over the panel.  planes = 0: the one sample whose counters the context holds, text to to.per_sample[0] (stdout).  planes > 0:
-    // the context is in cohort mode; every batch goes up once and is covered for all planes, a record's fixed columns are made once and
-    // only the INFO and GT:GQ fields per sample.
-    // --cohort-priors: a batch's coverages are made as always; its frequencies are then re-estimated over all planes and every plane genotyped
-    // under them by ONE mg_genotype_cohort per batch kind, whose arrays everything below reads; priors_file, when open, gets a line per record.
-    // --prior-groups with a cohort in several groups: the pass runs twice per group -- to.prior_cov: up to the coverages, which it writes and
-    // nothing else; to.prior_in: coverages and the cohort's frequencies read back, the cells genotyped under them, everything below as always.
+    // One pass over the panel (host/call_worker.hpp): the record loop here cuts the blocks and closes the batches, the pass takes them from there
     auto vcf_pass = [&](VcfReader &vcf, const uint32_t planes, PassOut &to) -> size_t {
-    std::deque<PartFile> &outs = to.per_sample;
-    PartFile *const merged_out = to.merged, *const cnt_out = to.site_counts;
-    const bool merged_fixed = to.merged_fixed;
-    PairsRun *const pairs = to.pairs;
-    uint64_t *const sample_table = to.sample_table;
-    PartFile *const prior_cov = to.prior_cov;
-    PriorGroupInput *const prior_in = to.prior_in;
-    const size_t P = planes ? planes : 1;
-
-    const bool want_probs = o.verbose || o.gp; // the likelihood lists: GTS= of -v, GP of --merged --gp
-
-    // One batch: device round trips, then the records' text.  Runs on a worker thread while this thread parses the
-    // next batch (the ABI has no thread affinity); batches are handed over one at a time, so output order is kept.
-    struct Job {
-        std::vector<Rec> recs;
-        Batch iso, gen;
-        size_t device = 0; // batches go round the devices: after the exchange every one of them holds the whole table's counters
+        const bool iso_path = getenv("MALVA_GENO_ISO_PATH") && atoi(getenv("MALVA_GENO_ISO_PATH")) != 0;
+        const BatchRules rules{o.k, o.haploid, vcf.keep.size() <= SPARSE_GT_SAMPLES && !vcf.defer_genotypes, vcf.keep.size(), iso_path, getenv("MALVA_GENO_HOST_ENUM") != nullptr,
+                               want_sample, geno_batch_records(200000)};
+        PanelPass pass(devs, o, planes, to, vcf.keep.size(), merged_fmt, priors_file, times);
+        BatchBuilder<std::reference_wrapper<PanelPass>> batches(rules, contig_base, std::ref(pass)); // (which records a batch keeps, when it closes: host/panel_batch.hpp)
+        const size_t n = for_each_block(vcf, o, refs, false, nullptr, std::ref(batches), &devs[0]);
+        batches.flush();
+        pass.finish();
+        return n;
     };
-    auto process = [&](Job &job) -> BatchText {
-        std::vector<Rec> &recs = job.recs;
-        Batch &iso = job.iso, &gen = job.gen;
-        Device &dev = devs[job.device];
-        Timed *t_dev = new Timed("worker: device calls");
-        std::unique_lock<std::mutex> device_lock(dev.mu); // (the parsing thread cuts blocks on device 0 meanwhile)
-        if (iso.n()) {
-            const size_t n = iso.n(), na = iso.var_allele_off.back(), ng = want_probs ? iso.var_gt_off.back() : 0;
-            iso.cov.resize(P * na); iso.g1.resize(P * n); iso.g2.resize(P * n); iso.gq.resize(P * n); iso.status.resize(P * n);
-            iso.probs.resize(P * ng);
-            for (size_t pl = 0; pl < P && !prior_in; ++pl) { // (the fused lone-variant call reads the selected plane)
-                if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
-                dev.check(mg_call_isolated(dev.ctx, n, iso.pos.data(), iso.var_allele_off.data(), iso.allele_off.data(), iso.pool.data(), iso.pool.size(),
-                                           iso.freq.data(), iso.present.data(), iso.flags.data(), o.error_rate, (int)o.max_coverage, o.haploid, iso.cov.data() + pl * na,
-                                           iso.g1.data() + pl * n, iso.g2.data() + pl * n, iso.gq.data() + pl * n, iso.status.data() + pl * n,
-                                           want_probs ? iso.probs.data() + pl * ng : nullptr, want_probs ? iso.var_gt_off.data() : nullptr),
-                          "mg_call_isolated");
-            }
-        }
-        auto cohort_priors = [&](Batch &b) { // the batch's priors from all of its planes, and the planes' calls under them
-            Timed t_prior("worker: cohort priors (mg_genotype_cohort)");
-            const size_t n = b.n(), ng = want_probs ? b.var_gt_off.back() : 0;
-            b.freq_out.resize(b.freq.size());
-            b.n_inf.resize(n);
-            b.probs.resize(P * ng);
-            // the output pass of a cohort in several groups: freq_out and n_inf hold the cohort's estimate; the cells under it, nothing re-estimated
-            const std::vector<float> f_t = prior_in ? b.freq_out : std::vector<float>();
-            std::vector<uint32_t> no_n(prior_in ? n : 0);
-            dev.check(mg_genotype_cohort(dev.ctx, n, (uint32_t)P, b.cov.data(), prior_in ? f_t.data() : b.freq.data(), b.var_allele_off.data(), o.error_rate,
-                                         (int)o.max_coverage, o.haploid, prior_in ? 0 : o.priors.iters, o.priors.weight, b.freq_out.data(),
-                                         prior_in ? no_n.data() : b.n_inf.data(), b.g1.data(), b.g2.data(), b.gq.data(), b.status.data(),
-                                         want_probs ? b.probs.data() : nullptr, want_probs ? b.var_gt_off.data() : nullptr),
-                      "mg_genotype_cohort");
-            float ms = 0;
-            dev.check(mg_cohort_prior_stats(dev.ctx, &ms), "mg_cohort_prior_stats");
-            prior_ms += ms;
-            ++prior_calls;
-        };
-        if (iso.n() && o.priors.on && !prior_cov) cohort_priors(iso); // (mg_call_isolated made the coverages; its calls are replaced)
-        if (gen.n()) {
-            const size_t n = gen.n(), na = gen.var_allele_off.back(), ng = want_probs ? gen.var_gt_off.back() : 0;
-            gen.cov.resize(P * na); gen.g1.resize(P * n); gen.g2.resize(P * n); gen.gq.resize(P * n); gen.status.resize(P * n);
-            gen.probs.resize(P * ng);
-            if (!prior_in) { // (the output pass of a cohort in several groups has the coverages from the group's file)
-                // panel genotypes of the batch as one [variant][sample] matrix of a1 | a2 << 7 | phased << 14
-                const uint32_t n_samples = (uint32_t)vcf.keep.size();
-                std::vector<uint8_t> overflow(n, 0);
-                bool device_ok = o.k <= MG_MAX_PACKED_K && !getenv("MALVA_GENO_HOST_ENUM"); // the variable forces the host enumerator (tests)
-                if (gen.wide_alleles) device_ok = false;
-                const size_t n_blocks = gen.n_blocks();
-                PanelGenotypes pg;
-                if (gen.dense_gt) pg.gt = std::move(gen.gt_dense);
-                else pg = pack_genotypes(gen.vars, n, n_samples, o.haploid); // (every record of such a batch is kept)
-                gt_bytes_uploaded += pg.bytes();
-                if (device_ok && planes) // the batch goes up once and is covered for every plane (cov: [planes][na])
-                    dev.check(mg_cover_blocks_cohort(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                                     gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                                     gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sparse ? nullptr : pg.gt.data(),
-                                                     pg.sparse ? pg.sp_off.data() : nullptr, pg.sparse ? pg.sp_sample.data() : nullptr,
-                                                     pg.sparse ? pg.sp_gt.data() : nullptr, pg.sparse ? pg.sp_default : (uint16_t)0, n_samples, o.haploid, gen.cov.data(),
-                                                     overflow.data()),
-                              "mg_cover_blocks_cohort");
-                else if (device_ok && pg.sparse)
-                    dev.check(mg_cover_blocks_sparse(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                                     gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                                     gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sp_off.data(), pg.sp_sample.data(),
-                                                     pg.sp_gt.data(), pg.sp_default, n_samples, o.haploid, gen.cov.data(), overflow.data()),
-                              "mg_cover_blocks_sparse"); // extract_kmers + set_coverages, main.cpp:556-557
-                else if (device_ok)
-                    dev.check(mg_cover_blocks(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                              gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                              gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.gt.data(), n_samples, o.haploid,
-                                              gen.cov.data(), overflow.data()),
-                              "mg_cover_blocks"); // extract_kmers + set_coverages, main.cpp:556-557
-                else
-                    std::fill(overflow.begin(), overflow.end(), 1);
-                // blocks the device handed back (a capacity was exceeded, or a window was clipped by a contig end):
-                // host enumerator + mg_lookup_cover for exactly those blocks
-                size_t n_fallback = 0;
-                for (size_t b = 0; b < n_blocks; ++b) {
-                    bool redo = false;
-                    for (uint32_t v = gen.blk_var_off[b]; v < gen.blk_var_off[b + 1]; ++v) redo = redo || overflow[v];
-                    if (!redo) continue;
-                    ++n_fallback;
-                    Block blk((int)o.k); // (rebuilt from the batch's records: nothing reads them after this)
-                    for (uint32_t v = gen.blk_var_off[b]; v < gen.blk_var_off[b + 1]; ++v) {
-                        if (gen.var_slot[v] < 0) throw std::runtime_error("internal: the device handed back a record tier 1 should have taken");
-                        blk.add(std::move(gen.vars[(size_t)gen.var_slot[v]]));
-                    }
-                    genotypes_from_entries(blk);
-                    const SignatureRows s = signature_rows(blk, blk.extract(*gen.block_ref[b], o.haploid));
-                    const size_t slot0 = gen.var_allele_off[gen.blk_var_off[b]];
-                    for (size_t pl = 0; pl < P; ++pl) { // (enumerated once; the lookups read the selected plane)
-                        if (planes) dev.check(mg_cohort_select(dev.ctx, (uint32_t)pl), "mg_cohort_select");
-                        dev.check(mg_lookup_cover(dev.ctx, s.rows.data.data(), STRIDE, s.rows.n, s.is_ref.data(), s.sig_off.data(), s.sig_off.size() - 1, s.al_off.data(),
-                                                  s.al_off.size() - 1, gen.cov.data() + pl * na + slot0),
-                                  "mg_lookup_cover");
-                    }
-                }
-                if (n_fallback) std::cerr << "[malva-geno] " << n_fallback << " block(s) enumerated on the host" << std::endl;
-            }
-            if (prior_cov) {} // (the coverage pass makes no calls)
-            else if (o.priors.on) cohort_priors(gen);
-            else
-            for (size_t pl = 0; pl < P; ++pl)
-                dev.check(mg_genotype(dev.ctx, gen.cov.data() + pl * na, gen.freq.data(), gen.var_allele_off.data(), n, o.error_rate, (int)o.max_coverage, o.haploid,
-                                      gen.g1.data() + pl * n, gen.g2.data() + pl * n, gen.gq.data() + pl * n, gen.status.data() + pl * n,
-                                      want_probs ? gen.probs.data() + pl * ng : nullptr, want_probs ? gen.var_gt_off.data() : nullptr),
-                          "mg_genotype"); // vb.genotype + the GT/GQ part of output_variants, main.cpp:558-559
-        }
-        if (prior_cov) { // the coverage pass: the batches' coverages for the estimate pass, and nothing else
-            BatchText text;
-            for (int w = 0; w < 2; ++w) {
-                const Batch &b = w ? gen : iso;
-                if (b.n()) put_cov_batch(text.prior_cov, (uint64_t)w, b.n(), b.var_allele_off.data(), b.freq.data(), to.prior_cov_panel, P, b.cov.data());
-            }
-            device_lock.unlock();
-            delete t_dev;
-            return text;
-        }
-        // --merged: the sample columns of both batches as text, made where the genotypes were
-        std::vector<char> row_text[2], info_text[2];
-        std::vector<uint64_t> row_off[2], info_off[2];
-        std::vector<uint32_t> site_ac[2], site_ns[2];
-        const bool tags = merged_out && o.site_tags;
-        if (merged_out) {
-            Timed t_fmt(bcf_out ? "worker: merged rows (mg_encode_calls_bcf)" : "worker: merged rows (mg_format_calls)");
-            for (int w = 0; w < 2; ++w) {
-                Batch &b = w ? gen : iso;
-                const size_t bn = b.n();
-                if (!bn) continue;
-                row_off[w].resize(bn + 1);
-                row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0) +
-                                   (o.gp ? P * (bn + (bcf_out ? 4 : 9) * (size_t)b.var_gt_off.back()) : 0)); // (a guess: the call says what it needs)
-                const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose || o.gp ? b.var_allele_off.data() : nullptr;
-                dev.check(call_grown(row_text[w], [&](uint64_t *need) {
-                    if (o.gp)
-                        return bcf_out ? mg_encode_calls_bcf_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
-                                                                b.probs.data(), b.var_gt_off.data(), b.status.data(), bcf_hdr.key("GT"), bcf_hdr.key("GQ"),
-                                                                o.verbose ? bcf_hdr.key("COVS") : 0, bcf_hdr.key("GP"), (uint8_t *)row_text[w].data(), row_text[w].size(),
-                                                                row_off[w].data(), need)
-                                       : mg_format_calls_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
-                                                            b.probs.data(), b.var_gt_off.data(), b.status.data(), row_text[w].data(), row_text[w].size(), row_off[w].data(),
-                                                            need);
-                    return bcf_out ? mg_encode_calls_bcf(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
-                                                         bcf_hdr.key("GT"), bcf_hdr.key("GQ"), o.verbose ? bcf_hdr.key("COVS") : 0,
-                                                         (uint8_t *)row_text[w].data(), row_text[w].size(), row_off[w].data(), need)
-                           : o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao,
-                                                                 row_text[w].data(), row_text[w].size(), row_off[w].data(), need)
-                                        : mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), cov, vao,
-                                                          row_text[w].data(), row_text[w].size(), row_off[w].data(), need);
-                }), bcf_out ? "mg_encode_calls_bcf" : "mg_format_calls");
-                float ms[3] = {0, 0, 0};
-                if (bcf_out) {
-                    dev.check(mg_bcf_stats(dev.ctx, ms), "mg_bcf_stats");
-                    for (int i = 0; i < 3; ++i) bcf_ms[i] += ms[i];
-                    ++bcf_calls;
-                } else {
-                    dev.check(mg_format_stats(dev.ctx, ms), "mg_format_stats");
-                    for (int i = 0; i < 3; ++i) format_ms[i] += ms[i];
-                    ++format_calls;
-                }
-                if (!tags) continue;
-                site_ac[w].resize(b.var_allele_off.back());
-                site_ns[w].resize(bn);
-                dev.check(mg_site_counts(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.var_allele_off.data(), 0,
-                                         site_ac[w].data(), site_ns[w].data()),
-                          "mg_site_counts");
-                dev.check(mg_site_stats(dev.ctx, ms), "mg_site_stats");
-                site_ms[0] += ms[0];
-                ++site_calls[0];
-                if (!cnt_out && !bcf_out) site_info(dev, bn, site_ac[w].data(), site_ns[w].data(), b.var_allele_off.data(), info_text[w], info_off[w]);
-            }
-        }
-        std::string pack_bytes;
-        if (pairs) {
-            Timed t_pairs("worker: pair table (mg_pack_dosage, mg_pair_counts)");
-            std::vector<uint64_t> words;
-            for (int w = 0; w < 2; ++w) {
-                Batch &b = w ? gen : iso;
-                const size_t bn = b.n(), W = (bn + 63) / 64;
-                if (!bn) continue;
-                words.resize(P * 3 * W);
-                dev.check(mg_pack_dosage(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.var_allele_off.data(),
-                                         words.data()),
-                          "mg_pack_dosage");
-                dev.check(mg_pair_counts(dev.ctx, W, words.data(), (uint32_t)P, nullptr, (uint32_t)P, 1, pairs->counts.data()), "mg_pair_counts");
-                float ms[2] = {0, 0};
-                dev.check(mg_pairs_stats(dev.ctx, ms), "mg_pairs_stats");
-                for (int i = 0; i < 2; ++i) pairs_ms[i] += ms[i], ++pairs_calls[i];
-                if (pairs->pack_out) put_pack_batch(pack_bytes, (uint64_t)w, bn, words);
-            }
-        }
-        if (sample_table) {
-            Timed t_sample("worker: sample table (mg_sample_counts)");
-            for (int w = 0; w < 2; ++w) {
-                Batch &b = w ? gen : iso;
-                const size_t bn = b.n();
-                if (!bn) continue;
-                dev.check(mg_sample_counts(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.status.data(), b.cov.data(),
-                                           b.var_allele_off.data(), b.allele_class.data(), 1, sample_table),
-                          "mg_sample_counts");
-                float ms = 0;
-                dev.check(mg_sample_stats(dev.ctx, &ms), "mg_sample_stats");
-                sample_ms += ms;
-                ++sample_calls;
-            }
-        }
-        device_lock.unlock(); // the records' text needs no device
-        delete t_dev;
-        Timed t_text("worker: records' text");
-        BatchText text;
-        text.per_sample.resize(outs.size());
-        text.pack = std::move(pack_bytes);
-        for (const Rec &r : recs) {
-            const Batch &b = r.isolated ? iso : gen;
-            const int w = r.isolated ? 0 : 1;
-            if (priors_file.f) priors_row(text.priors, r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
-            if (tags && cnt_out) put_site_counts(text.site_counts, r.n_alleles, site_ns[w][r.slot], site_ac[w].data() + r.allele0);
-        }
-        if (merged_out && bcf_out)
-            merged_bcf_records(text.merged, recs, row_text, row_off, site_ac, site_ns, bcf_hdr, (o.verbose ? 3 : 2) + (o.gp ? 1 : 0), (uint32_t)P, merged_fixed, bcf_direct, tags, bcf_bgzf);
-        else if (merged_out) merged_text_lines(text.merged, recs, row_text, row_off, info_text, info_off, o.verbose, o.gp, merged_fixed, tags && !cnt_out); // (INFO stays '.' in a block: the paste pass puts it in)
-        if (!outs.empty()) per_sample_lines(text.per_sample, recs, iso, gen, P, o.haploid, o.verbose, o.max_coverage);
-        return text;
-    };
-    // as many batches in flight as there are devices; their text leaves in submission order
-    std::deque<std::future<BatchText>> in_flight;
-    size_t jobs_started = 0;
-    auto drain = [&](size_t keep) {
-        Timed t_drain("main: wait for worker + write");
-        while (in_flight.size() > keep) {
-            const BatchText text = in_flight.front().get(); // (or the batch's exception comes back here)
-            in_flight.pop_front();
-            for (size_t pl = 0; pl < outs.size(); ++pl) outs[pl].write(text.per_sample[pl], "cannot write the output");
-            if (merged_out) merged_out->write(text.merged, "cannot write the merged output");
-            if (cnt_out) cnt_out->write(text.site_counts, "cannot write the merged output's counts");
-            if (pairs && pairs->pack_out) pairs->pack_out->write(text.pack, "cannot write the pair table's packed calls");
-            priors_file.write(text.priors);
-            if (prior_cov) prior_cov->write(text.prior_cov, "cannot write the coverages for the cohort's priors");
-        }
-    };
-    auto run_and_print = [&](std::vector<Rec> &&recs, Batch &&iso, Batch &&gen) {
-        drain(devs.size() - 1);
-        if (prior_in) // (read here, on the one thread that hands the batches over: the streams keep the batches' order)
-            for (Batch *b : {&iso, &gen})
-                if (b->n()) prior_in->next(b == &gen, b->n(), b->var_allele_off.back(), b->cov, b->freq_out, b->n_inf);
-        auto job = std::make_shared<Job>(Job{std::move(recs), std::move(iso), std::move(gen), jobs_started++ % devs.size()});
-        in_flight.push_back(std::async(std::launch::async, [&process, job]() { return process(*job); }));
-    };
-    const bool iso_path = getenv("MALVA_GENO_ISO_PATH") && atoi(getenv("MALVA_GENO_ISO_PATH")) != 0;
-    const BatchRules rules{o.k, o.haploid, vcf.keep.size() <= SPARSE_GT_SAMPLES && !vcf.defer_genotypes, vcf.keep.size(), iso_path, getenv("MALVA_GENO_HOST_ENUM") != nullptr,
-                           want_sample, geno_batch_records(200000)};
-    BatchBuilder<decltype(run_and_print)> batches(rules, contig_base, run_and_print); // (which records a batch keeps, when it closes: host/panel_batch.hpp)
-    const size_t n = for_each_block(vcf, o, refs, false, nullptr,
-                                    [&](Block &vb, const std::string &seq_name, const std::string &reference) { batches.add_block(vb, seq_name, reference); }, &devs[0]);
-    batches.flush();
-    drain(0);
-    if (prior_in) prior_in->done();
-    for (PartFile &f : outs) fflush(f.f);
-    if (merged_out) fflush(merged_out->f);
-    if (cnt_out) fflush(cnt_out->f);
-    return n;
-    }; // vcf_pass
 
     size_t n = 0;
     if (!o.cohort) {
@@ -1802,11 +1368,11 @@ int call_main(const Options &o)
             if (!hdr.ok()) throw std::runtime_error(hdr.error);
             if (bcf_out) { // the text header with a ##contig line per reference sequence where the panel's header has none
                 const bool declared = bcf_has_contig_lines(hdr.header_lines);
-                bcf_hdr = bcf_parse_header(merged_header(hdr.header_lines, o.verbose, names, o.site_tags,
+                merged_fmt.bcf_hdr = bcf_parse_header(merged_header(hdr.header_lines, o.verbose, names, o.site_tags,
                                                          declared ? std::vector<std::string>() : bcf_contig_lines(refs.names, refs.seqs), o.gp),
                                            declared);
-                bcf_samples = samples.size();
-                const std::string head = bcf_hdr.file_head();
+                merged_fmt.bcf_samples = samples.size();
+                const std::string head = merged_fmt.bcf_hdr.file_head();
                 if (bcf_bgzf) bgzf_append(head.data(), head.size(), merged_head);
                 else merged_head = head;
             } else
@@ -1895,7 +1461,7 @@ int call_main(const Options &o)
                 to.per_sample.back().write(header_text);
             }
             if (!o.merged.empty()) {
-                if (s0 == 0) bcf_direct = merged_direct = g == samples.size();
+                if (s0 == 0) merged_fmt.bcf_direct = merged_direct = g == samples.size();
                 to.merged = merged_direct ? &open_merged() : &open_scratch(merged_blocks, merged_tmp_base, bcf_out ? ".bcf.part" : ".part");
                 if (o.site_tags && !merged_direct) to.site_counts = &open_scratch(merged_counts, merged_tmp_base, ".cnt.part");
                 // (BCF in several groups: the header goes in front of the pasted records, the groups' files hold records alone)
@@ -1940,8 +1506,7 @@ int call_main(const Options &o)
                                                 "mg_estimate_priors");
                                       float ms = 0;
                                       dev.check(mg_estimate_priors_stats(dev.ctx, &ms), "mg_estimate_priors_stats");
-                                      estimate_ms += ms;
-                                      ++estimate_calls;
+                                      times.estimate.add(&ms, 1);
                                   },
                                   [&](const std::string &bytes) { prior_freq_file.write(bytes, "cannot write the cohort's priors"); });
                 prior_freq_file.close("cannot write the cohort's priors");
@@ -1957,14 +1522,14 @@ int call_main(const Options &o)
             auto sink = [&](const char *data, size_t n) { merged_file.write(data, n, "cannot write the merged output"); };
             if (bcf_out) {
                 sink(merged_head.data(), merged_head.size());
-                paste_bcf_groups(in.f, group_planes, (o.verbose ? 3 : 2) + (o.gp ? 1 : 0), (uint32_t)bcf_samples, bcf_hdr, o.site_tags ? &counts : nullptr, bcf_bgzf, sink);
+                paste_bcf_groups(in.f, group_planes, merged_fmt.n_fields(o), (uint32_t)merged_fmt.bcf_samples, merged_fmt.bcf_hdr, o.site_tags ? &counts : nullptr, bcf_bgzf, sink);
             } else {
                 // --site-tags: the groups' counts summed, 65,536 records at a time (MALVA_GENO_BATCH, when set: tests), and their INFO strings made on the device
                 const size_t paste_batch = geno_batch_records(65536);
                 std::vector<uint32_t> p_ac, p_ns, p_vao;
                 paste_text_groups(in.f, o.site_tags, [&](std::vector<char> &text, std::vector<uint64_t> &off) {
                     counts.next_batch(paste_batch, p_ac, p_ns, p_vao);
-                    site_info(dev, p_ns.size(), p_ac.data(), p_ns.data(), p_vao.data(), text, off);
+                    site_info(dev, p_ns.size(), p_ac.data(), p_ns.data(), p_vao.data(), text, off, times);
                 }, sink);
             }
             merged_file.close("cannot write the merged output");
@@ -1981,52 +1546,20 @@ int call_main(const Options &o)
                         dev.check(mg_pair_counts(dev.ctx, W, words_a, (uint32_t)ga, words_b, (uint32_t)gb, 1, cross.data()), "mg_pair_counts");
                         float ms[2] = {0, 0};
                         dev.check(mg_pairs_stats(dev.ctx, ms), "mg_pairs_stats");
-                        pairs_ms[1] += ms[1];
-                        ++pairs_calls[1];
+                        times.pairs.ms[1] += ms[1];
+                        ++times.pairs.calls[1];
                     });
                     for (size_t i = 0; i < ga; ++i)
                         std::copy_n(&cross[i * gb * 9], gb * 9, &pair_table[((group_first[gi] + i) * S + group_first[gj]) * 9]);
                 }
             PartFile::put(o.pairs, pair_table_text(names, pair_table.data()));
-            if (g_timers.on && pairs_calls[1]) {
-                g_timers.add("pairs: pack and count kernels (device)", (pairs_ms[0] + pairs_ms[1]) / 1000.0);
-                fprintf(stderr, "[malva-geno] pairs: %zu mg_pack_dosage, %zu mg_pair_counts, device ms per call: pack %.3f count %.3f\n", pairs_calls[0], pairs_calls[1],
-                        pairs_calls[0] ? pairs_ms[0] / pairs_calls[0] : 0.0, pairs_ms[1] / pairs_calls[1]);
-            }
         }
-        if (want_sample) {
-            PartFile::put(o.sample_stats, sample_table_text(names, sample_table.data()));
-            if (g_timers.on && sample_calls) {
-                g_timers.add("sample table: count kernel (device)", sample_ms / 1000.0);
-                fprintf(stderr, "[malva-geno] sample-stats: %zu mg_sample_counts, device ms per call: count %.3f\n", sample_calls, sample_ms / sample_calls);
-            }
-        }
+        if (want_sample) PartFile::put(o.sample_stats, sample_table_text(names, sample_table.data()));
         priors_file.finish();
-        if (g_timers.on && prior_calls) {
-            g_timers.add("cohort priors: kernel (device)", prior_ms / 1000.0);
-            fprintf(stderr, "[malva-geno] cohort-priors: %zu mg_genotype_cohort, device ms per call: %.3f\n", prior_calls, prior_ms / prior_calls);
-        }
-        if (g_timers.on && estimate_calls) {
-            g_timers.add("cohort priors: estimate kernel (device)", estimate_ms / 1000.0);
-            fprintf(stderr, "[malva-geno] cohort-priors: %zu mg_estimate_priors, device ms per call: %.3f\n", estimate_calls, estimate_ms / estimate_calls);
-        }
-        if (bcf_calls && g_timers.on) {
-            g_timers.add("merged: encode kernels (device)", (bcf_ms[0] + bcf_ms[1] + bcf_ms[2]) / 1000.0);
-            fprintf(stderr, "[malva-geno] merged: %zu mg_encode_calls_bcf, device ms per call: length %.3f scan %.3f write %.3f\n", bcf_calls, bcf_ms[0] / bcf_calls,
-                    bcf_ms[1] / bcf_calls, bcf_ms[2] / bcf_calls);
-            if (site_calls[0]) fprintf(stderr, "[malva-geno] merged: %zu mg_site_counts, device ms per call: count %.3f\n", site_calls[0], site_ms[0] / site_calls[0]);
-        }
-        if (format_calls) {
-            if (g_timers.on) g_timers.add("merged: format kernels (device)", (format_ms[0] + format_ms[1] + format_ms[2]) / 1000.0);
-            if (g_timers.on)
-                fprintf(stderr, "[malva-geno] merged: %zu mg_format_calls, device ms per call: length %.3f scan %.3f write %.3f\n", format_calls,
-                        format_ms[0] / format_calls, format_ms[1] / format_calls, format_ms[2] / format_calls);
-            if (g_timers.on && site_calls[0] && site_calls[1])
-                fprintf(stderr, "[malva-geno] merged: %zu mg_site_counts, %zu mg_format_site_info, device ms per call: count %.3f info %.3f\n", site_calls[0], site_calls[1],
-                        site_ms[0] / site_calls[0], site_ms[1] / site_calls[1]);
-        }
+        times.add_to_timers();
+        std::cerr << times.report();
     }
-    if (gt_bytes_uploaded) std::cerr << "[malva-geno] panel genotypes of the general blocks: " << gt_bytes_uploaded.load() << " bytes uploaded" << std::endl;
+    if (times.gt_bytes) std::cerr << "[malva-geno] panel genotypes of the general blocks: " << times.gt_bytes << " bytes uploaded" << std::endl;
     pelapsed("Processed " + std::to_string(n) + " variants");
     pelapsed("Execution completed");
     return 0;

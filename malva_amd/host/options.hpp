@@ -1,0 +1,34 @@
+// What the command line of malva-geno says, once parsed (parse_arguments, main.cpp)
+#pragma once
+#include <cstdint>
+#include <string>
+
+#include "cohort_priors.hpp"
+
+namespace malva {
+
+struct Options { // argument_parser.hpp:51-66
+    unsigned k = 35, ref_k = 43;
+    float error_rate = 0.001f;
+    std::string samples = "-", freq_key = "AF";
+    unsigned max_coverage = 200;
+    uint64_t bf_size = 1ULL << 35;
+    bool strip_chr = false, uniform = false, verbose = false, haploid = false;
+    int device = 0, gpus = 1;
+    uint32_t min_count = 2, max_count = 255; // READS: KMC's -ci / -cs defaults (MALVA:107)
+    std::string fasta_path, vcf_path, kmc_path;
+    bool cohort = false;    // kmc_path is a manifest (host/cohort.hpp)
+    std::string out_dir;    // -o
+    int cohort_group = 0;   // 0: as many as fit, at most 64
+    std::string merged;     // --merged: the multi-sample VCF ("-": stdout)
+    bool use_min_gq = false; // --min-gq: cells of the merged output below it print a missing genotype
+    int32_t min_gq = 0;
+    bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
+    std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
+    bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
+    std::string pairs;      // --pairs: the table of pairwise genotype sharing
+    std::string sample_stats; // --sample-stats: the per-sample QC table
+    PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
+};
+
+} // namespace malva

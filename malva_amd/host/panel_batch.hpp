@@ -201,6 +201,26 @@ struct BlockArrays : LoneArrays { // inputs of mg_index_blocks* / mg_cover_block
     void close_block() { blk_var_off.push_back((uint32_t)n()); }
 };
 
+// v.genotypes / v.phasing of a deferred record, for the host enumerator (a block the device handed back, dump-kmers' cousin paths)
+inline void genotypes_from_entries(Variant &v)
+{
+    if (!v.gt_deferred) return;
+    const auto pair_of = [](uint16_t w) { return std::make_pair((int)(w & 127), (int)((w >> 7) & 127)); };
+    v.genotypes.assign(v.n_kept, pair_of(v.sp_default));
+    v.phasing.assign(v.n_kept, (uint8_t)((v.sp_default >> 14) & 1));
+    for (size_t e = 0; e < v.sp_sample.size(); ++e) {
+        v.genotypes[v.sp_sample[e]] = pair_of(v.sp_gt[e]);
+        v.phasing[v.sp_sample[e]] = (uint8_t)((v.sp_gt[e] >> 14) & 1);
+    }
+    v.gt_deferred = false;
+    v.sp_sample.clear();
+    v.sp_gt.clear();
+}
+inline void genotypes_from_entries(Block &b)
+{
+    for (Variant &v : b.vars) genotypes_from_entries(v);
+}
+
 struct SignatureRows { Rows rows; std::vector<uint8_t> is_ref; std::vector<uint64_t> sig_off{0}, al_off{0}; }; // what mg_lookup_cover takes
 inline SignatureRows signature_rows(const Block &blk, const std::vector<AlleleSignatures> &sigs) // of a block the host enumerated (Block::extract)
 {
@@ -303,6 +323,7 @@ template <class Close> struct BatchBuilder {
         if (gen.dense_gt) gen.gt_dense.reserve(n * r.n_samples_kept);
     }
     void flush() { close(std::move(recs), std::move(iso), std::move(gen)), fresh(), recs.reserve(r.batch_records + 64); }
+    void operator()(Block &vb, const std::string &seq_name, const std::string &reference) { add_block(vb, seq_name, reference); } // (what the record loop hands its blocks to)
     void add_block(Block &vb, const std::string &seq_name, const std::string &reference)
     {
         if (!base_known || seq_name != base_name) {

@@ -4,78 +4,13 @@
 // text and BCF records made from hand-written result arrays.  Every expected value is written out here; the text follows the
 // reference's output_variants (var_block.hpp:337-396).  Meant to be built with -fsanitize=address,undefined and run on the CPU
 // (`make sanitize-host`); tests/test_call_batch_cpu.py builds it plain.  Exits non-zero on the first wrong answer.
-#include <functional>
-#include <iostream>
+#define HOST_CHECK_NAME "call_batch_host_check"
+#include "host_check_util.hpp"
 
 #include "call_text.hpp"
 
 using namespace malva;
 
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        if (!(cond)) {                                                         \
-            std::cerr << __FILE__ << ":" << __LINE__ << ": " #cond "\n";       \
-            std::cout << "call_batch_host_check: FAILED\n";                    \
-            exit(1);                                                           \
-        }                                                                      \
-    } while (0)
-
-template <class T> static bool same(const std::vector<T> &got, std::initializer_list<T> want) { return got == std::vector<T>(want); }
-static bool throws(const std::function<void()> &run)
-{
-    try {
-        run();
-    } catch (const std::exception &) {
-        return true;
-    }
-    return false;
-}
-
-// a record on `seq`, every kept sample with the genotype g1 g2 (phased or not); its frequencies are 0.5, 0.25, 0.125, ...
-static Variant var(const std::string &seq, int pos, const std::string &ref, const std::vector<std::string> &alts, size_t n_samples = 2, int g1 = 0, int g2 = 1,
-                   bool phased = true)
-{
-    Variant v;
-    v.seq_name = seq;
-    v.ref_pos = pos;
-    v.ref_sub = ref;
-    v.ref_size = v.min_size = v.max_size = (int)ref.size();
-    std::string alt_list;
-    for (const auto &a : alts) {
-        v.alts.push_back(a);
-        v.min_size = std::min(v.min_size, (int)a.size());
-        v.max_size = std::max(v.max_size, (int)a.size());
-        alt_list += (alt_list.empty() ? "" : ",") + a;
-    }
-    for (int a = 0; a < v.n_alleles(); ++a) v.frequencies.push_back(std::ldexp(0.5f, -a));
-    v.genotypes.assign(n_samples, std::make_pair(g1, g2));
-    v.phasing.assign(n_samples, (uint8_t)phased);
-    v.text_prefix = seq + "\t" + std::to_string(pos + 1) + "\t.\t" + ref + "\t" + alt_list + "\t.";
-    return v;
-}
-static Block block_of(int k, std::vector<Variant> vars)
-{
-    Block b(k);
-    for (Variant &v : vars) b.add(std::move(v));
-    return b;
-}
-
-// what a pass hands over, batch by batch
-struct Closed {
-    std::vector<Rec> recs;
-    Batch iso, gen;
-};
-struct Pass {
-    std::vector<Closed> closed;
-    std::map<std::string, uint64_t> bases{{"c1", 100}, {"c2", 1100}};
-    std::string ref1 = std::string(1000, 'A'), ref2 = std::string(500, 'C');
-    std::function<void(std::vector<Rec> &&, Batch &&, Batch &&)> close = [this](std::vector<Rec> &&r, Batch &&i, Batch &&g) {
-        closed.push_back({std::move(r), std::move(i), std::move(g)});
-    };
-    BatchBuilder<decltype(close)> b;
-    explicit Pass(const BatchRules &rules) : b(rules, bases, close) {}
-    void add(Block blk, const std::string &seq = "c1") { b.add_block(blk, seq, seq == "c2" ? ref2 : ref1); }
-};
 //                                  k  haploid dense samples iso    host   sample records
 static const BatchRules plain_rules{35, false, false, 2, false, false, false, 1000};
 

@@ -10,7 +10,9 @@ Timed, each the median of --repeats runs with their spread:
                  the device milliseconds per mg_encode_calls_bcf (mg_bcf_stats) -- on the batches the merged leg formats as text
     merged_gp    `--cohort --merged PATH --gp`, merged_gp_bcf the same with `--merged-format bcf`: the same two, the bytes written and
                  the device milliseconds per mg_format_calls_gp / mg_encode_calls_bcf_gp (mg_format_stats / mg_bcf_stats)
-    parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick
+    parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick; parent_verdict then holds,
+                 for the wall time and the panel pass, both medians, the parent's own spread (max - min) and whether per_sample's median
+                 lies within it
 The runs alternate (parent, per_sample, merged, parent, ...), so that whatever else the host is doing falls on all three alike.
 merged_equals_paste: the merged file is the column paste of the per-sample files.
 
@@ -160,8 +162,14 @@ def main():
         out["merged_bytes"] = os.path.getsize(os.path.join(td, "merged.vcf"))
         out["per_sample_bytes"] = sum(os.path.getsize(os.path.join(td, "out", "s%02d.vcf" % i)) for i in range(S))
         out["merged_equals_paste"] = int(is_paste(os.path.join(td, "merged.vcf"), [os.path.join(td, "out", "s%02d.vcf" % i) for i in range(S)]))
-        if a.parent_bin:
-            out["parent_same_bytes"] = int(all(open(os.path.join(td, "out", "s%02d.vcf" % i), "rb").read() == open(os.path.join(td, "out_parent", "s%02d.vcf" % i), "rb").read()
+        if a.parent_bin:                                                    # per line: medians, the parent's own spread (the margin), the verdict
+            out["parent_verdict"] = {}
+            for key in ("wall_s", "panel_pass_s"):
+                p, t = out["parent"][key], out["per_sample"][key]
+                spread = round(p["max"] - p["min"], 3)
+                out["parent_verdict"][key] = {"parent_median": p["median"], "parent_spread": spread, "this_median": t["median"],
+                                              "within_parent_spread": int(abs(t["median"] - p["median"]) <= spread)}
+            out["parent_same_bytes"] =int(all(open(os.path.join(td, "out", "s%02d.vcf" % i), "rb").read() == open(os.path.join(td, "out_parent", "s%02d.vcf" % i), "rb").read()
                                                for i in range(S)))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
