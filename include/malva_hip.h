@@ -525,6 +525,20 @@ int mg_format_calls_gp(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploi
 int mg_format_calls_gp_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                               int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
                               const void *d_status, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out);
+/* mg_format_calls_gp with a further field PL (Number=G, Type=Integer) behind the cell's last; GP itself becomes optional: probs and
+ * status are given both or neither, and with neither there is no GP.  A cell is `GT:GQ[:COVS][:GP]:PL`.  pl is required:
+ * [n_planes][var_gt_off[n_vars]] int32, a record's G values ALREADY in VCF order (what mg_phred_likelihoods leaves; the encoder
+ * copies and does not permute).  var_allele_off and var_gt_off are required.  The encoder formats integers and does not know where
+ * they came from: any int32 is a value and prints as std::to_string(int) prints it, MG_PL_MISSING alone is special and prints `.`.
+ * The field is `:` and the G comma-separated values; the whole field is one `.` when G == 0 or every value of the cell is
+ * missing.  A masked cell keeps its PL.  Everything else is mg_format_calls'. */
+#define MG_PL_MISSING INT32_MIN
+int mg_format_calls_pl(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                       int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                       const uint8_t *status, const int32_t *pl, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out);
+int mg_format_calls_pl_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                              int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                              const void *d_status, const void *d_pl, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out);
 
 /* ---- the site tags of a multi-sample VCF (AC / AN / AF / NS) -----------------------
  * mg_site_counts: the allele counts of every record over the planes.  gt1 / gt2 / gq as for mg_format_calls (n_planes 1..64;
@@ -774,7 +788,52 @@ int mg_encode_calls_bcf_gp_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes,
                                   int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
                                   const void *d_status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap,
                                   void *d_row_off_out, uint64_t *bytes_out);
+/* mg_encode_calls_bcf_gp with a further field behind the record's last; GP becomes optional (probs and status: both or neither),
+ * pl, var_allele_off and var_gt_off are required, as for mg_format_calls_pl --
+ *   PL    typed_int(key_pl),  desc(G, T), for every plane the record's G values of type T
+ * T is the smallest type that holds every value of the field over all planes that is not MG_PL_MISSING, by the rule above (a field
+ * without such a value: int8).  MG_PL_MISSING is written as T's missing code -- 0x80, 0x8000, 0x80000000, in int32 the sentinel
+ * itself --, a cell whose values are all missing as that code followed by G - 1 end-of-vector codes (0x81, 0x8001, 0x80000001).
+ * desc takes its long form from G = 15.  key_gp is not read without GP. */
+int mg_encode_calls_bcf_pl(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                           int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                           const uint8_t *status, const int32_t *pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
+                           uint8_t *out, size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out);
+int mg_encode_calls_bcf_pl_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                  int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                                  const void *d_status, const void *d_pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
+                                  void *d_out, size_t out_cap, void *d_row_off_out, uint64_t *bytes_out);
 int mg_bcf_stats(mg_ctx *ctx, float *ms_out);
+
+/* ---- Phred-scaled genotype likelihoods (PL), prior-free -----------------------------
+ * The likelihood part of the genotyper alone: what mg_genotype computes as log_post and multiplies with the allele-frequency prior
+ * before anything leaves it.  No frequencies are read and no cohort mode is needed.  cov is [n_planes][var_allele_off[n_vars]],
+ * plane-major, as mg_genotype_cohort takes it; pl_out is [n_planes][var_gt_off[n_vars]]; n_planes is 1..64, cap >= 1; n_vars == 0 is
+ * legal.  A bad argument returns MG_ERR_ARG and writes nothing.
+ * The values of a record are in VCF order: genotype j/k (j <= k) at index k (k + 1) / 2 + j of the record's slice, in haploid mode
+ * the allele (probs of the genotype calls is in the reference's order; mg_format_calls_pl / mg_encode_calls_bcf_pl copy).
+ * The cell (p, v), A the record's alleles, G = A (haploid) or A (A + 1) / 2:
+ *   1. if any (int)cov[a] > max_cov, all G values are MG_PL_MISSING (the over-covered cell the reference refuses to genotype);
+ *   2. if A == 1, the one value is 0 and nothing is computed;
+ *   3. if A == 0, nothing is written;
+ *   4. otherwise lp_g, for every genotype g, is the log_post of the genotyper with the same operations in the same order (the
+ *      host-made ln table, log_binomial, every (float)count * constant product rounded to float before it joins the double sum,
+ *      the error term of a heterozygote only for A > 2, no FMA contraction); a cell of total coverage 0 comes out as all zeros,
+ *      the honest likelihood of no data, and is not missing;
+ *   5. M is the largest finite lp_g; if there is none, every value of the cell is missing;
+ *   6. a NaN or +inf lp_g gives a missing value; otherwise d = M - lp_g, x = d * K with K = 0x1.15f2ced384f29p+2 (the double
+ *      nearest to 10 / ln 10), PL = cap when x >= (double)cap, else (int32_t)(x + 0.5) -- so -inf gives cap; the subtract, the
+ *      multiply and the add each rounded on their own.
+ * With every record's total coverage below 65536 the result is bit-identical to a CPU restatement of this; at or above it ln(n) is
+ * the device's log(double), as in mg_genotype_device, in both forms.  The host form checks that every record's slice of var_gt_off
+ * is G long (MG_ERR_ARG); the device form cannot, and leaves such a record alone.  The _device form takes device pointers and is
+ * asynchronous on the context's stream.  mg_pl_stats (waits): ms_out[1], device milliseconds of the most recent call;
+ * MG_ERR_STATE before the first. */
+int mg_phred_likelihoods(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, const uint32_t *cov, const uint32_t *var_allele_off, const uint64_t *var_gt_off,
+                         float error_rate, int max_cov, int haploid, int32_t cap, int32_t *pl_out);
+int mg_phred_likelihoods_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, const void *d_cov, const void *d_var_allele_off, const void *d_var_gt_off,
+                                float error_rate, int max_cov, int haploid, int32_t cap, void *d_pl_out);
+int mg_pl_stats(mg_ctx *ctx, float *ms_out);
 
 /* ---- index payloads  (bloom_filter.hpp:127-146, kmap.hpp:52-82) ----------- */
 

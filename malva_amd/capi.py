@@ -142,6 +142,13 @@ def lib():
         "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
         "mg_encode_calls_bcf_gp_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
         "mg_bcf_stats": [vp, vp],
+        "mg_format_calls_pl": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp],
+        "mg_format_calls_pl_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp],
+        "mg_encode_calls_bcf_pl": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp],
+        "mg_encode_calls_bcf_pl_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp],
+        "mg_phred_likelihoods": [vp, sz, u32, vp, vp, vp, fl, it, it, i32, vp],
+        "mg_phred_likelihoods_device": [vp, sz, u32, vp, vp, vp, fl, it, it, i32, vp],
+        "mg_pl_stats": [vp, vp],
         "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
         "mg_comm_unique_id": [vp],
         "mg_comm_init": [vp, it, it, vp],
@@ -209,6 +216,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
             "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
+            "mg_format_calls_pl", "mg_format_calls_pl_device", "mg_encode_calls_bcf_pl", "mg_encode_calls_bcf_pl_device",
+            "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
@@ -729,6 +738,60 @@ class Context:
             self._ck(rc)
         return rc, need.value
 
+    def _pl_rows(self, call_abi, gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, pl, cap):
+        """the host form of a *_pl entry: _gp_rows with the array pl ([planes, var_gt_off[n_vars]] int32) behind status"""
+        d = None if pl is None else np.ascontiguousarray(pl, dtype=np.int32)
+        return self._gp_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, out, c, row_off, need: call_abi(n, planes, g1, g2, q, cv, vo, pr, go, st, _p(d), out, c,
+                                                                                                             row_off, need),
+                             gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, cap)
+
+    def format_calls_pl(self, gt1, gt2, gq, haploid, var_allele_off, var_gt_off, pl, probs=None, status=None, cov=None, text_cap=None, min_gq=None):
+        """format_calls with the field PL behind every cell's last (mg_format_calls_pl): pl [planes, var_gt_off[n_vars]] int32, a
+        record's values in VCF order, MG_PL_MISSING = INT32_MIN a missing one.  probs and status (both or neither): GP in front of PL."""
+        return self._pl_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, d, out, cap, row_off, need: self._L.mg_format_calls_pl(
+            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, d, out, cap, row_off, need),
+            gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, pl, text_cap)
+
+    def format_calls_pl_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl, d_text, text_cap,
+                               d_row_off, min_gq=None):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_format_calls_pl_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0), v(d_cov),
+                                               v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), v(d_pl), v(d_text), int(text_cap), v(d_row_off),
+                                               C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
+    # Phred-scaled genotype likelihoods, prior-free
+    def phred_likelihoods(self, cov, var_allele_off, error_rate, max_cov, haploid, cap=255, var_gt_off=None, pl_out=None):
+        """cov: [planes, slots] uint32 -> (pl [planes, var_gt_off[-1]] int32 in VCF order, var_gt_off): the definition is
+        mg_phred_likelihoods' in include/malva_hip.h.  var_gt_off: made from var_allele_off unless given; pl_out: written in place."""
+        cov = np.ascontiguousarray(cov, dtype=np.uint32)
+        vo = np.ascontiguousarray(var_allele_off, dtype=np.uint32)
+        planes, n = cov.shape[0], len(vo) - 1
+        if var_gt_off is None:
+            A = np.diff(vo.astype(np.int64))
+            var_gt_off = np.zeros(n + 1, dtype=np.uint64)
+            var_gt_off[1:] = np.cumsum(A if haploid else A * (A + 1) // 2)
+        go = np.ascontiguousarray(var_gt_off, dtype=np.uint64)
+        pl = np.zeros((planes, int(go[-1])), dtype=np.int32) if pl_out is None else pl_out
+        self._ck(self._L.mg_phred_likelihoods(self.h, n, planes, _p(cov), _p(vo), _p(go), C.c_float(error_rate), int(max_cov), int(haploid), int(cap), _p(pl)))
+        return pl, go
+
+    def phred_likelihoods_device(self, n_vars, planes, d_cov, d_var_allele_off, d_var_gt_off, error_rate, max_cov, haploid, cap, d_pl_out):
+        """the same from device pointers into a device buffer, asynchronous on the context's stream"""
+        v = C.c_void_p
+        self._ck(self._L.mg_phred_likelihoods_device(self.h, n_vars, planes, v(d_cov), v(d_var_allele_off), v(d_var_gt_off), C.c_float(error_rate), int(max_cov),
+                                                     int(haploid), int(cap), v(d_pl_out)))
+
+    def pl_stats(self):
+        """-> device ms of the most recent phred_likelihoods"""
+        ms = (C.c_float * 1)()
+        self._ck(self._L.mg_pl_stats(self.h, ms))
+        return float(ms[0])
+
     def format_stats(self):
         """-> device ms of the most recent format_calls: (length pass, scan, write pass)"""
         ms = (C.c_float * 3)()
@@ -957,6 +1020,25 @@ class Context:
         rc = self._L.mg_encode_calls_bcf_gp_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
                                                    v(d_cov), v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), int(keys[0]), int(keys[1]), int(keys[2]),
                                                    int(keys[3]), v(d_out), int(out_cap), v(d_row_off), C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
+    def encode_calls_bcf_pl(self, gt1, gt2, gq, haploid, keys, var_allele_off, var_gt_off, pl, probs=None, status=None, cov=None, out_cap=None, min_gq=None):
+        """encode_calls_bcf with the integer field PL behind the record's last (mg_encode_calls_bcf_pl).  keys: (gt, gq, cov, gp, pl);
+        the arrays as format_calls_pl's."""
+        return self._pl_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, d, out, cap, row_off, need: self._L.mg_encode_calls_bcf_pl(
+            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, d, int(keys[0]), int(keys[1]), int(keys[2]),
+            int(keys[3]), int(keys[4]), out, cap, row_off, need), gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, pl, out_cap)
+
+    def encode_calls_bcf_pl_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl, keys, d_out,
+                                   out_cap, d_row_off, min_gq=None):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_encode_calls_bcf_pl_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
+                                                   v(d_cov), v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), v(d_pl), int(keys[0]), int(keys[1]),
+                                                   int(keys[2]), int(keys[3]), int(keys[4]), v(d_out), int(out_cap), v(d_row_off), C.byref(need))
         if rc not in (0, -5) or (rc == -5 and not need.value):
             self._ck(rc)
         return rc, need.value

@@ -11,6 +11,11 @@
 //                                                                      so that float denormals stay; an unprintable value (gp_printable)
 //                                                                      is the missing float, a cell that is not MG_GT_NORMAL the missing
 //                                                                      float and G - 1 end-of-vector floats
+//   PL    typed_int(key_pl)  desc(G, T)       [plane][G] values        mg_encode_calls_bcf_pl (GP is optional there): `pl` as it comes, already in
+//                                                                      VCF order; T the smallest type that holds every value of the field that
+//                                                                      is not MG_PL_MISSING (int8 when there is none); MG_PL_MISSING is T's missing
+//                                                                      code (0x80, 0x8000, 0x80000000), a cell whose values are all missing that
+//                                                                      code and G - 1 end-of-vector codes (0x81, 0x8001, 0x80000001)
 // desc(n, t) is the byte n << 4 | t for n < 15, else 0xF0 | t and typed_int(n); typed_int(x) is desc(1, t) and x in the smallest of int8
 // (t = 1), int16 (2), int32 (3) that holds it; little endian throughout.  T of a field of a record is the smallest type that holds
 // every value of that field over all planes with BCF's reserved codes (missing, end of vector) kept free: int8 for [-120, 127], int16
@@ -49,6 +54,9 @@ struct BcfArgs {
     const u64 *var_gt_off;       // [n_vars + 1]
     const u8 *status;            // [n_planes][n_vars]
     i32 key_gp;
+    // mg_encode_calls_bcf_pl (with var_allele_off and var_gt_off; probs and status then both or neither)
+    const i32 *pl;               // [n_planes][var_gt_off[n_vars]]
+    i32 key_pl;
 };
 
 constexpr u32 BCF_FLOAT_MISSING = 0x7F800001u, BCF_FLOAT_EOV = 0x7F800002u;
@@ -125,7 +133,7 @@ __device__ __forceinline__ i32 bcf_wave_max(i32 x)
 
 // the bytes of row v whose three fields have the types t[0..2] (t[2] unused without cov).  GP: the kernels of mg_encode_calls_bcf_gp, a
 // build of their own as in call_text_kernels.h
-template <bool GP>
+template <bool GP, bool PL = false>
 __device__ __forceinline__ u64 bcf_row_len(const BcfArgs &a, u64 v, const u32 *t)
 {
     const u64 P = a.n_planes;
@@ -139,11 +147,17 @@ __device__ __forceinline__ u64 bcf_row_len(const BcfArgs &a, u64 v, const u32 *t
         const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
         len += bcf_typed_int_len(a.key_gp) + bcf_desc_len((u32)G) + P * G * 4;
     }
+    if (PL) {
+        const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+        len += bcf_typed_int_len(a.key_pl) + bcf_desc_len((u32)G) + P * G * bcf_width(t[3]);
+    }
     return len;
 }
 
-// meta[1] is raised when a row does not fit 32 bits, as by fmt_len_kernel
-template <bool GP>
+// meta[1] is raised when a row does not fit 32 bits, as by fmt_len_kernel.  A record has three type codes, four with PL (BCF_TYPES)
+template <bool PL>
+constexpr u32 BCF_TYPES = PL ? 4 : 3;
+template <bool GP, bool PL = false>
 __global__ void __launch_bounds__(FMT_TPB) bcf_len_kernel(BcfArgs a, u32 *__restrict__ len, unsigned char *__restrict__ types, unsigned long long *meta)
 {
     const u32 lane = threadIdx.x & 63;
@@ -169,7 +183,7 @@ __global__ void __launch_bounds__(FMT_TPB) bcf_len_kernel(BcfArgs a, u32 *__rest
             }
         }
     }
-    u32 t[3];
+    u32 t[BCF_TYPES<PL>];
     t[0] = bcf_type_of(bcf_wave_min(g_lo), bcf_wave_max(g_hi));
     t[1] = bcf_type_of(bcf_wave_min(q_lo), bcf_wave_max(q_hi));
     t[2] = 1;
@@ -178,22 +192,39 @@ __global__ void __launch_bounds__(FMT_TPB) bcf_len_kernel(BcfArgs a, u32 *__rest
         c_hi = bcf_wave_max(c_hi);
         if (c_lo <= c_hi) t[2] = bcf_type_of(c_lo, c_hi); // (else: a record without alleles)
     }
-    if (lane < 3) types[3 * v + lane] = (unsigned char)(lane == 0 ? t[0] : lane == 1 ? t[1] : t[2]);
+    if (PL) {
+        i32 p_lo = INT32_MAX, p_hi = INT32_MIN;
+        if (lane < a.n_planes) {
+            const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+            const i32 *pl = a.pl + (u64)lane * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+            for (u64 g = 0; g < G; ++g) {
+                const i32 x = pl[g];
+                if (x == FMT_PL_MISSING) continue;
+                p_lo = x < p_lo ? x : p_lo;
+                p_hi = x > p_hi ? x : p_hi;
+            }
+        }
+        p_lo = bcf_wave_min(p_lo);
+        p_hi = bcf_wave_max(p_hi);
+        t[BCF_TYPES<PL> - 1] = p_lo <= p_hi ? bcf_type_of(p_lo, p_hi) : 1; // (else: no value that is not missing)
+    }
+    if (lane < BCF_TYPES<PL>) types[BCF_TYPES<PL> * v + lane] = (unsigned char)(lane == 0 ? t[0] : lane == 1 ? t[1] : lane == 2 ? t[2] : t[BCF_TYPES<PL> - 1]);
     if (lane == 0) {
-        const u64 bytes = bcf_row_len<GP>(a, v, t);
+        const u64 bytes = bcf_row_len<GP, PL>(a, v, t);
         if (bytes > 0xFFFFFFFFull) atomicOr(meta + 1, 1ull);
         len[v] = (u32)bytes;
     }
 }
 
 // a record's row: the field headers by lane 0, the values of plane `lane` by that lane
-template <bool GP>
+template <bool GP, bool PL = false>
 struct BcfRows {
     BcfArgs a;
     const unsigned char *types;
     __device__ __forceinline__ void put(const FmtWindow &w, u64 v, u32 lane, u64 r0, u64) const
     {
-        const u32 t_gt = types[3 * v], t_gq = types[3 * v + 1], t_cov = types[3 * v + 2];
+        constexpr u32 NT = BCF_TYPES<PL>;
+        const u32 t_gt = types[NT * v], t_gq = types[NT * v + 1], t_cov = types[NT * v + 2];
         const u32 ploidy = a.haploid ? 1 : 2;
         const bool mine = lane < a.n_planes;
         const u64 i = (u64)lane * a.n_vars + v;
@@ -227,14 +258,19 @@ struct BcfRows {
             }
             pos += (u64)a.n_planes * span;
         }
-        if (!GP) return;
-        // GP: value g of this plane at pos + (lane G + g) 4 -- only those of the window are loaded
+        if (GP) pos = put_gp(w, v, lane, mine, i, pos);
+        if (PL) put_pl(w, v, lane, mine, types[NT * v + NT - 1], pos);
+    }
+    // GP: value g of this plane at pos + (lane G + g) 4 -- only those of the window are loaded; returns the position behind the field
+    __device__ __forceinline__ u64 put_gp(const FmtWindow &w, u64 v, u32 lane, bool mine, u64 i, u64 pos) const
+    {
+        const u64 w1 = w.w0 + w.wlen;
         const u32 A = a.var_allele_off[v + 1] - a.var_allele_off[v];
         const u64 G = a.haploid ? (u64)A : (u64)A * (A + 1) / 2;
         if (lane == 0) bcf_put_desc(w, bcf_put_typed_int(w, pos, a.key_gp), (u32)G, 5);
         pos += bcf_typed_int_len(a.key_gp) + bcf_desc_len((u32)G);
-        const u64 at = pos + (u64)lane * G * 4;
-        if (!mine || at >= w1 || at + G * 4 <= w.w0) return;
+        const u64 at = pos + (u64)lane * G * 4, behind = pos + (u64)a.n_planes * G * 4;
+        if (!mine || at >= w1 || at + G * 4 <= w.w0) return behind;
         const u64 g_lo = w.w0 > at ? (w.w0 - at) / 4 : 0, g_hi = w1 - at < G * 4 ? (w1 - at + 3) / 4 : G; // (a value the window cuts is made on both sides)
         const bool normal = a.status[i] == MG_GT_NORMAL;
         const double *pr = a.probs + (u64)lane * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
@@ -258,15 +294,36 @@ struct BcfRows {
             }
             bcf_put_val(w, at + g * 4, (i32)f, 3);
         }
+        return behind;
+    }
+    // PL: value g of this plane at pos + (lane G + g) width(t); the values of the window alone are written, the whole cell is read to know
+    // whether it is all missing
+    __device__ __forceinline__ void put_pl(const FmtWindow &w, u64 v, u32 lane, bool mine, u32 t, u64 pos) const
+    {
+        const u64 w1 = w.w0 + w.wlen;
+        const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+        if (lane == 0) bcf_put_desc(w, bcf_put_typed_int(w, pos, a.key_pl), (u32)G, t);
+        pos += bcf_typed_int_len(a.key_pl) + bcf_desc_len((u32)G);
+        const u64 wd = bcf_width(t), at = pos + (u64)lane * G * wd;
+        if (!mine || at >= w1 || at + G * wd <= w.w0) return;
+        const i32 *pl = a.pl + (u64)lane * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+        bool any = false;
+        for (u64 g = 0; g < G && !any; ++g) any = pl[g] != FMT_PL_MISSING;
+        const i32 missing = t == 1 ? 0x80 : t == 2 ? 0x8000 : INT32_MIN;
+        const u64 g_lo = w.w0 > at ? (w.w0 - at) / wd : 0, g_hi = w1 - at < G * wd ? (w1 - at + wd - 1) / wd : G; // (a value the window cuts is made on both sides)
+        for (u64 g = g_lo; g < g_hi; ++g) {
+            const i32 x = pl[g];
+            bcf_put_val(w, at + g * wd, x != FMT_PL_MISSING ? x : any || g == 0 ? missing : missing + 1, t);
+        }
     }
 };
 
-template <bool GP>
+template <bool GP, bool PL = false>
 __global__ void __launch_bounds__(FMT_TPB) bcf_write_kernel(BcfArgs a, const unsigned char *__restrict__ types, const unsigned long long *__restrict__ row_off,
                                                            char *out, u64 out_cap)
 {
     __shared__ __attribute__((aligned(16))) char sh[FMT_WINDOW];
-    fmt_write_tile(BcfRows<GP>{a, types}, sh, a.n_vars, row_off, out, out_cap);
+    fmt_write_tile(BcfRows<GP, PL>{a, types}, sh, a.n_vars, row_off, out, out_cap);
 }
 
 } // namespace

@@ -21,6 +21,11 @@
 // single-sample output) in VCF genotype order, each printed as printf("%f") prints it.  A value is 8 bytes (`0.dddddd`, `1.000000`) when it
 // is printable -- sign bit clear and <= 1 -- and the one byte `.` when it is not, so the length pass formats nothing; the digits are made
 // in integers from the double's bits (gp_micro), to nearest on the exact value with ties to even, as glibc rounds.
+//
+// mg_format_calls_pl adds the field PL behind the cell's last (behind GP, which is optional there): the G integers of `pl` (what
+// mg_phred_likelihoods leaves: already in VCF order, copied and not permuted), each as std::to_string(int) prints it, `.` for
+// MG_PL_MISSING; the whole field is one `.` when G == 0 or every value of the cell is missing.  Any other int32 is a value: the encoder
+// does not know where the numbers came from.  A masked cell keeps its PL.
 #pragma once
 #include "kmer_dev.h"
 
@@ -78,7 +83,11 @@ struct FmtArgs {
     const double *probs;         // [n_planes][var_gt_off[n_vars]], a record's values in the reference's order: a outer, c >= a inner
     const u64 *var_gt_off;       // [n_vars + 1]
     const u8 *status;            // [n_planes][n_vars]: a cell that is not MG_GT_NORMAL has no list, its probs are not read
+    // mg_format_calls_pl (with var_allele_off and var_gt_off; probs and status then both or neither)
+    const i32 *pl;               // [n_planes][var_gt_off[n_vars]], a record's values in VCF order
 };
+
+constexpr i32 FMT_PL_MISSING = INT32_MIN; // MG_PL_MISSING
 
 // ---- GP: the genotype posteriors of a cell -----------------------------------------------------------------------------------------
 // printable: sign bit clear and 0 <= p <= 1 (as bit patterns the non-negative doubles are ordered like integers: NaN, +inf and
@@ -168,9 +177,46 @@ __device__ __forceinline__ u64 gp_put(const FmtArgs &a, const FmtWindow &w, u64 
     return pos;
 }
 
+// ---- PL: the Phred-scaled likelihoods of a cell ------------------------------------------------------------------------------------------
+// the bytes of a cell's PL field, its ':' included
+__device__ __forceinline__ u32 pl_len(const FmtArgs &a, u64 v, u32 p)
+{
+    const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+    const i32 *pl = a.pl + (u64)p * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+    u32 len = 0;
+    bool any = false;
+    for (u64 g = 0; g < G; ++g) {
+        const i32 x = pl[g];
+        any |= x != FMT_PL_MISSING;
+        len += 1 + (x == FMT_PL_MISSING ? 1u : fmt_int_len(x)); // (':' in front of the first, ',' of the others)
+    }
+    return any ? len : 2;
+}
+__device__ __forceinline__ u64 pl_put(const FmtArgs &a, const FmtWindow &w, u64 v, u32 p, u64 pos)
+{
+    const u64 A = a.var_allele_off[v + 1] - a.var_allele_off[v], G = a.haploid ? A : A * (A + 1) / 2;
+    const i32 *pl = a.pl + (u64)p * a.var_gt_off[a.n_vars] + a.var_gt_off[v];
+    const u64 w1 = w.w0 + w.wlen;
+    bool any = false;
+    for (u64 g = 0; g < G && !any; ++g) any = pl[g] != FMT_PL_MISSING;
+    w.put(pos++, ':');
+    if (!any) {
+        w.put(pos++, '.');
+        return pos;
+    }
+    for (u64 g = 0; g < G; ++g) {
+        if (pos >= w1) return pos; // (behind the window's end nothing is left to do)
+        if (g) w.put(pos++, ',');
+        const i32 x = pl[g];
+        if (x == FMT_PL_MISSING) w.put(pos++, '.');
+        else pos = w.put_int(pos, x);
+    }
+    return pos;
+}
+
 // plane p's cell of record v, the tab in front of it included.  GP: the kernels of mg_format_calls_gp -- a build of their own, so that
-// those of the entries without it keep the registers they had
-template <bool GP>
+// those of the entries without it keep the registers they had; PL: those of mg_format_calls_pl, for the same reason
+template <bool GP, bool PL = false>
 __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
 {
     const u64 i = (u64)p * a.n_vars + v;
@@ -188,9 +234,10 @@ __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
         if (a0 == a1) len += 1;                                          // a record without alleles: the empty list behind its ':'
     }
     if (GP) len += gp_len(a, v, p);
+    if (PL) len += pl_len(a, v, p);
     return len;
 }
-template <bool GP>
+template <bool GP, bool PL = false>
 __device__ __forceinline__ u64 fmt_cell_put(const FmtArgs &a, const FmtWindow &w, u64 v, u32 p, u64 pos)
 {
     const u64 i = (u64)p * a.n_vars + v;
@@ -221,17 +268,18 @@ __device__ __forceinline__ u64 fmt_cell_put(const FmtArgs &a, const FmtWindow &w
         }
     }
     if (GP) pos = gp_put(a, w, v, p, pos);
+    if (PL) pos = pl_put(a, w, v, p, pos);
     return pos;
 }
 
 // meta[1] is raised when a row does not fit 32 bits (the scan then reports ~0 as the total)
-template <bool GP>
+template <bool GP, bool PL = false>
 __global__ void __launch_bounds__(FMT_TPB) fmt_len_kernel(FmtArgs a, u32 *__restrict__ len, unsigned long long *meta)
 {
     const u32 lane = threadIdx.x & 63;
     const u64 v = (u64)blockIdx.x * (FMT_TPB / 64) + (threadIdx.x >> 6);
     if (v >= a.n_vars) return;
-    unsigned long long mine = lane < a.n_planes ? fmt_cell_len<GP>(a, v, lane) : 0;
+    unsigned long long mine = lane < a.n_planes ? fmt_cell_len<GP, PL>(a, v, lane) : 0;
     for (int d = 32; d; d >>= 1) mine += (unsigned long long)__shfl_xor((long long)mine, d, 64);
     if (lane == 0) {
         mine += 1; // '\n'
@@ -315,28 +363,28 @@ __device__ __forceinline__ void fmt_write_tile(const Rows &rows, char *sh, u64 n
 }
 
 // a record's sample columns: every lane its plane's cell at the offset a wave prefix sum gives it
-template <bool GP>
+template <bool GP, bool PL = false>
 struct FmtCellRows {
     FmtArgs a;
     __device__ __forceinline__ void put(const FmtWindow &w, u64 v, u32 lane, u64 r0, u64 r1) const
     {
-        const u32 mine = lane < a.n_planes ? fmt_cell_len<GP>(a, v, lane) : 0;
+        const u32 mine = lane < a.n_planes ? fmt_cell_len<GP, PL>(a, v, lane) : 0;
         u32 incl = mine;
         for (int d = 1; d < 64; d <<= 1) {
             const u32 up = (u32)__shfl_up((int)incl, d, 64);
             if (lane >= (u32)d) incl += up;
         }
         const u64 at = r0 + (incl - mine);
-        if (lane < a.n_planes && at < w.w0 + w.wlen && at + mine > w.w0) fmt_cell_put<GP>(a, w, v, lane, at);
+        if (lane < a.n_planes && at < w.w0 + w.wlen && at + mine > w.w0) fmt_cell_put<GP, PL>(a, w, v, lane, at);
         if (lane == 0) w.put(r1 - 1, '\n');
     }
 };
 
-template <bool GP>
+template <bool GP, bool PL = false>
 __global__ void __launch_bounds__(FMT_TPB) fmt_write_kernel(FmtArgs a, const unsigned long long *__restrict__ row_off, char *text, u64 text_cap)
 {
     __shared__ __attribute__((aligned(16))) char sh[FMT_WINDOW];
-    fmt_write_tile(FmtCellRows<GP>{a}, sh, a.n_vars, row_off, text, text_cap);
+    fmt_write_tile(FmtCellRows<GP, PL>{a}, sh, a.n_vars, row_off, text, text_cap);
 }
 
 } // namespace

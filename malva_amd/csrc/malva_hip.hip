@@ -44,6 +44,7 @@ constexpr int TPB = 256;
 #include "sample_kernels.h"
 #include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
+#include "pl_kernels.h"
 #include "reads_kernels.h"
 
 } // namespace
@@ -87,7 +88,7 @@ struct Timer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -100,6 +101,7 @@ enum {
     ST_AC, ST_NS, ST_PLANES, ST_PA, ST_PB, ST_COUNTS,                                                      // the counting calls' tables
     ST_OUT, ST_ROW_OFF,                                                                                    // an encoder's rows (stage_rows)
     ST_FREQ, ST_FREQ_OUT, ST_NINF,                                                                         // mg_genotype_cohort's priors
+    ST_PL,                                                                                                 // mg_phred_likelihoods' result, the *_pl encoders' input
     ST_COUNT
 };
 
@@ -167,7 +169,7 @@ struct mg_ctx {
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
     hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
     // the merged-batch section: each stats call reports the latest call of its own kinds, hence a timer per kind
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -3146,16 +3148,20 @@ struct Cells {
     const void *probs = nullptr, *var_gt_off = nullptr; // the *_gp entries (gp set), with status: the three arrays of the likelihoods
     const void *allele_class = nullptr;                 // mg_sample_counts*
     bool gp = false;
+    const void *pl = nullptr;                           // the *_pl entries (with_pl set): var_allele_off and var_gt_off required, gp = probs or status given
+    bool with_pl = false;
 };
 // The argument checks that a host form and its device form share: of whoever reads a batch's cells (gq where reads_gq; an encoder: cov with
 // var_allele_off or neither, and with gp var_allele_off with or without cov and the likelihoods), and of where an encoder's rows go
 int check_cells(mg_ctx *c, const char *who, const Cells &x, bool encoder, bool reads_gq)
 {
     if (x.n_planes < 1 || x.n_planes > 64) return fail(c, MG_ERR_ARG, "%s: n_planes is 1..64", who);
-    if (encoder && !x.gp && (x.cov != nullptr) != (x.var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
-    if (x.gp && (!x.var_allele_off || !x.var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
+    if (encoder && !x.gp && !x.with_pl && (x.cov != nullptr) != (x.var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
+    if ((x.gp || x.with_pl) && (!x.var_allele_off || !x.var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
+    if (x.with_pl && (x.probs != nullptr) != (x.status != nullptr)) return fail(c, MG_ERR_ARG, "%s: probs and status go together", who);
     if (x.n_vars && (!x.gt1 || (!x.haploid && !x.gt2) || (reads_gq && !x.gq))) return fail(c, MG_ERR_ARG, "NULL argument");
     if (x.n_vars && x.gp && (!x.probs || !x.status)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (x.n_vars && x.with_pl && !x.pl) return fail(c, MG_ERR_ARG, "NULL argument");
     if (x.n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "%s: more than 2^32 - 1 records in one call", who);
     return MG_OK;
 }
@@ -3253,7 +3259,7 @@ int rows_stats(mg_ctx *c, int enc, const char *who, float *ms_out)
 // The host forms' way in: a batch's cells go up, *d = h with device pointers.  gt1; gt2 unless haploid; gq where given and read (always, or
 // under the mask alone); whatever else is given -- at n_vars == 0 only when_empty (the encoders and mg_pack_dosage, who take var_allele_off
 // [0 .. n_vars] as it comes; mg_site_counts and mg_sample_counts do not read it then).  cov and allele_class are sized from
-// var_allele_off[n_vars], probs from var_gt_off[n_vars].  What is not uploaded is NULL on the device side.
+// var_allele_off[n_vars], probs and pl from var_gt_off[n_vars].  What is not uploaded is NULL on the device side.
 int stage_cells(mg_ctx *c, const Cells &h, Cells *d, bool always_gq, bool when_empty)
 {
     *d = h;
@@ -3271,7 +3277,8 @@ int stage_cells(mg_ctx *c, const Cells &h, Cells *d, bool always_gq, bool when_e
     TRY(up(ST_COV, h.cov, rest, 4 * (size_t)h.n_planes * slots, &d->cov));
     TRY(up(ST_VAR_ALLELE_OFF, h.var_allele_off, rest, 4 * (h.n_vars + 1), &d->var_allele_off));
     TRY(up(ST_PROBS, h.probs, h.gp, 8 * (size_t)h.n_planes * (h.gp ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->probs));
-    TRY(up(ST_VAR_GT_OFF, h.var_gt_off, h.gp, 8 * (h.n_vars + 1), &d->var_gt_off));
+    TRY(up(ST_VAR_GT_OFF, h.var_gt_off, h.gp || h.with_pl, 8 * (h.n_vars + 1), &d->var_gt_off));
+    TRY(up(ST_PL, h.pl, h.with_pl, 4 * (size_t)h.n_planes * (h.with_pl ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->pl));
     TRY(up(ST_STATUS, h.status, rest, cells, &d->status));
     return up(ST_ALLELE_CLASS, h.allele_class, rest, slots, &d->allele_class);
 }
@@ -3298,16 +3305,17 @@ int format_calls_device(mg_ctx *c, const Cells &x, void *d_text_out, size_t text
     if (!c) return MG_ERR_ARG;
     TRY(check_cells(c, "mg_format_calls", x, true, true));
     const FmtArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, (const u32 *)x.cov, (const u32 *)x.var_allele_off,
-                    x.use_mask, x.min_gq, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status};
+                    x.use_mask, x.min_gq, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, (const i32 *)x.pl};
+    const auto len_kernel = x.with_pl ? (x.gp ? fmt_len_kernel<true, true> : fmt_len_kernel<false, true>) : x.gp ? fmt_len_kernel<true> : fmt_len_kernel<false>;
+    const auto write_kernel = x.with_pl ? (x.gp ? fmt_write_kernel<true, true> : fmt_write_kernel<false, true>) : x.gp ? fmt_write_kernel<true> : fmt_write_kernel<false>;
     return encode_rows(
         c, TM_FMT, "mg_format_calls", x.n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
-            hipLaunchKernelGGL(x.gp ? fmt_len_kernel<true> : fmt_len_kernel<false>, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
+            hipLaunchKernelGGL(len_kernel, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, meta);
             return MG_OK;
         },
         [&](const unsigned long long *row_off) {
-            hipLaunchKernelGGL(x.gp ? fmt_write_kernel<true> : fmt_write_kernel<false>, fmt_write_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off,
-                               (char *)d_text_out, (u64)text_cap);
+            hipLaunchKernelGGL(write_kernel, fmt_write_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, row_off, (char *)d_text_out, (u64)text_cap);
         });
 }
 
@@ -3365,6 +3373,31 @@ MG_EXPORT int mg_format_calls_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, in
 {
     const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, true};
     return format_calls_host(c, x, text_out, text_cap, row_off_out, text_bytes_out);
+}
+// the same with the field PL behind the cell's last: `pl` as mg_phred_likelihoods leaves it; GP in front of it when probs and status are given
+namespace {
+Cells pl_cells(size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, int use_mask, int32_t min_gq, const void *cov,
+               const void *var_allele_off, const void *probs, const void *var_gt_off, const void *status, const void *pl)
+{
+    Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, probs || status};
+    x.pl = pl;
+    x.with_pl = true;
+    return x;
+}
+} // namespace
+MG_EXPORT int mg_format_calls_pl_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                        int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                                        const void *d_status, const void *d_pl, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
+{
+    return format_calls_device(c, pl_cells(n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl),
+                               d_text_out, text_cap, d_row_off_out, text_bytes_out);
+}
+MG_EXPORT int mg_format_calls_pl(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                 int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                                 const uint8_t *status, const int32_t *pl, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
+{
+    return format_calls_host(c, pl_cells(n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, probs, var_gt_off, status, pl), text_out,
+                             text_cap, row_off_out, text_bytes_out);
 }
 
 // device milliseconds of the most recent mg_format_calls* (rows_stats)
@@ -3837,33 +3870,97 @@ MG_EXPORT int mg_estimate_priors_stats(mg_ctx *c, float *ms_out)
     return timer_read(c, c->tm[TM_ESTIMATE], ms_out);
 }
 
+// ---- Phred-scaled likelihoods from the coverages, prior-free (pl_kernels.h) ------------------------------------------------------------------
 namespace {
-int encode_calls_bcf_device(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap, void *d_row_off_out,
-                            uint64_t *bytes_out)
+int check_phred(mg_ctx *c, size_t n_vars, uint32_t n_planes, const void *cov, const void *var_allele_off, const void *var_gt_off, int32_t cap, const void *pl_out)
+{
+    if (n_planes < 1 || n_planes > 64) return fail(c, MG_ERR_ARG, "mg_phred_likelihoods takes 1..64 planes");
+    if (cap < 1) return fail(c, MG_ERR_ARG, "mg_phred_likelihoods takes a cap >= 1");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_phred_likelihoods: more than 2^32 - 1 records in one call");
+    if (n_vars && (!cov || !var_allele_off || !var_gt_off || !pl_out)) return fail(c, MG_ERR_ARG, "NULL argument");
+    return MG_OK;
+}
+} // namespace
+
+MG_EXPORT int mg_phred_likelihoods_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, const void *d_cov, const void *d_var_allele_off, const void *d_var_gt_off,
+                                          float error_rate, int max_cov, int haploid, int32_t cap, void *d_pl_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_phred(c, n_vars, n_planes, d_cov, d_var_allele_off, d_var_gt_off, cap, d_pl_out));
+    GenoParams p;
+    if (n_vars) TRY(fill_geno_params(c, error_rate, max_cov, haploid, &p)); // (may synchronise: before the timer starts)
+    TRY(timer_begin(c, c->tm[TM_PL]));
+    if (n_vars) {
+        const PlArgs a{(u64)n_vars, (const u32 *)d_cov, (const u32 *)d_var_allele_off, (const u64 *)d_var_gt_off, cap, (i32 *)d_pl_out};
+        hipLaunchKernelGGL(pl_kernel, dim3((unsigned)((n_vars + PL_TPB - 1) / PL_TPB), n_planes), dim3(PL_TPB), 0, c->stream, a, p);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_PL], 1);
+}
+
+MG_EXPORT int mg_phred_likelihoods(mg_ctx *c, size_t n_vars, uint32_t n_planes, const uint32_t *cov, const uint32_t *var_allele_off, const uint64_t *var_gt_off,
+                                   float error_rate, int max_cov, int haploid, int32_t cap, int32_t *pl_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_phred(c, n_vars, n_planes, cov, var_allele_off, var_gt_off, cap, pl_out));
+    const size_t na = n_vars ? var_allele_off[n_vars] : 0, ng = n_vars ? var_gt_off[n_vars] : 0;
+    void *d_cov = nullptr, *d_vao = nullptr, *d_vgo = nullptr, *d_pl = nullptr;
+    for (size_t v = 0; v < n_vars; ++v) { // (the kernel leaves such a record alone; here the offsets can be read, and nothing is written)
+        const uint64_t A = var_allele_off[v + 1] - var_allele_off[v];
+        if (var_allele_off[v + 1] < var_allele_off[v] || var_gt_off[v + 1] - var_gt_off[v] != (haploid ? A : A * (A + 1) / 2))
+            return fail(c, MG_ERR_ARG, "mg_phred_likelihoods: record %zu's slice of var_gt_off is not its number of genotypes", v);
+    }
+    if (n_vars) {
+        TRY(upload(c, c->stage[ST_COV], cov, 4 * (size_t)n_planes * na, &d_cov));
+        TRY(upload(c, c->stage[ST_VAR_ALLELE_OFF], var_allele_off, 4 * (n_vars + 1), &d_vao));
+        TRY(upload(c, c->stage[ST_VAR_GT_OFF], var_gt_off, 8 * (n_vars + 1), &d_vgo));
+        TRY(scratch(c, c->stage[ST_PL], 4 * ((size_t)n_planes * ng ? (size_t)n_planes * ng : 1), &d_pl));
+    }
+    TRY(mg_phred_likelihoods_device(c, n_vars, n_planes, d_cov, d_vao, d_vgo, error_rate, max_cov, haploid, cap, d_pl));
+    if (n_vars && ng) HIP_TRY(c, hipMemcpyAsync(pl_out, d_pl, 4 * (size_t)n_planes * ng, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds (waits for them) of the most recent mg_phred_likelihoods*
+MG_EXPORT int mg_pl_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = 0.f; // (also where it fails)
+    if (!c->tm[TM_PL].valid) return fail(c, MG_ERR_STATE, "no mg_phred_likelihoods yet");
+    return timer_read(c, c->tm[TM_PL], ms_out);
+}
+
+namespace {
+int encode_calls_bcf_device(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl, void *d_out, size_t out_cap,
+                            void *d_row_off_out, uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
     TRY(check_cells(c, "mg_encode_calls_bcf", x, true, true));
-    if (key_gt < 0 || key_gq < 0 || (x.cov && key_cov < 0) || (x.gp && key_gp < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
+    if (key_gt < 0 || key_gq < 0 || (x.cov && key_cov < 0) || (x.gp && key_gp < 0) || (x.with_pl && key_pl < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
     const BcfArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, (const u32 *)x.cov, (const u32 *)x.var_allele_off,
-                    x.use_mask, x.min_gq, key_gt, key_gq, key_cov, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, key_gp};
-    void *d_types = nullptr; // the records' type codes: what the length pass found, for the write pass
+                    x.use_mask, x.min_gq, key_gt, key_gq, key_cov, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, key_gp, (const i32 *)x.pl, key_pl};
+    const auto len_kernel = x.with_pl ? (x.gp ? bcf_len_kernel<true, true> : bcf_len_kernel<false, true>) : x.gp ? bcf_len_kernel<true> : bcf_len_kernel<false>;
+    const auto write_kernel = x.with_pl ? (x.gp ? bcf_write_kernel<true, true> : bcf_write_kernel<false, true>) : x.gp ? bcf_write_kernel<true> : bcf_write_kernel<false>;
+    void *d_types = nullptr; // the records' type codes (three, with PL four): what the length pass found, for the write pass
     return encode_rows(
         c, TM_BCF, "mg_encode_calls_bcf", x.n_vars, d_out, out_cap, d_row_off_out, bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
-            TRY(scratch(c, c->s_enc[TM_BCF][ES_TYPES], 3 * x.n_vars, &d_types));
-            hipLaunchKernelGGL(x.gp ? bcf_len_kernel<true> : bcf_len_kernel<false>, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types,
-                               meta);
+            TRY(scratch(c, c->s_enc[TM_BCF][ES_TYPES], (x.with_pl ? 4 : 3) * x.n_vars, &d_types));
+            hipLaunchKernelGGL(len_kernel, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types, meta);
             return MG_OK;
         },
         [&](const unsigned long long *row_off) {
-            hipLaunchKernelGGL(x.gp ? bcf_write_kernel<true> : bcf_write_kernel<false>, fmt_write_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a,
-                               (const unsigned char *)d_types, row_off, (char *)d_out, (u64)out_cap);
+            hipLaunchKernelGGL(write_kernel, fmt_write_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, (const unsigned char *)d_types, row_off, (char *)d_out, (u64)out_cap);
         });
 }
 
-int encode_calls_bcf_host(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap, uint64_t *row_off_out,
-                          uint64_t *bytes_out)
+int encode_calls_bcf_host(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl, uint8_t *out, size_t out_cap,
+                          uint64_t *row_off_out, uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
@@ -3873,7 +3970,7 @@ int encode_calls_bcf_host(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key
     void *d_out, *d_off;
     TRY(stage_cells(c, x, &d, true, true));
     TRY(stage_rows(c, x.n_vars, out_cap, &d_out, &d_off));
-    const int rc = encode_calls_bcf_device(c, d, key_gt, key_gq, key_cov, key_gp, d_out, out_cap, d_off, bytes_out);
+    const int rc = encode_calls_bcf_device(c, d, key_gt, key_gq, key_cov, key_gp, key_pl, d_out, out_cap, d_off, bytes_out);
     return fetch_rows(c, rc, x.n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
 }
 } // namespace
@@ -3882,14 +3979,14 @@ MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_pl
                                          size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
 {
     const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov};
-    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, 0, d_out, out_cap, d_row_off_out, bytes_out);
+    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, 0, 0, d_out, out_cap, d_row_off_out, bytes_out);
 }
 MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
                                   int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
                                   size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
 {
     const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov};
-    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, 0, out, out_cap, row_off_out, bytes_out);
+    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, 0, 0, out, out_cap, row_off_out, bytes_out);
 }
 // the same with the float field GP behind the record's last (bcf_kernels.h)
 MG_EXPORT int mg_encode_calls_bcf_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
@@ -3898,7 +3995,7 @@ MG_EXPORT int mg_encode_calls_bcf_gp_device(mg_ctx *c, size_t n_vars, uint32_t n
                                             void *d_row_off_out, uint64_t *bytes_out)
 {
     const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov, d_status, d_probs, d_var_gt_off, nullptr, true};
-    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, key_gp, d_out, out_cap, d_row_off_out, bytes_out);
+    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, key_gp, 0, d_out, out_cap, d_row_off_out, bytes_out);
 }
 MG_EXPORT int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
                                      int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
@@ -3906,7 +4003,24 @@ MG_EXPORT int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes
                                      uint64_t *row_off_out, uint64_t *bytes_out)
 {
     const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, true};
-    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, key_gp, out, out_cap, row_off_out, bytes_out);
+    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, key_gp, 0, out, out_cap, row_off_out, bytes_out);
+}
+// the same with the integer field PL behind the record's last; GP in front of it when probs and status are given (bcf_kernels.h)
+MG_EXPORT int mg_encode_calls_bcf_pl_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                            int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
+                                            const void *d_status, const void *d_pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
+                                            void *d_out, size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
+{
+    return encode_calls_bcf_device(c, pl_cells(n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl),
+                                   key_gt, key_gq, key_cov, key_gp, key_pl, d_out, out_cap, d_row_off_out, bytes_out);
+}
+MG_EXPORT int mg_encode_calls_bcf_pl(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                     int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
+                                     const uint8_t *status, const int32_t *pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
+                                     uint8_t *out, size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
+{
+    return encode_calls_bcf_host(c, pl_cells(n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, probs, var_gt_off, status, pl), key_gt, key_gq,
+                                 key_cov, key_gp, key_pl, out, out_cap, row_off_out, bytes_out);
 }
 
 // device milliseconds of the most recent mg_encode_calls_bcf* (rows_stats)

@@ -248,8 +248,10 @@ inline void bcf_put_info(std::string &out, size_t shared_at, const BcfHeader &h,
 // rows[g]: group g's block of one record (planes[g] samples, n_fmt fields, each at the type the group chose).  The cohort's block
 // is appended to `out`: per field the key, the descriptor at the widest of the groups' types -- the smallest type that holds the
 // values of all of them -- and the groups' values one behind the other, sign-extended where a group was narrower (GT's missing
-// code 0 and every other value keep their meaning: no group writes a reserved code of its own type).  A float field (GP of --gp) has
-// one type: nothing to widen, the groups' values are joined as they are.
+// code 0 and every other value keep their meaning).  GT, GQ and COVS never hold a reserved code of their own type; PL of --pl does --
+// the missing code and the end-of-vector code of a narrower group's int8 or int16 become those of the wider type (no VALUE of such a
+// group equals either: its type was chosen to keep them free).  A float field (GP of --gp) has one type: nothing to widen, the groups'
+// values are joined as they are.
 inline void bcf_paste_rows(const std::vector<std::pair<const unsigned char *, size_t>> &rows, const std::vector<uint32_t> &planes, uint32_t n_fmt, std::string &out)
 {
     struct Cur {
@@ -314,7 +316,10 @@ inline void bcf_paste_rows(const std::vector<std::pair<const unsigned char *, si
                 out.append((const char *)cur[g].p, bytes);
                 cur[g].p += bytes;
             } else
-                for (size_t i = 0; i < (size_t)planes[g] * n; ++i) bcf_put_int(out, cur[g].int_of(ts[g]), T);
+                for (size_t i = 0; i < (size_t)planes[g] * n; ++i) {
+                    const int32_t v = cur[g].int_of(ts[g]), missing_g = ts[g] == 1 ? INT8_MIN : INT16_MIN, missing_T = T == 2 ? INT16_MIN : INT32_MIN;
+                    bcf_put_int(out, v == missing_g ? missing_T : v == missing_g + 1 ? missing_T + 1 : v, T);
+                }
         }
     }
     for (const auto &c : cur)

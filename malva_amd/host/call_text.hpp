@@ -56,9 +56,11 @@ inline void per_sample_lines(std::vector<std::string> &outs, const std::vector<R
 
 // --merged as text: the fixed columns (the first group's block; INFO from info_text when info_here, else '.') and the sample columns ([0]: of the lone records, [1]: the others)
 inline void merged_text_lines(std::string &out, const std::vector<Rec> &recs, const std::vector<char> *row_text, const std::vector<uint64_t> *row_off,
-                              const std::vector<char> *info_text, const std::vector<uint64_t> *info_off, bool verbose, bool gp, bool fixed_columns, bool info_here)
+                              const std::vector<char> *info_text, const std::vector<uint64_t> *info_off, bool verbose, bool gp, bool fixed_columns, bool info_here,
+                              bool pl = false)
 {
-    const char *fixed = verbose ? (gp ? "\tPASS\t.\tGT:GQ:COVS:GP" : "\tPASS\t.\tGT:GQ:COVS") : gp ? "\tPASS\t.\tGT:GQ:GP" : "\tPASS\t.\tGT:GQ";
+    const std::string fixed_text = std::string("\tPASS\t.\tGT:GQ") + (verbose ? ":COVS" : "") + (gp ? ":GP" : "") + (pl ? ":PL" : "");
+    const char *fixed = fixed_text.c_str();
     for (const Rec &r : recs) {
         const int w = r.isolated ? 0 : 1;
         if (fixed_columns && info_here) {

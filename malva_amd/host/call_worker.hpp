@@ -33,12 +33,13 @@ struct CallTimes {
     Kind sample;   // --sample-stats: mg_sample_counts
     Kind prior;    // --cohort-priors: mg_genotype_cohort
     Kind estimate; // --prior-groups: mg_estimate_priors
+    Kind pl;       // --pl: mg_phred_likelihoods
     size_t gt_bytes = 0; // panel genotypes handed to mg_cover_blocks[_sparse|_cohort]
 
     CallTimes &operator+=(const CallTimes &o)
     {
         Kind CallTimes::*const kinds[] = {&CallTimes::format, &CallTimes::bcf,   &CallTimes::site,    &CallTimes::pairs,
-                                          &CallTimes::sample, &CallTimes::prior, &CallTimes::estimate};
+                                          &CallTimes::sample, &CallTimes::prior, &CallTimes::estimate, &CallTimes::pl};
         for (auto k : kinds)
             for (int i = 0; i < 3; ++i) (this->*k).ms[i] += (o.*k).ms[i], (this->*k).calls[i] += (o.*k).calls[i];
         gt_bytes += o.gt_bytes;
@@ -52,6 +53,7 @@ struct CallTimes {
         if (sample.calls[0]) g_timers.add("sample table: count kernel (device)", sample.ms[0] / 1000.0);
         if (prior.calls[0]) g_timers.add("cohort priors: kernel (device)", prior.ms[0] / 1000.0);
         if (estimate.calls[0]) g_timers.add("cohort priors: estimate kernel (device)", estimate.ms[0] / 1000.0);
+        if (pl.calls[0]) g_timers.add("merged: likelihood kernel (device)", pl.ms[0] / 1000.0);
         if (bcf.calls[0]) g_timers.add("merged: encode kernels (device)", (bcf.ms[0] + bcf.ms[1] + bcf.ms[2]) / 1000.0);
         if (format.calls[0]) g_timers.add("merged: format kernels (device)", (format.ms[0] + format.ms[1] + format.ms[2]) / 1000.0);
     }
@@ -77,6 +79,10 @@ struct CallTimes {
         }
         if (estimate.calls[0]) {
             snprintf(line, sizeof line, "[malva-geno] cohort-priors: %zu mg_estimate_priors, device ms per call: %.3f\n", estimate.calls[0], estimate.ms[0] / estimate.calls[0]);
+            out += line;
+        }
+        if (pl.calls[0]) {
+            snprintf(line, sizeof line, "[malva-geno] merged: %zu mg_phred_likelihoods, device ms per call: %.3f\n", pl.calls[0], pl.ms[0] / pl.calls[0]);
             out += line;
         }
         if (bcf.calls[0]) {
@@ -145,7 +151,7 @@ struct MergedFormat {
     bool bcf_direct = false; // the cohort runs as one group: whole records leave the workers
     BcfHeader bcf_hdr;
     size_t bcf_samples = 0;  // the cohort's samples
-    uint32_t n_fields(const Options &o) const { return (o.verbose ? 3 : 2) + (o.gp ? 1 : 0); } // GT, GQ, COVS with -v, GP with --gp
+    uint32_t n_fields(const Options &o) const { return (o.verbose ? 3 : 2) + (o.gp ? 1 : 0) + (o.pl ? 1 : 0); } // GT, GQ, COVS with -v, GP with --gp, PL with --pl
 };
 
 // --site-tags: the INFO strings of n records from their counts (mg_format_site_info), whoever holds the device
@@ -265,6 +271,7 @@ private:
                 }
                 return text;
             }
+            if (to.merged && o.pl) phred_likelihoods(dev, job, text.times);
             if (to.merged) merged_rows(dev, job, rows, text.times);
             if (to.pairs) pair_table(dev, job, text);
             if (to.sample_table) sample_table(dev, job, text.times);
@@ -393,12 +400,38 @@ private:
         times.prior.add(&ms, 1);
     }
 
-    // one batch's sample columns: text or BCF, with or without GP and the GQ mask
+    // --pl: the Phred-scaled likelihoods of a batch's cells from its coverages, whoever made those (mg_call_isolated, the record loop, the
+    // group's scratch file): one call over all planes per batch kind
+    void phred_likelihoods(Device &dev, Job &job, CallTimes &times)
+    {
+        Timed t_pl("worker: likelihoods (mg_phred_likelihoods)");
+        for (Batch *b : {&job.iso, &job.gen}) {
+            if (!b->n()) continue;
+            b->pl.resize(P * (size_t)b->var_gt_off.back());
+            dev.check(mg_phred_likelihoods(dev.ctx, b->n(), (uint32_t)P, b->cov.data(), b->var_allele_off.data(), b->var_gt_off.data(), o.error_rate, (int)o.max_coverage,
+                                           o.haploid, o.pl_cap, b->pl.data()),
+                      "mg_phred_likelihoods");
+            float ms = 0;
+            dev.check(mg_pl_stats(dev.ctx, &ms), "mg_pl_stats");
+            times.pl.add(&ms, 1);
+        }
+    }
+
+    // one batch's sample columns: text or BCF, with or without GP, PL and the GQ mask
     int format_rows(Device &dev, Batch &b, std::vector<char> &text, std::vector<uint64_t> &off, uint64_t *need)
     {
         const size_t bn = b.n();
-        const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose || o.gp ? b.var_allele_off.data() : nullptr;
+        const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose || o.gp || o.pl ? b.var_allele_off.data() : nullptr;
         const BcfHeader &hdr = fmt.bcf_hdr;
+        if (o.pl) {
+            const double *probs = o.gp ? b.probs.data() : nullptr;
+            const uint8_t *status = o.gp ? b.status.data() : nullptr;
+            return fmt.bcf_out ? mg_encode_calls_bcf_pl(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao, probs,
+                                                        b.var_gt_off.data(), status, b.pl.data(), hdr.key("GT"), hdr.key("GQ"), o.verbose ? hdr.key("COVS") : 0,
+                                                        o.gp ? hdr.key("GP") : 0, hdr.key("PL"), (uint8_t *)text.data(), text.size(), off.data(), need)
+                               : mg_format_calls_pl(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao, probs,
+                                                    b.var_gt_off.data(), status, b.pl.data(), text.data(), text.size(), off.data(), need);
+        }
         if (o.gp)
             return fmt.bcf_out ? mg_encode_calls_bcf_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
                                                         b.probs.data(), b.var_gt_off.data(), b.status.data(), hdr.key("GT"), hdr.key("GQ"), o.verbose ? hdr.key("COVS") : 0,
@@ -421,7 +454,8 @@ private:
             if (!bn) continue;
             rows.row_off[w].resize(bn + 1);
             rows.row_text[w].resize(bn * (P * (o.haploid ? 8 : 10) + 1) + (o.verbose ? 4 * P * (size_t)b.var_allele_off.back() : 0) +
-                                    (o.gp ? P * (bn + (fmt.bcf_out ? 4 : 9) * (size_t)b.var_gt_off.back()) : 0)); // (a guess: the call says what it needs)
+                                    (o.gp ? P * (bn + (fmt.bcf_out ? 4 : 9) * (size_t)b.var_gt_off.back()) : 0) +
+                                    (o.pl ? P * (bn + (fmt.bcf_out ? 2 : 4) * (size_t)b.var_gt_off.back()) : 0)); // (a guess: the call says what it needs)
             dev.check(call_grown(rows.row_text[w], [&](uint64_t *need) { return format_rows(dev, b, rows.row_text[w], rows.row_off[w], need); }),
                       fmt.bcf_out ? "mg_encode_calls_bcf" : "mg_format_calls");
             float ms[3] = {0, 0, 0};
@@ -496,7 +530,7 @@ private:
             merged_bcf_records(text.merged, job.recs, rows.row_text, rows.row_off, rows.site_ac, rows.site_ns, fmt.bcf_hdr, fmt.n_fields(o), (uint32_t)P, to.merged_fixed,
                                fmt.bcf_direct, tags, fmt.bcf_bgzf);
         else if (to.merged) // (INFO stays '.' in a block: the paste pass puts it in)
-            merged_text_lines(text.merged, job.recs, rows.row_text, rows.row_off, rows.info_text, rows.info_off, o.verbose, o.gp, to.merged_fixed, tags && !to.site_counts);
+            merged_text_lines(text.merged, job.recs, rows.row_text, rows.row_off, rows.info_text, rows.info_off, o.verbose, o.gp, to.merged_fixed, tags && !to.site_counts, o.pl);
         if (!to.per_sample.empty()) per_sample_lines(text.per_sample, job.recs, iso, gen, P, o.haploid, o.verbose, o.max_coverage);
     }
 };

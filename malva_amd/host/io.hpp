@@ -1321,9 +1321,10 @@ inline std::string cleaned_header(const std::vector<std::string> &lines_in, bool
 // DONOR; verbose: the cells carry a COVS field, declared as FORMAT (INFO stays '.', so neither INFO line of the verbose header);
 // site_tags: INFO carries AC / AN / AF / NS, each declared directly in front of #CHROM unless the panel's header declares that ID;
 // contig_lines (the BCF form of the file, host/bcf_out.hpp): lines that go directly in front of those; gp (--gp): the cells carry the
-// genotype posteriors, FORMAT GP declared directly behind the COVS line (or where it would stand) unless the panel's header declares it
+// genotype posteriors, FORMAT GP declared directly behind the COVS line (or where it would stand) unless the panel's header declares it;
+// pl (--pl): the cells carry the Phred-scaled likelihoods, FORMAT PL declared behind GP's line (or where that would stand), likewise
 inline std::string merged_header(const std::vector<std::string> &lines_in, bool verbose, const std::vector<std::string> &names, bool site_tags = false,
-                                 const std::vector<std::string> &contig_lines = {}, bool gp = false)
+                                 const std::vector<std::string> &contig_lines = {}, bool gp = false, bool pl = false)
 {
     std::vector<std::string> lines = lines_in;
     const std::string covs = "##FORMAT=<ID=COVS";
@@ -1336,6 +1337,10 @@ inline std::string merged_header(const std::vector<std::string> &lines_in, bool 
     bool gp_declared = false;
     for (const auto &l : lines) gp_declared = gp_declared || (l.compare(0, gp_id.size(), gp_id) == 0 && (l[gp_id.size()] == ',' || l[gp_id.size()] == '>'));
     if (gp && !gp_declared) out += gp_id + ",Number=G,Type=Float,Description=\"Genotype posterior probabilities\">\n";
+    const std::string pl_id = "##FORMAT=<ID=PL";
+    bool pl_declared = false;
+    for (const auto &l : lines) pl_declared = pl_declared || (l.compare(0, pl_id.size(), pl_id) == 0 && (l[pl_id.size()] == ',' || l[pl_id.size()] == '>'));
+    if (pl && !pl_declared) out += pl_id + ",Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods from the allele coverages, prior-free (no allele frequency enters), capped\">\n";
     for (const auto &l : contig_lines) out += l + "\n";
     if (site_tags) {
         static const char *const tags[4][2] = {{"AC", "A,Type=Integer,Description=\"Allele count in called genotypes, for each ALT allele\""},

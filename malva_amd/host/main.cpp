@@ -80,6 +80,14 @@ const char *USAGE =
     "                                        numbers behind GTS= of -v, six decimals -- formatted on the GPU; '.' for a record without\n"
     "                                        a likelihood list (no coverage, one allele, over-covered).  With and without -v; a cell\n"
     "                                        masked by --min-gq keeps its GP; in BCF a float32 vector.  The files of -o are not touched [this build]\n"
+    "          --pl                          --merged: every cell carries a further field PL (Number=G, Type=Integer; FORMAT is\n"
+    "                                        GT:GQ[:COVS][:GP]:PL): the Phred-scaled likelihood of every genotype in VCF order, made on\n"
+    "                                        the GPU from the cell's coverages WITHOUT the allele-frequency prior (GP has it folded in,\n"
+    "                                        with re-estimated priors their estimate): what Beagle, GLIMPSE or bcftools +fill-tags\n"
+    "                                        read.  The best genotype is 0, the others round(10 log10 of the ratio), capped; a cell\n"
+    "                                        without coverage is all zeros, an over-covered one '.'.  The values do not depend on the\n"
+    "                                        priors, on -v, on GP or on the GQ mask; in BCF an integer vector.  The files of -o are not touched [this build]\n"
+    "          --pl-cap                      --pl: the largest value written, 1..2147483647 (default:255, the bcftools convention) [this build]\n"
     "          --min-gq                      --merged: a cell whose GQ is below this integer prints its genotype as missing ('./.',\n"
     "                                        haploid '.'); its :GQ (and :COVS) stay.  The files of -o are not touched        [this build]\n"
     "          --site-tags                   --merged: INFO becomes AC=..;AN=..;AF=..;NS=.. over the called (not masked) cells of the\n"
@@ -166,6 +174,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"cohort-priors", no_argument, nullptr, 1012},  {"prior-iters", required_argument, nullptr, 1013},
                                       {"prior-weight", required_argument, nullptr, 1014}, {"priors-out", required_argument, nullptr, 1015},
                                       {"prior-groups", no_argument, nullptr, 1016},
+                                      {"pl", no_argument, nullptr, 1017},             {"pl-cap", required_argument, nullptr, 1018},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -265,6 +274,18 @@ bool parse_arguments(int argc, char **argv, Options &o)
             }
             break;
         case 1016: o.priors.groups = true; break;
+        case 1017: o.pl = true; break;
+        case 1018: {
+            long long v = 0;
+            if (!(arg >> v) || !(arg >> std::ws).eof() || v < 1 || v > INT32_MAX) {
+                std::cerr << "malva : --pl-cap takes a whole number 1.." << INT32_MAX << "\n";
+                die = true;
+            } else {
+                o.pl_cap_given = true;
+                o.pl_cap = (int32_t)v;
+            }
+            break;
+        }
         case 'v': o.verbose = true; break;
         case '1': o.haploid = true; break;
         case '?': die = true; break;
@@ -300,6 +321,14 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.merged.empty() && o.gp) {
         std::cerr << "malva : --gp goes with --merged\n";
+        die = true;
+    }
+    if (o.merged.empty() && o.pl) {
+        std::cerr << "malva : --pl goes with --merged\n";
+        die = true;
+    }
+    if (o.pl_cap_given && !o.pl) {
+        std::cerr << "malva : --pl-cap goes with --pl\n";
         die = true;
     }
     if (o.cohort && o.gpus > 1) {
@@ -1369,14 +1398,14 @@ int call_main(const Options &o)
             if (bcf_out) { // the text header with a ##contig line per reference sequence where the panel's header has none
                 const bool declared = bcf_has_contig_lines(hdr.header_lines);
                 merged_fmt.bcf_hdr = bcf_parse_header(merged_header(hdr.header_lines, o.verbose, names, o.site_tags,
-                                                         declared ? std::vector<std::string>() : bcf_contig_lines(refs.names, refs.seqs), o.gp),
+                                                         declared ? std::vector<std::string>() : bcf_contig_lines(refs.names, refs.seqs), o.gp, o.pl),
                                            declared);
                 merged_fmt.bcf_samples = samples.size();
                 const std::string head = merged_fmt.bcf_hdr.file_head();
                 if (bcf_bgzf) bgzf_append(head.data(), head.size(), merged_head);
                 else merged_head = head;
             } else
-                merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags, {}, o.gp);
+                merged_head = merged_header(hdr.header_lines, o.verbose, names, o.site_tags, {}, o.gp, o.pl);
         }
         bool merged_direct = false; // one group: no temporary blocks
         std::vector<uint32_t> group_planes; // the samples of every group, in the order they ran

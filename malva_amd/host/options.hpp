@@ -26,6 +26,9 @@ struct Options { // argument_parser.hpp:51-66
     bool site_tags = false; // --site-tags: AC / AN / AF / NS in the merged output's INFO
     std::string merged_format; // --merged-format: vcf (or empty: not given), bcf, ubcf
     bool gp = false;        // --gp: the genotype posteriors as the FORMAT field GP of the merged output
+    bool pl = false;        // --pl: the prior-free Phred-scaled likelihoods as the FORMAT field PL of the merged output
+    bool pl_cap_given = false;
+    int32_t pl_cap = 255;   // --pl-cap: the largest PL written (the bcftools convention)
     std::string pairs;      // --pairs: the table of pairwise genotype sharing
     std::string sample_stats; // --sample-stats: the per-sample QC table
     PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)

@@ -268,6 +268,7 @@ struct Batch : BlockArrays { // inputs of mg_call_isolated (the lone arrays) or 
     std::vector<double> probs;
     std::vector<float> freq_out;   // --cohort-priors: the re-estimated frequencies, as freq
     std::vector<uint32_t> n_inf;   // --cohort-priors: per record, the planes that counted
+    std::vector<int32_t> pl;       // --pl: [plane][genotype slot], a record's values in VCF order (mg_phred_likelihoods)
 };
 
 // --sample-stats: the kind of the ALT allele `alt` of a record whose REF is `ref`, from the strings as the record prints them (the class

@@ -178,6 +178,15 @@ int mg_site_stats(mg_ctx *c, float *ms) { return stats(c, "mg_site_stats", ms, {
 int mg_pairs_stats(mg_ctx *c, float *ms) { return stats(c, "mg_pairs_stats", ms, {9, 10}); }
 int mg_sample_stats(mg_ctx *c, float *ms) { return stats(c, "mg_sample_stats", ms, {11}); }
 int mg_cohort_prior_stats(mg_ctx *c, float *ms) { return stats(c, "mg_cohort_prior_stats", ms, {12}); }
+int mg_pl_stats(mg_ctx *c, float *ms) { return stats(c, "mg_pl_stats", ms, {13}); }
+// every value of every plane's slice is written: 7
+int mg_phred_likelihoods(mg_ctx *c, size_t n, uint32_t planes, const uint32_t *cov, const uint32_t *vao, const uint64_t *var_gt_off, float, int, int, int32_t cap, int32_t *pl_out)
+{
+    touch(cov, planes * vao[n]);
+    say(c, "mg_phred_likelihoods n=%zu planes=%u cap=%d", n, planes, (int)cap);
+    for (size_t i = 0; i < planes * var_gt_off[n]; ++i) pl_out[i] = 7;
+    return MG_OK;
+}
 
 // the five row makers: record r's row is "\tR<r>\n"; the whole capacity they are given is written first
 static int rows(mg_ctx *c, const char *name, size_t n, uint32_t planes, const int32_t *gt1, const uint32_t *cov, char *out, size_t cap, uint64_t *off, uint64_t *need)
@@ -228,6 +237,26 @@ int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n, uint32_t planes, int, const int3
 {
     touch(probs, planes * var_gt_off[n]);
     return rows(c, "mg_encode_calls_bcf_gp", n, planes, gt1, cov, (char *)out, cap, off, need);
+}
+int mg_format_calls_pl(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *vao,
+                       const double *probs, const uint64_t *var_gt_off, const uint8_t *status, const int32_t *pl, char *out, size_t cap, uint64_t *off, uint64_t *need)
+{
+    touch(vao, n + 1);
+    if (probs) touch(probs, planes * var_gt_off[n]), touch(status, planes * n);
+    for (size_t i = 0; i < planes * var_gt_off[n]; ++i)
+        if (pl[i] != 7) abort(); // (what mg_phred_likelihoods left)
+    return rows(c, probs ? "mg_format_calls_pl+gp" : "mg_format_calls_pl", n, planes, gt1, cov, out, cap, off, need);
+}
+int mg_encode_calls_bcf_pl(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *vao,
+                           const double *probs, const uint64_t *var_gt_off, const uint8_t *status, const int32_t *pl, int32_t, int32_t, int32_t, int32_t, int32_t key_pl,
+                           uint8_t *out, size_t cap, uint64_t *off, uint64_t *need)
+{
+    touch(vao, n + 1);
+    if (probs) touch(probs, planes * var_gt_off[n]), touch(status, planes * n);
+    for (size_t i = 0; i < planes * var_gt_off[n]; ++i)
+        if (pl[i] != 7) abort();
+    if (key_pl != 8) abort(); // (small_header's ninth ID)
+    return rows(c, probs ? "mg_encode_calls_bcf_pl+gp" : "mg_encode_calls_bcf_pl", n, planes, gt1, cov, (char *)out, cap, off, need);
 }
 int mg_site_counts(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int use_mask, int32_t, const uint32_t *vao, int accumulate,
                    uint32_t *ac, uint32_t *ns)
@@ -707,7 +736,7 @@ static BcfHeader small_header()
 {
     return bcf_parse_header("##fileformat=VCFv4.2\n##contig=<ID=c1>\n##INFO=<ID=AC,Number=A,Type=Integer>\n##INFO=<ID=AN,Number=1,Type=Integer>\n"
                             "##INFO=<ID=AF,Number=A,Type=Float>\n##INFO=<ID=NS,Number=1,Type=Integer>\n##FORMAT=<ID=GT,Number=1,Type=String>\n"
-                            "##FORMAT=<ID=GQ,Number=1,Type=Integer>\n##FORMAT=<ID=GP,Number=G,Type=Float>\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\ts1\ts2\n",
+                            "##FORMAT=<ID=GQ,Number=1,Type=Integer>\n##FORMAT=<ID=GP,Number=G,Type=Float>\n##FORMAT=<ID=PL,Number=G,Type=Integer>\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\ts1\ts2\n",
                             true);
 }
 static void check_merged_rows()
@@ -740,6 +769,46 @@ static void check_merged_rows()
         if (!f.bcf)
             CHECK(slurp(s.merged.path) == "c1\t101\t.\tA\tG" + fixed + "R0\n" + "c1\t301\t.\tC\tG" + fixed + "R1\n" + "c1\t501\t.\tA\tG" + fixed + "R0\n" + "c1\t511\t.\tC\tG" + fixed + "R1\n");
         else CHECK(slurp(s.merged.path).size() > 4 * 4);
+    }
+    // --pl: one mg_phred_likelihoods over both planes per batch kind, in front of the rows; the *_pl row makers with and without GP and the mask.
+    // The guess: 42, with PL 2 (2 + 4 * 6) more as text and 2 (2 + 2 * 6) as BCF, with GP what GP adds
+    struct PlForm {
+        bool bcf, gp, min_gq;
+        const char *name;
+        size_t guess;
+    };
+    const PlForm pl_forms[] = {{false, false, false, "mg_format_calls_pl", 94},        {false, true, true, "mg_format_calls_pl+gp", 206},
+                               {true, false, true, "mg_encode_calls_bcf_pl", 70},      {true, true, false, "mg_encode_calls_bcf_pl+gp", 122}};
+    for (const PlForm &f : pl_forms) {
+        Scene s;
+        s.o.pl = true, s.o.pl_cap = 99, s.o.gp = f.gp, s.o.use_min_gq = f.min_gq, s.o.min_gq = 20;
+        s.fmt.bcf_out = f.bcf, s.fmt.bcf_direct = true, s.fmt.bcf_hdr = small_header();
+        s.ctx().n_planes = 2;
+        s.ctx().first_need = 1000;
+        s.with_merged();
+        s.run(2, 2, mixed_batch(2, false));
+        const std::string first = std::string(f.name) + " n=2 planes=2 cap=" + std::to_string(f.guess) + " cov=0", second = std::string(f.name) + " n=2 planes=2 cap=1000 cov=0";
+        const char *read_stats = f.bcf ? "mg_bcf_stats" : "mg_format_stats", *pl_call = "mg_phred_likelihoods n=2 planes=2 cap=99";
+        CHECK(only(s.ctx().log, {"mg_format", "mg_encode", "mg_bcf", "mg_site", "mg_phred", "mg_pl_"}) ==
+              Log({pl_call, "mg_pl_stats", pl_call, "mg_pl_stats", first, second, read_stats, first, second, read_stats})); // both kinds' likelihoods, then both kinds' rows
+        CHECK(same_kind(s.total.pl, {26}, {2}));
+        CHECK(s.fmt.n_fields(s.o) == (f.gp ? 4u : 3u));
+        s.merged.close();
+        const std::string fixed = f.gp ? "\t.\tPASS\t.\tGT:GQ:GP:PL\t" : "\t.\tPASS\t.\tGT:GQ:PL\t";
+        if (!f.bcf)
+            CHECK(slurp(s.merged.path) == "c1\t101\t.\tA\tG" + fixed + "R0\n" + "c1\t301\t.\tC\tG" + fixed + "R1\n" + "c1\t501\t.\tA\tG" + fixed + "R0\n" + "c1\t511\t.\tC\tG" + fixed + "R1\n");
+        else CHECK(slurp(s.merged.path).size() > 4 * 4);
+    }
+    {
+        CallTimes t; // the likelihoods' line of the report and their label
+        const float ms = 3;
+        t.pl.add(&ms, 1), t.pl.add(&ms, 1);
+        g_timers.on = true;
+        CHECK(t.report() == "[malva-geno] merged: 2 mg_phred_likelihoods, device ms per call: 3.000\n");
+        t.add_to_timers();
+        CHECK(g_timers.acc.size() == 1 && g_timers.acc.at("merged: likelihood kernel (device)") == 0.006);
+        g_timers.on = false;
+        g_timers.acc.clear();
     }
     for (int where = 0; where < 3; ++where) { // --site-tags: INFO made at once (text, the group is the cohort) | the counts to a file | BCF (INFO made on the host)
         Scene s;
