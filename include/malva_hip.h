@@ -475,70 +475,62 @@ int mg_call_isolated_device(mg_ctx *ctx, size_t n_vars, const void *d_pos, const
                             void *d_probs, const void *d_var_gt_off);
 
 /* ---- the sample columns of a multi-sample VCF ------------------------------------
- * The GT/GQ print of VB::output_variants (var_block.hpp:337-396), which the reference does for its one individual, repeated
- * per sample: the reference has no multi-sample output.  gt1 / gt2 / gq are [n_planes][n_vars] int32, plane-major, as n_planes
- * calls of mg_genotype / mg_call_isolated fill them (n_planes 1..64; the context need not be in cohort mode: the call formats
- * arrays and reads no counters; gt2 is not read in haploid mode and may then be NULL).  Row v is
- * text_out[row_off_out[v] .. row_off_out[v + 1]): for every plane in order a tab and the cell, then '\n'.  The cell is
- * `<gt1>:<gq>` in haploid mode, else `<gt1>/<gt2>:<gq>`; with cov ([n_planes][slots], slots = var_allele_off[n_vars]) and
- * var_allele_off ([n_vars + 1]) -- both or neither -- a third field follows: ':' and the record's coverages of that plane,
- * comma-separated.  Every number prints as std::to_string(int) prints it, a coverage as std::to_string((int)cov).
+ * mg_cells: the cells of a batch, as the encoders of this section and of the BCF section below take them.  Pointer members hold host
+ * pointers in a host form and device pointers in a _device form.  `fields` says which optional FORMAT fields are made; an array
+ * whose bit is not set is not read and may be NULL.
+ *   always        gt1 / gt2 / gq: [n_planes][n_vars] int32, plane-major, as n_planes calls of mg_genotype / mg_call_isolated fill them
+ *                 (n_planes 1..64; gt2 is not read in haploid mode and may then be NULL).  use_mask != 0: a cell whose gq < min_gq has
+ *                 its genotype made missing and keeps every other field.  cov ([n_planes][slots] uint32, slots =
+ *                 var_allele_off[n_vars]) is optional and adds the field COVS; var_allele_off is [n_vars + 1] uint32.  With neither
+ *                 bit set, cov and var_allele_off are given both or neither.  allele_class is not read by an encoder.
+ *   MG_CELLS_GP   the field GP behind GT, GQ and COVS.  Requires var_allele_off and var_gt_off ([n_vars + 1] uint64) with or without
+ *                 cov, and with n_vars > 0 probs and status.  The values are the doubles mg_genotype / mg_call_isolated leave in
+ *                 probs (gt.second / total_qual, var_block.hpp:381: the numbers behind GTS= of the single-sample output): probs is
+ *                 [n_planes][var_gt_off[n_vars]], record v's values of plane p start at probs[p * var_gt_off[n_vars] +
+ *                 var_gt_off[v]]; status is [n_planes][n_vars] uint8.  The record has A = var_allele_off[v + 1] - var_allele_off[v]
+ *                 alleles and G = A (haploid) or A (A + 1) / 2 genotypes.  probs holds them in the reference's order -- a outer,
+ *                 c >= a inner: 0/0, 0/1, 0/2, 1/1, .. -- and GP is in VCF order, genotype j/k (j <= k) at index k (k + 1) / 2 + j:
+ *                 0/0, 0/1, 1/1, 0/2, ..; haploid: the index is the allele.  A cell whose status is not MG_GT_NORMAL has no GP and
+ *                 its probs are not read.  A value is PRINTABLE when its sign bit is clear and 0 <= p <= 1 -- NaN, -0.0,
+ *                 negatives, anything above 1 and the infinities are not.
+ *   MG_CELLS_PL   the field PL behind the cell's last.  Requires var_allele_off, var_gt_off and, with n_vars > 0, pl:
+ *                 [n_planes][var_gt_off[n_vars]] int32, a record's G values ALREADY in VCF order (what mg_phred_likelihoods leaves;
+ *                 the encoder copies and does not permute).  probs and status are given both or neither (and both with
+ *                 MG_CELLS_GP).  The encoder does not know where the integers came from: any int32 is a value, MG_PL_MISSING alone
+ *                 is special.  A masked cell keeps its PL.
+ * mg_format_calls: the GT/GQ print of VB::output_variants (var_block.hpp:337-396), which the reference does for its one individual,
+ * repeated per sample: the reference has no multi-sample output.  The context need not be in cohort mode: the call formats arrays
+ * and reads no counters.  Row v is text_out[row_off_out[v] .. row_off_out[v + 1]): for every plane in order a tab and the cell,
+ * then '\n'.  The cell is `GT:GQ[:COVS][:GP][:PL]`.  GT is `<gt1>` in haploid mode, else `<gt1>/<gt2>`, under the mask `.` or `./.`;
+ * COVS the record's coverages of that plane, comma-separated.  Every integer prints as std::to_string(int) prints it, a coverage as
+ * std::to_string((int)cov).  GP is the G comma-separated values (none for a record without alleles), or one `.` for a cell that is
+ * not MG_GT_NORMAL; a printable value prints exactly as printf("%f") prints it, always 8 bytes, `0.dddddd` or `1.000000`: rounded to
+ * nearest on the exact binary value, ties to even, as glibc does, in integers (N = m 10^6 with m the 53-bit significand, q = N >> s,
+ * s = 1075 - the biased exponent, and the remainder against 2^(s-1)); an unprintable one prints `.`.  PL is the G comma-separated
+ * values, MG_PL_MISSING as `.`; the whole field is one `.` when G == 0 or every value of the cell is missing.
  * n_vars == 0 is legal: row_off_out[0] = 0.  *text_bytes_out always receives the bytes the text needs; when that is more
  * than text_cap the call returns MG_ERR_LIMIT, nothing is written at or behind text_cap, row_off_out is valid all the
- * same, and the caller may come again with a larger buffer.  The host form synchronises; the device form is asynchronous on
- * the context's stream until it reads the 8-byte total back (text_bytes_out is a HOST pointer in both).
+ * same, and the caller may come again with a larger buffer.  A NULL cells pointer: MG_ERR_ARG.  The host form synchronises; the
+ * device form is asynchronous on the context's stream until it reads the 8-byte total back (text_bytes_out is a HOST pointer in both).
  * mg_format_stats (waits for it): ms_out[3], device milliseconds of the most recent call's length pass, scan and write pass. */
-int mg_format_calls(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
-                    const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
-                    uint64_t *text_bytes_out);
-int mg_format_calls_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
-                           const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
-                           uint64_t *text_bytes_out);
-int mg_format_stats(mg_ctx *ctx, float *ms_out);
-/* mg_format_calls with a GQ mask: a cell whose gq < min_gq prints its genotype as missing -- `.` in haploid mode, else `./.` --
- * and keeps its `:<gq>` and coverage fields.  Everything else, the buffer contract and mg_format_stats included, is
- * mg_format_calls'; with a min_gq no cell is below, the text is mg_format_calls' byte for byte. */
-int mg_format_calls_masked(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
-                           int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
-                           uint64_t *row_off_out, uint64_t *text_bytes_out);
-int mg_format_calls_masked_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
-                                  int32_t min_gq, const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
-                                  void *d_row_off_out, uint64_t *text_bytes_out);
-/* mg_format_calls_masked (the mask applies when use_mask != 0) with the genotype posteriors of every cell, the FORMAT field GP
- * (Number=G, Type=Float), behind the cell's last field: `:` and the list, so a cell is `GT:GQ:GP` or, with cov, `GT:GQ:COVS:GP`.
- * The values are the doubles mg_genotype / mg_call_isolated leave in probs (gt.second / total_qual, var_block.hpp:381: the
- * numbers behind GTS= of the single-sample output): probs is [n_planes][var_gt_off[n_vars]], record v's values of plane p start
- * at probs[p * var_gt_off[n_vars] + var_gt_off[v]] (var_gt_off: [n_vars + 1]); status is [n_planes][n_vars].  var_allele_off is
- * required with or without cov (cov stays optional): the record has A = var_allele_off[v + 1] - var_allele_off[v] alleles and
- * G = A (haploid) or A (A + 1) / 2 genotypes.  probs holds them in the reference's order -- a outer, c >= a inner: 0/0, 0/1,
- * 0/2, 1/1, .. -- and GP is in VCF order, genotype j/k (j <= k) at index k (k + 1) / 2 + j: 0/0, 0/1, 1/1, 0/2, ..; haploid:
- * the index is the allele.  A cell whose status is not MG_GT_NORMAL prints the whole field as one `.` and its probs are not
- * read; otherwise G comma-separated values (none for a record without alleles).  A value is PRINTABLE when its sign bit is
- * clear and 0 <= p <= 1 -- NaN, -0.0, negatives, anything above 1 and the infinities are not -- and prints exactly as
- * printf("%f") prints it, always 8 bytes, `0.dddddd` or `1.000000`: rounded to nearest on the exact binary value, ties to even,
- * as glibc does, in integers (N = m 10^6 with m the 53-bit significand, q = N >> s, s = 1075 - the biased exponent, and the
- * remainder against 2^(s-1)).  An unprintable value prints `.`.  A masked cell keeps its GP as it keeps `:GQ` and `:COVS`.
- * Everything else -- rows, buffer contract, n_vars == 0, the two forms, mg_format_stats -- is mg_format_calls'. */
-int mg_format_calls_gp(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                       int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                       const uint8_t *status, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out);
-int mg_format_calls_gp_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                              int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                              const void *d_status, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out);
-/* mg_format_calls_gp with a further field PL (Number=G, Type=Integer) behind the cell's last; GP itself becomes optional: probs and
- * status are given both or neither, and with neither there is no GP.  A cell is `GT:GQ[:COVS][:GP]:PL`.  pl is required:
- * [n_planes][var_gt_off[n_vars]] int32, a record's G values ALREADY in VCF order (what mg_phred_likelihoods leaves; the encoder
- * copies and does not permute).  var_allele_off and var_gt_off are required.  The encoder formats integers and does not know where
- * they came from: any int32 is a value and prints as std::to_string(int) prints it, MG_PL_MISSING alone is special and prints `.`.
- * The field is `:` and the G comma-separated values; the whole field is one `.` when G == 0 or every value of the cell is
- * missing.  A masked cell keeps its PL.  Everything else is mg_format_calls'. */
+#define MG_CELLS_GP 1u
+#define MG_CELLS_PL 2u
 #define MG_PL_MISSING INT32_MIN
-int mg_format_calls_pl(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                       int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                       const uint8_t *status, const int32_t *pl, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out);
-int mg_format_calls_pl_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                              int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                              const void *d_status, const void *d_pl, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out);
+typedef struct mg_cells {
+    size_t n_vars;
+    uint32_t n_planes;
+    int haploid;
+    const void *gt1, *gt2, *gq;
+    int use_mask;
+    int32_t min_gq;
+    const void *cov, *var_allele_off;
+    const void *probs, *var_gt_off, *status, *pl;
+    const void *allele_class; /* mg_sample_counts' own; no encoder reads it */
+    uint32_t fields;          /* MG_CELLS_GP | MG_CELLS_PL */
+} mg_cells;
+int mg_format_calls(mg_ctx *ctx, const mg_cells *cells, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out);
+int mg_format_calls_device(mg_ctx *ctx, const mg_cells *cells, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out);
+int mg_format_stats(mg_ctx *ctx, float *ms_out);
 
 /* ---- the site tags of a multi-sample VCF (AC / AN / AF / NS) -----------------------
  * mg_site_counts: the allele counts of every record over the planes.  gt1 / gt2 / gq as for mg_format_calls (n_planes 1..64;
@@ -693,7 +685,7 @@ int mg_sample_stats(mg_ctx *ctx, float *ms_out);
  *   the following iterations would repeat it.
  * Outputs after T iterations: freq_out[slots] = f_T; n_informative[v] = n of the last iteration that ran; gt1 / gt2 / gq / status
  * [n_planes][n_vars], every plane's cell as mg_genotype makes it from (cov_p, f_T); probs (optional, with var_gt_off
- * [n_vars + 1]) [n_planes][var_gt_off[n_vars]], laid out as mg_format_calls_gp reads it.
+ * [n_vars + 1]) [n_planes][var_gt_off[n_vars]], laid out as mg_cells takes it.
  * Numerics: nothing is contracted into an FMA; every logf and exp is mg_genotype's restatement of the host libm's, every ln(n)
  * for n < 65536 its host-made table, so with every record's total coverage below 65536 the whole result is bit-identical to a
  * CPU restatement of the above.  At or beyond that total: the cells of a record the entry does not re-estimate are computed
@@ -749,60 +741,41 @@ int mg_estimate_priors_stats(mg_ctx *ctx, float *ms_out);
 
 /* ---- the sample columns of a multi-sample BCF --------------------------------------
  * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
- * parity with htslib unpinned).  Arrays, n_planes (1..64), the host and _device forms, the stream behaviour and the buffer
- * contract are mg_format_calls_masked's: *bytes_out (a HOST pointer in both forms) always receives the bytes needed,
+ * parity with htslib unpinned).  The cells (mg_cells, with its field rules), the host and _device forms, the stream behaviour and
+ * the buffer contract are mg_format_calls': *bytes_out (a HOST pointer in both forms) always receives the bytes needed,
  * MG_ERR_LIMIT when that exceeds out_cap, nothing written at or behind out_cap, row_off_out valid all the same, n_vars == 0
  * legal.  Row v = out[row_off_out[v] .. row_off_out[v + 1]) is exactly the record's per-sample ("indiv") block, its length the
- * record's l_indiv: two fields, three with cov (cov and var_allele_off: both or neither), in this order --
- *   GT    typed_int(key_gt),  desc(ploidy, T), for every plane `ploidy` values (1 in haploid mode, else 2): allele index a
+ * record's l_indiv: two fields, and one more each with cov, MG_CELLS_GP and MG_CELLS_PL, in this order --
+ *   GT    typed_int(keys->gt),  desc(ploidy, T), for every plane `ploidy` values (1 in haploid mode, else 2): allele index a
  *         as (a + 1) << 1, unphased; a cell with use_mask != 0 and gq < min_gq writes 0 (missing) for each of its values
- *   GQ    typed_int(key_gq),  desc(1, T), one value per plane, as it is, mask or no mask
- *   COVS  typed_int(key_cov), desc(A, T), for every plane the record's A = var_allele_off[v + 1] - var_allele_off[v] values
+ *   GQ    typed_int(keys->gq),  desc(1, T), one value per plane, as it is, mask or no mask
+ *   COVS  typed_int(keys->cov), desc(A, T), for every plane the record's A = var_allele_off[v + 1] - var_allele_off[v] values
  *         (int32_t)cov[..]
+ *   GP    typed_int(keys->gp),  desc(G, 5), for every plane the record's G float32
+ *   PL    typed_int(keys->pl),  desc(G, T), for every plane the record's G values of type T
  * desc(n, t): the byte n << 4 | t for n < 15, else 0xF0 | t and typed_int(n).  typed_int(x): desc(1, t) and x in the smallest of
  * int8 (t = 1), int16 (2), int32 (3) that holds it.  Little endian.  T of a field of a record is the smallest type holding every
  * value of the field over all planes with BCF's reserved codes kept free: int8 for [-120, 127], int16 for [-32760, 32767], else
  * int32 (a field without values: int8).  An int32 value inside int32's reserved range [INT32_MIN, INT32_MIN + 7] is written as
  * it is: what a reader makes of it is the caller's business.
+ * GP: a printable value is stored as (float)p, IEEE round to nearest even, float denormals kept (1e-40 does not become 0; the
+ * conversion is done in integers); an unprintable one as the missing float 0x7F800001; a cell that is not MG_GT_NORMAL as
+ * 0x7F800001 followed by G - 1 end-of-vector floats 0x7F800002, which is what `.` for a vector is in BCF.
+ * PL: T is the smallest type that holds every value of the field over all planes that is not MG_PL_MISSING, by the rule above (a
+ * field without such a value: int8).  MG_PL_MISSING is written as T's missing code -- 0x80, 0x8000, 0x80000000, in int32 the
+ * sentinel itself --, a cell whose values are all missing as that code followed by G - 1 end-of-vector codes (0x81, 0x8001,
+ * 0x80000001).
  * Where this departs from the text: an allele index outside [0, 2^30 - 2] has no code and writes 0 (missing), where
- * mg_format_calls prints the index as it is.  The keys are the header's dictionary indexes, >= 0 (key_cov is not read without cov).
+ * mg_format_calls prints the index as it is.  mg_bcf_keys holds the header's dictionary indexes, >= 0; cov, gp and pl are not read
+ * without cov, MG_CELLS_GP and MG_CELLS_PL.  A NULL cells or keys pointer: MG_ERR_ARG.
  * mg_bcf_stats (waits): ms_out[3], device milliseconds of the most recent call's length pass, scan and write pass;
  * MG_ERR_STATE before the first call. */
-int mg_encode_calls_bcf(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                        int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
-                        size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out);
-int mg_encode_calls_bcf_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                               int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
-                               size_t out_cap, void *d_row_off_out, uint64_t *bytes_out);
-/* mg_encode_calls_bcf with a further field behind GT, GQ and COVS (cov stays optional; var_allele_off is required) --
- *   GP    typed_int(key_gp),  desc(G, 5), for every plane the record's G float32
- * probs, var_gt_off, status, G, the order and PRINTABLE as for mg_format_calls_gp.  A printable value is stored as (float)p,
- * IEEE round to nearest even, float denormals kept (1e-40 does not become 0; the conversion is done in integers); an
- * unprintable one as the missing float 0x7F800001; a cell that is not MG_GT_NORMAL as 0x7F800001 followed by G - 1
- * end-of-vector floats 0x7F800002, which is what `.` for a vector is in BCF.  desc takes its long form from G = 15. */
-int mg_encode_calls_bcf_gp(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                           int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                           const uint8_t *status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap,
-                           uint64_t *row_off_out, uint64_t *bytes_out);
-int mg_encode_calls_bcf_gp_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                  int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                                  const void *d_status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap,
-                                  void *d_row_off_out, uint64_t *bytes_out);
-/* mg_encode_calls_bcf_gp with a further field behind the record's last; GP becomes optional (probs and status: both or neither),
- * pl, var_allele_off and var_gt_off are required, as for mg_format_calls_pl --
- *   PL    typed_int(key_pl),  desc(G, T), for every plane the record's G values of type T
- * T is the smallest type that holds every value of the field over all planes that is not MG_PL_MISSING, by the rule above (a field
- * without such a value: int8).  MG_PL_MISSING is written as T's missing code -- 0x80, 0x8000, 0x80000000, in int32 the sentinel
- * itself --, a cell whose values are all missing as that code followed by G - 1 end-of-vector codes (0x81, 0x8001, 0x80000001).
- * desc takes its long form from G = 15.  key_gp is not read without GP. */
-int mg_encode_calls_bcf_pl(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                           int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                           const uint8_t *status, const int32_t *pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
-                           uint8_t *out, size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out);
-int mg_encode_calls_bcf_pl_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                  int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                                  const void *d_status, const void *d_pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
-                                  void *d_out, size_t out_cap, void *d_row_off_out, uint64_t *bytes_out);
+typedef struct mg_bcf_keys {
+    int32_t gt, gq, cov, gp, pl;
+} mg_bcf_keys;
+int mg_encode_calls_bcf(mg_ctx *ctx, const mg_cells *cells, const mg_bcf_keys *keys, uint8_t *out, size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out);
+int mg_encode_calls_bcf_device(mg_ctx *ctx, const mg_cells *cells, const mg_bcf_keys *keys, void *d_out, size_t out_cap, void *d_row_off_out,
+                               uint64_t *bytes_out);
 int mg_bcf_stats(mg_ctx *ctx, float *ms_out);
 
 /* ---- Phred-scaled genotype likelihoods (PL), prior-free -----------------------------
@@ -811,7 +784,7 @@ int mg_bcf_stats(mg_ctx *ctx, float *ms_out);
  * plane-major, as mg_genotype_cohort takes it; pl_out is [n_planes][var_gt_off[n_vars]]; n_planes is 1..64, cap >= 1; n_vars == 0 is
  * legal.  A bad argument returns MG_ERR_ARG and writes nothing.
  * The values of a record are in VCF order: genotype j/k (j <= k) at index k (k + 1) / 2 + j of the record's slice, in haploid mode
- * the allele (probs of the genotype calls is in the reference's order; mg_format_calls_pl / mg_encode_calls_bcf_pl copy).
+ * the allele (probs of the genotype calls is in the reference's order; the encoders copy under MG_CELLS_PL).
  * The cell (p, v), A the record's alleles, G = A (haploid) or A (A + 1) / 2:
  *   1. if any (int)cov[a] > max_cov, all G values are MG_PL_MISSING (the over-covered cell the reference refuses to genotype);
  *   2. if A == 1, the one value is 0 and nothing is computed;

@@ -111,13 +111,9 @@ def lib():
         "mg_cohort_info": [vp, vp, vp],
         "mg_cover_blocks_cohort_device": [vp, vp, vp, vp, vp, it, vp, vp],
         "mg_cohort_stats": [vp, vp],
-        "mg_format_calls": [vp, sz, u32, it, vp, vp, vp, vp, vp, vp, sz, vp, vp],
-        "mg_format_calls_device": [vp, sz, u32, it, vp, vp, vp, vp, vp, vp, sz, vp, vp],
+        "mg_format_calls": [vp, C.POINTER(Cells), vp, sz, vp, vp],          # (typed: anything but a Cells or None is an ArgumentError, not a wild pointer)
+        "mg_format_calls_device": [vp, C.POINTER(Cells), vp, sz, vp, vp],
         "mg_format_stats": [vp, vp],
-        "mg_format_calls_masked": [vp, sz, u32, it, vp, vp, vp, i32, vp, vp, vp, sz, vp, vp],
-        "mg_format_calls_masked_device": [vp, sz, u32, it, vp, vp, vp, i32, vp, vp, vp, sz, vp, vp],
-        "mg_format_calls_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp],
-        "mg_format_calls_gp_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp],
         "mg_site_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp],
         "mg_site_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp],
         "mg_format_site_info": [vp, sz, vp, vp, vp, vp, sz, vp, vp],
@@ -137,15 +133,9 @@ def lib():
         "mg_estimate_priors": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp],
         "mg_estimate_priors_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp],
         "mg_estimate_priors_stats": [vp, vp],
-        "mg_encode_calls_bcf": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
-        "mg_encode_calls_bcf_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp],
-        "mg_encode_calls_bcf_gp": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
-        "mg_encode_calls_bcf_gp_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp],
+        "mg_encode_calls_bcf": [vp, C.POINTER(Cells), C.POINTER(BcfKeys), vp, sz, vp, vp],
+        "mg_encode_calls_bcf_device": [vp, C.POINTER(Cells), C.POINTER(BcfKeys), vp, sz, vp, vp],
         "mg_bcf_stats": [vp, vp],
-        "mg_format_calls_pl": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp],
-        "mg_format_calls_pl_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp],
-        "mg_encode_calls_bcf_pl": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp],
-        "mg_encode_calls_bcf_pl_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp],
         "mg_phred_likelihoods": [vp, sz, u32, vp, vp, vp, fl, it, it, i32, vp],
         "mg_phred_likelihoods_device": [vp, sz, u32, vp, vp, vp, fl, it, it, i32, vp],
         "mg_pl_stats": [vp, vp],
@@ -212,11 +202,9 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_counters_size", "mg_counters_export_device", "mg_counters_import_device", "mg_counters_reset", "mg_counters_view",
             "mg_cohort_begin", "mg_cohort_select", "mg_cohort_end", "mg_cohort_info", "mg_cover_blocks_cohort_device", "mg_cohort_stats", "mg_cover_blocks_cohort",
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
-            "mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
+            "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
             "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
-            "mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device",
-            "mg_format_calls_pl", "mg_format_calls_pl_device", "mg_encode_calls_bcf_pl", "mg_encode_calls_bcf_pl_device",
             "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -236,6 +224,31 @@ class PanelDev(C.Structure):
                 ("contig_id", C.c_void_p), ("pos", C.c_void_p), ("ref_size", C.c_void_p), ("min_size", C.c_void_p), ("present", C.c_void_p),
                 ("var_allele_off", C.c_void_p), ("allele_off", C.c_void_p), ("pool", C.c_void_p), ("canon", C.c_void_p), ("gt", C.c_void_p),
                 ("sp_off", C.c_void_p), ("sp_sample", C.c_void_p), ("sp_gt", C.c_void_p), ("sp_default", C.c_uint32), ("pool_bytes", C.c_uint64)]
+
+
+CELLS_GP, CELLS_PL = 1, 2    # MG_CELLS_GP, MG_CELLS_PL
+
+
+class Cells(C.Structure):
+    """mg_cells: a batch's cells for mg_format_calls* / mg_encode_calls_bcf* (host pointers in a host form, device pointers in a device form)"""
+    _fields_ = [("n_vars", C.c_size_t), ("n_planes", C.c_uint32), ("haploid", C.c_int), ("gt1", C.c_void_p), ("gt2", C.c_void_p), ("gq", C.c_void_p),
+                ("use_mask", C.c_int), ("min_gq", C.c_int32), ("cov", C.c_void_p), ("var_allele_off", C.c_void_p), ("probs", C.c_void_p),
+                ("var_gt_off", C.c_void_p), ("status", C.c_void_p), ("pl", C.c_void_p), ("allele_class", C.c_void_p), ("fields", C.c_uint32)]
+
+
+class BcfKeys(C.Structure):
+    """mg_bcf_keys: the header's dictionary indexes of the FORMAT fields"""
+    _fields_ = [("gt", C.c_int32), ("gq", C.c_int32), ("cov", C.c_int32), ("gp", C.c_int32), ("pl", C.c_int32)]
+
+
+def _pl_fields(gp):
+    """the field bits of a PL call, with GP in front of PL or without"""
+    return CELLS_PL | (CELLS_GP if gp else 0)
+
+
+def _bcf_keys(keys):
+    """(gt, gq, cov[, gp[, pl]]) -> BcfKeys, what is not given 0"""
+    return BcfKeys(*[int(k) for k in keys])
 
 
 def sparse_genotypes(gt, n_samples, default=1 << 14):
@@ -656,60 +669,28 @@ class Context:
         self._ck(self._L.mg_cohort_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
 
-    # the sample columns of a multi-sample VCF
-    def format_calls(self, gt1, gt2, gq, haploid, cov=None, var_allele_off=None, text_cap=None, min_gq=None):
-        """gt1 / gt2 / gq: [planes, n_vars] int32 -> (bytes, row_off): row v = bytes[row_off[v]:row_off[v + 1]], a tab and a
-        `GT:GQ[:COVS]` cell per plane, then a newline.  cov: [planes, slots] with var_allele_off [n_vars + 1].  text_cap: the
-        buffer to try first (default: sized by a first call); a buffer that is too small raises MalvaError(MG_ERR_LIMIT) with
-        .needed and .row_off set.  min_gq (mg_format_calls_masked): cells whose gq is below it print a missing genotype."""
-        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
-        g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
-        planes, n = g1.shape
-        cv, vo = a(cov, np.uint32), a(var_allele_off, np.uint32)
-        row_off = np.zeros(n + 1, dtype=np.uint64)
-        need = C.c_uint64(0)
+    def _rows(self, entry, keys, gt1, gt2, gq, haploid, min_gq, cap, fields=0, cov=None, var_allele_off=None, probs=None, var_gt_off=None, status=None, pl=None):
+        """the host form of a row encoder (entry: mg_format_calls or mg_encode_calls_bcf, the latter with keys): the arrays as numpy
+        arrays of the ABI's types into one mg_cells -> (bytes, row_off).  cap: the buffer to try first (default: sized by a first call);
+        a buffer that is too small raises MalvaError(MG_ERR_LIMIT) with .needed, .row_off and .text set."""
+        kept = []                     # (the converted arrays live as long as the struct's pointers are in use)
 
-        def call(cap):
-            text = np.zeros(max(cap, 1), dtype=np.uint8)
-            if min_gq is None:
-                rc = self._L.mg_format_calls(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), _p(cv), _p(vo), _p(text) if cap else None, cap, _p(row_off),
-                                             C.byref(need))
-            else:
-                rc = self._L.mg_format_calls_masked(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq), _p(cv), _p(vo),
-                                                    _p(text) if cap else None, cap, _p(row_off), C.byref(need))
-            return rc, text
-        rc, text = call(0 if text_cap is None else int(text_cap))
-        if rc == -5 and text_cap is None and need.value:
-            rc, text = call(need.value)
-        if rc != 0:
-            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
-            e.needed, e.row_off, e.text = need.value, row_off, text
-            raise e
-        return text[:need.value].tobytes(), row_off
-
-    def format_calls_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_text, text_cap, d_row_off):
-        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
-        v = C.c_void_p
-        need = C.c_uint64(0)
-        rc = self._L.mg_format_calls_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), v(d_cov), v(d_var_allele_off), v(d_text),
-                                            int(text_cap), v(d_row_off), C.byref(need))
-        if rc not in (0, -5) or (rc == -5 and not need.value):
-            self._ck(rc)
-        return rc, need.value
-
-    def _gp_rows(self, call_abi, gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, cap):
-        """the host form of a *_gp entry: call_abi(n, planes, arrays.., out, cap, row_off, need) -> rc; the buffer rule of format_calls"""
-        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
-        g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
-        planes, n = g1.shape
-        cv, vo = a(cov, np.uint32), a(var_allele_off, np.uint32)
-        pr, go, st = a(probs, np.float64), a(var_gt_off, np.uint64), a(status, np.uint8)
+        def ptr(x, t):
+            if x is None:
+                return None
+            kept.append(np.ascontiguousarray(x, dtype=t))
+            return kept[-1].ctypes.data
+        planes, n = np.shape(gt1)
+        x = Cells(n, planes, int(haploid), ptr(gt1, np.int32), ptr(gt2, np.int32), ptr(gq, np.int32), int(min_gq is not None), int(min_gq or 0),
+                  ptr(cov, np.uint32), ptr(var_allele_off, np.uint32), ptr(probs, np.float64), ptr(var_gt_off, np.uint64), ptr(status, np.uint8),
+                  ptr(pl, np.int32), None, fields)
+        head = (self.h, C.byref(x)) if keys is None else (self.h, C.byref(x), C.byref(_bcf_keys(keys)))
         row_off = np.zeros(n + 1, dtype=np.uint64)
         need = C.c_uint64(0)
 
         def call(c):
             out = np.zeros(max(c, 1), dtype=np.uint8)
-            return call_abi(n, planes, _p(g1), _p(g2), _p(q), _p(cv), _p(vo), _p(pr), _p(go), _p(st), _p(out) if c else None, c, _p(row_off), C.byref(need)), out
+            return entry(*head, _p(out) if c else None, c, _p(row_off), C.byref(need)), out
         rc, out = call(0 if cap is None else int(cap))
         if rc == -5 and cap is None and need.value:
             rc, out = call(need.value)
@@ -719,50 +700,53 @@ class Context:
             raise e
         return out[:need.value].tobytes(), row_off
 
+    def _rows_device(self, entry, keys, n_vars, planes, haploid, min_gq, d_out, cap, d_row_off, fields=0, **arrays):
+        """the device form of a row encoder: arrays are mg_cells' members as device pointers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
+        x = Cells(n_vars=n_vars, n_planes=planes, haploid=int(haploid), use_mask=int(min_gq is not None), min_gq=int(min_gq or 0), fields=fields, **arrays)
+        head = (self.h, C.byref(x)) if keys is None else (self.h, C.byref(x), C.byref(_bcf_keys(keys)))
+        need = C.c_uint64(0)
+        rc = entry(*head, C.c_void_p(d_out), int(cap), C.c_void_p(d_row_off), C.byref(need))
+        if rc not in (0, -5) or (rc == -5 and not need.value):
+            self._ck(rc)
+        return rc, need.value
+
+    # the sample columns of a multi-sample VCF
+    def format_calls(self, gt1, gt2, gq, haploid, cov=None, var_allele_off=None, text_cap=None, min_gq=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 -> (bytes, row_off): row v = bytes[row_off[v]:row_off[v + 1]], a tab and a
+        `GT:GQ[:COVS]` cell per plane, then a newline.  cov: [planes, slots] with var_allele_off [n_vars + 1].  text_cap: the
+        buffer to try first (default: sized by a first call); a buffer that is too small raises MalvaError(MG_ERR_LIMIT) with
+        .needed and .row_off set.  min_gq: cells whose gq is below it print a missing genotype."""
+        return self._rows(self._L.mg_format_calls, None, gt1, gt2, gq, haploid, min_gq, text_cap, cov=cov, var_allele_off=var_allele_off)
+
+    def format_calls_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_text, text_cap, d_row_off):
+        """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
+        return self._rows_device(self._L.mg_format_calls_device, None, n_vars, planes, haploid, None, d_text, text_cap, d_row_off, gt1=d_gt1, gt2=d_gt2, gq=d_gq,
+                                 cov=d_cov, var_allele_off=d_var_allele_off)
+
     def format_calls_gp(self, gt1, gt2, gq, haploid, var_allele_off, probs, var_gt_off, status, cov=None, text_cap=None, min_gq=None):
-        """format_calls with the field GP behind every cell's last (mg_format_calls_gp).  probs: [planes, var_gt_off[n_vars]] float64,
+        """format_calls with the field GP behind every cell's last (MG_CELLS_GP).  probs: [planes, var_gt_off[n_vars]] float64,
         a record's likelihoods in the reference's order; var_gt_off: [n_vars + 1] uint64; status: [planes, n_vars] uint8;
         var_allele_off is required, cov optional."""
-        return self._gp_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, out, cap, row_off, need: self._L.mg_format_calls_gp(
-            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, out, cap, row_off, need),
-            gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, text_cap)
+        return self._rows(self._L.mg_format_calls, None, gt1, gt2, gq, haploid, min_gq, text_cap, CELLS_GP, cov, var_allele_off, probs, var_gt_off, status)
 
     def format_calls_gp_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_text, text_cap,
                                d_row_off, min_gq=None):
         """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
-        v = C.c_void_p
-        need = C.c_uint64(0)
-        rc = self._L.mg_format_calls_gp_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0), v(d_cov),
-                                               v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), v(d_text), int(text_cap), v(d_row_off), C.byref(need))
-        if rc not in (0, -5) or (rc == -5 and not need.value):
-            self._ck(rc)
-        return rc, need.value
-
-    def _pl_rows(self, call_abi, gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, pl, cap):
-        """the host form of a *_pl entry: _gp_rows with the array pl ([planes, var_gt_off[n_vars]] int32) behind status"""
-        d = None if pl is None else np.ascontiguousarray(pl, dtype=np.int32)
-        return self._gp_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, out, c, row_off, need: call_abi(n, planes, g1, g2, q, cv, vo, pr, go, st, _p(d), out, c,
-                                                                                                             row_off, need),
-                             gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, cap)
+        return self._rows_device(self._L.mg_format_calls_device, None, n_vars, planes, haploid, min_gq, d_text, text_cap, d_row_off, CELLS_GP, gt1=d_gt1, gt2=d_gt2,
+                                 gq=d_gq, cov=d_cov, var_allele_off=d_var_allele_off, probs=d_probs, var_gt_off=d_var_gt_off, status=d_status)
 
     def format_calls_pl(self, gt1, gt2, gq, haploid, var_allele_off, var_gt_off, pl, probs=None, status=None, cov=None, text_cap=None, min_gq=None):
-        """format_calls with the field PL behind every cell's last (mg_format_calls_pl): pl [planes, var_gt_off[n_vars]] int32, a
+        """format_calls with the field PL behind every cell's last (MG_CELLS_PL): pl [planes, var_gt_off[n_vars]] int32, a
         record's values in VCF order, MG_PL_MISSING = INT32_MIN a missing one.  probs and status (both or neither): GP in front of PL."""
-        return self._pl_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, d, out, cap, row_off, need: self._L.mg_format_calls_pl(
-            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, d, out, cap, row_off, need),
-            gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, pl, text_cap)
+        return self._rows(self._L.mg_format_calls, None, gt1, gt2, gq, haploid, min_gq, text_cap, _pl_fields(probs is not None or status is not None), cov, var_allele_off, probs, var_gt_off,
+                          status, pl)
 
     def format_calls_pl_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl, d_text, text_cap,
                                d_row_off, min_gq=None):
         """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the text needs)"""
-        v = C.c_void_p
-        need = C.c_uint64(0)
-        rc = self._L.mg_format_calls_pl_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0), v(d_cov),
-                                               v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), v(d_pl), v(d_text), int(text_cap), v(d_row_off),
-                                               C.byref(need))
-        if rc not in (0, -5) or (rc == -5 and not need.value):
-            self._ck(rc)
-        return rc, need.value
+        return self._rows_device(self._L.mg_format_calls_device, None, n_vars, planes, haploid, min_gq, d_text, text_cap, d_row_off, _pl_fields(d_probs or d_status),
+                                 gt1=d_gt1, gt2=d_gt2, gq=d_gq, cov=d_cov, var_allele_off=d_var_allele_off, probs=d_probs, var_gt_off=d_var_gt_off, status=d_status,
+                                 pl=d_pl)
 
     # Phred-scaled genotype likelihoods, prior-free
     def phred_likelihoods(self, cov, var_allele_off, error_rate, max_cov, haploid, cap=255, var_gt_off=None, pl_out=None):
@@ -973,75 +957,36 @@ class Context:
         per-sample block, fields GT, GQ and (with cov [planes, slots] and var_allele_off [n_vars + 1]) COVS.  keys: the header's
         dictionary indexes (gt, gq, cov).  out_cap and min_gq as format_calls' text_cap and min_gq; a buffer that is too small
         raises MalvaError(MG_ERR_LIMIT) with .needed, .row_off and .text set."""
-        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
-        g1, g2, q = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32)
-        planes, n = g1.shape
-        cv, vo = a(cov, np.uint32), a(var_allele_off, np.uint32)
-        row_off = np.zeros(n + 1, dtype=np.uint64)
-        need = C.c_uint64(0)
-
-        def call(cap):
-            out = np.zeros(max(cap, 1), dtype=np.uint8)
-            rc = self._L.mg_encode_calls_bcf(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(cv), _p(vo),
-                                             int(keys[0]), int(keys[1]), int(keys[2]), _p(out) if cap else None, cap, _p(row_off), C.byref(need))
-            return rc, out
-        rc, out = call(0 if out_cap is None else int(out_cap))
-        if rc == -5 and out_cap is None and need.value:
-            rc, out = call(need.value)
-        if rc != 0:
-            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
-            e.needed, e.row_off, e.text = need.value, row_off, out
-            raise e
-        return out[:need.value].tobytes(), row_off
+        return self._rows(self._L.mg_encode_calls_bcf, keys[:3], gt1, gt2, gq, haploid, min_gq, out_cap, cov=cov, var_allele_off=var_allele_off)
 
     def encode_calls_bcf_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, keys, d_out, out_cap, d_row_off, min_gq=None):
         """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
-        v = C.c_void_p
-        need = C.c_uint64(0)
-        rc = self._L.mg_encode_calls_bcf_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
-                                                v(d_cov), v(d_var_allele_off), int(keys[0]), int(keys[1]), int(keys[2]), v(d_out), int(out_cap), v(d_row_off),
-                                                C.byref(need))
-        if rc not in (0, -5) or (rc == -5 and not need.value):
-            self._ck(rc)
-        return rc, need.value
+        return self._rows_device(self._L.mg_encode_calls_bcf_device, keys[:3], n_vars, planes, haploid, min_gq, d_out, out_cap, d_row_off, gt1=d_gt1, gt2=d_gt2,
+                                 gq=d_gq, cov=d_cov, var_allele_off=d_var_allele_off)
 
     def encode_calls_bcf_gp(self, gt1, gt2, gq, haploid, keys, var_allele_off, probs, var_gt_off, status, cov=None, out_cap=None, min_gq=None):
-        """encode_calls_bcf with the float field GP behind the record's last (mg_encode_calls_bcf_gp).  keys: (gt, gq, cov, gp);
+        """encode_calls_bcf with the float field GP behind the record's last (MG_CELLS_GP).  keys: (gt, gq, cov, gp);
         the arrays as format_calls_gp's."""
-        return self._gp_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, out, cap, row_off, need: self._L.mg_encode_calls_bcf_gp(
-            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, int(keys[0]), int(keys[1]), int(keys[2]),
-            int(keys[3]), out, cap, row_off, need), gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, out_cap)
+        return self._rows(self._L.mg_encode_calls_bcf, keys[:4], gt1, gt2, gq, haploid, min_gq, out_cap, CELLS_GP, cov, var_allele_off, probs, var_gt_off, status)
 
     def encode_calls_bcf_gp_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, keys, d_out, out_cap,
                                    d_row_off, min_gq=None):
         """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
-        v = C.c_void_p
-        need = C.c_uint64(0)
-        rc = self._L.mg_encode_calls_bcf_gp_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
-                                                   v(d_cov), v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), int(keys[0]), int(keys[1]), int(keys[2]),
-                                                   int(keys[3]), v(d_out), int(out_cap), v(d_row_off), C.byref(need))
-        if rc not in (0, -5) or (rc == -5 and not need.value):
-            self._ck(rc)
-        return rc, need.value
+        return self._rows_device(self._L.mg_encode_calls_bcf_device, keys[:4], n_vars, planes, haploid, min_gq, d_out, out_cap, d_row_off, CELLS_GP, gt1=d_gt1,
+                                 gt2=d_gt2, gq=d_gq, cov=d_cov, var_allele_off=d_var_allele_off, probs=d_probs, var_gt_off=d_var_gt_off, status=d_status)
 
     def encode_calls_bcf_pl(self, gt1, gt2, gq, haploid, keys, var_allele_off, var_gt_off, pl, probs=None, status=None, cov=None, out_cap=None, min_gq=None):
-        """encode_calls_bcf with the integer field PL behind the record's last (mg_encode_calls_bcf_pl).  keys: (gt, gq, cov, gp, pl);
+        """encode_calls_bcf with the integer field PL behind the record's last (MG_CELLS_PL).  keys: (gt, gq, cov, gp, pl);
         the arrays as format_calls_pl's."""
-        return self._pl_rows(lambda n, planes, g1, g2, q, cv, vo, pr, go, st, d, out, cap, row_off, need: self._L.mg_encode_calls_bcf_pl(
-            self.h, n, planes, int(haploid), g1, g2, q, int(min_gq is not None), int(min_gq or 0), cv, vo, pr, go, st, d, int(keys[0]), int(keys[1]), int(keys[2]),
-            int(keys[3]), int(keys[4]), out, cap, row_off, need), gt1, gt2, gq, cov, var_allele_off, probs, var_gt_off, status, pl, out_cap)
+        return self._rows(self._L.mg_encode_calls_bcf, keys[:5], gt1, gt2, gq, haploid, min_gq, out_cap, _pl_fields(probs is not None or status is not None), cov, var_allele_off, probs,
+                          var_gt_off, status, pl)
 
     def encode_calls_bcf_pl_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl, keys, d_out,
                                    out_cap, d_row_off, min_gq=None):
         """the same from device pointers into device buffers -> (return code: 0 or MG_ERR_LIMIT, bytes the rows need)"""
-        v = C.c_void_p
-        need = C.c_uint64(0)
-        rc = self._L.mg_encode_calls_bcf_pl_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
-                                                   v(d_cov), v(d_var_allele_off), v(d_probs), v(d_var_gt_off), v(d_status), v(d_pl), int(keys[0]), int(keys[1]),
-                                                   int(keys[2]), int(keys[3]), int(keys[4]), v(d_out), int(out_cap), v(d_row_off), C.byref(need))
-        if rc not in (0, -5) or (rc == -5 and not need.value):
-            self._ck(rc)
-        return rc, need.value
+        return self._rows_device(self._L.mg_encode_calls_bcf_device, keys[:5], n_vars, planes, haploid, min_gq, d_out, out_cap, d_row_off,
+                                 _pl_fields(d_probs or d_status), gt1=d_gt1, gt2=d_gt2, gq=d_gq, cov=d_cov, var_allele_off=d_var_allele_off, probs=d_probs,
+                                 var_gt_off=d_var_gt_off, status=d_status, pl=d_pl)
 
     def bcf_stats(self):
         """-> device ms of the most recent encode_calls_bcf: (length pass, scan, write pass)"""

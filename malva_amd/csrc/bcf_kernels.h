@@ -2,7 +2,7 @@
 // specification v4.3, section 6.3.3) -- what call_text_kernels.h makes as text, here in the binary form, 3 bytes per diploid GT:GQ cell
 // instead of 8 to 10.  Restated from the published layout; no file written by htslib exists here: parity unpinned, as for the reader.
 //
-// Row v = for each of its two fields (three with cov, one more with probs: mg_encode_calls_bcf_gp), in this order:
+// Row v = for each of its two fields (three with cov, one more with probs: MG_CELLS_GP), in this order:
 //   GT    typed_int(key_gt)  desc(ploidy, T)  [plane][ploidy] values   ploidy 1 (haploid) or 2; allele index a -> (a + 1) << 1 (unphased)
 //   GQ    typed_int(key_gq)  desc(1, T)       [plane] values           as they are, mask or no mask
 //   COVS  typed_int(key_cov) desc(A, T)       [plane][A] values        (int32_t)cov[..], A = the record's alleles
@@ -11,7 +11,7 @@
 //                                                                      so that float denormals stay; an unprintable value (gp_printable)
 //                                                                      is the missing float, a cell that is not MG_GT_NORMAL the missing
 //                                                                      float and G - 1 end-of-vector floats
-//   PL    typed_int(key_pl)  desc(G, T)       [plane][G] values        mg_encode_calls_bcf_pl (GP is optional there): `pl` as it comes, already in
+//   PL    typed_int(key_pl)  desc(G, T)       [plane][G] values        MG_CELLS_PL (GP is optional there): `pl` as it comes, already in
 //                                                                      VCF order; T the smallest type that holds every value of the field that
 //                                                                      is not MG_PL_MISSING (int8 when there is none); MG_PL_MISSING is T's missing
 //                                                                      code (0x80, 0x8000, 0x80000000), a cell whose values are all missing that
@@ -49,12 +49,12 @@ struct BcfArgs {
     int masked;
     i32 min_gq;
     i32 key_gt, key_gq, key_cov; // dictionary indexes, >= 0
-    // mg_encode_calls_bcf_gp (all three or none, as FmtArgs')
+    // MG_CELLS_GP (all three or none, as FmtArgs')
     const double *probs;         // [n_planes][var_gt_off[n_vars]]
     const u64 *var_gt_off;       // [n_vars + 1]
     const u8 *status;            // [n_planes][n_vars]
     i32 key_gp;
-    // mg_encode_calls_bcf_pl (with var_allele_off and var_gt_off; probs and status then both or neither)
+    // MG_CELLS_PL (with var_allele_off and var_gt_off; probs and status then both or neither)
     const i32 *pl;               // [n_planes][var_gt_off[n_vars]]
     i32 key_pl;
 };
@@ -131,7 +131,7 @@ __device__ __forceinline__ i32 bcf_wave_max(i32 x)
     return x;
 }
 
-// the bytes of row v whose three fields have the types t[0..2] (t[2] unused without cov).  GP: the kernels of mg_encode_calls_bcf_gp, a
+// the bytes of row v whose three fields have the types t[0..2] (t[2] unused without cov).  GP: the kernels under MG_CELLS_GP, a
 // build of their own as in call_text_kernels.h
 template <bool GP, bool PL = false>
 __device__ __forceinline__ u64 bcf_row_len(const BcfArgs &a, u64 v, const u32 *t)

@@ -17,12 +17,12 @@
 //                      text_cap cuts) are stored byte by byte.
 // Numbers print as std::to_string(int) prints them over the whole int32 range; a coverage as std::to_string((int)cov).
 //
-// mg_format_calls_gp adds the field GP behind the cell's last: the record's normalised likelihoods (`probs`, the doubles behind GTS= of the
+// MG_CELLS_GP adds the field GP behind the cell's last: the record's normalised likelihoods (`probs`, the doubles behind GTS= of the
 // single-sample output) in VCF genotype order, each printed as printf("%f") prints it.  A value is 8 bytes (`0.dddddd`, `1.000000`) when it
 // is printable -- sign bit clear and <= 1 -- and the one byte `.` when it is not, so the length pass formats nothing; the digits are made
 // in integers from the double's bits (gp_micro), to nearest on the exact value with ties to even, as glibc rounds.
 //
-// mg_format_calls_pl adds the field PL behind the cell's last (behind GP, which is optional there): the G integers of `pl` (what
+// MG_CELLS_PL adds the field PL behind the cell's last (behind GP, which is optional there): the G integers of `pl` (what
 // mg_phred_likelihoods leaves: already in VCF order, copied and not permuted), each as std::to_string(int) prints it, `.` for
 // MG_PL_MISSING; the whole field is one `.` when G == 0 or every value of the cell is missing.  Any other int32 is a value: the encoder
 // does not know where the numbers came from.  A masked cell keeps its PL.
@@ -77,13 +77,13 @@ struct FmtArgs {
     const i32 *gt1, *gt2, *gq;   // [n_planes][n_vars]
     const u32 *cov;              // [n_planes][var_allele_off[n_vars]] or NULL
     const u32 *var_allele_off;   // [n_vars + 1] (with cov or probs)
-    int masked;                  // mg_format_calls_masked: a cell whose gq < min_gq prints its genotype as missing ('.' or './.')
+    int masked;                  // mg_cells.use_mask: a cell whose gq < min_gq prints its genotype as missing ('.' or './.')
     i32 min_gq;
-    // mg_format_calls_gp (all three or none; var_allele_off is then required with or without cov)
+    // MG_CELLS_GP (all three or none; var_allele_off is then required with or without cov)
     const double *probs;         // [n_planes][var_gt_off[n_vars]], a record's values in the reference's order: a outer, c >= a inner
     const u64 *var_gt_off;       // [n_vars + 1]
     const u8 *status;            // [n_planes][n_vars]: a cell that is not MG_GT_NORMAL has no list, its probs are not read
-    // mg_format_calls_pl (with var_allele_off and var_gt_off; probs and status then both or neither)
+    // MG_CELLS_PL (with var_allele_off and var_gt_off; probs and status then both or neither)
     const i32 *pl;               // [n_planes][var_gt_off[n_vars]], a record's values in VCF order
 };
 
@@ -214,8 +214,8 @@ __device__ __forceinline__ u64 pl_put(const FmtArgs &a, const FmtWindow &w, u64 
     return pos;
 }
 
-// plane p's cell of record v, the tab in front of it included.  GP: the kernels of mg_format_calls_gp -- a build of their own, so that
-// those of the entries without it keep the registers they had; PL: those of mg_format_calls_pl, for the same reason
+// plane p's cell of record v, the tab in front of it included.  GP: the kernels under MG_CELLS_GP -- a build of their own, so that
+// those of the entries without it keep the registers they had; PL: those under MG_CELLS_PL, for the same reason
 template <bool GP, bool PL = false>
 __device__ __forceinline__ u32 fmt_cell_len(const FmtArgs &a, u64 v, u32 p)
 {

@@ -3134,34 +3134,22 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
 // ---- the rows of a merged batch: the sample columns as text (call_text_kernels.h), the site tags (site_tags_kernels.h), the sample columns
 // ---- as BCF (bcf_kernels.h) ---------------------------------------------------------------------------------------------------------
 namespace {
-// A batch's cells as every call of this section takes them, host pointers in a host form and device pointers in a device form: the nine
-// arguments they all share, then what only some have (NULL elsewhere)
-struct Cells {
-    size_t n_vars;
-    uint32_t n_planes;
-    int haploid;
-    const void *gt1, *gt2, *gq;
-    int use_mask;
-    int32_t min_gq;
-    const void *var_allele_off;
-    const void *cov = nullptr, *status = nullptr;       // the encoders and mg_sample_counts*
-    const void *probs = nullptr, *var_gt_off = nullptr; // the *_gp entries (gp set), with status: the three arrays of the likelihoods
-    const void *allele_class = nullptr;                 // mg_sample_counts*
-    bool gp = false;
-    const void *pl = nullptr;                           // the *_pl entries (with_pl set): var_allele_off and var_gt_off required, gp = probs or status given
-    bool with_pl = false;
-};
+// A batch's cells are mg_cells (malva_hip.h) for every call of this section, the encoders' public one included: host pointers in a host
+// form and device pointers in a device form, NULL where a call has no such array
+inline bool has_gp(const mg_cells &x) { return x.fields & MG_CELLS_GP; }
+inline bool has_pl(const mg_cells &x) { return x.fields & MG_CELLS_PL; }
 // The argument checks that a host form and its device form share: of whoever reads a batch's cells (gq where reads_gq; an encoder: cov with
 // var_allele_off or neither, and with gp var_allele_off with or without cov and the likelihoods), and of where an encoder's rows go
-int check_cells(mg_ctx *c, const char *who, const Cells &x, bool encoder, bool reads_gq)
+int check_cells(mg_ctx *c, const char *who, const mg_cells &x, bool encoder, bool reads_gq)
 {
+    const bool gp = has_gp(x), with_pl = has_pl(x);
     if (x.n_planes < 1 || x.n_planes > 64) return fail(c, MG_ERR_ARG, "%s: n_planes is 1..64", who);
-    if (encoder && !x.gp && !x.with_pl && (x.cov != nullptr) != (x.var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
-    if ((x.gp || x.with_pl) && (!x.var_allele_off || !x.var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
-    if (x.with_pl && (x.probs != nullptr) != (x.status != nullptr)) return fail(c, MG_ERR_ARG, "%s: probs and status go together", who);
+    if (encoder && !gp && !with_pl && (x.cov != nullptr) != (x.var_allele_off != nullptr)) return fail(c, MG_ERR_ARG, "%s: cov and var_allele_off go together", who);
+    if ((gp || with_pl) && (!x.var_allele_off || !x.var_gt_off)) return fail(c, MG_ERR_ARG, "%s: var_allele_off and var_gt_off are required", who);
+    if (with_pl && (x.probs != nullptr) != (x.status != nullptr)) return fail(c, MG_ERR_ARG, "%s: probs and status go together", who);
     if (x.n_vars && (!x.gt1 || (!x.haploid && !x.gt2) || (reads_gq && !x.gq))) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (x.n_vars && x.gp && (!x.probs || !x.status)) return fail(c, MG_ERR_ARG, "NULL argument");
-    if (x.n_vars && x.with_pl && !x.pl) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (x.n_vars && gp && (!x.probs || !x.status)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (x.n_vars && with_pl && !x.pl) return fail(c, MG_ERR_ARG, "NULL argument");
     if (x.n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "%s: more than 2^32 - 1 records in one call", who);
     return MG_OK;
 }
@@ -3260,9 +3248,10 @@ int rows_stats(mg_ctx *c, int enc, const char *who, float *ms_out)
 // under the mask alone); whatever else is given -- at n_vars == 0 only when_empty (the encoders and mg_pack_dosage, who take var_allele_off
 // [0 .. n_vars] as it comes; mg_site_counts and mg_sample_counts do not read it then).  cov and allele_class are sized from
 // var_allele_off[n_vars], probs and pl from var_gt_off[n_vars].  What is not uploaded is NULL on the device side.
-int stage_cells(mg_ctx *c, const Cells &h, Cells *d, bool always_gq, bool when_empty)
+int stage_cells(mg_ctx *c, const mg_cells &h, mg_cells *d, bool always_gq, bool when_empty)
 {
     *d = h;
+    const bool gp = has_gp(h), with_pl = has_pl(h);
     auto up = [&](int slot, const void *host, bool wanted, size_t bytes, const void **dev) -> int {
         void *p = nullptr;
         if (host && wanted) TRY(upload(c, c->stage[slot], host, bytes, &p));
@@ -3276,9 +3265,9 @@ int stage_cells(mg_ctx *c, const Cells &h, Cells *d, bool always_gq, bool when_e
     TRY(up(ST_GQ, h.gq, always_gq || h.use_mask, 4 * cells, &d->gq));
     TRY(up(ST_COV, h.cov, rest, 4 * (size_t)h.n_planes * slots, &d->cov));
     TRY(up(ST_VAR_ALLELE_OFF, h.var_allele_off, rest, 4 * (h.n_vars + 1), &d->var_allele_off));
-    TRY(up(ST_PROBS, h.probs, h.gp, 8 * (size_t)h.n_planes * (h.gp ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->probs));
-    TRY(up(ST_VAR_GT_OFF, h.var_gt_off, h.gp || h.with_pl, 8 * (h.n_vars + 1), &d->var_gt_off));
-    TRY(up(ST_PL, h.pl, h.with_pl, 4 * (size_t)h.n_planes * (h.with_pl ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->pl));
+    TRY(up(ST_PROBS, h.probs, gp, 8 * (size_t)h.n_planes * (gp ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->probs));
+    TRY(up(ST_VAR_GT_OFF, h.var_gt_off, gp || with_pl, 8 * (h.n_vars + 1), &d->var_gt_off));
+    TRY(up(ST_PL, h.pl, with_pl, 4 * (size_t)h.n_planes * (with_pl ? ((const uint64_t *)h.var_gt_off)[h.n_vars] : 0), &d->pl));
     TRY(up(ST_STATUS, h.status, rest, cells, &d->status));
     return up(ST_ALLELE_CLASS, h.allele_class, rest, slots, &d->allele_class);
 }
@@ -3299,15 +3288,18 @@ int fetch_rows(mg_ctx *c, int rc, size_t n_rows, const void *d_out, const void *
     return rc;
 }
 
-int format_calls_device(mg_ctx *c, const Cells &x, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
+} // namespace
+MG_EXPORT int mg_format_calls_device(mg_ctx *c, const mg_cells *cells, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
-    if (!c) return MG_ERR_ARG;
+    if (!c || !cells) return MG_ERR_ARG;
+    const mg_cells &x = *cells;
     TRY(check_cells(c, "mg_format_calls", x, true, true));
     const FmtArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, (const u32 *)x.cov, (const u32 *)x.var_allele_off,
                     x.use_mask, x.min_gq, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, (const i32 *)x.pl};
-    const auto len_kernel = x.with_pl ? (x.gp ? fmt_len_kernel<true, true> : fmt_len_kernel<false, true>) : x.gp ? fmt_len_kernel<true> : fmt_len_kernel<false>;
-    const auto write_kernel = x.with_pl ? (x.gp ? fmt_write_kernel<true, true> : fmt_write_kernel<false, true>) : x.gp ? fmt_write_kernel<true> : fmt_write_kernel<false>;
+    const bool gp = has_gp(x);
+    const auto len_kernel = has_pl(x) ? (gp ? fmt_len_kernel<true, true> : fmt_len_kernel<false, true>) : gp ? fmt_len_kernel<true> : fmt_len_kernel<false>;
+    const auto write_kernel = has_pl(x) ? (gp ? fmt_write_kernel<true, true> : fmt_write_kernel<false, true>) : gp ? fmt_write_kernel<true> : fmt_write_kernel<false>;
     return encode_rows(
         c, TM_FMT, "mg_format_calls", x.n_vars, d_text_out, text_cap, d_row_off_out, text_bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
@@ -3319,85 +3311,19 @@ int format_calls_device(mg_ctx *c, const Cells &x, void *d_text_out, size_t text
         });
 }
 
-int format_calls_host(mg_ctx *c, const Cells &x, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
+MG_EXPORT int mg_format_calls(mg_ctx *c, const mg_cells *cells, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
 {
     const DeviceGuard on_device(c, KEEP);
-    if (!c) return MG_ERR_ARG;
+    if (!c || !cells) return MG_ERR_ARG;
+    const mg_cells &x = *cells;
     TRY(check_cells(c, "mg_format_calls", x, true, true));
     TRY(check_rows_out(c, text_out, text_cap, row_off_out, text_bytes_out));
-    Cells d;
+    mg_cells d;
     void *d_text, *d_off;
     TRY(stage_cells(c, x, &d, true, true));
     TRY(stage_rows(c, x.n_vars, text_cap, &d_text, &d_off));
-    const int rc = format_calls_device(c, d, d_text, text_cap, d_off, text_bytes_out);
+    const int rc = mg_format_calls_device(c, &d, d_text, text_cap, d_off, text_bytes_out);
     return fetch_rows(c, rc, x.n_vars, d_text, d_off, text_out, text_cap, row_off_out, text_bytes_out);
-}
-} // namespace
-MG_EXPORT int mg_format_calls_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
-                                     const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap, void *d_row_off_out,
-                                     uint64_t *text_bytes_out)
-{
-    return format_calls_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 0, 0, d_var_allele_off, d_cov}, d_text_out, text_cap, d_row_off_out, text_bytes_out);
-}
-MG_EXPORT int mg_format_calls(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
-                              const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap, uint64_t *row_off_out,
-                              uint64_t *text_bytes_out)
-{
-    return format_calls_host(c, Cells{n_vars, n_planes, haploid, gt1, gt2, gq, 0, 0, var_allele_off, cov}, text_out, text_cap, row_off_out, text_bytes_out);
-}
-// the same with the genotype of every cell whose gq < min_gq printed as missing
-MG_EXPORT int mg_format_calls_masked_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq,
-                                            int32_t min_gq, const void *d_cov, const void *d_var_allele_off, void *d_text_out, size_t text_cap,
-                                            void *d_row_off_out, uint64_t *text_bytes_out)
-{
-    return format_calls_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, 1, min_gq, d_var_allele_off, d_cov}, d_text_out, text_cap, d_row_off_out,
-                               text_bytes_out);
-}
-MG_EXPORT int mg_format_calls_masked(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq,
-                                     int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, char *text_out, size_t text_cap,
-                                     uint64_t *row_off_out, uint64_t *text_bytes_out)
-{
-    return format_calls_host(c, Cells{n_vars, n_planes, haploid, gt1, gt2, gq, 1, min_gq, var_allele_off, cov}, text_out, text_cap, row_off_out, text_bytes_out);
-}
-// the same with the field GP behind every cell's last: the record's likelihoods in VCF genotype order (call_text_kernels.h)
-MG_EXPORT int mg_format_calls_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                        int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                                        const void *d_status, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
-{
-    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask != 0, min_gq, d_var_allele_off, d_cov, d_status, d_probs, d_var_gt_off, nullptr, true};
-    return format_calls_device(c, x, d_text_out, text_cap, d_row_off_out, text_bytes_out);
-}
-MG_EXPORT int mg_format_calls_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                                 int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                                 const uint8_t *status, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
-{
-    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, true};
-    return format_calls_host(c, x, text_out, text_cap, row_off_out, text_bytes_out);
-}
-// the same with the field PL behind the cell's last: `pl` as mg_phred_likelihoods leaves it; GP in front of it when probs and status are given
-namespace {
-Cells pl_cells(size_t n_vars, uint32_t n_planes, int haploid, const void *gt1, const void *gt2, const void *gq, int use_mask, int32_t min_gq, const void *cov,
-               const void *var_allele_off, const void *probs, const void *var_gt_off, const void *status, const void *pl)
-{
-    Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask != 0, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, probs || status};
-    x.pl = pl;
-    x.with_pl = true;
-    return x;
-}
-} // namespace
-MG_EXPORT int mg_format_calls_pl_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                        int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                                        const void *d_status, const void *d_pl, void *d_text_out, size_t text_cap, void *d_row_off_out, uint64_t *text_bytes_out)
-{
-    return format_calls_device(c, pl_cells(n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl),
-                               d_text_out, text_cap, d_row_off_out, text_bytes_out);
-}
-MG_EXPORT int mg_format_calls_pl(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                                 int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                                 const uint8_t *status, const int32_t *pl, char *text_out, size_t text_cap, uint64_t *row_off_out, uint64_t *text_bytes_out)
-{
-    return format_calls_host(c, pl_cells(n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, probs, var_gt_off, status, pl), text_out,
-                             text_cap, row_off_out, text_bytes_out);
 }
 
 // device milliseconds of the most recent mg_format_calls* (rows_stats)
@@ -3409,7 +3335,7 @@ MG_EXPORT int mg_format_stats(mg_ctx *c, float *ms_out)
 }
 
 namespace {
-int site_counts_device(mg_ctx *c, const Cells &x, int accumulate, void *d_ac, void *d_ns)
+int site_counts_device(mg_ctx *c, const mg_cells &x, int accumulate, void *d_ac, void *d_ns)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
@@ -3428,7 +3354,7 @@ int site_counts_device(mg_ctx *c, const Cells &x, int accumulate, void *d_ac, vo
 MG_EXPORT int mg_site_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                     int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_ac, void *d_ns)
 {
-    return site_counts_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off}, accumulate, d_ac, d_ns);
+    return site_counts_device(c, mg_cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, nullptr, d_var_allele_off}, accumulate, d_ac, d_ns);
 }
 
 MG_EXPORT int mg_site_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -3436,12 +3362,12 @@ MG_EXPORT int mg_site_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int ha
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off};
+    const mg_cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, nullptr, var_allele_off};
     TRY(check_cells(c, "mg_site_counts", x, false, use_mask));
     if (n_vars && !var_allele_off) return fail(c, MG_ERR_ARG, "NULL argument");
     const size_t slots = n_vars ? var_allele_off[n_vars] : 0;
     if (n_vars && (!ns || (slots && !ac))) return fail(c, MG_ERR_ARG, "NULL argument");
-    Cells d;
+    mg_cells d;
     void *d_ac, *d_ns;
     TRY(stage_cells(c, x, &d, false, false));
     TRY(scratch(c, c->stage[ST_AC], slots ? 4 * slots : 1, &d_ac));
@@ -3504,7 +3430,7 @@ MG_EXPORT int mg_site_stats(mg_ctx *c, float *ms_out)
 
 // ---- the pair table of a multi-sample call set (pair_kernels.h) ------------------------------------------------------------------------
 namespace {
-int pack_dosage_device(mg_ctx *c, const Cells &x, void *d_planes_out)
+int pack_dosage_device(mg_ctx *c, const mg_cells &x, void *d_planes_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
@@ -3526,7 +3452,7 @@ int pack_dosage_device(mg_ctx *c, const Cells &x, void *d_planes_out)
 MG_EXPORT int mg_pack_dosage_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
                                     int32_t min_gq, const void *d_var_allele_off, void *d_planes_out)
 {
-    return pack_dosage_device(c, Cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off}, d_planes_out);
+    return pack_dosage_device(c, mg_cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, nullptr, d_var_allele_off}, d_planes_out);
 }
 
 MG_EXPORT int mg_pack_dosage(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -3534,12 +3460,12 @@ MG_EXPORT int mg_pack_dosage(mg_ctx *c, size_t n_vars, uint32_t n_planes, int ha
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off};
+    const mg_cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, nullptr, var_allele_off};
     TRY(check_cells(c, "mg_pack_dosage", x, false, use_mask));
     if (!var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_dosage: var_allele_off is required");
     if (n_vars && !planes_out) return fail(c, MG_ERR_ARG, "NULL argument");
     const size_t out_bytes = 8 * (size_t)n_planes * 3 * ((n_vars + 63) / 64);
-    Cells d;
+    mg_cells d;
     void *d_out;
     TRY(stage_cells(c, x, &d, false, true));
     TRY(scratch(c, c->stage[ST_PLANES], out_bytes ? out_bytes : 1, &d_out));
@@ -3621,7 +3547,7 @@ MG_EXPORT int mg_pairs_stats(mg_ctx *c, float *ms_out)
 
 // ---- the per-sample table of a multi-sample call set (sample_kernels.h) -----------------------------------------------------------------
 namespace {
-int check_sample(mg_ctx *c, const Cells &x, const void *counts)
+int check_sample(mg_ctx *c, const mg_cells &x, const void *counts)
 {
     TRY(check_cells(c, "mg_sample_counts", x, false, true)); // (gq: the histogram reads it, mask or none)
     if (!counts || (x.n_vars && !x.var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
@@ -3640,7 +3566,7 @@ u64 sample_count_plan(u64 n_vars, u32 n_planes, u64 *n_runs)
     return run;
 }
 
-int sample_counts_device(mg_ctx *c, const Cells &x, int accumulate, void *d_counts)
+int sample_counts_device(mg_ctx *c, const mg_cells &x, int accumulate, void *d_counts)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c) return MG_ERR_ARG;
@@ -3662,7 +3588,7 @@ MG_EXPORT int mg_sample_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_plane
                                       int32_t min_gq, const void *d_status, const void *d_cov, const void *d_var_allele_off, const void *d_allele_class, int accumulate,
                                       void *d_counts)
 {
-    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov, d_status, nullptr, nullptr, d_allele_class};
+    const mg_cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, nullptr, nullptr, d_status, nullptr, d_allele_class};
     return sample_counts_device(c, x, accumulate, d_counts);
 }
 
@@ -3672,10 +3598,10 @@ MG_EXPORT int mg_sample_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int 
 {
     const DeviceGuard on_device(c, KEEP);
     if (!c) return MG_ERR_ARG;
-    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov, status, nullptr, nullptr, allele_class};
+    const mg_cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, nullptr, nullptr, status, nullptr, allele_class};
     TRY(check_sample(c, x, counts));
     const size_t count_bytes = 8 * (size_t)n_planes * MG_SAMPLE_SLOTS;
-    Cells d;
+    mg_cells d;
     void *d_counts;
     TRY(stage_cells(c, x, &d, true, false));
     TRY(scratch(c, c->stage[ST_COUNTS], count_bytes, &d_counts));
@@ -3934,23 +3860,24 @@ MG_EXPORT int mg_pl_stats(mg_ctx *c, float *ms_out)
     return timer_read(c, c->tm[TM_PL], ms_out);
 }
 
-namespace {
-int encode_calls_bcf_device(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl, void *d_out, size_t out_cap,
-                            void *d_row_off_out, uint64_t *bytes_out)
+MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, const mg_cells *cells, const mg_bcf_keys *keys, void *d_out, size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, LAZY);
-    if (!c) return MG_ERR_ARG;
+    if (!c || !cells || !keys) return MG_ERR_ARG;
+    const mg_cells &x = *cells;
+    const mg_bcf_keys &k = *keys;
+    const bool gp = has_gp(x), with_pl = has_pl(x);
     TRY(check_cells(c, "mg_encode_calls_bcf", x, true, true));
-    if (key_gt < 0 || key_gq < 0 || (x.cov && key_cov < 0) || (x.gp && key_gp < 0) || (x.with_pl && key_pl < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
+    if (k.gt < 0 || k.gq < 0 || (x.cov && k.cov < 0) || (gp && k.gp < 0) || (with_pl && k.pl < 0)) return fail(c, MG_ERR_ARG, "mg_encode_calls_bcf: a dictionary index is >= 0");
     const BcfArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, (const u32 *)x.cov, (const u32 *)x.var_allele_off,
-                    x.use_mask, x.min_gq, key_gt, key_gq, key_cov, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, key_gp, (const i32 *)x.pl, key_pl};
-    const auto len_kernel = x.with_pl ? (x.gp ? bcf_len_kernel<true, true> : bcf_len_kernel<false, true>) : x.gp ? bcf_len_kernel<true> : bcf_len_kernel<false>;
-    const auto write_kernel = x.with_pl ? (x.gp ? bcf_write_kernel<true, true> : bcf_write_kernel<false, true>) : x.gp ? bcf_write_kernel<true> : bcf_write_kernel<false>;
+                    x.use_mask, x.min_gq, k.gt, k.gq, k.cov, (const double *)x.probs, (const u64 *)x.var_gt_off, (const u8 *)x.status, k.gp, (const i32 *)x.pl, k.pl};
+    const auto len_kernel = with_pl ? (gp ? bcf_len_kernel<true, true> : bcf_len_kernel<false, true>) : gp ? bcf_len_kernel<true> : bcf_len_kernel<false>;
+    const auto write_kernel = with_pl ? (gp ? bcf_write_kernel<true, true> : bcf_write_kernel<false, true>) : gp ? bcf_write_kernel<true> : bcf_write_kernel<false>;
     void *d_types = nullptr; // the records' type codes (three, with PL four): what the length pass found, for the write pass
     return encode_rows(
         c, TM_BCF, "mg_encode_calls_bcf", x.n_vars, d_out, out_cap, d_row_off_out, bytes_out,
         [&](u32 *len, unsigned long long *meta) -> int {
-            TRY(scratch(c, c->s_enc[TM_BCF][ES_TYPES], (x.with_pl ? 4 : 3) * x.n_vars, &d_types));
+            TRY(scratch(c, c->s_enc[TM_BCF][ES_TYPES], (with_pl ? 4 : 3) * x.n_vars, &d_types));
             hipLaunchKernelGGL(len_kernel, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, len, (unsigned char *)d_types, meta);
             return MG_OK;
         },
@@ -3959,68 +3886,19 @@ int encode_calls_bcf_device(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t k
         });
 }
 
-int encode_calls_bcf_host(mg_ctx *c, const Cells &x, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl, uint8_t *out, size_t out_cap,
-                          uint64_t *row_off_out, uint64_t *bytes_out)
+MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, const mg_cells *cells, const mg_bcf_keys *keys, uint8_t *out, size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
 {
     const DeviceGuard on_device(c, KEEP);
-    if (!c) return MG_ERR_ARG;
+    if (!c || !cells || !keys) return MG_ERR_ARG;
+    const mg_cells &x = *cells;
     TRY(check_cells(c, "mg_encode_calls_bcf", x, true, true));
     TRY(check_rows_out(c, out, out_cap, row_off_out, bytes_out));
-    Cells d;
+    mg_cells d;
     void *d_out, *d_off;
     TRY(stage_cells(c, x, &d, true, true));
     TRY(stage_rows(c, x.n_vars, out_cap, &d_out, &d_off));
-    const int rc = encode_calls_bcf_device(c, d, key_gt, key_gq, key_cov, key_gp, key_pl, d_out, out_cap, d_off, bytes_out);
+    const int rc = mg_encode_calls_bcf_device(c, &d, keys, d_out, out_cap, d_off, bytes_out);
     return fetch_rows(c, rc, x.n_vars, d_out, d_off, out, out_cap, row_off_out, bytes_out);
-}
-} // namespace
-MG_EXPORT int mg_encode_calls_bcf_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                         int32_t min_gq, const void *d_cov, const void *d_var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, void *d_out,
-                                         size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
-{
-    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov};
-    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, 0, 0, d_out, out_cap, d_row_off_out, bytes_out);
-}
-MG_EXPORT int mg_encode_calls_bcf(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                                  int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, int32_t key_gt, int32_t key_gq, int32_t key_cov, uint8_t *out,
-                                  size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
-{
-    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov};
-    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, 0, 0, out, out_cap, row_off_out, bytes_out);
-}
-// the same with the float field GP behind the record's last (bcf_kernels.h)
-MG_EXPORT int mg_encode_calls_bcf_gp_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                            int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                                            const void *d_status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, void *d_out, size_t out_cap,
-                                            void *d_row_off_out, uint64_t *bytes_out)
-{
-    const Cells x{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_var_allele_off, d_cov, d_status, d_probs, d_var_gt_off, nullptr, true};
-    return encode_calls_bcf_device(c, x, key_gt, key_gq, key_cov, key_gp, 0, d_out, out_cap, d_row_off_out, bytes_out);
-}
-MG_EXPORT int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                                     int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                                     const uint8_t *status, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, uint8_t *out, size_t out_cap,
-                                     uint64_t *row_off_out, uint64_t *bytes_out)
-{
-    const Cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, var_allele_off, cov, status, probs, var_gt_off, nullptr, true};
-    return encode_calls_bcf_host(c, x, key_gt, key_gq, key_cov, key_gp, 0, out, out_cap, row_off_out, bytes_out);
-}
-// the same with the integer field PL behind the record's last; GP in front of it when probs and status are given (bcf_kernels.h)
-MG_EXPORT int mg_encode_calls_bcf_pl_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
-                                            int32_t min_gq, const void *d_cov, const void *d_var_allele_off, const void *d_probs, const void *d_var_gt_off,
-                                            const void *d_status, const void *d_pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
-                                            void *d_out, size_t out_cap, void *d_row_off_out, uint64_t *bytes_out)
-{
-    return encode_calls_bcf_device(c, pl_cells(n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, d_cov, d_var_allele_off, d_probs, d_var_gt_off, d_status, d_pl),
-                                   key_gt, key_gq, key_cov, key_gp, key_pl, d_out, out_cap, d_row_off_out, bytes_out);
-}
-MG_EXPORT int mg_encode_calls_bcf_pl(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
-                                     int32_t min_gq, const uint32_t *cov, const uint32_t *var_allele_off, const double *probs, const uint64_t *var_gt_off,
-                                     const uint8_t *status, const int32_t *pl, int32_t key_gt, int32_t key_gq, int32_t key_cov, int32_t key_gp, int32_t key_pl,
-                                     uint8_t *out, size_t out_cap, uint64_t *row_off_out, uint64_t *bytes_out)
-{
-    return encode_calls_bcf_host(c, pl_cells(n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, cov, var_allele_off, probs, var_gt_off, status, pl), key_gt, key_gq,
-                                 key_cov, key_gp, key_pl, out, out_cap, row_off_out, bytes_out);
 }
 
 // device milliseconds of the most recent mg_encode_calls_bcf* (rows_stats)

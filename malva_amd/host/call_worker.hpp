@@ -420,29 +420,21 @@ private:
     // one batch's sample columns: text or BCF, with or without GP, PL and the GQ mask
     int format_rows(Device &dev, Batch &b, std::vector<char> &text, std::vector<uint64_t> &off, uint64_t *need)
     {
-        const size_t bn = b.n();
-        const uint32_t *cov = o.verbose ? b.cov.data() : nullptr, *vao = o.verbose || o.gp || o.pl ? b.var_allele_off.data() : nullptr;
+        const bool lists = o.gp || o.pl; // (a field per genotype: the records' alleles and genotype slots are needed)
+        mg_cells x{};
+        x.n_vars = b.n(), x.n_planes = (uint32_t)P, x.haploid = o.haploid;
+        x.gt1 = b.g1.data(), x.gt2 = b.g2.data(), x.gq = b.gq.data();
+        x.use_mask = o.use_min_gq, x.min_gq = o.min_gq;
+        if (o.verbose) x.cov = b.cov.data();
+        if (o.verbose || lists) x.var_allele_off = b.var_allele_off.data();
+        if (lists) x.var_gt_off = b.var_gt_off.data();
+        if (o.gp) x.probs = b.probs.data(), x.status = b.status.data();
+        if (o.pl) x.pl = b.pl.data();
+        x.fields = (o.gp ? MG_CELLS_GP : 0) | (o.pl ? MG_CELLS_PL : 0);
+        if (!fmt.bcf_out) return mg_format_calls(dev.ctx, &x, text.data(), text.size(), off.data(), need);
         const BcfHeader &hdr = fmt.bcf_hdr;
-        if (o.pl) {
-            const double *probs = o.gp ? b.probs.data() : nullptr;
-            const uint8_t *status = o.gp ? b.status.data() : nullptr;
-            return fmt.bcf_out ? mg_encode_calls_bcf_pl(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao, probs,
-                                                        b.var_gt_off.data(), status, b.pl.data(), hdr.key("GT"), hdr.key("GQ"), o.verbose ? hdr.key("COVS") : 0,
-                                                        o.gp ? hdr.key("GP") : 0, hdr.key("PL"), (uint8_t *)text.data(), text.size(), off.data(), need)
-                               : mg_format_calls_pl(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao, probs,
-                                                    b.var_gt_off.data(), status, b.pl.data(), text.data(), text.size(), off.data(), need);
-        }
-        if (o.gp)
-            return fmt.bcf_out ? mg_encode_calls_bcf_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
-                                                        b.probs.data(), b.var_gt_off.data(), b.status.data(), hdr.key("GT"), hdr.key("GQ"), o.verbose ? hdr.key("COVS") : 0,
-                                                        hdr.key("GP"), (uint8_t *)text.data(), text.size(), off.data(), need)
-                               : mg_format_calls_gp(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao,
-                                                    b.probs.data(), b.var_gt_off.data(), b.status.data(), text.data(), text.size(), off.data(), need);
-        return fmt.bcf_out ? mg_encode_calls_bcf(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, cov, vao, hdr.key("GT"),
-                                                 hdr.key("GQ"), o.verbose ? hdr.key("COVS") : 0, (uint8_t *)text.data(), text.size(), off.data(), need)
-               : o.use_min_gq ? mg_format_calls_masked(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.min_gq, cov, vao, text.data(), text.size(),
-                                                       off.data(), need)
-                              : mg_format_calls(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), cov, vao, text.data(), text.size(), off.data(), need);
+        const mg_bcf_keys keys{hdr.key("GT"), hdr.key("GQ"), o.verbose ? hdr.key("COVS") : 0, o.gp ? hdr.key("GP") : 0, o.pl ? hdr.key("PL") : 0};
+        return mg_encode_calls_bcf(dev.ctx, &x, &keys, (uint8_t *)text.data(), text.size(), off.data(), need);
     }
 
     void merged_rows(Device &dev, Job &job, MergedRows &rows, CallTimes &times)

@@ -1,5 +1,5 @@
 """`call --cohort --merged --gp` and the entries behind it, as far as a machine without a GPU sees them: the header declares and the
-library exports mg_format_calls_gp / mg_encode_calls_bcf_gp and their device forms, the binding has them, the command line lists
+library exports the row encoders that take MG_CELLS_GP in their mg_cells, the binding has its GP methods, the command line lists
 --gp and refuses it without --merged before any device is created.  And the tie strings tests/test_gpu_gp.py expects of the
 device, from Python's own correctly rounded `%.6f`."""
 import os
@@ -11,11 +11,12 @@ from malva_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bin", "malva-geno")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-NAMES = ("mg_format_calls_gp", "mg_format_calls_gp_device", "mg_encode_calls_bcf_gp", "mg_encode_calls_bcf_gp_device")
+NAMES = ("mg_format_calls", "mg_format_calls_device", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device")  # (GP: the bit MG_CELLS_GP of mg_cells.fields)
 
 
 def test_library_exports_and_header_declares_the_gp_entries():
     text = open(os.path.join(ROOT, "include", "malva_hip.h")).read()
+    assert re.search(r"#define\s+MG_CELLS_GP\s+1u", text) and capi.CELLS_GP == 1
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     declared = set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", text))
     L = capi.lib()

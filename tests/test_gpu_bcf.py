@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from malva_amd import Context, MalvaError, synth
+from malva_amd.capi import BcfKeys, Cells
 from test_bcf_out_cpu import bcf_to_vcf, bgzf_members, BGZF_EOF
 
 pytestmark = pytest.mark.gpu
@@ -302,7 +303,7 @@ def test_buffer_too_small(ctx, planes, n, with_cov):
         buf = np.full(len(want) + 64, 0xAA, dtype=np.uint8)
         off = np.full(n + 1, 1 << 63, dtype=np.uint64)
         need = C.c_uint64(0)
-        call = lambda cap_: ctx._L.mg_encode_calls_bcf(ctx.h, n, planes, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), keys[0], keys[1], keys[2],
+        call = lambda cap_: ctx._L.mg_encode_calls_bcf(ctx.h, C.byref(Cells(n, planes, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao))), C.byref(BcfKeys(*keys)),
                                                        p(buf) if cap_ else None, cap_, p(off), C.byref(need))
         assert call(cap) == MG_ERR_LIMIT and need.value == len(want)
         assert np.array_equal(off, want_off)

@@ -1,5 +1,5 @@
 """`call --cohort --merged --gp`: the genotype posteriors as the FORMAT field GP of the merged file, made on the device by
-mg_format_calls_gp (text) and mg_encode_calls_bcf_gp (BCF2).
+mg_format_calls (text) and mg_encode_calls_bcf (BCF2) under MG_CELLS_GP.
 
 The expected bytes come from a restatement written here: Python's `"%.6f" % p` is correctly rounded on the exact binary value with
 ties to even, numpy.float32(p) is IEEE round to nearest even.  The rest of a cell and of a BCF row -- everything that is not GP --
@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from malva_amd import Context, MalvaError, synth
+from malva_amd.capi import CELLS_GP, BcfKeys, Cells
 from test_bcf_out_cpu import bcf_to_vcf, bgzf_members
 from test_gpu_bcf import desc, encode_plain, typed_int
 from test_gpu_merged import format_plain
@@ -292,11 +293,11 @@ def test_buffer_too_small(ctx, bcf):
         off = np.full(n + 1, 1 << 63, dtype=np.uint64)
         need = C.c_uint64(0)
         if bcf:
-            call = lambda c: ctx._L.mg_encode_calls_bcf_gp(ctx.h, n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), *keys,
-                                                           p(buf) if c else None, c, p(off), C.byref(need))
+            call = lambda c: ctx._L.mg_encode_calls_bcf(ctx.h, C.byref(Cells(n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), None, None,
+                                                                          CELLS_GP)), C.byref(BcfKeys(*keys)), p(buf) if c else None, c, p(off), C.byref(need))
         else:
-            call = lambda c: ctx._L.mg_format_calls_gp(ctx.h, n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status),
-                                                       p(buf) if c else None, c, p(off), C.byref(need))
+            call = lambda c: ctx._L.mg_format_calls(ctx.h, C.byref(Cells(n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), None, None,
+                                                                      CELLS_GP)), p(buf) if c else None, c, p(off), C.byref(need))
         assert call(cap) == MG_ERR_LIMIT and need.value == len(want)
         assert np.array_equal(off, want_off)
         assert (buf[cap:] == 0xAA).all()

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from malva_amd import Context, MalvaError, synth
+from malva_amd.capi import Cells
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -203,11 +204,11 @@ def test_buffer_too_small(ctx, planes, n, with_cov):
         buf = np.full(len(want) + 64, 0xAA, dtype=np.uint8)
         off = np.full(n + 1, 1 << 63, dtype=np.uint64)
         need = C.c_uint64(0)
-        rc = ctx._L.mg_format_calls(ctx.h, n, planes, int(haploid), p(g1), p(g2), p(gq), p(cov), p(vao), p(buf) if cap else None, cap, p(off), C.byref(need))
+        rc = ctx._L.mg_format_calls(ctx.h, C.byref(Cells(n, planes, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao))), p(buf) if cap else None, cap, p(off), C.byref(need))
         assert rc == MG_ERR_LIMIT and need.value == len(want)
         assert np.array_equal(off, want_off)
         assert (buf[cap:] == 0xAA).all()
-        rc = ctx._L.mg_format_calls(ctx.h, n, planes, int(haploid), p(g1), p(g2), p(gq), p(cov), p(vao), p(buf), need.value, p(off), C.byref(need))
+        rc = ctx._L.mg_format_calls(ctx.h, C.byref(Cells(n, planes, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao))), p(buf), need.value, p(off), C.byref(need))
         assert rc == 0 and need.value == len(want) and buf[:len(want)].tobytes() == want and (buf[len(want):] == 0xAA).all()
         for shift in (0, 7):
             rc, dneed, text, guard, doff = _device_form(ctx, g1, g2, gq, haploid, cov, vao, cap, guard=4096, shift=shift)

@@ -1,5 +1,5 @@
 """`call --cohort --merged --pl`: prior-free Phred-scaled genotype likelihoods, made on the device by mg_phred_likelihoods and written as
-the FORMAT field PL by mg_format_calls_pl (text) and mg_encode_calls_bcf_pl (BCF2).
+the FORMAT field PL by mg_format_calls (text) and mg_encode_calls_bcf (BCF2) under MG_CELLS_PL.
 
 The values are held against tests/pl_model.py, which tests/test_pl_cpu.py pins to the oracle; the rows against a restatement built here on
 what the tests of the entries without PL pin (test_gpu_merged.format_plain, test_gpu_bcf.encode_plain, test_gpu_gp.expect_text /
@@ -15,6 +15,7 @@ import torch
 
 import pl_model
 from malva_amd import Context, MalvaError
+from malva_amd.capi import CELLS_GP, CELLS_PL, BcfKeys, Cells
 from test_bcf_out_cpu import bcf_to_vcf, bgzf_members
 from test_gpu_bcf import PACK, desc, encode_plain, int_type, typed_int
 from test_gpu_gp import _records, _run, cohorts, expect_bcf, expect_text, n_gt  # noqa: F401 (cohorts: the fixture of the two small cohorts)
@@ -368,11 +369,11 @@ def test_buffer_too_small(ctx, bcf):
         off = np.full(n + 1, 1 << 63, dtype=np.uint64)
         need = C.c_uint64(0)
         if bcf:
-            call = lambda c: ctx._L.mg_encode_calls_bcf_pl(ctx.h, n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), p(pl), *keys,
-                                                           p(buf) if c else None, c, p(off), C.byref(need))
+            call = lambda c: ctx._L.mg_encode_calls_bcf(ctx.h, C.byref(Cells(n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), p(pl), None,
+                                                                          CELLS_GP | CELLS_PL)), C.byref(BcfKeys(*keys)), p(buf) if c else None, c, p(off), C.byref(need))
         else:
-            call = lambda c: ctx._L.mg_format_calls_pl(ctx.h, n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), p(pl),
-                                                       p(buf) if c else None, c, p(off), C.byref(need))
+            call = lambda c: ctx._L.mg_format_calls(ctx.h, C.byref(Cells(n, P, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao), p(probs), p(vgo), p(status), p(pl), None,
+                                                                      CELLS_GP | CELLS_PL)), p(buf) if c else None, c, p(off), C.byref(need))
         assert call(cap) == MG_ERR_LIMIT and need.value == len(want)
         assert np.array_equal(off, want_off)
         assert (buf[cap:] == 0xAA).all()

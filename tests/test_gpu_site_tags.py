@@ -1,5 +1,5 @@
 """`call --cohort --merged --min-gq Q --site-tags`: a GQ mask on the sample columns and AC / AN / AF / NS in INFO, both made on the
-device (mg_format_calls_masked, mg_site_counts, mg_format_site_info).
+device (mg_format_calls under a mask, mg_site_counts, mg_format_site_info).
 
 The ABI is compared with numpy counts and with the rules restated in tests/test_site_tags_cpu.py; the command line with that
 restatement applied to the plain merged file, which tests/test_gpu_merged.py pins.  Every comparison is exact."""
@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from malva_amd import Context, MalvaError, synth
+from malva_amd.capi import Cells
 from test_gpu_merged import COMMON, _case, _cli, _no_leftovers, _singles, _split, format_plain, haploid_cohort  # noqa: F401 (the fixture)
 from test_gpu_bcf import _case as _bcf_case, encode_plain
 from test_site_tags_cpu import info_text
@@ -376,8 +377,8 @@ def test_format_calls_masked_is_exact(ctx, planes, n, haploid, with_cov):
         doff = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
         torch.cuda.synchronize()
         need = C.c_uint64(0)
-        rc = ctx._L.mg_format_calls_masked_device(ctx.h, n, planes, int(haploid), ptr(d1), ptr(d2), ptr(dq), 100, ptr(dc), ptr(dv), text.data_ptr() + 3, cap,
-                                                  doff.data_ptr(), C.byref(need))
+        rc = ctx._L.mg_format_calls_device(ctx.h, C.byref(Cells(n, planes, int(haploid), ptr(d1), ptr(d2), ptr(dq), 1, 100, ptr(dc), ptr(dv))), text.data_ptr() + 3, cap,
+                                           doff.data_ptr(), C.byref(need))
         ctx.synchronize()
         h = text.cpu().numpy()
         assert rc == (0 if cap == len(want) else MG_ERR_LIMIT) and need.value == len(want)

@@ -17,8 +17,8 @@ from oracle import capi as ocapi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bin", "malva-geno")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-NAMES = ("mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats", "mg_format_calls_pl", "mg_format_calls_pl_device", "mg_encode_calls_bcf_pl",
-         "mg_encode_calls_bcf_pl_device")
+NAMES = ("mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats", "mg_format_calls", "mg_format_calls_device", "mg_encode_calls_bcf",
+         "mg_encode_calls_bcf_device")  # (PL: the bit MG_CELLS_PL of mg_cells.fields)
 M = pl_model.MISSING
 
 
@@ -104,6 +104,7 @@ def test_error_rate_zero():
 def test_library_exports_and_header_declares_the_pl_entries():
     text = open(os.path.join(ROOT, "include", "malva_hip.h")).read()
     assert re.search(r"#define\s+MG_PL_MISSING\s+INT32_MIN", text)
+    assert re.search(r"#define\s+MG_CELLS_PL\s+2u", text) and capi.CELLS_PL == 2
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     declared = set(re.findall(r"\b(mg_[a-z0-9_]+)\s*\(", text))
     L = capi.lib()

@@ -15,7 +15,7 @@ from malva_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "bin", "malva-geno")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-NAMES = ("mg_format_calls_masked", "mg_format_calls_masked_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
+NAMES = ("mg_format_calls", "mg_format_calls_device", "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
          "mg_format_site_info_device", "mg_site_stats")
 
 

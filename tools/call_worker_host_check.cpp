@@ -188,11 +188,18 @@ int mg_phred_likelihoods(mg_ctx *c, size_t n, uint32_t planes, const uint32_t *c
     return MG_OK;
 }
 
-// the five row makers: record r's row is "\tR<r>\n"; the whole capacity they are given is written first
-static int rows(mg_ctx *c, const char *name, size_t n, uint32_t planes, const int32_t *gt1, const uint32_t *cov, char *out, size_t cap, uint64_t *off, uint64_t *need)
+// the two row makers: record r's row is "\tR<r>\n"; the whole capacity they are given is written first.  The line says what was asked for:
+// the entry, the mask and the field bits
+static int rows(mg_ctx *c, const char *name, const mg_cells &x, char *out, size_t cap, uint64_t *off, uint64_t *need)
 {
-    touch(gt1, planes * n);
-    say(c, "%s n=%zu planes=%u cap=%zu cov=%d", name, n, planes, cap, (int)(cov != nullptr));
+    const size_t n = x.n_vars, planes = x.n_planes, lists = x.fields ? ((const uint64_t *)x.var_gt_off)[n] : 0;
+    touch((const int32_t *)x.gt1, planes * n);
+    if (x.fields) touch((const uint32_t *)x.var_allele_off, n + 1);
+    if (x.fields & MG_CELLS_GP) touch((const double *)x.probs, planes * lists), touch((const uint8_t *)x.status, planes * n);
+    else if (x.probs || x.status) abort(); // (no GP: its arrays are not given)
+    for (size_t i = 0; i < ((x.fields & MG_CELLS_PL) ? planes * lists : 0); ++i)
+        if (((const int32_t *)x.pl)[i] != 7) abort(); // (what mg_phred_likelihoods left)
+    say(c, "%s mask=%d fields=%u n=%zu planes=%zu cap=%zu cov=%d", name, x.use_mask, x.fields, n, planes, cap, (int)(x.cov != nullptr));
     if (cap) memset(out, 'x', cap);
     if (c->first_need && !c->limit_said) {
         c->limit_said = true;
@@ -210,53 +217,11 @@ static int rows(mg_ctx *c, const char *name, size_t n, uint32_t planes, const in
     memcpy(out, text.data(), text.size());
     return MG_OK;
 }
-int mg_format_calls(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, const uint32_t *cov, const uint32_t *, char *out, size_t cap,
-                    uint64_t *off, uint64_t *need)
+int mg_format_calls(mg_ctx *c, const mg_cells *x, char *out, size_t cap, uint64_t *off, uint64_t *need) { return rows(c, "mg_format_calls", *x, out, cap, off, need); }
+int mg_encode_calls_bcf(mg_ctx *c, const mg_cells *x, const mg_bcf_keys *keys, uint8_t *out, size_t cap, uint64_t *off, uint64_t *need)
 {
-    return rows(c, "mg_format_calls", n, planes, gt1, cov, out, cap, off, need);
-}
-int mg_format_calls_masked(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int32_t, const uint32_t *cov, const uint32_t *, char *out,
-                           size_t cap, uint64_t *off, uint64_t *need)
-{
-    return rows(c, "mg_format_calls_masked", n, planes, gt1, cov, out, cap, off, need);
-}
-int mg_format_calls_gp(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *,
-                       const double *probs, const uint64_t *var_gt_off, const uint8_t *, char *out, size_t cap, uint64_t *off, uint64_t *need)
-{
-    touch(probs, planes * var_gt_off[n]);
-    return rows(c, "mg_format_calls_gp", n, planes, gt1, cov, out, cap, off, need);
-}
-int mg_encode_calls_bcf(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *, int32_t,
-                        int32_t, int32_t, uint8_t *out, size_t cap, uint64_t *off, uint64_t *need)
-{
-    return rows(c, "mg_encode_calls_bcf", n, planes, gt1, cov, (char *)out, cap, off, need);
-}
-int mg_encode_calls_bcf_gp(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *,
-                           const double *probs, const uint64_t *var_gt_off, const uint8_t *, int32_t, int32_t, int32_t, int32_t, uint8_t *out, size_t cap, uint64_t *off,
-                           uint64_t *need)
-{
-    touch(probs, planes * var_gt_off[n]);
-    return rows(c, "mg_encode_calls_bcf_gp", n, planes, gt1, cov, (char *)out, cap, off, need);
-}
-int mg_format_calls_pl(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *vao,
-                       const double *probs, const uint64_t *var_gt_off, const uint8_t *status, const int32_t *pl, char *out, size_t cap, uint64_t *off, uint64_t *need)
-{
-    touch(vao, n + 1);
-    if (probs) touch(probs, planes * var_gt_off[n]), touch(status, planes * n);
-    for (size_t i = 0; i < planes * var_gt_off[n]; ++i)
-        if (pl[i] != 7) abort(); // (what mg_phred_likelihoods left)
-    return rows(c, probs ? "mg_format_calls_pl+gp" : "mg_format_calls_pl", n, planes, gt1, cov, out, cap, off, need);
-}
-int mg_encode_calls_bcf_pl(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int, int32_t, const uint32_t *cov, const uint32_t *vao,
-                           const double *probs, const uint64_t *var_gt_off, const uint8_t *status, const int32_t *pl, int32_t, int32_t, int32_t, int32_t, int32_t key_pl,
-                           uint8_t *out, size_t cap, uint64_t *off, uint64_t *need)
-{
-    touch(vao, n + 1);
-    if (probs) touch(probs, planes * var_gt_off[n]), touch(status, planes * n);
-    for (size_t i = 0; i < planes * var_gt_off[n]; ++i)
-        if (pl[i] != 7) abort();
-    if (key_pl != 8) abort(); // (small_header's ninth ID)
-    return rows(c, probs ? "mg_encode_calls_bcf_pl+gp" : "mg_encode_calls_bcf_pl", n, planes, gt1, cov, (char *)out, cap, off, need);
+    if ((x->fields & MG_CELLS_PL) && keys->pl != 8) abort(); // (small_header's ninth ID)
+    return rows(c, "mg_encode_calls_bcf", *x, (char *)out, cap, off, need);
 }
 int mg_site_counts(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int use_mask, int32_t, const uint32_t *vao, int accumulate,
                    uint32_t *ac, uint32_t *ns)
@@ -747,10 +712,10 @@ static void check_merged_rows()
         const char *name;
         size_t guess; // two records of two planes: 2 (2 * 10 + 1); with --gp 2 (2 + 9 * 6) more as text, 2 (2 + 4 * 6) as BCF
     };
-    const Form forms[] = {{false, false, false, "mg_format_calls", 42},     {false, false, true, "mg_format_calls_masked", 42},
-                          {false, true, false, "mg_format_calls_gp", 154},  {false, true, true, "mg_format_calls_gp", 154},
-                          {true, false, false, "mg_encode_calls_bcf", 42},  {true, false, true, "mg_encode_calls_bcf", 42},
-                          {true, true, false, "mg_encode_calls_bcf_gp", 94}, {true, true, true, "mg_encode_calls_bcf_gp", 94}};
+    const Form forms[] = {{false, false, false, "mg_format_calls mask=0 fields=0", 42},     {false, false, true, "mg_format_calls mask=1 fields=0", 42},
+                          {false, true, false, "mg_format_calls mask=0 fields=1", 154},     {false, true, true, "mg_format_calls mask=1 fields=1", 154},
+                          {true, false, false, "mg_encode_calls_bcf mask=0 fields=0", 42},  {true, false, true, "mg_encode_calls_bcf mask=1 fields=0", 42},
+                          {true, true, false, "mg_encode_calls_bcf mask=0 fields=1", 94},   {true, true, true, "mg_encode_calls_bcf mask=1 fields=1", 94}};
     for (const Form &f : forms) {
         Scene s;
         s.o.gp = f.gp, s.o.use_min_gq = f.min_gq, s.o.min_gq = 20;
@@ -770,15 +735,15 @@ static void check_merged_rows()
             CHECK(slurp(s.merged.path) == "c1\t101\t.\tA\tG" + fixed + "R0\n" + "c1\t301\t.\tC\tG" + fixed + "R1\n" + "c1\t501\t.\tA\tG" + fixed + "R0\n" + "c1\t511\t.\tC\tG" + fixed + "R1\n");
         else CHECK(slurp(s.merged.path).size() > 4 * 4);
     }
-    // --pl: one mg_phred_likelihoods over both planes per batch kind, in front of the rows; the *_pl row makers with and without GP and the mask.
+    // --pl: one mg_phred_likelihoods over both planes per batch kind, in front of the rows; the row makers under MG_CELLS_PL with and without GP and the mask.
     // The guess: 42, with PL 2 (2 + 4 * 6) more as text and 2 (2 + 2 * 6) as BCF, with GP what GP adds
     struct PlForm {
         bool bcf, gp, min_gq;
         const char *name;
         size_t guess;
     };
-    const PlForm pl_forms[] = {{false, false, false, "mg_format_calls_pl", 94},        {false, true, true, "mg_format_calls_pl+gp", 206},
-                               {true, false, true, "mg_encode_calls_bcf_pl", 70},      {true, true, false, "mg_encode_calls_bcf_pl+gp", 122}};
+    const PlForm pl_forms[] = {{false, false, false, "mg_format_calls mask=0 fields=2", 94},    {false, true, true, "mg_format_calls mask=1 fields=3", 206},
+                               {true, false, true, "mg_encode_calls_bcf mask=1 fields=2", 70},  {true, true, false, "mg_encode_calls_bcf mask=0 fields=3", 122}};
     for (const PlForm &f : pl_forms) {
         Scene s;
         s.o.pl = true, s.o.pl_cap = 99, s.o.gp = f.gp, s.o.use_min_gq = f.min_gq, s.o.min_gq = 20;
@@ -826,7 +791,7 @@ static void check_merged_rows()
         s.to.pairs = &pairs; // (and the two tables beside them)
         s.to.sample_table = sample_table.data();
         s.run(2, 2, mixed_batch(2, false));
-        const char *row = where == 2 ? "mg_encode_calls_bcf n=2 planes=2 cap=42 cov=0" : "mg_format_calls n=2 planes=2 cap=42 cov=0", *read_stats = where == 2 ? "mg_bcf_stats" : "mg_format_stats";
+        const char *row = where == 2 ? "mg_encode_calls_bcf mask=0 fields=0 n=2 planes=2 cap=42 cov=0" : "mg_format_calls mask=0 fields=0 n=2 planes=2 cap=42 cov=0", *read_stats = where == 2 ? "mg_bcf_stats" : "mg_format_stats";
         Log kind{row, read_stats, "mg_site_counts n=2 planes=2 mask=0 acc=0", "mg_site_stats"};
         if (where == 0) kind.insert(kind.end(), {"mg_format_site_info n=2 cap=80", "mg_site_stats"});
         Log want = kind;

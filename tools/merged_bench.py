@@ -9,9 +9,9 @@ Timed, each the median of --repeats runs with their spread:
     merged_bcf   `--cohort --merged PATH --merged-format bcf`, merged_ubcf the same with ubcf: the same two, the bytes written, and
                  the device milliseconds per mg_encode_calls_bcf (mg_bcf_stats) -- on the batches the merged leg formats as text
     merged_gp    `--cohort --merged PATH --gp`, merged_gp_bcf the same with `--merged-format bcf`: the same two, the bytes written and
-                 the device milliseconds per mg_format_calls_gp / mg_encode_calls_bcf_gp (mg_format_stats / mg_bcf_stats)
+                 the device milliseconds per mg_format_calls / mg_encode_calls_bcf with MG_CELLS_GP in their mg_cells (mg_format_stats / mg_bcf_stats)
     merged_pl    `--cohort --merged PATH --pl`, merged_pl_bcf the same with `--merged-format bcf`: the same two, the bytes written, the
-                 device milliseconds per mg_format_calls_pl / mg_encode_calls_bcf_pl and per mg_phred_likelihoods (mg_pl_stats); with
+                 device milliseconds per mg_format_calls / mg_encode_calls_bcf with MG_CELLS_PL and per mg_phred_likelihoods (mg_pl_stats); with
                  --parent-bin the parent commit's own `merged` / `merged_bcf` legs run beside them on the same input (parent_merged,
                  parent_merged_bcf): what the two legs are compared with
     parent       `--cohort -o OUTDIR` with --parent-bin, the malva-geno of the parent commit: the yardstick; parent_verdict then holds,
