@@ -735,7 +735,7 @@ MG_EXPORT int mg_create(mg_ctx **out, int device, uint32_t k, uint32_t ref_k, ui
             return MG_ERR_NOMEM;
         }
     }
-    if (alloc_gate(c) != MG_OK || hipMalloc(&c->d_hit_count, 32) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (alloc_gate(c) != MG_OK || hipMalloc(&c->d_hit_count, 40) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         mg_destroy(c);
         return MG_ERR_HIP;
     }
@@ -884,7 +884,7 @@ MG_EXPORT int mg_set_option(mg_ctx *c, const char *name, int64_t value)
         c->sub_words_log2 = (int)value;
     } else if (!strcmp(name, "sub_bins_log2")) c->sub_bins_log2 = (int)std::max<int64_t>(1, std::min<int64_t>(10, value));
     else if (!strcmp(name, "sub_split")) c->sub_split = (int)std::max<int64_t>(1, std::min<int64_t>(64, value));
-    else if (!strcmp(name, "sub_grid")) c->sub_grid = (int)std::max<int64_t>(0, std::min<int64_t>(4096, value));
+    else if (!strcmp(name, "sub_grid")) c->sub_grid = (int)std::max<int64_t>(0, std::min<int64_t>(SB_MAXB, value)); // (nseg <= SB_MAXB: a wave of scan_sub_gate_kernel keeps its segments' fills one per lane)
     else if (!strcmp(name, "ticket_min_log2")) c->ticket_min_log2 = (int)value;
     else if (!strcmp(name, "scan_chunk_log2")) c->chunk_log2 = (int)std::min<int64_t>(27, std::max<int64_t>(10, value));
     else if (!strcmp(name, "ticket_gate_grid")) c->tkg_grid = value > 0 ? (int)std::max<int64_t>(8, std::min<int64_t>(4096, value / 8 * 8)) : 0;
@@ -961,6 +961,7 @@ MG_EXPORT int mg_get_option(mg_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "scan_tickets")) *value = c->last_tickets;
     else if (!strcmp(name, "scan_subs")) *value = c->last_subs;
     else if (!strcmp(name, "use_sub")) *value = c->use_sub;
+    else if (!strcmp(name, "sub_grid")) *value = c->sub_grid;
     else if (!strcmp(name, "exchange_pack")) *value = c->exchange_pack;
     else if (!strcmp(name, "exchange_packed")) *value = c->last_exchange_packed;
     else if (!strcmp(name, "lazy_vectors")) *value = c->lazy_vectors;
@@ -1201,12 +1202,13 @@ int map_dump(mg_ctx *c, std::vector<u64> *klo, std::vector<u64> *khi, std::vecto
     TRY(scratch(c, c->s_misc[2], maxn * 8, &d_lo));
     TRY(scratch(c, c->s_misc[3], maxn * 8, &d_hi));
     TRY(scratch(c, c->s_misc[4], maxn * 4, &d_id));
-    HIP_TRY(c, hipMemsetAsync(c->d_hit_count, 0, 8, c->stream));
+    unsigned long long *d_n = c->d_hit_count + 4; // (a word of its own, not word 0: an export after a scan leaves the open-row count mg_scan_stats reports alone.  mg_bf_finalize and the record loop still reuse the scan's words)
+    HIP_TRY(c, hipMemsetAsync(d_n, 0, 8, c->stream));
     hipLaunchKernelGGL(map_dump_kernel, dim3(nblocks(cap)), dim3(TPB), 0, c->stream, view(c), (u64 *)d_lo, (u64 *)d_hi,
-                       (u32 *)d_id, c->d_hit_count);
+                       (u32 *)d_id, d_n);
     HIP_TRY(c, hipGetLastError());
     unsigned long long cnt = 0;
-    HIP_TRY(c, hipMemcpyAsync(&cnt, c->d_hit_count, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&cnt, d_n, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     klo->resize(cnt);
     khi->resize(cnt);
