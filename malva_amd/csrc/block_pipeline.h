@@ -204,13 +204,16 @@ __device__ __forceinline__ void list_append(bool take, u32 value, u32 *list, uns
     base = __shfl(base, leader, 64);
     if (take) list[base + __popcll(m & ((1ULL << lane) - 1))] = value;
 }
-constexpr int LONE_TILES = 8; // tiles of TPB / 2 records a workgroup of panel_lone_kernel takes (one list reservation per workgroup:
-                              // a returning atomic per wave on ONE counter serialises at ~10 ns each -- 3 ms per 5e6 records)
+constexpr int LONE_TILES = 8; // tiles of TPB / 2 records a workgroup of panel_lone_kernel takes at most (one list reservation per workgroup:
+                              // a returning atomic per wave on ONE counter serialises at ~10 ns each -- 3 ms per 5e6 records).
+                              // The launch says how many, `tiles` in {1, 2, 4, 8} (lone_tiles_for): eight leave a panel of 1e6 records 977
+                              // workgroups where 2,048 are resident together.  The SLOW redo walks the same groups of tiles on a grid of
+                              // its own, however few workgroups (most calls have nothing to redo: every workgroup reads one word and leaves)
 template <bool SLOW>
 __global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) panel_lone_kernel(PanelView P, u64 n_vars, const u32 *__restrict__ blk_var_off, const u32 *__restrict__ var_block,
                                                          const u8 *reference, const u64 *__restrict__ ref2, const u32 *__restrict__ refbad, const u8 *pool, int k,
                                                          int haploid, BFView bf, MapView map, u32 *cov_out, u32 *need_slow, u32 call_no, u32 *gen_list,
-                                                         unsigned long long *counters, unsigned short *rec_class)
+                                                         unsigned long long *counters, unsigned short *rec_class, int tiles)
 {
     __shared__ u32 sh_gen[LONE_TILES * TPB / 2];
     __shared__ u32 sh_n, sh_sigs;
@@ -219,18 +222,22 @@ __global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) panel_lone_kernel(PanelView
     if (threadIdx.x == 0) sh_n = sh_sigs = 0;
     __syncthreads();
     u32 sigs = 0;
-    for (int tile = 0; tile < LONE_TILES; ++tile) {
-        const u64 t = ((u64)blockIdx.x * LONE_TILES + tile) * TPB + threadIdx.x;
-        const u64 v = t >> 1;
-        if (v >= n_vars) break;
-        const LoneClass c = classify_lone(P, blk_var_off, var_block, v, k, haploid, pool);
-        if (!SLOW && !(t & 1)) {
-            if (!c.lone) {
-                sh_gen[atomicAdd(&sh_n, 1u)] = (u32)v;
-                rec_class[v] = c.cls; // (every member of a chain is a record of a block of two or more: listed here)
-            } else sigs += (u32)__popcll(c.mask);
+    // group g is tiles g * tiles .. g * tiles + tiles - 1; the fast kernel has a workgroup per group, the SLOW grid may be smaller and strides on
+    for (u64 group = blockIdx.x; group * tiles * TPB < 2 * n_vars; group += gridDim.x) {
+        for (int tile = 0; tile < tiles; ++tile) {
+            const u64 t = (group * tiles + tile) * TPB + threadIdx.x;
+            const u64 v = t >> 1;
+            if (v >= n_vars) break;
+            const LoneClass c = classify_lone(P, blk_var_off, var_block, v, k, haploid, pool);
+            if (!SLOW && !(t & 1)) {
+                if (!c.lone) {
+                    sh_gen[atomicAdd(&sh_n, 1u)] = (u32)v;
+                    rec_class[v] = c.cls; // (every member of a chain is a record of a block of two or more: listed here)
+                } else sigs += (u32)__popcll(c.mask);
+            }
+            if (c.lone) iso_cover_body<SLOW>(reference, ref2, refbad, c.site, c.a0, c.A, c.eligible, c.mask, (u32)(t & 1), P.allele_off, pool, k, bf, map, cov_out, need_slow, call_no);
         }
-        if (c.lone) iso_cover_body<SLOW>(reference, ref2, refbad, c.site, c.a0, c.A, c.eligible, c.mask, (u32)(t & 1), P.allele_off, pool, k, bf, map, cov_out, need_slow, call_no);
+        if (!SLOW) break;
     }
     if (SLOW) return;
     for (int d = 32; d; d >>= 1) sigs += __shfl_xor(sigs, d, 64);
@@ -253,7 +260,7 @@ template <bool SLOW>
 __global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) cohort_lone_kernel(PanelView P, u64 n_vars, const u32 *__restrict__ blk_var_off, const u32 *__restrict__ var_block,
                                                           const u8 *reference, const u64 *__restrict__ ref2, const u32 *__restrict__ refbad, const u8 *pool, int k,
                                                           int haploid, BFView bf, MapView map, u32 *cov_out, u32 n_planes, u64 plane_stride, u32 *need_slow, u32 call_no,
-                                                          u32 *gen_list, unsigned long long *counters, unsigned short *rec_class)
+                                                          u32 *gen_list, unsigned long long *counters, unsigned short *rec_class, int tiles)
 {
     __shared__ u32 sh_gen[LONE_TILES * TPB / 2];
     __shared__ u32 sh_n, sh_sigs;
@@ -262,20 +269,24 @@ __global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) cohort_lone_kernel(PanelVie
     if (threadIdx.x == 0) sh_n = sh_sigs = 0;
     __syncthreads();
     u32 sigs = 0;
-    for (int tile = 0; tile < LONE_TILES; ++tile) {
-        const u64 t = ((u64)blockIdx.x * LONE_TILES + tile) * TPB + threadIdx.x;
-        const u64 v = t >> 1;
-        if (v >= n_vars) break;
-        const LoneClass c = classify_lone(P, blk_var_off, var_block, v, k, haploid, pool);
-        if (!SLOW && !(t & 1)) {
-            if (!c.lone) {
-                sh_gen[atomicAdd(&sh_n, 1u)] = (u32)v;
-                rec_class[v] = c.cls;
-            } else sigs += (u32)__popcll(c.mask);
+    // group g is tiles g * tiles .. g * tiles + tiles - 1; the fast kernel has a workgroup per group, the SLOW grid may be smaller and strides on
+    for (u64 group = blockIdx.x; group * tiles * TPB < 2 * n_vars; group += gridDim.x) {
+        for (int tile = 0; tile < tiles; ++tile) {
+            const u64 t = (group * tiles + tile) * TPB + threadIdx.x;
+            const u64 v = t >> 1;
+            if (v >= n_vars) break;
+            const LoneClass c = classify_lone(P, blk_var_off, var_block, v, k, haploid, pool);
+            if (!SLOW && !(t & 1)) {
+                if (!c.lone) {
+                    sh_gen[atomicAdd(&sh_n, 1u)] = (u32)v;
+                    rec_class[v] = c.cls;
+                } else sigs += (u32)__popcll(c.mask);
+            }
+            if (c.lone)
+                iso_cover_body<SLOW, true>(reference, ref2, refbad, c.site, c.a0, c.A, c.eligible, c.mask, (u32)(t & 1), P.allele_off, pool, k, bf, map, cov_out, need_slow, call_no,
+                                           n_planes, plane_stride);
         }
-        if (c.lone)
-            iso_cover_body<SLOW, true>(reference, ref2, refbad, c.site, c.a0, c.A, c.eligible, c.mask, (u32)(t & 1), P.allele_off, pool, k, bf, map, cov_out, need_slow, call_no,
-                                       n_planes, plane_stride);
+        if (!SLOW) break;
     }
     if (SLOW) return;
     for (int d = 32; d; d >>= 1) sigs += __shfl_xor(sigs, d, 64);
@@ -291,15 +302,15 @@ __global__ void __launch_bounds__(TPB, SLOW ? 1 : 8) cohort_lone_kernel(PanelVie
 // index time: lone records are inserted here (REF key of record v takes insertion row row0 + v), the others listed
 __global__ void __launch_bounds__(TPB, 8) panel_lone_index_kernel(PanelView P, u64 n_vars, const u32 *__restrict__ blk_var_off, const u32 *__restrict__ var_block,
                                                                const u8 *reference, const u8 *pool, int k, int haploid, BFView bf, MapView map, u32 row0,
-                                                               u8 *overflow, u32 *gen_list, unsigned long long *counters, unsigned short *rec_class)
+                                                               u8 *overflow, u32 *gen_list, unsigned long long *counters, unsigned short *rec_class, int tiles)
 {
     __shared__ u32 sh_gen[LONE_TILES * TPB];
     __shared__ u32 sh_n;
     __shared__ unsigned long long sh_base;
     if (threadIdx.x == 0) sh_n = 0;
     __syncthreads();
-    for (int tile = 0; tile < LONE_TILES; ++tile) {
-        const u64 v = ((u64)blockIdx.x * LONE_TILES + tile) * TPB + threadIdx.x;
+    for (int tile = 0; tile < tiles; ++tile) {
+        const u64 v = ((u64)blockIdx.x * tiles + tile) * TPB + threadIdx.x;
         if (v >= n_vars) break;
         const LoneClass c = classify_lone(P, blk_var_off, var_block, v, k, haploid, pool);
         if (!c.lone) {
@@ -1526,6 +1537,29 @@ __global__ void __launch_bounds__(TPB) fw_slide_kernel(BlockBatch B, FlatWork W,
     }
 }
 
+// What a cover call zeroes before its tiers run, in one launch: two arrays of n bytes (either may be NULL; any alignment: sixteen bytes
+// a store between the unaligned ends) and two runs of 64-bit words (the call's counts, the rounds' counter blocks)
+struct ClearJob {
+    u8 *bytes[2];
+    u64 n;
+    unsigned long long *words[2];
+    u64 n_words[2];
+};
+__global__ void __launch_bounds__(TPB) blocks_clear_kernel(ClearJob J)
+{
+    const u64 n_threads = (u64)gridDim.x * TPB, tid = (u64)blockIdx.x * TPB + threadIdx.x;
+    for (int a = 0; a < 2; ++a) {
+        u8 *p = J.bytes[a];
+        if (!p) continue;
+        const u64 head = min(J.n, (u64)((16 - ((uintptr_t)p & 15)) & 15)), n16 = (J.n - head) / 16, tail = J.n - head - 16 * n16;
+        if (tid < head) p[tid] = 0;
+        uint4 *q = (uint4 *)(p + head);
+        for (u64 i = tid; i < n16; i += n_threads) q[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (tid < tail) p[head + 16 * n16 + tid] = 0;
+    }
+    for (int a = 0; a < 2; ++a)
+        for (u64 i = tid; i < J.n_words[a]; i += n_threads) J.words[a][i] = 0ULL;
+}
 // A/B and tests (use_flat_tier = 0): every general record is handed on to the workgroup kernel
 __global__ void __launch_bounds__(TPB) flag_all_kernel(const u32 *__restrict__ gen_list, const unsigned long long *__restrict__ gen_count, u8 *fb_flag, u32 *cov_out,
                                                        const u32 *__restrict__ var_allele_off)

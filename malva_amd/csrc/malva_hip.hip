@@ -135,6 +135,7 @@ struct mg_ctx {
     bool rec_off = false;                      // the counter vector has been handed out (mg_counters_view): whoever holds it may write it
     u32 rec_epoch = 1;
     int blocks_round_log2 = 24;                // see blocks_setup
+    int lone_tiles = 0;                        // record loop, tier 1: tiles a workgroup takes, 1 / 2 / 4 / 8; 0: by the panel's size (lone_tiles_for)
     int use_hit_entries = 1;                   // scan: the probe kernel hands the hit kernel each row's filter entry (counter index, record) with the row
     int use_snp_chains = 1;                    // record loop: chains of SNPs assembled as the reference window with the members' bases put in
     u64 last_rounds = 0;                       // rounds of tier 2 in the most recent record loop (blocks_listed_chains)
@@ -296,12 +297,17 @@ int scratch(mg_ctx *c, Scratch &s, size_t bytes, void **out)
 // exclusive scan of n_tiles u32 sums in place, their total (u64) to *d_total: store_kernels.h
 int launch_tile_scan(mg_ctx *c, u32 *d_tiles, u64 n_tiles, unsigned long long *d_total)
 {
+    if (n_tiles <= SCAN_CHUNK) { // one workgroup's worth: one launch instead of three
+        hipLaunchKernelGGL(tile_scan_small_kernel, dim3(1), dim3(SCAN_TPB), 0, c->stream, d_tiles, n_tiles, d_total);
+        HIP_TRY(c, hipGetLastError());
+        return MG_OK;
+    }
     const u64 n_part = (n_tiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
     void *part;
-    TRY(scratch(c, c->s_scan, 8 * (n_part ? n_part : 1), &part));
-    if (n_part) hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_tiles, n_tiles, (unsigned long long *)part);
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    hipLaunchKernelGGL(tile_reduce_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, (const u32 *)d_tiles, n_tiles, (unsigned long long *)part);
     hipLaunchKernelGGL(part_scan_kernel, dim3(1), dim3(SCAN_TPB), 0, c->stream, (unsigned long long *)part, n_part, d_total);
-    if (n_part) hipLaunchKernelGGL(tile_rescan_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, d_tiles, n_tiles, (const unsigned long long *)part);
+    hipLaunchKernelGGL(tile_rescan_kernel, dim3((unsigned)n_part), dim3(SCAN_TPB), 0, c->stream, d_tiles, n_tiles, (const unsigned long long *)part);
     HIP_TRY(c, hipGetLastError());
     return MG_OK;
 }
@@ -856,6 +862,10 @@ MG_EXPORT int mg_set_option(mg_ctx *c, const char *name, int64_t value)
         if (value < 10 || value > 24) return fail(c, MG_ERR_ARG, "blocks_round_log2: 10..24");
         c->blocks_round_log2 = (int)value;
     }
+    else if (!strcmp(name, "lone_tiles")) {
+        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(c, MG_ERR_ARG, "lone_tiles: 0 (by the panel's size), 1, 2, 4 or 8");
+        c->lone_tiles = (int)value;
+    }
     else if (!strcmp(name, "map_ordered")) {
         if (c->map.slots && (value != 0) != (c->map_ordered != 0)) return fail(c, MG_ERR_STATE, "map_ordered is a layout: set it before the index is built or loaded");
         c->map_ordered = value != 0;
@@ -947,6 +957,7 @@ MG_EXPORT int mg_get_option(mg_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "use_chain_kernel")) *value = c->use_chain_kernel;
     else if (!strcmp(name, "use_snp_kernel")) *value = c->use_snp_kernel;
     else if (!strcmp(name, "blocks_round_log2")) *value = c->blocks_round_log2;
+    else if (!strcmp(name, "lone_tiles")) *value = c->lone_tiles;
     else if (!strcmp(name, "map_ordered")) *value = c->map_ordered;
     else if (!strcmp(name, "use_record_counters")) *value = c->use_record_counters;
     else if (!strcmp(name, "record_counters_live")) *value = view(c).epoch != 0; // diagnostic: would a lookup launched now read the records' copies?
@@ -2871,7 +2882,43 @@ int blocks_setup(mg_ctx *c, const mg_panel_dev *p, const u32 *d_blk_var_off, con
     *out = R;
     return MG_OK;
 }
-// tier 2 over the whole general list, round by round
+// Tiles a workgroup of tier 1 takes, for `threads` threads in all (two a record; one at index time): as many as still leave the grid
+// five eighths of the workgroups that are resident together (eight a CU) -- the kernel waits for random lines, and a smaller grid
+// leaves wave slots empty while every thread walks its tiles one after the other; a larger one pays a reservation and two barriers
+// per workgroup for nothing.  1e6 records on 256 CUs (7,813 tiles, 2,048 resident): 0.137 / 0.113 / 0.102 / 0.132 ms with 1 / 2 / 4 / 8
+// tiles, so four (1,954 workgroups: all resident at once, no second round); 7e5: 0.086 / 0.082 / 0.109 with 2 / 4 / 8 (1,368 workgroups
+// at four); 1.5e6: 0.157 / 0.159 / 0.155 (1,465 at eight).  The 977 workgroups of 1e6 records at eight are too few, 1,368 are enough.
+// A whole-genome panel keeps LONE_TILES.
+constexpr int LONE_WGS_PER_CU = 5;
+int lone_tiles_for(mg_ctx *c, u64 threads)
+{
+    if (c->lone_tiles) return c->lone_tiles;
+    const u64 n_tiles = (threads + TPB - 1) / TPB, want = (u64)device_cus(c) * LONE_WGS_PER_CU;
+    int tiles = LONE_TILES;
+    while (tiles > 1 && (n_tiles + tiles - 1) / tiles < want) tiles /= 2;
+    return tiles;
+}
+unsigned lone_grid(u64 threads, int tiles) { return (unsigned)((threads + (u64)tiles * TPB - 1) / ((u64)tiles * TPB)); }
+// the SLOW redo of tier 1: no more workgroups than the fast launch has, and no more than are worth starting to find nothing to do
+unsigned lone_slow_grid(mg_ctx *c, unsigned fast_grid) { return std::min<unsigned>(fast_grid, (unsigned)device_cus(c) * 4); }
+// what a cover call zeroes before tier 1 (blocks_clear_kernel): the records' flags, the call's counts or some of them, the rounds' counters
+int blocks_clear(BlocksRun &R, u8 *d_overflow, unsigned long long *counts, u64 n_counts)
+{
+    mg_ctx *c = R.c;
+    ClearJob J{};
+    J.bytes[0] = d_overflow;
+    J.bytes[1] = R.fb_flag;
+    J.n = R.p->n_vars;
+    J.words[0] = counts;
+    J.n_words[0] = n_counts;
+    J.words[1] = R.round_counters;
+    J.n_words[1] = FW_ROUND_COUNTERS * R.n_rounds;
+    const u64 units = std::max<u64>(J.n / 16 + 2, J.n_words[1]);
+    hipLaunchKernelGGL(blocks_clear_kernel, dim3((unsigned)std::min<u64>(nblocks(units), (u64)R.cus * 8)), dim3(TPB), 0, c->stream, J);
+    HIP_TRY(c, hipGetLastError());
+    return MG_OK;
+}
+// tier 2 over the whole general list, round by round; the caller has zeroed the rounds' counters (blocks_clear, or a fill of its own)
 template <int MODE> int blocks_tier2(BlocksRun &R, u32 *d_cov, u8 *d_overflow, unsigned long long *d_cursor, u32 row0, unsigned long long *d_evaluated)
 {
     mg_ctx *c = R.c;
@@ -2881,7 +2928,6 @@ template <int MODE> int blocks_tier2(BlocksRun &R, u32 *d_cov, u8 *d_overflow, u
         HIP_TRY(c, hipGetLastError());
         return MG_OK;
     }
-    HIP_TRY(c, hipMemsetAsync(R.round_counters, 0, 8 * FW_ROUND_COUNTERS * R.n_rounds, c->stream));
     c->last_rounds = R.n_rounds;
     for (u64 r = 0; r < R.n_rounds; ++r) {
         FlatWork W{};
@@ -2943,13 +2989,13 @@ template <int MODE> unsigned blocks_grid(mg_ctx *c)
     }
     return (unsigned)g;
 }
-// tier 3: what tier 2 handed on, compacted, through the workgroup kernel
+// tier 3: what tier 2 handed on, compacted, through the workgroup kernel; where it compacts, the caller has zeroed the list's count
+// (c->d_gen_count[4]: blocks_clear, or a fill of its own; nothing but fb_compact_kernel writes it)
 template <int MODE> int blocks_tier3(BlocksRun &R, bool compact, u32 *d_cov, u8 *d_overflow, unsigned long long *d_cursor, u32 row0, unsigned long long *d_evaluated)
 {
     mg_ctx *c = R.c;
     unsigned long long *fb_count = c->d_gen_count + 4;
     if (compact) { // (the insert pass of `index` walks the counting pass's list)
-        HIP_TRY(c, hipMemsetAsync(fb_count, 0, 8, c->stream));
         hipLaunchKernelGGL(fb_compact_kernel, dim3(R.cus * 8), dim3(TPB), 0, c->stream, (const u32 *)R.gen_list, (const unsigned long long *)c->d_gen_count,
                            (const u8 *)R.fb_flag, R.fb_list, fb_count);
     }
@@ -3028,18 +3074,18 @@ MG_EXPORT int mg_cover_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
     BlocksRun R{};
     TRY(blocks_setup(c, p, (const u32 *)d_blk_var_off, (const u32 *)d_var_block, (const unsigned long long *)d_n_blocks, haploid, &R));
     const u64 n = p->n_vars;
-    HIP_TRY(c, hipMemsetAsync(d_overflow_out, 0, n, c->stream));
-    HIP_TRY(c, hipMemsetAsync(R.fb_flag, 0, n, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_gen_count, 0, 64, c->stream));
+    TRY(blocks_clear(R, (u8 *)d_overflow_out, c->d_gen_count, 8));
     // tier 1: lone and short records (classification fused in); everything else is listed
     u32 *need_slow = (u32 *)(c->d_hit_count + 3);
     if (++c->iso_call_no == 0) c->iso_call_no = 1;
-    hipLaunchKernelGGL(panel_lone_kernel<false>, dim3((unsigned)((2 * n + (u64)LONE_TILES * TPB - 1) / ((u64)LONE_TILES * TPB))), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref,
+    const int tiles = lone_tiles_for(c, 2 * n);
+    const unsigned grid = lone_grid(2 * n, tiles);
+    hipLaunchKernelGGL(panel_lone_kernel<false>, dim3(grid), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref,
                        (const u64 *)c->d_ref2, (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, need_slow,
-                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
-    hipLaunchKernelGGL(panel_lone_kernel<true>, dim3((unsigned)((2 * n + (u64)LONE_TILES * TPB - 1) / ((u64)LONE_TILES * TPB))), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref,
+                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
+    hipLaunchKernelGGL(panel_lone_kernel<true>, dim3(lone_slow_grid(c, grid)), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref,
                        (const u64 *)c->d_ref2, (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, need_slow,
-                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
+                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_b[1], c->stream));
     TRY(blocks_tier2<0>(R, (u32 *)d_cov_out, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3));
@@ -3082,29 +3128,26 @@ int cover_cohort(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, co
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         slots = h_slots;
     }
-    HIP_TRY(c, hipMemsetAsync(d_overflow_out, 0, n, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_gen_count, 0, 64, c->stream));
+    TRY(blocks_clear(R, (u8 *)d_overflow_out, c->d_gen_count, 8)); // (with plane 0's flags and round counters)
     u32 *need_slow = (u32 *)(c->d_hit_count + 3);
     if (++c->iso_call_no == 0) c->iso_call_no = 1;
     const u32 sel = c->coh_sel;
     c->coh_sel = 0; // tier 1's views address plane 0: the kernel walks the cells from there
-    const unsigned grid = (unsigned)((2 * n + (u64)LONE_TILES * TPB - 1) / ((u64)LONE_TILES * TPB));
+    const int tiles = lone_tiles_for(c, 2 * n);
+    const unsigned grid = lone_grid(2 * n, tiles);
     hipLaunchKernelGGL(cohort_lone_kernel<false>, dim3(grid), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u64 *)c->d_ref2,
                        (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, c->coh_planes, slots, need_slow,
-                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
-    hipLaunchKernelGGL(cohort_lone_kernel<true>, dim3(grid), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u64 *)c->d_ref2,
+                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
+    hipLaunchKernelGGL(cohort_lone_kernel<true>, dim3(lone_slow_grid(c, grid)), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u64 *)c->d_ref2,
                        (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, c->coh_planes, slots, need_slow,
-                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
+                       c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
     int rc = hipGetLastError() == hipSuccess ? MG_OK : fail(c, MG_ERR_HIP, "cohort_lone_kernel launch failed");
     if (rc == MG_OK && hipEventRecord(c->ev_c[1], c->stream) != hipSuccess) rc = fail(c, MG_ERR_HIP, "hipEventRecord failed");
     for (u32 s = 0; s < c->coh_planes && rc == MG_OK; ++s) { // the other records, plane by plane, through the single-sample tiers
         c->coh_sel = s;
         u32 *cov = (u32 *)d_cov_out + (u64)s * slots;
-        if (hipMemsetAsync(R.fb_flag, 0, n, c->stream) != hipSuccess || hipMemsetAsync(c->d_gen_count + 3, 0, 16, c->stream) != hipSuccess) {
-            rc = fail(c, MG_ERR_HIP, "hipMemsetAsync failed");
-            break;
-        }
-        rc = blocks_tier2<0>(R, cov, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3);
+        if (s) rc = blocks_clear(R, nullptr, c->d_gen_count + 3, 2); // the plane's own: flags, signature k-mers and tier 3's count, round counters
+        if (rc == MG_OK) rc = blocks_tier2<0>(R, cov, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3);
         if (rc == MG_OK) rc = blocks_tier3<0>(R, true, cov, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3);
         if (rc != MG_OK) break;
         hipLaunchKernelGGL(fw_finish_kernel, dim3(R.cus * 8), dim3(TPB), 0, c->stream, R.B, (const u32 *)R.gen_list, (const unsigned long long *)c->d_gen_count,
@@ -4105,13 +4148,16 @@ MG_EXPORT int mg_index_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
     HIP_TRY(c, hipMemsetAsync(R.fb_flag, 0, n, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_gen_count, 0, 64, c->stream));
     // tier 1: lone and short records are inserted at once; everything else is listed
-    hipLaunchKernelGGL(panel_lone_index_kernel, dim3((unsigned)((n + (u64)LONE_TILES * TPB - 1) / ((u64)LONE_TILES * TPB))), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u8 *)p->pool,
-                       (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32)c->map.rows_total, (u8 *)d_overflow_out, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class);
+    const int tiles = lone_tiles_for(c, n);
+    hipLaunchKernelGGL(panel_lone_index_kernel, dim3(lone_grid(n, tiles)), dim3(TPB), 0, c->stream, R.P, n, R.B.blk_var_off, R.B.var_block, (const u8 *)c->d_ref, (const u8 *)p->pool,
+                       (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32)c->map.rows_total, (u8 *)d_overflow_out, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
     HIP_TRY(c, hipGetLastError());
     c->map.rows_total += n;
     unsigned long long *d_cursor = c->d_gen_count + 1;
     // pass 1: how many exact-map insertion rows the other records need; which of them go to tier 3, which to the host
+    HIP_TRY(c, hipMemsetAsync(R.round_counters, 0, 8 * FW_ROUND_COUNTERS * R.n_rounds, c->stream));
     TRY(blocks_tier2<1>(R, nullptr, (u8 *)d_overflow_out, d_cursor, 0u, nullptr));
+    HIP_TRY(c, hipMemsetAsync(c->d_gen_count + 4, 0, 8, c->stream)); // (tier 3's count, before it compacts)
     TRY(blocks_tier3<1>(R, true, nullptr, (u8 *)d_overflow_out, d_cursor, 0u, nullptr));
     unsigned long long rows = 0;
     HIP_TRY(c, hipMemcpyAsync(&rows, d_cursor, 8, hipMemcpyDeviceToHost, c->stream));
@@ -4121,6 +4167,7 @@ MG_EXPORT int mg_index_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
     // device reached them in: the index FILE, which every GPU of a call loads alike, is what fixes the counter layout).
     // The records keep the tier pass 1 gave them (its flags stand), so the rows counted are the rows used.
     HIP_TRY(c, hipMemsetAsync(d_cursor, 0, 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(R.round_counters, 0, 8 * FW_ROUND_COUNTERS * R.n_rounds, c->stream));
     TRY(blocks_tier2<2>(R, nullptr, (u8 *)d_overflow_out, d_cursor, (u32)c->map.rows_total, nullptr));
     TRY(blocks_tier3<2>(R, false, nullptr, (u8 *)d_overflow_out, d_cursor, (u32)c->map.rows_total, nullptr));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

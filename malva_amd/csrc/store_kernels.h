@@ -348,6 +348,40 @@ __global__ void __launch_bounds__(SCAN_TPB) tile_rescan_kernel(u32 *x, u64 n, co
         __syncthreads();
     }
 }
+// The same scan for up to SCAN_CHUNK sums (the cut of 2.1e6 records) in ONE launch of one workgroup: the three above are then a
+// workgroup each, and what they cost is their launches.  A thread takes SCAN_PER sums in a row.
+__global__ void __launch_bounds__(SCAN_TPB) tile_scan_small_kernel(u32 *x, u64 n, unsigned long long *total)
+{
+    __shared__ unsigned long long sh16[SCAN_TPB / 64];
+    const u64 base = (u64)threadIdx.x * SCAN_PER;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u32 v[SCAN_PER];
+    unsigned long long own = 0;
+#pragma unroll
+    for (int j = 0; j < SCAN_PER; ++j) {
+        v[j] = base + j < n ? x[base + j] : 0u;
+        own += v[j];
+    }
+    unsigned long long incl = own;
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = (unsigned long long)__shfl_up((long long)incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) sh16[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (int w = 0; w < SCAN_TPB / 64; ++w) {
+        if (w < wave) before += sh16[w];
+        all += sh16[w];
+    }
+    unsigned long long run = before + incl - own;
+#pragma unroll
+    for (int j = 0; j < SCAN_PER; ++j) {
+        if (base + j < n) x[base + j] = (u32)run; // valid while the grand total fits 32 bits (checked by the host)
+        run += v[j];
+    }
+    if (threadIdx.x == 0) *total = all;
+}
 __global__ void __launch_bounds__(TPB) blk_add_kernel(u32 *blk, u64 n_blk, const u32 *tile_sums, u32 total)
 {
     const u64 b = (u64)blockIdx.x * TPB + threadIdx.x;
