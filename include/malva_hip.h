@@ -275,42 +275,59 @@ int mg_lookup_cover(mg_ctx *ctx, const char *rows, size_t stride, size_t n_rows,
 int mg_cut_blocks(mg_ctx *ctx, size_t n_vars, const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size,
                   const uint32_t *contig_id, uint32_t *blk_var_off_out, size_t *n_blocks_out);
 
+/* A batch of blocks of any shape in HOST memory, as the three host forms of the record loop below take it (mg_panel_dev is the
+ * same panel resident on the device).  Variants are flat across blocks; every pointer is a HOST pointer. */
+typedef struct mg_blocks_host {
+    size_t n_blocks;
+    const uint64_t *blk_ref_base;    /* [n_blocks] where the block's contig starts in the uploaded reference ... */
+    const uint32_t *blk_ref_len;     /* [n_blocks] ... and how long it is */
+    const uint32_t *blk_var_off;     /* [n_blocks + 1] first record of every block, n_vars behind the last (mg_cut_blocks) */
+    size_t n_vars;
+    const int32_t *pos;              /* [n_vars] 0-based position in the block's contig (Variant::ref_pos) */
+    const uint32_t *ref_size;        /* [n_vars] */
+    const uint32_t *min_size;        /* [n_vars] */
+    const uint8_t *present;          /* [n_vars] Variant::is_present */
+    const uint32_t *var_allele_off;  /* [n_vars + 1]; slots = var_allele_off[n_vars], one per (variant, allele) */
+    const uint32_t *allele_off;      /* [slots + 1] into pool */
+    const char *pool;                /* [pool_len] the alleles' text */
+    size_t pool_len;
+    const uint8_t *canon;            /* [slots] first allele index of the variant with the same text (variant.hpp:228) */
+    uint32_t n_samples;              /* kept panel samples */
+    /* gt[v * n_samples + s] = a1 | a2 << 7 | phased << 14 (variant.hpp:158-211); a1 and a2 are below the record's allele count (the
+     * reference reads out of bounds otherwise; the library does not check: its caller's reader does) */
+    const uint16_t *gt;              /* [n_vars][n_samples], or NULL with the sparse form */
+    /* the sparse form of mg_panel_dev (only the samples whose genotype word is not sp_default: what crosses PCIe for a 27,934-sample
+     * panel drops from 56 KB per record to a few bytes per non-reference genotype).  Given (non-NULL sp_off), `gt` is ignored; both
+     * NULL with n_samples > 0 is MG_ERR_ARG. */
+    const uint32_t *sp_off;          /* [n_vars + 1] or NULL */
+    const uint32_t *sp_sample;       /* [sp_off[n_vars]] ascending below n_samples inside a record */
+    const uint16_t *sp_gt;           /* [sp_off[n_vars]] */
+    uint16_t sp_default;
+} mg_blocks_host;
+
 /* VB::extract_kmers (var_block.hpp:95-219, chains :436-677, haplotype picks :709-786) fused with
- * set_coverages (main.cpp:151-184) for blocks of any shape, enumerated ON THE DEVICE.  Variants are flat
- * across blocks (blk_var_off); pos is the 0-based position in the block's contig, which starts at
- * blk_ref_base in the uploaded reference and is blk_ref_len long; canon[slot] = first allele index of
- * the variant with the same text (variant.hpp:228); gt[v * n_samples + s] = a1 | a2 << 7 | phased << 14
- * for the kept panel samples (variant.hpp:158-211); a1 and a2 are below the record's allele count (the reference
- * reads out of bounds otherwise; the library does not check: its caller's reader does).  cov_out as in mg_lookup_cover, one slot per
- * (variant, allele).  overflow_out[v] = 1 where a fixed device capacity (16 chains per side, 32 members per
+ * set_coverages (main.cpp:151-184) for blocks of any shape, enumerated ON THE DEVICE.  cov_out as in mg_lookup_cover, one
+ * slot per (variant, allele).  overflow_out[v] = 1 where a fixed device capacity (16 chains per side, 32 members per
  * chain side, 14 unphased members, 127 alleles, k <= 64) or a window clipped by a contig end was hit: redo
- * that variant's block through the host enumerator + mg_lookup_cover. */
-int mg_cover_blocks(mg_ctx *ctx, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len,
-                    const uint32_t *blk_var_off, size_t n_vars, const int32_t *pos, const uint32_t *ref_size,
-                    const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                    const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                    const uint16_t *gt, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out);
+ * that variant's block through the host enumerator + mg_lookup_cover.  A NULL batch is MG_ERR_ARG. */
+int mg_cover_blocks(mg_ctx *ctx, const mg_blocks_host *blocks, int haploid, uint32_t *cov_out, uint8_t *overflow_out);
 
 /* The same enumeration at INDEX time: VB::extract_kmers + add_kmers_to_bf (main.cpp:349-350, 122-144) for blocks of any
  * shape -- every signature k-mer of allele 0 is added to the exact map (KMAP::add_key), every other one sets its bit of
- * `bf` (BF::add_key).  Arguments as mg_cover_blocks (the panel genotypes decide which alleles have signatures); the
+ * `bf` (BF::add_key).  The batch as for mg_cover_blocks (the panel genotypes decide which alleles have signatures); the
  * blocks hold only the variants `index` keeps (has_alts and is_present, main.cpp:332).  overflow_out[v] = 1: nothing of
  * that variant was inserted (a device capacity, a window clipped by a contig end, or a REF k-mer the packed table cannot
  * hold) -- enumerate its block on the host and insert with mg_map_insert / mg_bf_insert.  Before mg_bf_finalize.
  * Counter ids of keys inserted here follow the order the device reached them in; ranks of a multi-GPU call agree on
  * the layout by loading the same index file. */
-int mg_index_blocks(mg_ctx *ctx, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len,
-                    const uint32_t *blk_var_off, size_t n_vars, const int32_t *pos, const uint32_t *ref_size,
-                    const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                    const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                    const uint16_t *gt, uint32_t n_samples, int haploid, uint8_t *overflow_out);
+int mg_index_blocks(mg_ctx *ctx, const mg_blocks_host *blocks, int haploid, uint8_t *overflow_out);
 
 /* ---- the record loop on a RESIDENT panel (main.cpp:522-579 / 309-370 with every array already in HBM) --------------------
  * A panel is the kept records of a VCF (or of a batch of one) in file order, as flat arrays: every pointer below is a
  * DEVICE pointer on the context's GPU, nothing is copied or re-uploaded, and the calls are asynchronous on the
  * context's stream (mg_index_blocks_device excepted, see there).  Record v sits on sequence contig_id[v], which starts
  * at contig_base[] in the buffer of mg_reference_upload and is contig_len[] long; the other arrays are those of
- * mg_cover_blocks.  One step of `call` on a resident panel is
+ * mg_blocks_host.  One step of `call` on a resident panel is
  *     mg_cut_blocks_device -> mg_cover_blocks_device -> mg_genotype_device
  * and of `index`:  mg_cut_blocks_device -> mg_index_blocks_device. */
 typedef struct mg_panel_dev {
@@ -366,14 +383,10 @@ int mg_cover_blocks_device(mg_ctx *ctx, const mg_panel_dev *panel, const void *d
 int mg_cover_blocks_cohort_device(mg_ctx *ctx, const mg_panel_dev *panel, const void *d_blk_var_off, const void *d_var_block /* or NULL */,
                                   const void *d_n_blocks, int haploid, void *d_cov_out, void *d_overflow_out);
 int mg_cohort_stats(mg_ctx *ctx, float *ms_out);
-/* The host form (as mg_cover_blocks / mg_cover_blocks_sparse are of mg_cover_blocks_device): the batch is uploaded ONCE and covered
- * for every plane; `gt` dense, or NULL with the sparse triple; cov_out is [n_planes][slots], overflow_out [n_vars].  Knows the slot
- * count from var_allele_off, so it does not wait for the device before the copy back.  Synchronous. */
-int mg_cover_blocks_cohort(mg_ctx *ctx, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off,
-                           size_t n_vars, const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present,
-                           const uint32_t *var_allele_off, const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                           const uint16_t *gt, const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default,
-                           uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out);
+/* The host form (as mg_cover_blocks is of mg_cover_blocks_device): the batch is uploaded ONCE and covered for every plane; cov_out is
+ * [n_planes][slots], overflow_out [n_vars].  Knows the slot count from var_allele_off, so it does not wait for the device before the
+ * copy back.  Synchronous. */
+int mg_cover_blocks_cohort(mg_ctx *ctx, const mg_blocks_host *blocks, int haploid, uint32_t *cov_out /* [n_planes][slots] */, uint8_t *overflow_out);
 /* extract_kmers + add_kmers_to_bf (main.cpp:349-350) for every block (the panel holds only what `index` keeps,
  * main.cpp:332); d_overflow_out as mg_index_blocks.  The arrays stay where they are, but the call waits for the device
  * twice on eight bytes: the exact map is sized from a counting pass before the insert pass runs. */
@@ -398,22 +411,6 @@ int mg_decode_gt_text(mg_ctx *ctx, const char *text, size_t text_bytes, size_t n
                       const int32_t *gt_index, uint32_t n_columns, const uint8_t *keep, int haploid, uint16_t *sp_default, uint32_t *sp_off,
                       uint64_t *raw_mask, uint32_t *max_allele, uint64_t *n_entries);
 int mg_decode_gt_entries(mg_ctx *ctx, uint32_t *sp_sample, uint16_t *sp_gt);
-
-/* mg_cover_blocks / mg_index_blocks with the panel's genotypes in the sparse form of mg_panel_dev (sp_off, sp_sample, sp_gt:
- * only the samples whose genotype word is not sp_default).  What crosses PCIe for a 27,934-sample panel drops from 56 KB per
- * record to a few bytes per non-reference genotype. */
-int mg_cover_blocks_sparse(mg_ctx *ctx, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len,
-                           const uint32_t *blk_var_off, size_t n_vars, const int32_t *pos, const uint32_t *ref_size,
-                           const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                           const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                           const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default,
-                           uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out);
-int mg_index_blocks_sparse(mg_ctx *ctx, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len,
-                           const uint32_t *blk_var_off, size_t n_vars, const int32_t *pos, const uint32_t *ref_size,
-                           const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                           const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                           const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default,
-                           uint32_t n_samples, int haploid, uint8_t *overflow_out);
 
 /* Result codes of mg_genotype / mg_call_isolated per variant */
 #define MG_GT_NORMAL 0   /* likelihood list computed                              */

@@ -139,7 +139,7 @@ def lib():
         "mg_phred_likelihoods": [vp, sz, u32, vp, vp, vp, fl, it, it, i32, vp],
         "mg_phred_likelihoods_device": [vp, sz, u32, vp, vp, vp, fl, it, it, i32, vp],
         "mg_pl_stats": [vp, vp],
-        "mg_cover_blocks_cohort": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
+        "mg_cover_blocks_cohort": [vp, C.POINTER(BlocksHost), it, vp, vp],
         "mg_comm_unique_id": [vp],
         "mg_comm_init": [vp, it, it, vp],
         "mg_comm_init_all": [C.POINTER(vp), it],
@@ -152,18 +152,16 @@ def lib():
         "mg_exchange_stats": [vp, vp, vp],
         "mg_lookup_cover": [vp, vp, sz, sz, vp, vp, sz, vp, sz, vp],
         "mg_genotype": [vp, vp, vp, vp, sz, fl, it, it, vp, vp, vp, vp, vp, vp],
-        "mg_cover_blocks": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, u32, it, vp, vp],
+        "mg_cover_blocks": [vp, C.POINTER(BlocksHost), it, vp, vp],
         "mg_decode_gt_text": [vp, vp, sz, sz, vp, vp, vp, u32, vp, it, vp, vp, vp, vp, vp],
         "mg_decode_gt_entries": [vp, vp, vp],
-        "mg_cover_blocks_sparse": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.c_uint16, u32, it, vp, vp],
-        "mg_index_blocks_sparse": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, C.c_uint16, u32, it, vp],
         "mg_cut_blocks": [vp, sz, vp, vp, vp, vp, vp, vp],
         "mg_cut_blocks_device": [vp, vp, vp, vp, vp],
         "mg_cover_blocks_device": [vp, vp, vp, vp, vp, it, vp, vp],
         "mg_index_blocks_device": [vp, vp, vp, vp, vp, it, vp],
         "mg_genotype_device": [vp, vp, vp, vp, sz, fl, it, it, vp, vp, vp, vp, vp, vp],
         "mg_index_isolated": [vp, sz, vp, vp, vp, vp, sz, vp, vp, vp],
-        "mg_index_blocks": [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, u32, it, vp],
+        "mg_index_blocks": [vp, C.POINTER(BlocksHost), it, vp],
         "mg_reference_upload": [vp, vp, sz],
         "mg_call_isolated": [vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, fl, it, it, vp, vp, vp, vp, vp, vp, vp],
         "mg_call_isolated_device": [vp, sz, vp, vp, vp, vp, vp, vp, vp, fl, it, it, vp, vp, vp, vp, vp, vp, vp],
@@ -209,7 +207,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
             "mg_index_isolated",
-            "mg_lookup_cover", "mg_cover_blocks", "mg_index_blocks", "mg_cover_blocks_sparse", "mg_index_blocks_sparse", "mg_genotype", "mg_reference_upload", "mg_call_isolated", "mg_call_isolated_device",
+            "mg_lookup_cover", "mg_cover_blocks", "mg_index_blocks", "mg_genotype", "mg_reference_upload", "mg_call_isolated", "mg_call_isolated_device",
             "mg_bf_export", "mg_bf_import", "mg_bf_export_sparse", "mg_bf_import_sparse", "mg_map_export", "mg_map_import", "mg_debug_bf_index",
             "mg_debug_packed_index", "mg_debug_tile_scan", "mg_debug_bucket_count", "mg_scan_stats", "mg_blocks_stats", "mg_set_option", "mg_get_option"]
 
@@ -236,6 +234,15 @@ class Cells(C.Structure):
                 ("var_gt_off", C.c_void_p), ("status", C.c_void_p), ("pl", C.c_void_p), ("allele_class", C.c_void_p), ("fields", C.c_uint32)]
 
 
+class BlocksHost(C.Structure):
+    """mg_blocks_host: a batch of blocks in host memory for mg_cover_blocks, mg_cover_blocks_cohort and mg_index_blocks (every pointer a host pointer)"""
+    _fields_ = [("n_blocks", C.c_size_t), ("blk_ref_base", C.c_void_p), ("blk_ref_len", C.c_void_p), ("blk_var_off", C.c_void_p),
+                ("n_vars", C.c_size_t), ("pos", C.c_void_p), ("ref_size", C.c_void_p), ("min_size", C.c_void_p), ("present", C.c_void_p),
+                ("var_allele_off", C.c_void_p), ("allele_off", C.c_void_p), ("pool", C.c_void_p), ("pool_len", C.c_size_t), ("canon", C.c_void_p),
+                ("n_samples", C.c_uint32), ("gt", C.c_void_p), ("sp_off", C.c_void_p), ("sp_sample", C.c_void_p), ("sp_gt", C.c_void_p),
+                ("sp_default", C.c_uint16)]
+
+
 class BcfKeys(C.Structure):
     """mg_bcf_keys: the header's dictionary indexes of the FORMAT fields"""
     _fields_ = [("gt", C.c_int32), ("gq", C.c_int32), ("cov", C.c_int32), ("gp", C.c_int32), ("pl", C.c_int32)]
@@ -259,6 +266,26 @@ def sparse_genotypes(gt, n_samples, default=1 << 14):
     off[1:] = np.cumsum(keep.sum(axis=1))
     rows, cols = np.nonzero(keep)
     return off, cols.astype(np.uint32), gt[rows, cols].astype(np.uint16)
+
+
+def _blocks_host(blk_ref_base, blk_ref_len, blk_var_off, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, canon, gt, n_samples,
+                 sparse, sp_default):
+    """the arrays of a host batch of blocks as numpy arrays of the ABI's types -> BlocksHost (which keeps the arrays it points into alive).
+    sparse: the genotypes as the entries other than the word sp_default (sparse_genotypes), and no `gt`"""
+    types = (np.uint64, np.uint32, np.uint32, np.int32, np.uint32, np.uint32, np.uint8, np.uint8, np.uint32, np.uint32, np.uint8, np.uint16)
+    given = (blk_ref_base, blk_ref_len, blk_var_off, pos, ref_size, min_size, present, canon, var_allele_off, allele_off, pool, gt)
+    bb, bl, bo, pos, rs, ms, pr, canon, vo, ao, pool, gt = arrays = [np.ascontiguousarray(g, dtype=t) for g, t in zip(given, types)]
+    n = len(pos)
+    x = BlocksHost(n_blocks=len(bb), blk_ref_base=_p(bb), blk_ref_len=_p(bl), blk_var_off=_p(bo), n_vars=n, pos=_p(pos), ref_size=_p(rs), min_size=_p(ms),
+                   present=_p(pr), var_allele_off=_p(vo), allele_off=_p(ao), pool=_p(pool), pool_len=pool.size, canon=_p(canon), n_samples=n_samples,
+                   sp_default=sp_default)
+    if sparse:
+        arrays += sparse_genotypes(gt.reshape(n, -1) if n else gt, n_samples, sp_default)
+        x.sp_off, x.sp_sample, x.sp_gt = (_p(q) for q in arrays[-3:])
+    else:
+        x.gt = _p(gt)
+    x.arrays = arrays
+    return x
 
 
 def host_alloc(n_bytes):
@@ -1039,22 +1066,16 @@ class Context:
         return cov
 
     def cover_blocks(self, blk_ref_base, blk_ref_len, blk_var_off, pos, ref_size, min_size, present, var_allele_off,
-                     allele_off, pool, canon, gt, n_samples, haploid, sparse=False, sp_default=1 << 14):
-        """sparse: hand the genotypes over as the entries other than the word sp_default (mg_cover_blocks_sparse)"""
-        a = lambda x, t: np.ascontiguousarray(x, dtype=t)
-        bb, bl, bo = a(blk_ref_base, np.uint64), a(blk_ref_len, np.uint32), a(blk_var_off, np.uint32)
-        pos, rs, ms, pr = a(pos, np.int32), a(ref_size, np.uint32), a(min_size, np.uint32), a(present, np.uint8)
-        vo, ao, pool, canon, gt = a(var_allele_off, np.uint32), a(allele_off, np.uint32), a(pool, np.uint8), a(canon, np.uint8), a(gt, np.uint16)
-        n = len(pos)
-        cov = np.zeros(int(vo[-1]), dtype=np.uint32)
-        ovf = np.zeros(n, dtype=np.uint8)
-        if sparse:
-            so, ss, sg = sparse_genotypes(gt.reshape(n, -1) if n else gt, n_samples, sp_default)
-            self._ck(self._L.mg_cover_blocks_sparse(self.h, len(bb), _p(bb), _p(bl), _p(bo), n, _p(pos), _p(rs), _p(ms), _p(pr), _p(vo), _p(ao),
-                                                    _p(pool), pool.size, _p(canon), _p(so), _p(ss), _p(sg), sp_default, n_samples, int(haploid), _p(cov), _p(ovf)))
-            return cov, ovf
-        self._ck(self._L.mg_cover_blocks(self.h, len(bb), _p(bb), _p(bl), _p(bo), n, _p(pos), _p(rs), _p(ms), _p(pr), _p(vo), _p(ao),
-                                         _p(pool), pool.size, _p(canon), _p(gt), n_samples, int(haploid), _p(cov), _p(ovf)))
+                     allele_off, pool, canon, gt, n_samples, haploid, sparse=False, sp_default=1 << 14, all_planes=False):
+        """sparse: hand the genotypes over as the entries other than the word sp_default.  all_planes: every plane of a context in cohort
+        mode (mg_cover_blocks_cohort), cov as [n_planes][slots]"""
+        x = _blocks_host(blk_ref_base, blk_ref_len, blk_var_off, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, canon, gt,
+                         n_samples, sparse, sp_default)
+        slots = int(var_allele_off[-1])
+        cov = np.zeros((self.cohort_info()[0], slots) if all_planes else slots, dtype=np.uint32)
+        ovf = np.zeros(x.n_vars, dtype=np.uint8)
+        entry = self._L.mg_cover_blocks_cohort if all_planes else self._L.mg_cover_blocks
+        self._ck(entry(self.h, C.byref(x), int(haploid), _p(cov), _p(ovf)))
         return cov, ovf
 
     def index_isolated(self, pos, var_allele_off, allele_off, pool, present_mask, flags):
@@ -1096,19 +1117,10 @@ class Context:
 
     def index_blocks(self, blk_ref_base, blk_ref_len, blk_var_off, pos, ref_size, min_size, present, var_allele_off,
                      allele_off, pool, canon, gt, n_samples, haploid, sparse=False, sp_default=1 << 14):
-        a = lambda x, t: np.ascontiguousarray(x, dtype=t)
-        bb, bl, bo = a(blk_ref_base, np.uint64), a(blk_ref_len, np.uint32), a(blk_var_off, np.uint32)
-        pos, rs, ms, pr = a(pos, np.int32), a(ref_size, np.uint32), a(min_size, np.uint32), a(present, np.uint8)
-        vo, ao, pool, canon, gt = a(var_allele_off, np.uint32), a(allele_off, np.uint32), a(pool, np.uint8), a(canon, np.uint8), a(gt, np.uint16)
-        n = len(pos)
-        ovf = np.zeros(n, dtype=np.uint8)
-        if sparse:
-            so, ss, sg = sparse_genotypes(gt.reshape(n, -1) if n else gt, n_samples, sp_default)
-            self._ck(self._L.mg_index_blocks_sparse(self.h, len(bb), _p(bb), _p(bl), _p(bo), n, _p(pos), _p(rs), _p(ms), _p(pr), _p(vo), _p(ao),
-                                                    _p(pool), pool.size, _p(canon), _p(so), _p(ss), _p(sg), sp_default, n_samples, int(haploid), _p(ovf)))
-            return ovf
-        self._ck(self._L.mg_index_blocks(self.h, len(bb), _p(bb), _p(bl), _p(bo), n, _p(pos), _p(rs), _p(ms), _p(pr), _p(vo), _p(ao),
-                                         _p(pool), pool.size, _p(canon), _p(gt), n_samples, int(haploid), _p(ovf)))
+        x = _blocks_host(blk_ref_base, blk_ref_len, blk_var_off, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, canon, gt,
+                         n_samples, sparse, sp_default)
+        ovf = np.zeros(x.n_vars, dtype=np.uint8)
+        self._ck(self._L.mg_index_blocks(self.h, C.byref(x), int(haploid), _p(ovf)))
         return ovf
 
     def genotype(self, cov, freq, var_allele_off, error_rate, max_cov, haploid, want_probs=False):

@@ -81,14 +81,15 @@ struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
 };
-// One timed call of the merged-batch section: its events (the first n of them: start, then the end of each part) and whether they are those
-// of a call that ran (timer_begin, timer_mark, timer_read).  TM_FMT .. TM_BCF are the three row encoders (encode_rows) and index s_enc too.
+// One timed call of the record loop or of the merged-batch section: its events (the first n of them: start, then the end of each part) and
+// whether they are those of a call that ran (timer_begin, timer_mark, timer_read).  TM_FMT .. TM_BCF are the three row encoders (encode_rows)
+// and index s_enc too.
 struct Timer {
     int n;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -118,8 +119,6 @@ struct mg_ctx {
     u64 gt_entries = 0;
     unsigned long long *d_gen_count = nullptr; // [0] records listed for cover_blocks_kernel, [1] insertion-row cursor / block count of a host-form batch,
                                                // [2] signature k-mers of the lone records, [3] of the others (mg_blocks_stats)
-    hipEvent_t ev_b[4] = {nullptr, nullptr, nullptr, nullptr}; // mg_cover_blocks_device: before / after the preparation, the lone kernels, the enumerating kernel
-    bool blocks_stats_valid = false;
     int blocks_grid[3] = {0, 0, 0};            // persistent grid of cover_blocks_kernel<MODE> (found at first use)
     int use_flat_tier = 1;                     // 0: every general record takes the workgroup kernel (A/B, tests)
     // the records' own copies of their counters (MapSlot::cval / cbf): current for epoch rec_epoch while rec_ok.  Every ABI call
@@ -168,9 +167,10 @@ struct mg_ctx {
     u32 coh_planes = 0, coh_shift = 0, coh_sel = 0;
     u32 *coh_sv_counts = nullptr, *coh_sv_vals = nullptr;
     std::vector<std::unordered_map<std::string, int32_t>> coh_irr;
-    hipEvent_t ev_c[3] = {nullptr, nullptr, nullptr}; // mg_cover_blocks_cohort_device: start, after tier 1, after the planes' tiers 2-3
-    // the merged-batch section: each stats call reports the latest call of its own kinds, hence a timer per kind
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}}; // the encoders' four events, the counting calls' two
+    // each stats call reports the latest call of its own kinds, hence a timer per kind: the encoders' four events, the counting calls' two;
+    // mg_cover_blocks_device: before / after the preparation, the lone kernels, the enumerating kernel; mg_cover_blocks_cohort_device: start,
+    // after tier 1, after the planes' tiers 2-3
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}};
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -315,6 +315,32 @@ int upload(mg_ctx *c, Scratch &s, const void *host, size_t bytes, void **dev)
 {
     TRY(scratch(c, s, bytes ? bytes : 1, dev));
     if (bytes) HIP_TRY(c, hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    return MG_OK;
+}
+
+// A call's timer: begin before its first work goes on the stream (an empty call counts as a call), mark(i) behind part i (the last mark
+// makes the timer valid), read in the stats call: waits for the call, ms[i] = device milliseconds of part i + 1; 0 where no call has run
+int timer_begin(mg_ctx *c, Timer &t)
+{
+    for (int i = 0; i < t.n; ++i)
+        if (!t.ev[i]) HIP_TRY(c, hipEventCreate(&t.ev[i]));
+    t.valid = false;
+    HIP_TRY(c, hipEventRecord(t.ev[0], c->stream));
+    return MG_OK;
+}
+int timer_mark(mg_ctx *c, Timer &t, int i)
+{
+    HIP_TRY(c, hipEventRecord(t.ev[i], c->stream));
+    if (i == t.n - 1) t.valid = true;
+    return MG_OK;
+}
+int timer_read(mg_ctx *c, const Timer &t, float *ms)
+{
+    if (t.valid) HIP_TRY(c, hipEventSynchronize(t.ev[t.n - 1]));
+    for (int i = 0; i + 1 < t.n; ++i) {
+        ms[i] = 0.f;
+        if (t.valid) HIP_TRY(c, hipEventElapsedTime(&ms[i], t.ev[i], t.ev[i + 1]));
+    }
     return MG_OK;
 }
 
@@ -763,8 +789,6 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     if (c->xstream) hipStreamDestroy(c->xstream);
     hipFree(c->d_xmax);
     hipFree(c->s_pack.p);
-    for (auto &e : c->ev_b)
-        if (e) hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) {
         if (c->ev_up[i]) hipEventDestroy(c->ev_up[i]);
         if (c->ev_free[i]) hipEventDestroy(c->ev_free[i]);
@@ -776,8 +800,6 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     hipFree(c->d_kmc_lut);
     hipFree(c->coh_sv_counts);
     hipFree(c->coh_sv_vals);
-    for (auto &e : c->ev_c)
-        if (e) hipEventDestroy(e);
     for (Timer &t : c->tm)
         for (hipEvent_t e : t.ev)
             if (e) hipEventDestroy(e);
@@ -3067,10 +3089,8 @@ MG_EXPORT int mg_cover_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
     if (!d_blk_var_off || !d_n_blocks || !d_cov_out || !d_overflow_out) return fail(c, MG_ERR_ARG, "NULL argument");
     if (!c->bf[0].mode) return fail(c, MG_ERR_STATE, "`bf` not finalised");
     if (!c->map.slots) TRY(map_reserve(c, 0));
-    for (auto &e : c->ev_b)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->blocks_stats_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_b[0], c->stream));
+    Timer &t = c->tm[TM_BLOCKS];
+    TRY(timer_begin(c, t));
     BlocksRun R{};
     TRY(blocks_setup(c, p, (const u32 *)d_blk_var_off, (const u32 *)d_var_block, (const unsigned long long *)d_n_blocks, haploid, &R));
     const u64 n = p->n_vars;
@@ -3087,16 +3107,14 @@ MG_EXPORT int mg_cover_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
                        (const u64 *)c->d_ref2, (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, need_slow,
                        c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_b[1], c->stream));
+    TRY(timer_mark(c, t, 1));
     TRY(blocks_tier2<0>(R, (u32 *)d_cov_out, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3));
-    HIP_TRY(c, hipEventRecord(c->ev_b[2], c->stream));
+    TRY(timer_mark(c, t, 2));
     TRY(blocks_tier3<0>(R, true, (u32 *)d_cov_out, (u8 *)d_overflow_out, nullptr, 0u, c->d_gen_count + 3));
     hipLaunchKernelGGL(fw_finish_kernel, dim3(R.cus * 8), dim3(TPB), 0, c->stream, R.B, (const u32 *)R.gen_list, (const unsigned long long *)c->d_gen_count,
                        (const u8 *)d_overflow_out, (u32 *)d_cov_out);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_b[3], c->stream));
-    c->blocks_stats_valid = true;
-    return MG_OK;
+    return timer_mark(c, t, 3);
 }
 
 // The record loop for every plane of a cohort: tier 1 once over all planes (cohort_lone_kernel), tiers 2 and 3 plane by plane over the
@@ -3114,10 +3132,9 @@ int cover_cohort(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, co
     if (p->n_vars == 0) return MG_OK;
     if (!d_blk_var_off || !d_n_blocks || !d_cov_out || !d_overflow_out) return fail(c, MG_ERR_ARG, "NULL argument");
     if (!c->map.slots) TRY(map_reserve(c, 0));
-    for (auto &e : c->ev_c)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    c->blocks_stats_valid = false;
-    HIP_TRY(c, hipEventRecord(c->ev_c[0], c->stream));
+    Timer &t = c->tm[TM_COHORT];
+    TRY(timer_begin(c, t));
+    c->tm[TM_BLOCKS].valid = false; // (mg_blocks_stats describes the single-sample call only)
     BlocksRun R{};
     TRY(blocks_setup(c, p, (const u32 *)d_blk_var_off, (const u32 *)d_var_block, (const unsigned long long *)d_n_blocks, haploid, &R));
     const u64 n = p->n_vars;
@@ -3142,7 +3159,7 @@ int cover_cohort(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, co
                        (const u32 *)c->d_refbad, (const u8 *)p->pool, (int)c->k, haploid, view(c, MG_BF_ALT), view(c), (u32 *)d_cov_out, c->coh_planes, slots, need_slow,
                        c->iso_call_no, R.gen_list, c->d_gen_count, (unsigned short *)R.B.rec_class, tiles);
     int rc = hipGetLastError() == hipSuccess ? MG_OK : fail(c, MG_ERR_HIP, "cohort_lone_kernel launch failed");
-    if (rc == MG_OK && hipEventRecord(c->ev_c[1], c->stream) != hipSuccess) rc = fail(c, MG_ERR_HIP, "hipEventRecord failed");
+    if (rc == MG_OK) rc = timer_mark(c, t, 1);
     for (u32 s = 0; s < c->coh_planes && rc == MG_OK; ++s) { // the other records, plane by plane, through the single-sample tiers
         c->coh_sel = s;
         u32 *cov = (u32 *)d_cov_out + (u64)s * slots;
@@ -3156,8 +3173,7 @@ int cover_cohort(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, co
     }
     c->coh_sel = sel;
     TRY(rc);
-    HIP_TRY(c, hipEventRecord(c->ev_c[2], c->stream));
-    return MG_OK;
+    return timer_mark(c, t, 2);
 }
 } // namespace
 MG_EXPORT int mg_cover_blocks_cohort_device(mg_ctx *c, const mg_panel_dev *p, const void *d_blk_var_off, const void *d_var_block, const void *d_n_blocks, int haploid,
@@ -3170,10 +3186,8 @@ MG_EXPORT int mg_cohort_stats(mg_ctx *c, float *ms_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out) return MG_ERR_ARG;
-    if (!c->ev_c[2]) return fail(c, MG_ERR_STATE, "no mg_cover_blocks_cohort_device yet");
-    HIP_TRY(c, hipEventSynchronize(c->ev_c[2]));
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_c[i], c->ev_c[i + 1]));
-    return MG_OK;
+    if (!c->tm[TM_COHORT].valid) return fail(c, MG_ERR_STATE, "no mg_cover_blocks_cohort_device yet");
+    return timer_read(c, c->tm[TM_COHORT], ms_out);
 }
 
 // ---- the rows of a merged batch: the sample columns as text (call_text_kernels.h), the site tags (site_tags_kernels.h), the sample columns
@@ -3201,32 +3215,6 @@ int check_cells(mg_ctx *c, const char *who, const mg_cells &x, bool encoder, boo
 int check_rows_out(mg_ctx *c, const void *out, size_t cap, const void *row_off, const uint64_t *bytes_out)
 {
     if (!row_off || !bytes_out || (!out && cap)) return fail(c, MG_ERR_ARG, "NULL argument");
-    return MG_OK;
-}
-
-// A call's timer: begin before its first work goes on the stream (an empty call counts as a call), mark(i) behind part i (the last mark
-// makes the timer valid), read in the stats call: waits for the call, ms[i] = device milliseconds of part i + 1; 0 where no call has run
-int timer_begin(mg_ctx *c, Timer &t)
-{
-    for (int i = 0; i < t.n; ++i)
-        if (!t.ev[i]) HIP_TRY(c, hipEventCreate(&t.ev[i]));
-    t.valid = false;
-    HIP_TRY(c, hipEventRecord(t.ev[0], c->stream));
-    return MG_OK;
-}
-int timer_mark(mg_ctx *c, Timer &t, int i)
-{
-    HIP_TRY(c, hipEventRecord(t.ev[i], c->stream));
-    if (i == t.n - 1) t.valid = true;
-    return MG_OK;
-}
-int timer_read(mg_ctx *c, const Timer &t, float *ms)
-{
-    if (t.valid) HIP_TRY(c, hipEventSynchronize(t.ev[t.n - 1]));
-    for (int i = 0; i + 1 < t.n; ++i) {
-        ms[i] = 0.f;
-        if (t.valid) HIP_TRY(c, hipEventElapsedTime(&ms[i], t.ev[i], t.ev[i + 1]));
-    }
     return MG_OK;
 }
 
@@ -3959,9 +3947,8 @@ MG_EXPORT int mg_blocks_stats(mg_ctx *c, float *ms_out, uint64_t *counts_out)
 {
     const DeviceGuard on_device(c, LAZY);
     if (!c || !ms_out || !counts_out) return MG_ERR_ARG;
-    if (!c->blocks_stats_valid) return fail(c, MG_ERR_STATE, "no mg_cover_blocks_device yet");
-    HIP_TRY(c, hipEventSynchronize(c->ev_b[3]));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&ms_out[i], c->ev_b[i], c->ev_b[i + 1]));
+    if (!c->tm[TM_BLOCKS].valid) return fail(c, MG_ERR_STATE, "no mg_cover_blocks_device yet");
+    TRY(timer_read(c, c->tm[TM_BLOCKS], ms_out));
     unsigned long long h[8];
     HIP_TRY(c, hipMemcpy(h, c->d_gen_count, 64, hipMemcpyDeviceToHost));
     counts_out[0] = h[0];
@@ -3973,158 +3960,106 @@ MG_EXPORT int mg_blocks_stats(mg_ctx *c, float *ms_out, uint64_t *counts_out)
 
 namespace {
 // the host forms' panel: every block its own "sequence" (blk_ref_base / blk_ref_len as the caller gives them)
-int upload_blocks(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
-                  const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                  const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, uint32_t n_samples,
-                  mg_panel_dev *out, void **d_blk_var_off, void **d_var_block, void **d_n_blocks, const uint32_t *sp_off = nullptr,
-                  const uint32_t *sp_sample = nullptr, const uint16_t *sp_gt = nullptr)
+// *out: x on the device (a non-NULL sp_off: the sparse genotypes, and `gt` stays behind); *d_var_block: the block of every record
+int upload_blocks(mg_ctx *c, const mg_blocks_host &x, mg_panel_dev *out, void **d_blk_var_off, void **d_var_block, void **d_n_blocks)
 {
-    if (!blk_ref_base || !blk_ref_len || !blk_var_off || !pos || !ref_size || !min_size || !present || !var_allele_off || !allele_off || !pool || !canon ||
-        (n_samples && !gt && !sp_off) || (sp_off && (!sp_sample || !sp_gt)))
+    if (!x.blk_ref_base || !x.blk_ref_len || !x.blk_var_off || !x.pos || !x.ref_size || !x.min_size || !x.present || !x.var_allele_off || !x.allele_off || !x.pool ||
+        !x.canon || (x.n_samples && !x.gt && !x.sp_off) || (x.sp_off && (!x.sp_sample || !x.sp_gt)))
         return fail(c, MG_ERR_ARG, "NULL argument");
-    if (sp_off)
+    const size_t n_blocks = x.n_blocks, n_vars = x.n_vars;
+    if (x.sp_off)
         for (size_t v = 0; v < n_vars; ++v) {
-            if (sp_off[v + 1] < sp_off[v] || sp_off[v + 1] - sp_off[v] > n_samples) return fail(c, MG_ERR_ARG, "sparse genotype offsets of record %zu", v);
-            for (u32 e = sp_off[v]; e < sp_off[v + 1]; ++e)
-                if (sp_sample[e] >= n_samples || (e > sp_off[v] && sp_sample[e] <= sp_sample[e - 1]))
+            if (x.sp_off[v + 1] < x.sp_off[v] || x.sp_off[v + 1] - x.sp_off[v] > x.n_samples) return fail(c, MG_ERR_ARG, "sparse genotype offsets of record %zu", v);
+            for (u32 e = x.sp_off[v]; e < x.sp_off[v + 1]; ++e)
+                if (x.sp_sample[e] >= x.n_samples || (e > x.sp_off[v] && x.sp_sample[e] <= x.sp_sample[e - 1]))
                     return fail(c, MG_ERR_ARG, "sparse genotypes of record %zu: samples must ascend below n_samples", v);
         }
     if (!c->d_ref) return fail(c, MG_ERR_STATE, "mg_reference_upload first");
-    if (blk_var_off[n_blocks] != n_vars) return fail(c, MG_ERR_ARG, "block offsets do not close");
-    const size_t na = var_allele_off[n_vars];
-    if (allele_off[na] > pool_len) return fail(c, MG_ERR_ARG, "allele offsets exceed the pool");
+    if (x.blk_var_off[n_blocks] != n_vars) return fail(c, MG_ERR_ARG, "block offsets do not close");
+    const size_t na = x.var_allele_off[n_vars];
+    if (x.allele_off[na] > x.pool_len) return fail(c, MG_ERR_ARG, "allele offsets exceed the pool");
     std::vector<u32> var_block(n_vars);
     for (size_t b = 0; b < n_blocks; ++b) {
-        if (blk_ref_base[b] + blk_ref_len[b] > c->ref_len) return fail(c, MG_ERR_ARG, "block %zu lies outside the uploaded reference", b);
-        for (u32 v = blk_var_off[b]; v < blk_var_off[b + 1]; ++v) var_block[v] = (u32)b;
+        if (x.blk_ref_base[b] + x.blk_ref_len[b] > c->ref_len) return fail(c, MG_ERR_ARG, "block %zu lies outside the uploaded reference", b);
+        for (u32 v = x.blk_var_off[b]; v < x.blk_var_off[b + 1]; ++v) var_block[v] = (u32)b;
     }
-    void *d[14];
-    TRY(upload(c, c->s_misc[0], blk_ref_base, 8 * n_blocks, &d[0]));
-    TRY(upload(c, c->s_misc[1], blk_ref_len, 4 * n_blocks, &d[1]));
-    TRY(upload(c, c->s_misc[2], blk_var_off, 4 * (n_blocks + 1), &d[2]));
-    TRY(upload(c, c->s_misc[3], var_block.data(), 4 * n_vars, &d[3]));
-    TRY(upload(c, c->s_misc[4], pos, 4 * n_vars, &d[4]));
-    TRY(upload(c, c->s_misc[5], ref_size, 4 * n_vars, &d[5]));
-    TRY(upload(c, c->s_misc[6], min_size, 4 * n_vars, &d[6]));
-    TRY(upload(c, c->s_misc[7], present, n_vars, &d[7]));
-    TRY(upload(c, c->s_rows, var_allele_off, 4 * (n_vars + 1), &d[8]));
-    TRY(upload(c, c->s_aux, allele_off, 4 * (na + 1), &d[9]));
-    TRY(upload(c, c->s_open[0], pool, pool_len, &d[10]));
-    TRY(upload(c, c->s_open[1], canon, na, &d[11]));
-    void *d_sp[3] = {nullptr, nullptr, nullptr};
-    if (sp_off) {
-        const size_t ne = sp_off[n_vars];
-        TRY(upload(c, c->s_open[2], sp_off, 4 * (n_vars + 1), &d_sp[0]));
-        TRY(upload(c, c->s_hit[0], sp_sample, 4 * ne, &d_sp[1]));
-        TRY(upload(c, c->s_hit[1], sp_gt, 2 * ne, &d_sp[2]));
-        d[12] = nullptr;
+    auto up = [&](Scratch &s, const void *host, size_t bytes, auto *dev) -> int {
+        void *p = nullptr;
+        TRY(upload(c, s, host, bytes, &p));
+        *dev = static_cast<std::remove_reference_t<decltype(*dev)>>(p);
+        return MG_OK;
+    };
+    mg_panel_dev p{};
+    p.n_vars = n_vars;
+    p.n_contigs = (uint32_t)n_blocks;
+    p.n_samples = x.n_samples;
+    p.pool_bytes = x.pool_len;
+    p.sp_default = x.sp_default;
+    const u32 *d_bo;
+    TRY(up(c->s_misc[0], x.blk_ref_base, 8 * n_blocks, &p.contig_base));
+    TRY(up(c->s_misc[1], x.blk_ref_len, 4 * n_blocks, &p.contig_len));
+    TRY(up(c->s_misc[2], x.blk_var_off, 4 * (n_blocks + 1), &d_bo));
+    TRY(up(c->s_misc[3], var_block.data(), 4 * n_vars, &p.contig_id));
+    TRY(up(c->s_misc[4], x.pos, 4 * n_vars, &p.pos));
+    TRY(up(c->s_misc[5], x.ref_size, 4 * n_vars, &p.ref_size));
+    TRY(up(c->s_misc[6], x.min_size, 4 * n_vars, &p.min_size));
+    TRY(up(c->s_misc[7], x.present, n_vars, &p.present));
+    TRY(up(c->s_rows, x.var_allele_off, 4 * (n_vars + 1), &p.var_allele_off));
+    TRY(up(c->s_aux, x.allele_off, 4 * (na + 1), &p.allele_off));
+    TRY(up(c->s_open[0], x.pool, x.pool_len, &p.pool));
+    TRY(up(c->s_open[1], x.canon, na, &p.canon));
+    if (x.sp_off) {
+        const size_t ne = x.sp_off[n_vars];
+        TRY(up(c->s_open[2], x.sp_off, 4 * (n_vars + 1), &p.sp_off));
+        TRY(up(c->s_hit[0], x.sp_sample, 4 * ne, &p.sp_sample));
+        TRY(up(c->s_hit[1], x.sp_gt, 2 * ne, &p.sp_gt));
     } else
-        TRY(upload(c, c->s_open[2], gt, 2 * (size_t)n_vars * n_samples, &d[12]));
+        TRY(up(c->s_open[2], x.gt, 2 * n_vars * x.n_samples, &p.gt));
     if (!c->d_gen_count) HIP_TRY(c, hipMalloc(&c->d_gen_count, 64));
     const unsigned long long nb = n_blocks;
     HIP_TRY(c, hipMemcpyAsync(c->d_gen_count + 1, &nb, 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // (`nb` and `var_block` live on this frame)
-    mg_panel_dev p{};
-    p.n_vars = n_vars;
-    p.n_contigs = (uint32_t)n_blocks;
-    p.contig_base = (const uint64_t *)d[0]; p.contig_len = (const uint32_t *)d[1]; p.contig_id = (const uint32_t *)d[3];
-    p.pos = (const int32_t *)d[4]; p.ref_size = (const uint32_t *)d[5]; p.min_size = (const uint32_t *)d[6]; p.present = (const uint8_t *)d[7];
-    p.var_allele_off = (const uint32_t *)d[8]; p.allele_off = (const uint32_t *)d[9]; p.pool = (const char *)d[10]; p.pool_bytes = pool_len; p.canon = (const uint8_t *)d[11];
-    p.gt = (const uint16_t *)d[12]; p.n_samples = n_samples;
-    p.sp_off = (const uint32_t *)d_sp[0]; p.sp_sample = (const uint32_t *)d_sp[1]; p.sp_gt = (const uint16_t *)d_sp[2];
     *out = p;
-    *d_blk_var_off = d[2];
-    *d_var_block = d[3];
+    *d_blk_var_off = (void *)d_bo;
+    *d_var_block = (void *)p.contig_id;
     *d_n_blocks = c->d_gen_count + 1;
     return MG_OK;
 }
-} // namespace
 
-namespace {
-int cover_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
-                      const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                      const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out,
-                      bool all_planes = false);
-int index_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
-                      const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                      const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint8_t *overflow_out);
-} // namespace
-
-MG_EXPORT int mg_cover_blocks(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len,
-                              const uint32_t *blk_var_off, size_t n_vars, const int32_t *pos, const uint32_t *ref_size,
-                              const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                              const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt,
-                              uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out)
-{
-    return cover_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                             canon, gt, nullptr, nullptr, nullptr, 0, n_samples, haploid, cov_out, overflow_out);
-}
-MG_EXPORT int mg_cover_blocks_sparse(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off,
-                                     size_t n_vars, const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present,
-                                     const uint32_t *var_allele_off, const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                                     const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid,
-                                     uint32_t *cov_out, uint8_t *overflow_out)
-{
-    if (c && !sp_off) return fail(c, MG_ERR_ARG, "NULL argument");
-    return cover_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                             canon, nullptr, sp_off, sp_sample, sp_gt, sp_default, n_samples, haploid, cov_out, overflow_out);
-}
-// the batch goes up once and is covered for every plane of a context in cohort mode: cov_out is [n_planes][slots]
-MG_EXPORT int mg_cover_blocks_cohort(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
-                                     const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                                     const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                                     const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out,
-                                     uint8_t *overflow_out)
-{
-    if (c && !c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cover_blocks_cohort: not in cohort mode (mg_cohort_begin first)");
-    if (c && !gt && !sp_off) return fail(c, MG_ERR_ARG, "NULL argument");
-    return cover_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                             canon, sp_off ? nullptr : gt, sp_off, sp_sample, sp_gt, sp_default, n_samples, haploid, cov_out, overflow_out, true);
-}
-MG_EXPORT int mg_index_blocks_sparse(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off,
-                                     size_t n_vars, const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present,
-                                     const uint32_t *var_allele_off, const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon,
-                                     const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid,
-                                     uint8_t *overflow_out)
-{
-    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
-    if (c && !sp_off) return fail(c, MG_ERR_ARG, "NULL argument");
-    return index_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                             canon, nullptr, sp_off, sp_sample, sp_gt, sp_default, n_samples, haploid, overflow_out);
-}
-
-namespace {
-int cover_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
-                      const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                      const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint32_t *cov_out, uint8_t *overflow_out,
-                      bool all_planes)
+int cover_blocks_host(mg_ctx *c, const mg_blocks_host &x, int haploid, uint32_t *cov_out, uint8_t *overflow_out, bool all_planes)
 {
     const DeviceGuard on_device(c, KEEP);
-    if (!c) return MG_ERR_ARG;
-    if (n_vars == 0) return MG_OK;
+    if (x.n_vars == 0) return MG_OK;
     if (!cov_out || !overflow_out) return fail(c, MG_ERR_ARG, "NULL argument");
     if (!c->bf[0].mode) return fail(c, MG_ERR_STATE, "`bf` not finalised");
     mg_panel_dev p{};
     void *d_bo, *d_vb, *d_nb;
-    TRY(upload_blocks(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                      canon, gt, n_samples, &p, &d_bo, &d_vb, &d_nb, sp_off, sp_sample, sp_gt));
-    p.sp_default = sp_default;
-    const size_t planes = all_planes ? c->coh_planes : 1;
-    const size_t na = (size_t)var_allele_off[n_vars] * planes;
+    TRY(upload_blocks(c, x, &p, &d_bo, &d_vb, &d_nb));
+    const size_t slots = x.var_allele_off[x.n_vars], na = slots * (all_planes ? c->coh_planes : 1);
     void *d_cov, *d_ovf;
     TRY(scratch(c, c->s_out, 4 * na, &d_cov));
-    TRY(scratch(c, c->s_irr, n_vars, &d_ovf));
-    if (all_planes) TRY(cover_cohort(c, &p, d_bo, d_vb, d_nb, haploid, d_cov, d_ovf, var_allele_off[n_vars]));
+    TRY(scratch(c, c->s_irr, x.n_vars, &d_ovf));
+    if (all_planes) TRY(cover_cohort(c, &p, d_bo, d_vb, d_nb, haploid, d_cov, d_ovf, slots));
     else TRY(mg_cover_blocks_device(c, &p, d_bo, d_vb, d_nb, haploid, d_cov, d_ovf));
     HIP_TRY(c, hipMemcpyAsync(cov_out, d_cov, 4 * na, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(overflow_out, d_ovf, n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(overflow_out, d_ovf, x.n_vars, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MG_OK;
 }
 } // namespace
+
+MG_EXPORT int mg_cover_blocks(mg_ctx *c, const mg_blocks_host *x, int haploid, uint32_t *cov_out, uint8_t *overflow_out)
+{
+    if (!c || !x) return MG_ERR_ARG;
+    return cover_blocks_host(c, *x, haploid, cov_out, overflow_out, false);
+}
+// the batch goes up once and is covered for every plane of a context in cohort mode: cov_out is [n_planes][slots]
+MG_EXPORT int mg_cover_blocks_cohort(mg_ctx *c, const mg_blocks_host *x, int haploid, uint32_t *cov_out, uint8_t *overflow_out)
+{
+    if (!c || !x) return MG_ERR_ARG;
+    if (!c->coh_planes) return fail(c, MG_ERR_STATE, "mg_cover_blocks_cohort: not in cohort mode (mg_cohort_begin first)");
+    return cover_blocks_host(c, *x, haploid, cov_out, overflow_out, true);
+}
 
 // index time: VB::extract_kmers + add_kmers_to_bf (main.cpp:349-350, 122-144) for every block of a resident panel.  Synchronises
 // once on eight bytes: the exact map is sized from the counting pass before the insert pass runs.
@@ -4175,40 +4110,30 @@ MG_EXPORT int mg_index_blocks_device(mg_ctx *c, const mg_panel_dev *p, const voi
     return MG_OK;
 }
 
-MG_EXPORT int mg_index_blocks(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len,
-                              const uint32_t *blk_var_off, size_t n_vars, const int32_t *pos, const uint32_t *ref_size,
-                              const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                              const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt,
-                              uint32_t n_samples, int haploid, uint8_t *overflow_out)
-{
-    if (c && c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
-    return index_blocks_host(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                             canon, gt, nullptr, nullptr, nullptr, 0, n_samples, haploid, overflow_out);
-}
 namespace {
-int index_blocks_host(mg_ctx *c, size_t n_blocks, const uint64_t *blk_ref_base, const uint32_t *blk_ref_len, const uint32_t *blk_var_off, size_t n_vars,
-                      const int32_t *pos, const uint32_t *ref_size, const uint32_t *min_size, const uint8_t *present, const uint32_t *var_allele_off,
-                      const uint32_t *allele_off, const char *pool, size_t pool_len, const uint8_t *canon, const uint16_t *gt, const uint32_t *sp_off,
-                      const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t sp_default, uint32_t n_samples, int haploid, uint8_t *overflow_out)
+int index_blocks_host(mg_ctx *c, const mg_blocks_host &x, int haploid, uint8_t *overflow_out)
 {
     const DeviceGuard on_device(c);
-    if (!c) return MG_ERR_ARG;
-    if (n_vars == 0) return MG_OK;
+    if (x.n_vars == 0) return MG_OK;
     if (!overflow_out) return fail(c, MG_ERR_ARG, "NULL argument");
     if (c->bf[MG_BF_ALT].mode) return fail(c, MG_ERR_STATE, "mg_index_blocks after mg_bf_finalize");
     mg_panel_dev p{};
     void *d_bo, *d_vb, *d_nb;
-    TRY(upload_blocks(c, n_blocks, blk_ref_base, blk_ref_len, blk_var_off, n_vars, pos, ref_size, min_size, present, var_allele_off, allele_off, pool, pool_len,
-                      canon, gt, n_samples, &p, &d_bo, &d_vb, &d_nb, sp_off, sp_sample, sp_gt));
-    p.sp_default = sp_default;
+    TRY(upload_blocks(c, x, &p, &d_bo, &d_vb, &d_nb));
     void *d_ovf;
-    TRY(scratch(c, c->s_irr, n_vars, &d_ovf));
-    HIP_TRY(c, hipMemsetAsync(d_ovf, 0, n_vars, c->stream));
+    TRY(scratch(c, c->s_irr, x.n_vars, &d_ovf));
+    HIP_TRY(c, hipMemsetAsync(d_ovf, 0, x.n_vars, c->stream));
     TRY(mg_index_blocks_device(c, &p, d_bo, d_vb, d_nb, haploid, d_ovf));
-    HIP_TRY(c, hipMemcpy(overflow_out, d_ovf, n_vars, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(overflow_out, d_ovf, x.n_vars, hipMemcpyDeviceToHost));
     return MG_OK;
 }
 } // namespace
+MG_EXPORT int mg_index_blocks(mg_ctx *c, const mg_blocks_host *x, int haploid, uint8_t *overflow_out)
+{
+    if (!c || !x) return MG_ERR_ARG;
+    if (c->coh_planes) return fail(c, MG_ERR_STATE, "%s: not while the context is in cohort mode (mg_cohort_end first)", __func__);
+    return index_blocks_host(c, *x, haploid, overflow_out);
+}
 
 // index time: blocks of one variant whose alleles are all shorter than k (nearly every block of a SNP panel), on the device
 MG_EXPORT int mg_index_isolated(mg_ctx *c, size_t n_vars, const uint64_t *pos, const uint32_t *var_allele_off, const uint32_t *allele_off,

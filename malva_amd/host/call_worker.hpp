@@ -34,7 +34,7 @@ struct CallTimes {
     Kind prior;    // --cohort-priors: mg_genotype_cohort
     Kind estimate; // --prior-groups: mg_estimate_priors
     Kind pl;       // --pl: mg_phred_likelihoods
-    size_t gt_bytes = 0; // panel genotypes handed to mg_cover_blocks[_sparse|_cohort]
+    size_t gt_bytes = 0; // panel genotypes handed to mg_cover_blocks[_cohort]
 
     CallTimes &operator+=(const CallTimes &o)
     {
@@ -305,7 +305,7 @@ private:
     // the general blocks' coverages: one call for the whole batch, in the form the panel's genotypes and the pass take; then the blocks it handed back
     void cover_blocks(Device &dev, Batch &gen, CallTimes &times)
     {
-        const size_t n = gen.n(), n_blocks = gen.n_blocks();
+        const size_t n = gen.n();
         // panel genotypes of the batch as one [variant][sample] matrix of a1 | a2 << 7 | phased << 14
         std::vector<uint8_t> overflow(n, 0);
         bool device_ok = o.k <= MG_MAX_PACKED_K && !getenv("MALVA_GENO_HOST_ENUM"); // the variable forces the host enumerator (tests)
@@ -314,26 +314,11 @@ private:
         if (gen.dense_gt) pg.gt = std::move(gen.gt_dense);
         else pg = pack_genotypes(gen.vars, n, n_samples, o.haploid); // (every record of such a batch is kept)
         times.gt_bytes += pg.bytes();
+        const mg_blocks_host x = gen.view(pg, n_samples);
         if (device_ok && planes) // the batch goes up once and is covered for every plane (cov: [planes][na])
-            dev.check(mg_cover_blocks_cohort(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                             gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                             gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sparse ? nullptr : pg.gt.data(),
-                                             pg.sparse ? pg.sp_off.data() : nullptr, pg.sparse ? pg.sp_sample.data() : nullptr,
-                                             pg.sparse ? pg.sp_gt.data() : nullptr, pg.sparse ? pg.sp_default : (uint16_t)0, n_samples, o.haploid, gen.cov.data(),
-                                             overflow.data()),
-                      "mg_cover_blocks_cohort");
-        else if (device_ok && pg.sparse)
-            dev.check(mg_cover_blocks_sparse(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                             gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                             gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.sp_off.data(), pg.sp_sample.data(),
-                                             pg.sp_gt.data(), pg.sp_default, n_samples, o.haploid, gen.cov.data(), overflow.data()),
-                      "mg_cover_blocks_sparse"); // extract_kmers + set_coverages, main.cpp:556-557
+            dev.check(mg_cover_blocks_cohort(dev.ctx, &x, o.haploid, gen.cov.data(), overflow.data()), "mg_cover_blocks_cohort");
         else if (device_ok)
-            dev.check(mg_cover_blocks(dev.ctx, n_blocks, gen.blk_base.data(), gen.blk_len.data(), gen.blk_var_off.data(), n, gen.ipos.data(),
-                                      gen.ref_size.data(), gen.min_size.data(), gen.is_present.data(), gen.var_allele_off.data(),
-                                      gen.allele_off.data(), gen.pool.data(), gen.pool.size(), gen.canon.data(), pg.gt.data(), n_samples, o.haploid,
-                                      gen.cov.data(), overflow.data()),
-                      "mg_cover_blocks"); // extract_kmers + set_coverages, main.cpp:556-557
+            dev.check(mg_cover_blocks(dev.ctx, &x, o.haploid, gen.cov.data(), overflow.data()), "mg_cover_blocks"); // extract_kmers + set_coverages, main.cpp:556-557
         else
             std::fill(overflow.begin(), overflow.end(), 1);
         host_fallback(dev, gen, overflow);

@@ -790,16 +790,10 @@ int index_main(const Options &o)
             const uint32_t n_samples = (uint32_t)vcf.keep.size();
             const PanelGenotypes pg = pack_genotypes(waiting, nv, n_samples, o.haploid);
             std::vector<uint8_t> overflow(nv, 1);
-            if (device_ok && pg.sparse)
-                dev.check(mg_index_blocks_sparse(dev.ctx, nb, ba.blk_base.data(), ba.blk_len.data(), ba.blk_var_off.data(), nv, ba.ipos.data(), ba.ref_size.data(), ba.min_size.data(),
-                                                 ba.is_present.data(), ba.var_allele_off.data(), ba.allele_off.data(), ba.pool.data(), ba.pool.size(), ba.canon.data(), pg.sp_off.data(),
-                                                 pg.sp_sample.data(), pg.sp_gt.data(), pg.sp_default, n_samples, o.haploid, overflow.data()),
-                          "mg_index_blocks_sparse");
-            else if (device_ok)
-                dev.check(mg_index_blocks(dev.ctx, nb, ba.blk_base.data(), ba.blk_len.data(), ba.blk_var_off.data(), nv, ba.ipos.data(), ba.ref_size.data(), ba.min_size.data(),
-                                          ba.is_present.data(), ba.var_allele_off.data(), ba.allele_off.data(), ba.pool.data(), ba.pool.size(), ba.canon.data(), pg.gt.data(),
-                                          n_samples, o.haploid, overflow.data()),
-                          "mg_index_blocks");
+            if (device_ok) {
+                const mg_blocks_host x = ba.view(pg, n_samples);
+                dev.check(mg_index_blocks(dev.ctx, &x, o.haploid, overflow.data()), "mg_index_blocks");
+            }
             for (size_t b = 0; b < nb; ++b)
                 for (uint32_t v = ba.blk_var_off[b]; v < ba.blk_var_off[b + 1]; ++v) redo[b] = redo[b] || overflow[v];
         }

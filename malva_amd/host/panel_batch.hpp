@@ -184,7 +184,7 @@ struct LoneArrays { // inputs of mg_index_isolated and mg_call_isolated: blocks 
         add_alleles(v, [](const std::string &) {});
     }
 };
-struct BlockArrays : LoneArrays { // inputs of mg_index_blocks* / mg_cover_blocks*: the base's three allele arrays (its other three stay empty) and eight more
+struct BlockArrays : LoneArrays { // inputs of mg_index_blocks / mg_cover_blocks*: the base's three allele arrays (its other three stay empty) and eight more
     std::vector<uint64_t> blk_base;
     std::vector<uint32_t> blk_len, blk_var_off{0}, ref_size, min_size;
     std::vector<int32_t> ipos;
@@ -199,6 +199,18 @@ struct BlockArrays : LoneArrays { // inputs of mg_index_blocks* / mg_cover_block
         add_alleles(v, [&](const std::string &al) { canon.push_back((uint8_t)std::min(255, v.allele_index(al))); });
     }
     void close_block() { blk_var_off.push_back((uint32_t)n()); }
+    // the batch as the library's host forms take it, with pg's dense or sparse half for the panel genotypes; points into both, owns nothing
+    mg_blocks_host view(const PanelGenotypes &pg, uint32_t n_samples) const
+    {
+        mg_blocks_host x{};
+        x.n_blocks = n_blocks(), x.blk_ref_base = blk_base.data(), x.blk_ref_len = blk_len.data(), x.blk_var_off = blk_var_off.data();
+        x.n_vars = n(), x.pos = ipos.data(), x.ref_size = ref_size.data(), x.min_size = min_size.data(), x.present = is_present.data();
+        x.var_allele_off = var_allele_off.data(), x.allele_off = allele_off.data(), x.pool = pool.data(), x.pool_len = pool.size(), x.canon = canon.data();
+        x.n_samples = n_samples, x.sp_default = pg.sp_default;
+        if (pg.sparse) x.sp_off = pg.sp_off.data(), x.sp_sample = pg.sp_sample.data(), x.sp_gt = pg.sp_gt.data();
+        else x.gt = pg.gt.data();
+        return x;
+    }
 };
 
 // v.genotypes / v.phasing of a deferred record, for the host enumerator (a block the device handed back, dump-kmers' cousin paths)

@@ -81,40 +81,26 @@ int mg_call_isolated(mg_ctx *c, size_t n, const uint64_t *pos, const uint32_t *v
     for (size_t i = 0; i < ng; ++i) probs[i] = 0.5;
     return MG_OK;
 }
-static int cover(mg_ctx *c, const char *name, size_t n_blocks, const uint32_t *blk_var_off, size_t n, const uint32_t *vao, bool dense, bool sparse, uint32_t n_samples,
-                 uint32_t planes, uint32_t *cov_out, uint8_t *overflow)
+static int cover(mg_ctx *c, const char *name, const mg_blocks_host &x, uint32_t planes, uint32_t *cov_out, uint8_t *overflow)
 {
-    const size_t na = vao[n];
-    touch(blk_var_off, n_blocks + 1);
+    const size_t n = x.n_vars, na = x.var_allele_off[n]; // every member over its documented extent (mg_blocks_host)
+    touch(x.blk_ref_base, x.n_blocks), touch(x.blk_ref_len, x.n_blocks), touch(x.blk_var_off, x.n_blocks + 1);
+    touch(x.pos, n), touch(x.ref_size, n), touch(x.min_size, n), touch(x.present, n), touch(x.var_allele_off, n + 1);
+    touch(x.allele_off, na + 1), touch(x.pool, x.pool_len), touch(x.canon, na);
+    if (x.sp_off) touch(x.sp_off, n + 1), touch(x.sp_sample, x.sp_off[n]), touch(x.sp_gt, x.sp_off[n]);
+    else touch(x.gt, n * x.n_samples);
     c->cov0 = cov_out, c->g10 = nullptr, c->probs0 = nullptr;
-    say(c, "%s blocks=%zu n=%zu samples=%u dense=%d sparse=%d", name, n_blocks, n, n_samples, (int)dense, (int)sparse);
+    say(c, "%s blocks=%zu n=%zu samples=%u dense=%d sparse=%d", name, x.n_blocks, n, x.n_samples, (int)(x.gt != nullptr), (int)(x.sp_off != nullptr));
     for (size_t pl = 0; pl < planes; ++pl)
         for (size_t i = 0; i < na; ++i) cov_out[pl * na + i] = 100 * ((uint32_t)pl + 1) + (uint32_t)i;
     for (size_t i = 0; i < n; ++i) overflow[i] = 0;
     for (size_t f : c->flagged) overflow[f] = 1;
     return MG_OK;
 }
-int mg_cover_blocks(mg_ctx *c, size_t n_blocks, const uint64_t *, const uint32_t *, const uint32_t *blk_var_off, size_t n, const int32_t *, const uint32_t *, const uint32_t *,
-                    const uint8_t *, const uint32_t *vao, const uint32_t *, const char *, size_t, const uint8_t *, const uint16_t *gt, uint32_t n_samples, int, uint32_t *cov_out,
-                    uint8_t *overflow)
+int mg_cover_blocks(mg_ctx *c, const mg_blocks_host *x, int, uint32_t *cov_out, uint8_t *overflow) { return cover(c, "mg_cover_blocks", *x, 1, cov_out, overflow); }
+int mg_cover_blocks_cohort(mg_ctx *c, const mg_blocks_host *x, int, uint32_t *cov_out, uint8_t *overflow)
 {
-    touch(gt, n * n_samples);
-    return cover(c, "mg_cover_blocks", n_blocks, blk_var_off, n, vao, gt != nullptr, false, n_samples, 1, cov_out, overflow);
-}
-int mg_cover_blocks_sparse(mg_ctx *c, size_t n_blocks, const uint64_t *, const uint32_t *, const uint32_t *blk_var_off, size_t n, const int32_t *, const uint32_t *,
-                           const uint32_t *, const uint8_t *, const uint32_t *vao, const uint32_t *, const char *, size_t, const uint8_t *, const uint32_t *sp_off,
-                           const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t, uint32_t n_samples, int, uint32_t *cov_out, uint8_t *overflow)
-{
-    touch(sp_off, n + 1), touch(sp_sample, sp_off[n]), touch(sp_gt, sp_off[n]);
-    return cover(c, "mg_cover_blocks_sparse", n_blocks, blk_var_off, n, vao, false, true, n_samples, 1, cov_out, overflow);
-}
-int mg_cover_blocks_cohort(mg_ctx *c, size_t n_blocks, const uint64_t *, const uint32_t *, const uint32_t *blk_var_off, size_t n, const int32_t *, const uint32_t *,
-                           const uint32_t *, const uint8_t *, const uint32_t *vao, const uint32_t *, const char *, size_t, const uint8_t *, const uint16_t *gt,
-                           const uint32_t *sp_off, const uint32_t *sp_sample, const uint16_t *sp_gt, uint16_t, uint32_t n_samples, int, uint32_t *cov_out, uint8_t *overflow)
-{
-    if (gt) touch(gt, n * n_samples);
-    if (sp_off) touch(sp_off, n + 1), touch(sp_sample, sp_off[n]), touch(sp_gt, sp_off[n]);
-    return cover(c, "mg_cover_blocks_cohort", n_blocks, blk_var_off, n, vao, gt != nullptr, sp_off != nullptr, n_samples, c->n_planes, cov_out, overflow);
+    return cover(c, "mg_cover_blocks_cohort", *x, c->n_planes, cov_out, overflow);
 }
 int mg_lookup_cover(mg_ctx *c, const char *rows, size_t stride, size_t n_rows, const uint8_t *is_ref, const uint64_t *sig_kmer_off, size_t n_sigs, const uint64_t *allele_sig_off,
                     size_t n_alleles, uint32_t *cov_out)
@@ -527,7 +513,7 @@ static void check_one_sample()
         Scene s; // 65 samples: the sparse form -- three offsets and every sample of both records (0|1 is not the default word)
         s.per_sample(1);
         s.run(0, 65, mixed_batch(65, false));
-        CHECK(s.ctx().log == Log({"mg_call_isolated n=2 cov+0 g1+0 probs+-1", "mg_cover_blocks_sparse blocks=1 n=2 samples=65 dense=0 sparse=1", "mg_genotype n=2 cov+0 g1+0 probs+-1 id=0"}));
+        CHECK(s.ctx().log == Log({"mg_call_isolated n=2 cov+0 g1+0 probs+-1", "mg_cover_blocks blocks=1 n=2 samples=65 dense=0 sparse=1", "mg_genotype n=2 cov+0 g1+0 probs+-1 id=0"}));
         CHECK(s.total.gt_bytes == 4 * 3 + 6 * 130);
     }
 }
