@@ -652,6 +652,50 @@ int mg_sample_counts_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int h
                             void *d_counts);
 int mg_sample_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- the per-record table of a multi-sample call set --------------------------------
+ * For every record and allele the genotype counts over the planes, and for every (record, ALT) the exact test of Hardy-Weinberg
+ * proportions that follows from them.  There is no reference call to cite: the reference genotypes one individual per run.
+ * mg_site_geno_counts: gt1 / gt2 / gq, n_planes (1..64), use_mask / min_gq, var_allele_off and accumulate exactly as for
+ * mg_site_counts: [n_planes][n_vars] int32, plane-major; gt2 is not read in haploid mode and may be NULL, gq not unless use_mask.
+ * With A = var_allele_off[v + 1] - var_allele_off[v], a cell of record v is USABLE when it is not masked (masked: use_mask != 0
+ * and gq < min_gq) and every allele index the mode reads lies in [0, A).  n_out[v] receives the number of usable cells.  Record v
+ * owns the slots [var_allele_off[v], var_allele_off[v + 1]) of het_out and of hom_out, one per allele, REF first: a usable diploid
+ * cell with gt1 == gt2 adds 1 to hom[slot gt1]; one with gt1 != gt2 adds 1 to het[slot gt1] and 1 to het[slot gt2]; a usable
+ * haploid cell adds 1 to hom[slot gt1].  So per diploid record the sum over its slots of het + 2 * hom is 2 * n_out[v].  This is
+ * NOT mg_site_counts' rule, which counts the valid index of a cell whose other index is invalid: here such a cell counts nowhere
+ * (the genotyper makes no such cells).  accumulate != 0 adds to what the three arrays hold (the groups of a cohort larger than
+ * 64 are summed this way); accumulate == 0 overwrites every slot of every record and every n_out.  Nothing is written outside a
+ * record's slots.  n_vars == 0 is legal.  n_planes out of range, a NULL gt1 / var_allele_off / n_out with n_vars > 0, a NULL gt2 in
+ * diploid mode, a NULL gq under the mask, a NULL het_out or hom_out with slots: MG_ERR_ARG.  The host form synchronises; the
+ * device form (every array a device pointer) is asynchronous on the context's stream.
+ * mg_hwe_exact: item i is one (record, ALT): n[i] usable diploid cells, het[i] of them with exactly one copy of the allele,
+ * hom[i] with two.  hwe_out[i] is the two-sided exact P value (the sum of the probabilities, given the allele count, of all
+ * heterozygote counts no likelier than the observed one), exc_het_out[i] the one-sided one for an excess of heterozygotes (the
+ * counts at and above the observed one).  Both are pure functions of (n, het, hom).  In 64-bit unsigned integers, `/` the integer
+ * division:  na = het + 2 * hom, nb = 2 * n - na, r = min(na, nb);  mid = r * (2 * n - r) / (2 * n), 0 when n == 0, raised by one
+ * if its parity differs from r's;  hr = (r - mid) / 2, hc = n - mid - hr.  Unnormalised terms in IEEE doubles:  q(mid) = 1.0;
+ * downward, while h > 1:  q(h - 2) = q(h) * ( double(h * (h - 1)) / double(4 * (hr + 1) * (hc + 1)) ), then hr++, hc++;  upward,
+ * restarting from mid, while h <= r - 2:  q(h + 2) = q(h) * ( double(4 * hr * hc) / double((h + 2) * (h + 1)) ), then hr--, hc--.
+ * Every ratio is formed first and then multiplied.  q_obs = q(het).  Three sums are added in visiting order (mid, downward,
+ * upward): S all terms, L the terms with q <= q_obs, G the terms with h >= het;  hwe = min(L / S, 1.0), exc_het = min(G / S, 1.0).
+ * Every step is one correctly rounded operation, so the results are the same bits on every device and in every restatement
+ * that keeps the order.  n == 0 gives 1.0 and 1.0.  An item with het + hom > n, or with n > MG_HWE_MAX_N (a bound on one thread's
+ * walk, 2^23 steps, far below where the 64-bit products above would wrap), gets a quiet NaN in both outputs.  n_items == 0 is legal; a
+ * NULL array with n_items > 0: MG_ERR_ARG.  One thread walks one item, r / 2 steps.  The host form synchronises; the device form
+ * is asynchronous on the context's stream.
+ * mg_hwe_stats (waits): ms_out[2], device milliseconds of the most recent mg_site_geno_counts* and of the most recent
+ * mg_hwe_exact*; 0 for a kind not called yet, MG_ERR_STATE when neither was.
+ * The calls keep their device copies of their tables and their events apart from the encoders', the site tags', the pair
+ * table's and the sample table's: a call of one kind between two of another changes nothing in either. */
+#define MG_HWE_MAX_N (1u << 24)
+int mg_site_geno_counts(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                        int32_t min_gq, const uint32_t *var_allele_off, int accumulate, uint32_t *n_out, uint32_t *het_out, uint32_t *hom_out);
+int mg_site_geno_counts_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                               int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_n_out, void *d_het_out, void *d_hom_out);
+int mg_hwe_exact(mg_ctx *ctx, size_t n_items, const uint32_t *n, const uint32_t *het, const uint32_t *hom, double *hwe_out, double *exc_het_out);
+int mg_hwe_exact_device(mg_ctx *ctx, size_t n_items, const void *d_n, const void *d_het, const void *d_hom, void *d_hwe_out, void *d_exc_het_out);
+int mg_hwe_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- allele priors re-estimated from the cohort -------------------------------------
  * mg_genotype_cohort: the batch's allele frequencies are re-estimated from all of its planes (a few EM steps from the panel's
  * priors, anchored to them), then every cell is genotyped under the result.  The reference genotypes one individual and has no

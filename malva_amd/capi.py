@@ -127,6 +127,11 @@ def lib():
         "mg_sample_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, it, vp],
         "mg_sample_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp, vp, vp, it, vp],
         "mg_sample_stats": [vp, vp],
+        "mg_site_geno_counts": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp, vp],
+        "mg_site_geno_counts_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, it, vp, vp, vp],
+        "mg_hwe_exact": [vp, sz, vp, vp, vp, vp, vp],
+        "mg_hwe_exact_device": [vp, sz, vp, vp, vp, vp, vp],
+        "mg_hwe_stats": [vp, vp],
         "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_cohort_prior_stats": [vp, vp],
@@ -202,7 +207,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_calls", "mg_format_calls_device", "mg_format_stats",
             "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
-            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats",
+            "mg_site_geno_counts", "mg_site_geno_counts_device", "mg_hwe_exact", "mg_hwe_exact_device", "mg_hwe_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -916,6 +922,52 @@ class Context:
         ms = (C.c_float * 1)()
         self._ck(self._L.mg_sample_stats(self.h, ms))
         return float(ms[0])
+
+    # the per-record table of a multi-sample call set
+    def site_geno_counts(self, gt1, gt2, gq, haploid, var_allele_off, min_gq=None, n=None, het=None, hom=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 (gt2 may be None in haploid mode) -> (n [n_vars], het [slots], hom [slots]) uint32: per
+        record the usable cells, per allele slot the heterozygous and homozygous ones among them (mg_site_geno_counts in
+        include/malva_hip.h).  min_gq: cells whose gq is below it are masked.  n / het / hom given: the counts are added to them (in place)."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q, vo = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32), a(var_allele_off, np.uint32)
+        planes, nv = g1.shape
+        slots = int(vo[nv]) if nv else 0
+        acc = n is not None
+        assert acc == (het is not None) == (hom is not None)
+        if acc:
+            for x, size in ((n, nv), (het, slots), (hom, slots)):
+                assert x.dtype == np.uint32 and x.flags.c_contiguous and x.size == size
+        else:
+            n, het, hom = np.zeros(nv, dtype=np.uint32), np.zeros(slots, dtype=np.uint32), np.zeros(slots, dtype=np.uint32)
+        self._ck(self._L.mg_site_geno_counts(self.h, nv, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(vo), int(acc),
+                                             _p(n), _p(het), _p(hom)))
+        return n, het, hom
+
+    def site_geno_counts_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_var_allele_off, d_n, d_het, d_hom, min_gq=None, accumulate=False):
+        """the same from device pointers into device buffers, asynchronous on the context's stream"""
+        v = C.c_void_p
+        self._ck(self._L.mg_site_geno_counts_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
+                                                    v(d_var_allele_off), int(accumulate), v(d_n), v(d_het), v(d_hom)))
+
+    def hwe_exact(self, n, het, hom):
+        """n / het / hom: [items] uint32 -> (hwe, exc_het) float64 [items]: the exact test of Hardy-Weinberg proportions per item, two-sided
+        and for an excess of heterozygotes (mg_hwe_exact in include/malva_hip.h); NaN where het + hom > n"""
+        n, het, hom = (np.ascontiguousarray(x, dtype=np.uint32) for x in (n, het, hom))
+        assert n.ndim == 1 and n.shape == het.shape == hom.shape
+        hwe, exc = np.zeros(n.size, dtype=np.float64), np.zeros(n.size, dtype=np.float64)
+        self._ck(self._L.mg_hwe_exact(self.h, n.size, _p(n), _p(het), _p(hom), _p(hwe), _p(exc)))
+        return hwe, exc
+
+    def hwe_exact_device(self, n_items, d_n, d_het, d_hom, d_hwe, d_exc_het):
+        """the same from device pointers into device buffers, asynchronous on the context's stream"""
+        v = C.c_void_p
+        self._ck(self._L.mg_hwe_exact_device(self.h, n_items, v(d_n), v(d_het), v(d_hom), v(d_hwe), v(d_exc_het)))
+
+    def hwe_stats(self):
+        """-> device ms of the most recent site_geno_counts and of the most recent hwe_exact"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.mg_hwe_stats(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     # allele priors re-estimated from the planes of a batch, and the cells genotyped under them
     def genotype_cohort(self, cov, freq, var_allele_off, error_rate, max_cov, haploid, iters=5, weight=1.0, want_probs=False):

@@ -42,6 +42,7 @@ constexpr int TPB = 256;
 #include "site_tags_kernels.h"
 #include "pair_kernels.h"
 #include "sample_kernels.h"
+#include "site_geno_kernels.h"
 #include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
 #include "pl_kernels.h"
@@ -89,7 +90,7 @@ struct Timer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_GENO, TM_HWE, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device, mg_site_geno_counts*, mg_hwe_exact*
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -103,6 +104,7 @@ enum {
     ST_OUT, ST_ROW_OFF,                                                                                    // an encoder's rows (stage_rows)
     ST_FREQ, ST_FREQ_OUT, ST_NINF,                                                                         // mg_genotype_cohort's priors
     ST_PL,                                                                                                 // mg_phred_likelihoods' result, the *_pl encoders' input
+    ST_SG_N, ST_SG_HET, ST_SG_HOM, ST_HWE, ST_EXC_HET,                                                     // mg_site_geno_counts' tables, mg_hwe_exact's items and results
     ST_COUNT
 };
 
@@ -170,7 +172,7 @@ struct mg_ctx {
     // each stats call reports the latest call of its own kinds, hence a timer per kind: the encoders' four events, the counting calls' two;
     // mg_cover_blocks_device: before / after the preparation, the lone kernels, the enumerating kernel; mg_cover_blocks_cohort_device: start,
     // after tier 1, after the planes' tiers 2-3
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}};
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}, {2}, {2}};
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -3653,6 +3655,103 @@ MG_EXPORT int mg_sample_stats(mg_ctx *c, float *ms_out)
     ms_out[0] = 0.f; // (also where it fails)
     if (!c->tm[TM_SAMPLE].valid) return fail(c, MG_ERR_STATE, "no mg_sample_counts yet");
     return timer_read(c, c->tm[TM_SAMPLE], ms_out);
+}
+
+// ---- the per-record table of a multi-sample call set (site_geno_kernels.h) ---------------------------------------------------------------
+namespace {
+int site_geno_counts_device(mg_ctx *c, const mg_cells &x, int accumulate, void *d_n, void *d_het, void *d_hom)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cells(c, "mg_site_geno_counts", x, false, x.use_mask));
+    if (x.n_vars && (!x.var_allele_off || !d_n)) return fail(c, MG_ERR_ARG, "NULL argument"); // (d_het and d_hom may be: records without slots)
+    TRY(timer_begin(c, c->tm[TM_GENO]));
+    if (x.n_vars) {
+        const SiteArgs a{(u64)x.n_vars, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, x.use_mask, x.min_gq,
+                         (const u32 *)x.var_allele_off, accumulate};
+        hipLaunchKernelGGL(site_geno_kernel, fmt_len_grid(x.n_vars), dim3(FMT_TPB), 0, c->stream, a, (u32 *)d_n, (u32 *)d_het, (u32 *)d_hom);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_GENO], 1);
+}
+} // namespace
+MG_EXPORT int mg_site_geno_counts_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                         int32_t min_gq, const void *d_var_allele_off, int accumulate, void *d_n_out, void *d_het_out, void *d_hom_out)
+{
+    return site_geno_counts_device(c, mg_cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, nullptr, d_var_allele_off}, accumulate, d_n_out, d_het_out,
+                                   d_hom_out);
+}
+
+MG_EXPORT int mg_site_geno_counts(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                  int32_t min_gq, const uint32_t *var_allele_off, int accumulate, uint32_t *n_out, uint32_t *het_out, uint32_t *hom_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    const mg_cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, nullptr, var_allele_off};
+    TRY(check_cells(c, "mg_site_geno_counts", x, false, use_mask));
+    if (n_vars && !var_allele_off) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t slots = n_vars ? var_allele_off[n_vars] : 0;
+    if (n_vars && (!n_out || (slots && (!het_out || !hom_out)))) return fail(c, MG_ERR_ARG, "NULL argument");
+    mg_cells d;
+    void *d_n, *d_het, *d_hom;
+    TRY(stage_cells(c, x, &d, false, false));
+    TRY(scratch(c, c->stage[ST_SG_N], n_vars ? 4 * n_vars : 1, &d_n));
+    TRY(scratch(c, c->stage[ST_SG_HET], slots ? 4 * slots : 1, &d_het));
+    TRY(scratch(c, c->stage[ST_SG_HOM], slots ? 4 * slots : 1, &d_hom));
+    if (accumulate && n_vars) HIP_TRY(c, hipMemcpyAsync(d_n, n_out, 4 * n_vars, hipMemcpyHostToDevice, c->stream));
+    if (accumulate && slots) HIP_TRY(c, hipMemcpyAsync(d_het, het_out, 4 * slots, hipMemcpyHostToDevice, c->stream));
+    if (accumulate && slots) HIP_TRY(c, hipMemcpyAsync(d_hom, hom_out, 4 * slots, hipMemcpyHostToDevice, c->stream));
+    TRY(site_geno_counts_device(c, d, accumulate, d_n, d_het, d_hom));
+    if (n_vars) HIP_TRY(c, hipMemcpyAsync(n_out, d_n, 4 * n_vars, hipMemcpyDeviceToHost, c->stream));
+    if (slots) HIP_TRY(c, hipMemcpyAsync(het_out, d_het, 4 * slots, hipMemcpyDeviceToHost, c->stream));
+    if (slots) HIP_TRY(c, hipMemcpyAsync(hom_out, d_hom, 4 * slots, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_hwe_exact_device(mg_ctx *c, size_t n_items, const void *d_n, const void *d_het, const void *d_hom, void *d_hwe_out, void *d_exc_het_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    if (n_items && (!d_n || !d_het || !d_hom || !d_hwe_out || !d_exc_het_out)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_items >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_hwe_exact: more than 2^32 - 1 items in one call");
+    TRY(timer_begin(c, c->tm[TM_HWE]));
+    if (n_items) {
+        hipLaunchKernelGGL(hwe_exact_kernel, dim3((unsigned)((n_items + HWE_TPB - 1) / HWE_TPB)), dim3(HWE_TPB), 0, c->stream, (u64)n_items, (const u32 *)d_n,
+                           (const u32 *)d_het, (const u32 *)d_hom, (double *)d_hwe_out, (double *)d_exc_het_out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_HWE], 1);
+}
+
+MG_EXPORT int mg_hwe_exact(mg_ctx *c, size_t n_items, const uint32_t *n, const uint32_t *het, const uint32_t *hom, double *hwe_out, double *exc_het_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n_items && (!n || !het || !hom || !hwe_out || !exc_het_out)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_items >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_hwe_exact: more than 2^32 - 1 items in one call");
+    void *d_n, *d_het, *d_hom, *d_hwe, *d_exc;
+    TRY(upload(c, c->stage[ST_SG_N], n, 4 * n_items, &d_n));
+    TRY(upload(c, c->stage[ST_SG_HET], het, 4 * n_items, &d_het));
+    TRY(upload(c, c->stage[ST_SG_HOM], hom, 4 * n_items, &d_hom));
+    TRY(scratch(c, c->stage[ST_HWE], n_items ? 8 * n_items : 1, &d_hwe));
+    TRY(scratch(c, c->stage[ST_EXC_HET], n_items ? 8 * n_items : 1, &d_exc));
+    TRY(mg_hwe_exact_device(c, n_items, d_n, d_het, d_hom, d_hwe, d_exc));
+    if (n_items) HIP_TRY(c, hipMemcpyAsync(hwe_out, d_hwe, 8 * n_items, hipMemcpyDeviceToHost, c->stream));
+    if (n_items) HIP_TRY(c, hipMemcpyAsync(exc_het_out, d_exc, 8 * n_items, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds (waits for them): ms_out[0] the most recent mg_site_geno_counts*, [1] the most recent mg_hwe_exact*; 0 where there was none
+MG_EXPORT int mg_hwe_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = ms_out[1] = 0.f; // (also where it fails)
+    if (!c->tm[TM_GENO].valid && !c->tm[TM_HWE].valid) return fail(c, MG_ERR_STATE, "no mg_site_geno_counts or mg_hwe_exact yet");
+    TRY(timer_read(c, c->tm[TM_GENO], &ms_out[0]));
+    return timer_read(c, c->tm[TM_HWE], &ms_out[1]);
 }
 
 // ---- allele priors re-estimated from the planes of a batch (cohort_prior_kernels.h) ------------------------------------------------------

@@ -34,12 +34,14 @@ struct CallTimes {
     Kind prior;    // --cohort-priors: mg_genotype_cohort
     Kind estimate; // --prior-groups: mg_estimate_priors
     Kind pl;       // --pl: mg_phred_likelihoods
+    Kind geno;     // --site-stats: [0] mg_site_geno_counts, [1] mg_hwe_exact
     size_t gt_bytes = 0; // panel genotypes handed to mg_cover_blocks[_cohort]
 
     CallTimes &operator+=(const CallTimes &o)
     {
         Kind CallTimes::*const kinds[] = {&CallTimes::format, &CallTimes::bcf,   &CallTimes::site,    &CallTimes::pairs,
-                                          &CallTimes::sample, &CallTimes::prior, &CallTimes::estimate, &CallTimes::pl};
+                                          &CallTimes::sample, &CallTimes::prior, &CallTimes::estimate, &CallTimes::pl,
+                                          &CallTimes::geno};
         for (auto k : kinds)
             for (int i = 0; i < 3; ++i) (this->*k).ms[i] += (o.*k).ms[i], (this->*k).calls[i] += (o.*k).calls[i];
         gt_bytes += o.gt_bytes;
@@ -51,6 +53,7 @@ struct CallTimes {
         if (!g_timers.on) return;
         if (pairs.calls[1]) g_timers.add("pairs: pack and count kernels (device)", (pairs.ms[0] + pairs.ms[1]) / 1000.0);
         if (sample.calls[0]) g_timers.add("sample table: count kernel (device)", sample.ms[0] / 1000.0);
+        if (geno.calls[0]) g_timers.add("site table: count and test kernels (device)", (geno.ms[0] + geno.ms[1]) / 1000.0);
         if (prior.calls[0]) g_timers.add("cohort priors: kernel (device)", prior.ms[0] / 1000.0);
         if (estimate.calls[0]) g_timers.add("cohort priors: estimate kernel (device)", estimate.ms[0] / 1000.0);
         if (pl.calls[0]) g_timers.add("merged: likelihood kernel (device)", pl.ms[0] / 1000.0);
@@ -71,6 +74,11 @@ struct CallTimes {
         }
         if (sample.calls[0]) {
             snprintf(line, sizeof line, "[malva-geno] sample-stats: %zu mg_sample_counts, device ms per call: count %.3f\n", sample.calls[0], sample.ms[0] / sample.calls[0]);
+            out += line;
+        }
+        if (geno.calls[0]) {
+            snprintf(line, sizeof line, "[malva-geno] site-stats: %zu mg_site_geno_counts, %zu mg_hwe_exact, device ms per call: count %.3f test %.3f\n", geno.calls[0],
+                     geno.calls[1], geno.ms[0] / geno.calls[0], geno.calls[1] ? geno.ms[1] / geno.calls[1] : 0.0);
             out += line;
         }
         if (prior.calls[0]) {
@@ -131,6 +139,12 @@ struct PassOut {
     // --sample-stats: the group's [planes][MG_SAMPLE_SLOTS] sums; every batch's cells are added while the batch is in hand (mg_sample_counts, accumulate)
     // (this table and pairs->counts are summed by the device call itself, batch after batch: the cohort's passes run on one device)
     uint64_t *sample_table = nullptr;
+    // --site-stats: the records' genotype counts over the group's planes are made while the batch is in hand (mg_site_geno_counts).  The group is the
+    // cohort: the ALTs are tested at once (mg_hwe_exact) and the table's lines go here.  site_stats_stream: the counts go here instead (put_site_geno,
+    // with the records' columns when site_stats_cols) for the pass behind the last group to sum (site_stats_groups)
+    PartFile *site_stats = nullptr;
+    bool site_stats_stream = false, site_stats_cols = false;
+    size_t site_stats_samples = 0; // the cohort's size
     // --prior-groups, a cohort in several groups (host/cohort_priors.hpp).  prior_cov: the coverage pass -- the batches' coverages go here
     // (put_cov_batch; the first group's with the records' offsets and panel priors), and the pass makes no calls and nothing else.
     // prior_in: the output pass -- the batches' coverages and the cohort's frequencies come from here instead of the counters, and the
@@ -141,7 +155,7 @@ struct PassOut {
 };
 struct BatchText { // the text of one batch, as its worker hands it over
     std::vector<std::string> per_sample;
-    std::string merged, site_counts, pack, priors, prior_cov; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
+    std::string merged, site_counts, pack, priors, prior_cov, site_stats; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
     CallTimes times; // of this batch's calls alone
 };
 
@@ -201,6 +215,7 @@ public:
         for (PartFile &f : to.per_sample) fflush(f.f);
         if (to.merged) fflush(to.merged->f);
         if (to.site_counts) fflush(to.site_counts->f);
+        if (to.site_stats) fflush(to.site_stats->f);
     }
 
 private:
@@ -213,6 +228,11 @@ private:
         std::vector<char> row_text[2], info_text[2];
         std::vector<uint64_t> row_off[2], info_off[2];
         std::vector<uint32_t> site_ac[2], site_ns[2];
+    };
+    struct SiteGeno { // --site-stats: the same two batches' counts, and (one group) the tests of their ALTs: record v's start at item_off[v]
+        std::vector<uint32_t> n[2], het[2], hom[2];
+        std::vector<size_t> item_off[2];
+        std::vector<double> hwe[2], exc[2];
     };
 
     std::vector<Device> &devs;
@@ -242,6 +262,7 @@ private:
             if (to.pairs && to.pairs->pack_out) to.pairs->pack_out->write(text.pack, "cannot write the pair table's packed calls");
             priors_file.write(text.priors);
             if (to.prior_cov) to.prior_cov->write(text.prior_cov, "cannot write the coverages for the cohort's priors");
+            if (to.site_stats) to.site_stats->write(text.site_stats, to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
         }
     }
 
@@ -252,6 +273,7 @@ private:
         BatchText text;
         text.per_sample.resize(to.per_sample.size());
         MergedRows rows;
+        SiteGeno geno;
         {
             Timed t_dev("worker: device calls");
             std::lock_guard<std::mutex> device_lock(dev.mu); // (the parsing thread cuts blocks on device 0 meanwhile)
@@ -275,8 +297,9 @@ private:
             if (to.merged) merged_rows(dev, job, rows, text.times);
             if (to.pairs) pair_table(dev, job, text);
             if (to.sample_table) sample_table(dev, job, text.times);
+            if (to.site_stats) site_table(dev, job, geno, text.times);
         } // the records' text needs no device
-        records_text(job, rows, text);
+        records_text(job, rows, geno, text);
         return text;
     }
 
@@ -493,7 +516,42 @@ private:
         }
     }
 
-    void records_text(const Job &job, const MergedRows &rows, BatchText &text)
+    void site_table(Device &dev, Job &job, SiteGeno &g, CallTimes &times)
+    {
+        Timed t_site("worker: site table (mg_site_geno_counts, mg_hwe_exact)");
+        std::vector<uint32_t> item_n, item_het, item_hom;
+        for (int w = 0; w < 2; ++w) {
+            Batch &b = w ? job.gen : job.iso;
+            const size_t bn = b.n();
+            if (!bn) continue;
+            g.n[w].resize(bn);
+            g.het[w].resize(b.var_allele_off.back());
+            g.hom[w].resize(b.var_allele_off.back());
+            dev.check(mg_site_geno_counts(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.var_allele_off.data(), 0,
+                                          g.n[w].data(), g.het[w].data(), g.hom[w].data()),
+                      "mg_site_geno_counts");
+            float ms[2] = {0, 0};
+            dev.check(mg_hwe_stats(dev.ctx, ms), "mg_hwe_stats");
+            times.geno.add(ms, 1);
+            if (to.site_stats_stream || o.haploid) continue; // (the pass behind the last group tests the sums; a haploid table has no test)
+            item_n.clear(), item_het.clear(), item_hom.clear();
+            g.item_off[w].resize(bn);
+            for (size_t v = 0; v < bn; ++v) {
+                g.item_off[w][v] = item_n.size();
+                site_stats_items(b.var_allele_off[v + 1] - b.var_allele_off[v], g.n[w][v], &g.het[w][b.var_allele_off[v]], &g.hom[w][b.var_allele_off[v]], item_n, item_het,
+                                 item_hom);
+            }
+            g.hwe[w].resize(item_n.size());
+            g.exc[w].resize(item_n.size());
+            if (item_n.empty()) continue;
+            dev.check(mg_hwe_exact(dev.ctx, item_n.size(), item_n.data(), item_het.data(), item_hom.data(), g.hwe[w].data(), g.exc[w].data()), "mg_hwe_exact");
+            dev.check(mg_hwe_stats(dev.ctx, ms), "mg_hwe_stats");
+            times.geno.ms[1] += ms[1];
+            ++times.geno.calls[1];
+        }
+    }
+
+    void records_text(const Job &job, const MergedRows &rows, const SiteGeno &geno, BatchText &text)
     {
         Timed t_text("worker: records' text");
         const Batch &iso = job.iso, &gen = job.gen;
@@ -502,6 +560,15 @@ private:
             const int w = r.isolated ? 0 : 1;
             if (priors_file.f) priors_row(text.priors, r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
             if (tags && to.site_counts) put_site_counts(text.site_counts, r.n_alleles, rows.site_ns[w][r.slot], rows.site_ac[w].data() + r.allele0);
+            if (!to.site_stats) continue;
+            const uint32_t *het = geno.het[w].data() + r.allele0, *hom = geno.hom[w].data() + r.allele0;
+            const size_t cols = site_stats_cols(r.prefix);
+            if (to.site_stats_stream) put_site_geno(text.site_stats, r.n_alleles, geno.n[w][r.slot], het, hom, to.site_stats_cols ? r.prefix.data() : nullptr, cols);
+            else {
+                const size_t item = o.haploid ? 0 : geno.item_off[w][r.slot];
+                site_stats_row(text.site_stats, r.prefix.data(), cols, to.site_stats_samples, o.haploid, r.n_alleles, geno.n[w][r.slot], het, hom, geno.hwe[w].data() + item,
+                               geno.exc[w].data() + item);
+            }
         }
         if (to.merged && fmt.bcf_out)
             merged_bcf_records(text.merged, job.recs, rows.row_text, rows.row_off, rows.site_ac, rows.site_ns, fmt.bcf_hdr, fmt.n_fields(o), (uint32_t)P, to.merged_fixed,

@@ -1,6 +1,6 @@
 // cohort_out.hpp -- the host-only half of the outputs of `call --cohort`: the streams a group leaves for the passes behind the last group
-// (the records' site counts, the packed calls), the two paste passes over the groups' blocks of the merged output, and the text of the --pairs and
-// --sample-stats tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp drives this file alone).
+// (the records' site counts, the packed calls, the records' genotype counts), the two paste passes over the groups' blocks of the merged output, and
+// the text of the --pairs, --sample-stats and --site-stats tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp drives this file alone).
 #pragma once
 #include <deque>
 
@@ -158,6 +158,156 @@ inline std::string sample_table_text(const std::vector<std::string> &names, cons
         text += "\n";
     }
     return text;
+}
+
+// ---- the per-record table (--site-stats) ------------------------------------------------------------------------------------------
+// One line per record with an ALT: the record's first five columns, SAMPLES (the cohort), N (the usable cells: mg_site_geno_counts), AN, and a
+// comma list per ALT of AC, AF, HOM, HET, HWE, EXC_HET (mg_hwe_exact).  Diploid: AN = 2 N, AC = het + 2 hom; haploid: AN = N, AC = hom.
+inline const char *site_stats_header() { return "#CHROM\tPOS\tID\tREF\tALT\tSAMPLES\tN\tAN\tAC\tAF\tHOM\tHET\tHWE\tEXC_HET\n"; }
+// how much of a record's fixed columns (CHROM .. QUAL, as Rec::prefix holds them) the first five are
+inline size_t site_stats_cols(const std::string &prefix)
+{
+    size_t at = 0;
+    for (int t = 0; t < 5 && at != std::string::npos; ++t) at = prefix.find('\t', at + (t ? 1 : 0));
+    return at == std::string::npos ? prefix.size() : at;
+}
+// AF by the integer rule of mg_format_site_info: six decimals rounded half up, trailing zeros dropped, `0`, `1`, `.` when AN = 0
+inline void site_stats_af(std::string &out, uint64_t ac, uint64_t an)
+{
+    if (an == 0) {
+        out += '.';
+        return;
+    }
+    uint64_t q = (2 * ac * 1000000 + an) / (2 * an);
+    if (q == 0 || q >= 1000000) {
+        out += q ? '1' : '0';
+        return;
+    }
+    char digits[8];
+    snprintf(digits, sizeof digits, "%06u", (unsigned)q);
+    size_t nd = 6;
+    while (digits[nd - 1] == '0') --nd;
+    out += "0.";
+    out.append(digits, nd);
+}
+// the items of mg_hwe_exact a record gives, one per ALT, appended
+inline void site_stats_items(uint32_t n_alleles, uint32_t n, const uint32_t *het, const uint32_t *hom, std::vector<uint32_t> &item_n, std::vector<uint32_t> &item_het,
+                             std::vector<uint32_t> &item_hom)
+{
+    for (uint32_t a = 1; a < n_alleles; ++a) item_n.push_back(n), item_het.push_back(het[a]), item_hom.push_back(hom[a]);
+}
+// the record's line (none for a record without ALT).  het / hom: its n_alleles slots; hwe / exc: its n_alleles - 1 values, not read in haploid mode
+inline void site_stats_row(std::string &out, const char *cols, size_t cols_len, size_t samples, bool haploid, uint32_t n_alleles, uint32_t n, const uint32_t *het,
+                           const uint32_t *hom, const double *hwe, const double *exc)
+{
+    if (n_alleles < 2) return;
+    const uint64_t an = haploid ? n : 2 * (uint64_t)n;
+    out.append(cols, cols_len);
+    out += "\t" + std::to_string(samples) + "\t" + std::to_string(n) + "\t" + std::to_string(an);
+    auto list = [&](auto &&item) {
+        out += '\t';
+        for (uint32_t a = 1; a < n_alleles; ++a) {
+            if (a > 1) out += ',';
+            item(a);
+        }
+    };
+    auto ac = [&](uint32_t a) { return haploid ? (uint64_t)hom[a] : het[a] + 2 * (uint64_t)hom[a]; };
+    auto p_value = [&](const double *p, uint32_t a) {
+        char num[40];
+        if (haploid || n == 0) out += '.';
+        else {
+            snprintf(num, sizeof num, "%.6g", p[a - 1]);
+            out += num;
+        }
+    };
+    list([&](uint32_t a) { out += std::to_string(ac(a)); });
+    list([&](uint32_t a) { site_stats_af(out, ac(a), an); });
+    list([&](uint32_t a) { out += std::to_string(hom[a]); });
+    list([&](uint32_t a) { out += std::to_string(het[a]); });
+    list([&](uint32_t a) { p_value(hwe, a); });
+    list([&](uint32_t a) { p_value(exc, a); });
+    out += '\n';
+}
+
+// The cohort in several groups: every group leaves per record, in output order, the u32s n_alleles, n, het[n_alleles], hom[n_alleles]; the first
+// group's stream has behind each record a u32 length and that many bytes, the record's first five columns.
+inline void put_site_geno(std::string &out, uint32_t n_alleles, uint32_t n, const uint32_t *het, const uint32_t *hom, const char *cols, size_t cols_len)
+{
+    const uint32_t head[2] = {n_alleles, n};
+    out.append((const char *)head, 8);
+    out.append((const char *)het, 4 * (size_t)n_alleles);
+    out.append((const char *)hom, 4 * (size_t)n_alleles);
+    if (!cols) return;
+    const uint32_t len = (uint32_t)cols_len;
+    out.append((const char *)&len, 4);
+    out.append(cols, cols_len);
+}
+// the groups' streams read in step and summed
+struct SiteGenoReader {
+    GroupFiles in;
+    std::vector<uint32_t> more;
+    const char *short_file = "internal: a group's counts for the per-record table are short";
+    explicit SiteGenoReader(const std::deque<PartFile> &files) { in.open(files); }
+    // the next record: its alleles, the groups' n summed, their het and hom summed and appended, its columns; false where the first group's file ends
+    bool next(uint32_t &n_alleles, uint32_t &n, std::vector<uint32_t> &het, std::vector<uint32_t> &hom, std::string &cols)
+    {
+        uint32_t head[2], h[2], len;
+        if (fread(head, 4, 2, in.f[0]) != 2) return false;
+        const size_t A = head[0], at = het.size();
+        if (hom.size() != at) throw std::logic_error("SiteGenoReader: het and hom differ in length");
+        het.resize(at + A);
+        hom.resize(at + A);
+        if (A && (fread(&het[at], 4, A, in.f[0]) != A || fread(&hom[at], 4, A, in.f[0]) != A)) throw std::runtime_error(short_file);
+        if (fread(&len, 4, 1, in.f[0]) != 1) throw std::runtime_error(short_file);
+        cols.resize(len);
+        if (len && fread(&cols[0], 1, len, in.f[0]) != len) throw std::runtime_error(short_file);
+        more.resize(A);
+        for (size_t gi = 1; gi < in.f.size(); ++gi) {
+            if (fread(h, 4, 2, in.f[gi]) != 2 || h[0] != A) throw std::runtime_error(short_file);
+            head[1] += h[1];
+            for (std::vector<uint32_t> *sum : {&het, &hom}) {
+                if (A && fread(more.data(), 4, A, in.f[gi]) != A) throw std::runtime_error(short_file);
+                for (size_t a = 0; a < A; ++a) (*sum)[at + a] += more[a];
+            }
+        }
+        n_alleles = head[0];
+        n = head[1];
+        return true;
+    }
+    // behind the last record every later group's stream must have ended too
+    void end()
+    {
+        char one;
+        for (size_t gi = 1; gi < in.f.size(); ++gi)
+            if (fread(&one, 1, 1, in.f[gi]) != 0) throw std::runtime_error(short_file);
+    }
+};
+// The pass behind the last group: the header, then the records' lines, `batch` records at a time -- their items go to
+// hwe(n_items, n, het, hom, hwe_out, exc_out) (mg_hwe_exact, whoever holds the device; not called in haploid mode), the text to sink(data, n).
+template <class Hwe, class Sink> void site_stats_groups(const std::deque<PartFile> &files, size_t samples, bool haploid, size_t batch, Hwe &&hwe, Sink &&sink)
+{
+    SiteGenoReader in(files);
+    std::string out = site_stats_header();
+    std::vector<uint32_t> A, n, het, hom, item_n, item_het, item_hom;
+    std::vector<std::string> cols;
+    std::vector<double> p, exc;
+    for (bool more = true; more;) {
+        A.clear(), n.clear(), het.clear(), hom.clear(), item_n.clear(), item_het.clear(), item_hom.clear();
+        size_t nr = 0;
+        for (uint32_t a, nn; nr < batch; ++nr) {
+            if (cols.size() <= nr) cols.emplace_back();
+            if (!(more = in.next(a, nn, het, hom, cols[nr]))) break;
+            A.push_back(a), n.push_back(nn);
+            if (!haploid) site_stats_items(a, nn, het.data() + het.size() - a, hom.data() + hom.size() - a, item_n, item_het, item_hom);
+        }
+        p.resize(item_n.size()), exc.resize(item_n.size());
+        if (!item_n.empty()) hwe(item_n.size(), item_n.data(), item_het.data(), item_hom.data(), p.data(), exc.data());
+        for (size_t r = 0, slot = 0, item = 0; r < nr; slot += A[r], item += haploid || !A[r] ? 0 : A[r] - 1, ++r)
+            site_stats_row(out, cols[r].data(), cols[r].size(), samples, haploid, A[r], n[r], het.data() + slot, hom.data() + slot, p.data() + item, exc.data() + item);
+        sink(out.data(), out.size());
+        out.clear();
+    }
+    in.end();
 }
 
 // ---- the paste passes over the groups' blocks of the merged output -----------------------------------------------------------------

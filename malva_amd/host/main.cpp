@@ -112,6 +112,14 @@ const char *USAGE =
     "                                        and histogram, the coverage sum, the genotyper's status codes, and CALL_RATE, HET_HOM, TSTV,\n"
     "                                        MEAN_GQ, MEAN_COV ('.' for 0 / 0).  Summed on the GPU, whatever the grouping; beside -o\n"
     "                                        and/or --merged                                                                 [this build]\n"
+    "          --site-stats                  --cohort: PATH receives a tab-separated table, one line per record with an ALT, in the order\n"
+    "                                        of the merged output: CHROM POS ID REF ALT, SAMPLES (the cohort's size), N (the cells that are\n"
+    "                                        neither masked -- --min-gq applies -- nor carry an allele the record lacks), AN (2 N; haploid: N)\n"
+    "                                        and per ALT, comma-separated, AC, AF (six decimals, as --site-tags), HOM and HET (the samples with\n"
+    "                                        two copies / one copy; haploid: HOM = AC, HET = 0), HWE (the exact two-sided P value of\n"
+    "                                        Hardy-Weinberg proportions) and EXC_HET (the one-sided one for an excess of heterozygotes), both\n"
+    "                                        to six significant digits, '.' when N = 0 or with -1.  Counted and tested on the GPU, whatever\n"
+    "                                        the grouping; beside -o and/or --merged                                         [this build]\n"
     "          --cohort-priors               --cohort: the allele priors of every record are re-estimated from ALL samples of the cohort\n"
     "                                        before the genotypes are made -- a few EM steps from the panel's AF (or -u's uniform\n"
     "                                        prior), anchored to it -- and every sample is genotyped under the cohort's frequencies.\n"
@@ -175,6 +183,7 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"prior-weight", required_argument, nullptr, 1014}, {"priors-out", required_argument, nullptr, 1015},
                                       {"prior-groups", no_argument, nullptr, 1016},
                                       {"pl", no_argument, nullptr, 1017},             {"pl-cap", required_argument, nullptr, 1018},
+                                      {"site-stats", required_argument, nullptr, 1019},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -251,6 +260,13 @@ bool parse_arguments(int argc, char **argv, Options &o)
             o.sample_stats = optarg;
             if (o.sample_stats.empty()) {
                 std::cerr << "malva : --sample-stats takes a path\n";
+                die = true;
+            }
+            break;
+        case 1019:
+            o.site_stats = optarg;
+            if (o.site_stats.empty()) {
+                std::cerr << "malva : --site-stats takes a path\n";
                 die = true;
             }
             break;
@@ -341,6 +357,10 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (!o.cohort && !o.sample_stats.empty()) {
         std::cerr << "malva : --sample-stats goes with --cohort\n";
+        die = true;
+    }
+    if (!o.cohort && !o.site_stats.empty()) {
+        std::cerr << "malva : --site-stats goes with --cohort\n";
         die = true;
     }
     if (const std::string why = check_prior_options(o.priors, o.cohort); !why.empty()) {
@@ -1368,6 +1388,11 @@ int call_main(const Options &o)
         std::vector<size_t> group_first; // the first sample of every group
         // --sample-stats: [samples][MG_SAMPLE_SLOTS]; a sample belongs to one group, whose panel pass sums its row, so the table needs no pass of its own
         std::vector<uint64_t> sample_table(want_sample ? S * MG_SAMPLE_SLOTS : 0, 0);
+        // --site-stats: a cohort that runs as ONE group writes the table's lines as its batches leave (PATH.part, renamed at the end).  Otherwise every
+        // group leaves its records' counts in PATH.gN.geno.part, and the pass behind the last group sums them, tests the sums and writes the table
+        const bool want_site = !o.site_stats.empty();
+        std::deque<PartFile> geno_files;
+        PartFile site_file;
         std::vector<std::string> names;
         for (const auto &sm : samples) names.push_back(sm.name);
         const bool merged_stdout = o.merged == "-";
@@ -1478,6 +1503,15 @@ int call_main(const Options &o)
             to.merged_fixed = s0 == 0;
             to.pairs = want_pairs ? &pairs_run : nullptr;
             to.sample_table = want_sample ? &sample_table[s0 * MG_SAMPLE_SLOTS] : nullptr;
+            if (want_site) {
+                to.site_stats_stream = g != S, to.site_stats_cols = s0 == 0, to.site_stats_samples = S;
+                if (g != S) to.site_stats = &open_scratch(geno_files, o.site_stats, ".geno.part");
+                else {
+                    site_file.open(o.site_stats);
+                    site_file.write(site_stats_header());
+                    to.site_stats = &site_file;
+                }
+            }
             for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
                 to.per_sample.emplace_back();
                 to.per_sample.back().open(o.out_dir + "/" + samples[s0 + i].name + ".vcf");
@@ -1505,6 +1539,7 @@ int call_main(const Options &o)
             for (size_t i = 0; want_pairs && i < g; ++i)
                 for (size_t j = i + 1; j < g; ++j) std::copy_n(&pairs_run.counts[(i * g + j) * 9], 9, &pair_table[((s0 + i) * S + s0 + j) * 9]);
             if (to.site_counts) to.site_counts->close("cannot write the merged output's counts");
+            if (to.site_stats) to.site_stats->close(to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
             if (to.merged) {
                 if (bcf_out && bcf_bgzf && merged_direct) to.merged->write(bgzf_eof(), "cannot write the merged output");
                 to.merged->close("cannot write the merged output");
@@ -1578,6 +1613,22 @@ int call_main(const Options &o)
             PartFile::put(o.pairs, pair_table_text(names, pair_table.data()));
         }
         if (want_sample) PartFile::put(o.sample_stats, sample_table_text(names, sample_table.data()));
+        if (want_site && !geno_files.empty()) {
+            Timed t("cohort: site table pass");
+            site_file.open(o.site_stats);
+            site_stats_groups(
+                geno_files, S, o.haploid, geno_batch_records(65536),
+                [&](size_t n_items, const uint32_t *n, const uint32_t *het, const uint32_t *hom, double *hwe, double *exc) {
+                    dev.check(mg_hwe_exact(dev.ctx, n_items, n, het, hom, hwe, exc), "mg_hwe_exact");
+                    float ms[2] = {0, 0};
+                    dev.check(mg_hwe_stats(dev.ctx, ms), "mg_hwe_stats");
+                    times.geno.ms[1] += ms[1];
+                    ++times.geno.calls[1];
+                },
+                [&](const char *data, size_t n) { site_file.write(data, n, "cannot write the per-record table"); });
+            geno_files.clear(); // (the groups' streams go before the table takes its name)
+        }
+        if (want_site) site_file.finish("cannot write the per-record table");
         priors_file.finish();
         times.add_to_timers();
         std::cerr << times.report();

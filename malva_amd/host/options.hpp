@@ -31,6 +31,7 @@ struct Options { // argument_parser.hpp:51-66
     int32_t pl_cap = 255;   // --pl-cap: the largest PL written (the bcftools convention)
     std::string pairs;      // --pairs: the table of pairwise genotype sharing
     std::string sample_stats; // --sample-stats: the per-sample QC table
+    std::string site_stats; // --site-stats: the per-record QC table
     PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
 };
 
