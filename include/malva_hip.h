@@ -696,6 +696,63 @@ int mg_hwe_exact(mg_ctx *ctx, size_t n_items, const uint32_t *n, const uint32_t 
 int mg_hwe_exact_device(mg_ctx *ctx, size_t n_items, const void *d_n, const void *d_het, const void *d_hom, void *d_hwe_out, void *d_exc_het_out);
 int mg_hwe_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- the LD table of a multi-sample call set ----------------------------------------
+ * Record against record along the samples: for a record and each of the `window` records behind it, the squared correlation r2 of
+ * the two dosages over the samples that contribute in both.  There is no reference call to cite: the reference genotypes one
+ * individual per run and has nothing that looks across samples.
+ * mg_pack_site_dosage: inputs and the CALLED rule exactly as for mg_pack_dosage: gt1 / gt2 / gq [n_planes][n_vars] int32,
+ * plane-major, n_planes 1..64; gt2 is not read in haploid mode and may be NULL, gq not unless use_mask; a cell is called unless
+ * use_mask != 0 and its gq < min_gq; var_allele_off ([n_vars + 1]) is required.  A cell (p, v) CONTRIBUTES when record v has two
+ * alleles, the cell is called and every allele index the mode reads is 0 or 1; its dosage is gt1 + gt2 (haploid: 2 * gt1).
+ * sites_out is uint64_t [3][n_vars] -- the transpose of mg_pack_dosage's layout, bits over samples per record: bit p of
+ * sites_out[d * n_vars + v] is set exactly when the cell (p, v) contributes with dosage d.  Bits at and above n_planes are 0.
+ * Every word is written, the caller need not clear it; n_vars == 0 is legal and writes nothing.  Argument errors as
+ * mg_pack_dosage's: n_planes out of range, a NULL var_allele_off, a NULL gt1 or sites_out with n_vars > 0, a NULL gt2 in diploid
+ * mode, a NULL gq under the mask: MG_ERR_ARG.
+ * mg_ld_window: sites is uint64_t [n_groups][3][n_vars], the groups' mg_pack_site_dosage outputs over the same records
+ * (n_groups 1..MG_LD_MAX_GROUPS: 16,384 samples, the cohort's own limit); chrom and pos are uint32_t [n_vars]; window is
+ * 1..MG_LD_MAX_WINDOW; min_r2 is finite and in [0, 1]; min_n is at least 1; n_first <= n_vars -- each of these else MG_ERR_ARG, as a
+ * NULL sites / chrom / pos with n_vars > 0, a NULL row_off_out or n_pairs_out, a NULL pairs_out with pairs_cap > 0.
+ * The pair (i, j) is ELIGIBLE when i < n_first, i < j <= i + window, j < n_vars, chrom[i] == chrom[j], and max_bp == 0 or
+ * |pos[j] - pos[i]| <= max_bp (the difference formed in signed 64-bit).  Records at and beyond n_first serve as partners only:
+ * a caller walks a long table in chunks with a look-ahead of `window` records, and every pair comes out exactly once.
+ * Over all groups and the samples whose cells contribute in BOTH records, with dosages x at i and y at j:  n the number of such
+ * samples, Sx, Sy, Sxx, Syy, Sxy the sums of x, y, x x, y y, x y -- popcounts of ANDs of the six words and their ORs, the groups'
+ * words only ever ANDed within a group and the popcounts summed, so the result does not depend on how a cohort is cut into groups.
+ * In signed 64-bit:  cov = n Sxy - Sx Sy,  vx = n Sxx - Sx Sx,  vy = n Syy - Sy Sy.  With n <= 2^14 each of the three is at most
+ * 2^30 in magnitude, so cov cov and vx vy are at most 2^60 and nothing wraps.  The pair is DEFINED when n >= min_n, vx > 0 and
+ * vy > 0; then r2 = double(uint64(cov cov)) / double(uint64(vx vy)): each conversion rounds once, to nearest even, and there is
+ * one division, so every step is one correctly rounded operation and the bits are the same on every device and in every
+ * restatement.  The pair is EMITTED when it is eligible, defined and r2 >= min_r2.
+ * An emitted pair is one mg_ld_pair: i, j, n, sign (+1, -1 or 0: the sign of cov) and r2.  Emitted pairs are ordered by i, then j
+ * ascending, whatever the launch geometry; row_off_out is uint64_t [n_first + 1], record i's pairs are
+ * pairs_out[row_off_out[i] .. row_off_out[i + 1]).  The buffer contract is mg_format_calls': *n_pairs_out (a HOST pointer in both
+ * forms) always receives the number of pairs needed; when that exceeds pairs_cap the call returns MG_ERR_LIMIT, nothing is written
+ * at or behind pairs_cap, row_off_out is valid all the same, and the caller may come again with a larger buffer.  n_first == 0 and
+ * n_vars == 0 are legal: row_off_out[0] = 0.
+ * Each call has a host form, which synchronises, and a _device form (every array a device pointer), asynchronous on the context's
+ * stream -- mg_ld_window_device until it reads the total back, behind its write pass.
+ * mg_ld_stats (waits): ms_out[2], device milliseconds of the most recent mg_pack_site_dosage* and of the most recent mg_ld_window*
+ * (its three passes together); 0 for a kind not called yet, MG_ERR_STATE when neither was.
+ * The calls keep their device copies of their tables and their events apart from every other section's: a call of another kind
+ * in between changes nothing. */
+#define MG_LD_MAX_GROUPS 256
+#define MG_LD_MAX_WINDOW 1024
+typedef struct mg_ld_pair {
+    uint32_t i, j, n;
+    int32_t sign;
+    double r2;
+} mg_ld_pair; /* 24 bytes */
+int mg_pack_site_dosage(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                        int32_t min_gq, const uint32_t *var_allele_off, uint64_t *sites_out);
+int mg_pack_site_dosage_device(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                               int32_t min_gq, const void *d_var_allele_off, void *d_sites_out);
+int mg_ld_window(mg_ctx *ctx, size_t n_vars, size_t n_first, uint32_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, uint32_t window,
+                 uint64_t max_bp, uint32_t min_n, double min_r2, mg_ld_pair *pairs_out, size_t pairs_cap, uint64_t *row_off_out, uint64_t *n_pairs_out);
+int mg_ld_window_device(mg_ctx *ctx, size_t n_vars, size_t n_first, uint32_t n_groups, const void *d_sites, const void *d_chrom, const void *d_pos, uint32_t window,
+                        uint64_t max_bp, uint32_t min_n, double min_r2, void *d_pairs_out, size_t pairs_cap, void *d_row_off_out, uint64_t *n_pairs_out);
+int mg_ld_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- allele priors re-estimated from the cohort -------------------------------------
  * mg_genotype_cohort: the batch's allele frequencies are re-estimated from all of its planes (a few EM steps from the panel's
  * priors, anchored to them), then every cell is genotyped under the result.  The reference genotypes one individual and has no

@@ -21,6 +21,8 @@ MAX_ROW = (MG_MAX_KMER + 1 + 7) // 8 * 8   # 136: MG_MAX_KMER bytes + NUL, round
 STREAM_DEFAULT = 1          # MG_STREAM_DEFAULT: HIP's legacy default stream (a NULL handle means the context's own stream)
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 COMM_ID_BYTES = 128
+LD_MAX_GROUPS, LD_MAX_WINDOW = 256, 1024   # MG_LD_MAX_GROUPS, MG_LD_MAX_WINDOW
+LD_PAIR = np.dtype([("i", np.uint32), ("j", np.uint32), ("n", np.uint32), ("sign", np.int32), ("r2", np.float64)])   # mg_ld_pair, 24 bytes
 SAMPLE_SLOTS = 32           # MG_SAMPLE_SLOTS: the counters per plane of mg_sample_counts (MG_SS_*)
 GT_NORMAL, GT_OVERCOV, GT_SINGLE, GT_NOCOV = 0, 1, 2, 3
 
@@ -132,6 +134,11 @@ def lib():
         "mg_hwe_exact": [vp, sz, vp, vp, vp, vp, vp],
         "mg_hwe_exact_device": [vp, sz, vp, vp, vp, vp, vp],
         "mg_hwe_stats": [vp, vp],
+        "mg_pack_site_dosage": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp],
+        "mg_pack_site_dosage_device": [vp, sz, u32, it, vp, vp, vp, it, i32, vp, vp],
+        "mg_ld_window": [vp, sz, sz, u32, vp, vp, vp, u32, C.c_uint64, u32, C.c_double, vp, sz, vp, vp],
+        "mg_ld_window_device": [vp, sz, sz, u32, vp, vp, vp, u32, C.c_uint64, u32, C.c_double, vp, sz, vp, vp],
+        "mg_ld_stats": [vp, vp],
         "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_cohort_prior_stats": [vp, vp],
@@ -208,7 +215,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_site_counts", "mg_site_counts_device", "mg_format_site_info",
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
             "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats",
-            "mg_site_geno_counts", "mg_site_geno_counts_device", "mg_hwe_exact", "mg_hwe_exact_device", "mg_hwe_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_site_geno_counts", "mg_site_geno_counts_device", "mg_hwe_exact", "mg_hwe_exact_device", "mg_hwe_stats",
+            "mg_pack_site_dosage", "mg_pack_site_dosage_device", "mg_ld_window", "mg_ld_window_device", "mg_ld_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -967,6 +975,69 @@ class Context:
         """-> device ms of the most recent site_geno_counts and of the most recent hwe_exact"""
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_hwe_stats(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    # the LD table of a multi-sample call set
+    def pack_site_dosage(self, gt1, gt2, gq, haploid, var_allele_off, min_gq=None, out=None):
+        """gt1 / gt2 / gq: [planes, n_vars] int32 -> uint64 [3, n_vars]: bit p of [d, v] is set when (p, v) is a called cell of a biallelic
+        record with allele indexes in {0, 1} and dosage d (haploid: 2 * gt1) -- pack_dosage's cells, bits over samples per record
+        (mg_pack_site_dosage in include/malva_hip.h).  out: the array to fill (every word is overwritten)."""
+        a = lambda x, t: None if x is None else np.ascontiguousarray(x, dtype=t)
+        g1, g2, q, vo = a(gt1, np.int32), a(gt2, np.int32), a(gq, np.int32), a(var_allele_off, np.uint32)
+        planes, n = g1.shape
+        if out is None:
+            out = np.zeros((3, n), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (3, n)
+        self._ck(self._L.mg_pack_site_dosage(self.h, n, planes, int(haploid), _p(g1), _p(g2), _p(q), int(min_gq is not None), int(min_gq or 0), _p(vo), _p(out)))
+        return out
+
+    def pack_site_dosage_device(self, n_vars, planes, haploid, d_gt1, d_gt2, d_gq, d_var_allele_off, d_sites_out, min_gq=None):
+        """the same from device pointers into a device buffer, asynchronous on the context's stream"""
+        v = C.c_void_p
+        self._ck(self._L.mg_pack_site_dosage_device(self.h, n_vars, planes, int(haploid), v(d_gt1), v(d_gt2), v(d_gq), int(min_gq is not None), int(min_gq or 0),
+                                                    v(d_var_allele_off), v(d_sites_out)))
+
+    def ld_window(self, sites, chrom, pos, window, n_first=None, max_bp=0, min_n=1, min_r2=0.0, pairs_cap=None):
+        """sites: uint64 [groups, 3, n_vars] (the groups' pack_site_dosage outputs); chrom / pos: uint32 [n_vars] -> (pairs, row_off): pairs a
+        structured array (LD_PAIR: i, j, n, sign, r2) of the emitted pairs ordered by i, then j; record i's are
+        pairs[row_off[i]:row_off[i + 1]], i < n_first (default: n_vars) -- mg_ld_window in include/malva_hip.h.  pairs_cap None: the call
+        is repeated with the buffer it asked for; a given one that is too small raises MalvaError(MG_ERR_LIMIT) with .needed, .row_off
+        and .pairs (the whole buffer) set."""
+        S = np.ascontiguousarray(sites, dtype=np.uint64)
+        ch, po = (np.ascontiguousarray(x, dtype=np.uint32) for x in (chrom, pos))
+        groups, three, n = S.shape
+        assert three == 3 and ch.shape == (n,) and po.shape == (n,)
+        nf = n if n_first is None else int(n_first)
+        row_off = np.zeros(max(nf, 0) + 1, dtype=np.uint64)
+        need = C.c_uint64(0)
+
+        def call(cap):
+            pairs = np.zeros(max(cap, 1), dtype=LD_PAIR)
+            return self._L.mg_ld_window(self.h, n, nf, groups, _p(S), _p(ch), _p(po), int(window), int(max_bp), int(min_n), float(min_r2),
+                                        _p(pairs) if cap else None, cap, _p(row_off), C.byref(need)), pairs
+        rc, pairs = call(0 if pairs_cap is None else int(pairs_cap))
+        if rc == -5 and pairs_cap is None and need.value:
+            rc, pairs = call(need.value)
+        if rc != 0:
+            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
+            e.needed, e.row_off, e.pairs = need.value, row_off, pairs
+            raise e
+        return pairs[:need.value], row_off
+
+    def ld_window_device(self, n_vars, n_first, groups, d_sites, d_chrom, d_pos, window, max_bp, min_n, min_r2, d_pairs, pairs_cap, d_row_off):
+        """the same from device pointers into device buffers -> (return code, pairs needed); MG_ERR_LIMIT (-5) is returned, not raised"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_ld_window_device(self.h, n_vars, n_first, groups, v(d_sites), v(d_chrom), v(d_pos), int(window), int(max_bp), int(min_n), float(min_r2),
+                                         v(d_pairs), pairs_cap, v(d_row_off), C.byref(need))
+        if rc not in (0, -5):
+            self._ck(rc)
+        return rc, need.value
+
+    def ld_stats(self):
+        """-> device ms of the most recent pack_site_dosage and of the most recent ld_window"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.mg_ld_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
 
     # allele priors re-estimated from the planes of a batch, and the cells genotyped under them

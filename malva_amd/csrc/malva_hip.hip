@@ -43,6 +43,7 @@ constexpr int TPB = 256;
 #include "pair_kernels.h"
 #include "sample_kernels.h"
 #include "site_geno_kernels.h"
+#include "ld_kernels.h"
 #include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
 #include "pl_kernels.h"
@@ -90,7 +91,7 @@ struct Timer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_GENO, TM_HWE, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device, mg_site_geno_counts*, mg_hwe_exact*
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_GENO, TM_HWE, TM_LD_PACK, TM_LD, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device, mg_site_geno_counts*, mg_hwe_exact*, mg_pack_site_dosage*, mg_ld_window* (length pass, scan, write pass)
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -105,6 +106,7 @@ enum {
     ST_FREQ, ST_FREQ_OUT, ST_NINF,                                                                         // mg_genotype_cohort's priors
     ST_PL,                                                                                                 // mg_phred_likelihoods' result, the *_pl encoders' input
     ST_SG_N, ST_SG_HET, ST_SG_HOM, ST_HWE, ST_EXC_HET,                                                     // mg_site_geno_counts' tables, mg_hwe_exact's items and results
+    ST_LD_WORDS, ST_LD_SITES, ST_LD_CHROM, ST_LD_POS, ST_LD_PAIRS, ST_LD_ROW_OFF,                          // mg_pack_site_dosage's words; mg_ld_window's tables and pairs
     ST_COUNT
 };
 
@@ -172,8 +174,9 @@ struct mg_ctx {
     // each stats call reports the latest call of its own kinds, hence a timer per kind: the encoders' four events, the counting calls' two;
     // mg_cover_blocks_device: before / after the preparation, the lone kernels, the enumerating kernel; mg_cover_blocks_cohort_device: start,
     // after tier 1, after the planes' tiers 2-3
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}, {2}, {2}};
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}, {2}, {2}, {2}, {4}};
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
+    Scratch s_ld[2]; // mg_ld_window_device, from its length pass to its write pass: the records' pair counts (u32), the meta block (the total)
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
     bool gate_dirty = false; // something has been inserted into `bf`
@@ -808,6 +811,7 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     for (auto &enc : c->s_enc)
         for (Scratch &q : enc) hipFree(q.p);
     for (Scratch &q : c->stage) hipFree(q.p);
+    for (Scratch &q : c->s_ld) hipFree(q.p);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3752,6 +3756,143 @@ MG_EXPORT int mg_hwe_stats(mg_ctx *c, float *ms_out)
     if (!c->tm[TM_GENO].valid && !c->tm[TM_HWE].valid) return fail(c, MG_ERR_STATE, "no mg_site_geno_counts or mg_hwe_exact yet");
     TRY(timer_read(c, c->tm[TM_GENO], &ms_out[0]));
     return timer_read(c, c->tm[TM_HWE], &ms_out[1]);
+}
+
+// ---- the LD table of a multi-sample call set (ld_kernels.h) ---------------------------------------------------------------------------
+namespace {
+int pack_site_dosage_device(mg_ctx *c, const mg_cells &x, void *d_sites_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_cells(c, "mg_pack_site_dosage", x, false, x.use_mask));
+    if (!x.var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_site_dosage: var_allele_off is required");
+    if (x.n_vars && !d_sites_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    TRY(timer_begin(c, c->tm[TM_LD_PACK]));
+    if (x.n_vars) {
+        const PackArgs a{(u64)x.n_vars, 0, x.n_planes, x.haploid, (const i32 *)x.gt1, (const i32 *)x.gt2, (const i32 *)x.gq, x.use_mask, x.min_gq,
+                         (const u32 *)x.var_allele_off};
+        hipLaunchKernelGGL(pack_site_kernel, dim3((unsigned)(((u64)x.n_vars + LD_PACK_RECS - 1) / LD_PACK_RECS)), dim3(LD_PACK_TPB), 0, c->stream, a,
+                           (unsigned long long *)d_sites_out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_LD_PACK], 1);
+}
+int check_ld(mg_ctx *c, size_t n_vars, size_t n_first, uint32_t n_groups, const void *sites, const void *chrom, const void *pos, uint32_t window, uint32_t min_n,
+             double min_r2, const void *pairs_out, size_t pairs_cap, const void *row_off_out, const uint64_t *n_pairs_out)
+{
+    if (n_groups < 1 || n_groups > MG_LD_MAX_GROUPS) return fail(c, MG_ERR_ARG, "mg_ld_window: n_groups is 1..%d", MG_LD_MAX_GROUPS);
+    if (window < 1 || window > MG_LD_MAX_WINDOW) return fail(c, MG_ERR_ARG, "mg_ld_window: window is 1..%d", MG_LD_MAX_WINDOW);
+    if (!(min_r2 >= 0.0 && min_r2 <= 1.0)) return fail(c, MG_ERR_ARG, "mg_ld_window: min_r2 is in [0, 1]"); // (a NaN fails both)
+    if (min_n < 1) return fail(c, MG_ERR_ARG, "mg_ld_window: min_n is at least 1");
+    if (n_first > n_vars) return fail(c, MG_ERR_ARG, "mg_ld_window: n_first beyond n_vars");
+    if (!row_off_out || !n_pairs_out || (!pairs_out && pairs_cap) || (n_vars && (!sites || !chrom || !pos))) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_ld_window: more than 2^32 - 1 records in one call");
+    return MG_OK;
+}
+} // namespace
+MG_EXPORT int mg_pack_site_dosage_device(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const void *d_gt1, const void *d_gt2, const void *d_gq, int use_mask,
+                                         int32_t min_gq, const void *d_var_allele_off, void *d_sites_out)
+{
+    return pack_site_dosage_device(c, mg_cells{n_vars, n_planes, haploid, d_gt1, d_gt2, d_gq, use_mask, min_gq, nullptr, d_var_allele_off}, d_sites_out);
+}
+
+MG_EXPORT int mg_pack_site_dosage(mg_ctx *c, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
+                                  int32_t min_gq, const uint32_t *var_allele_off, uint64_t *sites_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    const mg_cells x{n_vars, n_planes, haploid, gt1, gt2, gq, use_mask, min_gq, nullptr, var_allele_off};
+    TRY(check_cells(c, "mg_pack_site_dosage", x, false, use_mask));
+    if (!var_allele_off) return fail(c, MG_ERR_ARG, "mg_pack_site_dosage: var_allele_off is required");
+    if (n_vars && !sites_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    const size_t out_bytes = 8 * 3 * n_vars;
+    mg_cells d;
+    void *d_out;
+    TRY(stage_cells(c, x, &d, false, true));
+    TRY(scratch(c, c->stage[ST_LD_WORDS], out_bytes ? out_bytes : 1, &d_out));
+    TRY(pack_site_dosage_device(c, d, d_out));
+    if (out_bytes) HIP_TRY(c, hipMemcpyAsync(sites_out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// a length pass, the scan of the lengths into d_row_off[n_first + 1], a write pass that makes the same pairs again (ld_kernels.h); the
+// total comes back between the scan and the return, as an encoder's does
+MG_EXPORT int mg_ld_window_device(mg_ctx *c, size_t n_vars, size_t n_first, uint32_t n_groups, const void *d_sites, const void *d_chrom, const void *d_pos,
+                                  uint32_t window, uint64_t max_bp, uint32_t min_n, double min_r2, void *d_pairs_out, size_t pairs_cap, void *d_row_off_out,
+                                  uint64_t *n_pairs_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_ld(c, n_vars, n_first, n_groups, d_sites, d_chrom, d_pos, window, min_n, min_r2, d_pairs_out, pairs_cap, d_row_off_out, n_pairs_out));
+    Timer &t = c->tm[TM_LD];
+    TRY(timer_begin(c, t));
+    *n_pairs_out = 0;
+    if (n_first == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_row_off_out, 0, 8, c->stream));
+        for (int i = 1; i < 4; ++i) TRY(timer_mark(c, t, i));
+        return MG_OK;
+    }
+    void *d_len, *d_meta, *part;
+    TRY(scratch(c, c->s_ld[0], 4 * n_first, &d_len));
+    TRY(scratch(c, c->s_ld[1], 16, &d_meta));
+    const u64 n_part = ((u64)n_first + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    unsigned long long *meta = (unsigned long long *)d_meta;
+    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
+    const LdArgs a{(u64)n_vars, (u64)n_first, n_groups, window, (const unsigned long long *)d_sites, (const u32 *)d_chrom, (const u32 *)d_pos, max_bp, min_n, min_r2};
+    const dim3 grid((unsigned)(((u64)n_first + LD_TILE - 1) / LD_TILE));
+    hipLaunchKernelGGL(ld_window_kernel<false>, grid, dim3(LD_TPB), 0, c->stream, a, (u32 *)d_len, (const unsigned long long *)nullptr, (LdPair *)nullptr, (u64)0);
+    HIP_TRY(c, hipGetLastError());
+    TRY(timer_mark(c, t, 1));
+    fmt_scan(c, d_len, (u64)n_first, n_part, part, d_row_off_out, meta);
+    HIP_TRY(c, hipGetLastError());
+    TRY(timer_mark(c, t, 2));
+    hipLaunchKernelGGL(ld_window_kernel<true>, grid, dim3(LD_TPB), 0, c->stream, a, (u32 *)nullptr, (const unsigned long long *)d_row_off_out, (LdPair *)d_pairs_out,
+                       (u64)pairs_cap);
+    HIP_TRY(c, hipGetLastError());
+    TRY(timer_mark(c, t, 3));
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_pairs_out = total;
+    if (total > pairs_cap) return fail(c, MG_ERR_LIMIT, "mg_ld_window: %llu pairs, the buffer holds %llu", total, (unsigned long long)pairs_cap);
+    return MG_OK;
+}
+
+MG_EXPORT int mg_ld_window(mg_ctx *c, size_t n_vars, size_t n_first, uint32_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, uint32_t window,
+                           uint64_t max_bp, uint32_t min_n, double min_r2, mg_ld_pair *pairs_out, size_t pairs_cap, uint64_t *row_off_out, uint64_t *n_pairs_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_ld(c, n_vars, n_first, n_groups, sites, chrom, pos, window, min_n, min_r2, pairs_out, pairs_cap, row_off_out, n_pairs_out));
+    void *d_sites, *d_chrom, *d_pos, *d_pairs, *d_off;
+    TRY(upload(c, c->stage[ST_LD_SITES], sites, 8 * (size_t)n_groups * 3 * n_vars, &d_sites));
+    TRY(upload(c, c->stage[ST_LD_CHROM], chrom, 4 * n_vars, &d_chrom));
+    TRY(upload(c, c->stage[ST_LD_POS], pos, 4 * n_vars, &d_pos));
+    TRY(scratch(c, c->stage[ST_LD_PAIRS], pairs_cap ? sizeof(mg_ld_pair) * pairs_cap : 1, &d_pairs));
+    TRY(scratch(c, c->stage[ST_LD_ROW_OFF], 8 * (n_first + 1), &d_off));
+    const int rc = mg_ld_window_device(c, n_vars, n_first, n_groups, d_sites, d_chrom, d_pos, window, max_bp, min_n, min_r2, d_pairs, pairs_cap, d_off, n_pairs_out);
+    if (rc != MG_OK && !(rc == MG_ERR_LIMIT && *n_pairs_out > pairs_cap)) return rc;
+    const size_t have = std::min<uint64_t>(*n_pairs_out, pairs_cap);
+    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n_first + 1), hipMemcpyDeviceToHost, c->stream));
+    if (have) HIP_TRY(c, hipMemcpyAsync(pairs_out, d_pairs, sizeof(mg_ld_pair) * have, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+// device milliseconds (waits for them): ms_out[0] the most recent mg_pack_site_dosage*, [1] the most recent mg_ld_window* (its three passes together); 0 where there was none
+MG_EXPORT int mg_ld_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = ms_out[1] = 0.f; // (also where it fails)
+    if (!c->tm[TM_LD_PACK].valid && !c->tm[TM_LD].valid) return fail(c, MG_ERR_STATE, "no mg_pack_site_dosage or mg_ld_window yet");
+    float passes[3];
+    TRY(timer_read(c, c->tm[TM_LD_PACK], &ms_out[0]));
+    TRY(timer_read(c, c->tm[TM_LD], passes));
+    ms_out[1] = passes[0] + passes[1] + passes[2];
+    return MG_OK;
 }
 
 // ---- allele priors re-estimated from the planes of a batch (cohort_prior_kernels.h) ------------------------------------------------------

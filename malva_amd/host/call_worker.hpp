@@ -35,13 +35,14 @@ struct CallTimes {
     Kind estimate; // --prior-groups: mg_estimate_priors
     Kind pl;       // --pl: mg_phred_likelihoods
     Kind geno;     // --site-stats: [0] mg_site_geno_counts, [1] mg_hwe_exact
+    Kind ld;       // --ld: [0] mg_pack_site_dosage, [1] mg_ld_window
     size_t gt_bytes = 0; // panel genotypes handed to mg_cover_blocks[_cohort]
 
     CallTimes &operator+=(const CallTimes &o)
     {
         Kind CallTimes::*const kinds[] = {&CallTimes::format, &CallTimes::bcf,   &CallTimes::site,    &CallTimes::pairs,
                                           &CallTimes::sample, &CallTimes::prior, &CallTimes::estimate, &CallTimes::pl,
-                                          &CallTimes::geno};
+                                          &CallTimes::geno,   &CallTimes::ld};
         for (auto k : kinds)
             for (int i = 0; i < 3; ++i) (this->*k).ms[i] += (o.*k).ms[i], (this->*k).calls[i] += (o.*k).calls[i];
         gt_bytes += o.gt_bytes;
@@ -54,6 +55,7 @@ struct CallTimes {
         if (pairs.calls[1]) g_timers.add("pairs: pack and count kernels (device)", (pairs.ms[0] + pairs.ms[1]) / 1000.0);
         if (sample.calls[0]) g_timers.add("sample table: count kernel (device)", sample.ms[0] / 1000.0);
         if (geno.calls[0]) g_timers.add("site table: count and test kernels (device)", (geno.ms[0] + geno.ms[1]) / 1000.0);
+        if (ld.calls[0]) g_timers.add("ld table: pack and window kernels (device)", (ld.ms[0] + ld.ms[1]) / 1000.0);
         if (prior.calls[0]) g_timers.add("cohort priors: kernel (device)", prior.ms[0] / 1000.0);
         if (estimate.calls[0]) g_timers.add("cohort priors: estimate kernel (device)", estimate.ms[0] / 1000.0);
         if (pl.calls[0]) g_timers.add("merged: likelihood kernel (device)", pl.ms[0] / 1000.0);
@@ -79,6 +81,11 @@ struct CallTimes {
         if (geno.calls[0]) {
             snprintf(line, sizeof line, "[malva-geno] site-stats: %zu mg_site_geno_counts, %zu mg_hwe_exact, device ms per call: count %.3f test %.3f\n", geno.calls[0],
                      geno.calls[1], geno.ms[0] / geno.calls[0], geno.calls[1] ? geno.ms[1] / geno.calls[1] : 0.0);
+            out += line;
+        }
+        if (ld.calls[0]) {
+            snprintf(line, sizeof line, "[malva-geno] ld: %zu mg_pack_site_dosage, %zu mg_ld_window, device ms per call: pack %.3f window %.3f\n", ld.calls[0], ld.calls[1],
+                     ld.ms[0] / ld.calls[0], ld.calls[1] ? ld.ms[1] / ld.calls[1] : 0.0);
             out += line;
         }
         if (prior.calls[0]) {
@@ -145,6 +152,10 @@ struct PassOut {
     PartFile *site_stats = nullptr;
     bool site_stats_stream = false, site_stats_cols = false;
     size_t site_stats_samples = 0; // the cohort's size
+    // --ld: the records' words over the group's planes are made while the batch is in hand (mg_pack_site_dosage) and go here in output order
+    // (put_ld_words, with the records' columns when ld_cols) for the pass behind the last group (ld_table)
+    PartFile *ld = nullptr;
+    bool ld_cols = false;
     // --prior-groups, a cohort in several groups (host/cohort_priors.hpp).  prior_cov: the coverage pass -- the batches' coverages go here
     // (put_cov_batch; the first group's with the records' offsets and panel priors), and the pass makes no calls and nothing else.
     // prior_in: the output pass -- the batches' coverages and the cohort's frequencies come from here instead of the counters, and the
@@ -155,7 +166,7 @@ struct PassOut {
 };
 struct BatchText { // the text of one batch, as its worker hands it over
     std::vector<std::string> per_sample;
-    std::string merged, site_counts, pack, priors, prior_cov, site_stats; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
+    std::string merged, site_counts, pack, priors, prior_cov, site_stats, ld; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
     CallTimes times; // of this batch's calls alone
 };
 
@@ -216,6 +227,7 @@ public:
         if (to.merged) fflush(to.merged->f);
         if (to.site_counts) fflush(to.site_counts->f);
         if (to.site_stats) fflush(to.site_stats->f);
+        if (to.ld) fflush(to.ld->f);
     }
 
 private:
@@ -233,6 +245,9 @@ private:
         std::vector<uint32_t> n[2], het[2], hom[2];
         std::vector<size_t> item_off[2];
         std::vector<double> hwe[2], exc[2];
+    };
+    struct SiteWords { // --ld: the same two batches' words, [3][records]
+        std::vector<uint64_t> w[2];
     };
 
     std::vector<Device> &devs;
@@ -263,6 +278,7 @@ private:
             priors_file.write(text.priors);
             if (to.prior_cov) to.prior_cov->write(text.prior_cov, "cannot write the coverages for the cohort's priors");
             if (to.site_stats) to.site_stats->write(text.site_stats, to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
+            if (to.ld) to.ld->write(text.ld, "cannot write the LD table's words");
         }
     }
 
@@ -274,6 +290,7 @@ private:
         text.per_sample.resize(to.per_sample.size());
         MergedRows rows;
         SiteGeno geno;
+        SiteWords words;
         {
             Timed t_dev("worker: device calls");
             std::lock_guard<std::mutex> device_lock(dev.mu); // (the parsing thread cuts blocks on device 0 meanwhile)
@@ -298,8 +315,9 @@ private:
             if (to.pairs) pair_table(dev, job, text);
             if (to.sample_table) sample_table(dev, job, text.times);
             if (to.site_stats) site_table(dev, job, geno, text.times);
+            if (to.ld) ld_words(dev, job, words, text.times);
         } // the records' text needs no device
-        records_text(job, rows, geno, text);
+        records_text(job, rows, geno, words, text);
         return text;
     }
 
@@ -551,7 +569,24 @@ private:
         }
     }
 
-    void records_text(const Job &job, const MergedRows &rows, const SiteGeno &geno, BatchText &text)
+    void ld_words(Device &dev, Job &job, SiteWords &sw, CallTimes &times)
+    {
+        Timed t_ld("worker: ld words (mg_pack_site_dosage)");
+        for (int w = 0; w < 2; ++w) {
+            Batch &b = w ? job.gen : job.iso;
+            const size_t bn = b.n();
+            if (!bn) continue;
+            sw.w[w].resize(3 * bn);
+            dev.check(mg_pack_site_dosage(dev.ctx, bn, (uint32_t)P, o.haploid, b.g1.data(), b.g2.data(), b.gq.data(), o.use_min_gq, o.min_gq, b.var_allele_off.data(),
+                                          sw.w[w].data()),
+                      "mg_pack_site_dosage");
+            float ms[2] = {0, 0};
+            dev.check(mg_ld_stats(dev.ctx, ms), "mg_ld_stats");
+            times.ld.add(ms, 1);
+        }
+    }
+
+    void records_text(const Job &job, const MergedRows &rows, const SiteGeno &geno, const SiteWords &words, BatchText &text)
     {
         Timed t_text("worker: records' text");
         const Batch &iso = job.iso, &gen = job.gen;
@@ -560,6 +595,11 @@ private:
             const int w = r.isolated ? 0 : 1;
             if (priors_file.f) priors_row(text.priors, r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
             if (tags && to.site_counts) put_site_counts(text.site_counts, r.n_alleles, rows.site_ns[w][r.slot], rows.site_ac[w].data() + r.allele0);
+            if (to.ld) {
+                const std::vector<uint64_t> &sw = words.w[w];
+                const size_t bn = sw.size() / 3;
+                put_ld_words(text.ld, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.ld_cols ? r.prefix.data() : nullptr, site_stats_cols(r.prefix));
+            }
             if (!to.site_stats) continue;
             const uint32_t *het = geno.het[w].data() + r.allele0, *hom = geno.hom[w].data() + r.allele0;
             const size_t cols = site_stats_cols(r.prefix);

@@ -1,6 +1,7 @@
 // cohort_out.hpp -- the host-only half of the outputs of `call --cohort`: the streams a group leaves for the passes behind the last group
-// (the records' site counts, the packed calls, the records' genotype counts), the two paste passes over the groups' blocks of the merged output, and
-// the text of the --pairs, --sample-stats and --site-stats tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp drives this file alone).
+// (the records' site counts, the packed calls, the records' genotype counts, the records' words for the LD table), the two paste passes over the groups'
+// blocks of the merged output, and the text of the --pairs, --sample-stats, --site-stats and --ld tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp, tools/site_table_host_check.cpp
+// and tools/ld_out_host_check.cpp drive this file alone).
 #pragma once
 #include <deque>
 
@@ -308,6 +309,146 @@ template <class Hwe, class Sink> void site_stats_groups(const std::deque<PartFil
         out.clear();
     }
     in.end();
+}
+
+// ---- the LD table (--ld) -------------------------------------------------------------------------------------------------------
+// One line per emitted pair of records (mg_ld_window): A's CHROM, POS and ID, B's POS and ID, N (the samples that contribute in both), R2 to six
+// significant digits and the sign of the covariance.  Lines are in the order of the merged output, by A, then by B.
+inline const char *ld_header() { return "#CHROM\tPOS_A\tID_A\tPOS_B\tID_B\tN\tR2\tSIGN\n"; }
+// Every group -- a cohort of one group too -- leaves per record, in output order, the three u64 words of mg_pack_site_dosage over its planes and the
+// u32 n_alleles; the first group's stream has behind each record a u32 length and that many bytes, the record's first five columns.
+inline void put_ld_words(std::string &out, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t n_alleles, const char *cols, size_t cols_len)
+{
+    const uint64_t w[3] = {w0, w1, w2};
+    out.append((const char *)w, 24);
+    out.append((const char *)&n_alleles, 4);
+    if (!cols) return;
+    const uint32_t len = (uint32_t)cols_len;
+    out.append((const char *)&len, 4);
+    out.append(cols, cols_len);
+}
+inline void ld_row(std::string &out, const std::string &a, const std::string &b, size_t b_pos_at, const mg_ld_pair &p)
+{
+    char num[64];
+    out += a;
+    out += '\t';
+    out.append(b, b_pos_at, std::string::npos);
+    snprintf(num, sizeof num, "\t%u\t%.6g\t%c\n", p.n, p.r2, p.sign > 0 ? '+' : p.sign < 0 ? '-' : '0');
+    out += num;
+}
+// The groups' streams read in step.  The reader holds a run of records: words [record][group][3], the records' CHROM\tPOS\tID, a running contig
+// id that steps whenever the CHROM text changes, and POS parsed.
+struct LdReader {
+    GroupFiles in;
+    size_t G;
+    std::vector<uint64_t> words;
+    std::vector<std::string> cols;
+    std::vector<size_t> pos_at; // where POS starts in cols
+    std::vector<uint32_t> chrom, pos;
+    std::string last_chrom, five;
+    uint32_t chrom_id = 0;
+    bool any = false, ended = false;
+    const char *short_file = "internal: a group's words for the LD table are short";
+    explicit LdReader(const std::deque<PartFile> &files)
+    {
+        in.open(files);
+        G = in.f.size();
+        if (!G) throw std::logic_error("LdReader: no group");
+    }
+    size_t held() const { return cols.size(); }
+    // one more record behind those held; false where the first group's stream ends (every later group's must end there too)
+    bool read_one()
+    {
+        if (ended) return false;
+        const size_t at = words.size();
+        words.resize(at + 3 * G);
+        uint32_t A, a, len;
+        const size_t got = fread(&words[at], 8, 3, in.f[0]);
+        if (got == 0) {
+            char one;
+            for (size_t gi = 1; gi < G; ++gi)
+                if (fread(&one, 1, 1, in.f[gi]) != 0) throw std::runtime_error(short_file);
+            words.resize(at);
+            ended = true;
+            return false;
+        }
+        if (got != 3 || fread(&A, 4, 1, in.f[0]) != 1 || fread(&len, 4, 1, in.f[0]) != 1) throw std::runtime_error(short_file);
+        five.resize(len);
+        if (len && fread(&five[0], 1, len, in.f[0]) != len) throw std::runtime_error(short_file);
+        for (size_t gi = 1; gi < G; ++gi)
+            if (fread(&words[at + 3 * gi], 8, 3, in.f[gi]) != 3 || fread(&a, 4, 1, in.f[gi]) != 1 || a != A) throw std::runtime_error(short_file);
+        size_t tab[3] = {0, 0, 0};
+        for (int t = 0; t < 3; ++t) {
+            tab[t] = five.find('\t', t ? tab[t - 1] + 1 : 0);
+            if (tab[t] == std::string::npos) {
+                if (t < 2) throw std::runtime_error("internal: a record's columns in the LD table's stream are short");
+                tab[t] = five.size();
+            }
+        }
+        if (!any || five.compare(0, tab[0], last_chrom) != 0) {
+            if (any) ++chrom_id;
+            last_chrom.assign(five, 0, tab[0]);
+            any = true;
+        }
+        chrom.push_back(chrom_id);
+        pos.push_back((uint32_t)strtoul(five.c_str() + tab[0] + 1, nullptr, 10));
+        pos_at.push_back(tab[0] + 1);
+        cols.emplace_back(five, 0, tab[2]);
+        return true;
+    }
+    // the first n records leave
+    void drop(size_t n)
+    {
+        words.erase(words.begin(), words.begin() + 3 * G * n);
+        cols.erase(cols.begin(), cols.begin() + n);
+        pos_at.erase(pos_at.begin(), pos_at.begin() + n);
+        chrom.erase(chrom.begin(), chrom.begin() + n);
+        pos.erase(pos.begin(), pos.begin() + n);
+    }
+    // the held records as mg_ld_window takes them: [G][3][held]
+    void sites(std::vector<uint64_t> &out) const
+    {
+        const size_t n = held();
+        out.resize(3 * G * n);
+        for (size_t v = 0; v < n; ++v)
+            for (size_t k = 0; k < 3 * G; ++k) out[k * n + v] = words[v * 3 * G + k];
+    }
+};
+// The pass behind the last group: the header, then the pairs' lines, `chunk` records at a time with a look-ahead of `window` records that become the
+// head of the next chunk.  ld(n_vars, n_first, n_groups, sites, chrom, pos, pairs_out, pairs_cap, row_off_out, n_pairs_out) is mg_ld_window with the
+// run's options, whoever holds the device: it returns MG_OK or MG_ERR_LIMIT (then the buffer grows and it is called once more).  The text goes
+// to sink(data, n).
+template <class Ld, class Sink> void ld_table(const std::deque<PartFile> &files, size_t window, size_t chunk, Ld &&ld, Sink &&sink)
+{
+    LdReader in(files);
+    std::string out = ld_header();
+    std::vector<uint64_t> sites, row_off;
+    std::vector<mg_ld_pair> pairs(1024);
+    if (!chunk || !window) throw std::logic_error("ld_table: an empty chunk or window");
+    for (;;) {
+        while (in.held() < chunk + window && in.read_one()) {}
+        const size_t n = in.held(), n_first = in.ended ? n : chunk;
+        if (n) {
+            in.sites(sites);
+            row_off.assign(n_first + 1, 0);
+            uint64_t needed = 0;
+            int rc = ld(n, n_first, in.G, sites.data(), in.chrom.data(), in.pos.data(), pairs.data(), pairs.size(), row_off.data(), &needed);
+            if (rc == MG_ERR_LIMIT) {
+                pairs.resize(needed);
+                rc = ld(n, n_first, in.G, sites.data(), in.chrom.data(), in.pos.data(), pairs.data(), pairs.size(), row_off.data(), &needed);
+            }
+            if (rc != MG_OK || needed > pairs.size() || row_off[n_first] != needed) throw std::runtime_error("internal: the LD table's pairs do not fit their buffer");
+            for (uint64_t k = 0; k < needed; ++k) {
+                const mg_ld_pair &p = pairs[k];
+                if (p.i >= n_first || p.j >= n || p.j <= p.i) throw std::runtime_error("internal: a pair of the LD table lies outside its chunk");
+                ld_row(out, in.cols[p.i], in.cols[p.j], in.pos_at[p.j], p);
+            }
+        }
+        sink(out.data(), out.size());
+        out.clear();
+        if (in.ended) break;
+        in.drop(n_first);
+    }
 }
 
 // ---- the paste passes over the groups' blocks of the merged output -----------------------------------------------------------------

@@ -120,6 +120,18 @@ const char *USAGE =
     "                                        Hardy-Weinberg proportions) and EXC_HET (the one-sided one for an excess of heterozygotes), both\n"
     "                                        to six significant digits, '.' when N = 0 or with -1.  Counted and tested on the GPU, whatever\n"
     "                                        the grouping; beside -o and/or --merged                                         [this build]\n"
+    "          --ld                          --cohort: PATH receives a tab-separated table of linkage disequilibrium, one line per pair of\n"
+    "                                        nearby biallelic records, in the order of the merged output (by A, then by B): CHROM POS_A ID_A\n"
+    "                                        POS_B ID_B, N (the samples whose cells are called -- --min-gq applies -- in both), R2 (the squared\n"
+    "                                        correlation of the two dosages over those samples, six significant digits) and SIGN (+, - or 0:\n"
+    "                                        the sign of the covariance).  A pair is written when R2 exists (both records vary among the N\n"
+    "                                        samples) and passes the options below.  Counted on the GPU, the same bytes whatever the\n"
+    "                                        grouping; beside -o and/or --merged                                             [this build]\n"
+    "          --ld-window                   --ld: a record is paired with the N records behind it on its contig, 1..1024 (default:64);\n"
+    "                                        the panel's records count, biallelic or not                                     [this build]\n"
+    "          --ld-window-bp                --ld: and with none further away than N bases (default:1000000; 0: no limit)    [this build]\n"
+    "          --ld-min-r2                   --ld: the smallest R2 written, in [0, 1] (default:0.2)                          [this build]\n"
+    "          --ld-min-n                    --ld: the fewest samples an R2 is formed from, 1 or more (default:2)            [this build]\n"
     "          --cohort-priors               --cohort: the allele priors of every record are re-estimated from ALL samples of the cohort\n"
     "                                        before the genotypes are made -- a few EM steps from the panel's AF (or -u's uniform\n"
     "                                        prior), anchored to it -- and every sample is genotyped under the cohort's frequencies.\n"
@@ -184,6 +196,9 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"prior-groups", no_argument, nullptr, 1016},
                                       {"pl", no_argument, nullptr, 1017},             {"pl-cap", required_argument, nullptr, 1018},
                                       {"site-stats", required_argument, nullptr, 1019},
+                                      {"ld", required_argument, nullptr, 1020},       {"ld-window", required_argument, nullptr, 1021},
+                                      {"ld-window-bp", required_argument, nullptr, 1022}, {"ld-min-r2", required_argument, nullptr, 1023},
+                                      {"ld-min-n", required_argument, nullptr, 1024},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -270,6 +285,44 @@ bool parse_arguments(int argc, char **argv, Options &o)
                 die = true;
             }
             break;
+        case 1020:
+            o.ld = optarg;
+            if (o.ld.empty()) {
+                std::cerr << "malva : --ld takes a path\n";
+                die = true;
+            }
+            break;
+        case 1021:
+        case 1022:
+        case 1024: {
+            // (digits only: strtoull would take a sign and wrap)
+            const std::string text = optarg;
+            const unsigned long long most = c == 1021 ? MG_LD_MAX_WINDOW : c == 1022 ? ~0ull : 0xFFFFFFFFull, least = c == 1022 ? 0 : 1;
+            unsigned long long v = 0;
+            bool ok = !text.empty() && text.size() <= 20;
+            for (const char ch : text) {
+                ok = ok && ch >= '0' && ch <= '9' && v <= (~0ull - (ch - '0')) / 10;
+                if (ok) v = v * 10 + (ch - '0');
+            }
+            o.ld_sub = true;
+            if (!ok || v < least || v > most) {
+                std::cerr << "malva : --" << (c == 1021 ? "ld-window takes a whole number 1..1024" : c == 1022 ? "ld-window-bp takes a whole number (0: no limit)" : "ld-min-n takes a whole number 1..4294967295") << "\n";
+                die = true;
+            } else if (c == 1021) o.ld_window = (uint32_t)v;
+            else if (c == 1022) o.ld_window_bp = v;
+            else o.ld_min_n = (uint32_t)v;
+            break;
+        }
+        case 1023: {
+            char *end = nullptr;
+            const double v = strtod(optarg, &end);
+            o.ld_sub = true;
+            if (end == optarg || *end || !(v >= 0.0 && v <= 1.0)) {
+                std::cerr << "malva : --ld-min-r2 takes a number in [0, 1]\n";
+                die = true;
+            } else o.ld_min_r2 = v;
+            break;
+        }
         case 1012: o.priors.on = true; break;
         case 1013:
             if (!parse_prior_iters(optarg, o.priors)) {
@@ -361,6 +414,14 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (!o.cohort && !o.site_stats.empty()) {
         std::cerr << "malva : --site-stats goes with --cohort\n";
+        die = true;
+    }
+    if (!o.cohort && !o.ld.empty()) {
+        std::cerr << "malva : --ld goes with --cohort\n";
+        die = true;
+    }
+    if (o.ld.empty() && o.ld_sub) {
+        std::cerr << "malva : --ld-window, --ld-window-bp, --ld-min-r2 and --ld-min-n go with --ld\n";
         die = true;
     }
     if (const std::string why = check_prior_options(o.priors, o.cohort); !why.empty()) {
@@ -1393,6 +1454,11 @@ int call_main(const Options &o)
         const bool want_site = !o.site_stats.empty();
         std::deque<PartFile> geno_files;
         PartFile site_file;
+        // --ld: every group -- one group too -- leaves its records' words over its planes in PATH.gN.ld.part; the pass behind the last group reads
+        // them in step, forms r2 over all groups on the device and writes the table (PATH.part, renamed at the end)
+        const bool want_ld = !o.ld.empty();
+        std::deque<PartFile> ld_files;
+        PartFile ld_file;
         std::vector<std::string> names;
         for (const auto &sm : samples) names.push_back(sm.name);
         const bool merged_stdout = o.merged == "-";
@@ -1512,6 +1578,7 @@ int call_main(const Options &o)
                     to.site_stats = &site_file;
                 }
             }
+            if (want_ld) to.ld = &open_scratch(ld_files, o.ld, ".ld.part"), to.ld_cols = s0 == 0;
             for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
                 to.per_sample.emplace_back();
                 to.per_sample.back().open(o.out_dir + "/" + samples[s0 + i].name + ".vcf");
@@ -1540,6 +1607,7 @@ int call_main(const Options &o)
                 for (size_t j = i + 1; j < g; ++j) std::copy_n(&pairs_run.counts[(i * g + j) * 9], 9, &pair_table[((s0 + i) * S + s0 + j) * 9]);
             if (to.site_counts) to.site_counts->close("cannot write the merged output's counts");
             if (to.site_stats) to.site_stats->close(to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
+            if (to.ld) to.ld->close("cannot write the LD table's words");
             if (to.merged) {
                 if (bcf_out && bcf_bgzf && merged_direct) to.merged->write(bgzf_eof(), "cannot write the merged output");
                 to.merged->close("cannot write the merged output");
@@ -1629,6 +1697,26 @@ int call_main(const Options &o)
             geno_files.clear(); // (the groups' streams go before the table takes its name)
         }
         if (want_site) site_file.finish("cannot write the per-record table");
+        if (want_ld) {
+            Timed t("cohort: ld pass");
+            ld_file.open(o.ld);
+            ld_table(
+                ld_files, o.ld_window, geno_batch_records(65536),
+                [&](size_t n_vars, size_t n_first, size_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, mg_ld_pair *pairs, size_t cap,
+                    uint64_t *row_off, uint64_t *needed) {
+                    const int rc = mg_ld_window(dev.ctx, n_vars, n_first, (uint32_t)n_groups, sites, chrom, pos, o.ld_window, o.ld_window_bp, o.ld_min_n, o.ld_min_r2, pairs, cap,
+                                                row_off, needed);
+                    if (rc != MG_ERR_LIMIT) dev.check(rc, "mg_ld_window");
+                    float ms[2] = {0, 0};
+                    dev.check(mg_ld_stats(dev.ctx, ms), "mg_ld_stats");
+                    times.ld.ms[1] += ms[1];
+                    ++times.ld.calls[1];
+                    return rc;
+                },
+                [&](const char *data, size_t n) { ld_file.write(data, n, "cannot write the LD table"); });
+            ld_files.clear(); // (the groups' streams go before the table takes its name)
+            ld_file.finish("cannot write the LD table");
+        }
         priors_file.finish();
         times.add_to_timers();
         std::cerr << times.report();

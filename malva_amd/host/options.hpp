@@ -32,6 +32,12 @@ struct Options { // argument_parser.hpp:51-66
     std::string pairs;      // --pairs: the table of pairwise genotype sharing
     std::string sample_stats; // --sample-stats: the per-sample QC table
     std::string site_stats; // --site-stats: the per-record QC table
+    std::string ld;         // --ld: the table of r2 between nearby records
+    bool ld_sub = false;    // one of --ld's sub-options was given
+    uint32_t ld_window = 64;        // --ld-window: the records behind a record that are its partners (1..MG_LD_MAX_WINDOW)
+    uint64_t ld_window_bp = 1000000; // --ld-window-bp: and no further away than this (0: no limit)
+    double ld_min_r2 = 0.2;         // --ld-min-r2: the smallest r2 written
+    uint32_t ld_min_n = 2;          // --ld-min-n: the fewest samples a pair's r2 is formed from
     PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
 };
 

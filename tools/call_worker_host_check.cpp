@@ -275,6 +275,16 @@ int mg_hwe_exact(mg_ctx *c, size_t n_items, const uint32_t *n, const uint32_t *h
     return MG_OK;
 }
 int mg_hwe_stats(mg_ctx *c, float *ms) { return stats(c, "mg_hwe_stats", ms, {14, 15}); }
+// every word is written: record v's are v, planes and use_mask
+int mg_pack_site_dosage(mg_ctx *c, size_t n, uint32_t planes, int, const int32_t *gt1, const int32_t *, const int32_t *, int use_mask, int32_t, const uint32_t *vao,
+                        uint64_t *sites_out)
+{
+    touch(gt1, planes * n), touch(vao, n + 1);
+    say(c, "mg_pack_site_dosage n=%zu planes=%u mask=%d", n, planes, use_mask);
+    for (size_t v = 0; v < n; ++v) sites_out[v] = v, sites_out[n + v] = planes, sites_out[2 * n + v] = (uint64_t)use_mask;
+    return MG_OK;
+}
+int mg_ld_stats(mg_ctx *c, float *ms) { return stats(c, "mg_ld_stats", ms, {16, 17}); }
 } // extern "C"
 
 // ---- a pass over hand-made batches on fake devices ------------------------------------------------------------------------------------------
