@@ -61,16 +61,17 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
 
-# the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs (--site-stats and --ld in programs of their own) and of the panel batches and their text under
+# the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs (--site-stats, --ld and --ibd in programs of their own) and of the panel batches and their text under
 # AddressSanitizer and UBSan: stand-alone programs, run on the CPU.  The last one is a batch's device calls and the pipeline around them
 # (host/call_worker.hpp) against an ABI of its own, without libmalva_hip; it runs a second time under ThreadSanitizer
-sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/site_table_host_check bin/ld_out_host_check \
+sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/site_table_host_check bin/ld_out_host_check bin/ibd_out_host_check \
                bin/call_batch_host_check bin/call_worker_host_check bin/call_worker_host_check_tsan
 	bin/cohort_priors_host_check bin
 	bin/cohort_priors_groups_host_check bin
 	bin/cohort_out_host_check bin
 	bin/site_table_host_check bin
 	bin/ld_out_host_check bin
+	bin/ibd_out_host_check bin
 	bin/call_batch_host_check
 	bin/call_worker_host_check bin
 	bin/call_worker_host_check_tsan bin
@@ -87,6 +88,9 @@ bin/site_table_host_check: tools/site_table_host_check.cpp malva_amd/host/cohort
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
 bin/ld_out_host_check: tools/ld_out_host_check.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
+bin/ibd_out_host_check: tools/ibd_out_host_check.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
 bin/call_batch_host_check: tools/call_batch_host_check.cpp tools/host_check_util.hpp malva_amd/host/panel_batch.hpp malva_amd/host/call_text.hpp malva_amd/host/block.hpp \

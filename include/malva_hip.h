@@ -753,6 +753,49 @@ int mg_ld_window_device(mg_ctx *ctx, size_t n_vars, size_t n_first, uint32_t n_g
                         uint64_t max_bp, uint32_t min_n, double min_r2, void *d_pairs_out, size_t pairs_cap, void *d_row_off_out, uint64_t *n_pairs_out);
 int mg_ld_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- IBS0-free segments per pair of samples ------------------------------------------
+ * Where along the records two samples share genotypes.  There is no reference call to cite: the reference genotypes one individual
+ * per run.  The cells CONTRIBUTE, with dosage 0, 1 or 2, exactly as for mg_pack_dosage / mg_pack_site_dosage.
+ * mg_sites_to_planes: sites is uint64_t [n_groups][3][n_vars], the groups' mg_pack_site_dosage outputs over the same records, as
+ * mg_ld_window takes them (n_groups 1..MG_LD_MAX_GROUPS).  planes_out is uint64_t [64 * n_groups][3][W], W = ceil(n_vars / 64), laid
+ * out as mg_pack_dosage's: bit v & 63 of word v >> 6 of plane 64 g + p, dosage d, equals bit p of sites[g][d][v] -- the same cells in
+ * the records' order of `sites`, whatever the batches were.  Every word is written, the bits at and beyond n_vars are 0; n_vars == 0
+ * is legal and writes nothing.  A NULL sites or planes_out with n_vars > 0, n_groups out of range: MG_ERR_ARG.
+ * The segments.  For a pair of samples a < b (indexes over all groups, sample 64 g + p is bit p of group g) every record is DISC (both
+ * cells contribute, dosages {0, 2}), CONC (both contribute, not DISC; IBS2 when the dosages are equal) or NEUT.  The pair's state is open
+ * or closed, chrom, start_pos, end_pos, n, ibs2.  At record v, in this order: an open state whose chrom differs from chrom[v] closes; DISC
+ * closes an open state; CONC opens a closed state (chrom[v], start_pos = pos[v], n = ibs2 = 0), then end_pos = pos[v], n += 1, ibs2 += 1
+ * when IBS2; NEUT does nothing.  Closing emits the segment when n >= min_records and end_pos - start_pos >= min_bp (the difference
+ * formed in signed 64-bit).
+ * mg_ibd_begin: n_samples is 2..MG_IBD_MAX_SAMPLES, min_records at least 1, min_bp at most 2^63 - 1, else MG_ERR_ARG.  It allocates the
+ * device-resident state of all n (n - 1) / 2 pairs, five uint32_t per pair (2.7 GB at the limit), all closed; MG_ERR_NOMEM when that does
+ * not fit.  A second begin discards the first.  mg_ibd_end frees the state (and is legal without one).
+ * mg_ibd_step walks the next n_vars records: sites as above with n_groups == ceil(n_samples / 64) (else MG_ERR_ARG), chrom and pos
+ * uint32_t [n_vars]; a NULL among them with n_vars > 0, a NULL n_segs_out, a NULL segs_out with segs_cap > 0: MG_ERR_ARG.  Without a begin:
+ * MG_ERR_STATE.  Record 0's chrom is compared with the last record of the step before.  flush != 0 closes every open state behind the
+ * last record; n_vars == 0 is legal with and without it.  The segments closed in this step come out ordered by a, then b, then along the
+ * records.  *n_segs_out (a HOST pointer in both forms) always receives the number needed; when that exceeds segs_cap the call returns
+ * MG_ERR_LIMIT, writes nothing to segs_out and does NOT advance the state: the same call with a larger buffer is correct.
+ * Working memory of a step, from the context: the planes of its records (24 n_groups bytes per record) and 12 bytes per pair for
+ * the segment counts and their offsets.
+ * The host forms synchronise.  The device forms take device pointers; mg_sites_to_planes_device is asynchronous on the context's stream,
+ * mg_ibd_step_device waits for the total between its length pass and its write pass.
+ * mg_ibd_stats (waits): ms_out[2], device milliseconds of the most recent transpose (a step's own included) and of the most recent step
+ * (everything it put on the stream); 0 for a kind not called yet, MG_ERR_STATE when neither was. */
+#define MG_IBD_MAX_SAMPLES 16384
+typedef struct mg_ibd_seg {
+    uint32_t a, b, chrom, start_pos, end_pos, n, ibs2, zero;
+} mg_ibd_seg; /* 32 bytes */
+int mg_sites_to_planes(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const uint64_t *sites, uint64_t *planes_out);
+int mg_sites_to_planes_device(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const void *d_sites, void *d_planes_out);
+int mg_ibd_begin(mg_ctx *ctx, uint32_t n_samples, uint32_t min_records, uint64_t min_bp);
+int mg_ibd_step(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, int flush, mg_ibd_seg *segs_out,
+                size_t segs_cap, uint64_t *n_segs_out);
+int mg_ibd_step_device(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const void *d_sites, const void *d_chrom, const void *d_pos, int flush, void *d_segs_out,
+                       size_t segs_cap, uint64_t *n_segs_out);
+int mg_ibd_end(mg_ctx *ctx);
+int mg_ibd_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- allele priors re-estimated from the cohort -------------------------------------
  * mg_genotype_cohort: the batch's allele frequencies are re-estimated from all of its planes (a few EM steps from the panel's
  * priors, anchored to them), then every cell is genotyped under the result.  The reference genotypes one individual and has no

@@ -22,6 +22,8 @@ STREAM_DEFAULT = 1          # MG_STREAM_DEFAULT: HIP's legacy default stream (a 
 COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 COMM_ID_BYTES = 128
 LD_MAX_GROUPS, LD_MAX_WINDOW = 256, 1024   # MG_LD_MAX_GROUPS, MG_LD_MAX_WINDOW
+IBD_MAX_SAMPLES = 16384     # MG_IBD_MAX_SAMPLES
+IBD_SEG = np.dtype([(f, np.uint32) for f in ("a", "b", "chrom", "start_pos", "end_pos", "n", "ibs2", "zero")])   # mg_ibd_seg, 32 bytes
 LD_PAIR = np.dtype([("i", np.uint32), ("j", np.uint32), ("n", np.uint32), ("sign", np.int32), ("r2", np.float64)])   # mg_ld_pair, 24 bytes
 SAMPLE_SLOTS = 32           # MG_SAMPLE_SLOTS: the counters per plane of mg_sample_counts (MG_SS_*)
 GT_NORMAL, GT_OVERCOV, GT_SINGLE, GT_NOCOV = 0, 1, 2, 3
@@ -139,6 +141,13 @@ def lib():
         "mg_ld_window": [vp, sz, sz, u32, vp, vp, vp, u32, C.c_uint64, u32, C.c_double, vp, sz, vp, vp],
         "mg_ld_window_device": [vp, sz, sz, u32, vp, vp, vp, u32, C.c_uint64, u32, C.c_double, vp, sz, vp, vp],
         "mg_ld_stats": [vp, vp],
+        "mg_sites_to_planes": [vp, sz, u32, vp, vp],
+        "mg_sites_to_planes_device": [vp, sz, u32, vp, vp],
+        "mg_ibd_begin": [vp, u32, u32, C.c_uint64],
+        "mg_ibd_step": [vp, sz, u32, vp, vp, vp, it, vp, sz, vp],
+        "mg_ibd_step_device": [vp, sz, u32, vp, vp, vp, it, vp, sz, vp],
+        "mg_ibd_end": [vp],
+        "mg_ibd_stats": [vp, vp],
         "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_cohort_prior_stats": [vp, vp],
@@ -216,7 +225,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_format_site_info_device", "mg_site_stats", "mg_pack_dosage", "mg_pack_dosage_device", "mg_pair_counts", "mg_pair_counts_device",
             "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats",
             "mg_site_geno_counts", "mg_site_geno_counts_device", "mg_hwe_exact", "mg_hwe_exact_device", "mg_hwe_stats",
-            "mg_pack_site_dosage", "mg_pack_site_dosage_device", "mg_ld_window", "mg_ld_window_device", "mg_ld_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_pack_site_dosage", "mg_pack_site_dosage_device", "mg_ld_window", "mg_ld_window_device", "mg_ld_stats",
+            "mg_sites_to_planes", "mg_sites_to_planes_device", "mg_ibd_begin", "mg_ibd_step", "mg_ibd_step_device", "mg_ibd_end", "mg_ibd_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -1038,6 +1048,71 @@ class Context:
         """-> device ms of the most recent pack_site_dosage and of the most recent ld_window"""
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_ld_stats(self.h, ms))
+        return float(ms[0]), float(ms[1])
+
+    # IBS0-free segments per pair of samples
+    def sites_to_planes(self, sites, out=None):
+        """sites: uint64 [groups, 3, n_vars] (the groups' pack_site_dosage outputs) -> uint64 [64 * groups, 3, W], W = (n_vars + 63) // 64, laid
+        out as pack_dosage's: bit v & 63 of word v >> 6 of [64 g + p, d] is bit p of sites[g, d, v] (mg_sites_to_planes in
+        include/malva_hip.h).  out: the array to fill (every word is overwritten)."""
+        S = np.ascontiguousarray(sites, dtype=np.uint64)
+        groups, three, n = S.shape
+        assert three == 3
+        if out is None:
+            out = np.zeros((64 * groups, 3, (n + 63) // 64), dtype=np.uint64)
+        assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == (64 * groups, 3, (n + 63) // 64)
+        self._ck(self._L.mg_sites_to_planes(self.h, n, groups, _p(S), _p(out)))
+        return out
+
+    def sites_to_planes_device(self, n_vars, groups, d_sites, d_planes_out):
+        """the same from a device pointer into a device buffer, asynchronous on the context's stream"""
+        self._ck(self._L.mg_sites_to_planes_device(self.h, n_vars, groups, C.c_void_p(d_sites), C.c_void_p(d_planes_out)))
+
+    def ibd_begin(self, n_samples, min_records=1, min_bp=0):
+        """the state of all pairs of n_samples samples, every pair closed (mg_ibd_begin); a second begin discards the first"""
+        self._ck(self._L.mg_ibd_begin(self.h, int(n_samples), int(min_records), int(min_bp)))
+
+    def ibd_step(self, sites, chrom, pos, flush=False, segs_cap=None, segs=None):
+        """the next records: sites uint64 [groups, 3, n_vars], chrom / pos uint32 [n_vars] -> the segments closed in this step, a structured
+        array (IBD_SEG) ordered by (a, b, start) -- mg_ibd_step in include/malva_hip.h.  segs_cap None: the call is repeated with the buffer it
+        asked for; a given one that is too small raises MalvaError(MG_ERR_LIMIT) with .needed set, and the state has not advanced.  segs: the
+        buffer to use (at least segs_cap entries)."""
+        S = np.ascontiguousarray(sites, dtype=np.uint64)
+        ch, po = (np.ascontiguousarray(x, dtype=np.uint32) for x in (chrom, pos))
+        groups, three, n = S.shape
+        assert three == 3 and ch.shape == (n,) and po.shape == (n,)
+        need = C.c_uint64(0)
+
+        def call(cap, buf):
+            if buf is None:
+                buf = np.zeros(max(cap, 1), dtype=IBD_SEG)
+            assert buf.dtype == IBD_SEG and buf.flags.c_contiguous and len(buf) >= cap
+            return self._L.mg_ibd_step(self.h, n, groups, _p(S), _p(ch), _p(po), int(bool(flush)), _p(buf) if cap else None, cap, C.byref(need)), buf
+        rc, buf = call(0 if segs_cap is None else int(segs_cap), segs)
+        if rc == -5 and segs_cap is None and need.value:
+            rc, buf = call(need.value, None)
+        if rc != 0:
+            e = MalvaError(rc, self._L.mg_last_error(self.h).decode())
+            e.needed = need.value
+            raise e
+        return buf[:need.value]
+
+    def ibd_step_device(self, n_vars, groups, d_sites, d_chrom, d_pos, flush, d_segs, segs_cap):
+        """the same from device pointers into a device buffer -> (return code, segments needed); MG_ERR_LIMIT (-5) is returned, not raised"""
+        v = C.c_void_p
+        need = C.c_uint64(0)
+        rc = self._L.mg_ibd_step_device(self.h, n_vars, groups, v(d_sites), v(d_chrom), v(d_pos), int(bool(flush)), v(d_segs), segs_cap, C.byref(need))
+        if rc not in (0, -5):
+            self._ck(rc)
+        return rc, need.value
+
+    def ibd_end(self):
+        self._ck(self._L.mg_ibd_end(self.h))
+
+    def ibd_stats(self):
+        """-> device ms of the most recent transpose and of the most recent ibd_step"""
+        ms = (C.c_float * 2)()
+        self._ck(self._L.mg_ibd_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
 
     # allele priors re-estimated from the planes of a batch, and the cells genotyped under them

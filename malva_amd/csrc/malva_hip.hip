@@ -44,6 +44,7 @@ constexpr int TPB = 256;
 #include "sample_kernels.h"
 #include "site_geno_kernels.h"
 #include "ld_kernels.h"
+#include "ibd_kernels.h"
 #include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
 #include "pl_kernels.h"
@@ -91,7 +92,7 @@ struct Timer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool valid = false;
 };
-enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_GENO, TM_HWE, TM_LD_PACK, TM_LD, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device, mg_site_geno_counts*, mg_hwe_exact*, mg_pack_site_dosage*, mg_ld_window* (length pass, scan, write pass)
+enum { TM_FMT, TM_INFO, TM_BCF, TM_SITE, TM_PACK, TM_PAIR, TM_SAMPLE, TM_PRIOR, TM_ESTIMATE, TM_PL, TM_BLOCKS, TM_COHORT, TM_GENO, TM_HWE, TM_LD_PACK, TM_LD, TM_IBD_TR, TM_IBD, TM_COUNT }; // mg_format_calls*, mg_format_site_info*, mg_encode_calls_bcf*, mg_site_counts*, mg_pack_dosage*, mg_pair_counts*, mg_sample_counts*, mg_genotype_cohort*, mg_estimate_priors*, mg_phred_likelihoods*, mg_cover_blocks_device, mg_cover_blocks_cohort_device, mg_site_geno_counts*, mg_hwe_exact*, mg_pack_site_dosage*, mg_ld_window* (length pass, scan, write pass), mg_sites_to_planes*, mg_ibd_step*
 enum { ENC_COUNT = TM_BCF + 1 };
 // what an encoder's device form keeps from its length pass to its write pass: the rows' lengths (u32), the meta block (the total, "a row
 // beyond 32 bits"), and (mg_encode_calls_bcf*) the records' type codes
@@ -107,6 +108,7 @@ enum {
     ST_PL,                                                                                                 // mg_phred_likelihoods' result, the *_pl encoders' input
     ST_SG_N, ST_SG_HET, ST_SG_HOM, ST_HWE, ST_EXC_HET,                                                     // mg_site_geno_counts' tables, mg_hwe_exact's items and results
     ST_LD_WORDS, ST_LD_SITES, ST_LD_CHROM, ST_LD_POS, ST_LD_PAIRS, ST_LD_ROW_OFF,                          // mg_pack_site_dosage's words; mg_ld_window's tables and pairs
+    ST_IBD_SITES, ST_IBD_PLANES, ST_IBD_CHROM, ST_IBD_POS, ST_IBD_SEGS,                                    // mg_sites_to_planes' and mg_ibd_step's tables and segments
     ST_COUNT
 };
 
@@ -174,8 +176,15 @@ struct mg_ctx {
     // each stats call reports the latest call of its own kinds, hence a timer per kind: the encoders' four events, the counting calls' two;
     // mg_cover_blocks_device: before / after the preparation, the lone kernels, the enumerating kernel; mg_cover_blocks_cohort_device: start,
     // after tier 1, after the planes' tiers 2-3
-    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}, {2}, {2}, {2}, {4}};
+    Timer tm[TM_COUNT] = {{4}, {4}, {4}, {2}, {2}, {2}, {2}, {2}, {2}, {2}, {4}, {3}, {2}, {2}, {2}, {4}, {2}, {2}};
     Scratch s_enc[ENC_COUNT][ES_COUNT], stage[ST_COUNT];
+    // mg_ibd_begin .. mg_ibd_end: the pairs' state, five u32 arrays [n_pairs] and behind them the last record's chrom id (ibd_kernels.h);
+    // s_ibd: a step's planes, start words, segment counts (u32), offsets (u64) and the meta block (the total)
+    u32 *ibd_state = nullptr;
+    u64 ibd_pairs = 0;
+    u32 ibd_samples = 0, ibd_min_records = 0;
+    long long ibd_min_bp = 0;
+    Scratch s_ibd[5];
     Scratch s_ld[2]; // mg_ld_window_device, from its length pass to its write pass: the records' pair counts (u32), the meta block (the total)
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -812,6 +821,8 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
         for (Scratch &q : enc) hipFree(q.p);
     for (Scratch &q : c->stage) hipFree(q.p);
     for (Scratch &q : c->s_ld) hipFree(q.p);
+    for (Scratch &q : c->s_ibd) hipFree(q.p);
+    hipFree(c->ibd_state);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -3893,6 +3904,175 @@ MG_EXPORT int mg_ld_stats(mg_ctx *c, float *ms_out)
     TRY(timer_read(c, c->tm[TM_LD], passes));
     ms_out[1] = passes[0] + passes[1] + passes[2];
     return MG_OK;
+}
+
+// ---- IBS0-free segments per pair of samples (ibd_kernels.h) ---------------------------------------------------------------------------
+namespace {
+int check_sites_to_planes(mg_ctx *c, size_t n_vars, uint32_t n_groups, const void *sites, const void *planes_out)
+{
+    if (n_groups < 1 || n_groups > MG_LD_MAX_GROUPS) return fail(c, MG_ERR_ARG, "mg_sites_to_planes: n_groups is 1..%d", MG_LD_MAX_GROUPS);
+    if (n_vars && (!sites || !planes_out)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_sites_to_planes: more than 2^32 - 1 records in one call");
+    return MG_OK;
+}
+int check_ibd_step(mg_ctx *c, size_t n_vars, uint32_t n_groups, const void *sites, const void *chrom, const void *pos, const void *segs_out, size_t segs_cap,
+                   const uint64_t *n_segs_out)
+{
+    if (!c->ibd_state) return fail(c, MG_ERR_STATE, "mg_ibd_step: no mg_ibd_begin yet");
+    if (n_groups != (c->ibd_samples + 63) / 64) return fail(c, MG_ERR_ARG, "mg_ibd_step: n_groups is ceil(n_samples / 64) = %u", (c->ibd_samples + 63) / 64);
+    if (!n_segs_out || (!segs_out && segs_cap) || (n_vars && (!sites || !chrom || !pos))) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_ibd_step: more than 2^32 - 1 records in one call");
+    return MG_OK;
+}
+void ibd_drop(mg_ctx *c)
+{
+    if (c->ibd_state) hipFree(c->ibd_state);
+    c->ibd_state = nullptr;
+    c->ibd_pairs = 0;
+    c->ibd_samples = 0;
+}
+} // namespace
+
+MG_EXPORT int mg_sites_to_planes_device(mg_ctx *c, size_t n_vars, uint32_t n_groups, const void *d_sites, void *d_planes_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_sites_to_planes(c, n_vars, n_groups, d_sites, d_planes_out));
+    TRY(timer_begin(c, c->tm[TM_IBD_TR]));
+    if (n_vars) {
+        const u64 n_words = ((u64)n_vars + 63) / 64;
+        hipLaunchKernelGGL(sites_to_planes_kernel, dim3((unsigned)((n_words + IBD_TR_WORDS - 1) / IBD_TR_WORDS), 3, n_groups), dim3(IBD_TR_TPB), 0, c->stream,
+                           (const unsigned long long *)d_sites, (u64)n_vars, n_words, (unsigned long long *)d_planes_out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return timer_mark(c, c->tm[TM_IBD_TR], 1);
+}
+
+MG_EXPORT int mg_sites_to_planes(mg_ctx *c, size_t n_vars, uint32_t n_groups, const uint64_t *sites, uint64_t *planes_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_sites_to_planes(c, n_vars, n_groups, sites, planes_out));
+    const size_t in_bytes = 8 * (size_t)n_groups * 3 * n_vars, out_bytes = 8 * 64 * (size_t)n_groups * 3 * ((n_vars + 63) / 64);
+    void *d_sites, *d_planes;
+    TRY(upload(c, c->stage[ST_IBD_SITES], sites, in_bytes, &d_sites));
+    TRY(scratch(c, c->stage[ST_IBD_PLANES], out_bytes ? out_bytes : 1, &d_planes));
+    TRY(mg_sites_to_planes_device(c, n_vars, n_groups, d_sites, d_planes));
+    if (out_bytes) HIP_TRY(c, hipMemcpyAsync(planes_out, d_planes, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_ibd_begin(mg_ctx *c, uint32_t n_samples, uint32_t min_records, uint64_t min_bp)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n_samples < 2 || n_samples > MG_IBD_MAX_SAMPLES) return fail(c, MG_ERR_ARG, "mg_ibd_begin: n_samples is 2..%d", MG_IBD_MAX_SAMPLES);
+    if (min_records < 1) return fail(c, MG_ERR_ARG, "mg_ibd_begin: min_records is at least 1");
+    if (min_bp > (uint64_t)INT64_MAX) return fail(c, MG_ERR_ARG, "mg_ibd_begin: min_bp is at most 2^63 - 1");
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (a step of the state that goes may still run)
+    ibd_drop(c);
+    const u64 n_pairs = (u64)n_samples * (n_samples - 1) / 2;
+    const size_t bytes = 4 * IBD_FIELDS * n_pairs + 4; // every pair closed (n == 0); the last chrom id, which no closed pair asks for
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MG_ERR_NOMEM, "mg_ibd_begin: the state of %llu pairs (%zu bytes) does not fit", (unsigned long long)n_pairs, bytes);
+    }
+    c->ibd_state = (u32 *)p;
+    c->ibd_pairs = n_pairs;
+    c->ibd_samples = n_samples;
+    c->ibd_min_records = min_records;
+    c->ibd_min_bp = (long long)min_bp;
+    HIP_TRY(c, hipMemsetAsync(p, 0, bytes, c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_ibd_end(mg_ctx *c)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ibd_drop(c);
+    return MG_OK;
+}
+
+// the transpose and the start words; a length pass, the scan of the pairs' counts, the total read back; then, when the buffer holds it,
+// the write pass, which also stores the state, and the last record's chrom id (ibd_kernels.h)
+MG_EXPORT int mg_ibd_step_device(mg_ctx *c, size_t n_vars, uint32_t n_groups, const void *d_sites, const void *d_chrom, const void *d_pos, int flush, void *d_segs_out,
+                                 size_t segs_cap, uint64_t *n_segs_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_ibd_step(c, n_vars, n_groups, d_sites, d_chrom, d_pos, d_segs_out, segs_cap, n_segs_out));
+    Timer &t = c->tm[TM_IBD];
+    TRY(timer_begin(c, t));
+    *n_segs_out = 0;
+    if (!n_vars && !flush) return timer_mark(c, t, 1);
+    const u64 n_words = ((u64)n_vars + 63) / 64, n_pairs = c->ibd_pairs;
+    u32 *d_last = c->ibd_state + IBD_FIELDS * n_pairs;
+    void *d_planes = nullptr, *d_starts = nullptr, *d_len, *d_off, *d_meta, *part;
+    if (n_vars) {
+        TRY(scratch(c, c->s_ibd[0], 8 * 64 * (size_t)n_groups * 3 * n_words, &d_planes));
+        TRY(scratch(c, c->s_ibd[1], 8 * n_words, &d_starts));
+        TRY(mg_sites_to_planes_device(c, n_vars, n_groups, d_sites, d_planes));
+        hipLaunchKernelGGL(ibd_starts_kernel, dim3((unsigned)((n_words + 3) / 4)), dim3(256), 0, c->stream, (const u32 *)d_chrom, (u64)n_vars, n_words,
+                           (const u32 *)d_last, (unsigned long long *)d_starts);
+        HIP_TRY(c, hipGetLastError());
+    }
+    TRY(scratch(c, c->s_ibd[2], 4 * n_pairs, &d_len));
+    TRY(scratch(c, c->s_ibd[3], 8 * (n_pairs + 1), &d_off));
+    TRY(scratch(c, c->s_ibd[4], 16, &d_meta));
+    const u64 n_part = (n_pairs + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    HIP_TRY(c, hipMemsetAsync(d_meta, 0, 16, c->stream));
+    const IbdArgs a{(u64)n_vars, n_words, n_pairs, c->ibd_samples, (const unsigned long long *)d_planes, (const unsigned long long *)d_starts, (const u32 *)d_chrom,
+                    (const u32 *)d_pos, c->ibd_state, c->ibd_min_records, c->ibd_min_bp, flush != 0};
+    const unsigned tiles = (c->ibd_samples + PAIR_TILE - 1) / PAIR_TILE;
+    hipLaunchKernelGGL(ibd_walk_kernel<false>, dim3(tiles, tiles), dim3(PAIR_TPB), 0, c->stream, a, (u32 *)d_len, (const unsigned long long *)nullptr, (IbdSeg *)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    fmt_scan(c, d_len, n_pairs, n_part, part, d_off, (unsigned long long *)d_meta);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_segs_out = total;
+    if (total > segs_cap) {
+        TRY(timer_mark(c, t, 1));
+        return fail(c, MG_ERR_LIMIT, "mg_ibd_step: %llu segments, the buffer holds %llu", total, (unsigned long long)segs_cap);
+    }
+    hipLaunchKernelGGL(ibd_walk_kernel<true>, dim3(tiles, tiles), dim3(PAIR_TPB), 0, c->stream, a, (u32 *)nullptr, (const unsigned long long *)d_off, (IbdSeg *)d_segs_out);
+    HIP_TRY(c, hipGetLastError());
+    if (n_vars) HIP_TRY(c, hipMemcpyAsync(d_last, (const u32 *)d_chrom + (n_vars - 1), 4, hipMemcpyDeviceToDevice, c->stream));
+    return timer_mark(c, t, 1);
+}
+
+MG_EXPORT int mg_ibd_step(mg_ctx *c, size_t n_vars, uint32_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, int flush, mg_ibd_seg *segs_out,
+                          size_t segs_cap, uint64_t *n_segs_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_ibd_step(c, n_vars, n_groups, sites, chrom, pos, segs_out, segs_cap, n_segs_out));
+    void *d_sites, *d_chrom, *d_pos, *d_segs;
+    TRY(upload(c, c->stage[ST_IBD_SITES], sites, 8 * (size_t)n_groups * 3 * n_vars, &d_sites));
+    TRY(upload(c, c->stage[ST_IBD_CHROM], chrom, 4 * n_vars, &d_chrom));
+    TRY(upload(c, c->stage[ST_IBD_POS], pos, 4 * n_vars, &d_pos));
+    TRY(scratch(c, c->stage[ST_IBD_SEGS], segs_cap ? sizeof(mg_ibd_seg) * segs_cap : 1, &d_segs));
+    TRY(mg_ibd_step_device(c, n_vars, n_groups, d_sites, d_chrom, d_pos, flush, d_segs, segs_cap, n_segs_out));
+    if (*n_segs_out) HIP_TRY(c, hipMemcpyAsync(segs_out, d_segs, sizeof(mg_ibd_seg) * *n_segs_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds (waits for them): ms_out[0] the most recent transpose, [1] the most recent step; 0 where there was none
+MG_EXPORT int mg_ibd_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = ms_out[1] = 0.f; // (also where it fails)
+    if (!c->tm[TM_IBD_TR].valid && !c->tm[TM_IBD].valid) return fail(c, MG_ERR_STATE, "no mg_sites_to_planes or mg_ibd_step yet");
+    TRY(timer_read(c, c->tm[TM_IBD_TR], &ms_out[0]));
+    return timer_read(c, c->tm[TM_IBD], &ms_out[1]);
 }
 
 // ---- allele priors re-estimated from the planes of a batch (cohort_prior_kernels.h) ------------------------------------------------------

@@ -1,7 +1,7 @@
 // cohort_out.hpp -- the host-only half of the outputs of `call --cohort`: the streams a group leaves for the passes behind the last group
-// (the records' site counts, the packed calls, the records' genotype counts, the records' words for the LD table), the two paste passes over the groups'
-// blocks of the merged output, and the text of the --pairs, --sample-stats, --site-stats and --ld tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp, tools/site_table_host_check.cpp
-// and tools/ld_out_host_check.cpp drive this file alone).
+// (the records' site counts, the packed calls, the records' genotype counts, the records' words for the LD and IBD tables), the two paste passes over the groups'
+// blocks of the merged output, and the text of the --pairs, --sample-stats, --site-stats, --ld and --ibd tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp, tools/site_table_host_check.cpp
+// tools/ld_out_host_check.cpp and tools/ibd_out_host_check.cpp drive this file alone).
 #pragma once
 #include <deque>
 
@@ -449,6 +449,95 @@ template <class Ld, class Sink> void ld_table(const std::deque<PartFile> &files,
         if (in.ended) break;
         in.drop(n_first);
     }
+}
+
+// ---- the IBD table (--ibd) ------------------------------------------------------------------------------------------------------
+// One line per IBS0-free segment of a pair of samples (mg_ibd_step): the two names, CHROM, START, END, LENGTH = END - START, N and IBS2.  Lines are
+// ordered by pair -- A, then B, in the manifest's order -- and along the merged output.
+inline const char *ibd_header() { return "#A\tB\tCHROM\tSTART\tEND\tLENGTH\tN\tIBS2\n"; }
+inline void ibd_row(std::string &out, const std::string &a, const std::string &b, const std::string &chrom, const mg_ibd_seg &s)
+{
+    char num[128];
+    out += a;
+    out += '\t';
+    out += b;
+    out += '\t';
+    out += chrom;
+    snprintf(num, sizeof num, "\t%u\t%u\t%lld\t%u\t%u\n", s.start_pos, s.end_pos, (long long)s.end_pos - (long long)s.start_pos, s.n, s.ibs2);
+    out += num;
+}
+// The records held by an LdReader over groups of group_sizes[g] samples (bits 0 .. size - 1 of a group's words) as mg_ibd_step takes them: the
+// cohort's samples side by side, sample s in bit s & 63 of word s >> 6, [ceil(S / 64)][3][held] -- whatever the grouping was.
+inline void ibd_cohort_sites(const LdReader &in, const std::vector<size_t> &group_sizes, std::vector<uint64_t> &out)
+{
+    size_t S = 0;
+    for (const size_t g : group_sizes) S += g;
+    const size_t n = in.held(), W = (S + 63) / 64;
+    out.assign(3 * W * n, 0);
+    for (size_t v = 0; v < n; ++v) {
+        size_t s0 = 0;
+        for (size_t gi = 0; gi < in.G; ++gi) {
+            const size_t g = group_sizes[gi], word = s0 >> 6, bit = s0 & 63;
+            const uint64_t mask = g >= 64 ? ~0ull : (1ull << g) - 1;
+            for (size_t d = 0; d < 3; ++d) {
+                const uint64_t w = in.words[(v * in.G + gi) * 3 + d] & mask;
+                out[(word * 3 + d) * n + v] |= w << bit;
+                if (bit && bit + g > 64) out[((word + 1) * 3 + d) * n + v] |= w >> (64 - bit);
+            }
+            s0 += g;
+        }
+    }
+}
+// The pass behind the last group: the groups' streams walked `chunk` records at a time -- no look-ahead: the pairs' state stays on the device between
+// the steps -- the closed segments collected, put into (A, B, along the records) order by a stable sort by (A, B) of the steps' outputs, and written.
+// The whole table is held in memory, 32 bytes per segment.  step(n_vars, n_groups, sites, chrom, pos, flush, segs_out, segs_cap, n_segs_out) is
+// mg_ibd_step behind an mg_ibd_begin for names.size() samples, whoever holds the device: it returns MG_OK or MG_ERR_LIMIT (then the buffer grows
+// and it is called once more; the state has not moved).  A cohort of one sample has no pair: the header alone.  The text goes to sink(data, n).
+template <class Step, class Sink>
+void ibd_table(const std::deque<PartFile> &files, const std::vector<size_t> &group_sizes, const std::vector<std::string> &names, size_t chunk, Step &&step, Sink &&sink)
+{
+    LdReader in(files);
+    in.short_file = "internal: a group's words for the IBD table are short";
+    size_t S = 0;
+    for (const size_t g : group_sizes) {
+        if (g < 1 || g > 64) throw std::logic_error("ibd_table: a group of 1..64 samples");
+        S += g;
+    }
+    if (!chunk || group_sizes.size() != in.G || S != names.size()) throw std::logic_error("ibd_table: an empty chunk, or groups that are not the streams'");
+    std::string out = ibd_header();
+    std::vector<mg_ibd_seg> all, segs(1024);
+    std::vector<std::string> chrom_names; // by the reader's running contig id
+    std::vector<uint64_t> sites;
+    while (S >= 2) {
+        while (in.held() < chunk && in.read_one())
+            if (in.chrom.back() == chrom_names.size()) chrom_names.push_back(in.last_chrom);
+        const size_t n = in.held();
+        const int flush = in.ended;
+        ibd_cohort_sites(in, group_sizes, sites);
+        uint64_t needed = 0;
+        int rc = step(n, (S + 63) / 64, sites.data(), in.chrom.data(), in.pos.data(), flush, segs.data(), segs.size(), &needed);
+        if (rc == MG_ERR_LIMIT) {
+            segs.resize(needed);
+            rc = step(n, (S + 63) / 64, sites.data(), in.chrom.data(), in.pos.data(), flush, segs.data(), segs.size(), &needed);
+        }
+        if (rc != MG_OK || needed > segs.size()) throw std::runtime_error("internal: the IBD table's segments do not fit their buffer");
+        for (uint64_t k = 0; k < needed; ++k) {
+            const mg_ibd_seg &s = segs[k];
+            if (s.a >= s.b || s.b >= S || s.chrom >= chrom_names.size()) throw std::runtime_error("internal: a segment of the IBD table names no pair or no contig");
+        }
+        all.insert(all.end(), segs.begin(), segs.begin() + needed);
+        in.drop(n);
+        if (flush) break;
+    }
+    std::stable_sort(all.begin(), all.end(), [](const mg_ibd_seg &x, const mg_ibd_seg &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    for (const mg_ibd_seg &s : all) {
+        ibd_row(out, names[s.a], names[s.b], chrom_names[s.chrom], s);
+        if (out.size() >= (1u << 20)) {
+            sink(out.data(), out.size());
+            out.clear();
+        }
+    }
+    sink(out.data(), out.size());
 }
 
 // ---- the paste passes over the groups' blocks of the merged output -----------------------------------------------------------------

@@ -132,6 +132,14 @@ const char *USAGE =
     "          --ld-window-bp                --ld: and with none further away than N bases (default:1000000; 0: no limit)    [this build]\n"
     "          --ld-min-r2                   --ld: the smallest R2 written, in [0, 1] (default:0.2)                          [this build]\n"
     "          --ld-min-n                    --ld: the fewest samples an R2 is formed from, 1 or more (default:2)            [this build]\n"
+    "          --ibd                         --cohort: PATH receives a tab-separated table of IBS0-free segments, one line per segment and\n"
+    "                                        pair of samples, by pair (in the manifest's order) and along the merged output: A B CHROM START\n"
+    "                                        END LENGTH (END - START), N (the biallelic records where both samples are called -- --min-gq\n"
+    "                                        applies -- and are not opposite homozygotes) and IBS2 (those where their genotypes are equal).\n"
+    "                                        A segment ends in front of an opposite-homozygote record and at the end of a contig.  Made on\n"
+    "                                        the GPU, the same bytes whatever the grouping; beside -o and/or --merged        [this build]\n"
+    "          --ibd-min-records             --ibd: the fewest records (N) of a segment written, 1 or more (default:100)     [this build]\n"
+    "          --ibd-min-bp                  --ibd: the smallest LENGTH written (default:1000000; 0: no limit)               [this build]\n"
     "          --cohort-priors               --cohort: the allele priors of every record are re-estimated from ALL samples of the cohort\n"
     "                                        before the genotypes are made -- a few EM steps from the panel's AF (or -u's uniform\n"
     "                                        prior), anchored to it -- and every sample is genotyped under the cohort's frequencies.\n"
@@ -199,6 +207,8 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"ld", required_argument, nullptr, 1020},       {"ld-window", required_argument, nullptr, 1021},
                                       {"ld-window-bp", required_argument, nullptr, 1022}, {"ld-min-r2", required_argument, nullptr, 1023},
                                       {"ld-min-n", required_argument, nullptr, 1024},
+                                      {"ibd", required_argument, nullptr, 1025},      {"ibd-min-records", required_argument, nullptr, 1026},
+                                      {"ibd-min-bp", required_argument, nullptr, 1027},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -323,6 +333,32 @@ bool parse_arguments(int argc, char **argv, Options &o)
             } else o.ld_min_r2 = v;
             break;
         }
+        case 1025:
+            o.ibd = optarg;
+            if (o.ibd.empty()) {
+                std::cerr << "malva : --ibd takes a path\n";
+                die = true;
+            }
+            break;
+        case 1026:
+        case 1027: {
+            // (digits only, as --ld-window)
+            const std::string text = optarg;
+            const unsigned long long most = c == 1026 ? 0xFFFFFFFFull : 0x7FFFFFFFFFFFFFFFull, least = c == 1026 ? 1 : 0;
+            unsigned long long v = 0;
+            bool ok = !text.empty() && text.size() <= 20;
+            for (const char ch : text) {
+                ok = ok && ch >= '0' && ch <= '9' && v <= (~0ull - (ch - '0')) / 10;
+                if (ok) v = v * 10 + (ch - '0');
+            }
+            o.ibd_sub = true;
+            if (!ok || v < least || v > most) {
+                std::cerr << "malva : --" << (c == 1026 ? "ibd-min-records takes a whole number 1..4294967295" : "ibd-min-bp takes a whole number (0: no limit)") << "\n";
+                die = true;
+            } else if (c == 1026) o.ibd_min_records = (uint32_t)v;
+            else o.ibd_min_bp = v;
+            break;
+        }
         case 1012: o.priors.on = true; break;
         case 1013:
             if (!parse_prior_iters(optarg, o.priors)) {
@@ -422,6 +458,14 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.ld.empty() && o.ld_sub) {
         std::cerr << "malva : --ld-window, --ld-window-bp, --ld-min-r2 and --ld-min-n go with --ld\n";
+        die = true;
+    }
+    if (!o.cohort && !o.ibd.empty()) {
+        std::cerr << "malva : --ibd goes with --cohort\n";
+        die = true;
+    }
+    if (o.ibd.empty() && o.ibd_sub) {
+        std::cerr << "malva : --ibd-min-records and --ibd-min-bp go with --ibd\n";
         die = true;
     }
     if (const std::string why = check_prior_options(o.priors, o.cohort); !why.empty()) {
@@ -1459,6 +1503,12 @@ int call_main(const Options &o)
         const bool want_ld = !o.ld.empty();
         std::deque<PartFile> ld_files;
         PartFile ld_file;
+        // --ibd: the same words in a stream of its own, PATH.gN.sites.part; the pass behind the last group walks every pair of samples along them
+        // on the device, chunk by chunk, and writes the table (PATH.part, renamed at the end)
+        const bool want_ibd = !o.ibd.empty();
+        std::deque<PartFile> ibd_files;
+        std::vector<size_t> ibd_group_sizes;
+        PartFile ibd_file;
         std::vector<std::string> names;
         for (const auto &sm : samples) names.push_back(sm.name);
         const bool merged_stdout = o.merged == "-";
@@ -1579,6 +1629,7 @@ int call_main(const Options &o)
                 }
             }
             if (want_ld) to.ld = &open_scratch(ld_files, o.ld, ".ld.part"), to.ld_cols = s0 == 0;
+            if (want_ibd) to.ibd = &open_scratch(ibd_files, o.ibd, ".sites.part"), to.ibd_cols = s0 == 0, ibd_group_sizes.push_back(g);
             for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
                 to.per_sample.emplace_back();
                 to.per_sample.back().open(o.out_dir + "/" + samples[s0 + i].name + ".vcf");
@@ -1608,6 +1659,7 @@ int call_main(const Options &o)
             if (to.site_counts) to.site_counts->close("cannot write the merged output's counts");
             if (to.site_stats) to.site_stats->close(to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
             if (to.ld) to.ld->close("cannot write the LD table's words");
+            if (to.ibd) to.ibd->close("cannot write the IBD table's words");
             if (to.merged) {
                 if (bcf_out && bcf_bgzf && merged_direct) to.merged->write(bgzf_eof(), "cannot write the merged output");
                 to.merged->close("cannot write the merged output");
@@ -1716,6 +1768,26 @@ int call_main(const Options &o)
                 [&](const char *data, size_t n) { ld_file.write(data, n, "cannot write the LD table"); });
             ld_files.clear(); // (the groups' streams go before the table takes its name)
             ld_file.finish("cannot write the LD table");
+        }
+        if (want_ibd) {
+            Timed t("cohort: ibd pass");
+            ibd_file.open(o.ibd);
+            if (S >= 2) dev.check(mg_ibd_begin(dev.ctx, (uint32_t)S, o.ibd_min_records, o.ibd_min_bp), "mg_ibd_begin");
+            ibd_table(
+                ibd_files, ibd_group_sizes, names, geno_batch_records(65536),
+                [&](size_t n_vars, size_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, int flush, mg_ibd_seg *segs, size_t cap, uint64_t *needed) {
+                    const int rc = mg_ibd_step(dev.ctx, n_vars, (uint32_t)n_groups, sites, chrom, pos, flush, segs, cap, needed);
+                    if (rc != MG_ERR_LIMIT) dev.check(rc, "mg_ibd_step");
+                    float ms[2] = {0, 0};
+                    dev.check(mg_ibd_stats(dev.ctx, ms), "mg_ibd_stats");
+                    times.ibd.ms[1] += ms[1];
+                    ++times.ibd.calls[1];
+                    return rc;
+                },
+                [&](const char *data, size_t n) { ibd_file.write(data, n, "cannot write the IBD table"); });
+            if (S >= 2) dev.check(mg_ibd_end(dev.ctx), "mg_ibd_end");
+            ibd_files.clear(); // (the groups' streams go before the table takes its name)
+            ibd_file.finish("cannot write the IBD table");
         }
         priors_file.finish();
         times.add_to_timers();

@@ -38,6 +38,10 @@ struct Options { // argument_parser.hpp:51-66
     uint64_t ld_window_bp = 1000000; // --ld-window-bp: and no further away than this (0: no limit)
     double ld_min_r2 = 0.2;         // --ld-min-r2: the smallest r2 written
     uint32_t ld_min_n = 2;          // --ld-min-n: the fewest samples a pair's r2 is formed from
+    std::string ibd;        // --ibd: the table of IBS0-free segments per pair of samples
+    bool ibd_sub = false;   // one of --ibd's sub-options was given
+    uint32_t ibd_min_records = 100;   // --ibd-min-records: the fewest records of a segment written
+    uint64_t ibd_min_bp = 1000000;    // --ibd-min-bp: and its smallest END - START (0: no limit)
     PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
 };
 
