@@ -61,10 +61,10 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-value -o $@ $<
 
-# the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs (--site-stats, --ld and --ibd in programs of their own) and of the panel batches and their text under
+# the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs (--site-stats, --ld, --ibd and --grm in programs of their own) and of the panel batches and their text under
 # AddressSanitizer and UBSan: stand-alone programs, run on the CPU.  The last one is a batch's device calls and the pipeline around them
 # (host/call_worker.hpp) against an ABI of its own, without libmalva_hip; it runs a second time under ThreadSanitizer
-sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/site_table_host_check bin/ld_out_host_check bin/ibd_out_host_check \
+sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/site_table_host_check bin/ld_out_host_check bin/ibd_out_host_check bin/grm_out_host_check \
                bin/call_batch_host_check bin/call_worker_host_check bin/call_worker_host_check_tsan
 	bin/cohort_priors_host_check bin
 	bin/cohort_priors_groups_host_check bin
@@ -72,6 +72,7 @@ sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check 
 	bin/site_table_host_check bin
 	bin/ld_out_host_check bin
 	bin/ibd_out_host_check bin
+	bin/grm_out_host_check bin
 	bin/call_batch_host_check
 	bin/call_worker_host_check bin
 	bin/call_worker_host_check_tsan bin
@@ -93,6 +94,14 @@ bin/ld_out_host_check: tools/ld_out_host_check.cpp malva_amd/host/cohort_out.hpp
 bin/ibd_out_host_check: tools/ibd_out_host_check.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
+bin/grm_out_host_check: tools/grm_out_host_check.cpp tools/grm_host_loop.cpp malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
+# the GRM's definition as a one-core loop, for tools/grm_bench.py (which loads it) and on its own
+grm-tools: bin/libgrm_host_loop.so
+bin/libgrm_host_loop.so: tools/grm_host_loop.cpp
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -fPIC -shared -o $@ $<
 bin/call_batch_host_check: tools/call_batch_host_check.cpp tools/host_check_util.hpp malva_amd/host/panel_batch.hpp malva_amd/host/call_text.hpp malva_amd/host/block.hpp \
                            malva_amd/host/io.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
 	@mkdir -p bin
@@ -107,4 +116,4 @@ bin/call_worker_host_check_tsan: tools/call_worker_host_check.cpp tools/host_che
 clean:
 	rm -rf malva_amd/lib bin oracle/libmalva_oracle.so oracle/_ref
 
-.PHONY: all lib cli oracle ref microbench sanitize-host clean
+.PHONY: all lib cli oracle ref microbench sanitize-host grm-tools clean

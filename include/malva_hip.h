@@ -796,6 +796,47 @@ int mg_ibd_step_device(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const void
 int mg_ibd_end(mg_ctx *ctx);
 int mg_ibd_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- the genetic relationship matrix (GRM) ---------------------------------------------
+ * For every pair of samples, the sum over the records of the product of their standardised dosages, in fixed point and exact.  There is no
+ * reference call to cite: the reference genotypes one individual per run.  The cells CONTRIBUTE, with dosage 0, 1 or 2, exactly as for
+ * mg_pack_dosage / mg_pack_site_dosage.  sites is uint64_t [n_groups][3][n_vars], the groups' mg_pack_site_dosage outputs side by side as
+ * mg_ibd_step takes them: sample 64 g + p is bit p of group g, n_groups == ceil(n_samples / 64) (else MG_ERR_ARG); the bits at and beyond
+ * n_samples are masked off by the library.
+ * Per record, over the whole cohort, n_d = the set bits of dosage d.  Diploid: n = n0 + n1 + n2, AN = 2 n, AC = n1 + 2 n2, D = 2 AC (AN - AC).
+ * Haploid (the pack gives dosages 0 and 2; dosage-1 bits are ignored): n = n0 + n2, AN = n, AC = n2, D = 4 AC (AN - AC).  D < 2^31.
+ *   q_d = rint((d AN - 2 AC) 1024 / sqrt((double)D)),  d = 0, 1, 2:  IEEE binary64 sqrt, one divide, round-half-even
+ * -- the standardised dosage (d - 2p) / sqrt(2p (1 - p)), or its haploid counterpart, with MG_GRM_SHIFT fraction bits.  The record ENTERS when
+ * D > 0, n >= min_n, min(AC, AN - AC) 1000000 >= maf_ppm AN (64-bit integers) and every |q_d| <= MG_GRM_MAX_Q (both balanced base-256 digits of
+ * q fit a signed byte; a minor allele frequency of about 0.002 and up).
+ * For samples a <= b (a == b included), over the entering records where both cells contribute: N_ab their number, S_ab the signed 64-bit sum
+ * of q_{x_a} q_{x_b}.  The GRM value is S_ab / (2^20 N_ab).  Integer sums: the same values whatever the steps, pieces and order of summation.
+ * mg_grm_weights: q_out is int16_t [n_vars][4] -- q0 q1 q2 1 for a record that enters, 0 0 0 0 for one that does not.  n_samples is
+ * 1..MG_GRM_MAX_SAMPLES, maf_ppm 0..500000, min_n at least 1, else MG_ERR_ARG; n_vars == 0 is legal.
+ * mg_grm_begin: the same ranges.  It allocates the device-resident state of all n (n + 1) / 2 pairs, 16 bytes per pair (2.1 GB at the
+ * limit), all zero; MG_ERR_NOMEM when that does not fit.  A second begin discards the first.  mg_grm_end frees the state (and is legal
+ * without one).
+ * mg_grm_step adds the next n_vars records (n_vars == 0 is legal).  Without a begin: MG_ERR_STATE.  Working memory of a step, from the
+ * context: 3 bytes per record and sample (samples padded to 32, records to 64) plus 8 bytes per record, for a piece of the step at a time;
+ * the pieces are cut so that the 3-byte part stays at or under 384 MiB (option grm_scratch_mb), or one 64-record slice where that is more.
+ * mg_grm_read (waits; callable between steps): sum_out int64_t and n_out uint64_t [n (n + 1) / 2], pair (a, b), a <= b, row-major --
+ * at a (2 n - a + 1) / 2 + b - a; records_out[0] the records seen since the begin, [1] those that entered.  Host pointers.
+ * The host forms synchronise.  The device forms take device pointers and are asynchronous on the context's stream.
+ * mg_grm_stats (waits): ms_out[3], device milliseconds of the most recent step -- [0] weights and expansion, [1] the Gram kernel, over all
+ * its pieces -- and [2] of the most recent read; 0 for a kind not called yet, MG_ERR_STATE when neither was. */
+#define MG_GRM_MAX_SAMPLES 16384
+#define MG_GRM_SHIFT 10
+#define MG_GRM_MAX_Q 32639
+int mg_grm_weights(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, uint32_t n_samples, const uint64_t *sites, int haploid, uint32_t maf_ppm, uint32_t min_n,
+                   int16_t *q_out);
+int mg_grm_weights_device(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, uint32_t n_samples, const void *d_sites, int haploid, uint32_t maf_ppm, uint32_t min_n,
+                          void *d_q_out);
+int mg_grm_begin(mg_ctx *ctx, uint32_t n_samples, int haploid, uint32_t maf_ppm, uint32_t min_n);
+int mg_grm_step(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const uint64_t *sites);
+int mg_grm_step_device(mg_ctx *ctx, size_t n_vars, uint32_t n_groups, const void *d_sites);
+int mg_grm_read(mg_ctx *ctx, int64_t *sum_out, uint64_t *n_out, uint64_t *records_out);
+int mg_grm_end(mg_ctx *ctx);
+int mg_grm_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- allele priors re-estimated from the cohort -------------------------------------
  * mg_genotype_cohort: the batch's allele frequencies are re-estimated from all of its planes (a few EM steps from the panel's
  * priors, anchored to them), then every cell is genotyped under the result.  The reference genotypes one individual and has no

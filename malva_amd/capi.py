@@ -23,6 +23,7 @@ COMM_NONE, COMM_RCCL, COMM_LOCAL = 0, 1, 2
 COMM_ID_BYTES = 128
 LD_MAX_GROUPS, LD_MAX_WINDOW = 256, 1024   # MG_LD_MAX_GROUPS, MG_LD_MAX_WINDOW
 IBD_MAX_SAMPLES = 16384     # MG_IBD_MAX_SAMPLES
+GRM_MAX_SAMPLES, GRM_SHIFT, GRM_MAX_Q = 16384, 10, 32639   # MG_GRM_MAX_SAMPLES, MG_GRM_SHIFT, MG_GRM_MAX_Q
 IBD_SEG = np.dtype([(f, np.uint32) for f in ("a", "b", "chrom", "start_pos", "end_pos", "n", "ibs2", "zero")])   # mg_ibd_seg, 32 bytes
 LD_PAIR = np.dtype([("i", np.uint32), ("j", np.uint32), ("n", np.uint32), ("sign", np.int32), ("r2", np.float64)])   # mg_ld_pair, 24 bytes
 SAMPLE_SLOTS = 32           # MG_SAMPLE_SLOTS: the counters per plane of mg_sample_counts (MG_SS_*)
@@ -148,6 +149,14 @@ def lib():
         "mg_ibd_step_device": [vp, sz, u32, vp, vp, vp, it, vp, sz, vp],
         "mg_ibd_end": [vp],
         "mg_ibd_stats": [vp, vp],
+        "mg_grm_weights": [vp, sz, u32, u32, vp, it, u32, u32, vp],
+        "mg_grm_weights_device": [vp, sz, u32, u32, vp, it, u32, u32, vp],
+        "mg_grm_begin": [vp, u32, it, u32, u32],
+        "mg_grm_step": [vp, sz, u32, vp],
+        "mg_grm_step_device": [vp, sz, u32, vp],
+        "mg_grm_read": [vp, vp, vp, vp],
+        "mg_grm_end": [vp],
+        "mg_grm_stats": [vp, vp],
         "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_cohort_prior_stats": [vp, vp],
@@ -226,7 +235,8 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_pairs_stats", "mg_sample_counts", "mg_sample_counts_device", "mg_sample_stats",
             "mg_site_geno_counts", "mg_site_geno_counts_device", "mg_hwe_exact", "mg_hwe_exact_device", "mg_hwe_stats",
             "mg_pack_site_dosage", "mg_pack_site_dosage_device", "mg_ld_window", "mg_ld_window_device", "mg_ld_stats",
-            "mg_sites_to_planes", "mg_sites_to_planes_device", "mg_ibd_begin", "mg_ibd_step", "mg_ibd_step_device", "mg_ibd_end", "mg_ibd_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_sites_to_planes", "mg_sites_to_planes_device", "mg_ibd_begin", "mg_ibd_step", "mg_ibd_step_device", "mg_ibd_end", "mg_ibd_stats",
+            "mg_grm_weights", "mg_grm_weights_device", "mg_grm_begin", "mg_grm_step", "mg_grm_step_device", "mg_grm_read", "mg_grm_end", "mg_grm_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -1114,6 +1124,55 @@ class Context:
         ms = (C.c_float * 2)()
         self._ck(self._L.mg_ibd_stats(self.h, ms))
         return float(ms[0]), float(ms[1])
+
+    # the genetic relationship matrix
+    def grm_weights(self, sites, n_samples, haploid=False, maf_ppm=0, min_n=1, out=None):
+        """sites: uint64 [groups, 3, n_vars], groups == ceil(n_samples / 64) -> int16 [n_vars, 4]: q0 q1 q2 1 of a record that enters, zeros of
+        one that does not (mg_grm_weights in include/malva_hip.h).  out: the array to fill."""
+        S = np.ascontiguousarray(sites, dtype=np.uint64)
+        groups, three, n = S.shape
+        assert three == 3
+        if out is None:
+            out = np.zeros((n, 4), dtype=np.int16)
+        assert out.dtype == np.int16 and out.flags.c_contiguous and out.shape == (n, 4)
+        self._ck(self._L.mg_grm_weights(self.h, n, groups, int(n_samples), _p(S), int(bool(haploid)), int(maf_ppm), int(min_n), _p(out)))
+        return out
+
+    def grm_weights_device(self, n_vars, groups, n_samples, d_sites, haploid, maf_ppm, min_n, d_q_out):
+        """the same from a device pointer into a device buffer, asynchronous on the context's stream"""
+        self._ck(self._L.mg_grm_weights_device(self.h, n_vars, groups, int(n_samples), C.c_void_p(d_sites), int(bool(haploid)), int(maf_ppm), int(min_n),
+                                               C.c_void_p(d_q_out)))
+
+    def grm_begin(self, n_samples, haploid=False, maf_ppm=0, min_n=1):
+        """the state of all n (n + 1) / 2 pairs, zero (mg_grm_begin); a second begin discards the first"""
+        self._ck(self._L.mg_grm_begin(self.h, int(n_samples), int(bool(haploid)), int(maf_ppm), int(min_n)))
+
+    def grm_step(self, sites):
+        """the next records: sites uint64 [groups, 3, n_vars] (mg_grm_step)"""
+        S = np.ascontiguousarray(sites, dtype=np.uint64)
+        groups, three, n = S.shape
+        assert three == 3
+        self._ck(self._L.mg_grm_step(self.h, n, groups, _p(S) if n else None))
+
+    def grm_step_device(self, n_vars, groups, d_sites):
+        """the same from a device pointer, asynchronous on the context's stream"""
+        self._ck(self._L.mg_grm_step_device(self.h, n_vars, groups, C.c_void_p(d_sites)))
+
+    def grm_read(self, n_samples):
+        """-> (S int64 [n (n + 1) / 2], N uint64 likewise, records seen, records entered): pair (a, b), a <= b, row-major (mg_grm_read)"""
+        k = n_samples * (n_samples + 1) // 2
+        S, N, rec = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+        self._ck(self._L.mg_grm_read(self.h, _p(S), _p(N), _p(rec)))
+        return S, N, int(rec[0]), int(rec[1])
+
+    def grm_end(self):
+        self._ck(self._L.mg_grm_end(self.h))
+
+    def grm_stats(self):
+        """-> device ms of the most recent step's weights + expansion and Gram kernel, and of the most recent read"""
+        ms = (C.c_float * 3)()
+        self._ck(self._L.mg_grm_stats(self.h, ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     # allele priors re-estimated from the planes of a batch, and the cells genotyped under them
     def genotype_cohort(self, cov, freq, var_allele_off, error_rate, max_cov, haploid, iters=5, weight=1.0, want_probs=False):

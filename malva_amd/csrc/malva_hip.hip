@@ -45,6 +45,7 @@ constexpr int TPB = 256;
 #include "site_geno_kernels.h"
 #include "ld_kernels.h"
 #include "ibd_kernels.h"
+#include "grm_kernels.h"
 #include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
 #include "pl_kernels.h"
@@ -185,6 +186,19 @@ struct mg_ctx {
     u32 ibd_samples = 0, ibd_min_records = 0;
     long long ibd_min_bp = 0;
     Scratch s_ibd[5];
+    // mg_grm_begin .. mg_grm_end: the pairs' state -- the sums (i64 [n_pairs]), the counts (u64 [n_pairs]) and behind them the number of
+    // records that entered (u64) -- and the records seen (grm_kernels.h).  s_grm: a piece's weights and its three byte images; grm_in:
+    // the host forms' words and weights.  grm_tm: start, behind weights + expand, behind gram, of the step's latest piece; grm_ms: the
+    // pieces before it, and the latest read
+    void *grm_state = nullptr;
+    u64 grm_pairs = 0, grm_seen = 0;
+    u32 grm_samples = 0, grm_maf_ppm = 0, grm_min_n = 0;
+    int grm_haploid = 0;
+    Scratch s_grm[2], grm_in[2];
+    Timer grm_tm{3}, grm_read_tm{2};
+    float grm_ms[3] = {0.f, 0.f, 0.f};
+    bool grm_timed = false;
+    int grm_scratch_mb = GRM_SCRATCH_MB; // the cap on a piece's byte images (tests: smaller, so that a step takes several pieces)
     Scratch s_ld[2]; // mg_ld_window_device, from its length pass to its write pass: the records' pair counts (u32), the meta block (the total)
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -823,6 +837,12 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     for (Scratch &q : c->s_ld) hipFree(q.p);
     for (Scratch &q : c->s_ibd) hipFree(q.p);
     hipFree(c->ibd_state);
+    for (Scratch &q : c->s_grm) hipFree(q.p);
+    for (Scratch &q : c->grm_in) hipFree(q.p);
+    hipFree(c->grm_state);
+    for (Timer *t : {&c->grm_tm, &c->grm_read_tm})
+        for (hipEvent_t e : t->ev)
+            if (e) hipEventDestroy(e);
     if (c->joined) { // the two counter arrays alias one allocation
         hipFree(c->joined);
         c->bf[MG_BF_ALT].counts = nullptr;
@@ -953,6 +973,7 @@ MG_EXPORT int mg_set_option(mg_ctx *c, const char *name, int64_t value)
     else if (!strcmp(name, "reads_budget_mb")) c->reads_budget_mb = (int)std::max<int64_t>(1, std::min<int64_t>(1 << 20, value));
     else if (!strcmp(name, "reads_passes")) c->reads_passes = (int)std::max<int64_t>(0, std::min<int64_t>(RD_PARTS, value));
     else if (!strcmp(name, "reads_parts_log2")) c->reads_parts_log2 = (int)std::max<int64_t>(0, std::min<int64_t>(RD_PART_LOG2, value));
+    else if (!strcmp(name, "grm_scratch_mb")) c->grm_scratch_mb = (int)std::max<int64_t>(1, std::min<int64_t>(4096, value));
     else if (!strcmp(name, "scan_variant")) c->scan_variant = (int)value & 2;
     else if (!strcmp(name, "scan_grid")) c->scan_grid = value > 0 ? (int)value : 8192;
     else if (!strcmp(name, "gate_log2") || !strcmp(name, "gate_k")) {
@@ -1021,6 +1042,7 @@ MG_EXPORT int mg_get_option(mg_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "reads_budget_mb")) *value = c->reads_budget_mb;
     else if (!strcmp(name, "reads_passes")) *value = c->reads_passes;
     else if (!strcmp(name, "reads_parts_log2")) *value = c->reads_parts_log2;
+    else if (!strcmp(name, "grm_scratch_mb")) *value = c->grm_scratch_mb;
     else if (!strcmp(name, "scan_spilled")) { // rows of the last chunk that took the spill list
         unsigned long long t = 0;
         if (c->last_bins || c->last_tickets || c->last_subs) {
@@ -4073,6 +4095,202 @@ MG_EXPORT int mg_ibd_stats(mg_ctx *c, float *ms_out)
     if (!c->tm[TM_IBD_TR].valid && !c->tm[TM_IBD].valid) return fail(c, MG_ERR_STATE, "no mg_sites_to_planes or mg_ibd_step yet");
     TRY(timer_read(c, c->tm[TM_IBD_TR], &ms_out[0]));
     return timer_read(c, c->tm[TM_IBD], &ms_out[1]);
+}
+
+// ---- the genetic relationship matrix (grm_kernels.h) ------------------------------------------------------------------------------------
+namespace {
+int check_grm_weights(mg_ctx *c, size_t n_vars, uint32_t n_groups, uint32_t n_samples, const void *sites, uint32_t maf_ppm, uint32_t min_n, const void *q_out)
+{
+    if (n_samples < 1 || n_samples > MG_GRM_MAX_SAMPLES) return fail(c, MG_ERR_ARG, "mg_grm: n_samples is 1..%d", MG_GRM_MAX_SAMPLES);
+    if (n_groups != (n_samples + 63) / 64) return fail(c, MG_ERR_ARG, "mg_grm: n_groups is ceil(n_samples / 64) = %u", (n_samples + 63) / 64);
+    if (maf_ppm > 500000) return fail(c, MG_ERR_ARG, "mg_grm: maf_ppm is 0..500000");
+    if (min_n < 1) return fail(c, MG_ERR_ARG, "mg_grm: min_n is at least 1");
+    if (n_vars && (!sites || !q_out)) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_grm: more than 2^32 - 1 records in one call");
+    return MG_OK;
+}
+int check_grm_step(mg_ctx *c, size_t n_vars, uint32_t n_groups, const void *sites)
+{
+    if (!c->grm_state) return fail(c, MG_ERR_STATE, "mg_grm_step: no mg_grm_begin yet");
+    if (n_groups != (c->grm_samples + 63) / 64) return fail(c, MG_ERR_ARG, "mg_grm_step: n_groups is ceil(n_samples / 64) = %u", (c->grm_samples + 63) / 64);
+    if (n_vars && !sites) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (n_vars >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_grm_step: more than 2^32 - 1 records in one call");
+    return MG_OK;
+}
+void grm_drop(mg_ctx *c)
+{
+    if (c->grm_state) hipFree(c->grm_state);
+    c->grm_state = nullptr;
+    c->grm_pairs = c->grm_seen = 0;
+    c->grm_samples = 0;
+}
+void grm_launch_weights(mg_ctx *c, u64 n_vars, u64 v0, u64 count, u32 n_groups, u32 n_samples, const void *d_sites, int haploid, u32 maf_ppm, u32 min_n, void *d_q,
+                        unsigned long long *d_entered)
+{
+    const GrmWeightArgs a{n_vars, v0, count, n_groups, n_samples, (const unsigned long long *)d_sites, haploid != 0, maf_ppm, min_n};
+    hipLaunchKernelGGL(grm_weights_kernel, dim3((unsigned)((count + GRM_TPB - 1) / GRM_TPB)), dim3(GRM_TPB), 0, c->stream, a, (short4 *)d_q, d_entered);
+}
+} // namespace
+
+MG_EXPORT int mg_grm_weights_device(mg_ctx *c, size_t n_vars, uint32_t n_groups, uint32_t n_samples, const void *d_sites, int haploid, uint32_t maf_ppm, uint32_t min_n,
+                                    void *d_q_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_grm_weights(c, n_vars, n_groups, n_samples, d_sites, maf_ppm, min_n, d_q_out));
+    if (n_vars) {
+        grm_launch_weights(c, n_vars, 0, n_vars, n_groups, n_samples, d_sites, haploid, maf_ppm, min_n, d_q_out, nullptr);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return MG_OK;
+}
+
+MG_EXPORT int mg_grm_weights(mg_ctx *c, size_t n_vars, uint32_t n_groups, uint32_t n_samples, const uint64_t *sites, int haploid, uint32_t maf_ppm, uint32_t min_n,
+                             int16_t *q_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_grm_weights(c, n_vars, n_groups, n_samples, sites, maf_ppm, min_n, q_out));
+    void *d_sites, *d_q;
+    TRY(upload(c, c->grm_in[0], sites, 8 * (size_t)n_groups * 3 * n_vars, &d_sites));
+    TRY(scratch(c, c->grm_in[1], n_vars ? 8 * n_vars : 1, &d_q));
+    TRY(mg_grm_weights_device(c, n_vars, n_groups, n_samples, d_sites, haploid, maf_ppm, min_n, d_q));
+    if (n_vars) HIP_TRY(c, hipMemcpyAsync(q_out, d_q, 8 * n_vars, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_grm_begin(mg_ctx *c, uint32_t n_samples, int haploid, uint32_t maf_ppm, uint32_t min_n)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (n_samples < 1 || n_samples > MG_GRM_MAX_SAMPLES) return fail(c, MG_ERR_ARG, "mg_grm_begin: n_samples is 1..%d", MG_GRM_MAX_SAMPLES);
+    if (maf_ppm > 500000) return fail(c, MG_ERR_ARG, "mg_grm_begin: maf_ppm is 0..500000");
+    if (min_n < 1) return fail(c, MG_ERR_ARG, "mg_grm_begin: min_n is at least 1");
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (a step of the state that goes may still run)
+    grm_drop(c);
+    const u64 n_pairs = (u64)n_samples * (n_samples + 1) / 2;
+    const size_t bytes = 16 * n_pairs + 8; // the sums, the counts, the records that entered
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MG_ERR_NOMEM, "mg_grm_begin: the state of %llu pairs (%zu bytes) does not fit", (unsigned long long)n_pairs, bytes);
+    }
+    c->grm_state = p;
+    c->grm_pairs = n_pairs;
+    c->grm_samples = n_samples;
+    c->grm_haploid = haploid != 0;
+    c->grm_maf_ppm = maf_ppm;
+    c->grm_min_n = min_n;
+    c->grm_timed = false;
+    HIP_TRY(c, hipMemsetAsync(p, 0, bytes, c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_grm_end(mg_ctx *c)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    grm_drop(c);
+    return MG_OK;
+}
+
+// The step in pieces of at most `grm_scratch_mb` MiB of byte images (3 bytes per padded sample and record, at least GRM_K records): per piece
+// the weights, the expansion, the Gram kernel.  A block of pairs gets as many runs along the records as fill the device, none longer than
+// GRM_MAX_RUN; with one run per block the fold needs no atomics.
+MG_EXPORT int mg_grm_step_device(mg_ctx *c, size_t n_vars, uint32_t n_groups, const void *d_sites)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_grm_step(c, n_vars, n_groups, d_sites));
+    c->grm_ms[0] = c->grm_ms[1] = 0.f;
+    c->grm_timed = true;
+    c->grm_tm.valid = false;
+    c->grm_seen += n_vars;
+    if (!n_vars) return MG_OK;
+    const u32 n = c->grm_samples, rows = (n + GRM_BLOCK - 1) / GRM_BLOCK * GRM_BLOCK, blocks = rows / GRM_BLOCK;
+    const u64 cap = (u64)c->grm_scratch_mb << 20;
+    const u64 piece_max = std::max<u64>(GRM_K, cap / (3ull * rows) / GRM_K * GRM_K);
+    long long *d_sum = (long long *)c->grm_state;
+    unsigned long long *d_count = (unsigned long long *)c->grm_state + c->grm_pairs, *d_entered = d_count + c->grm_pairs;
+    const u64 upper = (u64)blocks * (blocks + 1) / 2;
+    for (u64 v0 = 0; v0 < n_vars; v0 += piece_max) {
+        const u64 piece = std::min<u64>(piece_max, n_vars - v0), ld = (piece + GRM_K - 1) / GRM_K * GRM_K;
+        if (c->grm_tm.valid) { // the piece before: its events are about to be used again
+            float ms[2];
+            TRY(timer_read(c, c->grm_tm, ms));
+            c->grm_ms[0] += ms[0];
+            c->grm_ms[1] += ms[1];
+        }
+        void *d_q, *d_img;
+        TRY(scratch(c, c->s_grm[0], 8 * piece, &d_q));
+        TRY(scratch(c, c->s_grm[1], 3 * (size_t)rows * ld, &d_img));
+        TRY(timer_begin(c, c->grm_tm));
+        grm_launch_weights(c, n_vars, v0, piece, n_groups, n, d_sites, c->grm_haploid, c->grm_maf_ppm, c->grm_min_n, d_q, d_entered);
+        signed char *h = (signed char *)d_img, *l = h + (size_t)rows * ld, *cc = l + (size_t)rows * ld;
+        const GrmExpandArgs e{(u64)n_vars, v0, piece, ld, n_groups, n, rows, (const unsigned long long *)d_sites, (const short4 *)d_q, c->grm_haploid, h, l, cc};
+        hipLaunchKernelGGL(grm_expand_kernel, dim3((unsigned)((ld / 4 + GRM_TPB - 1) / GRM_TPB), (rows + 63) / 64), dim3(GRM_TPB), 0, c->stream, e);
+        HIP_TRY(c, hipGetLastError());
+        TRY(timer_mark(c, c->grm_tm, 1));
+        // runs: at least ceil(ld / GRM_MAX_RUN); more while the launch has fewer than GRM_FILL waves and a run keeps GRM_MIN_RUN records
+        const u64 steps = ld / GRM_K;
+        u64 runs = (ld + GRM_MAX_RUN - 1) / GRM_MAX_RUN;
+        runs = std::max(runs, std::min<u64>((GRM_FILL + upper - 1) / upper, (ld + GRM_MIN_RUN - 1) / GRM_MIN_RUN));
+        runs = std::min<u64>(std::min<u64>(runs, steps), 65535);
+        const u64 run = (steps + runs - 1) / runs * GRM_K; // (at most GRM_MAX_RUN: runs >= ceil(ld / GRM_MAX_RUN), both multiples of GRM_K)
+        runs = (ld + run - 1) / run;
+        const GrmGramArgs g{ld, run, n, h, l, cc, d_sum, d_count};
+        if (runs > 1) hipLaunchKernelGGL(grm_gram_kernel<true>, dim3(blocks, blocks, (unsigned)runs), dim3(64), 0, c->stream, g);
+        else hipLaunchKernelGGL(grm_gram_kernel<false>, dim3(blocks, blocks, 1), dim3(64), 0, c->stream, g);
+        HIP_TRY(c, hipGetLastError());
+        TRY(timer_mark(c, c->grm_tm, 2));
+    }
+    return MG_OK;
+}
+
+MG_EXPORT int mg_grm_step(mg_ctx *c, size_t n_vars, uint32_t n_groups, const uint64_t *sites)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_grm_step(c, n_vars, n_groups, sites));
+    void *d_sites;
+    TRY(upload(c, c->grm_in[0], sites, 8 * (size_t)n_groups * 3 * n_vars, &d_sites));
+    TRY(mg_grm_step_device(c, n_vars, n_groups, d_sites));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+MG_EXPORT int mg_grm_read(mg_ctx *c, int64_t *sum_out, uint64_t *n_out, uint64_t *records_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if (!c->grm_state) return fail(c, MG_ERR_STATE, "mg_grm_read: no mg_grm_begin yet");
+    if (!sum_out || !n_out || !records_out) return fail(c, MG_ERR_ARG, "NULL argument");
+    const char *state = (const char *)c->grm_state;
+    TRY(timer_begin(c, c->grm_read_tm));
+    HIP_TRY(c, hipMemcpyAsync(sum_out, state, 8 * c->grm_pairs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(n_out, state + 8 * c->grm_pairs, 8 * c->grm_pairs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&records_out[1], state + 16 * c->grm_pairs, 8, hipMemcpyDeviceToHost, c->stream));
+    TRY(timer_mark(c, c->grm_read_tm, 1));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    records_out[0] = c->grm_seen;
+    return MG_OK;
+}
+
+// device milliseconds (waits for them): ms_out[0] weights + expand and [1] gram of the most recent step, all its pieces; [2] the most
+// recent read; 0 where there was none
+MG_EXPORT int mg_grm_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    ms_out[0] = ms_out[1] = ms_out[2] = 0.f; // (also where it fails)
+    if (!c->grm_timed && !c->grm_read_tm.valid) return fail(c, MG_ERR_STATE, "no mg_grm_step or mg_grm_read yet");
+    float ms[2] = {0.f, 0.f};
+    TRY(timer_read(c, c->grm_tm, ms));
+    ms_out[0] = c->grm_ms[0] + ms[0];
+    ms_out[1] = c->grm_ms[1] + ms[1];
+    return timer_read(c, c->grm_read_tm, &ms_out[2]);
 }
 
 // ---- allele priors re-estimated from the planes of a batch (cohort_prior_kernels.h) ------------------------------------------------------

@@ -37,13 +37,15 @@ struct CallTimes {
     Kind geno;     // --site-stats: [0] mg_site_geno_counts, [1] mg_hwe_exact
     Kind ld;       // --ld: [0] mg_pack_site_dosage, [1] mg_ld_window
     Kind ibd;      // --ibd: [0] mg_pack_site_dosage (where --ld did not ask for the words already), [1] mg_ibd_step
+    Kind grm;      // --grm: [0] mg_pack_site_dosage (where neither --ld nor --ibd asked), [1] mg_grm_step's weights + expansion, [2] its Gram kernel
     size_t gt_bytes = 0; // panel genotypes handed to mg_cover_blocks[_cohort]
 
     CallTimes &operator+=(const CallTimes &o)
     {
         Kind CallTimes::*const kinds[] = {&CallTimes::format, &CallTimes::bcf,   &CallTimes::site,    &CallTimes::pairs,
                                           &CallTimes::sample, &CallTimes::prior, &CallTimes::estimate, &CallTimes::pl,
-                                          &CallTimes::geno,   &CallTimes::ld,   &CallTimes::ibd};
+                                          &CallTimes::geno,   &CallTimes::ld,   &CallTimes::ibd,
+                                          &CallTimes::grm};
         for (auto k : kinds)
             for (int i = 0; i < 3; ++i) (this->*k).ms[i] += (o.*k).ms[i], (this->*k).calls[i] += (o.*k).calls[i];
         gt_bytes += o.gt_bytes;
@@ -58,6 +60,7 @@ struct CallTimes {
         if (geno.calls[0]) g_timers.add("site table: count and test kernels (device)", (geno.ms[0] + geno.ms[1]) / 1000.0);
         if (ld.calls[0]) g_timers.add("ld table: pack and window kernels (device)", (ld.ms[0] + ld.ms[1]) / 1000.0);
         if (ibd.calls[0] || ibd.calls[1]) g_timers.add("ibd table: pack and step kernels (device)", (ibd.ms[0] + ibd.ms[1]) / 1000.0);
+        if (grm.calls[0] || grm.calls[1]) g_timers.add("grm: pack, weights, expand and gram kernels (device)", (grm.ms[0] + grm.ms[1] + grm.ms[2]) / 1000.0);
         if (prior.calls[0]) g_timers.add("cohort priors: kernel (device)", prior.ms[0] / 1000.0);
         if (estimate.calls[0]) g_timers.add("cohort priors: estimate kernel (device)", estimate.ms[0] / 1000.0);
         if (pl.calls[0]) g_timers.add("merged: likelihood kernel (device)", pl.ms[0] / 1000.0);
@@ -93,6 +96,11 @@ struct CallTimes {
         if (ibd.calls[0] || ibd.calls[1]) {
             snprintf(line, sizeof line, "[malva-geno] ibd: %zu mg_pack_site_dosage, %zu mg_ibd_step, device ms per call: pack %.3f step %.3f\n", ibd.calls[0], ibd.calls[1],
                      ibd.calls[0] ? ibd.ms[0] / ibd.calls[0] : 0.0, ibd.calls[1] ? ibd.ms[1] / ibd.calls[1] : 0.0);
+            out += line;
+        }
+        if (grm.calls[0] || grm.calls[1]) {
+            snprintf(line, sizeof line, "[malva-geno] grm: %zu mg_pack_site_dosage, %zu mg_grm_step, device ms per call: pack %.3f weights+expand %.3f gram %.3f\n", grm.calls[0],
+                     grm.calls[1], grm.calls[0] ? grm.ms[0] / grm.calls[0] : 0.0, grm.calls[1] ? grm.ms[1] / grm.calls[1] : 0.0, grm.calls[1] ? grm.ms[2] / grm.calls[1] : 0.0);
             out += line;
         }
         if (prior.calls[0]) {
@@ -166,6 +174,9 @@ struct PassOut {
     // --ibd: the same words and columns in a stream of its own, for its pass behind the last group (ibd_table)
     PartFile *ibd = nullptr;
     bool ibd_cols = false;
+    // --grm: the same words and columns in a stream of its own, for its pass behind the last group (grm_table)
+    PartFile *grm = nullptr;
+    bool grm_cols = false;
     // --prior-groups, a cohort in several groups (host/cohort_priors.hpp).  prior_cov: the coverage pass -- the batches' coverages go here
     // (put_cov_batch; the first group's with the records' offsets and panel priors), and the pass makes no calls and nothing else.
     // prior_in: the output pass -- the batches' coverages and the cohort's frequencies come from here instead of the counters, and the
@@ -176,7 +187,7 @@ struct PassOut {
 };
 struct BatchText { // the text of one batch, as its worker hands it over
     std::vector<std::string> per_sample;
-    std::string merged, site_counts, pack, priors, prior_cov, site_stats, ld, ibd; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
+    std::string merged, site_counts, pack, priors, prior_cov, site_stats, ld, ibd, grm; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
     CallTimes times; // of this batch's calls alone
 };
 
@@ -239,6 +250,7 @@ public:
         if (to.site_stats) fflush(to.site_stats->f);
         if (to.ld) fflush(to.ld->f);
         if (to.ibd) fflush(to.ibd->f);
+        if (to.grm) fflush(to.grm->f);
     }
 
 private:
@@ -257,7 +269,7 @@ private:
         std::vector<size_t> item_off[2];
         std::vector<double> hwe[2], exc[2];
     };
-    struct SiteWords { // --ld, --ibd: the same two batches' words, [3][records]
+    struct SiteWords { // --ld, --ibd, --grm: the same two batches' words, [3][records]
         std::vector<uint64_t> w[2];
     };
 
@@ -291,6 +303,7 @@ private:
             if (to.site_stats) to.site_stats->write(text.site_stats, to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
             if (to.ld) to.ld->write(text.ld, "cannot write the LD table's words");
             if (to.ibd) to.ibd->write(text.ibd, "cannot write the IBD table's words");
+            if (to.grm) to.grm->write(text.grm, "cannot write the GRM's words");
         }
     }
 
@@ -327,7 +340,7 @@ private:
             if (to.pairs) pair_table(dev, job, text);
             if (to.sample_table) sample_table(dev, job, text.times);
             if (to.site_stats) site_table(dev, job, geno, text.times);
-            if (to.ld || to.ibd) ld_words(dev, job, words, text.times);
+            if (to.ld || to.ibd || to.grm) ld_words(dev, job, words, text.times);
         } // the records' text needs no device
         records_text(job, rows, geno, words, text);
         return text;
@@ -583,7 +596,7 @@ private:
 
     void ld_words(Device &dev, Job &job, SiteWords &sw, CallTimes &times)
     {
-        Timed t_ld(to.ld ? "worker: ld words (mg_pack_site_dosage)" : "worker: ibd words (mg_pack_site_dosage)");
+        Timed t_ld(to.ld ? "worker: ld words (mg_pack_site_dosage)" : to.ibd ? "worker: ibd words (mg_pack_site_dosage)" : "worker: grm words (mg_pack_site_dosage)");
         for (int w = 0; w < 2; ++w) {
             Batch &b = w ? job.gen : job.iso;
             const size_t bn = b.n();
@@ -594,7 +607,7 @@ private:
                       "mg_pack_site_dosage");
             float ms[2] = {0, 0};
             dev.check(mg_ld_stats(dev.ctx, ms), "mg_ld_stats");
-            (to.ld ? times.ld : times.ibd).add(ms, 1);
+            (to.ld ? times.ld : to.ibd ? times.ibd : times.grm).add(ms, 1);
         }
     }
 
@@ -616,6 +629,11 @@ private:
                 const std::vector<uint64_t> &sw = words.w[w];
                 const size_t bn = sw.size() / 3;
                 put_ld_words(text.ibd, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.ibd_cols ? r.prefix.data() : nullptr, site_stats_cols(r.prefix));
+            }
+            if (to.grm) {
+                const std::vector<uint64_t> &sw = words.w[w];
+                const size_t bn = sw.size() / 3;
+                put_ld_words(text.grm, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.grm_cols ? r.prefix.data() : nullptr, site_stats_cols(r.prefix));
             }
             if (!to.site_stats) continue;
             const uint32_t *het = geno.het[w].data() + r.allele0, *hom = geno.hom[w].data() + r.allele0;

@@ -1,7 +1,7 @@
 // cohort_out.hpp -- the host-only half of the outputs of `call --cohort`: the streams a group leaves for the passes behind the last group
-// (the records' site counts, the packed calls, the records' genotype counts, the records' words for the LD and IBD tables), the two paste passes over the groups'
-// blocks of the merged output, and the text of the --pairs, --sample-stats, --site-stats, --ld and --ibd tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp, tools/site_table_host_check.cpp
-// tools/ld_out_host_check.cpp and tools/ibd_out_host_check.cpp drive this file alone).
+// (the records' site counts, the packed calls, the records' genotype counts, the records' words for the LD and IBD tables and the GRM), the two paste passes over the groups'
+// blocks of the merged output, and the text of the --pairs, --sample-stats, --site-stats, --ld, --ibd and --grm tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp, tools/site_table_host_check.cpp
+// tools/ld_out_host_check.cpp, tools/ibd_out_host_check.cpp and tools/grm_out_host_check.cpp drive this file alone).
 #pragma once
 #include <deque>
 
@@ -538,6 +538,103 @@ void ibd_table(const std::deque<PartFile> &files, const std::vector<size_t> &gro
         }
     }
     sink(out.data(), out.size());
+}
+
+// ---- the GRM (--grm) ----------------------------------------------------------------------------------------------------------------
+// The genetic relationship matrix (mg_grm_step): per pair of samples a <= b, in the manifest's order, N -- the entering records where both are called --
+// and S / (2^20 N).  The text has six decimals, formed in integers: S 10^6 / (2^20 N) rounded half away from zero, no sign on a value that
+// rounds to zero, `.` where N is 0.
+inline const char *grm_header() { return "#A\tB\tN\tGRM\n"; }
+inline void grm_value(std::string &out, int64_t s, uint64_t n)
+{
+    if (!n) {
+        out += '.';
+        return;
+    }
+    const unsigned __int128 mag = s < 0 ? (unsigned __int128)(-(__int128)s) : (unsigned __int128)s, den = (unsigned __int128)n << 20;
+    const unsigned __int128 v = (2 * mag * 1000000u + den) / (2 * den);
+    char num[64];
+    snprintf(num, sizeof num, "%s%llu.%06u", s < 0 && v ? "-" : "", (unsigned long long)(v / 1000000u), (unsigned)(v % 1000000u));
+    out += num;
+}
+struct GrmState { // mg_grm_read's outputs: pair (a, b), a <= b, row-major
+    std::vector<int64_t> sum;
+    std::vector<uint64_t> n;
+    uint64_t records[2] = {0, 0}; // seen, entered
+};
+// The pass behind the last group: the groups' streams walked `chunk` records at a time, the cohort's bits put side by side (ibd_cohort_sites) and
+// handed to step(n_vars, n_groups, sites) -- mg_grm_step behind an mg_grm_begin for the groups' samples, whoever holds the device; the pairs' sums
+// stay there between the steps.  read(sum, n, records) -- mg_grm_read -- is called once, behind the last step.
+template <class Step, class Read> GrmState grm_table(const std::deque<PartFile> &files, const std::vector<size_t> &group_sizes, size_t chunk, Step &&step, Read &&read)
+{
+    LdReader in(files);
+    in.short_file = "internal: a group's words for the GRM are short";
+    size_t S = 0;
+    for (const size_t g : group_sizes) {
+        if (g < 1 || g > 64) throw std::logic_error("grm_table: a group of 1..64 samples");
+        S += g;
+    }
+    if (!chunk || group_sizes.size() != in.G) throw std::logic_error("grm_table: an empty chunk, or groups that are not the streams'");
+    std::vector<uint64_t> sites;
+    for (;;) {
+        while (in.held() < chunk && in.read_one()) {}
+        const size_t n = in.held();
+        if (n) {
+            ibd_cohort_sites(in, group_sizes, sites);
+            step(n, (S + 63) / 64, (const uint64_t *)sites.data());
+            in.drop(n);
+        }
+        if (in.ended) break;
+    }
+    GrmState st;
+    st.sum.resize(S * (S + 1) / 2), st.n.resize(S * (S + 1) / 2);
+    read(st.sum.data(), st.n.data(), st.records);
+    return st;
+}
+// the table's text, to sink(data, n) about a MiB at a time
+template <class Sink> void grm_text(const GrmState &st, const std::vector<std::string> &names, Sink &&sink)
+{
+    const size_t S = names.size();
+    if (st.sum.size() != S * (S + 1) / 2 || st.n.size() != st.sum.size()) throw std::logic_error("grm_text: a state that is not the names'");
+    std::string out = grm_header();
+    char num[32];
+    for (size_t a = 0, k = 0; a < S; ++a)
+        for (size_t b = a; b < S; ++b, ++k) {
+            out += names[a];
+            out += '\t';
+            out += names[b];
+            snprintf(num, sizeof num, "\t%llu\t", (unsigned long long)st.n[k]);
+            out += num;
+            grm_value(out, st.sum[k], st.n[k]);
+            out += '\n';
+            if (out.size() >= (1u << 20)) {
+                sink(out.data(), out.size());
+                out.clear();
+            }
+        }
+    sink(out.data(), out.size());
+}
+// GCTA's binary form: values(data, n), counts(data, n) and ids(data, n) receive the bytes of PATH.grm.bin, PATH.grm.N.bin -- float32, the lower
+// triangle row by row, diagonal included: (float)((double)S / ((double)N 1048576.0)), 0 where N is 0, and N as a float -- and PATH.grm.id,
+// NAME\tNAME per sample.
+template <class Values, class Counts, class Ids> void grm_gcta(const GrmState &st, const std::vector<std::string> &names, Values &&values, Counts &&counts, Ids &&ids)
+{
+    const size_t S = names.size();
+    if (st.sum.size() != S * (S + 1) / 2 || st.n.size() != st.sum.size()) throw std::logic_error("grm_gcta: a state that is not the names'");
+    std::vector<float> val, cnt;
+    for (size_t i = 0; i < S; ++i) {
+        val.resize(i + 1), cnt.resize(i + 1);
+        for (size_t j = 0; j <= i; ++j) { // the pair a = j, b = i
+            const size_t k = j * (2 * S - j + 1) / 2 + (i - j);
+            val[j] = st.n[k] ? (float)((double)st.sum[k] / ((double)st.n[k] * 1048576.0)) : 0.f;
+            cnt[j] = (float)st.n[k];
+        }
+        values((const char *)val.data(), 4 * (i + 1));
+        counts((const char *)cnt.data(), 4 * (i + 1));
+    }
+    std::string id;
+    for (const std::string &name : names) id += name + "\t" + name + "\n";
+    ids(id.data(), id.size());
 }
 
 // ---- the paste passes over the groups' blocks of the merged output -----------------------------------------------------------------

@@ -140,6 +140,18 @@ const char *USAGE =
     "                                        the GPU, the same bytes whatever the grouping; beside -o and/or --merged        [this build]\n"
     "          --ibd-min-records             --ibd: the fewest records (N) of a segment written, 1 or more (default:100)     [this build]\n"
     "          --ibd-min-bp                  --ibd: the smallest LENGTH written (default:1000000; 0: no limit)               [this build]\n"
+    "          --grm                         --cohort: PATH receives the genetic relationship matrix of the cohort's samples, a tab-separated\n"
+    "                                        table with one line per pair A <= B in the manifest's order: A B N GRM -- N the biallelic records\n"
+    "                                        that enter and where both samples are called (--min-gq applies), GRM the mean over them of the\n"
+    "                                        product of the two standardised dosages (d - 2p) / sqrt(2p(1 - p)), p the record's allele\n"
+    "                                        frequency in the cohort; six decimals, `.` where N is 0.  Exact: 16-bit fixed-point weights,\n"
+    "                                        integer sums on the GPU's matrix cores, the same bytes whatever the grouping; beside -o and/or\n"
+    "                                        --merged                                                                         [this build]\n"
+    "          --grm-min-maf                 --grm: the smallest minor allele frequency of a record that enters, 0 .. 0.5 with at most six\n"
+    "                                        decimals (default:0.01; below about 0.002 a record's weights leave 16 bits and it stays out) [this build]\n"
+    "          --grm-min-n                   --grm: the fewest called samples of a record that enters, 1 or more (default:2)   [this build]\n"
+    "          --grm-format                  --grm: tsv (default) or gcta -- PATH.grm.bin, PATH.grm.N.bin (float32, lower triangle row by\n"
+    "                                        row) and PATH.grm.id, as GCTA and PLINK read them                                [this build]\n"
     "          --cohort-priors               --cohort: the allele priors of every record are re-estimated from ALL samples of the cohort\n"
     "                                        before the genotypes are made -- a few EM steps from the panel's AF (or -u's uniform\n"
     "                                        prior), anchored to it -- and every sample is genotyped under the cohort's frequencies.\n"
@@ -209,6 +221,8 @@ bool parse_arguments(int argc, char **argv, Options &o)
                                       {"ld-min-n", required_argument, nullptr, 1024},
                                       {"ibd", required_argument, nullptr, 1025},      {"ibd-min-records", required_argument, nullptr, 1026},
                                       {"ibd-min-bp", required_argument, nullptr, 1027},
+                                      {"grm", required_argument, nullptr, 1028},      {"grm-min-maf", required_argument, nullptr, 1029},
+                                      {"grm-min-n", required_argument, nullptr, 1030}, {"grm-format", required_argument, nullptr, 1031},
                                       {nullptr, 0, nullptr, 0}};
     bool die = false;
     optind = 1;
@@ -359,6 +373,57 @@ bool parse_arguments(int argc, char **argv, Options &o)
             else o.ibd_min_bp = v;
             break;
         }
+        case 1028:
+            o.grm = optarg;
+            if (o.grm.empty()) {
+                std::cerr << "malva : --grm takes a path\n";
+                die = true;
+            }
+            break;
+        case 1029: {
+            // the decimal text read exactly: [D][.DDDDDD], parts per million
+            const std::string text = optarg;
+            const size_t dot = text.find('.');
+            const std::string head = text.substr(0, dot), tail = dot == std::string::npos ? std::string() : text.substr(dot + 1);
+            bool ok = head.size() + tail.size() >= 1 && head.size() <= 1 && tail.size() <= 6;
+            for (const char ch : head + tail) ok = ok && ch >= '0' && ch <= '9';
+            uint32_t ppm = 0;
+            if (ok) {
+                ppm = head.empty() ? 0 : (uint32_t)(head[0] - '0') * 1000000u;
+                uint32_t scale = 100000;
+                for (const char ch : tail) ppm += (uint32_t)(ch - '0') * scale, scale /= 10;
+            }
+            o.grm_sub = true;
+            if (!ok || ppm > 500000) {
+                std::cerr << "malva : --grm-min-maf takes a decimal number 0 .. 0.5 with at most six decimals\n";
+                die = true;
+            } else o.grm_maf_ppm = ppm;
+            break;
+        }
+        case 1030: {
+            const std::string text = optarg;
+            unsigned long long v = 0;
+            bool ok = !text.empty() && text.size() <= 10;
+            for (const char ch : text) {
+                ok = ok && ch >= '0' && ch <= '9';
+                if (ok) v = v * 10 + (ch - '0');
+            }
+            o.grm_sub = true;
+            if (!ok || v < 1 || v > 0xFFFFFFFFull) {
+                std::cerr << "malva : --grm-min-n takes a whole number 1..4294967295\n";
+                die = true;
+            } else o.grm_min_n = (uint32_t)v;
+            break;
+        }
+        case 1031: {
+            const std::string text = optarg;
+            o.grm_sub = true;
+            if (text != "tsv" && text != "gcta") {
+                std::cerr << "malva : --grm-format takes tsv or gcta\n";
+                die = true;
+            } else o.grm_gcta = text == "gcta";
+            break;
+        }
         case 1012: o.priors.on = true; break;
         case 1013:
             if (!parse_prior_iters(optarg, o.priors)) {
@@ -466,6 +531,14 @@ bool parse_arguments(int argc, char **argv, Options &o)
     }
     if (o.ibd.empty() && o.ibd_sub) {
         std::cerr << "malva : --ibd-min-records and --ibd-min-bp go with --ibd\n";
+        die = true;
+    }
+    if (!o.cohort && !o.grm.empty()) {
+        std::cerr << "malva : --grm goes with --cohort\n";
+        die = true;
+    }
+    if (o.grm.empty() && o.grm_sub) {
+        std::cerr << "malva : --grm-min-maf, --grm-min-n and --grm-format go with --grm\n";
         die = true;
     }
     if (const std::string why = check_prior_options(o.priors, o.cohort); !why.empty()) {
@@ -1509,6 +1582,12 @@ int call_main(const Options &o)
         std::deque<PartFile> ibd_files;
         std::vector<size_t> ibd_group_sizes;
         PartFile ibd_file;
+        // --grm: the same words in a stream of its own, PATH.gN.grm.part; the pass behind the last group hands them to the device chunk by chunk, where
+        // the pairs' sums stay, and writes the table (PATH.part, renamed at the end) or GCTA's three files
+        const bool want_grm = !o.grm.empty();
+        std::deque<PartFile> grm_files;
+        std::vector<size_t> grm_group_sizes;
+        PartFile grm_file, grm_bin, grm_n_bin, grm_id;
         std::vector<std::string> names;
         for (const auto &sm : samples) names.push_back(sm.name);
         const bool merged_stdout = o.merged == "-";
@@ -1630,6 +1709,7 @@ int call_main(const Options &o)
             }
             if (want_ld) to.ld = &open_scratch(ld_files, o.ld, ".ld.part"), to.ld_cols = s0 == 0;
             if (want_ibd) to.ibd = &open_scratch(ibd_files, o.ibd, ".sites.part"), to.ibd_cols = s0 == 0, ibd_group_sizes.push_back(g);
+            if (want_grm) to.grm = &open_scratch(grm_files, o.grm, ".grm.part"), to.grm_cols = s0 == 0, grm_group_sizes.push_back(g);
             for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
                 to.per_sample.emplace_back();
                 to.per_sample.back().open(o.out_dir + "/" + samples[s0 + i].name + ".vcf");
@@ -1660,6 +1740,7 @@ int call_main(const Options &o)
             if (to.site_stats) to.site_stats->close(to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
             if (to.ld) to.ld->close("cannot write the LD table's words");
             if (to.ibd) to.ibd->close("cannot write the IBD table's words");
+            if (to.grm) to.grm->close("cannot write the GRM's words");
             if (to.merged) {
                 if (bcf_out && bcf_bgzf && merged_direct) to.merged->write(bgzf_eof(), "cannot write the merged output");
                 to.merged->close("cannot write the merged output");
@@ -1788,6 +1869,36 @@ int call_main(const Options &o)
             if (S >= 2) dev.check(mg_ibd_end(dev.ctx), "mg_ibd_end");
             ibd_files.clear(); // (the groups' streams go before the table takes its name)
             ibd_file.finish("cannot write the IBD table");
+        }
+        if (want_grm) {
+            Timed t("cohort: grm pass");
+            if (o.grm_gcta) grm_bin.open(o.grm + ".grm.bin"), grm_n_bin.open(o.grm + ".grm.N.bin"), grm_id.open(o.grm + ".grm.id");
+            else grm_file.open(o.grm);
+            dev.check(mg_grm_begin(dev.ctx, (uint32_t)S, o.haploid, o.grm_maf_ppm, o.grm_min_n), "mg_grm_begin");
+            const GrmState st = grm_table(
+                grm_files, grm_group_sizes, geno_batch_records(65536),
+                [&](size_t n_vars, size_t n_groups, const uint64_t *sites) {
+                    dev.check(mg_grm_step(dev.ctx, n_vars, (uint32_t)n_groups, sites), "mg_grm_step");
+                    float ms[3] = {0, 0, 0};
+                    dev.check(mg_grm_stats(dev.ctx, ms), "mg_grm_stats");
+                    times.grm.ms[1] += ms[0], times.grm.ms[2] += ms[1];
+                    ++times.grm.calls[1];
+                },
+                [&](int64_t *sum, uint64_t *count, uint64_t *records) { dev.check(mg_grm_read(dev.ctx, sum, count, records), "mg_grm_read"); });
+            dev.check(mg_grm_end(dev.ctx), "mg_grm_end");
+            std::cerr << "[malva-geno] grm: " << st.records[0] << " records seen, " << st.records[1] << " entered" << std::endl;
+            grm_files.clear(); // (the groups' streams go before the outputs take their names)
+            const char *what = "cannot write the GRM";
+            if (o.grm_gcta) {
+                grm_gcta(
+                    st, names, [&](const char *data, size_t n) { grm_bin.write(data, n, what); }, [&](const char *data, size_t n) { grm_n_bin.write(data, n, what); },
+                    [&](const char *data, size_t n) { grm_id.write(data, n, what); });
+                grm_bin.close(what), grm_n_bin.close(what), grm_id.close(what);
+                grm_bin.finish(what), grm_n_bin.finish(what), grm_id.finish(what);
+            } else {
+                grm_text(st, names, [&](const char *data, size_t n) { grm_file.write(data, n, what); });
+                grm_file.finish(what);
+            }
         }
         priors_file.finish();
         times.add_to_timers();

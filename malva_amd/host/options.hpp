@@ -42,6 +42,11 @@ struct Options { // argument_parser.hpp:51-66
     bool ibd_sub = false;   // one of --ibd's sub-options was given
     uint32_t ibd_min_records = 100;   // --ibd-min-records: the fewest records of a segment written
     uint64_t ibd_min_bp = 1000000;    // --ibd-min-bp: and its smallest END - START (0: no limit)
+    std::string grm;        // --grm: the genetic relationship matrix of the cohort's samples
+    bool grm_sub = false;   // one of --grm's sub-options was given
+    uint32_t grm_maf_ppm = 10000;     // --grm-min-maf: the smallest minor allele frequency of a record that enters, in parts per million
+    uint32_t grm_min_n = 2;           // --grm-min-n: the fewest called samples of a record that enters
+    bool grm_gcta = false;            // --grm-format gcta: PATH.grm.bin, PATH.grm.N.bin, PATH.grm.id instead of the text
     PriorOptions priors;    // --cohort-priors and its sub-options (host/cohort_priors.hpp)
 };
 
