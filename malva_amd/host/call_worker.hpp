@@ -167,16 +167,12 @@ struct PassOut {
     PartFile *site_stats = nullptr;
     bool site_stats_stream = false, site_stats_cols = false;
     size_t site_stats_samples = 0; // the cohort's size
-    // --ld: the records' words over the group's planes are made while the batch is in hand (mg_pack_site_dosage) and go here in output order
-    // (put_ld_words, with the records' columns when ld_cols) for the pass behind the last group (ld_table)
-    PartFile *ld = nullptr;
-    bool ld_cols = false;
-    // --ibd: the same words and columns in a stream of its own, for its pass behind the last group (ibd_table)
-    PartFile *ibd = nullptr;
-    bool ibd_cols = false;
-    // --grm: the same words and columns in a stream of its own, for its pass behind the last group (grm_table)
-    PartFile *grm = nullptr;
-    bool grm_cols = false;
+    // --ld, --ibd, --grm: the records' words over the group's planes are made while the batch is in hand (mg_pack_site_dosage) and go here in output
+    // order (put_site_words, with the records' columns when site_words_cols): one stream for the passes behind the last group (ld_table, ibd_table,
+    // grm_table).  site_words_for: the first of the three options that is given -- its timer and its CallTimes::Kind take the pack calls
+    PartFile *site_words = nullptr;
+    bool site_words_cols = false;
+    enum SiteWordsFor { LD, IBD, GRM } site_words_for = LD;
     // --prior-groups, a cohort in several groups (host/cohort_priors.hpp).  prior_cov: the coverage pass -- the batches' coverages go here
     // (put_cov_batch; the first group's with the records' offsets and panel priors), and the pass makes no calls and nothing else.
     // prior_in: the output pass -- the batches' coverages and the cohort's frequencies come from here instead of the counters, and the
@@ -187,7 +183,7 @@ struct PassOut {
 };
 struct BatchText { // the text of one batch, as its worker hands it over
     std::vector<std::string> per_sample;
-    std::string merged, site_counts, pack, priors, prior_cov, site_stats, ld, ibd, grm; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
+    std::string merged, site_counts, pack, priors, prior_cov, site_stats, site_words; // priors: the lines of --priors-out; prior_cov: the coverage pass's bytes
     CallTimes times; // of this batch's calls alone
 };
 
@@ -248,9 +244,7 @@ public:
         if (to.merged) fflush(to.merged->f);
         if (to.site_counts) fflush(to.site_counts->f);
         if (to.site_stats) fflush(to.site_stats->f);
-        if (to.ld) fflush(to.ld->f);
-        if (to.ibd) fflush(to.ibd->f);
-        if (to.grm) fflush(to.grm->f);
+        if (to.site_words) fflush(to.site_words->f);
     }
 
 private:
@@ -301,9 +295,7 @@ private:
             priors_file.write(text.priors);
             if (to.prior_cov) to.prior_cov->write(text.prior_cov, "cannot write the coverages for the cohort's priors");
             if (to.site_stats) to.site_stats->write(text.site_stats, to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
-            if (to.ld) to.ld->write(text.ld, "cannot write the LD table's words");
-            if (to.ibd) to.ibd->write(text.ibd, "cannot write the IBD table's words");
-            if (to.grm) to.grm->write(text.grm, "cannot write the GRM's words");
+            if (to.site_words) to.site_words->write(text.site_words, "cannot write the records' site words");
         }
     }
 
@@ -340,7 +332,7 @@ private:
             if (to.pairs) pair_table(dev, job, text);
             if (to.sample_table) sample_table(dev, job, text.times);
             if (to.site_stats) site_table(dev, job, geno, text.times);
-            if (to.ld || to.ibd || to.grm) ld_words(dev, job, words, text.times);
+            if (to.site_words) site_words(dev, job, words, text.times);
         } // the records' text needs no device
         records_text(job, rows, geno, words, text);
         return text;
@@ -594,9 +586,10 @@ private:
         }
     }
 
-    void ld_words(Device &dev, Job &job, SiteWords &sw, CallTimes &times)
+    void site_words(Device &dev, Job &job, SiteWords &sw, CallTimes &times)
     {
-        Timed t_ld(to.ld ? "worker: ld words (mg_pack_site_dosage)" : to.ibd ? "worker: ibd words (mg_pack_site_dosage)" : "worker: grm words (mg_pack_site_dosage)");
+        const PassOut::SiteWordsFor asked = to.site_words_for;
+        Timed t_words(asked == PassOut::LD ? "worker: ld words (mg_pack_site_dosage)" : asked == PassOut::IBD ? "worker: ibd words (mg_pack_site_dosage)" : "worker: grm words (mg_pack_site_dosage)");
         for (int w = 0; w < 2; ++w) {
             Batch &b = w ? job.gen : job.iso;
             const size_t bn = b.n();
@@ -607,7 +600,7 @@ private:
                       "mg_pack_site_dosage");
             float ms[2] = {0, 0};
             dev.check(mg_ld_stats(dev.ctx, ms), "mg_ld_stats");
-            (to.ld ? times.ld : to.ibd ? times.ibd : times.grm).add(ms, 1);
+            (asked == PassOut::LD ? times.ld : asked == PassOut::IBD ? times.ibd : times.grm).add(ms, 1);
         }
     }
 
@@ -620,20 +613,11 @@ private:
             const int w = r.isolated ? 0 : 1;
             if (priors_file.f) priors_row(text.priors, r.prefix, r.n_alleles, b.freq.data() + r.allele0, b.freq_out.data() + r.allele0, b.n_inf[r.slot]);
             if (tags && to.site_counts) put_site_counts(text.site_counts, r.n_alleles, rows.site_ns[w][r.slot], rows.site_ac[w].data() + r.allele0);
-            if (to.ld) {
+            if (to.site_words) {
                 const std::vector<uint64_t> &sw = words.w[w];
                 const size_t bn = sw.size() / 3;
-                put_ld_words(text.ld, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.ld_cols ? r.prefix.data() : nullptr, site_stats_cols(r.prefix));
-            }
-            if (to.ibd) {
-                const std::vector<uint64_t> &sw = words.w[w];
-                const size_t bn = sw.size() / 3;
-                put_ld_words(text.ibd, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.ibd_cols ? r.prefix.data() : nullptr, site_stats_cols(r.prefix));
-            }
-            if (to.grm) {
-                const std::vector<uint64_t> &sw = words.w[w];
-                const size_t bn = sw.size() / 3;
-                put_ld_words(text.grm, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.grm_cols ? r.prefix.data() : nullptr, site_stats_cols(r.prefix));
+                put_site_words(text.site_words, sw[r.slot], sw[bn + r.slot], sw[2 * bn + r.slot], r.n_alleles, to.site_words_cols ? r.prefix.data() : nullptr,
+                               site_stats_cols(r.prefix));
             }
             if (!to.site_stats) continue;
             const uint32_t *het = geno.het[w].data() + r.allele0, *hom = geno.hom[w].data() + r.allele0;

@@ -1,9 +1,10 @@
 // cohort_out.hpp -- the host-only half of the outputs of `call --cohort`: the streams a group leaves for the passes behind the last group
-// (the records' site counts, the packed calls, the records' genotype counts, the records' words for the LD and IBD tables and the GRM), the two paste passes over the groups'
+// (the records' site counts, the packed calls, the records' genotype counts, the records' site words -- one stream for the LD table, the IBD table and the GRM), the two paste passes over the groups'
 // blocks of the merged output, and the text of the --pairs, --sample-stats, --site-stats, --ld, --ibd and --grm tables.  No device is needed: what needs one comes in as a callable (tools/cohort_out_host_check.cpp, tools/site_table_host_check.cpp
 // tools/ld_out_host_check.cpp, tools/ibd_out_host_check.cpp and tools/grm_out_host_check.cpp drive this file alone).
 #pragma once
 #include <deque>
+#include <numeric>
 
 #include "../../include/malva_hip.h" // (the MG_SS_* slots of the sample table; nothing here calls the library)
 #include "bcf_out.hpp"
@@ -311,13 +312,11 @@ template <class Hwe, class Sink> void site_stats_groups(const std::deque<PartFil
     in.end();
 }
 
-// ---- the LD table (--ld) -------------------------------------------------------------------------------------------------------
-// One line per emitted pair of records (mg_ld_window): A's CHROM, POS and ID, B's POS and ID, N (the samples that contribute in both), R2 to six
-// significant digits and the sign of the covariance.  Lines are in the order of the merged output, by A, then by B.
-inline const char *ld_header() { return "#CHROM\tPOS_A\tID_A\tPOS_B\tID_B\tN\tR2\tSIGN\n"; }
+// ---- the records' site words (--ld, --ibd, --grm) ---------------------------------------------------------------------------------
 // Every group -- a cohort of one group too -- leaves per record, in output order, the three u64 words of mg_pack_site_dosage over its planes and the
-// u32 n_alleles; the first group's stream has behind each record a u32 length and that many bytes, the record's first five columns.
-inline void put_ld_words(std::string &out, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t n_alleles, const char *cols, size_t cols_len)
+// u32 n_alleles; the first group's stream has behind each record a u32 length and that many bytes, the record's first five columns.  One stream per
+// group serves the three tables: each of their passes behind the last group reads it with a reader of its own.
+inline void put_site_words(std::string &out, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t n_alleles, const char *cols, size_t cols_len)
 {
     const uint64_t w[3] = {w0, w1, w2};
     out.append((const char *)w, 24);
@@ -327,18 +326,9 @@ inline void put_ld_words(std::string &out, uint64_t w0, uint64_t w1, uint64_t w2
     out.append((const char *)&len, 4);
     out.append(cols, cols_len);
 }
-inline void ld_row(std::string &out, const std::string &a, const std::string &b, size_t b_pos_at, const mg_ld_pair &p)
-{
-    char num[64];
-    out += a;
-    out += '\t';
-    out.append(b, b_pos_at, std::string::npos);
-    snprintf(num, sizeof num, "\t%u\t%.6g\t%c\n", p.n, p.r2, p.sign > 0 ? '+' : p.sign < 0 ? '-' : '0');
-    out += num;
-}
 // The groups' streams read in step.  The reader holds a run of records: words [record][group][3], the records' CHROM\tPOS\tID, a running contig
 // id that steps whenever the CHROM text changes, and POS parsed.
-struct LdReader {
+struct SiteWordsReader {
     GroupFiles in;
     size_t G;
     std::vector<uint64_t> words;
@@ -348,12 +338,12 @@ struct LdReader {
     std::string last_chrom, five;
     uint32_t chrom_id = 0;
     bool any = false, ended = false;
-    const char *short_file = "internal: a group's words for the LD table are short";
-    explicit LdReader(const std::deque<PartFile> &files)
+    const char *const short_file; // the pass's own text: "internal: a group's words for the ... are short"
+    SiteWordsReader(const std::deque<PartFile> &files, const char *short_file) : short_file(short_file)
     {
         in.open(files);
         G = in.f.size();
-        if (!G) throw std::logic_error("LdReader: no group");
+        if (!G) throw std::logic_error("SiteWordsReader: no group");
     }
     size_t held() const { return cols.size(); }
     // one more record behind those held; false where the first group's stream ends (every later group's must end there too)
@@ -414,13 +404,64 @@ struct LdReader {
             for (size_t k = 0; k < 3 * G; ++k) out[k * n + v] = words[v * 3 * G + k];
     }
 };
+inline size_t cohort_size(const std::vector<size_t> &group_sizes) { return std::accumulate(group_sizes.begin(), group_sizes.end(), (size_t)0); }
+// The records held by a reader over groups of group_sizes[g] samples (bits 0 .. size - 1 of a group's words) as mg_ibd_step and mg_grm_step take
+// them: the cohort's samples side by side, sample s in bit s & 63 of word s >> 6, [ceil(S / 64)][3][held] -- whatever the grouping was.
+inline void cohort_sites(const SiteWordsReader &in, const std::vector<size_t> &group_sizes, std::vector<uint64_t> &out)
+{
+    const size_t n = in.held(), W = (cohort_size(group_sizes) + 63) / 64;
+    out.assign(3 * W * n, 0);
+    for (size_t v = 0; v < n; ++v) {
+        size_t s0 = 0;
+        for (size_t gi = 0; gi < in.G; ++gi) {
+            const size_t g = group_sizes[gi], word = s0 >> 6, bit = s0 & 63;
+            const uint64_t mask = g >= 64 ? ~0ull : (1ull << g) - 1;
+            for (size_t d = 0; d < 3; ++d) {
+                const uint64_t w = in.words[(v * in.G + gi) * 3 + d] & mask;
+                out[(word * 3 + d) * n + v] |= w << bit;
+                if (bit && bit + g > 64) out[((word + 1) * 3 + d) * n + v] |= w >> (64 - bit);
+            }
+            s0 += g;
+        }
+    }
+}
+// The front of the two passes without look-ahead (ibd_table and grm_table; `who` starts their logic errors): the reader's streams walked `chunk` records
+// at a time.  each(sites, ended, in) gets a chunk's cohort_sites and whether the streams have ended; the reader still holds the chunk (held(), cols,
+// chrom, pos), which is dropped behind the call.  The last call is the one with `ended` set: its chunk is empty where the records end on a chunk's edge.
+template <class Each> void walk_cohort_sites(SiteWordsReader &in, const std::vector<size_t> &group_sizes, size_t chunk, const std::string &who, Each &&each)
+{
+    for (const size_t g : group_sizes)
+        if (g < 1 || g > 64) throw std::logic_error(who + ": a group of 1..64 samples");
+    if (!chunk || group_sizes.size() != in.G) throw std::logic_error(who + ": an empty chunk, or groups that are not the streams'");
+    std::vector<uint64_t> sites;
+    do {
+        while (in.held() < chunk && in.read_one()) {}
+        cohort_sites(in, group_sizes, sites);
+        each(sites, in.ended, in);
+        in.drop(in.held());
+    } while (!in.ended);
+}
+
+// ---- the LD table (--ld) -------------------------------------------------------------------------------------------------------
+// One line per emitted pair of records (mg_ld_window): A's CHROM, POS and ID, B's POS and ID, N (the samples that contribute in both), R2 to six
+// significant digits and the sign of the covariance.  Lines are in the order of the merged output, by A, then by B.
+inline const char *ld_header() { return "#CHROM\tPOS_A\tID_A\tPOS_B\tID_B\tN\tR2\tSIGN\n"; }
+inline void ld_row(std::string &out, const std::string &a, const std::string &b, size_t b_pos_at, const mg_ld_pair &p)
+{
+    char num[64];
+    out += a;
+    out += '\t';
+    out.append(b, b_pos_at, std::string::npos);
+    snprintf(num, sizeof num, "\t%u\t%.6g\t%c\n", p.n, p.r2, p.sign > 0 ? '+' : p.sign < 0 ? '-' : '0');
+    out += num;
+}
 // The pass behind the last group: the header, then the pairs' lines, `chunk` records at a time with a look-ahead of `window` records that become the
 // head of the next chunk.  ld(n_vars, n_first, n_groups, sites, chrom, pos, pairs_out, pairs_cap, row_off_out, n_pairs_out) is mg_ld_window with the
 // run's options, whoever holds the device: it returns MG_OK or MG_ERR_LIMIT (then the buffer grows and it is called once more).  The text goes
 // to sink(data, n).
 template <class Ld, class Sink> void ld_table(const std::deque<PartFile> &files, size_t window, size_t chunk, Ld &&ld, Sink &&sink)
 {
-    LdReader in(files);
+    SiteWordsReader in(files, "internal: a group's words for the LD table are short");
     std::string out = ld_header();
     std::vector<uint64_t> sites, row_off;
     std::vector<mg_ld_pair> pairs(1024);
@@ -466,69 +507,39 @@ inline void ibd_row(std::string &out, const std::string &a, const std::string &b
     snprintf(num, sizeof num, "\t%u\t%u\t%lld\t%u\t%u\n", s.start_pos, s.end_pos, (long long)s.end_pos - (long long)s.start_pos, s.n, s.ibs2);
     out += num;
 }
-// The records held by an LdReader over groups of group_sizes[g] samples (bits 0 .. size - 1 of a group's words) as mg_ibd_step takes them: the
-// cohort's samples side by side, sample s in bit s & 63 of word s >> 6, [ceil(S / 64)][3][held] -- whatever the grouping was.
-inline void ibd_cohort_sites(const LdReader &in, const std::vector<size_t> &group_sizes, std::vector<uint64_t> &out)
-{
-    size_t S = 0;
-    for (const size_t g : group_sizes) S += g;
-    const size_t n = in.held(), W = (S + 63) / 64;
-    out.assign(3 * W * n, 0);
-    for (size_t v = 0; v < n; ++v) {
-        size_t s0 = 0;
-        for (size_t gi = 0; gi < in.G; ++gi) {
-            const size_t g = group_sizes[gi], word = s0 >> 6, bit = s0 & 63;
-            const uint64_t mask = g >= 64 ? ~0ull : (1ull << g) - 1;
-            for (size_t d = 0; d < 3; ++d) {
-                const uint64_t w = in.words[(v * in.G + gi) * 3 + d] & mask;
-                out[(word * 3 + d) * n + v] |= w << bit;
-                if (bit && bit + g > 64) out[((word + 1) * 3 + d) * n + v] |= w >> (64 - bit);
-            }
-            s0 += g;
-        }
-    }
-}
-// The pass behind the last group: the groups' streams walked `chunk` records at a time -- no look-ahead: the pairs' state stays on the device between
-// the steps -- the closed segments collected, put into (A, B, along the records) order by a stable sort by (A, B) of the steps' outputs, and written.
+// The pass behind the last group: the groups' streams walked `chunk` records at a time (walk_cohort_sites) -- no look-ahead: the pairs' state stays on the
+// device between the steps -- the closed segments collected, put into (A, B, along the records) order by a stable sort by (A, B) of the steps' outputs, and written.
 // The whole table is held in memory, 32 bytes per segment.  step(n_vars, n_groups, sites, chrom, pos, flush, segs_out, segs_cap, n_segs_out) is
 // mg_ibd_step behind an mg_ibd_begin for names.size() samples, whoever holds the device: it returns MG_OK or MG_ERR_LIMIT (then the buffer grows
-// and it is called once more; the state has not moved).  A cohort of one sample has no pair: the header alone.  The text goes to sink(data, n).
+// and it is called once more; the state has not moved).  A cohort of one sample has no pair: the header alone, and the streams
+// are not read.  The text goes to sink(data, n).
 template <class Step, class Sink>
 void ibd_table(const std::deque<PartFile> &files, const std::vector<size_t> &group_sizes, const std::vector<std::string> &names, size_t chunk, Step &&step, Sink &&sink)
 {
-    LdReader in(files);
-    in.short_file = "internal: a group's words for the IBD table are short";
-    size_t S = 0;
-    for (const size_t g : group_sizes) {
-        if (g < 1 || g > 64) throw std::logic_error("ibd_table: a group of 1..64 samples");
-        S += g;
-    }
-    if (!chunk || group_sizes.size() != in.G || S != names.size()) throw std::logic_error("ibd_table: an empty chunk, or groups that are not the streams'");
+    SiteWordsReader reader(files, "internal: a group's words for the IBD table are short");
+    const size_t S = names.size();
+    if (cohort_size(group_sizes) != S) throw std::logic_error("ibd_table: groups that are not the names'");
     std::string out = ibd_header();
     std::vector<mg_ibd_seg> all, segs(1024);
     std::vector<std::string> chrom_names; // by the reader's running contig id
-    std::vector<uint64_t> sites;
-    while (S >= 2) {
-        while (in.held() < chunk && in.read_one())
-            if (in.chrom.back() == chrom_names.size()) chrom_names.push_back(in.last_chrom);
-        const size_t n = in.held();
-        const int flush = in.ended;
-        ibd_cohort_sites(in, group_sizes, sites);
-        uint64_t needed = 0;
-        int rc = step(n, (S + 63) / 64, sites.data(), in.chrom.data(), in.pos.data(), flush, segs.data(), segs.size(), &needed);
-        if (rc == MG_ERR_LIMIT) {
-            segs.resize(needed);
-            rc = step(n, (S + 63) / 64, sites.data(), in.chrom.data(), in.pos.data(), flush, segs.data(), segs.size(), &needed);
-        }
-        if (rc != MG_OK || needed > segs.size()) throw std::runtime_error("internal: the IBD table's segments do not fit their buffer");
-        for (uint64_t k = 0; k < needed; ++k) {
-            const mg_ibd_seg &s = segs[k];
-            if (s.a >= s.b || s.b >= S || s.chrom >= chrom_names.size()) throw std::runtime_error("internal: a segment of the IBD table names no pair or no contig");
-        }
-        all.insert(all.end(), segs.begin(), segs.begin() + needed);
-        in.drop(n);
-        if (flush) break;
-    }
+    if (S >= 2)
+        walk_cohort_sites(reader, group_sizes, chunk, "ibd_table", [&](const std::vector<uint64_t> &sites, const int flush, const SiteWordsReader &in) {
+            const size_t n = in.held();
+            for (size_t v = 0; v < n; ++v)
+                if (in.chrom[v] == chrom_names.size()) chrom_names.emplace_back(in.cols[v], 0, in.pos_at[v] - 1);
+            uint64_t needed = 0;
+            int rc = step(n, (S + 63) / 64, sites.data(), in.chrom.data(), in.pos.data(), flush, segs.data(), segs.size(), &needed);
+            if (rc == MG_ERR_LIMIT) {
+                segs.resize(needed);
+                rc = step(n, (S + 63) / 64, sites.data(), in.chrom.data(), in.pos.data(), flush, segs.data(), segs.size(), &needed);
+            }
+            if (rc != MG_OK || needed > segs.size()) throw std::runtime_error("internal: the IBD table's segments do not fit their buffer");
+            for (uint64_t k = 0; k < needed; ++k) {
+                const mg_ibd_seg &s = segs[k];
+                if (s.a >= s.b || s.b >= S || s.chrom >= chrom_names.size()) throw std::runtime_error("internal: a segment of the IBD table names no pair or no contig");
+            }
+            all.insert(all.end(), segs.begin(), segs.begin() + needed);
+        });
     std::stable_sort(all.begin(), all.end(), [](const mg_ibd_seg &x, const mg_ibd_seg &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
     for (const mg_ibd_seg &s : all) {
         ibd_row(out, names[s.a], names[s.b], chrom_names[s.chrom], s);
@@ -562,30 +573,16 @@ struct GrmState { // mg_grm_read's outputs: pair (a, b), a <= b, row-major
     std::vector<uint64_t> n;
     uint64_t records[2] = {0, 0}; // seen, entered
 };
-// The pass behind the last group: the groups' streams walked `chunk` records at a time, the cohort's bits put side by side (ibd_cohort_sites) and
+// The pass behind the last group: the groups' streams walked `chunk` records at a time (walk_cohort_sites) and every chunk that holds a record
 // handed to step(n_vars, n_groups, sites) -- mg_grm_step behind an mg_grm_begin for the groups' samples, whoever holds the device; the pairs' sums
 // stay there between the steps.  read(sum, n, records) -- mg_grm_read -- is called once, behind the last step.
 template <class Step, class Read> GrmState grm_table(const std::deque<PartFile> &files, const std::vector<size_t> &group_sizes, size_t chunk, Step &&step, Read &&read)
 {
-    LdReader in(files);
-    in.short_file = "internal: a group's words for the GRM are short";
-    size_t S = 0;
-    for (const size_t g : group_sizes) {
-        if (g < 1 || g > 64) throw std::logic_error("grm_table: a group of 1..64 samples");
-        S += g;
-    }
-    if (!chunk || group_sizes.size() != in.G) throw std::logic_error("grm_table: an empty chunk, or groups that are not the streams'");
-    std::vector<uint64_t> sites;
-    for (;;) {
-        while (in.held() < chunk && in.read_one()) {}
-        const size_t n = in.held();
-        if (n) {
-            ibd_cohort_sites(in, group_sizes, sites);
-            step(n, (S + 63) / 64, (const uint64_t *)sites.data());
-            in.drop(n);
-        }
-        if (in.ended) break;
-    }
+    SiteWordsReader reader(files, "internal: a group's words for the GRM are short");
+    const size_t S = cohort_size(group_sizes);
+    walk_cohort_sites(reader, group_sizes, chunk, "grm_table", [&](const std::vector<uint64_t> &sites, bool, const SiteWordsReader &in) {
+        if (in.held()) step(in.held(), (S + 63) / 64, sites.data());
+    });
     GrmState st;
     st.sum.resize(S * (S + 1) / 2), st.n.resize(S * (S + 1) / 2);
     read(st.sum.data(), st.n.data(), st.records);

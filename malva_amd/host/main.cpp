@@ -1571,23 +1571,17 @@ int call_main(const Options &o)
         const bool want_site = !o.site_stats.empty();
         std::deque<PartFile> geno_files;
         PartFile site_file;
-        // --ld: every group -- one group too -- leaves its records' words over its planes in PATH.gN.ld.part; the pass behind the last group reads
-        // them in step, forms r2 over all groups on the device and writes the table (PATH.part, renamed at the end)
-        const bool want_ld = !o.ld.empty();
-        std::deque<PartFile> ld_files;
-        PartFile ld_file;
-        // --ibd: the same words in a stream of its own, PATH.gN.sites.part; the pass behind the last group walks every pair of samples along them
-        // on the device, chunk by chunk, and writes the table (PATH.part, renamed at the end)
-        const bool want_ibd = !o.ibd.empty();
-        std::deque<PartFile> ibd_files;
-        std::vector<size_t> ibd_group_sizes;
-        PartFile ibd_file;
-        // --grm: the same words in a stream of its own, PATH.gN.grm.part; the pass behind the last group hands them to the device chunk by chunk, where
-        // the pairs' sums stay, and writes the table (PATH.part, renamed at the end) or GCTA's three files
-        const bool want_grm = !o.grm.empty();
-        std::deque<PartFile> grm_files;
-        std::vector<size_t> grm_group_sizes;
-        PartFile grm_file, grm_bin, grm_n_bin, grm_id;
+        // --ld, --ibd, --grm: every group -- one group too -- leaves its records' words over its planes in PATH.gN.sites.part, one stream for the three,
+        // beside the first of the three outputs that is given.  Their passes behind the last group read it one after the other, each with a reader of
+        // its own.  --ld: r2 formed over all groups on the device.  --ibd: every pair of samples walked along the records on the device, chunk by chunk.
+        // --grm: the chunks handed to the device, where the pairs' sums stay.  Each writes its table as PATH.part (--grm-format gcta: GCTA's three files).
+        // The groups' streams go before a table takes its name: the tables are renamed behind the last of the passes, LD, IBD, GRM, so a failure in a
+        // later pass leaves no earlier table under its name and no scratch file behind.
+        const bool want_ld = !o.ld.empty(), want_ibd = !o.ibd.empty(), want_grm = !o.grm.empty();
+        const std::string &site_words_base = want_ld ? o.ld : want_ibd ? o.ibd : o.grm;
+        std::deque<PartFile> site_word_files;
+        std::vector<size_t> site_word_group_sizes;
+        PartFile ld_file, ibd_file, grm_file, grm_bin, grm_n_bin, grm_id;
         std::vector<std::string> names;
         for (const auto &sm : samples) names.push_back(sm.name);
         const bool merged_stdout = o.merged == "-";
@@ -1707,9 +1701,11 @@ int call_main(const Options &o)
                     to.site_stats = &site_file;
                 }
             }
-            if (want_ld) to.ld = &open_scratch(ld_files, o.ld, ".ld.part"), to.ld_cols = s0 == 0;
-            if (want_ibd) to.ibd = &open_scratch(ibd_files, o.ibd, ".sites.part"), to.ibd_cols = s0 == 0, ibd_group_sizes.push_back(g);
-            if (want_grm) to.grm = &open_scratch(grm_files, o.grm, ".grm.part"), to.grm_cols = s0 == 0, grm_group_sizes.push_back(g);
+            if (want_ld || want_ibd || want_grm) {
+                to.site_words = &open_scratch(site_word_files, site_words_base, ".sites.part"), to.site_words_cols = s0 == 0;
+                site_word_group_sizes.push_back(g);
+                to.site_words_for = want_ld ? PassOut::LD : want_ibd ? PassOut::IBD : PassOut::GRM;
+            }
             for (size_t i = 0; i < g && !o.out_dir.empty(); ++i) {
                 to.per_sample.emplace_back();
                 to.per_sample.back().open(o.out_dir + "/" + samples[s0 + i].name + ".vcf");
@@ -1738,9 +1734,7 @@ int call_main(const Options &o)
                 for (size_t j = i + 1; j < g; ++j) std::copy_n(&pairs_run.counts[(i * g + j) * 9], 9, &pair_table[((s0 + i) * S + s0 + j) * 9]);
             if (to.site_counts) to.site_counts->close("cannot write the merged output's counts");
             if (to.site_stats) to.site_stats->close(to.site_stats_stream ? "cannot write the per-record table's counts" : "cannot write the per-record table");
-            if (to.ld) to.ld->close("cannot write the LD table's words");
-            if (to.ibd) to.ibd->close("cannot write the IBD table's words");
-            if (to.grm) to.grm->close("cannot write the GRM's words");
+            if (to.site_words) to.site_words->close("cannot write the records' site words");
             if (to.merged) {
                 if (bcf_out && bcf_bgzf && merged_direct) to.merged->write(bgzf_eof(), "cannot write the merged output");
                 to.merged->close("cannot write the merged output");
@@ -1834,7 +1828,7 @@ int call_main(const Options &o)
             Timed t("cohort: ld pass");
             ld_file.open(o.ld);
             ld_table(
-                ld_files, o.ld_window, geno_batch_records(65536),
+                site_word_files, o.ld_window, geno_batch_records(65536),
                 [&](size_t n_vars, size_t n_first, size_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, mg_ld_pair *pairs, size_t cap,
                     uint64_t *row_off, uint64_t *needed) {
                     const int rc = mg_ld_window(dev.ctx, n_vars, n_first, (uint32_t)n_groups, sites, chrom, pos, o.ld_window, o.ld_window_bp, o.ld_min_n, o.ld_min_r2, pairs, cap,
@@ -1847,15 +1841,14 @@ int call_main(const Options &o)
                     return rc;
                 },
                 [&](const char *data, size_t n) { ld_file.write(data, n, "cannot write the LD table"); });
-            ld_files.clear(); // (the groups' streams go before the table takes its name)
-            ld_file.finish("cannot write the LD table");
+            ld_file.close("cannot write the LD table");
         }
         if (want_ibd) {
             Timed t("cohort: ibd pass");
             ibd_file.open(o.ibd);
             if (S >= 2) dev.check(mg_ibd_begin(dev.ctx, (uint32_t)S, o.ibd_min_records, o.ibd_min_bp), "mg_ibd_begin");
             ibd_table(
-                ibd_files, ibd_group_sizes, names, geno_batch_records(65536),
+                site_word_files, site_word_group_sizes, names, geno_batch_records(65536),
                 [&](size_t n_vars, size_t n_groups, const uint64_t *sites, const uint32_t *chrom, const uint32_t *pos, int flush, mg_ibd_seg *segs, size_t cap, uint64_t *needed) {
                     const int rc = mg_ibd_step(dev.ctx, n_vars, (uint32_t)n_groups, sites, chrom, pos, flush, segs, cap, needed);
                     if (rc != MG_ERR_LIMIT) dev.check(rc, "mg_ibd_step");
@@ -1867,8 +1860,7 @@ int call_main(const Options &o)
                 },
                 [&](const char *data, size_t n) { ibd_file.write(data, n, "cannot write the IBD table"); });
             if (S >= 2) dev.check(mg_ibd_end(dev.ctx), "mg_ibd_end");
-            ibd_files.clear(); // (the groups' streams go before the table takes its name)
-            ibd_file.finish("cannot write the IBD table");
+            ibd_file.close("cannot write the IBD table");
         }
         if (want_grm) {
             Timed t("cohort: grm pass");
@@ -1876,7 +1868,7 @@ int call_main(const Options &o)
             else grm_file.open(o.grm);
             dev.check(mg_grm_begin(dev.ctx, (uint32_t)S, o.haploid, o.grm_maf_ppm, o.grm_min_n), "mg_grm_begin");
             const GrmState st = grm_table(
-                grm_files, grm_group_sizes, geno_batch_records(65536),
+                site_word_files, site_word_group_sizes, geno_batch_records(65536),
                 [&](size_t n_vars, size_t n_groups, const uint64_t *sites) {
                     dev.check(mg_grm_step(dev.ctx, n_vars, (uint32_t)n_groups, sites), "mg_grm_step");
                     float ms[3] = {0, 0, 0};
@@ -1887,19 +1879,16 @@ int call_main(const Options &o)
                 [&](int64_t *sum, uint64_t *count, uint64_t *records) { dev.check(mg_grm_read(dev.ctx, sum, count, records), "mg_grm_read"); });
             dev.check(mg_grm_end(dev.ctx), "mg_grm_end");
             std::cerr << "[malva-geno] grm: " << st.records[0] << " records seen, " << st.records[1] << " entered" << std::endl;
-            grm_files.clear(); // (the groups' streams go before the outputs take their names)
             const char *what = "cannot write the GRM";
-            if (o.grm_gcta) {
+            if (o.grm_gcta)
                 grm_gcta(
                     st, names, [&](const char *data, size_t n) { grm_bin.write(data, n, what); }, [&](const char *data, size_t n) { grm_n_bin.write(data, n, what); },
                     [&](const char *data, size_t n) { grm_id.write(data, n, what); });
-                grm_bin.close(what), grm_n_bin.close(what), grm_id.close(what);
-                grm_bin.finish(what), grm_n_bin.finish(what), grm_id.finish(what);
-            } else {
-                grm_text(st, names, [&](const char *data, size_t n) { grm_file.write(data, n, what); });
-                grm_file.finish(what);
-            }
+            else grm_text(st, names, [&](const char *data, size_t n) { grm_file.write(data, n, what); });
+            for (PartFile *f : {&grm_file, &grm_bin, &grm_n_bin, &grm_id}) f->close(what);
         }
+        site_word_files.clear(); // (the groups' streams go before a table takes its name)
+        for (PartFile *f : {&ld_file, &ibd_file, &grm_file, &grm_bin, &grm_n_bin, &grm_id}) f->finish(); // (closed above; one that was never opened takes no name)
         priors_file.finish();
         times.add_to_timers();
         std::cerr << times.report();

@@ -425,6 +425,32 @@ def test_cli_grm_on_general_blocks(tmp_path):
     assert not [f for f in os.listdir(data) if f.endswith(".part")]
 
 
+def test_cli_the_three_tables_of_one_stream(haploid_cohort, tmp_path):
+    """--ld, --ibd and --grm read one stream of site words per group: each table alone and all three together, in groups of two and as one
+    group, in batches and chunks of 7 records -- the same bytes in every run that makes a table, the same merged file in all"""
+    tmp, fa, vcf, fq, inputs = haploid_cohort
+    man = str(tmp / "cohort.tsv")
+    _cli(["index"] + COMMON + [fa, vcf, fq])
+    opts = {"ld": ["--ld-window", "5", "--ld-min-r2", "0"], "ibd": ["--ibd-min-records", "1", "--ibd-min-bp", "0"], "grm": GRM_OPTS}
+    runs = [("ld", ["ld"], True), ("ibd", ["ibd"], True), ("grm", ["grm"], True), ("all", ["ld", "ibd", "grm"], True), ("one", ["ld", "ibd", "grm"], False)]
+    tables, merged = {}, set()
+    for tag, made, grouped in runs:
+        d = tmp_path / tag
+        d.mkdir()
+        args = sum((["--" + t, str(d / (t + ".tsv"))] + opts[t] for t in made), [])
+        assert _cli(["call"] + COMMON + (["--cohort-group", "2"] if grouped else []) + ["--cohort", "--merged", str(d / "m.vcf")] + args + [fa, vcf, man],
+                    env=dict(os.environ, MALVA_GENO_BATCH="7")) == ""
+        _no_leftovers(d, ["m.vcf"] + [t + ".tsv" for t in made])
+        for t in made:
+            tables.setdefault(t, []).append(open(str(d / (t + ".tsv"))).read())
+        merged.add(open(str(d / "m.vcf")).read())
+    assert len(merged) == 1 and len([l for l in merged.pop().split("\n") if l and l[0] != "#"]) > 3 * 7, "a few batches of 7 records"
+    for t, texts in tables.items():
+        assert len(texts) == 3 and len(set(texts)) == 1, "the %s table depends on the run" % t
+        assert texts[0].count("\n") >= 2 and texts[0][0] == "#", "a %s table without a data line" % t
+    assert not [f for d in [tmp] + [tmp_path / r[0] for r in runs] for f in os.listdir(d) if f.endswith(".part")]
+
+
 def test_cli_grm_reports_and_timers(haploid_cohort, tmp_path):
     import subprocess
     tmp, fa, vcf, fq, inputs = haploid_cohort

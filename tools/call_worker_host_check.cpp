@@ -899,6 +899,65 @@ static void check_pipeline()
     }
 }
 
+// ---- 9. the records' site words (--ld, --ibd, --grm) ------------------------------------------------------------------------------------------------
+// lone records and general blocks in turn: the output order is neither batch kind's order
+static Closed interleaved_batch()
+{
+    BatchRules r = dense2;
+    r.iso_path = true;
+    Pass &p = new_pass(r);
+    p.add(block_of(35, {var("c1", 100, "A", {"G"})}));
+    p.add(block_of(35, {var("c1", 300, "A", {"G"}), var("c1", 310, "C", {"G", "T"})}));
+    p.add(block_of(35, {var("c1", 500, "C", {"G", "T"})}));
+    p.add(block_of(35, {var("c1", 700, "A", {"G"}), var("c1", 705, "A", {"G"})}));
+    p.add(block_of(35, {var("c1", 900, "A", {"G"})}));
+    return closed_of(p);
+}
+static void check_site_words()
+{
+    struct Want { // a record of the stream: its slot in its batch kind (the fake's first word), its alleles, its first five columns
+        uint64_t slot;
+        uint32_t n_alleles;
+        const char *cols;
+    };
+    const Want want[] = {{0, 2, "c1\t101\t.\tA\tG"}, {0, 2, "c1\t301\t.\tA\tG"}, {1, 3, "c1\t311\t.\tC\tG,T"}, {1, 3, "c1\t501\t.\tC\tG,T"}, {2, 2, "c1\t701\t.\tA\tG"},
+                         {3, 2, "c1\t706\t.\tA\tG"}, {2, 2, "c1\t901\t.\tA\tG"}, // the interleaved batch: lone, two general, lone, two general, lone
+                         {0, 2, "c1\t101\t.\tA\tG"}, {1, 3, "c1\t301\t.\tC\tG,T"}, {0, 2, "c1\t501\t.\tA\tG"}, {1, 3, "c1\t511\t.\tC\tG,T"}}; // mixed_batch: two lone, two general
+    const char *labels[3] = {"worker: ld words (mg_pack_site_dosage)", "worker: ibd words (mg_pack_site_dosage)", "worker: grm words (mg_pack_site_dosage)"};
+    for (int asked = 0; asked < 3; ++asked) // LD asked; IBD without LD; GRM alone
+        for (const bool cols : {true, false}) {
+            Scene s;
+            s.o.use_min_gq = true, s.o.min_gq = 20;
+            s.ctx().n_planes = 2;
+            PartFile words;
+            words.open(scratch + "/call_worker_check.sites", PartFile::SCRATCH);
+            s.to.site_words = &words, s.to.site_words_cols = cols;
+            s.to.site_words_for = asked == 0 ? PassOut::LD : asked == 1 ? PassOut::IBD : PassOut::GRM;
+            std::vector<Closed> batches;
+            batches.push_back(interleaved_batch());
+            batches.push_back(mixed_batch(2, true));
+            std::vector<bool> lone;
+            for (const Rec &r : batches[0].recs) lone.push_back(r.isolated);
+            CHECK(lone == std::vector<bool>({true, false, false, true, false, false, true}));
+            g_timers.on = true;
+            s.run(2, 2, std::move(batches));
+            g_timers.on = false;
+            for (int k = 0; k < 3; ++k) CHECK(g_timers.acc.count(labels[k]) == (k == asked)); // the worker's timer: the asking option's alone
+            g_timers.acc.clear();
+            // a pack call per batch kind, the lone records' first, over both planes and under the mask
+            CHECK(only(s.ctx().log, {"mg_pack", "mg_ld_"}) == Log({"mg_pack_site_dosage n=3 planes=2 mask=1", "mg_ld_stats", "mg_pack_site_dosage n=4 planes=2 mask=1", "mg_ld_stats",
+                                                                   "mg_pack_site_dosage n=2 planes=2 mask=1", "mg_ld_stats", "mg_pack_site_dosage n=2 planes=2 mask=1", "mg_ld_stats"}));
+            const CallTimes::Kind *kinds[3] = {&s.total.ld, &s.total.ibd, &s.total.grm};
+            for (int k = 0; k < 3; ++k) CHECK(k == asked ? same_kind(*kinds[k], {64}, {4}) : same_kind(*kinds[k], no_ms, no_calls)); // four calls of 16 ms
+            // the stream: put_site_words over the records in output order -- the fake's words are the slot, the planes and the mask
+            std::string bytes;
+            for (const Want &w : want) put_site_words(bytes, w.slot, 2, 1, w.n_alleles, cols ? w.cols : nullptr, strlen(w.cols));
+            CHECK(bytes.size() == 11 * 28 + (cols ? 11 * 4 + 7 * 12 + 4 * 14 : 0)); // (without the columns: neither their length nor their bytes)
+            words.close();
+            CHECK(slurp(words.path) == bytes);
+        }
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1) scratch = argv[1];
@@ -912,6 +971,7 @@ int main(int argc, char **argv)
     check_cohort_priors();
     check_merged_rows();
     check_pipeline();
+    check_site_words();
     std::cout << "call_worker_host_check: ok\n";
     return 0;
 }

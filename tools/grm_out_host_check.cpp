@@ -126,7 +126,7 @@ static std::vector<std::string> streams(const std::vector<Record> &recs, const s
                 if (r.dosage[s0 + p] >= 0) w[r.dosage[s0 + p]] |= 1ull << p;
             if (sizes[g] < 64)
                 for (uint64_t &x : w) x |= ~0ull << sizes[g];
-            put_ld_words(out[g], w[0], w[1], w[2], 2, g ? nullptr : r.cols.data(), r.cols.size());
+            put_site_words(out[g], w[0], w[1], w[2], 2, g ? nullptr : r.cols.data(), r.cols.size());
             s0 += sizes[g];
         }
     }
@@ -165,7 +165,7 @@ static void fill(std::deque<PartFile> &files, const std::string &base, const std
 {
     for (size_t g = 0; g < contents.size(); ++g) {
         files.emplace_back();
-        files.back().open(base + ".g" + std::to_string(g) + ".grm.part", PartFile::SCRATCH);
+        files.back().open(base + ".g" + std::to_string(g) + ".sites.part", PartFile::SCRATCH);
         files.back().write(contents[g]);
         files.back().finish();
     }
@@ -183,7 +183,7 @@ static std::string run_pass(const std::string &dir, const std::vector<std::strin
             files, sizes, chunk, [&](size_t n_vars, size_t G, const uint64_t *sites) { fake.step(n_vars, G, sites); },
             [&](int64_t *s, uint64_t *n, uint64_t *records) { fake.read(s, n, records); });
         files.clear();
-        for (size_t g = 0; g < contents.size(); ++g) CHECK(!exists(path + ".g" + std::to_string(g) + ".grm.part"));
+        for (size_t g = 0; g < contents.size(); ++g) CHECK(!exists(path + ".g" + std::to_string(g) + ".sites.part"));
         grm_text(st, sample_names(S), [&](const char *data, size_t n) { table.write(data, n); });
         CHECK(!exists(path) && exists(path + ".part"));
         table.finish();
@@ -282,7 +282,7 @@ int main(int argc, char **argv)
                 table.finish();
             });
             CHECK(has(why, why_piece));
-            CHECK(!exists(path) && !exists(path + ".part") && !exists(path + ".g0.grm.part") && !exists(path + ".g1.grm.part"));
+            CHECK(!exists(path) && !exists(path + ".part") && !exists(path + ".g0.sites.part") && !exists(path + ".g1.sites.part"));
         };
         for (size_t g = 0; g < 2; ++g) {
             std::vector<std::string> bad = contents;

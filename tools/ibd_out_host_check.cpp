@@ -152,7 +152,7 @@ static std::vector<std::string> streams(const std::vector<Record> &recs, const s
             uint64_t w[3] = {0, 0, 0};
             for (size_t p = 0; p < sizes[g]; ++p)
                 if (r.dosage[s0 + p] >= 0) w[r.dosage[s0 + p]] |= 1ull << p;
-            put_ld_words(out[g], w[0], w[1], w[2], 2, g ? nullptr : r.cols.data(), r.cols.size());
+            put_site_words(out[g], w[0], w[1], w[2], 2, g ? nullptr : r.cols.data(), r.cols.size());
             s0 += sizes[g];
         }
     }

@@ -95,9 +95,9 @@ static void text_rules()
     CHECK(out == "c1\t7\trs1\t19\t.\t12\t0.25\t+\n" "c1\t7\trs1\t19\t.\t16384\t0.333333\t-\n" "c1\t7\trs1\t19\t.\t2\t0\t0\n" "c1\t7\trs1\t19\t.\t2\t1e-07\t+\n");
     CHECK(std::string(ld_header()) == "#CHROM\tPOS_A\tID_A\tPOS_B\tID_B\tN\tR2\tSIGN\n");
     std::string s;
-    put_ld_words(s, 1, 2, 3, 2, nullptr, 0);
+    put_site_words(s, 1, 2, 3, 2, nullptr, 0);
     CHECK(s.size() == 28);
-    put_ld_words(s, 1, 2, 3, 2, "abc", 3);
+    put_site_words(s, 1, 2, 3, 2, "abc", 3);
     CHECK(s.size() == 28 + 28 + 4 + 3);
 }
 
@@ -123,7 +123,7 @@ static std::vector<std::string> streams(const std::vector<Record> &recs, size_t 
 {
     std::vector<std::string> out(groups);
     for (const Record &r : recs)
-        for (size_t g = 0; g < groups; ++g) put_ld_words(out[g], r.words[3 * g], r.words[3 * g + 1], r.words[3 * g + 2], r.A, g ? nullptr : r.cols.data(), r.cols.size());
+        for (size_t g = 0; g < groups; ++g) put_site_words(out[g], r.words[3 * g], r.words[3 * g + 1], r.words[3 * g + 2], r.A, g ? nullptr : r.cols.data(), r.cols.size());
     return out;
 }
 // the whole table in one call, without the reader
@@ -154,7 +154,7 @@ static void fill(std::deque<PartFile> &files, const std::string &base, const std
 {
     for (size_t g = 0; g < contents.size(); ++g) {
         files.emplace_back();
-        files.back().open(base + ".g" + std::to_string(g) + ".ld.part", PartFile::SCRATCH);
+        files.back().open(base + ".g" + std::to_string(g) + ".sites.part", PartFile::SCRATCH);
         files.back().write(contents[g]);
         files.back().finish();
     }
@@ -174,7 +174,7 @@ static std::string run_pass(const std::string &dir, const std::vector<std::strin
         table.finish();
     }
     CHECK(exists(path) && !exists(path + ".part"));
-    for (size_t g = 0; g < contents.size(); ++g) CHECK(!exists(path + ".g" + std::to_string(g) + ".ld.part"));
+    for (size_t g = 0; g < contents.size(); ++g) CHECK(!exists(path + ".g" + std::to_string(g) + ".sites.part"));
     const std::string text = slurp(path);
     unlink(path.c_str());
     return text;
@@ -230,7 +230,7 @@ int main(int argc, char **argv)
                 table.finish();
             });
             CHECK(has(why, why_piece));
-            CHECK(!exists(path) && !exists(path + ".part") && !exists(path + ".g0.ld.part"));
+            CHECK(!exists(path) && !exists(path + ".part") && !exists(path + ".g0.sites.part"));
         };
         for (size_t g = 0; g < groups; ++g) {
             std::vector<std::string> bad = contents;
