@@ -217,6 +217,18 @@ struct BFView {
     u32 pre_shift;
     u32 pre_k;
     u32 use_gate;
+    // A gate whose word count is no power of two (the direct single-level form only; 0: the shift form above, which the ticket,
+    // sub-slice and partition forms cut into slices).  An L2-sized gate shares the XCD's 4 MiB with the table stream, and every
+    // stream line that allocates evicts a gate line; a gate of 2.5-3.5 MiB leaves the stream its room.  The slot range is scaled
+    // onto gate_words words by a multiply-high: x = the top 32 significant bits of idx (idx << gate_ls, high dword; gate_ls =
+    // 64 - bit length of size - 1), word = x * gate_mul >> (32 + gate_rs), with gate_mul = gate_words * 2^(32 + gate_rs) / x(size - 1)
+    // rounded so that idx = size - 1 lands in the last word and nothing beyond it (gate_geometry on the host; gate_rs makes
+    // gate_mul fill its 32 bits, so that a gate of few words is cut as evenly as one of many).  A word
+    // then covers a contiguous run of 2^g <= size / gate_words < 2^(g+1) slots; gate_shift = g - 6, so the mask (gate_mask_sk)
+    // is made as in the shift form from bits in which two slots of one word differ.
+    u32 gate_words;
+    u32 gate_mul;
+    u32 gate_ls, gate_rs;
 };
 // the cell of filter counter (rank) r in the view's plane
 __device__ __forceinline__ u32 *bf_cell(const BFView &b, u32 r) { return b.counts + (((u64)r << b.cshift) + b.coff); }
@@ -255,7 +267,11 @@ __device__ __forceinline__ u64 gate_mask_sk(u64 idx, u32 shift, u32 k)
     if (k > 3) m |= 1ULL << (mul24(t, 0xB2AE3Du) >> 26);
     return m;
 }
-__device__ __forceinline__ u64 gate_word(const BFView &b, u64 idx) { return idx >> (b.gate_shift + 6); }
+__device__ __forceinline__ u64 gate_word(const BFView &b, u64 idx)
+{
+    if (b.gate_words) return __umulhi((u32)((idx << b.gate_ls) >> 32), b.gate_mul) >> b.gate_rs; // (BFView::gate_words)
+    return idx >> (b.gate_shift + 6);
+}
 __device__ __forceinline__ u64 gate_mask(const BFView &b, u64 idx) { return gate_mask_sk(idx, b.gate_shift, b.gate_k); }
 __device__ __forceinline__ u64 pre_word(const BFView &b, u64 idx) { return idx >> (b.pre_shift + 6); }
 __device__ __forceinline__ u64 pre_mask(const BFView &b, u64 idx) { return gate_mask_sk(idx, b.pre_shift, b.pre_k); }

@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "gate_geometry.h"
 #include "geno_dev.h"
 #include "malva_hip.h"
 
@@ -32,6 +33,8 @@ namespace {
 constexpr size_t TK_META_HEAD = 8; // ticket meta block: spill count, then the segment fills
 constexpr int BIN_SEGS = 2048; // workgroups of the binning kernel = segments per bin
 constexpr int TPB = 256;
+constexpr int GATE_RESIDENT_KIB = 3072;   // default of option gate_resident_kib (mg_ctx): swept 2048..4096 at C3, 3072 and 3584 tie on the whole step, 4096 loses 0.07 ms
+constexpr int GATE_RESIDENT_MIN_BITS = 8; // a sized gate keeps at least this many bits per entry (8.4 at C3 with 2048 KiB still beat the 4 MiB gate, by 0.02 ms)
 
 #include "store_kernels.h"
 #include "scan_kernels.h"
@@ -65,6 +68,7 @@ struct BFState {
     u64 *gate = nullptr; // only `bf` (MG_BF_ALT) owns one
     u64 n_gate_bits = 0;
     u32 gate_shift = 6;
+    u32 gate_words = 0, gate_mul = 0, gate_ls = 0, gate_rs = 0; // a gate sized in words (BFView::gate_words); 0: the shift form
     u64 *pos_set = nullptr; // `context_bf`, call time: its set positions as a hash set (BFView::pos_set); built at the first scan
     u32 pos_set_log2 = 0;
     bool pos_set_valid = false;
@@ -245,7 +249,14 @@ struct mg_ctx {
     Scratch s_bin[3], s_spill[3];
     unsigned long long *d_bin_meta = nullptr; // spill count, then u32 [BIN_MAXP][BIN_SEGS] segment fills
     int gate_k = 4;     // gate bits per entry (blocked Bloom filter inside one 64-bit word; swept 2..4)
-    int gate_log2 = 25; // gate of at most 2^gate_log2 bits = 4 MiB (swept 24..26: 25 gives the best whole-scan time)
+    int gate_log2 = 25; // gate of at most 2^gate_log2 bits (swept 24..26 among the powers of two: 25 = 4 MiB; such a gate is then allocated with gate_resident_kib, below)
+    // A gate of exactly the L2 size leaves the table stream no room in L2 beside it: every stream line that allocates evicts a
+    // gate line.  Where the sizing rule of mg_bf_finalize lands on 2^pregate_log2 = 2^25 bits and the direct single-level form scans, the gate is
+    // allocated with gate_resident_kib KiB instead (no power of two: BFView::gate_words), unless that leaves an entry fewer than
+    // GATE_RESIDENT_MIN_BITS bits.  0: keep the power of two.  (profiles/gate_span_sweep.txt)
+    int gate_resident_kib = GATE_RESIDENT_KIB;
+    u64 gate_words_opt = 0; // option gate_words (tests, A/B): the direct single-level form's gate has exactly this many words, whatever the index holds
+    u64 gate_words = 0;     // words of the sized gate that alloc_gate makes (0: the shift form): set_option / mg_bf_finalize decide
     // multi-GPU exchange (mg_comm_*): an RCCL communicator, or -- contexts of one process that share a device, where
     // RCCL refuses duplicate ranks -- the list of contexts whose counters a kernel sums
     ncclComm_t comm = nullptr;
@@ -404,6 +415,10 @@ BFView view(const mg_ctx *c, int which)
     v.mod = b.mod;
     v.gate_shift = b.gate_shift;
     v.gate_k = (u32)c->gate_k;
+    v.gate_words = b.gate_words;
+    v.gate_mul = b.gate_mul;
+    v.gate_ls = b.gate_ls;
+    v.gate_rs = b.gate_rs;
     v.pregate = pregate_on(c) ? b.pregate : nullptr;
     v.pregate_fill = b.pregate; // filled whenever it exists, so use_pregate / pre_skip may change between scans
     v.pre_shift = b.pre_shift;
@@ -457,7 +472,24 @@ int unjoin(mg_ctx *c)
     return MG_OK;
 }
 
-// (re)allocate the gate of `bf`: at most 2^gate_log2 bits, one per 2^gate_shift filter bits
+// (the geometry of a gate sized in words: gate_geometry.h)
+u64 gate_words_max(const BFState &b) { return std::min<u64>(std::max<u64>(1, b.size / 64), 1ULL << 30); }
+// Words of the sized gate that takes the place of a gate of 2^want bits over `entries` entries; 0: the power of two stays.  Only
+// where the direct single-level form scans (no coarse gate; the ticket and sub-slice forms cut the gate by word index) and the
+// caller did not fix the size.
+u64 sized_gate_words(const mg_ctx *c, int want, u64 entries)
+{
+    if (c->gate_fixed || want > c->pregate_log2) return 0;
+    if (c->use_sub && want >= c->sub_min_log2) return 0;
+    if (c->use_tickets && want >= c->ticket_min_log2) return 0;
+    if (c->gate_words_opt) return c->gate_words_opt;
+    const u64 bits = (u64)c->gate_resident_kib * 8192; // (want == pregate_log2: the gate is exactly what the context takes for an XCD's L2)
+    if (want != c->pregate_log2 || !bits || bits >= (1ULL << want) || bits < (u64)GATE_RESIDENT_MIN_BITS * entries) return 0;
+    return bits / 64;
+}
+
+// (re)allocate the gate of `bf`: at most 2^gate_log2 bits, one per 2^gate_shift filter bits -- or, for a gate sized in words
+// (mg_ctx::gate_words != 0), that many words
 int alloc_gate(mg_ctx *c)
 {
     BFState &b = c->bf[MG_BF_ALT];
@@ -465,6 +497,12 @@ int alloc_gate(mg_ctx *c)
     while (((b.size + (1ULL << S) - 1) >> S) > (1ULL << c->gate_log2)) ++S;
     b.gate_shift = S;
     b.n_gate_bits = (b.size + (1ULL << S) - 1) >> S;
+    b.gate_words = b.gate_mul = b.gate_ls = b.gate_rs = 0;
+    if (c->gate_words && c->gate_log2 <= c->pregate_log2) { // (no coarse gate in front of a sized one)
+        b.gate_words = (u32)std::min<u64>(c->gate_words, gate_words_max(b));
+        gate_geometry(b.size, b.gate_words, &b.gate_mul, &b.gate_ls, &b.gate_rs, &b.gate_shift);
+        b.n_gate_bits = 64ULL * b.gate_words;
+    }
     if (b.gate) HIP_TRY(c, hipFree(b.gate));
     b.gate = nullptr;
     const size_t bytes = ((b.n_gate_bits + 63) / 64) * 8;
@@ -976,14 +1014,23 @@ MG_EXPORT int mg_set_option(mg_ctx *c, const char *name, int64_t value)
     else if (!strcmp(name, "grm_scratch_mb")) c->grm_scratch_mb = (int)std::max<int64_t>(1, std::min<int64_t>(4096, value));
     else if (!strcmp(name, "scan_variant")) c->scan_variant = (int)value & 2;
     else if (!strcmp(name, "scan_grid")) c->scan_grid = value > 0 ? (int)value : 8192;
-    else if (!strcmp(name, "gate_log2") || !strcmp(name, "gate_k")) {
+    else if (!strcmp(name, "gate_log2") || !strcmp(name, "gate_k") || !strcmp(name, "gate_words") || !strcmp(name, "gate_resident_kib")) {
         if (c->map.rows_total || c->gate_dirty) return fail(c, MG_ERR_STATE, "%s must be set before the first insert", name);
         if (!strcmp(name, "gate_k")) {
             if (value < 1 || value > 4) return fail(c, MG_ERR_ARG, "gate_k must be 1..4");
             c->gate_k = (int)value;
+        } else if (!strcmp(name, "gate_resident_kib")) { // (takes effect when mg_bf_finalize sizes the gate)
+            if (value < 0 || value > 4096) return fail(c, MG_ERR_ARG, "gate_resident_kib must be 0..4096");
+            c->gate_resident_kib = (int)value;
+            return MG_OK;
+        } else if (!strcmp(name, "gate_words")) { // 0: back to the sizing rule
+            if (value < 0 || value > (1LL << 30)) return fail(c, MG_ERR_ARG, "gate_words must be 0..2^30");
+            c->gate_words_opt = (u64)value;
+            c->gate_words = value ? sized_gate_words(c, c->gate_log2, 0) : 0;
         } else {
             c->gate_log2 = (int)value;
             c->gate_fixed = true;
+            c->gate_words = 0;
         }
         return alloc_gate(c);
     }
@@ -1026,6 +1073,8 @@ MG_EXPORT int mg_get_option(mg_ctx *c, const char *name, int64_t *value)
     else if (!strcmp(name, "use_packed_ref_scan")) *value = c->use_packed_ref_scan;
     else if (!strcmp(name, "gate_log2")) *value = c->gate_log2;
     else if (!strcmp(name, "gate_k")) *value = c->gate_k;
+    else if (!strcmp(name, "gate_words")) *value = c->bf[MG_BF_ALT].gate_words; // words of a gate sized in words; 0: a power-of-two gate of at most 2^gate_log2 bits
+    else if (!strcmp(name, "gate_resident_kib")) *value = c->gate_resident_kib;
     else if (!strcmp(name, "pregate_log2")) *value = c->pregate_log2;
     else if (!strcmp(name, "pregate_k")) *value = c->bf[MG_BF_ALT].pregate && pregate_on(c) ? c->pre_k : 0;
     else if (!strcmp(name, "scan_bins")) *value = c->last_bins;
@@ -1136,8 +1185,11 @@ MG_EXPORT int mg_bf_finalize(mg_ctx *c, int which)
         pk = pk < 1 ? 1 : pk > 4 ? 4 : pk;
         // a coarse gate that would let more than 3 of 4 rows through costs an L2 probe per row and saves little
         c->pre_skip = std::pow(1.0 - std::exp(-(double)pk * (double)entries / (double)(1ULL << c->pregate_log2)), pk) > 0.75;
-        if (want != c->gate_log2 || (want > c->pregate_log2 && pk != c->pre_k)) {
+        // a gate of exactly the L2 size gives way to one that stays resident beside the table stream (mg_ctx::gate_resident_kib)
+        const u64 words = sized_gate_words(c, want, entries);
+        if (want != c->gate_log2 || words != c->gate_words || (want > c->pregate_log2 && pk != c->pre_k)) {
             c->gate_log2 = want;
+            c->gate_words = words;
             c->pre_k = pk;
             TRY(alloc_gate(c));
             hipLaunchKernelGGL(gate_from_bits_kernel, dim3(nblocks(b.nwords)), dim3(TPB), 0, c->stream, view(c, MG_BF_ALT), b.nwords);
@@ -1584,7 +1636,7 @@ int scan_plan(mg_ctx *c, u64 n, bool rows12, ScanPlan *out)
     u32 idx_bits = 1; // a ticket holds a filter index and the row number: rows per launch group = 2^row_bits
     while (idx_bits < 64 && (alt.size - 1) >> idx_bits) ++idx_bits;
     const u32 row_bits = std::min<u32>(27, 64 - idx_bits);
-    const bool two_pass = c->use_summary && alt.gate && idx_bits <= 44;
+    const bool two_pass = c->use_summary && alt.gate && idx_bits <= 44 && !alt.gate_words; // (a gate sized in words is not cut into slices)
     const u64 NB = sub_bins(c), TP = ticket_slices(c);
     if (two_pass && c->use_sub && c->gate_log2 >= c->sub_min_log2 && NB >= 2 && NB <= (u64)SB_MAXB && c->sub_words_log2 >= 0 &&
         c->sub_words_log2 <= SB_WORDS_LOG2)

@@ -1,6 +1,8 @@
 // Microbenchmark behind DESIGN.md's bound for the scan's filter kernel: how many independent, uniformly random
 // 8-byte reads per second one MI355X sustains from a table of F bytes (F = 16 KiB .. 1 GiB: L2-resident up to
-// 4 MiB per XCD), alone and beside a non-temporal 20-byte-per-lane stream shaped like the k-mer table.
+// 4 MiB per XCD), alone and beside a non-temporal 20-byte-per-lane stream shaped like the k-mer table.  Then the same for tables
+// of 1..8 MiB whose word count is no power of two, beside the 20 B/row stream and beside the packed 12 B/row one
+// (profiles/gate_span_l2_gather.txt: flat up to 3 MiB, +0.02 ms at 3.5 MiB, +0.06 ms at 4 MiB).
 //   make microbench && bin/l2_gather_bench
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -62,6 +64,42 @@ __global__ void __launch_bounds__(256) bench(const uint64_t *__restrict__ hi, co
     if (acc == 0x1234567) atomicAdd(sink, 1ULL);
 }
 
+// The same beside a table whose word count is no power of two (a gate of 2..4 MiB that leaves the stream room in L2): the word
+// index is a multiply-high of 32 mixed bits, as BFView::gate_words scales a filter slot.  ROWB: bytes per row of the stream,
+// 20 (the SoA table, as above) or 12 (packed rows: three 8-byte loads per thread, as scan_filter12_kernel), 0 = no stream.
+template <int ROWB>
+__global__ void __launch_bounds__(256) bench_span(const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo,
+                                                  const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ rows12, uint64_t n,
+                                                  const uint64_t *__restrict__ table, uint32_t words, unsigned long long *sink)
+{
+    uint64_t acc = 0;
+    const uint64_t step = (uint64_t)gridDim.x * 512;
+    for (uint64_t base = (uint64_t)blockIdx.x * 512; base + 512 <= n; base += step) {
+        const uint64_t i = base + 2 * threadIdx.x;
+        uint64_t a0 = i * 0x9E3779B97F4A7C15ULL, a1 = (i + 1) * 0x9E3779B97F4A7C15ULL;
+        typedef unsigned long long __attribute__((ext_vector_type(2))) v2u64;
+        typedef unsigned int __attribute__((ext_vector_type(2))) v2u32;
+        if (ROWB == 20) {
+            const v2u64 l2 = __builtin_nontemporal_load((const v2u64 *)(lo + i));
+            const v2u64 h2 = __builtin_nontemporal_load((const v2u64 *)(hi + i));
+            const v2u32 c2 = __builtin_nontemporal_load((const v2u32 *)(cnt + i));
+            a0 ^= l2.x + h2.x + c2.x;
+            a1 ^= l2.y + h2.y + c2.y;
+        } else if (ROWB == 12) {
+            const v2u32 *src = (const v2u32 *)rows12 + 3 * (i / 2);
+            const v2u32 w0 = __builtin_nontemporal_load(src), w1 = __builtin_nontemporal_load(src + 1), w2 = __builtin_nontemporal_load(src + 2);
+            a0 ^= w0.x + ((uint64_t)w0.y << 32) + w1.x;
+            a1 ^= w1.y + ((uint64_t)w2.x << 32) + w2.y;
+        }
+        a0 ^= a0 >> 29;
+        a1 ^= a1 >> 29;
+        a0 *= 0xBF58476D1CE4E5B9ULL;
+        a1 *= 0xBF58476D1CE4E5B9ULL;
+        acc += table[__umulhi((uint32_t)(a0 >> 20), words)] + table[__umulhi((uint32_t)(a1 >> 20), words)];
+    }
+    if (acc == 0x1234567) atomicAdd(sink, 1ULL);
+}
+
 int main()
 {
     const uint64_t n = 100000000ULL / 512 * 512;
@@ -114,5 +152,29 @@ int main()
         printf("table %6llu KiB: gather only %.3f ms = %.3g reads/s | stream + gather %.3f ms = %.3g rows/s (stream only + gather only = %.3f)\n",
                (unsigned long long)((1ULL << lg) >> 10), g, n / (g * 1e-3), sg, n / (sg * 1e-3), s_only + g);
     }
+    // between 1 MiB and 4 MiB: does a table that leaves the stream room in an XCD's 4 MiB L2 gather faster beside it?
+    uint32_t *rows12;
+    CK(hipMalloc(&rows12, n * 12));
+    CK(hipMemset(rows12, 4, n * 12));
+    auto time_span = [&](auto kern, uint32_t words) -> float {
+        float best = 1e9f;
+        for (int rep = 0; rep < 6; ++rep) {
+            hipEventRecord(e0, 0);
+            hipLaunchKernelGGL(kern, dim3(8192), dim3(256), 0, 0, hi, lo, cnt, rows12, n, table, words, sink);
+            hipEventRecord(e1, 0);
+            hipEventSynchronize(e1);
+            float ms;
+            hipEventElapsedTime(&ms, e0, e1);
+            if (rep && ms < best) best = ms;
+        }
+        return best;
+    };
+    printf("word index by multiply-high (any table size):\n");
+    for (int kib : {1024, 2048, 2560, 3072, 3584, 4096, 8192}) {
+        const uint32_t words = (uint32_t)kib * 128u;
+        const float g = time_span(bench_span<0>, words), s20 = time_span(bench_span<20>, words), s12 = time_span(bench_span<12>, words);
+        printf("table %6d KiB: gather only %.3f ms | 20 B/row stream + gather %.3f ms | 12 B/row stream + gather %.3f ms\n", kib, g, s20, s12);
+    }
+    CK(hipGetLastError());
     return 0;
 }
