@@ -63,9 +63,10 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 
 # the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs (--site-stats, --ld, --ibd and --grm in programs of their own) and of the panel batches and their text under
 # AddressSanitizer and UBSan: stand-alone programs, run on the CPU.  The last one is a batch's device calls and the pipeline around them
-# (host/call_worker.hpp) against an ABI of its own, without libmalva_hip; it runs a second time under ThreadSanitizer
+# (host/call_worker.hpp) against an ABI of its own, without libmalva_hip; it runs a second time under ThreadSanitizer.  Last, the command line
+# (host/options.hpp) against the records of the parser it replaced
 sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/site_table_host_check bin/ld_out_host_check bin/ibd_out_host_check bin/grm_out_host_check \
-               bin/call_batch_host_check bin/call_worker_host_check bin/call_worker_host_check_tsan
+               bin/call_batch_host_check bin/call_worker_host_check bin/call_worker_host_check_tsan bin/options_host_check
 	bin/cohort_priors_host_check bin
 	bin/cohort_priors_groups_host_check bin
 	bin/cohort_out_host_check bin
@@ -76,6 +77,7 @@ sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check 
 	bin/call_batch_host_check
 	bin/call_worker_host_check bin
 	bin/call_worker_host_check_tsan bin
+	bin/options_host_check
 bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
@@ -112,6 +114,10 @@ bin/call_worker_host_check: tools/call_worker_host_check.cpp tools/host_check_ut
 bin/call_worker_host_check_tsan: tools/call_worker_host_check.cpp tools/host_check_util.hpp $(HOSTHDR) include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -pthread -fsanitize=thread -Imalva_amd/host -o $@ $< -lz
+# the command line (host/options.hpp, usage.hpp) against the records of tests/golden/options_cases.jsonl
+bin/options_host_check: tools/options_host_check.cpp malva_amd/host/options.hpp malva_amd/host/usage.hpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
 
 clean:
 	rm -rf malva_amd/lib bin oracle/libmalva_oracle.so oracle/_ref

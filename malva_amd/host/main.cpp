@@ -8,7 +8,6 @@
 #include <fcntl.h>
 #include <functional>
 #include <future>
-#include <getopt.h>
 #include <sys/mman.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
@@ -31,535 +30,14 @@
 #include "cohort.hpp"
 #include "bcf_out.hpp"
 #include "cohort_priors.hpp"
+#include "options.hpp"
+#include "usage.hpp"
 #include "cohort_out.hpp"
 #include "call_worker.hpp"
 
 using namespace malva;
 
 namespace {
-
-const char *USAGE =
-    "Usage: malva-geno <index|call> [-k KMER-SIZE] [-r REF-KMER-SIZE] [-c MAX-COV] "
-    "<reference.fa> <variants.vcf> <kmc_output_prefix | READS>\n"
-    "\n"
-    "      -h, --help                        display this help and exit\n"
-    "      -k, --kmer-size                   size of the kmers to index (default:35)\n"
-    "      -r, --ref-kmer-size               size of the reference kmers to index (default:43)\n"
-    "      -e, --error-rate                  expected sample error rate (default:0.001)\n"
-    "      -s, --samples                     file containing the list of (VCF) samples to consider (default:-, i.e. all samples)\n"
-    "      -f, --freq-key                    a priori frequency key in the INFO column of the input VCF (default:AF)\n"
-    "      -c, --max-coverage                maximum coverage for variant alleles (default:200)\n"
-    "      -b, --bf-size                     bloom filter size in GB (default:4)\n"
-    "      -p, --strip-chr                   strip \"chr\" from sequence names (default:false)\n"
-    "      -u, --uniform                     use uniform a priori probabilities (default:false)\n"
-    "      -v, --verbose                     output COVS and GTS in INFO column (default: false)\n"
-    "      -1, --haploid                     run MALVA in haploid mode (default: false)\n"
-    "      -d, --device                      first GPU to run on (default:0)                     [this build]\n"
-    "      -g, --gpus                        GPUs to use, devices -d .. -d+N-1 (default:1)       [this build; N > 1 has run\n"
-    "                                        only with all contexts on ONE device: untested on multi-GPU hardware]\n"
-    "                                        call: the k-mer table is sharded over them, the per-allele counters\n"
-    "                                        are all-reduced over RCCL, the variants are split between them\n"
-    "          --min-count                   READS only: drop k-mers seen fewer times (default:2, KMC -ci; 0 = 1)  [this build]\n"
-    "          --max-count                   READS only: cap counts at this value (default:255, KMC -cs)             [this build]\n"
-    "          --cohort                      call: the third argument is a manifest, one sample per line NAME<tab>INPUT ('#' lines\n"
-    "                                        and blank lines skipped; INPUT as the third argument of call, relative paths relative\n"
-    "                                        to the manifest); needs -o or --merged; not with --gpus > 1            [this build]\n"
-    "      -o, --out-dir                     --cohort: directory that receives NAME.vcf per sample, each byte for byte what\n"
-    "                                        `call` with that INPUT prints to stdout                                 [this build]\n"
-    "          --cohort-group                --cohort: samples held on the GPU at once, 1..64 (default: all of them, at most 64,\n"
-    "                                        halved while their counters do not fit in HBM beside the index).  A cohort of any\n"
-    "                                        size runs as groups of that many; the index is loaded once, the panel VCF is read\n"
-    "                                        again for every group (it does not stay resident across groups)          [this build]\n"
-    "          --merged                      --cohort: PATH ('-': stdout) receives ONE multi-sample VCF, a GT:GQ column per sample in\n"
-    "                                        manifest order -- the column paste of the per-sample outputs, whatever the grouping;\n"
-    "                                        the sample columns are formatted on the GPU.  -o is then optional (both: both are\n"
-    "                                        written in one pass).  With -v: INFO stays '.', FORMAT is GT:GQ:COVS and every cell\n"
-    "                                        carries its sample's allele coverages; GTS (the likelihoods) come as GP with --gp [this build]\n"
-    "          --gp                          --merged: every cell carries a further field GP (Number=G, Type=Float; FORMAT is GT:GQ:GP,\n"
-    "                                        with -v GT:GQ:COVS:GP): the posterior probability of every genotype in VCF order -- the\n"
-    "                                        numbers behind GTS= of -v, six decimals -- formatted on the GPU; '.' for a record without\n"
-    "                                        a likelihood list (no coverage, one allele, over-covered).  With and without -v; a cell\n"
-    "                                        masked by --min-gq keeps its GP; in BCF a float32 vector.  The files of -o are not touched [this build]\n"
-    "          --pl                          --merged: every cell carries a further field PL (Number=G, Type=Integer; FORMAT is\n"
-    "                                        GT:GQ[:COVS][:GP]:PL): the Phred-scaled likelihood of every genotype in VCF order, made on\n"
-    "                                        the GPU from the cell's coverages WITHOUT the allele-frequency prior (GP has it folded in,\n"
-    "                                        with re-estimated priors their estimate): what Beagle, GLIMPSE or bcftools +fill-tags\n"
-    "                                        read.  The best genotype is 0, the others round(10 log10 of the ratio), capped; a cell\n"
-    "                                        without coverage is all zeros, an over-covered one '.'.  The values do not depend on the\n"
-    "                                        priors, on -v, on GP or on the GQ mask; in BCF an integer vector.  The files of -o are not touched [this build]\n"
-    "          --pl-cap                      --pl: the largest value written, 1..2147483647 (default:255, the bcftools convention) [this build]\n"
-    "          --min-gq                      --merged: a cell whose GQ is below this integer prints its genotype as missing ('./.',\n"
-    "                                        haploid '.'); its :GQ (and :COVS) stay.  The files of -o are not touched        [this build]\n"
-    "          --site-tags                   --merged: INFO becomes AC=..;AN=..;AF=..;NS=.. over the called (not masked) cells of the\n"
-    "                                        WHOLE cohort, whatever the grouping: AC per ALT allele, AN the called allele copies, AF =\n"
-    "                                        AC/AN rounded half up to six decimals (trailing zeros dropped; '.' when AN is 0), NS the\n"
-    "                                        samples with a called cell; counted and formatted on the GPU                    [this build]\n"
-    "          --merged-format               --merged: vcf (default: the text above), bcf (BCF2, BGZF-compressed) or ubcf (the same\n"
-    "                                        bytes uncompressed).  The same records and fields as the text; a cell costs 3 bytes\n"
-    "                                        (diploid GT:GQ) instead of 8 to 10, and the per-sample part of every record is encoded\n"
-    "                                        on the GPU.  A panel header without ##contig lines gets one per reference sequence;\n"
-    "                                        one with some must name every CHROM.  Combines with -1, -v (FORMAT COVS), --min-gq,\n"
-    "                                        --site-tags and -o.  Written from the published layout, like the BCF reader: no file\n"
-    "                                        written by bcftools was available to compare with (format UNPINNED)          [this build]\n"
-    "          --pairs                       --cohort: PATH receives a tab-separated table, one line per unordered pair of samples in\n"
-    "                                        manifest order: over the biallelic records where both are called (--min-gq applies) the\n"
-    "                                        joint counts N00..N22 of their dosages (0, 1, 2 ALT copies; haploid: 0 or 2), their sum N,\n"
-    "                                        IBS0/1/2 and KING = (N11 - 2 IBS0) / (het A + het B), '.' without heterozygotes.  Counted on\n"
-    "                                        the GPU, whatever the grouping; beside -o and/or --merged                       [this build]\n"
-    "          --sample-stats                --cohort: PATH receives a tab-separated table, one line per sample in manifest order: how\n"
-    "                                        many of its cells are called, masked (--min-gq applies) or carry an allele the record lacks,\n"
-    "                                        HOM_REF / HET / HOM_ALT, the called ALT alleles by kind (TS, TV, INS, DEL, OTHER), the GQ sum\n"
-    "                                        and histogram, the coverage sum, the genotyper's status codes, and CALL_RATE, HET_HOM, TSTV,\n"
-    "                                        MEAN_GQ, MEAN_COV ('.' for 0 / 0).  Summed on the GPU, whatever the grouping; beside -o\n"
-    "                                        and/or --merged                                                                 [this build]\n"
-    "          --site-stats                  --cohort: PATH receives a tab-separated table, one line per record with an ALT, in the order\n"
-    "                                        of the merged output: CHROM POS ID REF ALT, SAMPLES (the cohort's size), N (the cells that are\n"
-    "                                        neither masked -- --min-gq applies -- nor carry an allele the record lacks), AN (2 N; haploid: N)\n"
-    "                                        and per ALT, comma-separated, AC, AF (six decimals, as --site-tags), HOM and HET (the samples with\n"
-    "                                        two copies / one copy; haploid: HOM = AC, HET = 0), HWE (the exact two-sided P value of\n"
-    "                                        Hardy-Weinberg proportions) and EXC_HET (the one-sided one for an excess of heterozygotes), both\n"
-    "                                        to six significant digits, '.' when N = 0 or with -1.  Counted and tested on the GPU, whatever\n"
-    "                                        the grouping; beside -o and/or --merged                                         [this build]\n"
-    "          --ld                          --cohort: PATH receives a tab-separated table of linkage disequilibrium, one line per pair of\n"
-    "                                        nearby biallelic records, in the order of the merged output (by A, then by B): CHROM POS_A ID_A\n"
-    "                                        POS_B ID_B, N (the samples whose cells are called -- --min-gq applies -- in both), R2 (the squared\n"
-    "                                        correlation of the two dosages over those samples, six significant digits) and SIGN (+, - or 0:\n"
-    "                                        the sign of the covariance).  A pair is written when R2 exists (both records vary among the N\n"
-    "                                        samples) and passes the options below.  Counted on the GPU, the same bytes whatever the\n"
-    "                                        grouping; beside -o and/or --merged                                             [this build]\n"
-    "          --ld-window                   --ld: a record is paired with the N records behind it on its contig, 1..1024 (default:64);\n"
-    "                                        the panel's records count, biallelic or not                                     [this build]\n"
-    "          --ld-window-bp                --ld: and with none further away than N bases (default:1000000; 0: no limit)    [this build]\n"
-    "          --ld-min-r2                   --ld: the smallest R2 written, in [0, 1] (default:0.2)                          [this build]\n"
-    "          --ld-min-n                    --ld: the fewest samples an R2 is formed from, 1 or more (default:2)            [this build]\n"
-    "          --ibd                         --cohort: PATH receives a tab-separated table of IBS0-free segments, one line per segment and\n"
-    "                                        pair of samples, by pair (in the manifest's order) and along the merged output: A B CHROM START\n"
-    "                                        END LENGTH (END - START), N (the biallelic records where both samples are called -- --min-gq\n"
-    "                                        applies -- and are not opposite homozygotes) and IBS2 (those where their genotypes are equal).\n"
-    "                                        A segment ends in front of an opposite-homozygote record and at the end of a contig.  Made on\n"
-    "                                        the GPU, the same bytes whatever the grouping; beside -o and/or --merged        [this build]\n"
-    "          --ibd-min-records             --ibd: the fewest records (N) of a segment written, 1 or more (default:100)     [this build]\n"
-    "          --ibd-min-bp                  --ibd: the smallest LENGTH written (default:1000000; 0: no limit)               [this build]\n"
-    "          --grm                         --cohort: PATH receives the genetic relationship matrix of the cohort's samples, a tab-separated\n"
-    "                                        table with one line per pair A <= B in the manifest's order: A B N GRM -- N the biallelic records\n"
-    "                                        that enter and where both samples are called (--min-gq applies), GRM the mean over them of the\n"
-    "                                        product of the two standardised dosages (d - 2p) / sqrt(2p(1 - p)), p the record's allele\n"
-    "                                        frequency in the cohort; six decimals, `.` where N is 0.  Exact: 16-bit fixed-point weights,\n"
-    "                                        integer sums on the GPU's matrix cores, the same bytes whatever the grouping; beside -o and/or\n"
-    "                                        --merged                                                                         [this build]\n"
-    "          --grm-min-maf                 --grm: the smallest minor allele frequency of a record that enters, 0 .. 0.5 with at most six\n"
-    "                                        decimals (default:0.01; below about 0.002 a record's weights leave 16 bits and it stays out) [this build]\n"
-    "          --grm-min-n                   --grm: the fewest called samples of a record that enters, 1 or more (default:2)   [this build]\n"
-    "          --grm-format                  --grm: tsv (default) or gcta -- PATH.grm.bin, PATH.grm.N.bin (float32, lower triangle row by\n"
-    "                                        row) and PATH.grm.id, as GCTA and PLINK read them                                [this build]\n"
-    "          --cohort-priors               --cohort: the allele priors of every record are re-estimated from ALL samples of the cohort\n"
-    "                                        before the genotypes are made -- a few EM steps from the panel's AF (or -u's uniform\n"
-    "                                        prior), anchored to it -- and every sample is genotyped under the cohort's frequencies.\n"
-    "                                        Records of 2..8 alleles; estimated on the GPU.  Every output (-o, --merged in text and\n"
-    "                                        BCF, --gp, -v, --min-gq, --site-tags, --pairs, --sample-stats) is made from the new\n"
-    "                                        calls.  The cohort must run as ONE group: more than 64 samples, a --cohort-group below\n"
-    "                                        the cohort, or a cohort that does not fit beside the index is an error -- unless\n"
-    "                                        --prior-groups is given                                                    [this build]\n"
-    "          --prior-groups                --cohort-priors: the cohort may run as several groups -- more than 64 samples (at most\n"
-    "                                        16384), a --cohort-group below the cohort, or as many samples at once as fit beside the\n"
-    "                                        index.  Every group first leaves its coverages in a scratch file beside the output (under\n"
-    "                                        $TMPDIR for stdout; 4 B x allele slots x samples of disk, removed at the end), the\n"
-    "                                        frequencies are estimated from all of them on the GPU, then every group is genotyped under\n"
-    "                                        them.  Every output is byte for byte the one-group run's while every record's total\n"
-    "                                        coverage stays below 65536 (leaving that range takes a --max-coverage of 8192 or more).\n"
-    "                                        A cohort that runs as one group anyway takes the one-group path               [this build]\n"
-    "          --prior-iters                 --cohort-priors: EM iterations, 0..64 (default:5; 0: the panel's priors, every output as\n"
-    "                                        without --cohort-priors).  The default is a design choice, not a measurement [this build]\n"
-    "          --prior-weight                --cohort-priors: the panel's prior counts as this many allele copies beside the cohort's,\n"
-    "                                        a number >= 0 (default:1; 0: the cohort alone, a frequency may then reach 0 and stay).\n"
-    "                                        The default is a design choice, not a measurement                         [this build]\n"
-    "          --priors-out                  --cohort-priors: PATH receives a tab-separated table, one line per output record in output\n"
-    "                                        order: CHROM POS ID REF ALT PANEL_AF COHORT_AF N_INFORMATIVE -- the two AF columns are comma\n"
-    "                                        lists over the ALT alleles, N_INFORMATIVE the samples whose reads entered the estimate [this build]\n"
-    "\n"
-    "  <kmc_output_prefix>: a KMC database (<prefix>.kmc_pre + <prefix>.kmc_suf, KMC 2/3 format), read directly;\n"
-    "  or <prefix>.txt / <prefix> holding `kmc_tools transform <db> dump` text (one `KMER<tab>count` per line).\n"
-    "  READS (call): the sample's reads, counted on the GPU as `kmc -k<r> -ci<min> -cs<max> -fm` would (MALVA:107) -- a FASTQ\n"
-    "  file, a FASTA or multi-line FASTA file, either of them gzip- or BGZF-compressed; a comma-separated list of such files\n"
-    "  (paired ends: a.fq,b.fq, counted together); or @list.txt, one path per line.  Taken in this order: a KMC database at\n"
-    "  the prefix, <prefix>.txt, @list / a comma list, a file whose first non-blank byte is '>' or '@', else a text dump.\n"
-    "  index file: <variants.vcf>.c<r>.k<k>.malvax.zst, the reference's container (sdsl + zstd); `call` also reads this\n"
-    "  build's compact <...>.malvax.hipz (written when MALVA_GENO_INDEX_FORMAT=hipz).\n"
-    "  extra sub-commands (no GPU needed): dump-kmers (signature k-mers of every block); index-convert <fa> <vcf> zst|hipz\n"
-    "\n"
-    "  Verified inputs: the text k-mer dump and text / gzip / bgzip VCF (checked against the reference's own example).  The three\n"
-    "  BINARY formats -- a KMC database, a BCF panel (and the BCF of --merged-format), the reference's sdsl + zstd index container -- are read and written from their\n"
-    "  published layouts and checked against an independent second implementation only: no file written by KMC, bcftools or the\n"
-    "  reference binary was available to this build (formats UNPINNED).  When in doubt convert: `kmc_tools transform <db> dump`,\n"
-    "  `bcftools view -Ov`, and let this build write its own index.\n";
-
-bool parse_arguments(int argc, char **argv, Options &o)
-{
-    // same short options and long names as the reference, including its quirks: --strip-chr / --uniform are
-    // declared with required_argument and --haploid is spelt "haplod" (argument_parser.hpp:70-84)
-    static const option longopts[] = {{"kmer-size", required_argument, nullptr, 'k'},   {"ref-kmer-size", required_argument, nullptr, 'r'},
-                                      {"error-rate", required_argument, nullptr, 'e'},  {"freq-key", required_argument, nullptr, 'f'},
-                                      {"samples", required_argument, nullptr, 's'},     {"max-coverage", required_argument, nullptr, 'c'},
-                                      {"bf-size", required_argument, nullptr, 'b'},     {"strip-chr", required_argument, nullptr, 'p'},
-                                      {"uniform", required_argument, nullptr, 'u'},     {"verbose", no_argument, nullptr, 'v'},
-                                      {"haplod", no_argument, nullptr, '1'},            {"haploid", no_argument, nullptr, '1'},
-                                      {"device", required_argument, nullptr, 'd'},      {"help", no_argument, nullptr, 'h'},
-                                      {"gpus", required_argument, nullptr, 'g'},
-                                      {"min-count", required_argument, nullptr, 1001}, {"max-count", required_argument, nullptr, 1002},
-                                      {"cohort", no_argument, nullptr, 1003},          {"cohort-group", required_argument, nullptr, 1004},
-                                      {"out-dir", required_argument, nullptr, 'o'},   {"merged", required_argument, nullptr, 1005},
-                                      {"min-gq", required_argument, nullptr, 1006},   {"site-tags", no_argument, nullptr, 1007},
-                                      {"merged-format", required_argument, nullptr, 1008}, {"gp", no_argument, nullptr, 1009},
-                                      {"pairs", required_argument, nullptr, 1010},    {"sample-stats", required_argument, nullptr, 1011},
-                                      {"cohort-priors", no_argument, nullptr, 1012},  {"prior-iters", required_argument, nullptr, 1013},
-                                      {"prior-weight", required_argument, nullptr, 1014}, {"priors-out", required_argument, nullptr, 1015},
-                                      {"prior-groups", no_argument, nullptr, 1016},
-                                      {"pl", no_argument, nullptr, 1017},             {"pl-cap", required_argument, nullptr, 1018},
-                                      {"site-stats", required_argument, nullptr, 1019},
-                                      {"ld", required_argument, nullptr, 1020},       {"ld-window", required_argument, nullptr, 1021},
-                                      {"ld-window-bp", required_argument, nullptr, 1022}, {"ld-min-r2", required_argument, nullptr, 1023},
-                                      {"ld-min-n", required_argument, nullptr, 1024},
-                                      {"ibd", required_argument, nullptr, 1025},      {"ibd-min-records", required_argument, nullptr, 1026},
-                                      {"ibd-min-bp", required_argument, nullptr, 1027},
-                                      {"grm", required_argument, nullptr, 1028},      {"grm-min-maf", required_argument, nullptr, 1029},
-                                      {"grm-min-n", required_argument, nullptr, 1030}, {"grm-format", required_argument, nullptr, 1031},
-                                      {nullptr, 0, nullptr, 0}};
-    bool die = false;
-    optind = 1;
-    for (int c; (c = getopt_long(argc, argv, "k:r:e:s:f:c:b:d:g:o:hpuv1", longopts, nullptr)) != -1;) {
-        std::istringstream arg(optarg ? optarg : "");
-        switch (c) {
-        case 'p': o.strip_chr = true; break;
-        case 'u': o.uniform = true; break;
-        case 'k': arg >> o.k; break;
-        case 'r': arg >> o.ref_k; break;
-        case 'e': arg >> o.error_rate; break;
-        case 's': arg >> o.samples; break;
-        case 'f': arg >> o.freq_key; break;
-        case 'c': arg >> o.max_coverage; break;
-        case 'b':
-            arg >> o.bf_size;
-            o.bf_size *= 1ULL << 33; // "GB" on the command line, 2^33 bits each (argument_parser.hpp:119-123)
-            break;
-        case 'd': arg >> o.device; break;
-        case 'g': arg >> o.gpus; break;
-        case 1001:
-        case 1002: {
-            long long v = -1;
-            if (!(arg >> v) || v < 0 || v > 0xFFFFFFFFLL) {
-                std::cerr << "malva : --" << (c == 1001 ? "min" : "max") << "-count takes a count 0.." << 0xFFFFFFFFu << "\n";
-                die = true;
-            } else if (c == 1001) o.min_count = (uint32_t)v;
-            else o.max_count = (uint32_t)v;
-            break;
-        }
-        case 1003: o.cohort = true; break;
-        case 1004:
-            if (!(arg >> o.cohort_group) || o.cohort_group < 1 || o.cohort_group > 64) {
-                std::cerr << "malva : --cohort-group takes 1..64\n";
-                die = true;
-            }
-            break;
-        case 'o': o.out_dir = optarg; break;
-        case 1005:
-            o.merged = optarg;
-            if (o.merged.empty()) {
-                std::cerr << "malva : --merged takes a path, or - for stdout\n";
-                die = true;
-            }
-            break;
-        case 1006: {
-            long long v = 0;
-            if (!(arg >> v) || !(arg >> std::ws).eof() || v < INT32_MIN || v > INT32_MAX) {
-                std::cerr << "malva : --min-gq takes an integer (int32)\n";
-                die = true;
-            } else {
-                o.use_min_gq = true;
-                o.min_gq = (int32_t)v;
-            }
-            break;
-        }
-        case 1007: o.site_tags = true; break;
-        case 1008:
-            o.merged_format = optarg;
-            if (o.merged_format != "vcf" && o.merged_format != "bcf" && o.merged_format != "ubcf") {
-                std::cerr << "malva : --merged-format takes vcf, bcf or ubcf\n";
-                die = true;
-            }
-            break;
-        case 1009: o.gp = true; break;
-        case 1010:
-            o.pairs = optarg;
-            if (o.pairs.empty()) {
-                std::cerr << "malva : --pairs takes a path\n";
-                die = true;
-            }
-            break;
-        case 1011:
-            o.sample_stats = optarg;
-            if (o.sample_stats.empty()) {
-                std::cerr << "malva : --sample-stats takes a path\n";
-                die = true;
-            }
-            break;
-        case 1019:
-            o.site_stats = optarg;
-            if (o.site_stats.empty()) {
-                std::cerr << "malva : --site-stats takes a path\n";
-                die = true;
-            }
-            break;
-        case 1020:
-            o.ld = optarg;
-            if (o.ld.empty()) {
-                std::cerr << "malva : --ld takes a path\n";
-                die = true;
-            }
-            break;
-        case 1021:
-        case 1022:
-        case 1024: {
-            // (digits only: strtoull would take a sign and wrap)
-            const std::string text = optarg;
-            const unsigned long long most = c == 1021 ? MG_LD_MAX_WINDOW : c == 1022 ? ~0ull : 0xFFFFFFFFull, least = c == 1022 ? 0 : 1;
-            unsigned long long v = 0;
-            bool ok = !text.empty() && text.size() <= 20;
-            for (const char ch : text) {
-                ok = ok && ch >= '0' && ch <= '9' && v <= (~0ull - (ch - '0')) / 10;
-                if (ok) v = v * 10 + (ch - '0');
-            }
-            o.ld_sub = true;
-            if (!ok || v < least || v > most) {
-                std::cerr << "malva : --" << (c == 1021 ? "ld-window takes a whole number 1..1024" : c == 1022 ? "ld-window-bp takes a whole number (0: no limit)" : "ld-min-n takes a whole number 1..4294967295") << "\n";
-                die = true;
-            } else if (c == 1021) o.ld_window = (uint32_t)v;
-            else if (c == 1022) o.ld_window_bp = v;
-            else o.ld_min_n = (uint32_t)v;
-            break;
-        }
-        case 1023: {
-            char *end = nullptr;
-            const double v = strtod(optarg, &end);
-            o.ld_sub = true;
-            if (end == optarg || *end || !(v >= 0.0 && v <= 1.0)) {
-                std::cerr << "malva : --ld-min-r2 takes a number in [0, 1]\n";
-                die = true;
-            } else o.ld_min_r2 = v;
-            break;
-        }
-        case 1025:
-            o.ibd = optarg;
-            if (o.ibd.empty()) {
-                std::cerr << "malva : --ibd takes a path\n";
-                die = true;
-            }
-            break;
-        case 1026:
-        case 1027: {
-            // (digits only, as --ld-window)
-            const std::string text = optarg;
-            const unsigned long long most = c == 1026 ? 0xFFFFFFFFull : 0x7FFFFFFFFFFFFFFFull, least = c == 1026 ? 1 : 0;
-            unsigned long long v = 0;
-            bool ok = !text.empty() && text.size() <= 20;
-            for (const char ch : text) {
-                ok = ok && ch >= '0' && ch <= '9' && v <= (~0ull - (ch - '0')) / 10;
-                if (ok) v = v * 10 + (ch - '0');
-            }
-            o.ibd_sub = true;
-            if (!ok || v < least || v > most) {
-                std::cerr << "malva : --" << (c == 1026 ? "ibd-min-records takes a whole number 1..4294967295" : "ibd-min-bp takes a whole number (0: no limit)") << "\n";
-                die = true;
-            } else if (c == 1026) o.ibd_min_records = (uint32_t)v;
-            else o.ibd_min_bp = v;
-            break;
-        }
-        case 1028:
-            o.grm = optarg;
-            if (o.grm.empty()) {
-                std::cerr << "malva : --grm takes a path\n";
-                die = true;
-            }
-            break;
-        case 1029: {
-            // the decimal text read exactly: [D][.DDDDDD], parts per million
-            const std::string text = optarg;
-            const size_t dot = text.find('.');
-            const std::string head = text.substr(0, dot), tail = dot == std::string::npos ? std::string() : text.substr(dot + 1);
-            bool ok = head.size() + tail.size() >= 1 && head.size() <= 1 && tail.size() <= 6;
-            for (const char ch : head + tail) ok = ok && ch >= '0' && ch <= '9';
-            uint32_t ppm = 0;
-            if (ok) {
-                ppm = head.empty() ? 0 : (uint32_t)(head[0] - '0') * 1000000u;
-                uint32_t scale = 100000;
-                for (const char ch : tail) ppm += (uint32_t)(ch - '0') * scale, scale /= 10;
-            }
-            o.grm_sub = true;
-            if (!ok || ppm > 500000) {
-                std::cerr << "malva : --grm-min-maf takes a decimal number 0 .. 0.5 with at most six decimals\n";
-                die = true;
-            } else o.grm_maf_ppm = ppm;
-            break;
-        }
-        case 1030: {
-            const std::string text = optarg;
-            unsigned long long v = 0;
-            bool ok = !text.empty() && text.size() <= 10;
-            for (const char ch : text) {
-                ok = ok && ch >= '0' && ch <= '9';
-                if (ok) v = v * 10 + (ch - '0');
-            }
-            o.grm_sub = true;
-            if (!ok || v < 1 || v > 0xFFFFFFFFull) {
-                std::cerr << "malva : --grm-min-n takes a whole number 1..4294967295\n";
-                die = true;
-            } else o.grm_min_n = (uint32_t)v;
-            break;
-        }
-        case 1031: {
-            const std::string text = optarg;
-            o.grm_sub = true;
-            if (text != "tsv" && text != "gcta") {
-                std::cerr << "malva : --grm-format takes tsv or gcta\n";
-                die = true;
-            } else o.grm_gcta = text == "gcta";
-            break;
-        }
-        case 1012: o.priors.on = true; break;
-        case 1013:
-            if (!parse_prior_iters(optarg, o.priors)) {
-                std::cerr << "malva : --prior-iters takes a whole number 0..64\n";
-                die = true;
-            }
-            break;
-        case 1014:
-            if (!parse_prior_weight(optarg, o.priors)) {
-                std::cerr << "malva : --prior-weight takes a finite number >= 0\n";
-                die = true;
-            }
-            break;
-        case 1015:
-            if (!parse_priors_out(optarg, o.priors)) {
-                std::cerr << "malva : --priors-out takes a path\n";
-                die = true;
-            }
-            break;
-        case 1016: o.priors.groups = true; break;
-        case 1017: o.pl = true; break;
-        case 1018: {
-            long long v = 0;
-            if (!(arg >> v) || !(arg >> std::ws).eof() || v < 1 || v > INT32_MAX) {
-                std::cerr << "malva : --pl-cap takes a whole number 1.." << INT32_MAX << "\n";
-                die = true;
-            } else {
-                o.pl_cap_given = true;
-                o.pl_cap = (int32_t)v;
-            }
-            break;
-        }
-        case 'v': o.verbose = true; break;
-        case '1': o.haploid = true; break;
-        case '?': die = true; break;
-        case 'h': std::cout << USAGE; exit(EXIT_SUCCESS);
-        }
-    }
-    if (argc - optind < 3) {
-        std::cerr << "malva : missing arguments\n";
-        die = true;
-    } else if (argc - optind > 3) {
-        std::cerr << "malva : too many arguments\n";
-        die = true;
-    }
-    if (o.gpus < 1 || o.gpus > 64) {
-        std::cerr << "malva : --gpus must be 1..64\n";
-        die = true;
-    }
-    if (o.cohort && o.out_dir.empty() && o.merged.empty()) {
-        std::cerr << "malva : --cohort needs -o OUTDIR or --merged PATH\n";
-        die = true;
-    }
-    if (!o.cohort && !o.merged.empty()) {
-        std::cerr << "malva : --merged goes with --cohort\n";
-        die = true;
-    }
-    if (o.merged.empty() && (o.use_min_gq || o.site_tags)) {
-        std::cerr << "malva : --min-gq and --site-tags go with --merged\n";
-        die = true;
-    }
-    if (o.merged.empty() && !o.merged_format.empty()) {
-        std::cerr << "malva : --merged-format goes with --merged\n";
-        die = true;
-    }
-    if (o.merged.empty() && o.gp) {
-        std::cerr << "malva : --gp goes with --merged\n";
-        die = true;
-    }
-    if (o.merged.empty() && o.pl) {
-        std::cerr << "malva : --pl goes with --merged\n";
-        die = true;
-    }
-    if (o.pl_cap_given && !o.pl) {
-        std::cerr << "malva : --pl-cap goes with --pl\n";
-        die = true;
-    }
-    if (o.cohort && o.gpus > 1) {
-        std::cerr << "malva : --cohort does not combine with --gpus > 1\n";
-        die = true;
-    }
-    if (!o.cohort && !o.pairs.empty()) {
-        std::cerr << "malva : --pairs goes with --cohort\n";
-        die = true;
-    }
-    if (!o.cohort && !o.sample_stats.empty()) {
-        std::cerr << "malva : --sample-stats goes with --cohort\n";
-        die = true;
-    }
-    if (!o.cohort && !o.site_stats.empty()) {
-        std::cerr << "malva : --site-stats goes with --cohort\n";
-        die = true;
-    }
-    if (!o.cohort && !o.ld.empty()) {
-        std::cerr << "malva : --ld goes with --cohort\n";
-        die = true;
-    }
-    if (o.ld.empty() && o.ld_sub) {
-        std::cerr << "malva : --ld-window, --ld-window-bp, --ld-min-r2 and --ld-min-n go with --ld\n";
-        die = true;
-    }
-    if (!o.cohort && !o.ibd.empty()) {
-        std::cerr << "malva : --ibd goes with --cohort\n";
-        die = true;
-    }
-    if (o.ibd.empty() && o.ibd_sub) {
-        std::cerr << "malva : --ibd-min-records and --ibd-min-bp go with --ibd\n";
-        die = true;
-    }
-    if (!o.cohort && !o.grm.empty()) {
-        std::cerr << "malva : --grm goes with --cohort\n";
-        die = true;
-    }
-    if (o.grm.empty() && o.grm_sub) {
-        std::cerr << "malva : --grm-min-maf, --grm-min-n and --grm-format go with --grm\n";
-        die = true;
-    }
-    if (const std::string why = check_prior_options(o.priors, o.cohort); !why.empty()) {
-        std::cerr << "malva : " << why << "\n";
-        die = true;
-    }
-    if (!o.cohort && (!o.out_dir.empty() || o.cohort_group)) {
-        std::cerr << "malva : -o and --cohort-group go with --cohort\n";
-        die = true;
-    }
-    if (die) {
-        std::cerr << "\n" << USAGE;
-        return false;
-    }
-    o.fasta_path = argv[optind++];
-    o.vcf_path = argv[optind++];
-    o.kmc_path = argv[optind++];
-    if (const char *bits = getenv("MALVA_GENO_BF_BITS")) // tests: filters smaller than -b's 2^33-bit granule
-        if (atoll(bits) > 0) o.bf_size = (uint64_t)atoll(bits);
-    return true;
-}
 
 // pelapsed(), main.cpp:93-115
 auto t_start = std::chrono::steady_clock::now();
@@ -1962,29 +1440,23 @@ int main(int argc, char **argv)
         std::cerr << "malva missing arguments\n" << USAGE << std::endl;
         return 1;
     }
-    Options o;
     const std::string cmd = argv[1];
+    int (*const run)(const Options &) = cmd == "index-convert"            ? convert_main
+                                        : cmd.compare(0, 5, "index") == 0 ? index_main
+                                        : cmd.compare(0, 4, "call") == 0  ? call_main
+                                        : cmd == "dump-kmers"             ? dump_main
+                                                                          : nullptr;
+    if (!run) {
+        std::cerr << "Could not interpret command " << argv[1] << ".\nAccepted commands are index and call." << std::endl;
+        return 1;
+    }
     try {
-        if (cmd == "index-convert") {
-            if (!parse_arguments(argc - 1, argv + 1, o)) return EXIT_FAILURE;
-            return convert_main(o);
-        }
-        if (cmd.compare(0, 5, "index") == 0) {
-            if (!parse_arguments(argc - 1, argv + 1, o)) return EXIT_FAILURE;
-            return index_main(o);
-        }
-        if (cmd.compare(0, 4, "call") == 0) {
-            if (!parse_arguments(argc - 1, argv + 1, o)) return EXIT_FAILURE;
-            return call_main(o);
-        }
-        if (cmd == "dump-kmers") {
-            if (!parse_arguments(argc - 1, argv + 1, o)) return EXIT_FAILURE;
-            return dump_main(o);
-        }
+        Options o;
+        const Parsed parsed = parse_arguments(argc - 1, argv + 1, o, std::cerr);
+        if (parsed == Parsed::help) std::cout << USAGE;
+        return parsed == Parsed::ok ? run(o) : parsed == Parsed::help ? EXIT_SUCCESS : EXIT_FAILURE;
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << std::endl;
         return 1;
     }
-    std::cerr << "Could not interpret command " << argv[1] << ".\nAccepted commands are index and call." << std::endl;
-    return 1;
 }
