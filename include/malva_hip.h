@@ -506,9 +506,10 @@ int mg_call_isolated_device(mg_ctx *ctx, size_t n_vars, const void *d_pos, const
  * s = 1075 - the biased exponent, and the remainder against 2^(s-1)); an unprintable one prints `.`.  PL is the G comma-separated
  * values, MG_PL_MISSING as `.`; the whole field is one `.` when G == 0 or every value of the cell is missing.
  * n_vars == 0 is legal: row_off_out[0] = 0.  *text_bytes_out always receives the bytes the text needs; when that is more
- * than text_cap the call returns MG_ERR_LIMIT, nothing is written at or behind text_cap, row_off_out is valid all the
- * same, and the caller may come again with a larger buffer.  A NULL cells pointer: MG_ERR_ARG.  The host form synchronises; the
- * device form is asynchronous on the context's stream until it reads the 8-byte total back (text_bytes_out is a HOST pointer in both).
+ * than text_cap the call returns MG_ERR_LIMIT, nothing is written at or behind text_cap, the text_cap bytes in front of it are the
+ * text's first text_cap bytes, row_off_out is valid all the same, and the caller may come again with a larger buffer.  A NULL
+ * cells pointer: MG_ERR_ARG.  The host form synchronises; the device form is asynchronous on the context's stream until it reads the
+ * 8-byte total back (text_bytes_out is a HOST pointer in both).
  * mg_format_stats (waits for it): ms_out[3], device milliseconds of the most recent call's length pass, scan and write pass. */
 #define MG_CELLS_GP 1u
 #define MG_CELLS_PL 2u
@@ -543,7 +544,7 @@ int mg_format_stats(mg_ctx *ctx, float *ms_out);
  * prints `0`, q == 10^6 prints `1`, anything else `0.` and q as six zero-padded digits with trailing zeros removed; AN == 0
  * prints `.` for every AF.  A record with fewer than two slots prints `AN=n;NS=s`.  Buffer contract as mg_format_calls:
  * *text_bytes_out (a HOST pointer in both forms) always receives the bytes needed, MG_ERR_LIMIT when that exceeds text_cap,
- * nothing written at or behind text_cap, row_off_out valid all the same.
+ * nothing written at or behind text_cap, the bytes in front of it the text's first, row_off_out valid all the same.
  * mg_site_stats (waits): ms_out[2], device milliseconds of the most recent mg_site_counts* and of the most recent
  * mg_format_site_info* (its three passes together); 0 for a kind not called yet, MG_ERR_STATE when neither was. */
 int mg_site_counts(mg_ctx *ctx, size_t n_vars, uint32_t n_planes, int haploid, const int32_t *gt1, const int32_t *gt2, const int32_t *gq, int use_mask,
@@ -925,9 +926,10 @@ int mg_estimate_priors_stats(mg_ctx *ctx, float *ms_out);
  * mg_format_calls' rows in BCF2's binary form (VCF/BCF specification v4.3, section 6.3.3; restated from the published layout,
  * parity with htslib unpinned).  The cells (mg_cells, with its field rules), the host and _device forms, the stream behaviour and
  * the buffer contract are mg_format_calls': *bytes_out (a HOST pointer in both forms) always receives the bytes needed,
- * MG_ERR_LIMIT when that exceeds out_cap, nothing written at or behind out_cap, row_off_out valid all the same, n_vars == 0
- * legal.  Row v = out[row_off_out[v] .. row_off_out[v + 1]) is exactly the record's per-sample ("indiv") block, its length the
- * record's l_indiv: two fields, and one more each with cov, MG_CELLS_GP and MG_CELLS_PL, in this order --
+ * MG_ERR_LIMIT when that exceeds out_cap, nothing written at or behind out_cap, the out_cap bytes in front of it the output's
+ * first, row_off_out valid all the same, n_vars == 0 legal.  Row v = out[row_off_out[v] .. row_off_out[v + 1]) is exactly the
+ * record's per-sample ("indiv") block, its length the record's l_indiv: two fields, and one more each with cov, MG_CELLS_GP and
+ * MG_CELLS_PL, in this order --
  *   GT    typed_int(keys->gt),  desc(ploidy, T), for every plane `ploidy` values (1 in haploid mode, else 2): allele index a
  *         as (a + 1) << 1, unphased; a cell with use_mask != 0 and gq < min_gq writes 0 (missing) for each of its values
  *   GQ    typed_int(keys->gq),  desc(1, T), one value per plane, as it is, mask or no mask
@@ -1019,6 +1021,11 @@ int mg_debug_packed_index(mg_ctx *ctx, int which, const uint64_t *hi, const uint
 /* the exclusive scan mg_bf_finalize runs over its tile sums, on n values of the caller's: x is replaced by its exclusive prefix
  * (each entry modulo 2^32, as the kernel stores it), *total by the sum of all of them in 64 bits.  n == 0 gives a total of 0. */
 int mg_debug_tile_scan(mg_ctx *ctx, uint32_t *x, uint64_t n, uint64_t *total);
+/* the scan the three row encoders (mg_format_calls, mg_format_site_info, mg_encode_calls_bcf) run between their length pass and their
+ * write pass, on n row lengths of the caller's: row_off_out[0 .. n] receives the exclusive prefix in 64 bits (row_off_out[n] the sum),
+ * *total what the encoder would read as the bytes needed.  flag != 0 raises the mark a length pass leaves for a row of 4 GB or more:
+ * row_off_out is what it is without the mark, *total is ~0.  n == 0 gives row_off_out[0] = 0 and a total of 0.  No kernel of its own. */
+int mg_debug_row_scan(mg_ctx *ctx, const uint32_t *len, uint64_t n, int flag, uint64_t *row_off_out /* [n + 1] */, uint64_t *total);
 /* the filter's directory inside the records as the call-time lookups read it: for each slot idx[i] of `bf` (MG_BF_ALT), the
  * counter index (rank) of its bit or -1 when the bit is clear, and the u16 counter the genotyping would read (0 when clear),
  * through the context's current views -- so the counters come from the records' copies whenever those are live.

@@ -204,6 +204,7 @@ def lib():
         "mg_debug_bf_index": [vp, it, vp, sz, sz, vp],
         "mg_debug_packed_index": [vp, it, vp, vp, sz, u32, vp],
         "mg_debug_tile_scan": [vp, vp, u64, vp],
+        "mg_debug_row_scan": [vp, vp, u64, it, vp, vp],
         "mg_debug_bucket_count": [vp, vp, u64, vp, vp],
         "mg_scan_stats": [vp, vp, vp],
         "mg_blocks_stats": [vp, vp, vp],
@@ -243,7 +244,7 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_index_isolated",
             "mg_lookup_cover", "mg_cover_blocks", "mg_index_blocks", "mg_genotype", "mg_reference_upload", "mg_call_isolated", "mg_call_isolated_device",
             "mg_bf_export", "mg_bf_import", "mg_bf_export_sparse", "mg_bf_import_sparse", "mg_map_export", "mg_map_import", "mg_debug_bf_index",
-            "mg_debug_packed_index", "mg_debug_tile_scan", "mg_debug_bucket_count", "mg_scan_stats", "mg_blocks_stats", "mg_set_option", "mg_get_option"]
+            "mg_debug_packed_index", "mg_debug_tile_scan", "mg_debug_row_scan", "mg_debug_bucket_count", "mg_scan_stats", "mg_blocks_stats", "mg_set_option", "mg_get_option"]
 
 
 def _p(a):
@@ -482,6 +483,14 @@ class Context:
         total = C.c_uint64()
         self._ck(self._L.mg_debug_tile_scan(self.h, _p(x) if x.size else None, x.size, C.byref(total)))
         return x, total.value
+
+    def row_scan(self, length, flag=False):
+        """the row encoders' scan on the caller's row lengths: (row_off [n + 1] uint64, total); flag: as behind a row of 4 GB or more"""
+        length = np.ascontiguousarray(length, dtype=np.uint32)
+        row_off = np.zeros(length.size + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        self._ck(self._L.mg_debug_row_scan(self.h, _p(length) if length.size else None, length.size, int(flag), _p(row_off), C.byref(total)))
+        return row_off, total.value
 
     def bucket_count(self, idx):
         """(rank or -1, u16 counter) of filter slots of `bf` as the call-time lookups read them from the records"""

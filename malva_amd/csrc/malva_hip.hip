@@ -5703,6 +5703,34 @@ MG_EXPORT int mg_debug_tile_scan(mg_ctx *c, uint32_t *x, uint64_t n, uint64_t *t
     *total = t;
     return MG_OK;
 }
+// fmt_scan on the caller's row lengths, as encode_rows runs it behind a length pass: the text encoder's scratch, the meta block zeroed
+// and, with `flag`, meta[1] raised as a length kernel raises it for a row of 4 GB or more
+MG_EXPORT int mg_debug_row_scan(mg_ctx *c, const uint32_t *len, uint64_t n, int flag, uint64_t *row_off_out, uint64_t *total)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    if ((n && !len) || !row_off_out || !total) return fail(c, MG_ERR_ARG, "len, row_off_out or total is NULL");
+    if (n >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_debug_row_scan: more than 2^32 - 1 rows in one call");
+    *total = 0;
+    row_off_out[0] = 0;
+    if (n == 0) return MG_OK;
+    void *d_len, *d_meta, *part, *d_off;
+    TRY(upload(c, c->s_enc[TM_FMT][ES_LEN], len, 4 * n, &d_len));
+    TRY(scratch(c, c->s_enc[TM_FMT][ES_META], 16, &d_meta));
+    const u64 n_part = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TRY(scratch(c, c->s_scan, 8 * n_part, &part));
+    TRY(scratch(c, c->stage[ST_ROW_OFF], 8 * (n + 1), &d_off));
+    const unsigned long long raised[2] = {0, flag ? 1ull : 0ull};
+    unsigned long long t = 0;
+    HIP_TRY(c, hipMemcpyAsync(d_meta, raised, 16, hipMemcpyHostToDevice, c->stream));
+    fmt_scan(c, d_len, n, n_part, part, d_off, (unsigned long long *)d_meta);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(row_off_out, d_off, 8 * (n + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&t, d_meta, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *total = t;
+    return MG_OK;
+}
 // bucket_rank / bucket_count of filter slots, through the views a lookup launched now would get
 MG_EXPORT int mg_debug_bucket_count(mg_ctx *c, const uint64_t *idx, uint64_t n, int64_t *rank_out, uint32_t *count_out)
 {

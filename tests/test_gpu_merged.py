@@ -194,8 +194,8 @@ def test_format_calls_is_exact(ctx, planes, haploid, with_cov, n):
 @pytest.mark.parametrize("with_cov", [False, True], ids=["gt-gq", "gt-gq-covs"])
 @pytest.mark.parametrize("planes,n", [(1, 1), (3, 257), (17, 5000), (64, 40000)])
 def test_buffer_too_small(ctx, planes, n, with_cov):
-    """text_cap one byte short, and 0: MG_ERR_LIMIT with the exact size, row_off valid, nothing at or behind text_cap touched, and the
-    call with the size it reported succeeds -- host form and device form"""
+    """text_cap one byte short, and 0: MG_ERR_LIMIT with the exact size, row_off valid, nothing at or behind text_cap touched, the bytes
+    in front of it the text's first, and the call with the size it reported succeeds -- host form and device form"""
     haploid = planes == 3
     g1, g2, gq, cov, vao = _case(planes, n, haploid, with_cov, seed=77 + planes)
     want, want_off = format_numpy(g1, g2, gq, haploid, cov, vao)
@@ -208,12 +208,14 @@ def test_buffer_too_small(ctx, planes, n, with_cov):
         assert rc == MG_ERR_LIMIT and need.value == len(want)
         assert np.array_equal(off, want_off)
         assert (buf[cap:] == 0xAA).all()
+        assert buf[:cap].tobytes() == want[:cap]
         rc = ctx._L.mg_format_calls(ctx.h, C.byref(Cells(n, planes, int(haploid), p(g1), p(g2), p(gq), 0, 0, p(cov), p(vao))), p(buf), need.value, p(off), C.byref(need))
         assert rc == 0 and need.value == len(want) and buf[:len(want)].tobytes() == want and (buf[len(want):] == 0xAA).all()
         for shift in (0, 7):
             rc, dneed, text, guard, doff = _device_form(ctx, g1, g2, gq, haploid, cov, vao, cap, guard=4096, shift=shift)
             assert rc == MG_ERR_LIMIT and dneed == len(want)
             assert np.array_equal(doff, want_off)
+            assert text == want[:cap]
             assert (guard == 0xAA).all(), "bytes behind text_cap were written"
             rc, dneed, text, guard, doff = _device_form(ctx, g1, g2, gq, haploid, cov, vao, dneed, shift=shift)
             assert rc == 0 and text == want and (guard == 0xAA).all()
