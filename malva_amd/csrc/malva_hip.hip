@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "count_plan.h"
 #include "gate_geometry.h"
 #include "geno_dev.h"
 #include "malva_hip.h"
@@ -3608,18 +3609,7 @@ int check_pairs(mg_ctx *c, size_t n_words, const void *a, uint32_t n_a, const vo
     if (n_words >= (1ull << 32)) return fail(c, MG_ERR_LIMIT, "mg_pair_counts: more than 2^32 - 1 words in one call");
     return MG_OK;
 }
-// The word axis is cut into runs, one workgroup per tile of pairs and run: as many runs as give about PAIR_TARGET_WGS workgroups -- with
-// one tile (2 planes x 1e7 records) all the parallelism comes from here --, none longer than PAIR_MAX_RUN (the 32-bit sums)
-constexpr u64 PAIR_TARGET_WGS = 2048;
-u64 pair_count_plan(u64 n_words, u32 tiles, u64 *n_runs)
-{
-    const u64 chunks = (n_words + PAIR_CHUNK - 1) / PAIR_CHUNK;
-    u64 runs = std::min<u64>(chunks, std::max<u64>(1, PAIR_TARGET_WGS / tiles));
-    runs = std::max<u64>(runs, (n_words + PAIR_MAX_RUN - 1) / PAIR_MAX_RUN);
-    const u64 run = (chunks + runs - 1) / runs * PAIR_CHUNK; // (whole chunks; at most PAIR_MAX_RUN, itself a multiple of PAIR_CHUNK)
-    *n_runs = (n_words + run - 1) / run;
-    return run;
-}
+// (the cut of the word axis into runs: pair_count_plan, count_plan.h)
 } // namespace
 
 MG_EXPORT int mg_pair_counts_device(mg_ctx *c, size_t n_words, const void *d_planes_a, uint32_t n_a, const void *d_planes_b, uint32_t n_b, int accumulate, void *d_counts)
@@ -3677,18 +3667,7 @@ int check_sample(mg_ctx *c, const mg_cells &x, const void *counts)
     if (!counts || (x.n_vars && !x.var_allele_off)) return fail(c, MG_ERR_ARG, "NULL argument");
     return MG_OK;
 }
-// The records are cut into runs, one workgroup per plane and run: as many runs as give about SAMPLE_TARGET_WGS workgroups over all
-// planes -- a chip's worth of waves, and a few dozen atomic adds per counter --, none longer than SAMPLE_MAX_RUN (the 32-bit accumulators)
-constexpr u64 SAMPLE_TARGET_WGS = 2048;
-u64 sample_count_plan(u64 n_vars, u32 n_planes, u64 *n_runs)
-{
-    const u64 chunks = (n_vars + SAMPLE_TPB - 1) / SAMPLE_TPB;
-    u64 runs = std::min<u64>(chunks, std::max<u64>(1, SAMPLE_TARGET_WGS / n_planes));
-    runs = std::max<u64>(runs, (n_vars + SAMPLE_MAX_RUN - 1) / SAMPLE_MAX_RUN);
-    const u64 run = (chunks + runs - 1) / runs * SAMPLE_TPB; // (whole chunks; at most SAMPLE_MAX_RUN, itself a multiple of SAMPLE_TPB)
-    *n_runs = (n_vars + run - 1) / run;
-    return run;
-}
+// (the cut of the records into runs: sample_count_plan, count_plan.h)
 
 int sample_counts_device(mg_ctx *c, const mg_cells &x, int accumulate, void *d_counts)
 {

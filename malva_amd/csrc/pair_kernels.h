@@ -21,6 +21,7 @@
 // (pair_count_plan), so a sum stays below 2^26.
 #pragma once
 #include "call_text_kernels.h"
+#include "count_plan.h" // PAIR_CHUNK, PAIR_MAX_RUN, pair_count_plan (plain C++: malva_hip.hip includes it first, outside every namespace)
 
 namespace {
 using namespace mg;
@@ -28,9 +29,7 @@ using namespace mg;
 constexpr u32 PACK_TPB = 256;           // four waves, four words of one plane
 constexpr u32 PAIR_TILE = 16;           // a workgroup's pairs: PAIR_TILE x PAIR_TILE, one per thread
 constexpr u32 PAIR_TPB = PAIR_TILE * PAIR_TILE;
-constexpr u32 PAIR_CHUNK = 32;          // words of every plane staged at a time
 constexpr u32 PAIR_LD = PAIR_TILE + 1;  // the padded row of the LDS image
-constexpr u64 PAIR_MAX_RUN = 1u << 20;  // words per workgroup at most (the 32-bit sums)
 // LDS: 2 operands x 3 dosages x PAIR_CHUNK x PAIR_LD x 8 bytes = 26,112 bytes, static
 
 struct PackArgs {

@@ -24,12 +24,11 @@
 // plane in one call -- the caller's table is 64-bit and wraps there as well, by definition.
 #pragma once
 #include "call_text_kernels.h"
+#include "count_plan.h" // SAMPLE_TPB, SAMPLE_MAX_RUN, sample_count_plan (plain C++: malva_hip.hip includes it first, outside every namespace)
 
 namespace {
 using namespace mg;
 
-constexpr u32 SAMPLE_TPB = 256;           // four waves, 256 consecutive records of one plane per step
-constexpr u64 SAMPLE_MAX_RUN = 1u << 20;  // records per workgroup at most (the 32-bit accumulators), a multiple of SAMPLE_TPB
 static_assert(MG_SAMPLE_SLOTS == 32 && MG_SS_COUNTED == 29 && MG_SS_GQ_0 + 10 == MG_SS_COUNTED, "the slot table of include/malva_hip.h");
 
 struct SampleArgs {
