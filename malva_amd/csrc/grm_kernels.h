@@ -26,19 +26,15 @@
 // (a small cohort is split along the records) and add with 64-bit atomics -- integer sums do not depend on the order.  Otherwise a block
 // has one wave in the launch and adds in place.
 #pragma once
+#include "grm_plan.h" // GRM_K, GRM_BLOCK, GRM_MAX_RUN, grm_run_plan (plain C++: malva_hip.hip includes it first, outside every namespace)
 #include "ibd_kernels.h"
 
 namespace {
 using namespace mg;
 
 constexpr u32 GRM_TPB = 256;
-constexpr u32 GRM_K = 64;           // records per MFMA step; a piece's rows are padded to it
-constexpr u32 GRM_BLOCK = 32;       // a wave's block of pairs: 2 x 2 tiles of 16 x 16
-constexpr u32 GRM_MAX_RUN = 65536;  // records per wave at most (the i32 accumulators)
 constexpr i32 GRM_SHIFT = 10, GRM_MAX_Q = 32639;
 constexpr int GRM_SCRATCH_MB = 384; // a piece's three byte images at most (3 bytes per padded sample and record), unless one MFMA step needs more
-constexpr u64 GRM_FILL = 2048;      // waves a Gram launch should have (256 CUs x 4 SIMDs x 2): a small cohort is split along the records
-constexpr u64 GRM_MIN_RUN = 1024;   // ... into runs no shorter than this
 
 struct GrmWeightArgs {
     u64 n_vars, v0, count; // the step's records (the stride of `sites`); the records to weigh: v0 .. v0 + count - 1, q_out[0 .. count - 1]

@@ -19,6 +19,7 @@
 #include "count_plan.h"
 #include "gate_geometry.h"
 #include "geno_dev.h"
+#include "grm_plan.h"
 #include "malva_hip.h"
 
 using namespace mg;
@@ -4240,14 +4241,12 @@ MG_EXPORT int mg_grm_step_device(mg_ctx *c, size_t n_vars, uint32_t n_groups, co
     c->grm_tm.valid = false;
     c->grm_seen += n_vars;
     if (!n_vars) return MG_OK;
-    const u32 n = c->grm_samples, rows = (n + GRM_BLOCK - 1) / GRM_BLOCK * GRM_BLOCK, blocks = rows / GRM_BLOCK;
-    const u64 cap = (u64)c->grm_scratch_mb << 20;
-    const u64 piece_max = std::max<u64>(GRM_K, cap / (3ull * rows) / GRM_K * GRM_K);
+    const u32 n = c->grm_samples, rows = grm_rows(n), blocks = rows / GRM_BLOCK;
+    const u64 piece_max = grm_piece_max(rows, (u64)c->grm_scratch_mb << 20); // (the cut into pieces and runs: grm_plan.h)
     long long *d_sum = (long long *)c->grm_state;
     unsigned long long *d_count = (unsigned long long *)c->grm_state + c->grm_pairs, *d_entered = d_count + c->grm_pairs;
-    const u64 upper = (u64)blocks * (blocks + 1) / 2;
     for (u64 v0 = 0; v0 < n_vars; v0 += piece_max) {
-        const u64 piece = std::min<u64>(piece_max, n_vars - v0), ld = (piece + GRM_K - 1) / GRM_K * GRM_K;
+        const u64 piece = std::min<u64>(piece_max, n_vars - v0), ld = grm_ld(piece);
         if (c->grm_tm.valid) { // the piece before: its events are about to be used again
             float ms[2];
             TRY(timer_read(c, c->grm_tm, ms));
@@ -4264,13 +4263,8 @@ MG_EXPORT int mg_grm_step_device(mg_ctx *c, size_t n_vars, uint32_t n_groups, co
         hipLaunchKernelGGL(grm_expand_kernel, dim3((unsigned)((ld / 4 + GRM_TPB - 1) / GRM_TPB), (rows + 63) / 64), dim3(GRM_TPB), 0, c->stream, e);
         HIP_TRY(c, hipGetLastError());
         TRY(timer_mark(c, c->grm_tm, 1));
-        // runs: at least ceil(ld / GRM_MAX_RUN); more while the launch has fewer than GRM_FILL waves and a run keeps GRM_MIN_RUN records
-        const u64 steps = ld / GRM_K;
-        u64 runs = (ld + GRM_MAX_RUN - 1) / GRM_MAX_RUN;
-        runs = std::max(runs, std::min<u64>((GRM_FILL + upper - 1) / upper, (ld + GRM_MIN_RUN - 1) / GRM_MIN_RUN));
-        runs = std::min<u64>(std::min<u64>(runs, steps), 65535);
-        const u64 run = (steps + runs - 1) / runs * GRM_K; // (at most GRM_MAX_RUN: runs >= ceil(ld / GRM_MAX_RUN), both multiples of GRM_K)
-        runs = (ld + run - 1) / run;
+        uint64_t runs = 0;
+        const u64 run = grm_run_plan(ld, blocks, &runs);
         const GrmGramArgs g{ld, run, n, h, l, cc, d_sum, d_count};
         if (runs > 1) hipLaunchKernelGGL(grm_gram_kernel<true>, dim3(blocks, blocks, (unsigned)runs), dim3(64), 0, c->stream, g);
         else hipLaunchKernelGGL(grm_gram_kernel<false>, dim3(blocks, blocks, 1), dim3(64), 0, c->stream, g);

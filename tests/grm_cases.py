@@ -103,3 +103,78 @@ def fold_case():
     """508 samples, 140,000 identical records, sample 0 hom-alt and the rest hom-ref: h h = 16129 a record, past 2^31 from 133,145 records on.
     -> (one record's D, the number of records)"""
     return _one_alt(FOLD_SAMPLES).reshape(1, -1), FOLD_RECORDS
+
+
+# ---- the run plan: the Gram kernel without atomics, and a full run of the i32 accumulators ---------------------------------------------
+# A plan case is a dict: name, n_samples, front (random records, no two samples alike, or None), record (one record's dosages) and count
+# (how often it follows the front), and `plan`: the pieces mg_grm_step must cut the one step into, as (records, run, runs) -- runs == 1 is
+# grm_gram_kernel<false>.  tests/test_grm_cases_cpu.py proves the plan from the restatement of tests/test_grm_plan_cpu.py, which that file
+# holds against csrc/grm_plan.h.
+BOUND_SAMPLES, BOUND_ALT = 2017, (0, 31, 32, 2016)          # 64 blocks of 32: 2,080 on and above the diagonal, the first count past GRM_FILL
+BOUND_Q, BOUND_H = (-65, 16211, 32487), 127                 # the record's weights and the high digit of q2: the largest |h| there is
+FRONT_RECORDS = 300
+
+
+def bound_record(n_samples):
+    """four hom-alt samples -- the first, both sides of the first block seam, the last -- among hom-ref ones: at 2,017 samples the entering
+    record whose h h comes closest to what an i32 run can hold (16,129 a record, 1,057,030,144 over 65,536 records, below 2^30)"""
+    row = np.zeros(n_samples, dtype=np.int64)
+    row[[s if s < n_samples else n_samples - 1 for s in BOUND_ALT]] = 2
+    row.setflags(write=False)
+    return row
+
+
+def _plan_case(name, n_samples, records, plan, front):
+    F = random_dosage(FRONT_RECORDS, n_samples, seed=300 + n_samples) if front else None
+    if F is not None:
+        F.setflags(write=False)
+    return dict(name=name, n_samples=n_samples, front=F, record=bound_record(n_samples), count=records - (FRONT_RECORDS if front else 0), records=records, plan=plan,
+                haploid=False, maf_ppm=0, min_n=1)
+
+
+def plan_cases():
+    out = []
+    for front in (False, True):
+        tag = "_behind_random_records" if front else ""
+        out.append(_plan_case("no_atomics_17_steps" + tag, BOUND_SAMPLES, 1025, [(1025, 1088, 1)], front))
+        out.append(_plan_case("no_atomics_full_run_then_one_step" + tag, BOUND_SAMPLES, 65537, [(65536, 65536, 1), (1, 64, 1)], front))
+        out.append(_plan_case("one_block_row_fewer_flips_to_atomics" + tag, BOUND_SAMPLES - 1, 65537, [(65537, 32832, 2)], front))
+    return out
+
+
+def plan_case_words(case):
+    """-> uint64 [groups, 3, records]: the front's words, then the one record's `count` times"""
+    one = np.repeat(M.words_from_dosage(case["record"], case["n_samples"]), case["count"], axis=2)
+    if case["front"] is None:
+        return np.ascontiguousarray(one)
+    return np.ascontiguousarray(np.concatenate([M.words_from_dosage(case["front"], case["n_samples"]), one], axis=2))
+
+
+_FRONT_SUMS = {}
+
+
+def sums_in_doubles(D, n_samples):
+    """M.grm_sums for a wide cohort: the model's cell weights, the two matrix products in binary64 -- exact while every sum stays below
+    2^53 (asserted) -- because numpy's int64 product takes seconds at 2,017 samples"""
+    X, Cc, entered = M.cell_weights(np.asarray(D, dtype=np.int64).reshape(-1, n_samples))
+    assert int(np.abs(X).max(initial=0)) ** 2 * max(len(X), 1) < 2 ** 53
+    a, b = M.pair_index(n_samples)
+    Xf, Cf = X.astype(np.float64), Cc.astype(np.float64)
+    return np.rint(Xf.T @ Xf)[a, b].astype(np.int64), np.rint(Cf.T @ Cf)[a, b].astype(np.uint64), len(X), entered
+
+
+def plan_case_expected(case):
+    """-> (S, N, seen, entered): the model's one-record table times the count, on top of the model's table of the front (made once per
+    sample count and left unchanged)"""
+    n = case["n_samples"]
+    S1, N1, _, e1 = M.grm_sums(case["record"], n)
+    assert e1 == 1
+    S, N, entered = S1 * case["count"], N1 * np.uint64(case["count"]), case["count"]
+    if case["front"] is not None:
+        if n not in _FRONT_SUMS:
+            _FRONT_SUMS[n] = sums_in_doubles(case["front"], n)
+            for x in _FRONT_SUMS[n][:2]:
+                x.setflags(write=False)
+        S0, N0, _, e0 = _FRONT_SUMS[n]
+        S, N, entered = S + S0, N + N0, entered + e0
+    return S, N, case["records"], entered

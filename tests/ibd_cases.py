@@ -157,3 +157,119 @@ def random_case(n_samples, n_vars, min_records, seed):
     pos = np.cumsum(rng.integers(1, 201, size=n_vars)).astype(np.uint32)
     cuts = [[], list(range(64, n_vars, 64)), list(range(65, n_vars, 65)), list(range(1000, n_vars, 1000))]
     return _case("random_%d_%d_%d" % (n_samples, n_vars, min_records), D, n_samples, chrom=chrom, pos=pos, min_records=min_records, min_bp=RANDOM_MIN_BP, cuts=cuts)
+
+
+# ---- seam cases: the chunks of ibd_walk_kernel, the words of ibd_starts_kernel, the tiles of pairs -------------------------------------------
+# The same dicts as directed_cases(), with `seams`: the seams of IBD_SEAMS the case claims.  A step of more than 2,048 records takes a second
+# trip through the kernel's chunk loop (PAIR_CHUNK = 32 words, staged with the chromosome-start words beside them); these cases put a
+# break, an open run or a chromosome change on both sides of that trip, in one step and with cuts at the seam.
+PAIR_CHUNK, PAIR_TILE, IBD_TR_WORDS = 32, 16, 16                        # pair_kernels.h, ibd_kernels.h (a test's copy)
+CHUNK_RECORDS = 64 * PAIR_CHUNK
+
+
+def _only_pair(S, a, b, pattern, n_front=0):
+    """S samples, all cells missing but those of samples a and b, which carry the two-sample pattern"""
+    D = np.full((n_front + len(pattern), S), -1, dtype=np.int64)
+    for v, s in enumerate(pattern):
+        D[n_front + v, a], D[n_front + v, b] = SYMBOLS[s]
+    return D
+
+
+def _counts_case(S, n=120):
+    """sample s is hom-alt at the records v with v % (s + 2) == 0, hom-ref elsewhere: every pair is broken at places of its own, so the pairs'
+    segment counts differ and the table is right only if every pair's segments lie at its own offset, in order"""
+    v = np.arange(n)[:, None]
+    D = np.where(v % (np.arange(S)[None, :] + 2) == 0, 2, 0).astype(np.int64)
+    return _case("samples_%d_every_pair_its_own_count" % S, D, S, cuts=[[], [64], [50, 50, 100]], seam=lambda c: True)
+
+
+def seam_cases():
+    out = []
+    E = lambda *t: [tuple(x) for x in t]
+    C = CHUNK_RECORDS
+
+    def add(seams, *a, **kw):
+        c = _two(*a, **kw)
+        c["seams"] = set(seams)
+        out.append(c)
+    # ---- the second trip through the chunk loop: records 2,047 / 2,048 and 4,095 / 4,096
+    add({"step_2049", "disc_at_2047"}, "disc_last_of_the_first_trip", "=" * (C - 1) + "x" + "=", cuts=[[], [C], [C - 1]],
+        expect=E((0, _p(0), _p(C - 2), C - 1, C - 1), (0, _p(C), _p(C), 1, 1)), seam=lambda c: _kind(c, C - 1) == "DISC" and len(c["D"]) == C + 1)
+    add({"step_4096", "disc_at_2048"}, "disc_first_of_the_second_trip", "=" * C + "x" + "=" * (C - 1), cuts=[[], [C], [C + 1]],
+        expect=E((0, _p(0), _p(C - 1), C, C), (0, _p(C + 1), _p(2 * C - 1), C - 1, C - 1)), seam=lambda c: _kind(c, C) == "DISC" and len(c["D"]) == 2 * C)
+    add({"step_4097", "open_across_2047_2048", "open_across_4095_4096"}, "runs_open_across_both_trips", "." * (C - 8) + "h" * 16 + "." * (C - 16) + "=" * 9,
+        cuts=[[], [C], [C, 2 * C], [2 * C]], expect=E((0, _p(C - 8), _p(2 * C), 25, 9)),                      # (NEUT records break nothing: one run, open across both seams)
+        seam=lambda c: all(_kind(c, v) == "CONC" for v in (C - 1, C, 2 * C - 1, 2 * C)) and len(c["D"]) == 2 * C + 1)
+    add({"step_2049", "opens_2047_closes_2048"}, "opens_last_of_the_first_trip_closes_first_of_the_second", "." * (C - 1) + "=" + "x", cuts=[[], [C]],
+        expect=E((0, _p(C - 1), _p(C - 1), 1, 1)), seam=lambda c: _kind(c, C - 2) == "NEUT" and _kind(c, C - 1) == "CONC" and _kind(c, C) == "DISC")
+    add({"step_2048"}, "one_full_trip", "x" + "=" * (C - 1), cuts=[[], [C]], expect=E((0, _p(1), _p(C - 1), C - 1, C - 1)), seam=lambda c: len(c["D"]) == C)
+    add({"step_4096", "second_trip_neut_only"}, "second_trip_of_neut_records_only", "=" * C + ":" * C, cuts=[[], [C]], expect=E((0, _p(0), _p(C - 1), C, C)),
+        seam=lambda c: all(_kind(c, v) == "NEUT" for v in range(C, 2 * C)))
+    # ---- a chromosome change exactly at record 2,048 and at 4,096: the start words staged beside the chunk
+    for sym, kind in (("=", "CONC"), ("x", "DISC"), (".", "NEUT")):
+        open_at = 0 if kind == "CONC" else 1
+        segs = [(0, _p(0), _p(C - 1), C, C), (1, _p(C + open_at), _p(2 * C - 1), C - open_at, C - open_at)] + ([(2, _p(2 * C), _p(2 * C), 1, 1)] if kind == "CONC" else [])
+        add({"step_4097", "chrom_at_2048_" + kind, "chrom_at_4096_" + kind}, "chrom_change_first_of_each_later_trip_on_" + kind.lower(),
+            "=" * C + sym + "=" * (C - 1) + sym, chrom=[0] * C + [1] * C + [2], cuts=[[], [C], [C, 2 * C]], expect=E(*segs),
+            seam=lambda c, kind=kind: _kind(c, C) == kind and _kind(c, 2 * C) == kind and c["chrom"][C - 1] != c["chrom"][C] and c["chrom"][2 * C - 1] != c["chrom"][2 * C])
+    # the start word of the second trip is not the first trip's: a change at record 2,048 + 69 alone, and -- the decoy -- one at record 69 alone
+    k = C + 69
+    add({"start_word_of_the_second_trip"}, "chrom_change_inside_the_second_trip_alone", "=" * (C + 200), chrom=[0] * k + [1] * (C + 200 - k), cuts=[[], [C]],
+        expect=E((0, _p(0), _p(k - 1), k, k), (1, _p(k), _p(C + 199), C + 200 - k, C + 200 - k)), seam=lambda c: int(np.flatnonzero(np.diff(c["chrom"]))[0]) + 1 == C + 69)
+    add({"start_word_decoy"}, "chrom_change_inside_the_first_trip_alone", "=" * (C + 200), chrom=[0] * 69 + [1] * (C + 131), cuts=[[], [C]],
+        expect=E((0, _p(0), _p(68), 69, 69), (1, _p(69), _p(C + 199), C + 131, C + 131)), seam=lambda c: int(np.flatnonzero(np.diff(c["chrom"]))[0]) + 1 == 69)
+    # ---- ibd_starts_kernel: a word a wave, four words a workgroup; record 0 of a step is compared with *last
+    changes = [63, 64, 255, 256, 512]
+    chrom = np.searchsorted(changes, np.arange(600), side="right")
+    edges = [0] + changes + [600]
+    add({"starts_63_64", "starts_255_256", "starts_256k", "change_after_an_empty_step", "last_over_two_empty_steps"}, "chrom_changes_at_word_and_workgroup_seams", "=" * 600,
+        chrom=chrom, cuts=[[], [64], [256], [256, 256], [256, 256, 256, 512], [63, 255]],
+        expect=E(*[(i, _p(lo), _p(hi - 1), hi - lo, hi - lo) for i, (lo, hi) in enumerate(zip(edges[:-1], edges[1:]))]),
+        seam=lambda c: [int(x) + 1 for x in np.flatnonzero(np.diff(c["chrom"]))] == changes and [256, 256] in c["cuts"] and [256, 256, 256, 512] in c["cuts"])
+    # ---- break words
+    add({"breaks_0_63_neighbours"}, "breaks_at_bit_0_and_at_two_neighbouring_bits_62_63", "x" + "=" * 61 + "xX" + "=" * 64, cuts=[[], [63], [64]],
+        expect=E((0, _p(1), _p(61), 61, 61), (0, _p(64), _p(127), 64, 64)), seam=lambda c: [_kind(c, v) for v in (0, 62, 63)] == ["DISC"] * 3)
+    add({"start_and_disc"}, "a_record_that_starts_a_chromosome_and_is_disc", "=" * 64 + "x" + "=" * 5, chrom=[0] * 64 + [1] * 6, cuts=[[], [64]],
+        expect=E((0, _p(0), _p(63), 64, 64), (1, _p(65), _p(69), 5, 5)), seam=lambda c: _kind(c, 64) == "DISC" and c["chrom"][63] != c["chrom"][64])
+    add({"word_of_disc"}, "a_whole_word_of_disc_then_a_whole_word_of_conc", "h" * 64 + "x" * 64 + "=" * 64, cuts=[[], [64], [128]],
+        expect=E((0, _p(0), _p(63), 64, 0), (0, _p(128), _p(191), 64, 64)), seam=lambda c: all(_kind(c, v) == "DISC" for v in range(64, 128)))
+    # ---- the tiles of pairs: exactly one pair has segments, every other sample is missing throughout
+    pattern = "==x=h=X=="
+    for S in (15, 16, 17, 31, 32, 33):
+        for a, b in sorted({(0, 15), (15, 16), (0, 16), (16, 17), (S - 2, S - 1)}):
+            if b >= S:
+                continue
+            c = _case("samples_%d_only_pair_%d_%d" % (S, a, b), _only_pair(S, a, b, pattern), S, cuts=[[], [3]], seam=lambda c: True)
+            c["seams"], c["only"] = {"samples_%d" % S}, (a, b)
+            if (a, b) in ((0, 15), (15, 16), (0, 16), (16, 17)):
+                c["seams"].add("only_pair_%d_%d" % (a, b))
+            if (a, b) == (S - 2, S - 1):
+                c["seams"].add("only_pair_last_pair")
+            out.append(c)
+        c = _counts_case(S)
+        c["seams"] = {"samples_%d" % S, "all_pairs_%d" % S}
+        out.append(c)
+    assert len({c["name"] for c in out}) == len(out)
+    return out
+
+
+IBD_SEAMS = ({"step_2048", "step_2049", "step_4096", "step_4097", "disc_at_2047", "disc_at_2048", "open_across_2047_2048", "open_across_4095_4096", "opens_2047_closes_2048",
+              "second_trip_neut_only", "start_word_of_the_second_trip", "start_word_decoy", "starts_63_64", "starts_255_256", "starts_256k", "change_after_an_empty_step",
+              "last_over_two_empty_steps", "breaks_0_63_neighbours", "start_and_disc", "word_of_disc", "only_pair_0_15", "only_pair_15_16", "only_pair_0_16", "only_pair_16_17",
+              "only_pair_last_pair"} | {"chrom_at_%d_%s" % (v, k) for v in (2048, 4096) for k in ("CONC", "DISC", "NEUT")} |
+             {"samples_%d" % s for s in (15, 16, 17, 31, 32, 33)} | {"all_pairs_%d" % s for s in (15, 16, 17, 31, 32, 33)})
+
+# the transpose: one cell, and the decoy the same bit one record and one sample on, in the next dosage row: two bits come out, nothing else
+TR_SAMPLES, TR_N = (0, 1, 62, 63, 64, 127, 129), 1100
+TR_RECORDS = (0, 63, 64, 255, 256, 1023, 1024, TR_N - 1)
+
+
+def transpose_case(sample, record, decoy=True):
+    """-> (words [3, 3, 1100], planes [192, 3, 18]): the input and what must come out, written down bit by bit"""
+    words, planes = np.zeros((3, 3, TR_N), dtype=np.uint64), np.zeros((192, 3, (TR_N + 63) // 64), dtype=np.uint64)
+    d = (sample + record) % 3
+    cells = [(sample, d, record)] + ([((sample + 1) % 130, (d + 1) % 3, (record + 1) % TR_N)] if decoy else [])
+    for s, dd, v in cells:
+        words[s // 64, dd, v] |= np.uint64(1) << np.uint64(s % 64)
+        planes[s, dd, v // 64] |= np.uint64(1) << np.uint64(v % 64)
+    return words, planes

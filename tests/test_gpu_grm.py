@@ -220,7 +220,9 @@ def test_haploid_wide(ctx):
 
 
 def test_the_fold_case(ctx):
-    """140,000 identical records whose h h terms pass 2^31 from 133,145 on: expected is 140,000 times the one-record table"""
+    """140,000 identical records whose h h terms pass 2^31 from 133,145 on: expected is 140,000 times the one-record table.  This is the
+    64-bit fold across 16 runs of 8,768 records that add with atomics (508 samples: 136 blocks, far below GRM_FILL), not a full i32 run:
+    no accumulator here goes past 16,129 x 8,768 < 2^28.  A run of GRM_MAX_RUN records without atomics is in tests/test_gpu_site_word_edges.py"""
     D, records = grm_cases.fold_case()
     n = grm_cases.FOLD_SAMPLES
     S1, N1, _, e1 = M.grm_sums(D, n)

@@ -138,3 +138,82 @@ def test_text_value_rounds_half_away_from_zero():
 def test_maf_text():
     assert [M.parse_maf(t) for t in ("0.01", "0", "0.5", ".25", "0.000001", "0.123456", "0.")] == [10000, 0, 500000, 250000, 1, 123456, 0]
     assert [M.parse_maf(t) for t in ("0.5000001", "0.51", "1", "-0.1", "1e-2", "", ".", "0.1234567", "0,1", "00.1")] == [None] * 10
+
+
+# ---- the plan cases: the Gram kernel without atomics and a full run of the i32 accumulators -------------------------------------------
+
+PLAN_CASES = grm_cases.plan_cases()
+
+
+@pytest.mark.parametrize("case", PLAN_CASES, ids=[c["name"] for c in PLAN_CASES])
+def test_a_plan_case_hits_the_plan_it_states(case):
+    from test_grm_plan_cpu import step_plan
+    assert step_plan(case["n_samples"], case["records"]) == case["plan"], "under the default cap of 384 MiB"
+    assert sum(p[0] for p in case["plan"]) == case["records"] == case["count"] + (0 if case["front"] is None else len(case["front"]))
+    atomics = [runs > 1 for _, _, runs in case["plan"]]
+    assert all(atomics) if "atomics" in case["name"] and "no_atomics" not in case["name"] else not any(atomics)
+    w = M.weights_table(case["record"].reshape(1, -1))
+    assert w[0, 3] == 1, "the repeated record enters"
+    if case["front"] is not None:
+        F = case["front"]
+        assert len(F) == grm_cases.FRONT_RECORDS and len({F[:, s].tobytes() for s in range(case["n_samples"])}) == case["n_samples"], "no two samples alike"
+        assert M.weights_table(F)[:, 3].sum() >= 250
+
+
+def test_the_plan_cases_name_both_forms_and_the_flip():
+    plans = {(c["n_samples"], c["records"], c["front"] is not None): c["plan"] for c in PLAN_CASES}
+    assert len(plans) == len(PLAN_CASES) == 6 and len({c["name"] for c in PLAN_CASES}) == 6
+    for front in (False, True):
+        assert plans[(2017, 1025, front)] == [(1025, 1088, 1)], "17 MFMA steps in one run: one more than any run of the older tests"
+        assert plans[(2017, 65537, front)] == [(65536, 65536, 1), (1, 64, 1)], "1,024 steps, GRM_MAX_RUN exactly, then a piece of one step"
+        assert plans[(2016, 65537, front)] == [(65537, 32832, 2)], "63 blocks: 2,016 on and above the diagonal, below GRM_FILL"
+
+
+def test_the_bound_record_comes_closest_to_the_i32_bound():
+    n = grm_cases.BOUND_SAMPLES
+    row = grm_cases.bound_record(n)
+    assert (row == 2).sum() == 4 and (row == 0).sum() == n - 4 and [int(s) for s in np.nonzero(row)[0]] == [0, 31, 32, 2016]
+    w = M.weights_table(row.reshape(1, -1))
+    assert tuple(int(x) for x in w[0]) == grm_cases.BOUND_Q + (1,) == (-65, 16211, 32487, 1)
+    h, l = M.digits(w[0, :3].astype(np.int64))
+    assert int(h[2]) == grm_cases.BOUND_H == 127 and int(l[2]) == -25
+    assert 127 * 127 == 16129 and 16129 * 65536 == 1_057_030_144 < 2 ** 30
+    # no entering record has a larger |h|: |q| <= MG_GRM_MAX_Q bounds it (test_digit_extremes_are_met), and among the records of 2,017
+    # called samples with hom-alt and hom-ref cells alone, q2 falls as the hom-alt count grows: three or fewer do not enter
+    q, enters = M.weights_from_counts(n - np.arange(1, 40), 0, np.arange(1, 40))
+    assert list(enters[:4]) == [False, False, False, True] and (np.diff(q[:, 2]) < 0).all()
+    hq, _ = M.digits(np.arange(-M.MAX_Q, M.MAX_Q + 1))
+    assert np.abs(hq).max() == 127
+    # the pairs of two hom-alt samples carry it, in the table as in the accumulators
+    S1, N1, _, _ = M.grm_sums(row, n)
+    a, b = M.pair_index(n)
+    both = (row[a] == 2) & (row[b] == 2)
+    assert both.sum() == 10 and (S1[both] == 32487 ** 2).all() and (N1 == 1).all()
+    # the same record one sample fewer (the flip case) enters as well
+    assert M.weights_table(grm_cases.bound_record(n - 1).reshape(1, -1))[0, 3] == 1
+
+
+def test_a_plan_case_expects_the_models_table():
+    """the one-record table times the count, on top of the front's: held against the model over the whole input with a count of 5; the
+    products in doubles are the model's integer products, over a narrow cohort as a whole and over the rows of both ends of the wide one"""
+    D70 = grm_cases.random_dosage(200, 70, seed=12)
+    for got, want in zip(grm_cases.sums_in_doubles(D70, 70), M.grm_sums(D70, 70)):
+        assert np.array_equal(got, want)
+    case = next(c for c in PLAN_CASES if c["name"] == "no_atomics_17_steps_behind_random_records")
+    n = case["n_samples"]
+    case = dict(case, count=5, records=len(case["front"]) + 5)
+    S, N, seen, entered = grm_cases.plan_case_expected(case)
+    words = grm_cases.plan_case_words(case)
+    assert words.shape == ((n + 63) // 64, 3, 305) and seen == 305
+    D = np.concatenate([case["front"], np.repeat(case["record"].reshape(1, -1), case["count"], axis=0)])
+    assert np.array_equal(words, M.words_from_dosage(D, n))
+    X, Cc, entered2 = M.cell_weights(D)
+    assert entered == entered2
+    full, full_n = np.zeros((n, n), dtype=np.int64), np.zeros((n, n), dtype=np.int64)
+    a, b = M.pair_index(n)
+    full[a, b], full_n[a, b] = S, N.astype(np.int64)
+    rows = list(range(0, 34)) + list(range(n - 3, n))
+    for r in rows:                                                                 # (row r of the upper triangle, in the model's integers)
+        assert np.array_equal((X[:, r:r + 1] * X[:, r:]).sum(axis=0), full[r, r:]) and np.array_equal((Cc[:, r:r + 1] * Cc[:, r:]).sum(axis=0), full_n[r, r:])
+    off = full[0:32, 32:64]
+    assert (off != off.T).sum() > 900, "a swapped row and column would show"

@@ -78,3 +78,58 @@ def test_a_random_case_emits_and_filters(n_samples, n_vars, min_records, seed):
     if n_samples <= 17:                                                 # the cuts, where the model is quick
         for cuts in c["cuts"][1:]:
             assert np.array_equal(_whole(c, cuts), whole)
+
+
+# ---- the seam cases ---------------------------------------------------------------------------------------------------------------------
+
+SEAMS = ibd_cases.seam_cases()
+
+
+@pytest.mark.parametrize("case", SEAMS, ids=[c["name"] for c in SEAMS])
+def test_a_seam_case_hits_its_seam_and_does_not_depend_on_the_cuts(case):
+    test_a_directed_case_hits_its_seam_and_does_not_depend_on_the_cuts(case)
+    whole = _whole(case)
+    if "only" in case:                                                   # one pair has segments; every other pair none, in the model
+        assert len(whole) == 3 and {(int(s["a"]), int(s["b"])) for s in whole} == {case["only"]}
+        assert (case["D"][:, [s for s in range(case["n_samples"]) if s not in case["only"]]] == -1).all()
+    if any(s.startswith("all_pairs_") for s in case["seams"]):
+        S = case["n_samples"]
+        per_pair = np.bincount(whole["a"].astype(np.int64) * S + whole["b"], minlength=S * S).reshape(S, S)[np.triu_indices(S, 1)]
+        assert per_pair.min() >= 1 and len(set(per_pair.tolist())) >= 8, "every pair has segments, and the counts differ"
+
+
+def test_the_seam_cases_claim_every_seam():
+    assert set().union(*(c["seams"] for c in SEAMS)) == ibd_cases.IBD_SEAMS
+    assert ibd_cases.CHUNK_RECORDS == 2048 and {len(c["D"]) for c in SEAMS if any(s.startswith("step_") for s in c["seams"])} == {2048, 2049, 4096, 4097}
+    for S in (15, 16, 17, 31, 32, 33):
+        pairs = {c["only"] for c in SEAMS if "only" in c and c["n_samples"] == S}
+        assert pairs == {p for p in ((0, 15), (15, 16), (0, 16), (16, 17)) if p[1] < S} | {(S - 2, S - 1)}
+    # a cut at the seam is among every chunk case's cuts, and so is the uncut walk: the second trip through the chunk loop
+    for c in SEAMS:
+        if any(s.startswith("step_") for s in c["seams"]):
+            assert [] in c["cuts"] and any(ibd_cases.CHUNK_RECORDS in cut for cut in c["cuts"])
+
+
+def test_the_start_word_decoy_is_the_other_case_one_trip_off():
+    """a change at record 69 alone and at record 2,048 + 69 alone: bit 5 of start word 1 and of start word 33 -- what a walk that stages the
+    first trip's start words again would confuse"""
+    by = {c["name"]: c for c in SEAMS}
+    a, b = by["chrom_change_inside_the_first_trip_alone"], by["chrom_change_inside_the_second_trip_alone"]
+    ca, cb = (int(np.flatnonzero(np.diff(c["chrom"]))[0]) + 1 for c in (a, b))
+    assert (ca, cb) == (69, 2048 + 69) and (ca >> 6) + ibd_cases.PAIR_CHUNK == cb >> 6 and ca & 63 == cb & 63 == 5
+    assert len(_whole(a)) == len(_whole(b)) == 2 and _kind_all(a, 2048 + 69) and _kind_all(b, 69)
+
+
+def _kind_all(c, v):
+    return ibd_cases._kind(c, v) == "CONC" and c["chrom"][v] == c["chrom"][v - 1]
+
+
+@pytest.mark.parametrize("sample", ibd_cases.TR_SAMPLES)
+def test_a_transpose_case_is_the_bit_transpose(sample):
+    for record in ibd_cases.TR_RECORDS:
+        words, planes = ibd_cases.transpose_case(sample, record)
+        assert np.array_equal(planes_from_words(words), planes)
+        assert sum(bin(int(x)).count("1") for x in planes.reshape(-1)) == 2
+        alone = ibd_cases.transpose_case(sample, record, decoy=False)[1]
+        assert sum(bin(int(x)).count("1") for x in alone.reshape(-1)) == 1 and int(alone[sample, (sample + record) % 3, record >> 6]) == 1 << (record & 63)
+    assert set(ibd_cases.TR_RECORDS) == {0, 63, 64, 255, 256, 1023, 1024, ibd_cases.TR_N - 1} and ibd_cases.IBD_TR_WORDS * 64 == 1024
