@@ -64,9 +64,9 @@ bin/ticket_gate_bench: tools/ticket_gate_bench.hip
 # the host side of --cohort-priors (option values, --priors-out; --prior-groups' scratch streams), of the cohort's outputs (--site-stats, --ld, --ibd and --grm in programs of their own) and of the panel batches and their text under
 # AddressSanitizer and UBSan: stand-alone programs, run on the CPU.  The last one is a batch's device calls and the pipeline around them
 # (host/call_worker.hpp) against an ABI of its own, without libmalva_hip; it runs a second time under ThreadSanitizer.  Last, the command line
-# (host/options.hpp) against the records of the parser it replaced
+# (host/options.hpp) against the records of the parser it replaced, and the host half of `pca` (host/pca.hpp, csrc/pca_plan.h)
 sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check bin/cohort_out_host_check bin/site_table_host_check bin/ld_out_host_check bin/ibd_out_host_check bin/grm_out_host_check \
-               bin/call_batch_host_check bin/call_worker_host_check bin/call_worker_host_check_tsan bin/options_host_check
+               bin/call_batch_host_check bin/call_worker_host_check bin/call_worker_host_check_tsan bin/options_host_check bin/pca_host_check
 	bin/cohort_priors_host_check bin
 	bin/cohort_priors_groups_host_check bin
 	bin/cohort_out_host_check bin
@@ -78,6 +78,7 @@ sanitize-host: bin/cohort_priors_host_check bin/cohort_priors_groups_host_check 
 	bin/call_worker_host_check bin
 	bin/call_worker_host_check_tsan bin
 	bin/options_host_check
+	bin/pca_host_check bin
 bin/cohort_priors_host_check: tools/cohort_priors_host_check.cpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
@@ -118,6 +119,10 @@ bin/call_worker_host_check_tsan: tools/call_worker_host_check.cpp tools/host_che
 bin/options_host_check: tools/options_host_check.cpp malva_amd/host/options.hpp malva_amd/host/usage.hpp malva_amd/host/cohort_priors.hpp malva_amd/host/part_file.hpp include/malva_hip.h
 	@mkdir -p bin
 	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $<
+# the readers, writers and parser of `malva-geno pca`, the block geometry and the small Jacobi solver
+bin/pca_host_check: tools/pca_host_check.cpp malva_amd/host/pca.hpp malva_amd/csrc/pca_plan.h malva_amd/host/cohort_out.hpp malva_amd/host/part_file.hpp malva_amd/host/bcf_out.hpp include/malva_hip.h
+	@mkdir -p bin
+	$(CXX) -std=c++17 -O1 -g -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Imalva_amd/host -o $@ $< -lz
 
 clean:
 	rm -rf malva_amd/lib bin oracle/libmalva_oracle.so oracle/_ref

@@ -838,6 +838,56 @@ int mg_grm_read(mg_ctx *ctx, int64_t *sum_out, uint64_t *n_out, uint64_t *record
 int mg_grm_end(mg_ctx *ctx);
 int mg_grm_stats(mg_ctx *ctx, float *ms_out);
 
+/* ---- principal components: the leading eigenpairs of a symmetric matrix ---------------------
+ * What GCTA and PLINK --pca make of a GRM, solved on the device.  There is no reference call to cite: the reference genotypes one
+ * individual per run.  G is a real symmetric n x n matrix, resident in double.  The result is K eigenpairs (theta_i, v_i), i = 0 .. K - 1.
+ *   Order.  The K ALGEBRAICALLY LARGEST eigenvalues, descending.
+ *   Vectors.  Orthonormal.  Each vector's sign is fixed so that its component of largest magnitude is positive; among equal magnitudes
+ *   the lowest index decides.
+ *   Residual.  Per pair r_i = ||G v_i - theta_i v_i||_2 / s, s the largest |theta| of the final Rayleigh-Ritz block (all m values, not
+ *   only the K returned), or 1 when that is 0.  s is written out.
+ *   Convergence.  A pair is converged when r_i <= tol.  The solve stops when the first K pairs are converged, or at max_iters products;
+ *   it always returns K pairs, and an unconverged result is MG_OK.
+ *   Determinism.  No floating-point atomics and no reduction whose order depends on scheduling: every split of an n-long sum over waves
+ *   and workgroups is a function of n alone (csrc/pca_plan.h).  Two solves of one matrix give the same bytes; the host form and the device
+ *   form give the same bytes.
+ *   Method.  Blocked subspace iteration with Rayleigh-Ritz on a block of m = min(n, roundup16(max(2 K, K + 16))) columns.  The start
+ *   vectors are a counter hash of (row, column) (pca_hash_value; no library generator).  A step forms Y = G Q (one PRODUCT) and
+ *   orthonormalises Y on the device by Cholesky QR, twice; a column whose pivot collapses is replaced by a fresh hashed vector and made
+ *   orthogonal to the rest by the second pass, so the block keeps its full width on a matrix of any rank.  After every 4th product, and
+ *   after the last one allowed: H = Q^T Y, its m x m eigenproblem (on the host, cyclic Jacobi in double; values algebraically
+ *   descending), Q <- Q S, Y <- Y S, and the residual test on the columns of Y - Q diag(theta).  m == n: nothing to iterate, G itself goes
+ *   through the small solver and 0 products are reported.
+ *   Limit of the method.  It iterates by magnitude: a matrix with more than m - K eigenvalues below -theta_{K-1} cannot converge for pair
+ *   K - 1; that is reported as not converged, not refused.  One large negative eigenvalue takes a block slot and is not among the K.
+ * mg_pca_load_tri_f32: GCTA's .grm.bin layout -- the lower triangle row by row, diagonal included, n (n + 1) / 2 floats, element (i, j),
+ * j <= i, at i (i + 1) / 2 + j -- expanded on the device to the resident symmetric matrix (8 n'^2 bytes, n' = n rounded up to 16: 2.1 GB at
+ * the limit).  mg_pca_load_f64: row-major n x n doubles, of which only a[i][j], j <= i, is read and mirrored: the resident matrix is
+ * symmetric by construction.  A second load discards the first; a matrix (or, in a host form, its input) that does not fit: MG_ERR_NOMEM.
+ * n outside 1..MG_PCA_MAX_N or a NULL pointer: MG_ERR_ARG.  A value that is not finite is found by a device reduction over the load: the
+ * host forms return MG_ERR_ARG with a message and keep no matrix; the _device forms take device pointers and are asynchronous on the
+ * context's stream, so there the first mg_pca_solve* after the load returns it (and the matrix is gone).
+ * mg_pca_solve: k is 1..min(n, MG_PCA_MAX_K), tol finite and > 0, max_iters >= 1, no pointer NULL, else MG_ERR_ARG; without a load
+ * MG_ERR_STATE.  values_out[k], descending; vectors_out[k][n], one row per component; resid_out[k] = r_i; scale_out[1] = s; info_out[3]:
+ * [0] the products G Q performed, [1] how many of the k pairs are converged, [2] m.  Callable repeatedly on one load: the matrix is not
+ * modified.  Nothing outside these arrays is written.  mg_pca_solve_device takes the five outputs as device pointers; both forms wait
+ * (a Rayleigh-Ritz step needs the host) and return with the result complete.
+ * mg_pca_end frees the matrix (legal without a load).  mg_pca_stats (waits): ms_out[4], device milliseconds of the most recent solve --
+ * [0] products, [1] orthonormalisation, [2] Rayleigh-Ritz (projection, block update, residual norms, and the device's wait for the
+ * host's small solver), [3] total; MG_ERR_STATE before any solve. */
+#define MG_PCA_MAX_N 16384
+#define MG_PCA_MAX_K 32
+int mg_pca_load_tri_f32(mg_ctx *ctx, uint32_t n, const float *tri);
+int mg_pca_load_f64(mg_ctx *ctx, uint32_t n, const double *full);
+int mg_pca_load_tri_f32_device(mg_ctx *ctx, uint32_t n, const void *d_tri);
+int mg_pca_load_f64_device(mg_ctx *ctx, uint32_t n, const void *d_full);
+int mg_pca_solve(mg_ctx *ctx, uint32_t k, double tol, uint32_t max_iters, double *values_out, double *vectors_out, double *resid_out, double *scale_out,
+                 uint32_t *info_out);
+int mg_pca_solve_device(mg_ctx *ctx, uint32_t k, double tol, uint32_t max_iters, void *d_values_out, void *d_vectors_out, void *d_resid_out, void *d_scale_out,
+                        void *d_info_out);
+int mg_pca_end(mg_ctx *ctx);
+int mg_pca_stats(mg_ctx *ctx, float *ms_out);
+
 /* ---- allele priors re-estimated from the cohort -------------------------------------
  * mg_genotype_cohort: the batch's allele frequencies are re-estimated from all of its planes (a few EM steps from the panel's
  * priors, anchored to them), then every cell is genotyped under the result.  The reference genotypes one individual and has no

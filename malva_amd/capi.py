@@ -24,6 +24,7 @@ COMM_ID_BYTES = 128
 LD_MAX_GROUPS, LD_MAX_WINDOW = 256, 1024   # MG_LD_MAX_GROUPS, MG_LD_MAX_WINDOW
 IBD_MAX_SAMPLES = 16384     # MG_IBD_MAX_SAMPLES
 GRM_MAX_SAMPLES, GRM_SHIFT, GRM_MAX_Q = 16384, 10, 32639   # MG_GRM_MAX_SAMPLES, MG_GRM_SHIFT, MG_GRM_MAX_Q
+PCA_MAX_N, PCA_MAX_K = 16384, 32   # MG_PCA_MAX_N, MG_PCA_MAX_K
 IBD_SEG = np.dtype([(f, np.uint32) for f in ("a", "b", "chrom", "start_pos", "end_pos", "n", "ibs2", "zero")])   # mg_ibd_seg, 32 bytes
 LD_PAIR = np.dtype([("i", np.uint32), ("j", np.uint32), ("n", np.uint32), ("sign", np.int32), ("r2", np.float64)])   # mg_ld_pair, 24 bytes
 SAMPLE_SLOTS = 32           # MG_SAMPLE_SLOTS: the counters per plane of mg_sample_counts (MG_SS_*)
@@ -157,6 +158,14 @@ def lib():
         "mg_grm_read": [vp, vp, vp, vp],
         "mg_grm_end": [vp],
         "mg_grm_stats": [vp, vp],
+        "mg_pca_load_tri_f32": [vp, u32, vp],
+        "mg_pca_load_f64": [vp, u32, vp],
+        "mg_pca_load_tri_f32_device": [vp, u32, vp],
+        "mg_pca_load_f64_device": [vp, u32, vp],
+        "mg_pca_solve": [vp, u32, C.c_double, u32, vp, vp, vp, vp, vp],
+        "mg_pca_solve_device": [vp, u32, C.c_double, u32, vp, vp, vp, vp, vp],
+        "mg_pca_end": [vp],
+        "mg_pca_stats": [vp, vp],
         "mg_genotype_cohort": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_genotype_cohort_device": [vp, sz, u32, vp, vp, vp, fl, it, it, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp],
         "mg_cohort_prior_stats": [vp, vp],
@@ -237,7 +246,9 @@ EXPORTED = ["mg_create", "mg_destroy", "mg_last_error", "mg_set_stream", "mg_syn
             "mg_site_geno_counts", "mg_site_geno_counts_device", "mg_hwe_exact", "mg_hwe_exact_device", "mg_hwe_stats",
             "mg_pack_site_dosage", "mg_pack_site_dosage_device", "mg_ld_window", "mg_ld_window_device", "mg_ld_stats",
             "mg_sites_to_planes", "mg_sites_to_planes_device", "mg_ibd_begin", "mg_ibd_step", "mg_ibd_step_device", "mg_ibd_end", "mg_ibd_stats",
-            "mg_grm_weights", "mg_grm_weights_device", "mg_grm_begin", "mg_grm_step", "mg_grm_step_device", "mg_grm_read", "mg_grm_end", "mg_grm_stats", "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
+            "mg_grm_weights", "mg_grm_weights_device", "mg_grm_begin", "mg_grm_step", "mg_grm_step_device", "mg_grm_read", "mg_grm_end", "mg_grm_stats",
+            "mg_pca_load_tri_f32", "mg_pca_load_f64", "mg_pca_load_tri_f32_device", "mg_pca_load_f64_device", "mg_pca_solve", "mg_pca_solve_device", "mg_pca_end", "mg_pca_stats",
+            "mg_genotype_cohort", "mg_genotype_cohort_device", "mg_cohort_prior_stats", "mg_estimate_priors", "mg_estimate_priors_device", "mg_estimate_priors_stats", "mg_encode_calls_bcf", "mg_encode_calls_bcf_device", "mg_bcf_stats",
             "mg_phred_likelihoods", "mg_phred_likelihoods_device", "mg_pl_stats",
             "mg_comm_unique_id", "mg_comm_init", "mg_comm_init_all", "mg_comm_destroy", "mg_comm_info", "mg_counters_allreduce",
             "mg_counters_allreduce_all", "mg_counters_allreduce_begin", "mg_counters_allreduce_end", "mg_exchange_stats", "mg_decode_gt_text", "mg_decode_gt_entries", "mg_cut_blocks", "mg_cut_blocks_device", "mg_cover_blocks_device", "mg_index_blocks_device", "mg_genotype_device",
@@ -1182,6 +1193,47 @@ class Context:
         ms = (C.c_float * 3)()
         self._ck(self._L.mg_grm_stats(self.h, ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # principal components of a resident symmetric matrix
+    def pca_load_tri(self, tri, n):
+        """tri: float32 [n (n + 1) / 2], the lower triangle row by row as in GCTA's .grm.bin (mg_pca_load_tri_f32); a second load discards the first"""
+        T = np.ascontiguousarray(tri, dtype=np.float32).reshape(-1)
+        assert T.size == n * (n + 1) // 2
+        self._ck(self._L.mg_pca_load_tri_f32(self.h, int(n), _p(T)))
+
+    def pca_load(self, full):
+        """full: float64 [n, n]; only its lower triangle is read and mirrored (mg_pca_load_f64)"""
+        A = np.ascontiguousarray(full, dtype=np.float64)
+        assert A.ndim == 2 and A.shape[0] == A.shape[1]
+        self._ck(self._L.mg_pca_load_f64(self.h, A.shape[0], _p(A)))
+
+    def pca_load_tri_device(self, n, d_tri):
+        """the same from a device pointer, asynchronous on the context's stream; a non-finite value is reported by the first solve"""
+        self._ck(self._L.mg_pca_load_tri_f32_device(self.h, int(n), C.c_void_p(d_tri)))
+
+    def pca_load_device(self, n, d_full):
+        self._ck(self._L.mg_pca_load_f64_device(self.h, int(n), C.c_void_p(d_full)))
+
+    def pca_solve(self, n, k, tol=1e-10, max_iters=2000):
+        """-> (values [k], vectors [k, n], resid [k], scale, (products, converged, m)) of the loaded n x n matrix (mg_pca_solve)"""
+        values, vectors, resid = np.zeros(k, dtype=np.float64), np.zeros((k, n), dtype=np.float64), np.zeros(k, dtype=np.float64)
+        scale, info = np.zeros(1, dtype=np.float64), np.zeros(3, dtype=np.uint32)
+        self._ck(self._L.mg_pca_solve(self.h, int(k), float(tol), int(max_iters), _p(values), _p(vectors), _p(resid), _p(scale), _p(info)))
+        return values, vectors, resid, float(scale[0]), (int(info[0]), int(info[1]), int(info[2]))
+
+    def pca_solve_device(self, k, tol, max_iters, d_values, d_vectors, d_resid, d_scale, d_info):
+        """the same into device buffers: float64 [k], [k, n], [k], [1] and uint32 [3]"""
+        self._ck(self._L.mg_pca_solve_device(self.h, int(k), float(tol), int(max_iters), C.c_void_p(d_values), C.c_void_p(d_vectors), C.c_void_p(d_resid),
+                                             C.c_void_p(d_scale), C.c_void_p(d_info)))
+
+    def pca_end(self):
+        self._ck(self._L.mg_pca_end(self.h))
+
+    def pca_stats(self):
+        """-> device ms of the most recent solve: products, orthonormalisation, Rayleigh-Ritz, total"""
+        ms = (C.c_float * 4)()
+        self._ck(self._L.mg_pca_stats(self.h, ms))
+        return tuple(float(x) for x in ms)
 
     # allele priors re-estimated from the planes of a batch, and the cells genotyped under them
     def genotype_cohort(self, cov, freq, var_allele_off, error_rate, max_cov, haploid, iters=5, weight=1.0, want_probs=False):

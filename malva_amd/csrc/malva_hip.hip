@@ -21,6 +21,7 @@
 #include "geno_dev.h"
 #include "grm_plan.h"
 #include "malva_hip.h"
+#include "pca_plan.h"
 
 using namespace mg;
 
@@ -51,6 +52,7 @@ constexpr int GATE_RESIDENT_MIN_BITS = 8; // a sized gate keeps at least this ma
 #include "ld_kernels.h"
 #include "ibd_kernels.h"
 #include "grm_kernels.h"
+#include "pca_kernels.h"
 #include "cohort_prior_kernels.h"
 #include "bcf_kernels.h"
 #include "pl_kernels.h"
@@ -205,6 +207,18 @@ struct mg_ctx {
     float grm_ms[3] = {0.f, 0.f, 0.f};
     bool grm_timed = false;
     int grm_scratch_mb = GRM_SCRATCH_MB; // the cap on a piece's byte images (tests: smaller, so that a step takes several pieces)
+    // mg_pca_load* .. mg_pca_end: the resident matrix ([np][np] doubles, np = pca_np(n), and behind them the "a value is not finite" flag,
+    // a u32), whether the flag has been read since the load, the blocks and small tables of a solve (pca_work), the host forms' input and
+    // output (pca_io).  pca_ev: the events of a solve between two of its waits, pca_ev_phase[i] the phase the interval ending at event i
+    // belongs to; pca_ms: products, orthonormalisation, Rayleigh-Ritz, total of the most recent solve.
+    void *pca_g = nullptr;
+    u32 pca_n = 0;
+    bool pca_checked = false, pca_timed = false;
+    Scratch pca_work, pca_io[2];
+    std::vector<hipEvent_t> pca_ev;
+    std::vector<int> pca_ev_phase;
+    size_t pca_ev_used = 0;
+    float pca_ms[4] = {0.f, 0.f, 0.f, 0.f};
     Scratch s_ld[2]; // mg_ld_window_device, from its length pass to its write pass: the records' pair counts (u32), the meta block (the total)
     u32 *joined = nullptr; // when set: one allocation holding [bf counters | map counters] (mg_counters_view)
     int use_summary = 1;
@@ -880,6 +894,10 @@ MG_EXPORT int mg_destroy(mg_ctx *c)
     for (Scratch &q : c->s_grm) hipFree(q.p);
     for (Scratch &q : c->grm_in) hipFree(q.p);
     hipFree(c->grm_state);
+    hipFree(c->pca_g);
+    hipFree(c->pca_work.p);
+    for (Scratch &q : c->pca_io) hipFree(q.p);
+    for (hipEvent_t e : c->pca_ev) hipEventDestroy(e);
     for (Timer *t : {&c->grm_tm, &c->grm_read_tm})
         for (hipEvent_t e : t->ev)
             if (e) hipEventDestroy(e);
@@ -4316,6 +4334,361 @@ MG_EXPORT int mg_grm_stats(mg_ctx *c, float *ms_out)
     ms_out[0] = c->grm_ms[0] + ms[0];
     ms_out[1] = c->grm_ms[1] + ms[1];
     return timer_read(c, c->grm_read_tm, &ms_out[2]);
+}
+
+// ---- principal components of a resident symmetric matrix (pca_kernels.h, pca_plan.h) -----------------------------------------------------
+namespace {
+enum { PCA_PH_PRODUCT, PCA_PH_ORTH, PCA_PH_RITZ, PCA_PH_OTHER };
+void pca_drop(mg_ctx *c)
+{
+    if (c->pca_g) hipFree(c->pca_g);
+    c->pca_g = nullptr;
+    c->pca_n = 0;
+    c->pca_checked = false;
+}
+u32 *pca_flag(const mg_ctx *c)
+{
+    const u64 np = pca_np(c->pca_n);
+    return (u32 *)((double *)c->pca_g + np * np);
+}
+// an event behind what is on the stream; the interval that ends at it belongs to `phase`
+int pca_tick(mg_ctx *c, int phase)
+{
+    if (c->pca_ev_used == c->pca_ev.size()) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(c, hipEventCreate(&e));
+        c->pca_ev.push_back(e);
+        c->pca_ev_phase.push_back(PCA_PH_OTHER);
+    }
+    HIP_TRY(c, hipEventRecord(c->pca_ev[c->pca_ev_used], c->stream));
+    c->pca_ev_phase[c->pca_ev_used++] = phase;
+    return MG_OK;
+}
+// after a wait: the intervals so far go to their phases and to the total; the last event becomes the first of what follows
+int pca_flush(mg_ctx *c)
+{
+    for (size_t i = 1; i < c->pca_ev_used; ++i) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->pca_ev[i - 1], c->pca_ev[i]));
+        if (c->pca_ev_phase[i] != PCA_PH_OTHER) c->pca_ms[c->pca_ev_phase[i]] += ms;
+        c->pca_ms[3] += ms;
+    }
+    if (c->pca_ev_used > 1) {
+        std::swap(c->pca_ev[0], c->pca_ev[c->pca_ev_used - 1]);
+        c->pca_ev_used = 1;
+    }
+    return MG_OK;
+}
+template <typename T> int pca_load_device(mg_ctx *c, uint32_t n, const void *d_src, int packed)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (a solve of the matrix that goes has ended; a load of it may still run)
+    pca_drop(c);
+    const u64 np = pca_np(n);
+    const size_t bytes = 8 * np * np + 8; // the matrix and the flag
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MG_ERR_NOMEM, "mg_pca_load: the matrix of %u samples (%zu bytes) does not fit", n, bytes);
+    }
+    c->pca_g = p;
+    c->pca_n = n;
+    HIP_TRY(c, hipMemsetAsync(pca_flag(c), 0, 8, c->stream));
+    const PcaExpandArgs<T> a{(const T *)d_src, (double *)p, n, (u32)np, packed, pca_flag(c)};
+    hipLaunchKernelGGL(pca_expand_kernel<T>, dim3((unsigned)((np * np + PCA_TPB - 1) / PCA_TPB)), dim3(PCA_TPB), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return MG_OK;
+}
+// waits; the flag of the load, once per load
+int pca_check_finite(mg_ctx *c, const char *who)
+{
+    if (c->pca_checked) return MG_OK;
+    u32 bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&bad, pca_flag(c), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (bad) {
+        pca_drop(c);
+        return fail(c, MG_ERR_ARG, "%s: the matrix holds a value that is not finite (the load is dropped)", who);
+    }
+    c->pca_checked = true;
+    return MG_OK;
+}
+int check_pca_load(mg_ctx *c, uint32_t n, const void *src)
+{
+    if (n < 1 || n > MG_PCA_MAX_N) return fail(c, MG_ERR_ARG, "mg_pca_load: n is 1..%d", MG_PCA_MAX_N);
+    if (!src) return fail(c, MG_ERR_ARG, "NULL argument");
+    return MG_OK;
+}
+template <typename T> int pca_load_host(mg_ctx *c, uint32_t n, const T *src, int packed)
+{
+    TRY(check_pca_load(c, n, src));
+    const size_t count = packed ? (size_t)n * (n + 1) / 2 : (size_t)n * n;
+    void *d_src = nullptr;
+    if (hipMalloc(&d_src, sizeof(T) * count) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MG_ERR_NOMEM, "mg_pca_load: the input of %u samples (%zu bytes) does not fit", n, sizeof(T) * count);
+    }
+    int rc = MG_OK;
+    if (hipMemcpyAsync(d_src, src, sizeof(T) * count, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(c, MG_ERR_HIP, "mg_pca_load: the upload failed");
+    if (rc == MG_OK) rc = pca_load_device<T>(c, n, d_src, packed);
+    if (rc == MG_OK) rc = pca_check_finite(c, "mg_pca_load");
+    else (void)hipStreamSynchronize(c->stream);
+    hipFree(d_src);
+    return rc;
+}
+
+struct PcaWork { // a solve's device tables, all inside pca_work
+    double *blk[4], *parts, *gparts, *w, *s, *theta, *norm;
+    u32 *flags;
+};
+int pca_launch_gram(mg_ctx *c, const PcaWork &k, const double *a, const double *b, u32 np, u32 m)
+{
+    const u32 blocks = pca_red_blocks(np);
+    hipLaunchKernelGGL(pca_gram_part_kernel, dim3(blocks), dim3(PCA_TPB), 0, c->stream, a, b, np, m, k.gparts);
+    hipLaunchKernelGGL(pca_gram_sum_kernel, dim3((m * m + PCA_TPB - 1) / PCA_TPB), dim3(PCA_TPB), 0, c->stream, (const double *)k.gparts, blocks, m * m, k.w);
+    HIP_TRY(c, hipGetLastError());
+    return MG_OK;
+}
+int pca_launch_update(mg_ctx *c, const double *in, const double *s, u32 np, u32 m, double *out)
+{
+    hipLaunchKernelGGL(pca_update_kernel, dim3((np + 63) / 64), dim3(PCA_TPB), 0, c->stream, in, s, np, m, out);
+    HIP_TRY(c, hipGetLastError());
+    return MG_OK;
+}
+// x -> orthonormal columns in `out`, through `tmp`; collapsed columns of the first pass are replaced by fresh hashed vectors (salt)
+int pca_orthonormalise(mg_ctx *c, const PcaWork &k, const double *x, double *tmp, double *out, u32 n, u32 np, u32 m, u64 salt)
+{
+    TRY(pca_launch_gram(c, k, x, x, np, m));
+    hipLaunchKernelGGL(pca_chol_kernel, dim3(1), dim3(PCA_TPB), 0, c->stream, (const double *)k.w, m, k.s, k.flags);
+    TRY(pca_launch_update(c, x, k.s, np, m, tmp));
+    hipLaunchKernelGGL(pca_fill_kernel, dim3((unsigned)(((u64)np * m + PCA_TPB - 1) / PCA_TPB)), dim3(PCA_TPB), 0, c->stream, tmp, n, np, m, salt, (const u32 *)k.flags);
+    TRY(pca_launch_gram(c, k, tmp, tmp, np, m));
+    hipLaunchKernelGGL(pca_chol_kernel, dim3(1), dim3(PCA_TPB), 0, c->stream, (const double *)k.w, m, k.s, k.flags);
+    TRY(pca_launch_update(c, tmp, k.s, np, m, out));
+    return MG_OK;
+}
+int pca_launch_product(mg_ctx *c, const PcaWork &k, const double *q, double *y, u32 np, u32 m)
+{
+    u32 chunk = 0;
+    const u32 splits = pca_splits(np, &chunk);
+    const PcaProductArgs a{(const double *)c->pca_g, q, splits > 1 ? k.parts : y, np, m, chunk};
+    const dim3 grid(np / PCA_TILE, splits), block(64 * PCA_WAVES);
+    if (m == 32) hipLaunchKernelGGL(pca_product_kernel<2>, grid, block, 0, c->stream, a);
+    else if (m == 48) hipLaunchKernelGGL(pca_product_kernel<3>, grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL(pca_product_kernel<4>, grid, block, 0, c->stream, a);
+    if (splits > 1) {
+        const u64 count = (u64)np * m;
+        hipLaunchKernelGGL(pca_sum_parts_kernel, dim3((unsigned)((count + PCA_TPB - 1) / PCA_TPB)), dim3(PCA_TPB), 0, c->stream, (const double *)k.parts, splits, count, y);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return MG_OK;
+}
+int check_pca_solve(mg_ctx *c, uint32_t k, double tol, uint32_t max_iters, const void *values, const void *vectors, const void *resid, const void *scale, const void *info)
+{
+    if (!values || !vectors || !resid || !scale || !info) return fail(c, MG_ERR_ARG, "NULL argument");
+    if (!std::isfinite(tol) || !(tol > 0.0)) return fail(c, MG_ERR_ARG, "mg_pca_solve: tol is finite and above 0");
+    if (max_iters == 0) return fail(c, MG_ERR_ARG, "mg_pca_solve: max_iters is at least 1");
+    if (!c->pca_g) return fail(c, MG_ERR_STATE, "mg_pca_solve: no mg_pca_load yet");
+    const u32 k_max = c->pca_n < MG_PCA_MAX_K ? c->pca_n : MG_PCA_MAX_K;
+    if (k < 1 || k > k_max) return fail(c, MG_ERR_ARG, "mg_pca_solve: k is 1..%u for this matrix", k_max);
+    return MG_OK;
+}
+// m == n: the matrix itself goes through the small solver; residuals and the sign rule on the host.  vectors: [k][n]
+int pca_solve_small(mg_ctx *c, u32 k, double *values, double *vectors, double *norms, double *scale)
+{
+    const u32 n = c->pca_n, np = pca_np(n);
+    std::vector<double> g((size_t)n * n), a, w(n), v((size_t)n * n);
+    HIP_TRY(c, hipMemcpy2DAsync(g.data(), 8 * (size_t)n, c->pca_g, 8 * (size_t)np, 8 * (size_t)n, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    a = g;
+    if (pca_jacobi(n, a.data(), w.data(), v.data()) < 0) return fail(c, MG_ERR_LIMIT, "mg_pca_solve: the small eigenproblem did not settle in 64 sweeps");
+    double s = 0.0;
+    for (u32 j = 0; j < n; ++j) s = std::fabs(w[j]) > s ? std::fabs(w[j]) : s;
+    *scale = s > 0.0 ? s : 1.0;
+    for (u32 j = 0; j < k; ++j) {
+        double sum = 0.0, best = -1.0;
+        u32 where = 0;
+        for (u32 i = 0; i < n; ++i) {
+            double gv = 0.0;
+            for (u32 t = 0; t < n; ++t) gv += g[(size_t)i * n + t] * v[(size_t)t * n + j];
+            const double d = gv - w[j] * v[(size_t)i * n + j];
+            sum += d * d;
+            if (std::fabs(v[(size_t)i * n + j]) > best) best = std::fabs(v[(size_t)i * n + j]), where = i;
+        }
+        const bool flip = v[(size_t)where * n + j] < 0.0;
+        values[j] = w[j];
+        norms[j] = std::sqrt(sum);
+        for (u32 i = 0; i < n; ++i) vectors[(size_t)j * n + i] = flip ? -v[(size_t)i * n + j] : v[(size_t)i * n + j];
+    }
+    return MG_OK;
+}
+} // namespace
+
+MG_EXPORT int mg_pca_load_tri_f32_device(mg_ctx *c, uint32_t n, const void *d_tri)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_pca_load(c, n, d_tri));
+    return pca_load_device<float>(c, n, d_tri, 1);
+}
+MG_EXPORT int mg_pca_load_f64_device(mg_ctx *c, uint32_t n, const void *d_full)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_pca_load(c, n, d_full));
+    return pca_load_device<double>(c, n, d_full, 0);
+}
+MG_EXPORT int mg_pca_load_tri_f32(mg_ctx *c, uint32_t n, const float *tri)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    return pca_load_host<float>(c, n, tri, 1);
+}
+MG_EXPORT int mg_pca_load_f64(mg_ctx *c, uint32_t n, const double *full)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    return pca_load_host<double>(c, n, full, 0);
+}
+MG_EXPORT int mg_pca_end(mg_ctx *c)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    pca_drop(c);
+    return MG_OK;
+}
+
+// The solve: products, orthonormalisations and, every PCA_CHECK_EVERY products (and at the last one allowed), a Rayleigh-Ritz step with the
+// residual test.  A Rayleigh-Ritz step waits twice -- for H on its way to the host's Jacobi and for the residual norms -- so the call
+// returns with everything done; what it put on the stream last are the copies into the outputs.
+MG_EXPORT int mg_pca_solve_device(mg_ctx *c, uint32_t k, double tol, uint32_t max_iters, void *d_values_out, void *d_vectors_out, void *d_resid_out, void *d_scale_out,
+                                  void *d_info_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_pca_solve(c, k, tol, max_iters, d_values_out, d_vectors_out, d_resid_out, d_scale_out, d_info_out));
+    TRY(pca_check_finite(c, "mg_pca_solve"));
+    const u32 n = c->pca_n, np = pca_np(n), m = pca_block(n, k);
+    c->pca_ms[0] = c->pca_ms[1] = c->pca_ms[2] = c->pca_ms[3] = 0.f;
+    c->pca_timed = false;
+    c->pca_ev_used = 0;
+    TRY(pca_tick(c, PCA_PH_OTHER));
+    std::vector<double> values(k), norms(k), resid(k);
+    double scale = 1.0;
+    u32 products = 0;
+    if (m == n) {
+        std::vector<double> vectors((size_t)k * n);
+        TRY(pca_solve_small(c, k, values.data(), vectors.data(), norms.data(), &scale));
+        HIP_TRY(c, hipMemcpyAsync(d_vectors_out, vectors.data(), 8 * (size_t)k * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else {
+        const u64 blk = (u64)np * m, mm = (u64)m * m;
+        u32 chunk = 0;
+        const u32 splits = pca_splits(np, &chunk), red = pca_red_blocks(np);
+        const u64 doubles = 4 * blk + (splits > 1 ? splits * blk : 0) + red * mm + 2 * mm + 2 * m;
+        void *base;
+        TRY(scratch(c, c->pca_work, 8 * doubles + 4 * m, &base));
+        PcaWork wk;
+        double *p = (double *)base;
+        for (double *&b : wk.blk) b = p, p += blk;
+        wk.parts = p, p += splits > 1 ? splits * blk : 0;
+        wk.gparts = p, p += red * mm;
+        wk.w = p, p += mm;
+        wk.s = p, p += mm;
+        wk.theta = p, p += m;
+        wk.norm = p, p += m;
+        wk.flags = (u32 *)p;
+        double *q = wk.blk[0], *y = wk.blk[1], *t1 = wk.blk[2], *t2 = wk.blk[3];
+        u64 salt = 0;
+        hipLaunchKernelGGL(pca_fill_kernel, dim3((unsigned)((blk + PCA_TPB - 1) / PCA_TPB)), dim3(PCA_TPB), 0, c->stream, y, n, np, m, salt++, (const u32 *)nullptr);
+        TRY(pca_orthonormalise(c, wk, y, t1, q, n, np, m, salt++));
+        TRY(pca_tick(c, PCA_PH_ORTH));
+        std::vector<double> h(mm), theta(m), s(mm), all_norms(m);
+        for (;;) {
+            TRY(pca_launch_product(c, wk, q, y, np, m));
+            ++products;
+            TRY(pca_tick(c, PCA_PH_PRODUCT));
+            if (products % PCA_CHECK_EVERY == 0 || products == max_iters) {
+                TRY(pca_launch_gram(c, wk, q, y, np, m));
+                HIP_TRY(c, hipMemcpyAsync(h.data(), wk.w, 8 * mm, hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                for (u32 i = 0; i < m; ++i) // H = Q^T G Q is symmetric up to rounding: the small solver gets the mean of the two halves
+                    for (u32 j = i + 1; j < m; ++j) h[(size_t)i * m + j] = 0.5 * (h[(size_t)i * m + j] + h[(size_t)j * m + i]);
+                if (pca_jacobi(m, h.data(), theta.data(), s.data()) < 0) return fail(c, MG_ERR_LIMIT, "mg_pca_solve: the small eigenproblem did not settle in 64 sweeps");
+                HIP_TRY(c, hipMemcpyAsync(wk.s, s.data(), 8 * mm, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(wk.theta, theta.data(), 8 * (size_t)m, hipMemcpyHostToDevice, c->stream));
+                TRY(pca_launch_update(c, q, wk.s, np, m, t1));
+                TRY(pca_launch_update(c, y, wk.s, np, m, t2));
+                hipLaunchKernelGGL(pca_resid_kernel, dim3(m), dim3(PCA_TPB), 0, c->stream, (const double *)t1, (const double *)t2, (const double *)wk.theta, np, m, wk.norm);
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipMemcpyAsync(all_norms.data(), wk.norm, 8 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+                TRY(pca_tick(c, PCA_PH_RITZ));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+                TRY(pca_flush(c));
+                std::swap(q, t1);
+                std::swap(y, t2);
+                double big = 0.0;
+                for (u32 j = 0; j < m; ++j) big = std::fabs(theta[j]) > big ? std::fabs(theta[j]) : big;
+                scale = big > 0.0 ? big : 1.0;
+                u32 done = 0;
+                for (u32 j = 0; j < k; ++j) done += all_norms[j] / scale <= tol;
+                if (done == k || products == max_iters) break;
+            }
+            TRY(pca_orthonormalise(c, wk, y, t1, q, n, np, m, salt++));
+            TRY(pca_tick(c, PCA_PH_ORTH));
+        }
+        for (u32 j = 0; j < k; ++j) values[j] = theta[j], norms[j] = all_norms[j];
+        hipLaunchKernelGGL(pca_emit_kernel, dim3(k), dim3(PCA_TPB), 0, c->stream, (const double *)q, n, m, (double *)d_vectors_out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    u32 info[3] = {products, 0, m};
+    for (u32 j = 0; j < k; ++j) {
+        resid[j] = norms[j] / scale;
+        info[1] += resid[j] <= tol;
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_values_out, values.data(), 8 * (size_t)k, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_resid_out, resid.data(), 8 * (size_t)k, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_scale_out, &scale, 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_info_out, info, sizeof info, hipMemcpyHostToDevice, c->stream));
+    TRY(pca_tick(c, PCA_PH_OTHER));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    TRY(pca_flush(c));
+    c->pca_timed = true;
+    return MG_OK;
+}
+
+MG_EXPORT int mg_pca_solve(mg_ctx *c, uint32_t k, double tol, uint32_t max_iters, double *values_out, double *vectors_out, double *resid_out, double *scale_out,
+                           uint32_t *info_out)
+{
+    const DeviceGuard on_device(c, KEEP);
+    if (!c) return MG_ERR_ARG;
+    TRY(check_pca_solve(c, k, tol, max_iters, values_out, vectors_out, resid_out, scale_out, info_out));
+    const size_t n = c->pca_n, small = 8 * (2 * (size_t)k + 1) + 16;
+    void *d_vec, *d_small;
+    TRY(scratch(c, c->pca_io[0], 8 * k * n, &d_vec));
+    TRY(scratch(c, c->pca_io[1], small, &d_small));
+    double *d_values = (double *)d_small, *d_resid = d_values + k, *d_scale = d_resid + k;
+    TRY(mg_pca_solve_device(c, k, tol, max_iters, d_values, d_vec, d_resid, d_scale, d_scale + 1));
+    HIP_TRY(c, hipMemcpyAsync(vectors_out, d_vec, 8 * k * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(values_out, d_values, 8 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(resid_out, d_resid, 8 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scale_out, d_scale, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(info_out, d_scale + 1, 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MG_OK;
+}
+
+// device milliseconds of the most recent solve: products, orthonormalisation, Rayleigh-Ritz (the host's part of it included: the device
+// waits for the small solver), total
+MG_EXPORT int mg_pca_stats(mg_ctx *c, float *ms_out)
+{
+    const DeviceGuard on_device(c, LAZY);
+    if (!c || !ms_out) return MG_ERR_ARG;
+    for (int i = 0; i < 4; ++i) ms_out[i] = 0.f; // (also where it fails)
+    if (!c->pca_timed) return fail(c, MG_ERR_STATE, "no mg_pca_solve yet");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4; ++i) ms_out[i] = c->pca_ms[i];
+    return MG_OK;
 }
 
 // ---- allele priors re-estimated from the planes of a batch (cohort_prior_kernels.h) ------------------------------------------------------

@@ -34,6 +34,7 @@
 #include "usage.hpp"
 #include "cohort_out.hpp"
 #include "call_worker.hpp"
+#include "pca.hpp"
 
 using namespace malva;
 
@@ -1432,6 +1433,58 @@ int dump_main(const Options &o)
     return 0;
 }
 
+// ---- pca: the principal components of a GRM that `call --cohort --grm` wrote (pca.hpp; mg_pca_* in include/malva_hip.h) -----------------
+// Its own parser and usage text; no index and no panel: the context is the smallest mg_create makes.
+int pca_main(int argc, char **argv)
+{
+    PcaOptions o;
+    const PcaParsed parsed = pca_parse(argc, argv, o, std::cerr);
+    if (parsed == PcaParsed::help) std::cout << PCA_USAGE;
+    if (parsed != PcaParsed::ok) return parsed == PcaParsed::help ? EXIT_SUCCESS : EXIT_FAILURE;
+    try {
+        PcaInput in;
+        {
+            Timed t("pca: read");
+            in = pca_read(o.grm);
+        }
+        PcaResult r;
+        r.n = (uint32_t)in.names.size();
+        r.k = o.pcs;
+        r.tol = o.tol;
+        if (r.k > r.n) {
+            std::cerr << "[malva-geno] --pcs " << o.pcs << " lowered to the " << r.n << " sample(s) of " << o.grm << std::endl;
+            r.k = r.n;
+        }
+        Device dev;
+        if (mg_create(&dev.ctx, o.device, 1, 1, 1) != MG_OK) throw std::runtime_error("no usable MI355X/HIP device " + std::to_string(o.device) + "; this build has no CPU path");
+        {
+            Timed t("pca: load");
+            dev.check(in.packed ? mg_pca_load_tri_f32(dev.ctx, r.n, in.tri.data()) : mg_pca_load_f64(dev.ctx, r.n, in.full.data()), "mg_pca_load");
+        }
+        std::vector<float>().swap(in.tri);
+        std::vector<double>().swap(in.full);
+        r.values.resize(r.k), r.resid.resize(r.k), r.vectors.resize((size_t)r.k * r.n);
+        {
+            Timed t("pca: solve");
+            dev.check(mg_pca_solve(dev.ctx, r.k, o.tol, o.max_iters, r.values.data(), r.vectors.data(), r.resid.data(), &r.scale, r.info), "mg_pca_solve");
+        }
+        dev.check(mg_pca_stats(dev.ctx, r.ms), "mg_pca_stats");
+        dev.check(mg_pca_end(dev.ctx), "mg_pca_end");
+        pca_write(o.out, r, in.names, in.trace);
+        const uint32_t first = pca_first_unconverged(r);
+        std::cerr << "[malva-geno] pca: " << r.k << " component(s) of " << r.n << " sample(s), " << r.info[0] << " product(s), block of " << r.info[2] << std::endl;
+        if (first < r.k) {
+            std::cerr << "malva : pca: component " << first + 1 << " is not converged after " << r.info[0] << " product(s) (residual " << r.resid[first] << ", --tol " << o.tol
+                      << "); " << r.info[1] << " of " << r.k << " are" << std::endl;
+            return 2;
+        }
+        return EXIT_SUCCESS;
+    } catch (const std::exception &e) {
+        std::cerr << "malva : " << e.what() << std::endl;
+        return EXIT_FAILURE;
+    }
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -1441,6 +1494,7 @@ int main(int argc, char **argv)
         return 1;
     }
     const std::string cmd = argv[1];
+    if (cmd == "pca") return pca_main(argc - 1, argv + 1); // (before parse_arguments: OPTIONS and USAGE are index's and call's)
     int (*const run)(const Options &) = cmd == "index-convert"            ? convert_main
                                         : cmd.compare(0, 5, "index") == 0 ? index_main
                                         : cmd.compare(0, 4, "call") == 0  ? call_main
